@@ -304,6 +304,26 @@ def progress(msg):
         print("[bench %6.1fs] %s" % (time.time() - T_START, msg), file=sys.stderr, flush=True)
 
 
+DUMP_NAMES = ("start", "stop", "tlen", "in_ddict")     # the columns of Engine.trim_coords, what a caller of the step receives
+DUMP_MAX_READS = 1 << 20         # --dump-outputs: 5 float64 arrays of at most 2^20 reads = 40 MB
+DUMP_SEED = 20241015             # the sample of a larger job: the same reads in every run
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs DIR: what the last timed step returned -- per read start, stop, tlen (-1 = None) and in_ddict, over all ranks
+    in read order -- as DIR/<name>.npy in float64 (exact for these integers), beside read_index.npy naming the reads.  A job of
+    more than DUMP_MAX_READS reads is cut to a fixed seeded sample of them, so that two builds can be compared array for array."""
+    import numpy as np
+    rows = np.stack(out[0], axis=1) if isinstance(out[0], tuple) else np.concatenate(out)
+    n = rows.shape[0]
+    idx = np.arange(n) if n <= DUMP_MAX_READS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_READS, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "read_index.npy"), idx.astype(np.float64))
+    for j, name in enumerate(DUMP_NAMES):
+        np.save(os.path.join(dirname, name + ".npy"), rows[idx, j].astype(np.float64))
+    return {"dir": dirname, "reads": int(n), "reads_written": int(idx.size), "arrays": ["read_index"] + list(DUMP_NAMES), "dtype": "float64"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -351,8 +371,13 @@ def main():
     ap.add_argument("--files-leg", type=int, default=1,
                     help="N = 1, --rows lazy: after the timed steps the job's uc.txt, rep.fa and the winners' domtbl.txt are written once (what "
                          "ITSXPRESS_DOMTBL=winners hands the reference's own parsers), outside `value`: `winners_files` (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the per-read coordinates the last timed step returned to DIR/<name>.npy "
+                         "(float64; a fixed seeded sample of %d reads when the job has more)" % DUMP_MAX_READS)
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -560,6 +585,10 @@ def main():
     else:
         total_local = n_local
     st = eng.stats()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        progress("writing the last timed step's coordinates to %s" % args.dump_outputs)
+        dumped = dump_outputs(args.dump_outputs, out)
 
     # one more step with nothing beside the scan kernels (ITSX_MSV_OVERLAP=0: the next chunk's k_msv does not run beside the domain stage and
     # the bound pass), outside `value`: the kernels' ALONE times, which the roofline block uses when the timed steps' are stretched
@@ -883,6 +912,7 @@ def main():
                      "bwd_rows_per_s": rows / (kern["k_bwd_decode"] * 1e-3) if kern["k_bwd_decode"] > 0 else None,
                      "env_rows_per_s_x3_sweeps": 3 * st["env_rows"] / (kern["k_env_fwd+k_env_bwd+k_env_post"] * 1e-3) if kern["k_env_fwd+k_env_bwd+k_env_post"] > 0 else None,
                      "peak_nofma_tflops": VALU_NOFMA_TFLOPS},
+            "dump_outputs": dumped,
         }
         if args.cpu_sample != 0 and world == 1:          # the CPU baseline is a rank-0, N=1 leg only
             threads, cpu_limit = effective_cpus()        # usable CPUs, not the host's hardware threads
