@@ -263,7 +263,8 @@ int itsx_keyset_assign(itsx_keyset *k, const int64_t *tuples, int64_t n_unique, 
  * With S samples itsx_get_domz / itsx_set_domz move S * n_profiles counters ([sample][profile]).
  * itsx_select_sample: the file writers (itsx_write_uc / _rep_fasta / _domtbl) emit that sample only (cluster numbers
  * and the E-value columns as in a run of that sample alone); -1 = every sample.
- * Not batched: itsx_cluster at id < 1 (sequential per sample) and itsx_unique_keys (shard whole samples instead). */
+ * Greedy clustering at id < 1 is batched by its own call, itsx_cluster_samples (itsx_cluster keeps refusing S > 1).
+ * Not batched: itsx_unique_keys (shard whole samples instead). */
 int itsx_load_reads_files(itsx_ctx *ctx, const char *const *paths, int32_t n_paths, int64_t *n_reads_per_file);
 int itsx_set_samples(itsx_ctx *ctx, const int32_t *sample_of_read, int32_t n_samples);
 int itsx_num_samples(const itsx_ctx *ctx);
@@ -317,6 +318,14 @@ int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique);
 /* after itsx_cluster at id < 1: pct_id[n_reads] = identity of each member with its centroid (uc column 4; -1 for
  * centroids and dropped reads), order[n_order] = kept reads in processing order (the order of uc's S/H rows). */
 int itsx_get_cluster(const itsx_ctx *ctx, double *pct_id, int64_t *order, int64_t *n_order);
+/* a2 for every sample of a batch (itsx_set_samples): SeqSample.cluster (itsxpress/SeqSample.py:133-176), which the QIIME 2
+ * plugin runs once per sample at cluster_id < 1 (itsxpress/q2_itsxpress.py:287-290), in one call.  Each sample is clustered
+ * exactly as itsx_cluster clusters that sample's reads alone: label order inside the sample, --minseqlength 32, DUST,
+ * maxaccepts 1 / maxrejects 32, --iddef 2; a member's centroid, strand and pct_id are those of the solo run.  The samples'
+ * windows advance side by side (k_cluster.hip: segmented windows).  Fills the same arrays as itsx_cluster, and the per-unique
+ * sample that itsx_search keeps domZ by; itsx_get_cluster's order is the samples' processing orders, sample after sample.
+ * id == 1.0 is itsx_derep(ctx, strand_both, 32, ...) on the batch; with S == 1 this is itsx_cluster. */
+int itsx_cluster_samples(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique);
 /* Dedup.parse's matchdict (itsxpress/SeqSample.py:542-562) as arrays over reads:
  * rep_of[i] = read index of the cluster seed (first occurrence), -1 if the read was dropped;
  * strand[i] = +1 / -1 (uc column 5); uniq_of[i] = index into the unique list, -1 if dropped. */

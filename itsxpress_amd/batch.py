@@ -78,11 +78,36 @@ class SampleBatch:
             raise f
 
     def cluster(self, threads: Union[int, str], cluster_id: float = 0.995) -> None:
-        """cluster_id == 1.0 is dereplication (main.py:534-537).  Greedy clustering below 1.0 is sequential per sample
-        and is not batched: run `sobj.cluster(...)` per sample for that."""
+        """cluster_id == 1.0 is dereplication (main.py:534-537).  Greedy clustering below 1.0 is not run by this
+        method: `cluster_per_sample` clusters every sample of the batch as `sobj.cluster(...)` would."""
         if float(cluster_id) == 1.0:
             return self.deduplicate(threads=threads)
         raise EngineError(-5, "cluster_id < 1 is not batched across samples; call SeqSample.cluster per sample")
+
+    def cluster_per_sample(self, threads: Union[int, str], cluster_id: float = 0.995) -> None:
+        """`SeqSample.cluster(threads, cluster_id)` of every sample (SeqSample.py:133-176; the QIIME 2 plugin's per-sample
+        loop at cluster_id < 1, q2_itsxpress.py:287-290) in one engine call: each sample's uc.txt / rep.fa are
+        byte-identical to those of its own run (itsx_cluster_samples)."""
+        try:
+            eng = self.engine
+            self.counts = np.asarray(eng.load_reads_files([s.seq_file for s in self.samples]), np.int64)
+            self.first = np.concatenate([[0], np.cumsum(self.counts)[:-1]]).astype(np.int64)
+            n = eng.cluster_samples(float(cluster_id), strand_both=True)
+            for i, s in enumerate(self.samples):
+                d = self._dir(i)
+                s.uc_file = os.path.join(d, "uc.txt")
+                s.rep_file = os.path.join(d, "rep.fa")
+                eng.select_sample(i)
+                eng.write_uc(s.uc_file)
+                eng.write_rep_fasta(s.rep_file)
+            eng.select_sample(-1)
+            logging.info("itsx_hip batch cluster at %g: %d samples, %d reads -> %d clusters", float(cluster_id), len(self.samples), eng.n_reads, n)
+        except EngineError as e:
+            logging.exception("Could not perform clustering with the HIP engine: %s", e)
+            raise e
+        except FileNotFoundError as f:
+            logging.error("The HIP engine or its input was not found")
+            raise f
 
     # -- a4 for all samples ------------------------------------------------------------------
     def _search(self, hmmfile: str, threads: Union[int, str] = 1) -> None:

@@ -1383,27 +1383,31 @@ static void dust_host(const uint8_t *codes, int64_t L, std::vector<uint8_t> &mas
   }
 }
 
-// a2: greedy centroid clustering (k_cluster.hip explains the speculative windows)
-int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
+// a2: greedy centroid clustering (k_cluster.hip explains the speculative windows).  batched: every sample of the batch is
+// clustered as a run of that sample alone, the samples' windows advancing side by side as the segments of shared windows.
+static int cluster_run(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique, bool batched)
 {
-  CTXCHK(ctx);
-  if (!(id > 0.0 && id <= 1.0)) SET_ERR(ctx, ITSX_E_ARG, "cluster id must be in (0, 1]");
-  if (id == 1.0) return itsx_derep(ctx, strand_both, 32, n_unique);      // main.py:534-537 never clusters at 1.0
-  if (ctx->S > 1) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "greedy clustering (id < 1) is sequential per sample: run it one sample per call, not on a sample batch");
   HIPCHK(hipSetDevice(ctx->device));
   const int64_t n = ctx->N;
   const int minlen = 32;
+  const int32_t S = batched ? ctx->S : 1;
   StageTimer tm(ctx->st);
-  // processing order: abundance (all 1) descending, then label, then input position
+  // processing order: abundance (all 1) descending, then label, then input position -- inside each sample, the samples one
+  // after another; sample s owns processing positions and centroid columns [sstart[s], sstart[s + 1])
   std::vector<int32_t> ord; ord.reserve((size_t)n);
+  std::vector<int32_t> sstart((size_t)S + 1, 0);
   int Lmax = 1;
   for (int64_t r = 0; r < n; r++)                          // vsearch defaults: --minseqlength 32, --maxseqlength 50000
-    if (ctx->h_len[r] >= minlen && ctx->h_len[r] <= 50000) { ord.push_back((int32_t)r); Lmax = std::max(Lmax, (int)ctx->h_len[r]); }
-  if (!ctx->h_names.empty())
-    std::sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) {
-      const int c = ctx->h_names.cmp((size_t)a, (size_t)b);
-      return c < 0 || (c == 0 && a < b);
-    });
+    if (ctx->h_len[r] >= minlen && ctx->h_len[r] <= 50000) {
+      ord.push_back((int32_t)r); Lmax = std::max(Lmax, (int)ctx->h_len[r]);
+      sstart[batched ? (size_t)ctx->h_sample[(size_t)r] + 1 : 1]++;
+    }
+  for (int32_t s = 0; s < S; s++) sstart[(size_t)s + 1] += sstart[(size_t)s];
+  std::sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) {
+    if (batched && ctx->h_sample[(size_t)a] != ctx->h_sample[(size_t)b]) return ctx->h_sample[(size_t)a] < ctx->h_sample[(size_t)b];
+    const int c = ctx->h_names.empty() ? 0 : ctx->h_names.cmp((size_t)a, (size_t)b);
+    return c < 0 || (c == 0 && a < b);
+  });
   const int32_t nk = (int32_t)ord.size();
   int Bmax = 4096;                                          // k_cl_resolve keeps the window's flags in LDS
   if (const char *e = sw_get("ITSX_CL_WINDOW")) Bmax = std::min(4096, std::max(1, atoi(e)));
@@ -1418,9 +1422,9 @@ int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
 
   DBuf<int32_t> d_order, cent_len, cent_pos, cent_read, res_col, knk, state, rejects, acc_col, is_new, new_rank, scan_tmp, xlist, xn, hard, dbg;
   DBuf<int32_t> sel, selm, sel_short, wn, wcol, newq, rm, wout, work, xwork, work_n, replay, skipm, canon, ctab_val, need, awork, spairs;
-  DBuf<int32_t> cw_n, wsum, wscan, qi_cnt, qi_cur, qi_off, ncand, ntop, ovf, qi_hid, qi_nheavy;
+  DBuf<int32_t> cw_n, wsum, wscan, qi_cnt, qi_cur, qi_off, ncand, ntop, ovf, qi_hid, qi_nheavy, cent_q, segtab, qpos, qseg, newcol;
   DBuf<uint32_t> qi_bm;
-  DBuf<int64_t> cw_off, cw_base;
+  DBuf<int64_t> cw_off;
   DBuf<uint16_t> klist, cw_poolA, cw_poolB, qi_ent, cntx; DBuf<uint32_t> tq, minm;
   DBuf<unsigned long long> ctab_key, n_skipped, pre_stats, cand, tkey;
   DBuf<int8_t> res_strand; DBuf<double> res_id, acc_id, d_pct, selpid, wpid, xpid;
@@ -1429,8 +1433,7 @@ int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
   HIPCHK(upload(d_order, ord, ctx->st));
   const size_t ccap = (size_t)nk + 2048;
   HIPCHK(cent_len.alloc(ccap)); HIPCHK(cent_pos.alloc(ccap)); HIPCHK(cent_read.alloc(ccap));
-  HIPCHK(cw_n.alloc(ccap)); HIPCHK(cw_off.alloc(ccap + 1)); HIPCHK(cw_base.alloc(2));
-  HIPCHK(hipMemsetAsync(cw_off.p, 0, sizeof(int64_t), ctx->st));                       // the first column starts at 0
+  HIPCHK(cw_n.alloc(ccap)); HIPCHK(cw_off.alloc(ccap + 1)); HIPCHK(cent_q.alloc(ccap));
   HIPCHK(res_col.alloc((size_t)nk + 1)); HIPCHK(res_strand.alloc((size_t)nk + 1)); HIPCHK(res_id.alloc((size_t)nk + 1));
   const size_t nqs = 2 * (size_t)Bmax;
   HIPCHK(klist.alloc(nqs * kcap)); HIPCHK(knk.alloc(nqs)); HIPCHK(state.alloc(nqs)); HIPCHK(rejects.alloc(nqs));
@@ -1440,10 +1443,12 @@ int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
   HIPCHK(xlist.alloc(nqs * 32)); HIPCHK(xn.alloc(nqs)); HIPCHK(hard.alloc(nqs)); HIPCHK(xkey.alloc(nqs * 32)); HIPCHK(xpid.alloc(nqs * 32));
   HIPCHK(is_new.alloc((size_t)Bmax + 1)); HIPCHK(new_rank.alloc((size_t)Bmax + 1)); HIPCHK(newq.alloc((size_t)Bmax + 1)); HIPCHK(rm.alloc((size_t)Bmax + 1));
   HIPCHK(wsum.alloc((size_t)Bmax + 1)); HIPCHK(wscan.alloc((size_t)Bmax + 1));
-  HIPCHK(wout.alloc(4)); HIPCHK(dbg.alloc(4)); HIPCHK(work.alloc(nqs * 32)); HIPCHK(xwork.alloc(nqs * 32)); HIPCHK(work_n.alloc(8)); HIPCHK(awork.alloc(2 * nqs * 32)); HIPCHK(spairs.alloc(4 * nqs * 32)); HIPCHK(replay.alloc((size_t)Bmax + 1)); HIPCHK(skipm.alloc((size_t)Bmax + 1)); HIPCHK(canon.alloc((size_t)Bmax + 1)); HIPCHK(need.alloc(2 * nqs * 32)); HIPCHK(n_skipped.alloc(1)); HIPCHK(pre_stats.alloc(16)); HIPCHK(hipMemsetAsync(pre_stats.p, 0, 16 * sizeof(unsigned long long), ctx->st));
+  HIPCHK(segtab.alloc(5 * ((size_t)Bmax + 1))); HIPCHK(qpos.alloc((size_t)Bmax)); HIPCHK(qseg.alloc((size_t)Bmax)); HIPCHK(newcol.alloc((size_t)Bmax));
+  HIPCHK(wout.alloc(3 * (size_t)Bmax + 1)); HIPCHK(dbg.alloc(4)); HIPCHK(work.alloc(nqs * 32)); HIPCHK(xwork.alloc(nqs * 32)); HIPCHK(work_n.alloc(8)); HIPCHK(awork.alloc(2 * nqs * 32)); HIPCHK(spairs.alloc(4 * nqs * 32)); HIPCHK(replay.alloc((size_t)Bmax + 1)); HIPCHK(skipm.alloc((size_t)Bmax + 1)); HIPCHK(canon.alloc((size_t)Bmax + 1)); HIPCHK(need.alloc(2 * nqs * 32)); HIPCHK(n_skipped.alloc(1)); HIPCHK(pre_stats.alloc(16)); HIPCHK(hipMemsetAsync(pre_stats.p, 0, 16 * sizeof(unsigned long long), ctx->st));
   HIPCHK(hipMemsetAsync(n_skipped.p, 0, sizeof(unsigned long long), ctx->st)); HIPCHK(ctab_key.alloc(16384)); HIPCHK(ctab_val.alloc(16384));
   HIPCHK(ctx->w_hf.alloc((size_t)n + 1)); HIPCHK(ctx->w_hr.alloc((size_t)n + 1));
-  if (n > 0) launch_hash_reads(ctx->rd, 0, 0, ctx->w_hf.p, ctx->w_hr.p, ctx->st);      // identical reads of a window share one search
+  // identical reads of a window share one search (a batch: identical reads of one sample -- the hash carries the sample)
+  if (n > 0) launch_hash_reads(ctx->rd, 0, 0, ctx->w_hf.p, ctx->w_hr.p, ctx->st, batched ? ctx->dev_sample() : nullptr);
   // vsearch's default --qmask dust / --dbmask dust: the DUST soft mask of every read (queries and centroids alike), once
   DBuf<uint32_t> dmask;
   const bool use_dust = qmask_dust();
@@ -1472,7 +1477,8 @@ int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
   a.rd = ctx->rd; a.order = d_order.p; a.strand_both = strand_both ? 1 : 0; a.dmask = (use_dust && n > 0) ? dmask.p : nullptr;
   a.cent_len = cent_len.p; a.cent_pos = cent_pos.p; a.cent_read = cent_read.p;
   a.klist = klist.p; a.kcap = kcap; a.nk = knk.p;
-  a.cw_off = cw_off.p; a.cw_n = cw_n.p; a.cw_base = cw_base.p; a.wsum = wsum.p; a.wscan = wscan.p;
+  a.cw_off = cw_off.p; a.cw_n = cw_n.p; a.wsum = wsum.p; a.wscan = wscan.p;
+  a.cent_q = cent_q.p; a.qpos = qpos.p; a.qseg = qseg.p; a.newcol = newcol.p;
   a.qi_cnt = qi_cnt.p; a.qi_cur = qi_cur.p; a.qi_off = qi_off.p; a.qi_ent = qi_ent.p;
   a.qi_hid = qi_hid.p; a.qi_nheavy = qi_nheavy.p; a.qi_bm = qi_bm.p; a.hcap = hcap;
   a.heavy_min = CL_HEAVY;                                    // ITSX_CL_HEAVY_MIN: strands that must hold a word before it gets a bitmap (tuning; results do not depend on it)
@@ -1489,12 +1495,34 @@ int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
   a.scratch = scratch.p; a.scratch_pitch = scratch_pitch;
   a.thr = 100.0 * id; a.n_align = n_align.p;
 
-  int32_t f = 0, C = 0, ncent = 0;
-  int B = std::min(Bmax, 256);
+  // per sample: queries done f, centroid columns C, adaptive segment size B (start 256, double after an uncut segment,
+  // max(64, 2 cut) after a cut).  A window takes a segment of every unfinished sample in sample order until it holds Bmax queries.
+  std::vector<int32_t> sf((size_t)S, 0), sC((size_t)S, 0), sB((size_t)S, std::min(Bmax, 256));
+  std::vector<int32_t> tab, wsmp, wo;                        // the window's segment table (5 rows of G + 1), its samples, the outcome
+  int32_t first = 0, ncent = 0;
   int64_t windows = 0, cuts = 0, regrown = 0, stream_launches = 0;
   const bool debug = sw_get("ITSX_CL_DEBUG") != nullptr;
-  while (f < nk) {
-    const int nq = std::min<int32_t>(B, nk - f);
+  for (;;) {
+    while (first < S && sf[(size_t)first] >= sstart[(size_t)first + 1] - sstart[(size_t)first]) first++;
+    if (first >= S) break;
+    int nq = 0, Ctot = 0;
+    wsmp.clear();
+    std::vector<int32_t> q0, cb, base, cs, pos0;
+    for (int32_t s = first; s < S && nq < Bmax; s++) {
+      const int32_t rem = sstart[(size_t)s + 1] - sstart[(size_t)s] - sf[(size_t)s];
+      if (rem <= 0) continue;
+      const int32_t take = std::min(std::min(sB[(size_t)s], rem), Bmax - nq);
+      wsmp.push_back(s); q0.push_back(nq); cb.push_back(Ctot); base.push_back(sstart[(size_t)s]); cs.push_back(sC[(size_t)s]);
+      pos0.push_back(sstart[(size_t)s] + sf[(size_t)s]);
+      nq += take; Ctot += sC[(size_t)s];
+    }
+    const int32_t G = (int32_t)wsmp.size();
+    q0.push_back(nq); cb.push_back(Ctot); base.push_back(0); cs.push_back(0); pos0.push_back(0);
+    tab.clear();
+    for (const std::vector<int32_t> *v : {&q0, &cb, &base, &cs, &pos0}) tab.insert(tab.end(), v->begin(), v->end());
+    HIPCHK(hipMemcpyAsync(segtab.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->st));
+    a.G = G; a.seg = G > 1 ? 1 : 0;
+    a.sg_q0 = segtab.p; a.sg_cb = segtab.p + (G + 1); a.sg_base = segtab.p + 2 * (G + 1); a.sg_C = segtab.p + 3 * (G + 1); a.sg_pos0 = segtab.p + 4 * (G + 1);
     if (pool_used + (int64_t)nq * kcap > pool_cap) {          // the window's would-be centroids could overrun the word pool: grow it
       int64_t ncap = pool_cap;
       while (pool_used + (int64_t)nq * kcap > ncap) ncap *= 2;
@@ -1504,15 +1532,16 @@ int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
       std::swap(cw_pool, cw_other); cw_other->release();
       pool_cap = ncap;
     }
-    a.f = f; a.nq = nq; a.C = C; a.cw_pool = cw_pool->p; a.cand = cand.p; a.ccap = cand_cap; a.xpitch = nq;
+    a.nq = nq; a.pool0 = pool_used; a.cw_pool = cw_pool->p; a.cand = cand.p; a.ccap = cand_cap; a.xpitch = nq;
+    launch_cl_segs(a, ctx->st);
     launch_cl_kmers(a, ctx->st);
     // every centroid streams past the window's query index; a strand keeps the candidates that can still be among its 32 best
     launch_cl_qindex(a, scan_tmp.p, ctx->st);
-    for (int c0 = 0, step = 2048; c0 < C; step = std::min(step * 2, 1 << 20)) {
-      const int c1 = std::min(C, c0 + step);
+    for (int c0 = 0, step = 2048; c0 < Ctot; step = std::min(step * 2, 1 << 20)) {
+      const int c1 = std::min(Ctot, c0 + step);
       launch_cl_stream(a, c0, c1, 1, ctx->st);
       stream_launches++;
-      if (c1 < C) launch_cl_topk(a, 0, ctx->st);              // cut the lists back to their 32 best, raise the thresholds
+      if (c1 < Ctot) launch_cl_topk(a, 0, ctx->st);              // cut the lists back to their 32 best, raise the thresholds
       c0 = c1;
     }
     launch_cl_topk(a, 1, ctx->st);
@@ -1522,7 +1551,7 @@ int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
       HIPCHK(hipMemcpyAsync(&early, ovf.p, sizeof(early), hipMemcpyDeviceToHost, ctx->st));
       HIPCHK(hipStreamSynchronize(ctx->st));
       if (early) {
-        if ((int64_t)cand_cap >= (int64_t)C) SET_ERR(ctx, ITSX_E_DEVICE, "clustering candidate lists overflow although they hold every centroid");
+        if ((int64_t)cand_cap >= (int64_t)Ctot) SET_ERR(ctx, ITSX_E_DEVICE, "clustering candidate lists overflow although they hold every centroid");
         cand_cap *= 4;
         HIPCHK(cand.alloc(nqs * (size_t)cand_cap));
         regrown++;
@@ -1530,33 +1559,31 @@ int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
       }
     }
     launch_cl_init(a, ctx->st);
-    if (C > 0) launch_cl_walk(a, rows_per_lane, ctx->st);
+    if (Ctot > 0) launch_cl_walk(a, rows_per_lane, ctx->st);
     launch_cl_outcome(a, ctx->st);
     launch_exclusive_scan(is_new.p, new_rank.p, nq + 1, scan_tmp.p, ctx->st);
     launch_cl_wsum(a, ctx->st);
     launch_exclusive_scan(wsum.p, wscan.p, nq + 1, scan_tmp.p, ctx->st);
     launch_cl_columns(a, 0, ctx->st);
     HIPCHK(hipMemsetAsync(cntx.p, 0, (size_t)2 * nq * nq * sizeof(uint16_t), ctx->st));
-    launch_cl_stream(a, C, C + nq, 2, ctx->st);               // the window's speculative centroids against the window's strands
+    launch_cl_stream(a, 0, nq, 2, ctx->st);                   // the window's speculative centroids against their segments' strands
     launch_cl_validate(a, rows_per_lane, ctx->st);
     launch_cl_columns(a, 1, ctx->st);                         // roll back the speculative centroids that did not survive
-    int32_t wo[3] = {0, 0, 0}, overflow = 0;
-    int64_t cwb[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(wo, wout.p, sizeof(wo), hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(cwb, cw_base.p, sizeof(cwb), hipMemcpyDeviceToHost, ctx->st));
+    int32_t overflow = 0;
+    wo.assign(3 * (size_t)G + 1, 0);
+    HIPCHK(hipMemcpyAsync(wo.data(), wout.p, wo.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipMemcpyAsync(&overflow, ovf.p, sizeof(overflow), hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
     HIPCHK(hipGetLastError());                              // a kernel that failed to launch must not pass silently
     if (overflow) {
       // a strand met more candidates at (or above) its threshold than its list holds -- long runs of equal counts: nothing of
       // this window is kept, the lists grow and the window is searched again (the centroid set has not changed yet)
-      if ((int64_t)cand_cap >= (int64_t)C) SET_ERR(ctx, ITSX_E_DEVICE, "clustering candidate lists overflow although they hold every centroid");
+      if ((int64_t)cand_cap >= (int64_t)Ctot) SET_ERR(ctx, ITSX_E_DEVICE, "clustering candidate lists overflow although they hold every centroid");
       cand_cap *= 4;
       HIPCHK(cand.alloc(nqs * (size_t)cand_cap));
       regrown++;
       continue;
     }
-    const int32_t cut = wo[0];
     if (debug) {
       int32_t d[4] = {0, 0, 0, 0};
       (void)hipMemcpy(d, dbg.p, sizeof(d), hipMemcpyDeviceToHost);
@@ -1566,13 +1593,19 @@ int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
       (void)hipMemcpy(hc.data(), ncand.p, hc.size() * 4, hipMemcpyDeviceToHost);
       long sc[4] = {0, 0, 0, 0}, sw[4] = {0, 0, 0, 0}, acc1 = 0, ncs = 0, ncm = 0;
       for (size_t q = 0; q < hs.size(); q++) { sc[hs[q] & 3]++; sw[hs[q] & 3] += hw[q]; acc1 += hs[q] == 1 && hw[q] == 1; ncs += hc[q]; ncm = std::max<long>(ncm, hc[q]); }
-      fprintf(stderr, "[cluster] f=%d nq=%d C=%d cut=%d cols=%d new=%d | hard=%d budget=%d joined_new=%d xaligns=%d | accept %ld (first try %ld, walk %ld) rej32 %ld exhausted %ld (walk %ld) | appended %ld (max %ld per strand)\n",
-              f, nq, C, cut, wo[1], wo[2], d[0], d[1], d[2], d[3], sc[1], acc1, sw[1], sc[2], sc[3], sw[3], ncs, ncm);
+      fprintf(stderr, "[cluster] G=%d f=%d nq=%d C=%d cut=%d cols=%d new=%d | hard=%d budget=%d joined_new=%d xaligns=%d | accept %ld (first try %ld, walk %ld) rej32 %ld exhausted %ld (walk %ld) | appended %ld (max %ld per strand)\n",
+              G, sf[(size_t)wsmp[0]], nq, Ctot, wo[0] - q0[0], wo[G], wo[2 * G], d[0], d[1], d[2], d[3], sc[1], acc1, sw[1], sc[2], sc[3], sw[3], ncs, ncm);
     }
-    if (cut < 1 || cut > nq) SET_ERR(ctx, ITSX_E_DEVICE, "clustering window validation returned an impossible cut");
-    C += wo[1]; ncent += wo[2]; f += cut; windows++; cuts += cut < nq;
-    pool_used = cwb[1];
-    B = cut == nq ? std::min(Bmax, std::max(B, nq) * 2) : std::min(Bmax, std::max(64, 2 * cut));
+    bool any_cut = false;
+    for (int32_t g = 0; g < G; g++) {
+      const size_t s = (size_t)wsmp[(size_t)g];
+      const int32_t sq = q0[(size_t)g + 1] - q0[(size_t)g], cut = wo[(size_t)g] - q0[(size_t)g];
+      if (cut < 1 || cut > sq) SET_ERR(ctx, ITSX_E_DEVICE, "clustering window validation returned an impossible cut");
+      sC[s] += wo[(size_t)G + g]; ncent += wo[2 * (size_t)G + g]; sf[s] += cut; any_cut |= cut < sq;
+      sB[s] = cut == sq ? std::min(Bmax, std::max(sB[s], sq) * 2) : std::min(Bmax, std::max(64, 2 * cut));
+    }
+    windows++; cuts += any_cut;
+    pool_used += wo[3 * (size_t)G];                           // (the words of the last segment's rolled-back tail are taken again)
   }
   if (debug) fprintf(stderr, "[cluster] %lld windows, %lld stream launches, %lld regrown candidate lists, word pool %.1f MB\n", (long long)windows, (long long)stream_launches, (long long)regrown, pool_used * 2.0 / 1e6);
 
@@ -1608,6 +1641,22 @@ int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
   if (ctx->U != ncent) SET_ERR(ctx, ITSX_E_DEVICE, "clustering bookkeeping mismatch (centroids " + std::to_string(ncent) + " vs uniques " + std::to_string(ctx->U) + ")");
   if (n_unique) *n_unique = ctx->U;
   return ITSX_OK;
+}
+int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
+{
+  CTXCHK(ctx);
+  if (!(id > 0.0 && id <= 1.0)) SET_ERR(ctx, ITSX_E_ARG, "cluster id must be in (0, 1]");
+  if (id == 1.0) return itsx_derep(ctx, strand_both, 32, n_unique);      // main.py:534-537 never clusters at 1.0
+  if (ctx->S > 1) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "greedy clustering (id < 1) is sequential per sample: run it one sample per call, not on a sample batch");
+  return cluster_run(ctx, id, strand_both, n_unique, false);
+}
+int itsx_cluster_samples(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
+{
+  CTXCHK(ctx);
+  if (!(id > 0.0 && id <= 1.0)) SET_ERR(ctx, ITSX_E_ARG, "cluster id must be in (0, 1]");
+  if (id == 1.0) return itsx_derep(ctx, strand_both, 32, n_unique);      // as itsx_cluster: a batched derep keeps every sample apart
+  if (ctx->S <= 1) return itsx_cluster(ctx, id, strand_both, n_unique);
+  return cluster_run(ctx, id, strand_both, n_unique, true);
 }
 
 int itsx_get_cluster(const itsx_ctx *ctx, double *pct_id, int64_t *order, int64_t *n_order)
@@ -4319,7 +4368,7 @@ static const std::vector<int32_t> &cluster_order(const itsx_ctx *cctx)
   ord.reserve((size_t)ctx->U);
   const int32_t sel = ctx->S > 1 ? ctx->sel_sample : -1;      // writers restricted to one sample of a batch
   if (ctx->clustered) {                  // --cluster_size: clusters are numbered as their centroids were created
-    for (int32_t r : ctx->h_order) if (ctx->h_rep_of[r] == r) ord.push_back(ctx->h_uniq_of[r]);
+    for (int32_t r : ctx->h_order) if (ctx->h_rep_of[r] == r && (sel < 0 || ctx->h_sample[(size_t)r] == sel)) ord.push_back(ctx->h_uniq_of[r]);
     ctx->order_cache_ok = true;
     return ord;
   }
@@ -4359,7 +4408,9 @@ int itsx_write_uc(const itsx_ctx *ctx, const char *path)
     // vsearch --cluster_size writes the S and H rows as the queries are processed, then one C row per cluster
     std::vector<int32_t> cno((size_t)ctx->U);
     for (size_t c = 0; c < ord.size(); c++) cno[ord[c]] = (int32_t)c;
+    const int32_t sel = ctx->S > 1 ? ctx->sel_sample : -1;    // (a batch clustered by itsx_cluster_samples: one sample's rows)
     for (int32_t r : ctx->h_order) {
+      if (sel >= 0 && ctx->h_sample[(size_t)r] != sel) continue;
       const int32_t u = ctx->h_uniq_of[r];
       if (ctx->h_rep_of[r] == r) fprintf(f, "S\t%d\t%d\t*\t*\t*\t*\t*\t%s\t*\n", cno[u], ctx->h_len[r], read_name(ctx, r).c_str());
       else fprintf(f, "H\t%d\t%d\t%.1f\t%c\t0\t0\t*\t%s\t%s\n", cno[u], ctx->h_len[r], ctx->h_pct[r], ctx->h_strand[r] < 0 ? '-' : '+',

@@ -39,14 +39,24 @@ void launch_region_upos_follow(int64_t nr, const int32_t *rep_region, const int3
 // ---- k_cluster.hip (row a2: greedy centroid clustering, speculative windows)
 struct ClusterArgs {
   ReadsDev rd;
-  const int32_t *order;         // [nk] read index by processing position (label order)
-  int32_t f, nq;                // window = positions [f, f+nq)
+  const int32_t *order;         // [nk] read index by processing position (label order; a sample batch: the samples' orders one after another)
+  int32_t nq;                   // window queries
   int32_t strand_both;
   int32_t *cent_len, *cent_pos, *cent_read;   // per centroid column
-  int32_t C;                    // centroids at the window start
+  int32_t *cent_q;              // window query of each speculative column (k_cl_resolve)
+  // The window is made of SEGMENTS, one per sample it holds (a single sample: one segment): segment g is window queries
+  // [sg_q0[g], sg_q0[g + 1]) = processing positions sg_pos0[g] + ..., and its sample owns the centroid columns [sg_base[g],
+  // sg_base[g] + its kept reads), of which the first sg_C[g] exist at the window start.  Every (strand, centroid) relation stays
+  // inside one segment: a centroid's counts, candidates, entrants and cuts never reach another sample's strands.
+  int32_t G;                    // segments of this window
+  int32_t seg;                  // G > 1: k_cl_stream keeps each centroid's additions and candidates inside its own segment
+  const int32_t *sg_q0, *sg_cb, *sg_base, *sg_C, *sg_pos0;   // [G + 1]; sg_cb = prefix of sg_C (the mode-1 stream index)
+  int32_t *qpos, *qseg;         // [nq] processing position and segment of each window query (k_cl_segs)
+  int32_t *newcol;              // [nq] column of the window's j-th speculative centroid (mode 2 streams j = 0 .. n_new - 1)
+  int64_t pool0;                // where this window's words start in the pool
   uint16_t *klist; int32_t kcap; int32_t *nk;  // distinct words of each (query, strand): [2 nq][kcap], [2 nq]
   // the centroids' distinct forward words, column after column (append-only; a rolled-back column has cw_n = 0)
-  uint16_t *cw_pool; int64_t *cw_off; int32_t *cw_n; int64_t *cw_base;   // cw_base[0] = cw_off[C] of this window; cw_base[1] = end after validation
+  uint16_t *cw_pool; int64_t *cw_off; int32_t *cw_n;
   int32_t *wsum, *wscan;        // [nq+1] words of each would-be centroid, and their exclusive scan
   // the window's query index: word -> the (query strand) byte offsets 4 * qs that hold it, each list padded to 8 entries with the
   // dummy offset 4 * QS_MAX
@@ -69,7 +79,7 @@ struct ClusterArgs {
   int32_t *wn, *wcol; unsigned long long *wkey; double *wpid;                    // the recorded walk [2 nq][32]
   int32_t *res_col; int8_t *res_strand; double *res_id;   // outcome by processing position
   int32_t *is_new, *new_rank;   // [nq+1]
-  int32_t *newq, *rm;           // [nq] window index of each speculative centroid; columns to clear after validation
+  int32_t *newq, *rm;           // [nq] window query of the j-th speculative centroid; columns to clear after validation
   int32_t *xlist, *xn, *hard; unsigned long long *xkey; double *xpid;            // speculative centroids entering a walk [2 nq][32]
   int32_t *work, *xwork, *work_n;   // (query strand * 32 + slot) items for the two alignment kernels; work_n[6]: items of work / xwork, of awork's two halves, of spairs' two halves
   int32_t *spairs;                  // [2][need_pitch][2]: the score pass's list: two items of one strand (or one and -1) per entry
@@ -79,7 +89,7 @@ struct ClusterArgs {
   unsigned long long *ctab_key; int32_t *ctab_val; int32_t *canon;   // window-local table of identical reads; canon[nq]
   int32_t *replay;              // [nq] queries whose walk must be replayed by k_cl_resolve
   int32_t *skipm;               // [nq] minus-strand walk cut short because the plus strand holds a 100 % hit
-  int32_t *wout;                // [3] cut, columns consumed, true new centroids
+  int32_t *wout;                // [3][G] per segment: cut (window query), columns consumed, true new centroids
   int32_t *dbg;                 // [4] hard cuts, member->centroid cuts, centroid->member resolutions, validation alignments
   unsigned long long *scratch; int32_t scratch_pitch;     // alignment boundary rows [2 nq * 32][pitch][2]
   double thr;                   // 100 * id
@@ -92,9 +102,10 @@ struct ClusterArgs {
 };
 constexpr int CL_QS_MAX = 8192;  // query strands of one window (2 x the largest window)
 constexpr int CL_HEAVY = 128;    // a word held by at least this many strands of the window goes through its strand bitmap
+void launch_cl_segs(const ClusterArgs &a, hipStream_t st);
 void launch_cl_kmers(const ClusterArgs &a, hipStream_t st);
 void launch_cl_qindex(const ClusterArgs &a, int32_t *scan_tmp, hipStream_t st);
-void launch_cl_stream(const ClusterArgs &a, int c0, int c1, int mode, hipStream_t st);      // mode 1: the old centroids [c0, c1); mode 2: the window's speculative ones
+void launch_cl_stream(const ClusterArgs &a, int c0, int c1, int mode, hipStream_t st);      // mode 1: the old centroids [c0, c1) of the sg_cb index; mode 2: the window's speculative ones
 void launch_cl_topk(const ClusterArgs &a, int final, hipStream_t st);
 void launch_cl_init(const ClusterArgs &a, hipStream_t st);
 void launch_cl_walk(const ClusterArgs &a, int rows_per_lane, hipStream_t st);

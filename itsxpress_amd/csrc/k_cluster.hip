@@ -155,11 +155,20 @@ __device__ __forceinline__ bool same_read(const ReadsDev &rd, int64_t x, int64_t
   for (int i = 0; i < ne; i++) if (rd.exc[ex + i] != rd.exc[ey + i]) return false;
   return true;
 }
+// every window query's segment and processing position, from the window's segment table
+__global__ void k_cl_segs(ClusterArgs a)
+{
+  const int qi = blockIdx.x * blockDim.x + threadIdx.x;
+  if (qi >= a.nq) return;
+  int lo = 0, hi = a.G - 1;                                   // the last segment that starts at or before qi
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (a.sg_q0[mid] <= qi) lo = mid; else hi = mid - 1; }
+  a.qseg[qi] = lo; a.qpos[qi] = a.sg_pos0[lo] + qi - a.sg_q0[lo];
+}
 __global__ void k_cl_canon_insert(ClusterArgs a)
 {
   const int qi = blockIdx.x * blockDim.x + threadIdx.x;
   if (qi >= a.nq) return;
-  const u64 h = a.rhash[a.order[a.f + qi]] | 1ULL;
+  const u64 h = a.rhash[a.order[a.qpos[qi]]] | 1ULL;
   for (uint32_t slot = (uint32_t)(h >> 17) & (CTAB - 1);; slot = (slot + 1) & (CTAB - 1)) {
     const u64 prev = atomicCAS(&a.ctab_key[slot], 0ULL, h);
     if (prev == 0ULL || prev == h) { atomicMin(&a.ctab_val[slot], qi); break; }
@@ -169,12 +178,12 @@ __global__ void k_cl_canon_lookup(ClusterArgs a)
 {
   const int qi = blockIdx.x * blockDim.x + threadIdx.x;
   if (qi >= a.nq) return;
-  const int64_t r = a.order[a.f + qi];
+  const int64_t r = a.order[a.qpos[qi]];
   const u64 h = a.rhash[r] | 1ULL;
   uint32_t slot = (uint32_t)(h >> 17) & (CTAB - 1);
   while (a.ctab_key[slot] != h) slot = (slot + 1) & (CTAB - 1);
   const int c = a.ctab_val[slot];
-  a.canon[qi] = (c < qi && same_read(a.rd, r, a.order[a.f + c])) ? c : qi;
+  a.canon[qi] = (c < qi && a.qseg[c] == a.qseg[qi] && same_read(a.rd, r, a.order[a.qpos[c]])) ? c : qi;      // (the hashes carry the sample: this only guards a collision)
 }
 
 // ------------------------------------------------------------------ distinct 8-mers of each (query, strand)
@@ -187,7 +196,7 @@ __global__ __launch_bounds__(256) void k_cl_kmers(ClusterArgs a)
   const int qs = blockIdx.x, qi = qs >> 1, s = qs & 1;
   if (a.canon[qi] != qi) return;
   if (s && !a.strand_both) { if (tid == 0) a.nk[qs] = 0; return; }
-  const int64_t r = a.order[a.f + qi];
+  const int64_t r = a.order[a.qpos[qi]];
   const int L = a.rd.len[r];
   const uint32_t *w = a.rd.words + a.rd.woff[r];
   const int64_t eo = a.rd.excoff[r];
@@ -314,6 +323,17 @@ __device__ __forceinline__ void cl_add8(uint32_t *hist, uint4 v, uint32_t r)
   atomicAdd(reinterpret_cast<uint32_t *>(h + (z & 0xffffu)), 1u); atomicAdd(reinterpret_cast<uint32_t *>(h + (z >> 16)), 1u);
   atomicAdd(reinterpret_cast<uint32_t *>(h + (w & 0xffffu)), 1u); atomicAdd(reinterpret_cast<uint32_t *>(h + (w >> 16)), 1u);
 }
+// the same for a segment's centroid: entries of strands outside [lo, hi) (other samples') are skipped
+__device__ __forceinline__ void cl_add8_in(uint32_t *hist, uint4 v, int lo, int hi)
+{
+  char *h = reinterpret_cast<char *>(hist);
+  const uint32_t e[8] = {v.x & 0xffffu, v.x >> 16, v.y & 0xffffu, v.y >> 16, v.z & 0xffffu, v.z >> 16, v.w & 0xffffu, v.w >> 16};
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int p = (int)(e[k] >> 2), qs = cl_strand(p);
+    if (p < CL_QS_MAX && qs >= lo && qs < hi) atomicAdd(reinterpret_cast<uint32_t *>(h + e[k]), 1u);
+  }
+}
 // a full adder over 32 strands at once is TWO instructions on gfx950: v_bitop3_b32 with the majority (0xE8) and the parity (0x96) tables
 // (written with the bit operators the compiler shared x ^ y between the two and spent three or more)
 #define CSA(h, l, x, y, z) { const uint32_t x_ = (x), y_ = (y), z_ = (z); h = __builtin_amdgcn_bitop3_b32(x_, y_, z_, 0xE8); l = __builtin_amdgcn_bitop3_b32(x_, y_, z_, 0x96); }
@@ -333,7 +353,7 @@ __global__ __launch_bounds__(256, 4) void k_cl_stream(ClusterArgs a, int c0, int
   // so the scan needs no bound check.
   const uint4 *thr = reinterpret_cast<const uint4 *>(mode == 2 ? a.minm : a.tq);
   for (int i = tid; i < CL_QS_MAX + 8; i += 256) hist[i] = 0u;
-  if (mode == 2) { const int lim = a.C + a.new_rank[a.nq]; c1 = c1 < lim ? c1 : lim; }
+  if (mode == 2) { const int lim = a.new_rank[a.nq]; c1 = c1 < lim ? c1 : lim; }
   const uint4 *ent = reinterpret_cast<const uint4 *>(a.qi_ent);
 #ifdef ITSX_CL_PROF
   long long tp[6] = {0, 0, 0, 0, 0, 0}, tn = 0, tadd = 0;
@@ -343,7 +363,18 @@ __global__ __launch_bounds__(256, 4) void k_cl_stream(ClusterArgs a, int c0, int
 #define CLK(i)
 #endif
   __syncthreads();
-  for (int c = c0 + blockIdx.x; c < c1; c += gridDim.x) {
+  for (int t = c0 + blockIdx.x; t < c1; t += gridDim.x) {
+    // t -> the centroid's column and its segment's strands [slo, shi): mode 2 streams the window's j-th speculative centroid,
+    // mode 1 the t-th existing column of the window's samples (segment after segment, each in column = position order)
+    int c, slo = 0, shi = nqs;
+    if (mode == 2) {
+      c = a.newcol[t];
+      if (a.seg) { const int g = a.qseg[a.newq[t]]; slo = 2 * a.sg_q0[g]; shi = 2 * a.sg_q0[g + 1]; }
+    } else if (a.seg) {
+      int lo = 0, hi = a.G - 1;                               // the last segment whose columns start at or before t
+      while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (a.sg_cb[mid] <= t) lo = mid; else hi = mid - 1; }
+      c = a.sg_base[lo] + t - a.sg_cb[lo]; slo = 2 * a.sg_q0[lo]; shi = 2 * a.sg_q0[lo + 1];
+    } else c = a.sg_base[0] + t;
     const int n = a.cw_n[c];
     if (n == 0) continue;                                     // a rolled-back column
     const uint16_t *cw = a.cw_pool + a.cw_off[c];
@@ -389,19 +420,26 @@ __global__ __launch_bounds__(256, 4) void k_cl_stream(ClusterArgs a, int c0, int
         uint4 v[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) if (k < take) v[k] = ent[s + k];
+        if (!a.seg) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) if (k < take) cl_add8(hist, v[k], 0u);
+          for (int k = 0; k < 8; k++) if (k < take) cl_add8(hist, v[k], 0u);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 8; k++) if (k < take) cl_add8_in(hist, v[k], slo, shi);
+        }
       }
       __syncthreads();
       CLK(1)
       // ---- conserved words: wave wv owns strands 2048 wv .. + 2047, a lane one dword (32 strands) of every bitmap; bit-sliced
       // carry-save counting over the batch's bitmaps, then the counts go into the lane's own 32 histogram slots (no atomics)
       const int nh = n_hv;
-      const bool bitmaps = nh > 0 && wv * 2048 < nqs;
+      // (a segment's centroid: only the waves and lanes whose strands overlap its segment load anything)
+      const bool bitmaps = nh > 0 && wv * 2048 < nqs && wv * 2048 < shi && wv * 2048 + 2048 > slo;
+      const bool lane_in = 32 * (wv * 64 + lane) < shi && 32 * (wv * 64 + lane) + 32 > slo;
       uint32_t ones = 0, twos = 0, fours = 0, hc[CL_HVL];
 #pragma unroll
       for (int b = 0; b < CL_HVL; b++) hc[b] = 0;
-      if (bitmaps) {
+      if (bitmaps && lane_in) {
         // (a bitmap's address = a wave-uniform base + this lane's dword: the load takes the base from scalar registers and the
         // lane's offset as it is, no address arithmetic per load)
         const uint32_t loff = (uint32_t)(wv * 64 + lane);
@@ -527,7 +565,8 @@ __global__ __launch_bounds__(256, 4) void k_cl_stream(ClusterArgs a, int c0, int
           const int slot_h = ((b >> 2) * 256 + tid) * 4 + (b & 3);
           const uint32_t cnt = hist[slot_h];
           const int qs = cl_strand(slot_h);
-          if (mode == 2) a.cntx[(size_t)qs * a.xpitch + (c - a.C)] = (uint16_t)cnt;
+          if (qs < slo || qs >= shi) continue;                  // another sample's strand (counts there are not this centroid's)
+          if (mode == 2) a.cntx[(size_t)qs * a.xpitch + t] = (uint16_t)cnt;
           else {
             const int slot = atomicAdd(&a.ncand[qs], 1);
             if (slot < a.ccap) a.cand[(size_t)qs * a.ccap + slot] = cand_key(cnt, clen, cpos);
@@ -577,7 +616,8 @@ __global__ __launch_bounds__(64) void k_cl_topk(ClusterArgs a, int final)
   if (final && lane < m) {
     const unsigned long long b = top[lane];
     const int32_t pos = (int32_t)(0xffffffffu - (uint32_t)(b & 0xffffffffu));
-    int lo = 0, hi = a.C - 1;                                 // cent_pos grows with the column index
+    const int g = a.qseg[qs >> 1];                            // the strand's sample owns columns [sg_base, sg_base + sg_C)
+    int lo = a.sg_base[g], hi = a.sg_base[g] + a.sg_C[g] - 1;   // cent_pos grows with the column index
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (a.cent_pos[mid] < pos) lo = mid + 1; else hi = mid; }
     a.sel[qs * 32 + lane] = lo; a.selkey[qs * 32 + lane] = b;
   }
@@ -590,7 +630,7 @@ __global__ void k_cl_init(ClusterArgs a)
   if (qs == 0) { for (int r = 0; r < 4; r++) a.dbg[r] = 0; for (int r = 0; r < 6; r++) a.work_n[r] = 0; }
   if (qs < a.nq) { a.replay[qs] = 0; a.skipm[qs] = 0; }
   if (qs >= 2 * a.nq) return;
-  a.state[qs] = a.canon[qs >> 1] != (qs >> 1) ? 4 : (a.nk[qs] == 0 || a.C == 0) ? 3 : 0;      // 4 = a copy: reads its canonical query's state
+  a.state[qs] = a.canon[qs >> 1] != (qs >> 1) ? 4 : (a.nk[qs] == 0 || a.sg_C[a.qseg[qs >> 1]] == 0) ? 3 : 0;      // 4 = a copy: reads its canonical query's state
   a.rejects[qs] = 0; a.acc_col[qs] = -1; a.wn[qs] = 0; a.selm[qs] = 0; a.sel_short[qs] = 0;
   a.prev[qs] = ~0ULL; a.bound[qs] = 0ULL; a.acc_id[qs] = -1.0; a.xn[qs] = 0; a.hard[qs] = 0;
 }
@@ -629,7 +669,7 @@ template <int S> __device__ __forceinline__ bool align_pair(const ClusterArgs &a
 {
   const int lane = threadIdx.x;
   const int qi = qs >> 1, s = qs & 1;
-  const int64_t rq = a.order[a.f + qi], rt = a.cent_read[col];
+  const int64_t rq = a.order[a.qpos[qi]], rt = a.cent_read[col];
   const int Lq = a.rd.len[rq], Lt = a.rd.len[rt];
   const uint32_t *wq = a.rd.words + a.rd.woff[rq];
   const uint32_t *wt = a.rd.words + a.rd.woff[rt];
@@ -762,7 +802,7 @@ __device__ int precheck_pair(const ClusterArgs &a, int qs, int col, uint8_t *lds
 {
   const int lane = threadIdx.x;
   const int qi = qs >> 1, s = qs & 1;
-  const int64_t rq = a.order[a.f + qi], rt = a.cent_read[col];
+  const int64_t rq = a.order[a.qpos[qi]], rt = a.cent_read[col];
   const int Lq = a.rd.len[rq], Lt = a.rd.len[rt];
   const int minL = Lq < Lt ? Lq : Lt;
   // K = the largest E for which ANY alignment with M <= minL matches could pass: M / (M + E) grows with M, and the test is
@@ -930,7 +970,7 @@ template <int S> __device__ __forceinline__ bool score_pair(const ClusterArgs &a
 {
   const int lane = threadIdx.x;
   const int qi = qs >> 1, s = qs & 1;
-  const int64_t rq = a.order[a.f + qi], rt = a.cent_read[col];
+  const int64_t rq = a.order[a.qpos[qi]], rt = a.cent_read[col];
   const int Lq = a.rd.len[rq], Lt = a.rd.len[rt];
   const uint32_t *wq = a.rd.words + a.rd.woff[rq];
   const uint32_t *wt = a.rd.words + a.rd.woff[rt];
@@ -1013,7 +1053,7 @@ template <int S> __device__ __forceinline__ void score_pair2(const ClusterArgs &
 {
   const int lane = threadIdx.x;
   const int qi = qs >> 1, s = qs & 1;
-  const int64_t rq = a.order[a.f + qi], rt1 = a.cent_read[col1], rt2 = a.cent_read[col2];
+  const int64_t rq = a.order[a.qpos[qi]], rt1 = a.cent_read[col1], rt2 = a.cent_read[col2];
   const int Lq = a.rd.len[rq], Lt1 = a.rd.len[rt1], Lt2 = a.rd.len[rt2];
   const uint32_t *wq = a.rd.words + a.rd.woff[rq];
   const int64_t eoq = a.rd.excoff[rq];
@@ -1145,7 +1185,7 @@ template <int S> __global__ __launch_bounds__(64) void k_cl_score(ClusterArgs a,
   for (int w = blockIdx.x; w < np; w += gridDim.x) {
     const int c[2] = {pairs[2 * w], pairs[2 * w + 1]};
     const int qs = c[0] >> 5;
-    const int Lq = a.rd.len[a.order[a.f + (qs >> 1)]];
+    const int Lq = a.rd.len[a.order[a.qpos[qs >> 1]]];
     const bool pair = c[1] >= 0;
     int verdict[2] = {1, 1};
     if (Lq + 1 <= 64 * S) {
@@ -1238,7 +1278,7 @@ __global__ void k_cl_outcome(ClusterArgs a)
   const bool hit = p || m;
   const bool minus = m && (!p || a.acc_id[c2 + 1] > a.acc_id[c2]);
   const int k = c2 + (minus ? 1 : 0);
-  const int pos = a.f + qi;
+  const int pos = a.qpos[qi];
   a.res_col[pos] = hit ? a.acc_col[k] : -1;
   a.res_strand[pos] = (int8_t)(hit && minus ? -1 : 1);
   a.res_id[pos] = hit ? a.acc_id[k] : -1.0;
@@ -1250,33 +1290,30 @@ __global__ void k_cl_outcome(ClusterArgs a)
 __global__ void k_cl_wsum(ClusterArgs a)
 {
   const int qi = blockIdx.x * blockDim.x + threadIdx.x;
-  if (qi == 0) a.cw_base[0] = a.cw_off[a.C];
   if (qi > a.nq) return;
   a.wsum[qi] = (qi < a.nq && a.is_new[qi]) ? a.nk[2 * a.canon[qi]] : 0;
 }
 // register each speculative centroid as a column: its distinct forward words go to the pool (mode 0); or roll back the
-// columns flagged in rm[] (mode 1: the column stays, without words, and never counts again); one wave per query
+// columns flagged in rm[] (mode 1: the column stays, without words, and never counts again); one wave per query.  A segment's
+// speculative centroids take the next columns of its sample, in window order.
 __global__ __launch_bounds__(64) void k_cl_columns(ClusterArgs a, int clear)
 {
   const int qi = blockIdx.x, lane = threadIdx.x;
-  if (qi == a.nq) {                                          // one extra block: where the next window's first column starts
-    if (lane == 0 && !clear) a.cw_off[a.C + a.new_rank[a.nq]] = a.cw_base[0] + a.wscan[a.nq];
-    return;
-  }
   if (clear ? !a.rm[qi] : !a.is_new[qi]) return;
-  const int col = a.C + a.new_rank[qi];
+  const int g = a.qseg[qi];
+  const int col = a.sg_base[g] + a.sg_C[g] + a.new_rank[qi] - a.new_rank[a.sg_q0[g]];
   if (clear) { if (lane == 0) a.cw_n[col] = 0; return; }
   const int qs = 2 * a.canon[qi];
   const int n = a.nk[qs];
   const uint16_t *kl = a.klist + (size_t)qs * a.kcap;
-  const int64_t off = a.cw_base[0] + a.wscan[qi];
+  const int64_t off = a.pool0 + a.wscan[qi];
   for (int i = lane; i < n; i += 64) a.cw_pool[off + i] = kl[i];
   if (lane == 0) {
-    const int64_t r = a.order[a.f + qi];
+    const int64_t r = a.order[a.qpos[qi]];
     a.cw_off[col] = off; a.cw_n[col] = n;
-    a.cent_len[col] = a.rd.len[r]; a.cent_pos[col] = a.f + qi; a.cent_read[col] = (int32_t)r;
-    a.res_col[a.f + qi] = col;
-    a.newq[a.new_rank[qi]] = qi;
+    a.cent_len[col] = a.rd.len[r]; a.cent_pos[col] = a.qpos[qi]; a.cent_read[col] = (int32_t)r; a.cent_q[col] = qi;
+    a.res_col[a.qpos[qi]] = col;
+    a.newq[a.new_rank[qi]] = qi; a.newcol[a.new_rank[qi]] = col;
   }
 }
 
@@ -1295,14 +1332,16 @@ __global__ __launch_bounds__(256) void k_cl_affected(ClusterArgs a)
   if ((qs & 1) && a.skipm[cqi]) return;                  // this strand's walk was cut short: it has no say (see k_cl_take)
   if (tid == 0) xcount = 0;
   __syncthreads();
-  const int pos = a.f + (qs >> 1);
+  const int pos = a.qpos[qs >> 1];
   const uint32_t minm = n < 12 ? n : 12;
   const int state = a.state[cs];
   const u64 bound = state == 3 ? 0ULL : a.bound[cs];
   const uint16_t *cn = a.cntx + (size_t)cs * a.xpitch;      // k_cl_stream, mode 2
-  for (int c = a.C + tid; c < a.C + n_new; c += 256) {
+  const int g = a.qseg[qs >> 1];                            // the speculative centroids of this query's own segment, in position order
+  for (int j = a.new_rank[a.sg_q0[g]] + tid; j < a.new_rank[a.sg_q0[g + 1]]; j += 256) {
+    const int c = a.newcol[j];
     if (a.cent_pos[c] >= pos) break;
-    const uint32_t v = cn[c - a.C];
+    const uint32_t v = cn[j];
     if (v >= minm) {
       const u64 key = cand_key(v, a.cent_len[c], a.cent_pos[c]);
       if (key > bound) {
@@ -1348,19 +1387,20 @@ template <int S> __global__ __launch_bounds__(64) void k_cl_align_x(ClusterArgs 
 // the first accepting element wins if fewer than 32 rejects precede it.  A query that turns from centroid into
 // member is dropped from the entrants of the queries after it; a query that would turn from member into centroid
 // (its accepted hit fell out of the reject budget) has no column in this window, so the window is cut there.
-// One wave: lanes 0-31 hold the walk, lanes 32-63 the entrants; the merge is a rank count over 64 keys.
+// One wave per SEGMENT (the samples of a window never see each other's centroids, so each cuts on its own): lanes 0-31 hold
+// the walk, lanes 32-63 the entrants; the merge is a rank count over 64 keys.
 static constexpr int CL_MAXB = 4096;
 __global__ __launch_bounds__(64) void k_cl_resolve(ClusterArgs a)
 {
   __shared__ uint8_t tnew[CL_MAXB];
   __shared__ int32_t list[CL_MAXB];
   __shared__ int nlist;
-  const int lane = threadIdx.x;
-  const int nq = a.nq;
-  for (int qi = lane; qi < nq; qi += 64) tnew[qi] = (uint8_t)a.is_new[qi];
+  const int lane = threadIdx.x, g = blockIdx.x;
+  const int q0 = a.sg_q0[g], nq = a.sg_q0[g + 1];            // (tnew is indexed from the segment's first query)
+  for (int qi = q0 + lane; qi < nq; qi += 64) tnew[qi - q0] = (uint8_t)a.is_new[qi];
   if (lane == 0) nlist = 0;
   __syncthreads();
-  for (int base = 0; base < nq; base += 64) {
+  for (int base = q0; base < nq; base += 64) {
     const int qi = base + lane;
     const bool flag = qi < nq && a.replay[qi] != 0;
     const u64 mask = __ballot(flag);
@@ -1383,7 +1423,7 @@ __global__ __launch_bounds__(64) void k_cl_resolve(ClusterArgs a)
       if (lane < 32) { if (lane < wn) { key = a.wkey[cs * 32 + lane]; pid = a.wpid[cs * 32 + lane]; col = a.wcol[cs * 32 + lane]; } }
       else if (lane - 32 < xn) {
         const int c = a.xlist[qs * 32 + lane - 32];
-        if (tnew[a.newq[c - a.C]]) { key = a.xkey[qs * 32 + lane - 32]; pid = a.xpid[qs * 32 + lane - 32]; col = c; }
+        if (tnew[a.cent_q[c] - q0]) { key = a.xkey[qs * 32 + lane - 32]; pid = a.xpid[qs * 32 + lane - 32]; col = c; }
       }
       int rank = 0;
       for (int j = 0; j < 64; j++) { const u64 kj = __shfl(key, j); rank += kj > key ? 1 : 0; }
@@ -1407,22 +1447,25 @@ __global__ __launch_bounds__(64) void k_cl_resolve(ClusterArgs a)
     if (!hit && !a.is_new[qi]) { cut = qi; if (lane == 0) atomicAdd(&a.dbg[1], 1); break; }
     if (lane == 0) {
       if (hit) {
-        const int pos = a.f + qi;
+        const int pos = a.qpos[qi];
         a.res_col[pos] = hcol[minus ? 1 : 0]; a.res_strand[pos] = (int8_t)(minus ? -1 : 1); a.res_id[pos] = hid[minus ? 1 : 0];
-        if (tnew[qi]) atomicAdd(&a.dbg[2], 1);
+        if (tnew[qi - q0]) atomicAdd(&a.dbg[2], 1);
       }
-      tnew[qi] = hit ? 0 : 1;
+      tnew[qi - q0] = hit ? 0 : 1;
     }
     __syncthreads();
   }
   int ntrue = 0;
-  for (int qi = lane; qi < nq; qi += 64) {
+  for (int qi = q0 + lane; qi < nq; qi += 64) {
     const int isn = a.is_new[qi];
-    a.rm[qi] = (isn && (qi >= cut || !tnew[qi])) ? 1 : 0;
-    ntrue += (qi < cut && tnew[qi]) ? 1 : 0;
+    a.rm[qi] = (isn && (qi >= cut || !tnew[qi - q0])) ? 1 : 0;
+    ntrue += (qi < cut && tnew[qi - q0]) ? 1 : 0;
   }
   for (int off = 32; off; off >>= 1) ntrue += __shfl_xor(ntrue, off);
-  if (lane == 0) { a.wout[0] = cut; a.wout[1] = a.new_rank[cut]; a.wout[2] = ntrue; a.cw_base[1] = a.cw_off[a.C + a.new_rank[cut]]; }
+  if (lane == 0) {
+    a.wout[g] = cut; a.wout[a.G + g] = a.new_rank[cut] - a.new_rank[q0]; a.wout[2 * a.G + g] = ntrue;
+    if (g == a.G - 1) a.wout[3 * a.G] = a.wscan[cut];        // pool words kept: everything before the last segment's rolled-back tail
+  }
 }
 
 __global__ void k_cl_finalize(int32_t nk, const int32_t *order, const int32_t *res_col, const int8_t *res_strand, const double *res_id,
@@ -1436,6 +1479,7 @@ __global__ void k_cl_finalize(int32_t nk, const int32_t *order, const int32_t *r
 }
 
 // ------------------------------------------------------------------ launchers
+void launch_cl_segs(const ClusterArgs &a, hipStream_t st) { hipLaunchKernelGGL(k_cl_segs, dim3((a.nq + 255) / 256), dim3(256), 0, st, a); }
 void launch_cl_kmers(const ClusterArgs &a, hipStream_t st)
 {
   (void)hipMemsetAsync(a.ctab_key, 0, CTAB * sizeof(unsigned long long), st);
@@ -1504,7 +1548,7 @@ void launch_cl_walk(const ClusterArgs &a, int rows_per_lane, hipStream_t st)
 }
 void launch_cl_outcome(const ClusterArgs &a, hipStream_t st) { hipLaunchKernelGGL(k_cl_outcome, dim3((a.nq + 255) / 256), dim3(256), 0, st, a); }
 void launch_cl_wsum(const ClusterArgs &a, hipStream_t st) { hipLaunchKernelGGL(k_cl_wsum, dim3((a.nq + 256) / 256), dim3(256), 0, st, a); }
-void launch_cl_columns(const ClusterArgs &a, int clear, hipStream_t st) { hipLaunchKernelGGL(k_cl_columns, dim3(a.nq + 1), dim3(64), 0, st, a, clear); }
+void launch_cl_columns(const ClusterArgs &a, int clear, hipStream_t st) { hipLaunchKernelGGL(k_cl_columns, dim3(a.nq), dim3(64), 0, st, a, clear); }
 void launch_cl_validate(const ClusterArgs &a, int rows_per_lane, hipStream_t st)
 {
   hipLaunchKernelGGL(k_cl_affected, dim3(2 * a.nq), dim3(256), 0, st, a);
@@ -1518,7 +1562,7 @@ void launch_cl_validate(const ClusterArgs &a, int rows_per_lane, hipStream_t st)
   if (rows_per_lane <= 5) hipLaunchKernelGGL(k_cl_align_x<5>, dim3(grid), dim3(64), lds, st, a);
   else if (rows_per_lane <= 8) hipLaunchKernelGGL(k_cl_align_x<8>, dim3(grid), dim3(64), lds, st, a);
   else hipLaunchKernelGGL(k_cl_align_x<10>, dim3(grid), dim3(64), lds, st, a);
-  hipLaunchKernelGGL(k_cl_resolve, dim3(1), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_cl_resolve, dim3(a.G), dim3(64), 0, st, a);
 }
 void launch_cl_finalize(int32_t nk, const int32_t *order, const int32_t *res_col, const int8_t *res_strand, const double *res_id,
                         const int32_t *cent_read, int32_t *rep_of, int8_t *strand, double *pct, int32_t *is_seed, hipStream_t st)

@@ -204,6 +204,14 @@ class Engine:
         self.n_unique = n.value
         return n.value
 
+    def cluster_samples(self, cluster_id, strand_both=True):
+        """cluster(cluster_id) of every sample of the batch (set_samples) in one call: each sample's clusters are those of
+        a run of that sample alone.  With one sample this is cluster()."""
+        n = C.c_int64(0)
+        self._chk(self.L.itsx_cluster_samples(self.h, float(cluster_id), int(strand_both), C.byref(n)))
+        self.n_unique = n.value
+        return n.value
+
     # ---- f4: read orientation
     def orient_load_db(self, fasta_path):
         if not os.path.exists(fasta_path):
