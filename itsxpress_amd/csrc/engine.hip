@@ -26,6 +26,7 @@
 #include "engine.h"
 #include "k_api.h"
 #include "fastq_io.h"
+#include "writers.h"
 
 namespace itsx {
 void launch_region_offsets(int64_t npairs, const PairRec *pairs, const int32_t *pref, const int64_t *seg_pair_start,
@@ -492,16 +493,7 @@ struct StageTimer {
   ~StageTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
 };
 
-// run fn(t) on T host threads (the domain table of a large sample has millions of rows: ordering and formatting it on one
-// thread took longer than the whole GPU path)
-template <class F> static void on_threads(int T, F fn)
-{
-  if (T <= 1) { fn(0); return; }
-  std::vector<std::thread> th;
-  th.reserve((size_t)T);
-  for (int t = 0; t < T; t++) th.emplace_back([&fn, t] { fn(t); });
-  for (auto &x : th) x.join();
-}
+using itsx_io::on_threads;
 
 extern "C" {
 
@@ -1050,26 +1042,6 @@ static void parse_fastx_range(const char *s, const char *end, bool want_qual, bo
   }
 }
 
-// first record start at or after `from`: FASTQ -- a line that starts with '@' whose second line below starts with '+' (a
-// quality line may start with '@', but then that line is a sequence line, which never starts with '+'); FASTA -- a '>' line
-static size_t next_record_start(const char *t, size_t n, size_t from, bool fastq)
-{
-  size_t q = from;
-  if (q > 0) { const char *nl = (const char *)memchr(t + q - 1, '\n', n - (q - 1)); if (!nl) return n; q = (size_t)(nl - t) + 1; }
-  while (q < n) {
-    if (!fastq) { if (t[q] == '>') return q; }
-    else if (t[q] == '@') {
-      const char *l1 = (const char *)memchr(t + q, '\n', n - q);
-      const char *l2 = l1 ? (const char *)memchr(l1 + 1, '\n', n - (size_t)(l1 + 1 - t)) : nullptr;
-      if (l2 && (size_t)(l2 + 1 - t) < n && l2[1] == '+') return q;
-    }
-    const char *nl = (const char *)memchr(t + q, '\n', n - q);
-    if (!nl) return n;
-    q = (size_t)(nl - t) + 1;
-  }
-  return n;
-}
-
 static int parse_fastx(const itsx_io::Text &text, bool want_qual, bool upper, FastxPart &out, std::string &err)
 {
   const size_t n = text.size();
@@ -1082,7 +1054,7 @@ static int parse_fastx(const itsx_io::Text &text, bool want_qual, bool upper, Fa
   std::vector<size_t> cut(1, 0);
   if (T > 1) {
     const bool fastq = text[first] == '@';
-    for (int k = 1; k < T; k++) { const size_t c = next_record_start(text.data(), n, n / (size_t)T * (size_t)k, fastq); if (c > cut.back() && c < n) cut.push_back(c); }
+    for (int k = 1; k < T; k++) { const size_t from = n / (size_t)T * (size_t)k, c = fastq ? itsx_io::fastq_record_start(text.data(), n, from) : itsx_io::fasta_record_start(text.data(), n, from); if (c > cut.back() && c < n) cut.push_back(c); }
   }
   cut.push_back(n);
   const size_t np = cut.size() - 1;
@@ -4285,17 +4257,23 @@ int itsx_profile_params(const itsx_ctx *ctx, int i, int32_t *M, float *evparam6)
   if (evparam6) for (int k = 0; k < 6; k++) evparam6[k] = ctx->profs[(size_t)i].evparam[k];
   return ITSX_OK;
 }
+// reads handed over in device memory: the text comes back once (rep.fa, the seeds' sequences)
+static int host_bases(const itsx_ctx *cctx)
+{
+  itsx_ctx *ctx = const_cast<itsx_ctx *>(cctx);
+  if (ctx->bases_view) return ITSX_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->h_bases.resize((size_t)ctx->h_off[(size_t)ctx->N]);
+  if (!ctx->h_bases.empty()) HIPCHK(hipMemcpy(&ctx->h_bases[0], ctx->dev_bases, ctx->h_bases.size(), hipMemcpyDeviceToHost));
+  ctx->bases_view = ctx->h_bases.data();
+  return ITSX_OK;
+}
 // sequences of the unique representatives in input order of the seeds (what rep.fa holds), concatenated; offsets[n_unique + 1];
 // bases == NULL fills the offsets only
 int itsx_get_unique_seqs(itsx_ctx *ctx, char *bases, int64_t cap, int64_t *offsets)
 {
   CTXCHK(ctx && offsets && ctx->have_derep);
-  if (!ctx->bases_view) {                                   // reads handed over in device memory: the text comes back once
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->h_bases.resize((size_t)ctx->h_off[(size_t)ctx->N]);
-    if (!ctx->h_bases.empty()) HIPCHK(hipMemcpy(&ctx->h_bases[0], ctx->dev_bases, ctx->h_bases.size(), hipMemcpyDeviceToHost));
-    ctx->bases_view = ctx->h_bases.data();
-  }
+  { const int rc = host_bases(ctx); if (rc != ITSX_OK) return rc; }
   int64_t o = 0;
   for (int32_t u = 0; u < ctx->U; u++) {
     const int64_t s = ctx->h_seed_read[(size_t)u], L = ctx->h_len[(size_t)s];
@@ -4308,261 +4286,77 @@ int itsx_get_unique_seqs(itsx_ctx *ctx, char *bases, int64_t cap, int64_t *offse
 }
 
 // ------------------------------------------------------------------------------ writers
-// blocks of a text file formatted by a pool of threads while this thread writes the finished ones in order (a few blocks ahead at most);
-// false on a short write
-static bool write_blocks(FILE *f, size_t nb, const std::function<void(size_t, std::string &)> &format_block)
-{
-  const int T = (int)std::min<size_t>((size_t)itsx_io::io_threads(), std::max<size_t>(nb, 1));
-  bool io_ok = true;
-  if (T <= 1 || nb <= 1) {
-    std::string out;
-    for (size_t b = 0; b < nb; b++) { out.clear(); format_block(b, out); if (!out.empty() && fwrite(out.data(), 1, out.size(), f) != out.size()) io_ok = false; }
-  } else {
-    std::vector<std::string> blocks(nb);
-    std::vector<char> ready(nb, 0);
-    std::mutex mu; std::condition_variable cv;
-    size_t next = 0, written = 0;
-    const size_t ahead = (size_t)T * 4;
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; t++)
-      th.emplace_back([&] {
-        for (;;) {
-          size_t b;
-          {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return next >= nb || next < written + ahead; });
-            if (next >= nb) return;
-            b = next++;
-          }
-          std::string out;
-          out.reserve(32768 * 200);
-          format_block(b, out);
-          { std::lock_guard<std::mutex> lk(mu); blocks[b].swap(out); ready[b] = 1; }
-          cv.notify_all();
-        }
-      });
-    for (size_t b = 0; b < nb; b++) {
-      std::string out;
-      { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return ready[b] != 0; }); out.swap(blocks[b]); }
-      if (!out.empty() && fwrite(out.data(), 1, out.size(), f) != out.size()) io_ok = false;
-      { std::lock_guard<std::mutex> lk(mu); written = b + 1; }
-      cv.notify_all();
-    }
-    for (auto &x : th) x.join();
-  }
-  return io_ok;
-}
+// the files themselves are formatted by writers_host.cpp (writers.h), which the array writers of a multi-GPU run share: these
+// adapters check the state, hand over the context's arrays and map a failure to the context's error
 
-static std::string read_name(const itsx_ctx *ctx, int64_t r)
+static itsx::Labels read_labels(const itsx_ctx *ctx)
 {
-  if (!ctx->h_names.empty()) return ctx->h_names[(size_t)r];
-  char b[32]; snprintf(b, sizeof(b), "r%09lld", (long long)r); return b;
+  return ctx->h_names.empty() ? itsx::Labels{} : itsx::Labels{ctx->h_names.blob.data(), ctx->h_names.off.data()};
 }
-// clusters in vsearch's output order: abundance descending, ties by label
-static const std::vector<int32_t> &cluster_order(const itsx_ctx *cctx)
+static itsx::Clusters clusters(const itsx_ctx *ctx)
+{
+  itsx::Clusters c;
+  c.n = ctx->N; c.U = ctx->U;
+  c.uniq_of = ctx->h_uniq_of.data(); c.seed_read = ctx->h_seed_read.data(); c.abund = ctx->h_abund.data();
+  c.len = ctx->h_len.data(); c.strand = ctx->h_strand.data(); c.labels = read_labels(ctx);
+  if (ctx->clustered) { c.order = ctx->h_order.data(); c.n_order = (int64_t)ctx->h_order.size(); c.pct = ctx->h_pct.data(); }
+  if (ctx->S > 1) { c.sample = ctx->h_sample.data(); c.usample = ctx->h_usample.data(); c.sel = ctx->sel_sample; }   // writers restricted to one sample of a batch
+  return c;
+}
+// clusters in vsearch's output order, kept for the current dereplication (uc.txt and rep.fa both ask)
+static const std::vector<int32_t> &cluster_order(const itsx_ctx *cctx, const itsx::Clusters &c)
 {
   itsx_ctx *ctx = const_cast<itsx_ctx *>(cctx);
-  if (ctx->order_cache_ok) return ctx->order_cache;
-  std::vector<int32_t> &ord = ctx->order_cache;
-  ord.clear();
-  ord.reserve((size_t)ctx->U);
-  const int32_t sel = ctx->S > 1 ? ctx->sel_sample : -1;      // writers restricted to one sample of a batch
-  if (ctx->clustered) {                  // --cluster_size: clusters are numbered as their centroids were created
-    for (int32_t r : ctx->h_order) if (ctx->h_rep_of[r] == r && (sel < 0 || ctx->h_sample[(size_t)r] == sel)) ord.push_back(ctx->h_uniq_of[r]);
-    ctx->order_cache_ok = true;
-    return ord;
-  }
-  for (int32_t u = 0; u < ctx->U; u++) if (sel < 0 || ctx->usample(u) == sel) ord.push_back(u);
-  std::vector<std::string> lab((size_t)ctx->U);
-  const int T = ctx->U >= (1 << 17) ? std::max(1, std::min(16, itsx_io::io_threads())) : 1;
-  on_threads(T, [&](int t) { for (int64_t u = (int64_t)ctx->U * t / T, hi = (int64_t)ctx->U * (t + 1) / T; u < hi; u++) lab[(size_t)u] = read_name(ctx, ctx->h_seed_read[(size_t)u]); });
-  auto before = [&](int32_t a, int32_t b) {
-    if (ctx->h_abund[a] != ctx->h_abund[b]) return ctx->h_abund[a] > ctx->h_abund[b];
-    return strcmp(lab[a].c_str(), lab[b].c_str()) < 0;
-  };
-  // a stable sort in pieces (6 M labels of a 10 M-read sample: seconds on one thread): every thread orders its share, neighbouring
-  // shares are merged pairwise -- std::inplace_merge keeps equal elements in order, so the result is std::stable_sort's
-  const size_t n = ord.size();
-  std::vector<size_t> cut((size_t)T + 1);
-  for (int t = 0; t <= T; t++) cut[(size_t)t] = n * (size_t)t / (size_t)T;
-  on_threads(T, [&](int t) { std::stable_sort(ord.begin() + (ptrdiff_t)cut[(size_t)t], ord.begin() + (ptrdiff_t)cut[(size_t)t + 1], before); });
-  for (int w = 1; w < T; w *= 2) {
-    std::vector<int> lefts;
-    for (int t = 0; t + w < T; t += 2 * w) lefts.push_back(t);
-    on_threads((int)lefts.size(), [&](int k) {
-      const int t = lefts[(size_t)k];
-      std::inplace_merge(ord.begin() + (ptrdiff_t)cut[(size_t)t], ord.begin() + (ptrdiff_t)cut[(size_t)(t + w)], ord.begin() + (ptrdiff_t)cut[(size_t)std::min(T, t + 2 * w)], before);
-    });
-  }
-  ctx->order_cache_ok = true;
-  return ord;
+  if (!ctx->order_cache_ok) { itsx::cluster_order(c, ctx->order_cache); ctx->order_cache_ok = true; }
+  return ctx->order_cache;
 }
 
 int itsx_write_uc(const itsx_ctx *ctx, const char *path)
 {
   CTXCHK(ctx && path && ctx->have_derep);
-  FILE *f = fopen(path, "w");
-  if (!f) SET_ERR(ctx, ITSX_E_IO, std::string("cannot write ") + path);
-  const std::vector<int32_t> &ord = cluster_order(ctx);
-  if (ctx->clustered) {
-    // vsearch --cluster_size writes the S and H rows as the queries are processed, then one C row per cluster
-    std::vector<int32_t> cno((size_t)ctx->U);
-    for (size_t c = 0; c < ord.size(); c++) cno[ord[c]] = (int32_t)c;
-    const int32_t sel = ctx->S > 1 ? ctx->sel_sample : -1;    // (a batch clustered by itsx_cluster_samples: one sample's rows)
-    for (int32_t r : ctx->h_order) {
-      if (sel >= 0 && ctx->h_sample[(size_t)r] != sel) continue;
-      const int32_t u = ctx->h_uniq_of[r];
-      if (ctx->h_rep_of[r] == r) fprintf(f, "S\t%d\t%d\t*\t*\t*\t*\t*\t%s\t*\n", cno[u], ctx->h_len[r], read_name(ctx, r).c_str());
-      else fprintf(f, "H\t%d\t%d\t%.1f\t%c\t0\t0\t*\t%s\t%s\n", cno[u], ctx->h_len[r], ctx->h_pct[r], ctx->h_strand[r] < 0 ? '-' : '+',
-                   read_name(ctx, r).c_str(), read_name(ctx, ctx->h_rep_of[r]).c_str());
-    }
-    for (size_t c = 0; c < ord.size(); c++)
-      fprintf(f, "C\t%zu\t%d\t*\t*\t*\t*\t*\t%s\t*\n", c, ctx->h_abund[ord[c]], read_name(ctx, ctx->h_seed_read[ord[c]]).c_str());
-    const bool bad = ferror(f) != 0;
-    if (fclose(f) != 0 || bad) SET_ERR(ctx, ITSX_E_IO, std::string("short write to ") + path);
-    return ITSX_OK;
-  }
-  // the members of every cluster in input order (a counting sort by representative), then blocks of clusters formatted by the I/O pool:
-  // the S row and the H rows of a cluster, cluster after cluster, then the C rows (10 M reads: 16 M lines)
-  std::vector<int64_t> mstart((size_t)ctx->U + 1, 0);
-  for (int64_t r = 0; r < ctx->N; r++) { const int32_t u = ctx->h_uniq_of[r]; if (u >= 0 && ctx->h_rep_of[r] != r) mstart[(size_t)u + 1]++; }
-  for (int32_t u = 0; u < ctx->U; u++) mstart[(size_t)u + 1] += mstart[(size_t)u];
-  std::vector<int64_t> member((size_t)mstart[(size_t)ctx->U]);
-  {
-    std::vector<int64_t> cur(mstart.begin(), mstart.end() - 1);
-    for (int64_t r = 0; r < ctx->N; r++) { const int32_t u = ctx->h_uniq_of[r]; if (u >= 0 && ctx->h_rep_of[r] != r) member[(size_t)cur[(size_t)u]++] = r; }
-  }
-  const size_t BLK = 16384, nbc = (ord.size() + BLK - 1) / BLK;
-  auto append = [](std::string &out, const char *fmt, auto... args) {
-    char line[512];
-    const int len = snprintf(line, sizeof(line), fmt, args...);
-    if (len < 0) return;
-    if ((size_t)len < sizeof(line)) { out.append(line, (size_t)len); return; }
-    std::string big((size_t)len + 1, '\0');                  // (labels longer than the line buffer)
-    snprintf(&big[0], big.size(), fmt, args...);
-    out.append(big.data(), (size_t)len);
-  };
-  auto format_block = [&](size_t b, std::string &out) {
-    if (b < nbc) {
-      for (size_t c = b * BLK; c < std::min(ord.size(), (b + 1) * BLK); c++) {
-        const int32_t u = ord[c]; const int64_t s = ctx->h_seed_read[u];
-        const std::string sl = read_name(ctx, s);
-        append(out, "S\t%zu\t%d\t*\t*\t*\t*\t*\t%s\t*\n", c, ctx->h_len[s], sl.c_str());
-        for (int64_t k = mstart[(size_t)u]; k < mstart[(size_t)u + 1]; k++) {
-          const int64_t r = member[(size_t)k];
-          append(out, "H\t%zu\t%d\t100.0\t%c\t0\t0\t*\t%s\t%s\n", c, ctx->h_len[r], ctx->h_strand[r] < 0 ? '-' : '+', read_name(ctx, r).c_str(), sl.c_str());
-        }
-      }
-    } else {
-      for (size_t c = (b - nbc) * BLK; c < std::min(ord.size(), (b - nbc + 1) * BLK); c++) {
-        const int32_t u = ord[c];
-        append(out, "C\t%zu\t%d\t*\t*\t*\t*\t*\t%s\t*\n", c, ctx->h_abund[u], read_name(ctx, ctx->h_seed_read[u]).c_str());
-      }
-    }
-  };
-  // a truncated uc.txt would silently shorten Dedup.parse's matchdict (vsearch exits non-zero on a full disk)
-  const bool ok = write_blocks(f, 2 * nbc, format_block);
-  const bool bad = ferror(f) != 0;
-  if (fclose(f) != 0 || bad || !ok) SET_ERR(ctx, ITSX_E_IO, std::string("short write to ") + path);
+  const itsx::Clusters c = clusters(ctx);
+  std::string err;
+  const int rc = itsx::write_uc(path, c, cluster_order(ctx, c), err);
+  if (rc != ITSX_OK) SET_ERR(ctx, rc, err);
   return ITSX_OK;
 }
 
-int itsx_write_rep_fasta(const itsx_ctx *cctx, const char *path)
+int itsx_write_rep_fasta(const itsx_ctx *ctx, const char *path)
 {
-  CTXCHK(cctx && path && cctx->have_derep);
-  itsx_ctx *ctx = const_cast<itsx_ctx *>(cctx);
-  if (!ctx->bases_view) {                                   // reads handed over in device memory: the text comes back once
-    ctx->h_bases.resize((size_t)ctx->h_off[(size_t)ctx->N]);
-    if (!ctx->h_bases.empty()) HIPCHK(hipMemcpy(&ctx->h_bases[0], ctx->dev_bases, ctx->h_bases.size(), hipMemcpyDeviceToHost));
-    ctx->bases_view = ctx->h_bases.data();
-  }
-  FILE *f = fopen(path, "w");
-  if (!f) SET_ERR(ctx, ITSX_E_IO, std::string("cannot write ") + path);
-  const std::vector<int32_t> &ord = cluster_order(ctx);
-  const size_t BLK = 8192, nb = (ord.size() + BLK - 1) / BLK;
-  auto format_block = [&](size_t bk, std::string &out) {
-    for (size_t c = bk * BLK; c < std::min(ord.size(), (bk + 1) * BLK); c++) {
-      const int64_t s = ctx->h_seed_read[ord[c]];
-      out.push_back('>'); out.append(read_name(ctx, s)); out.push_back('\n');
-      const char *b = ctx->bases_view + ctx->h_off[s]; const int64_t L = ctx->h_len[s];
-      for (int64_t i = 0; i < L; i += 80) { out.append(b + i, (size_t)std::min<int64_t>(80, L - i)); out.push_back('\n'); }
-    }
-  };
-  const bool ok = write_blocks(f, nb, format_block);
-  const bool bad = ferror(f) != 0;
-  if (fclose(f) != 0 || bad || !ok) SET_ERR(ctx, ITSX_E_IO, std::string("short write to ") + path);
+  CTXCHK(ctx && path && ctx->have_derep);
+  { const int rc = host_bases(ctx); if (rc != ITSX_OK) return rc; }
+  const itsx::Clusters c = clusters(ctx);
+  std::string err;
+  const int rc = itsx::write_rep_fasta(path, c, cluster_order(ctx, c), itsx::Seqs{ctx->bases_view, ctx->h_off.data(), false}, err);
+  if (rc != ITSX_OK) SET_ERR(ctx, rc, err);
   return ITSX_OK;
 }
 
 int itsx_write_domtbl(const itsx_ctx *ctx, const char *path)
 {
   CTXCHK(ctx && path && ctx->have_final);
-  const int rc = fetch_domains(ctx);
-  if (rc != ITSX_OK) return rc;
-  FILE *f = fopen(path, "w");
-  if (!f) SET_ERR(ctx, ITSX_E_IO, std::string("cannot write ") + path);
-  fprintf(f, "#                                                                            --- full sequence --- -------------- this domain -------------   hmm coord   ali coord   env coord\n");
-  fprintf(f, "# target name        accession   tlen query name           accession   qlen   E-value  score  bias   #  of  c-Evalue  i-Evalue  score  bias  from    to  from    to  from    to  acc description of target\n");
-  // rows: profile order; within a profile, targets; within a target, reported domains renumbered
-  const std::vector<itsx_domain> &D = ctx->h_dom;
+  { const int rc = fetch_domains(ctx); if (rc != ITSX_OK) return rc; }
   std::vector<int64_t> Zs((size_t)ctx->S, 0);          // hmmsearch's Z: targets searched, per sample
   // (a context narrowed by itsx_set_active_uniques searched only its active targets: the E-value columns of a sharded run are
   // this shard's own, the reported / not-reported decisions are global through the all-reduced domZ)
   if (ctx->S == 1) Zs[0] = ctx->U_active; else for (int32_t u = 0; u < ctx->U; u++) Zs[(size_t)ctx->usample(u)]++;
-  // one (profile, target) group is formatted on its own, so the table is cut into blocks of whole groups that a pool of
-  // threads formats while this thread writes the finished blocks in order (a few blocks ahead at most)
-  std::vector<size_t> cut(1, 0);
-  {
-    const size_t target = 32768;
-    size_t i = 0, last = 0;
-    while (i < D.size()) {
-      size_t j = i;
-      while (j < D.size() && D[j].prof == D[i].prof && D[j].rep == D[i].rep) j++;
-      if (j - last >= target) { cut.push_back(j); last = j; }
-      i = j;
-    }
-    if (cut.back() != D.size()) cut.push_back(D.size());
+  std::string pnames;
+  std::vector<int64_t> poffs(1, 0);
+  std::vector<int32_t> M;
+  std::vector<float> tau, lambda;
+  for (const HostProfile &h : ctx->profs) {
+    pnames += h.name; poffs.push_back((int64_t)pnames.size());
+    M.push_back(h.M); tau.push_back(h.evparam[4]); lambda.push_back(h.evparam[5]);
   }
-  const size_t nb = cut.size() - 1;
-  auto format_block = [&](size_t b, std::string &out) {
-    char line[1024];
-    size_t i = cut[b];
-    const size_t end = cut[b + 1];
-    while (i < end) {
-      size_t j = i; int nrep = 0;
-      while (j < end && D[j].prof == D[i].prof && D[j].rep == D[i].rep) { nrep += D[j].dom_reported; j++; }
-      int k = 0;
-      const int32_t smp = ctx->usample(D[i].rep);
-      if (ctx->S > 1 && ctx->sel_sample >= 0 && smp != ctx->sel_sample) { i = j; continue; }
-      const std::string tname = nrep ? read_name(ctx, ctx->h_seed_read[D[i].rep]) : std::string();
-      for (size_t d = i; d < j; d++) {
-        if (!D[d].dom_reported) continue;
-        k++;
-        const HostProfile &h = ctx->profs[D[d].prof];
-        const double Z = (double)Zs[(size_t)smp], dz = (double)ctx->domz[(size_t)smp * ctx->P + D[d].prof];
-        const double seqE = Z * det_exp(exp_logsurv((double)D[d].seq_score, (double)h.evparam[4], (double)h.evparam[5]));
-        const double P = det_exp(D[d].lnP);
-        // hmm/ali coordinates and acc need the optimal-accuracy alignment, which the engine does not compute:
-        // envelope coordinates are written in their place (the reference reads only env coords and the score).
-        const int len = snprintf(line, sizeof(line), "%-20s %-10s %5d %-20s %-10s %5d %9.2g %6.1f %5.1f %3d %3d %9.2g %9.2g %6.1f %5.1f %5d %5d %5d %5d %5d %5d %4.2f %s\n",
-              tname.c_str(), "-", D[d].tlen, h.name.c_str(), "-", h.M, seqE, D[d].seq_score, D[d].seq_bias,
-              k, nrep, P * dz, P * Z, D[d].bitscore, D[d].dombias / 0.69314718055994529, 1, h.M, D[d].ienv, D[d].jenv, D[d].ienv, D[d].jenv, 0.0, "-");
-        if (len < 0) continue;
-        if ((size_t)len < sizeof(line)) out.append(line, (size_t)len);
-        else {                                        // a label longer than the line buffer
-          std::string big((size_t)len + 1, '\0');
-          snprintf(&big[0], big.size(), "%-20s %-10s %5d %-20s %-10s %5d %9.2g %6.1f %5.1f %3d %3d %9.2g %9.2g %6.1f %5.1f %5d %5d %5d %5d %5d %5d %4.2f %s\n",
-              tname.c_str(), "-", D[d].tlen, h.name.c_str(), "-", h.M, seqE, D[d].seq_score, D[d].seq_bias,
-              k, nrep, P * dz, P * Z, D[d].bitscore, D[d].dombias / 0.69314718055994529, 1, h.M, D[d].ienv, D[d].jenv, D[d].ienv, D[d].jenv, 0.0, "-");
-          out.append(big.data(), (size_t)len);
-        }
-      }
-      i = j;
-    }
-  };
-  bool io_ok = write_blocks(f, nb, format_block);
-  if (fclose(f) != 0) io_ok = false;
-  if (!io_ok) SET_ERR(ctx, ITSX_E_IO, std::string("short write to ") + path);
+  itsx::DomTable t;
+  t.rows = ctx->h_dom.data(); t.n = ctx->h_dom.size(); t.P = ctx->P;
+  t.prof_names = itsx::Labels{pnames.data(), poffs.data()}; t.M = M.data(); t.tau = tau.data(); t.lambda = lambda.data();
+  t.Z = Zs.data(); t.domz = ctx->domz.data();
+  if (ctx->S > 1) { t.usample = ctx->h_usample.data(); t.sel = ctx->sel_sample; }
+  t.seed_read = ctx->h_seed_read.data(); t.targets = read_labels(ctx);
+  std::string err;
+  const int rc = itsx::write_domtbl(path, t, err);
+  if (rc != ITSX_OK) SET_ERR(ctx, rc, err);
   return ITSX_OK;
 }
 
@@ -4580,7 +4374,7 @@ int itsx_get_read_names(const itsx_ctx *ctx, char *names, int64_t cap, int64_t *
   int64_t o = 0;
   for (int64_t r = 0; r < ctx->N; r++) {
     offsets[r] = o;
-    const std::string nm = read_name(ctx, r);
+    const std::string nm = read_labels(ctx)(r);
     if (names) { if (o + (int64_t)nm.size() > cap) SET_ERR(ctx, ITSX_E_ARG, "name buffer too small"); memcpy(names + o, nm.data(), nm.size()); }
     o += (int64_t)nm.size();
   }

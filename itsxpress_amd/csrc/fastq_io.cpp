@@ -457,14 +457,13 @@ struct StreamImpl {
 };
 
 namespace {
-// first FASTQ record start at or after `from` inside t[0, n): a line that starts with '@' whose second line below starts with '+'
-// (a quality line may start with '@'; then the second line below it is a sequence line, which never starts with '+')
-size_t fastq_start_from(const char *t, size_t n, size_t from)
+size_t record_start(const char *t, size_t n, size_t from, bool fastq)
 {
   size_t q = from;
   if (q > 0) { const char *nl = (const char *)memchr(t + q - 1, '\n', n - (q - 1)); if (!nl) return n; q = (size_t)(nl - t) + 1; }
   while (q < n) {
-    if (t[q] == '@') {
+    if (!fastq) { if (t[q] == '>') return q; }
+    else if (t[q] == '@') {
       const char *l1 = (const char *)memchr(t + q, '\n', n - q);
       const char *l2 = l1 ? (const char *)memchr(l1 + 1, '\n', n - (size_t)(l1 + 1 - t)) : nullptr;
       if (l2 && (size_t)(l2 + 1 - t) < n && l2[1] == '+') return q;
@@ -477,7 +476,8 @@ size_t fastq_start_from(const char *t, size_t n, size_t from)
 }
 }  // namespace
 
-size_t fastq_record_start(const char *t, size_t n, size_t from) { return fastq_start_from(t, n, from); }
+size_t fastq_record_start(const char *t, size_t n, size_t from) { return record_start(t, n, from, true); }
+size_t fasta_record_start(const char *t, size_t n, size_t from) { return record_start(t, n, from, false); }
 
 TextStream::TextStream() : s(new StreamImpl) {}
 TextStream::~TextStream()
@@ -615,7 +615,7 @@ bool TextStream::next(size_t min_bytes, const char **ptr, size_t *nbytes, bool *
     const int gen = s->gen;
     s->scanning = true;
     g.unlock();
-    const size_t c = fastq_start_from(t, avail, from);
+    const size_t c = fastq_record_start(t, avail, from);
     g.lock();
     s->scanning = false;
     s->cv.notify_all();

@@ -21,6 +21,8 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <thread>
+#include <vector>
 
 namespace itsx_io {
 
@@ -79,6 +81,17 @@ void cache_put(const char *path, std::shared_ptr<const Text> text);
 
 int io_threads();               // ITSX_IO_THREADS or min(hardware threads, 32)
 
+// run fn(t) on T host threads (the domain table of a large sample has millions of rows: ordering and formatting it on one
+// thread took longer than the whole GPU path)
+template <class F> void on_threads(int T, F fn)
+{
+  if (T <= 1) { fn(0); return; }
+  std::vector<std::thread> th;
+  th.reserve((size_t)T);
+  for (int t = 0; t < T; t++) th.emplace_back([&fn, t] { fn(t); });
+  for (auto &x : th) x.join();
+}
+
 // pinflate.cpp: block-parallel inflate of a single-member gzip buffer (data[n .. n+16) must be readable).  true = `out`
 // holds the content and its length and CRC-32 matched the trailer; false = not applicable or any doubt: inflate serially.
 // progress (may be null): called after every round with the number of bytes of `out` that are final (front to back).
@@ -117,8 +130,11 @@ class TextStream {
   StreamImpl *s;
 };
 
-// first FASTQ record start at or after `from` in t[0, n) (a line that starts with '@' whose second line below starts with '+'); n: none
+// first record start at or after `from` in t[0, n), n: none.  FASTQ: a line that starts with '@' whose second line below starts
+// with '+' (a quality line may start with '@', but then that second line is a sequence line, which never starts with '+');
+// FASTA: a line that starts with '>'.  `from` inside a line: the search begins at the next line.
 size_t fastq_record_start(const char *t, size_t n, size_t from);
+size_t fasta_record_start(const char *t, size_t n, size_t from);
 
 struct WriterImpl;
 class BlockWriter {

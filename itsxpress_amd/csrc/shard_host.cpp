@@ -28,19 +28,6 @@ size_t count_nl(const char *t, size_t a, size_t b)
   while (p < e) { const char *q = (const char *)memchr(p, '\n', (size_t)(e - p)); if (!q) break; c++; p = q + 1; }
   return c;
 }
-// FASTA: a record starts at a line that begins with '>'
-size_t fasta_start_from(const char *t, size_t n, size_t from)
-{
-  size_t q = from;
-  if (q > 0) { const char *nl = (const char *)memchr(t + q - 1, '\n', n - (q - 1)); if (!nl) return n; q = (size_t)(nl - t) + 1; }
-  while (q < n) {
-    if (t[q] == '>') return q;
-    const char *nl = (const char *)memchr(t + q, '\n', n - q);
-    if (!nl) return n;
-    q = (size_t)(nl - t) + 1;
-  }
-  return n;
-}
 size_t count_gt(const char *t, size_t a, size_t b)      // lines of t[a, b) that start with '>' (a is a line start)
 {
   size_t c = 0, q = a;
@@ -108,7 +95,7 @@ int itsx_shard_text(const char *path, int32_t n_parts, const int64_t *match_reco
   if (!match_records) {
     for (int p = 1; p < n_parts; p++) {
       const size_t target = (size_t)((double)n * (double)p / (double)n_parts);
-      size_t c = fastq ? itsx_io::fastq_record_start(t, n, target) : fasta_start_from(t, n, target);
+      size_t c = fastq ? itsx_io::fastq_record_start(t, n, target) : itsx_io::fasta_record_start(t, n, target);
       cut[(size_t)p] = std::max(c, cut[(size_t)p - 1]);
     }
   } else {
@@ -121,7 +108,7 @@ int itsx_shard_text(const char *path, int32_t n_parts, const int64_t *match_reco
     on_pool(T, nb, [&](int b) {
       const size_t a = (size_t)b * BS, e = std::min(n, a + BS);
       if (fastq) cnt[(size_t)b + 1] = count_nl(t, a, e);
-      else { size_t q = a; if (q > 0) { q = fasta_start_from(t, n, a); } cnt[(size_t)b + 1] = q < e ? count_gt(t, q, e) : 0; }
+      else { size_t q = a; if (q > 0) { q = itsx_io::fasta_record_start(t, n, a); } cnt[(size_t)b + 1] = q < e ? count_gt(t, q, e) : 0; }
     });
     for (int b = 0; b < nb; b++) cnt[(size_t)b + 1] += cnt[(size_t)b];
     int64_t acc = 0;
@@ -143,7 +130,7 @@ int itsx_shard_text(const char *path, int32_t n_parts, const int64_t *match_reco
         if (want >= cnt[(size_t)nb]) { cut[(size_t)p] = n; continue; }
         int b = (int)(std::upper_bound(cnt.begin(), cnt.end(), want) - cnt.begin()) - 1;      // cnt[b] <= want < cnt[b + 1]
         size_t seen = cnt[(size_t)b], q = (size_t)b * BS;
-        if (q > 0) q = fasta_start_from(t, n, q);
+        if (q > 0) q = itsx_io::fasta_record_start(t, n, q);
         while (q < n) {                                     // title number `want` (0-based) starts the piece
           if (t[q] == '>') { if (seen == want) break; seen++; }
           const char *nl = (const char *)memchr(t + q, '\n', n - q);

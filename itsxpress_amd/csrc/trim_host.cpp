@@ -129,20 +129,6 @@ extern "C" {
 
 const char *itsx_trim_last_error(void) { return g_trim_error.c_str(); }
 
-// a cursor over a byte range of a FASTQ text that starts at a record start (the record parser of Records, on a slice)
-static bool fastq_record_start(const char *t, const char *end, const char *p)
-{
-  // a line that starts with '@' and whose second line below starts with '+' (a quality line may start with '@' too, but then that
-  // second line is a sequence line): the rule the engine's loader cuts large texts by
-  if (p >= end || *p != '@') return false;
-  const char *l1 = (const char *)memchr(p, '\n', (size_t)(end - p));
-  if (!l1) return false;
-  const char *l2 = (const char *)memchr(l1 + 1, '\n', (size_t)(end - (l1 + 1)));
-  if (!l2 || l2 + 1 >= end) return false;
-  (void)t;
-  return l2[1] == '+';
-}
-
 int itsx_write_trimmed_fastq(const char *seq_path, const char *out_path, int compression, int trim_ccs,
                              const int32_t *start, const int32_t *stop, int64_t n_records,
                              int64_t *n_written, int64_t *total_len)
@@ -270,11 +256,10 @@ struct itsx_twriter {
         if (!text_done) break;
         hi = avail;
       } else {
-        const char *t0 = base, *tend = base + avail;
-        const char *p = (const char *)memchr(t0 + want, '\n', avail - want);
-        while (p && p + 1 < tend && !fastq_record_start_at(t0, tend, p + 1)) p = (const char *)memchr(p + 1, '\n', (size_t)(tend - (p + 1)));
-        if (!p || p + 1 >= tend) { if (!text_done) break; hi = avail; }
-        else hi = (size_t)(p + 1 - t0);
+        // the first record start after the first newline at or after `want`
+        const size_t c = itsx_io::fastq_record_start(base, avail, want + 1);
+        if (c >= avail) { if (!text_done) break; hi = avail; }
+        else hi = c;
       }
       next_cut_at = want;
       if (hi <= lo) continue;               // (a record longer than a unit)
@@ -301,7 +286,6 @@ struct itsx_twriter {
     }
     cv_work.notify_all();
   }
-  static bool fastq_record_start_at(const char *t, const char *end, const char *p);
   void work();
   // writes every finished unit that is next in order (called without the lock)
   void flush_ready()
@@ -354,8 +338,6 @@ struct itsx_twriter {
     return !bad;
   }
 };
-
-bool itsx_twriter::fastq_record_start_at(const char *t, const char *end, const char *p) { return fastq_record_start(t, end, p); }
 
 void itsx_twriter::work()
 {
@@ -644,10 +626,9 @@ int itsx_write_trimmed_paired(const char *r1_path, const char *r2_path, const ch
       const size_t size = (size_t)(tend - t0);
       cut.assign(1, t0);
       for (size_t at = range; at < size; at += range) {
-        const char *p = (const char *)memchr(t0 + at, '\n', size - at);
-        while (p && p + 1 < tend && !fastq_record_start(t0, tend, p + 1)) p = (const char *)memchr(p + 1, '\n', (size_t)(tend - (p + 1)));
-        if (!p || p + 1 >= tend) break;
-        if (p + 1 > cut.back()) cut.push_back(p + 1);
+        const size_t c = itsx_io::fastq_record_start(t0, size, at + 1);      // (after the first newline at or after `at`)
+        if (c >= size) break;
+        if (t0 + c > cut.back()) cut.push_back(t0 + c);
       }
       cut.push_back(tend);
     };

@@ -207,3 +207,112 @@ def test_shard_text_cuts_at_record_starts_and_follows_the_mate_file(tmp_path):
     short.write_text("".join(r2[:900]))
     rc, _, _ = shard(str(short), 3, match=np.array([400, 300, 300]))
     assert rc != 0 and b"mate" in L.itsx_shard_last_error()
+
+
+def _blob(labels):
+    offs = np.zeros(len(labels) + 1, np.int64)
+    np.cumsum([len(x) for x in labels], out=offs[1:])
+    return b"".join(labels), offs
+
+
+def _synthetic_derep(n=40000, seed=23):
+    """n reads, about 25 000 clusters (more than one 16 384-cluster block), ties of abundance with equal and unequal labels, dropped
+    reads, both strands, and one label longer than 512 bytes"""
+    rng = np.random.default_rng(seed)
+    rep_of = np.empty(n, np.int64)
+    seeds = []
+    for r in range(n):
+        k = rng.random()
+        if k < 0.02:
+            rep_of[r] = -1
+        elif k < 0.62 or not seeds:
+            rep_of[r] = r
+            seeds.append(r)
+        else:
+            rep_of[r] = seeds[int(rng.integers(len(seeds)) if rng.random() < 0.5 else rng.integers(max(0, len(seeds) - 50), len(seeds)))]
+    strand = np.where(rng.random(n) < 0.3, -1, 1).astype(np.int8)
+    lens = rng.integers(30, 260, n).astype(np.int32)
+    labels = [b"read%d;size=%d" % (int(rng.integers(5000)), r % 7) for r in range(n)]     # duplicate labels on purpose
+    labels[seeds[len(seeds) // 2]] = b"L" * 700
+    nb, no = _blob(labels)
+    sb = b"".join(bytes(rng.choice(list(b"ACGTacgt"), int(lens[r]))) for r in seeds)
+    so = np.zeros(len(seeds) + 1, np.int64)
+    np.cumsum([int(lens[r]) for r in seeds], out=so[1:])
+    return rep_of, strand, lens, nb, no, sb, so, len(seeds)
+
+
+def test_array_derep_writer_pool_and_one_thread_agree(tmp_path, monkeypatch):
+    """uc.txt / rep.fa of a derep larger than one block of clusters: the same bytes on one thread and on eight, and the bytes the
+    writer has always written (sha256 pinned)"""
+    import hashlib
+    from itsxpress_amd import _lib
+    L = _lib.lib()
+    rep_of, strand, lens, nb, no, sb, so, ns = _synthetic_derep()
+    out = {}
+    for threads in ("1", "8"):
+        monkeypatch.setenv("ITSX_IO_THREADS", threads)
+        uc, rep = tmp_path / ("uc%s.txt" % threads), tmp_path / ("rep%s.fa" % threads)
+        rc = L.itsx_write_derep_arrays(os.fsencode(uc), os.fsencode(rep), len(rep_of), rep_of.ctypes.data, strand.ctypes.data,
+                                       lens.ctypes.data, nb, no.ctypes.data, sb, so.ctypes.data, ns)
+        assert rc == 0, L.itsx_writers_last_error()
+        out[threads] = (uc.read_bytes(), rep.read_bytes())
+    assert out["1"] == out["8"]
+    uc, rep = out["1"]
+    assert uc.count(b"\nC\t") + uc.startswith(b"C\t") == ns > 16384 and b"L" * 700 in uc
+    assert hashlib.sha256(uc).hexdigest() == "1f2407497199f2c0c53e6c48bc8f2436d238140db928990b31c0ca78d968a289"
+    assert hashlib.sha256(rep).hexdigest() == "7132c38e60ea5e32f214f29a76dd7e457ea7ee05211cfa1519c1309f8ee26ade"
+    # without names: reads are labelled r%09d
+    uc0 = tmp_path / "uc0.txt"
+    assert L.itsx_write_derep_arrays(os.fsencode(uc0), None, len(rep_of), rep_of.ctypes.data, strand.ctypes.data, lens.ctypes.data,
+                                     None, None, None, None, 0) == 0
+    assert hashlib.sha256(uc0.read_bytes()).hexdigest() == "43ff7caeae3f616b56dbf3410b31a1b4216c4c649226a2b7686fe3347b97159f"
+
+
+def _domtbl_rows():
+    from itsxpress_amd._lib import DOMAIN_DTYPE
+    # (prof, rep, dom_idx, reported, tlen, ienv, jenv, bitscore, dombias, lnP, seq_score, seq_bias), in no particular order
+    spec = [(1, 0, 0, 1, 180, 101, 140, 31.5, 0.3, -21.25, 33.0, 0.5),
+            (0, 2, 0, 1, 250, 7, 66, 45.25, 0.0, -30.5, 45.5, 0.0),
+            (0, 0, 1, 0, 180, 90, 120, 2.5, 1.2, -1.5, 38.75, 1.5),
+            (0, 0, 0, 1, 180, 3, 60, 36.0, 0.1, -25.0, 38.75, 1.5),
+            (0, 0, 2, 1, 180, 130, 178, 12.75, 0.6, -9.0, 38.75, 1.5),
+            (0, 3, 0, 0, 90, 10, 40, 1.25, 0.0, -0.75, 1.5, 0.25),
+            (1, 3, 0, 0, 90, 50, 80, 0.5, 0.0, -0.25, 0.5, 0.0),
+            (1, 1, 1, 1, 300, 200, 260, 22.0, 0.2, -14.5, 40.25, 0.75),
+            (1, 1, 0, 1, 300, 20, 70, 18.5, 0.4, -11.75, 40.25, 0.75),
+            (1, 1, -1, 1, 300, 1, 2, 99.0, 0.0, -99.0, 99.0, 0.0)]          # dom_idx < 0: not a domain, never written
+    rows = np.zeros(len(spec), DOMAIN_DTYPE)
+    for i, (p, t, d, rep, tlen, ie, je, bit, db, lnp, ss, sb) in enumerate(spec):
+        rows[i] = (t, p, tlen, ie, je, d, 3, 0, 0.0, 0.0, db, bit, lnp, ss, sb, 1, rep)
+    return rows
+
+
+DOMTBL_EXPECTED = (
+    '#                                                                            --- full sequence --- -------------- this domain -------------   hmm coord   ali coord   env coord\n' +
+    '# target name        accession   tlen query name           accession   qlen   E-value  score  bias   #  of  c-Evalue  i-Evalue  score  bias  from    to  from    to  from    to  acc description of target\n' +
+    'target_zero          -            180 3_ITS2_start         -             61   9.4e-13   38.8   1.5   1   2   4.2e-11   9.7e-11   36.0   0.1     1    61     3    60     3    60 0.00 -\n' +
+    'target_zero          -            180 3_ITS2_start         -             61   9.4e-13   38.8   1.5   2   2   0.00037   0.00086   12.8   0.9     1    61   130   178   130   178 0.00 -\n' +
+    "X" * 1500 + ' -            250 3_ITS2_start         -             61   8.6e-15   45.5   0.0   1   1   1.7e-13     4e-13   45.2   0.0     1    61     7    66     7    66 0.00 -\n' +
+    'target_zero          -            180 4_ITS2_end_of_a_long_profile_name -             44     3e-11   33.0   0.5   1   1   1.2e-09   4.1e-09   31.5   0.4     1    44   101   140   101   140 0.00 -\n' +
+    't1                   -            300 4_ITS2_end_of_a_long_profile_name -             44   1.8e-13   40.2   0.8   1   2   1.6e-05   5.5e-05   18.5   0.6     1    44    20    70    20    70 0.00 -\n' +
+    't1                   -            300 4_ITS2_end_of_a_long_profile_name -             44   1.8e-13   40.2   0.8   2   2     1e-06   3.5e-06   22.0   0.3     1    44   200   260   200   260 0.00 -\n'
+)
+
+
+def test_array_domtbl_writer_rows(tmp_path):
+    """domtbl.txt from hand-built rows: two profiles, a target with several domains of which one is not reported (renumbered
+    k of nrep), a target without a reported domain (no line), a row that is no domain, and a label longer than 1 024 bytes"""
+    from itsxpress_amd import _lib
+    L = _lib.lib()
+    rows = _domtbl_rows()
+    pn, po = _blob([b"3_ITS2_start", b"4_ITS2_end_of_a_long_profile_name"])
+    M = np.array([61, 44], np.int32)
+    tau = np.array([-3.875, -4.25], np.float32)
+    lam = np.array([0.6953125, 0.703125], np.float32)
+    domz = np.array([3, 2], np.int64)
+    tb, to = _blob([b"target_zero", b"t1", b"X" * 1500, b"t3"])
+    path = tmp_path / "domtbl.txt"
+    rc = L.itsx_write_domtbl_arrays(os.fsencode(path), rows.ctypes.data, len(rows), 7, domz.ctypes.data, 2, pn, po.ctypes.data,
+                                    M.ctypes.data, tau.ctypes.data, lam.ctypes.data, tb, to.ctypes.data)
+    assert rc == 0, L.itsx_writers_last_error()
+    assert path.read_text() == DOMTBL_EXPECTED
