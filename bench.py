@@ -17,6 +17,10 @@ cross-shard duplicates to find; `--total-reads T` sets another total; `--weak` g
 `--workload cfg4` is BASELINE configs[4]'s per-GPU shape: 2x250-merged reads (300-480 bases), `--region ALL` profiles
 (`1_` / `4_`), greedy clustering at 0.995 (row a2) instead of exact dereplication.
 
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` if asked and prints the line.  `--full` adds every leg
+beside the headline figure, each outside `value`: the CPU baseline, the host hand-over step, one step with the kernels alone
+(the roofline then uses their alone times), the full-pipeline step, the winners' files and, at N > 1, the one-engine concordance.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -338,8 +342,15 @@ def main():
                     help="strong scaling: this many reads in total, sharded over the ranks (shards share their templates); "
                          "the default at N > 1, with the workload's own size as the total")
     ap.add_argument("--weak", action="store_true", help="N > 1: every rank its own shard of the workload's size (weak scaling)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="reads in the CPU-baseline sample (0 = skip, -1 = auto: ~20-30 s of CPU work)")
-    ap.add_argument("--handover-steps", type=int, default=1, help="steps fed from the host buffer, outside `value` (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure, each at its default: the CPU baseline, the host hand-over step, "
+                         "the kernels-alone step, the full-pipeline step, the files leg and, at N > 1, concordance_vs_single_engine.  "
+                         "Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line; a leg's own "
+                         "option given a value runs that leg either way")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="reads in the CPU-baseline sample (0 = skip, -1 = auto: ~20-30 s of CPU work; default -1 with --full, else 0)")
+    ap.add_argument("--handover-steps", type=int, default=None,
+                    help="steps fed from the host buffer, outside `value` (0 = skip; default 1 with --full, else 0)")
     ap.add_argument("--paired-pairs", type=int, default=0,
                     help="N = 1 only: after the timed steps, configs[2] as the config states it -- this many synthetic 2x250 PAIRS, R1 / R2 .fastq.gz in, "
                          "trimmed R1 / R2 .fastq.gz out, through the mirror classes in arrays mode (scripts/paired_run.py) -- reported as the extra key "
@@ -356,21 +367,24 @@ def main():
                     help="N > 1: every rank dereplicates and scores its own shard only (SURVEY 8e option 1): a sequence present in two shards is "
                          "scored twice and counted twice in domZ, so coordinates can differ from the one-GPU answer near the thresholds.  The "
                          "default is EXACT global dereplication (option 2): the result of one GPU on the whole input, read for read")
-    ap.add_argument("--concordance-reads", type=int, default=12000000,
+    ap.add_argument("--concordance-reads", type=int, default=None,
                     help="N > 1: rank 0 re-runs the whole job on ONE engine after the timed steps and compares every coordinate for equality "
-                         "(`concordance_vs_single_engine`) when the job has at most this many reads (0 = skip)")
+                         "(`concordance_vs_single_engine`) when the job has at most this many reads (0 = skip; default 12000000 with --full, else 0)")
     ap.add_argument("--rows", choices=["lazy", "compact", "full"], default="lazy",
                     help="what the search keeps of the domain table (itsx_set_rows_mode): lazy = pairs that cannot win ItsPosition's argmax "
                          "are not evaluated past their Forward score (the default: the step asks for coordinates, not for domtbl.txt); compact = "
                          "every pair evaluated, only the rows that can still win kept; full = every row resident (66 GB at 10 M reads)")
     ap.add_argument("--full-rows", action="store_true", help="= --rows full")
-    ap.add_argument("--alone-steps", type=int, default=1, help="1: one extra step with ITSX_MSV_OVERLAP=0 for the kernels' alone times (0 = skip)")
-    ap.add_argument("--full-steps", type=int, default=1,
+    ap.add_argument("--alone-steps", type=int, default=None,
+                    help="1: one extra step with ITSX_MSV_OVERLAP=0 for the kernels' alone times (0 = skip; default 1 with --full, else 0)")
+    ap.add_argument("--full-steps", type=int, default=None,
                     help="with --rows lazy: this many extra steps with every pair evaluated (--rows compact), after the timed ones and outside "
-                         "`value`: `full_pipeline_value`, and the lazy coordinates are compared with them for equality (0 = skip)")
-    ap.add_argument("--files-leg", type=int, default=1,
+                         "`value`: `full_pipeline_value`, and the lazy coordinates are compared with them for equality (0 = skip; default 1 "
+                         "with --full, else 0)")
+    ap.add_argument("--files-leg", type=int, default=None,
                     help="N = 1, --rows lazy: after the timed steps the job's uc.txt, rep.fa and the winners' domtbl.txt are written once (what "
-                         "ITSXPRESS_DOMTBL=winners hands the reference's own parsers), outside `value`: `winners_files` (0 = skip)")
+                         "ITSXPRESS_DOMTBL=winners hands the reference's own parsers), outside `value`: `winners_files` (0 = skip; default 1 "
+                         "with --full, else 0)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the per-read coordinates the last timed step returned to DIR/<name>.npy "
                          "(float64; a fixed seeded sample of %d reads when the job has more)" % DUMP_MAX_READS)
@@ -378,6 +392,11 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    # the legs beside the headline figure: each at its default with --full, none in a plain run, an explicit value honoured either way
+    for name, default in (("cpu_sample", -1), ("handover_steps", 1), ("alone_steps", 1), ("full_steps", 1), ("files_leg", 1),
+                          ("concordance_reads", 12000000)):
+        if getattr(args, name) is None:
+            setattr(args, name, default if args.full else 0)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -971,7 +990,9 @@ def main():
         if use_dist and out is not None and args.cluster_id >= 1.0:
             tot = int(total_local)
             room = args.budget_s - (time.time() - T_START)
-            if not args.concordance_reads or tot > args.concordance_reads:
+            if not args.concordance_reads:
+                res["concordance_vs_single_engine"] = {"skipped": "not asked for (--full or --concordance-reads)"}
+            elif tot > args.concordance_reads:
                 res["concordance_vs_single_engine"] = {"skipped": "the job has %d reads, --concordance-reads is %d" % (tot, args.concordance_reads)}
             elif room < 40.0 + 6.0 * dt / max(args.steps, 1) * world:
                 res["concordance_vs_single_engine"] = {"skipped": "wall-clock budget (--budget-s %.0f): %.0f s left" % (args.budget_s, room)}

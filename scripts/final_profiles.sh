@@ -4,7 +4,7 @@ set -o pipefail
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/final; mkdir -p $out
 lean="--cpu-sample 0 --handover-steps 0 --full-steps 0 --files-leg 0"
-echo "[final] default bench"; python bench.py > $out/bench_default_line.json 2> $out/bench_default.err || { echo FAILED default; tail -5 $out/bench_default.err; }
+echo "[final] default bench"; python bench.py --full > $out/bench_default_line.json 2> $out/bench_default.err || { echo FAILED default; tail -5 $out/bench_default.err; }
 echo "[final] kernel stats"; rm -rf $out/stats
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 1 --warmup 1 $lean --alone-steps 0 > $out/bench_10M_profiled_line.json 2> $out/stats.err
 f=$(find $out/stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $out/bench_10M_kernel_stats.csv; rm -rf $out/stats

@@ -126,7 +126,7 @@ def test_bench_runs_its_n_rank_path_with_two_ranks_on_one_gpu():
     env.update(ITSX_BENCH_ONE_GPU="1", ITSX_BENCH_BACKEND="gloo")
     for extra in (["--reads", "40000", "--per-shard-derep"], ["--total-reads", "80000"]):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "cfg1", "--steps", "1", "--warmup", "1",
-                            "--cpu-sample", "0", "--handover-steps", "0"] + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                            "--full", "--cpu-sample", "0", "--handover-steps", "0"] + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
         assert p.returncode == 0, p.stderr.decode()[-2000:]
         lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
         assert len(lines) == 1
@@ -151,7 +151,7 @@ def test_every_collective_over_rccl_with_one_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "ITSX_BENCH_BACKEND", "ITSX_BENCH_ONE_GPU")}
     env.update(ITSX_FORCE_DIST="1", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "cfg1", "--reads", "60000", "--steps", "1", "--warmup", "1",
-                        "--cpu-sample", "0", "--handover-steps", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--full", "--cpu-sample", "0", "--handover-steps", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     rec = json.loads([ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")][0])
     assert rec["n_gpus"] == 1 and rec["ranks"] is not None and rec["ranks"]["allreduce_ms_per_step_max"] > 0
