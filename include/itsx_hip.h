@@ -315,6 +315,11 @@ int itsx_derep(itsx_ctx *ctx, int strand_both, int minseqlength, int64_t *n_uniq
  * fixture for it).  id == 1.0 is exact dereplication (itsx_derep), which is what the reference runs at 1.0
  * (main.py:534-537).  Fills the same arrays as itsx_derep. */
 int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique);
+/* itsx_cluster with the centroid stream (the quadratic term) spread over `ctx` and n_helpers more contexts, one shard each.
+ * Same results as itsx_cluster(ctx, ...) bit for bit, whatever n_helpers and whichever devices the helpers sit on.
+ * Helpers need no reads or profiles; they are only borrowed for the call. n_helpers == 0 is itsx_cluster. id == 1.0 is
+ * itsx_derep as in itsx_cluster. */
+int itsx_cluster_multi(itsx_ctx *ctx, itsx_ctx *const *helpers, int32_t n_helpers, double id, int strand_both, int64_t *n_unique);
 /* after itsx_cluster at id < 1: pct_id[n_reads] = identity of each member with its centroid (uc column 4; -1 for
  * centroids and dropped reads), order[n_order] = kept reads in processing order (the order of uc's S/H rows). */
 int itsx_get_cluster(const itsx_ctx *ctx, double *pct_id, int64_t *order, int64_t *n_order);

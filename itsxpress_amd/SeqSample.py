@@ -61,6 +61,12 @@ def _fast_from_env():
     return os.environ.get("ITSXPRESS_ARRAYS", "").strip() not in ("", "0")
 
 
+def _cluster_gpus_from_env(world):
+    """ITSXPRESS_CLUSTER_GPUS: how many of the sample's ITSXPRESS_GPUS devices cluster it at cluster_id < 1 (default all; 1: one GPU)"""
+    v = os.environ.get("ITSXPRESS_CLUSTER_GPUS", "").strip()
+    return max(1, min(int(v), world)) if v else world
+
+
 def _winners_from_env():
     return os.environ.get("ITSXPRESS_DOMTBL", "").strip().lower() == "winners"
 
@@ -162,14 +168,35 @@ class SeqSample:
             self.rep_file = os.path.join(self.tempdir, "rep.fa")
             self._load_reads()
             cid = float(cluster_id)
-            if cid < 1.0 and (getattr(self.engine, "world", 1) > 1 or getattr(self.engine, "deferred", False)):
+            helpers = []
+            world = getattr(self.engine, "world", 1)
+            if cid < 1.0 and world > 1 and not getattr(self.engine, "deferred", False) and _cluster_gpus_from_env(world) > 1:
+                # greedy clustering is sequential per query, but the centroid stream is not: a leader on the first device runs the
+                # procedure and the others each stream a shard of the centroids (itsx_cluster_multi, the same clusters bit for bit)
+                from .multi import _devices_from_env
+                devs = _devices_from_env(world)[:_cluster_gpus_from_env(world)]
+                logging.info("cluster_id < 1: one sample clustered on devices %s (leader %d, centroid stream in %d shards)",
+                             ",".join(str(d) for d in devs), devs[0], len(devs))
+                self._engine.close()
+                self._engine = Engine(devs[0])
+                self._reads_loaded_from = None
+                self._load_reads()
+                helpers = [Engine(d) for d in devs[1:]]
+            elif cid < 1.0 and (world > 1 or getattr(self.engine, "deferred", False)):
                 # greedy clustering is sequential by definition (a query sees every centroid before it): one GPU runs it, in one piece
                 logging.warning("cluster_id < 1 does not shard over GPUs or chunks: this sample runs on one GPU (ITSXPRESS_GPUS / ITSXPRESS_STREAM ignored)")
                 self._engine.close()
                 self._engine = Engine()
                 self._reads_loaded_from = None
                 self._load_reads()
-            self.engine.cluster(cid, strand_both=True)
+            try:
+                if helpers:
+                    self.engine.cluster(cid, strand_both=True, helpers=helpers)
+                else:
+                    self.engine.cluster(cid, strand_both=True)
+            finally:
+                for h in helpers:
+                    h.close()
             if self._is_fast():
                 self.uc_file = EngineTable(self.uc_file, self.engine, "uc")
             else:

@@ -64,7 +64,7 @@ STATS_DTYPE = np.dtype(STATS_FIELDS, align=True)
 EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy", "itsx_load_profiles_file",
            "itsx_load_profiles_mem", "itsx_profile_name", "itsx_profile_tables", "itsx_set_reads", "itsx_set_reads_view", "itsx_set_reads_device", "itsx_domz_device", "itsx_trim_coords_device",
            "itsx_rep_coords_device", "itsx_derep_device", "itsx_unique_keys128_device",
-           "itsx_load_reads_file", "itsx_derep", "itsx_cluster", "itsx_cluster_samples", "itsx_get_cluster", "itsx_get_derep", "itsx_unique_keys", "itsx_set_active_uniques", "itsx_get_uniques",
+           "itsx_load_reads_file", "itsx_derep", "itsx_cluster", "itsx_cluster_multi", "itsx_cluster_samples", "itsx_get_cluster", "itsx_get_derep", "itsx_unique_keys", "itsx_set_active_uniques", "itsx_get_uniques",
            "itsx_search", "itsx_get_domz", "itsx_set_domz", "itsx_search_finalize", "itsx_num_domains",
            "itsx_get_domains", "itsx_num_pairtraces", "itsx_get_pairtraces", "itsx_trim_coords",
            "itsx_rep_coords", "itsx_write_uc", "itsx_write_rep_fasta", "itsx_write_domtbl", "itsx_get_stats", "itsx_switches", "itsx_switch_registry", "itsx_release_scratch",
@@ -152,6 +152,7 @@ def lib():
         "itsx_get_unique_seqs": (i32, [vp, vp, i64, vp]),
         "itsx_derep": (i32, [vp, i32, i32, vp]),
         "itsx_cluster": (i32, [vp, f64, i32, vp]),
+        "itsx_cluster_multi": (i32, [vp, vp, i32, f64, i32, vp]),
         "itsx_cluster_samples": (i32, [vp, f64, i32, vp]),
         "itsx_get_cluster": (i32, [vp, vp, vp, vp]),
         "itsx_merge_buffers": (i32, [vp, cp, cp, vp, cp, cp, vp, i64, i32, f64, i32, vp, vp, vp, vp, vp, vp]),

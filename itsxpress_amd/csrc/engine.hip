@@ -25,6 +25,7 @@
 #include "detmath.h"
 #include "engine.h"
 #include "k_api.h"
+#include "cluster_multi.h"
 #include "fastq_io.h"
 #include "writers.h"
 
@@ -1357,7 +1358,8 @@ static void dust_host(const uint8_t *codes, int64_t L, std::vector<uint8_t> &mas
 
 // a2: greedy centroid clustering (k_cluster.hip explains the speculative windows).  batched: every sample of the batch is
 // clustered as a run of that sample alone, the samples' windows advancing side by side as the segments of shared windows.
-static int cluster_run(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique, bool batched)
+// shards (itsx_cluster_multi): the mode-1 centroid stream is spread over the leader and helper contexts (cluster_multi.hip).
+static int cluster_run(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique, bool batched, ClusterShards *shards = nullptr)
 {
   HIPCHK(hipSetDevice(ctx->device));
   const int64_t n = ctx->N;
@@ -1444,6 +1446,7 @@ static int cluster_run(itsx_ctx *ctx, double id, int strand_both, int64_t *n_uni
   pool_cap = std::max<int64_t>(pool_cap, (int64_t)Bmax * kcap);
   HIPCHK(cw_pool->alloc((size_t)pool_cap, true));
   int64_t pool_used = 0;
+  struct ShardGuard { ClusterShards *s; ~ShardGuard() { if (s) s->sync(); } } shard_guard{shards};   // (no helper copy outlives the buffers above)
 
   ClusterArgs a{};
   a.rd = ctx->rd; a.order = d_order.p; a.strand_both = strand_both ? 1 : 0; a.dmask = (use_dust && n > 0) ? dmask.p : nullptr;
@@ -1466,6 +1469,10 @@ static int cluster_run(itsx_ctx *ctx, double id, int strand_both, int64_t *n_uni
   a.pre_k = std::min(16, (int)((double)Lmax * (1.0 - id) / id) + 1); a.ctab_key = ctab_key.p; a.ctab_val = ctab_val.p; a.rhash = ctx->w_hf.p;
   a.scratch = scratch.p; a.scratch_pitch = scratch_pitch;
   a.thr = 100.0 * id; a.n_align = n_align.p;
+  if (shards) {
+    ClusterArgs ai = a; ai.ccap = cand_cap;
+    if (shards->init(ai, (int32_t)nqs, nk, pool_cap) != hipSuccess) SET_ERR(ctx, ITSX_E_DEVICE, "clustering shards: " + shards->error());
+  }
 
   // per sample: queries done f, centroid columns C, adaptive segment size B (start 256, double after an uncut segment,
   // max(64, 2 cut) after a cut).  A window takes a segment of every unfinished sample in sample order until it holds Bmax queries.
@@ -1509,6 +1516,9 @@ static int cluster_run(itsx_ctx *ctx, double id, int strand_both, int64_t *n_uni
     launch_cl_kmers(a, ctx->st);
     // every centroid streams past the window's query index; a strand keeps the candidates that can still be among its 32 best
     launch_cl_qindex(a, scan_tmp.p, ctx->st);
+    if (shards) {                                              // each shard streams its own columns; their lists meet on the leader
+      if (shards->stream(a, stream_launches) != hipSuccess) SET_ERR(ctx, ITSX_E_DEVICE, "clustering shards: " + shards->error());
+    } else
     for (int c0 = 0, step = 2048; c0 < Ctot; step = std::min(step * 2, 1 << 20)) {
       const int c1 = std::min(Ctot, c0 + step);
       launch_cl_stream(a, c0, c1, 1, ctx->st);
@@ -1541,6 +1551,7 @@ static int cluster_run(itsx_ctx *ctx, double id, int strand_both, int64_t *n_uni
     launch_cl_stream(a, 0, nq, 2, ctx->st);                   // the window's speculative centroids against their segments' strands
     launch_cl_validate(a, rows_per_lane, ctx->st);
     launch_cl_columns(a, 1, ctx->st);                         // roll back the speculative centroids that did not survive
+    if (shards && shards->fetch_columns(a, cs[0]) != hipSuccess) SET_ERR(ctx, ITSX_E_DEVICE, "clustering shards: " + shards->error());
     int32_t overflow = 0;
     wo.assign(3 * (size_t)G + 1, 0);
     HIPCHK(hipMemcpyAsync(wo.data(), wout.p, wo.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
@@ -1578,7 +1589,9 @@ static int cluster_run(itsx_ctx *ctx, double id, int strand_both, int64_t *n_uni
     }
     windows++; cuts += any_cut;
     pool_used += wo[3 * (size_t)G];                           // (the words of the last segment's rolled-back tail are taken again)
+    if (shards && shards->adopt(a, cs[0], wo[(size_t)G]) != hipSuccess) SET_ERR(ctx, ITSX_E_DEVICE, "clustering shards: " + shards->error());
   }
+  if (debug && shards) fprintf(stderr, "%s", shards->debug_line(windows).c_str());
   if (debug) fprintf(stderr, "[cluster] %lld windows, %lld stream launches, %lld regrown candidate lists, word pool %.1f MB\n", (long long)windows, (long long)stream_launches, (long long)regrown, pool_used * 2.0 / 1e6);
 
   HIPCHK(ctx->d_rep_of.alloc((size_t)n + 1)); HIPCHK(ctx->d_strand.alloc((size_t)n + 1)); HIPCHK(ctx->d_uniq_of.alloc((size_t)n + 1));
@@ -1621,6 +1634,25 @@ int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
   if (id == 1.0) return itsx_derep(ctx, strand_both, 32, n_unique);      // main.py:534-537 never clusters at 1.0
   if (ctx->S > 1) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "greedy clustering (id < 1) is sequential per sample: run it one sample per call, not on a sample batch");
   return cluster_run(ctx, id, strand_both, n_unique, false);
+}
+int itsx_cluster_multi(itsx_ctx *ctx, itsx_ctx *const *helpers, int32_t n_helpers, double id, int strand_both, int64_t *n_unique)
+{
+  CTXCHK(ctx);
+  if (n_helpers < 0 || (n_helpers > 0 && !helpers)) SET_ERR(ctx, ITSX_E_ARG, "itsx_cluster_multi: helpers is NULL or n_helpers is negative");
+  std::vector<ClusterShards::Helper> hs;
+  for (int32_t h = 0; h < n_helpers; h++) {
+    if (!helpers[h]) SET_ERR(ctx, ITSX_E_ARG, "itsx_cluster_multi: helper " + std::to_string(h) + " is NULL");
+    if (helpers[h] == ctx) SET_ERR(ctx, ITSX_E_ARG, "itsx_cluster_multi: a helper is the leader context itself");
+    for (int32_t g = 0; g < h; g++)
+      if (helpers[g] == helpers[h]) SET_ERR(ctx, ITSX_E_ARG, "itsx_cluster_multi: helper " + std::to_string(h) + " appears twice");
+    hs.push_back(ClusterShards::Helper{helpers[h]->device, helpers[h]->st});
+  }
+  if (n_helpers == 0) return itsx_cluster(ctx, id, strand_both, n_unique);
+  if (!(id > 0.0 && id <= 1.0)) SET_ERR(ctx, ITSX_E_ARG, "cluster id must be in (0, 1]");
+  if (id == 1.0) return itsx_derep(ctx, strand_both, 32, n_unique);      // as itsx_cluster
+  if (ctx->S > 1) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "greedy clustering (id < 1) is sequential per sample: run it one sample per call, not on a sample batch");
+  ClusterShards shards(ctx->device, ctx->st, hs);
+  return cluster_run(ctx, id, strand_both, n_unique, false, &shards);
 }
 int itsx_cluster_samples(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
 {

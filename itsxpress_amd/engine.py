@@ -198,9 +198,16 @@ class Engine:
         self.n_unique = n.value
         return n.value
 
-    def cluster(self, cluster_id, strand_both=True):
+    def cluster(self, cluster_id, strand_both=True, helpers=None):
+        """Greedy clustering (itsx_cluster).  helpers: other Engines (no reads needed, any devices) that each take a shard of the
+        centroid stream for this call (itsx_cluster_multi); the result is the same bit for bit.  None or empty: itsx_cluster."""
         n = C.c_int64(0)
-        self._chk(self.L.itsx_cluster(self.h, float(cluster_id), int(strand_both), C.byref(n)))
+        if helpers:
+            hs = list(helpers)
+            arr = (C.c_void_p * len(hs))(*[h.h for h in hs])
+            self._chk(self.L.itsx_cluster_multi(self.h, arr, len(hs), float(cluster_id), int(strand_both), C.byref(n)))
+        else:
+            self._chk(self.L.itsx_cluster(self.h, float(cluster_id), int(strand_both), C.byref(n)))
         self.n_unique = n.value
         return n.value
 

@@ -15,6 +15,7 @@ PY_SWITCHES = [
     ("ITSXPRESS_GPU", "mode", "device ordinal of a one-GPU engine (default 0)"),
     ("ITSXPRESS_GPUS", "mode", "N > 1: one sample over N worker processes, one GPU each (multi.py); outputs byte-identical to one GPU's"),
     ("ITSXPRESS_GPU_IDS", "mode", "comma-separated device ordinals for ITSXPRESS_GPUS"),
+    ("ITSXPRESS_CLUSTER_GPUS", "mode", "how many of the ITSXPRESS_GPUS devices cluster one sample at cluster_id < 1 (default all: itsx_cluster_multi, same clusters; 1: one GPU)"),
     ("ITSXPRESS_ARRAYS", "mode", "=1: arrays instead of uc.txt / rep.fa / domtbl.txt between the stages, lazy rows mode (same trimmed reads)"),
     ("ITSXPRESS_DOMTBL", "mode", "=winners: files as ever, the lazy search behind them; domtbl.txt holds per target and side the row ItsPosition.parse ends up with (same dictionary, same trimmed reads)"),
     ("ITSXPRESS_STREAM", "mode", "=1 / 0: streamed file-order chunks on / off (default: by input size, ITSX_STREAM_AUTO_MB)"),
