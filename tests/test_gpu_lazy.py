@@ -10,6 +10,7 @@ import pytest
 
 import orc
 import synth
+from edge_cases import _ccs_reads, _without_match_to_delete
 from test_gpu_compact import PAIRS, _same, _weak
 from test_gpu_parity import _its2_subset
 
@@ -243,33 +244,6 @@ def test_bound_kernel_agrees_with_the_forward_parser(engine, t_hmm_text, mini_hm
         assert 0.0 <= st["lazy_bound_maxdiff"] < 1e-3, st["lazy_bound_maxdiff"]
 
 
-def _ccs_reads(t_hmm_text, rng, lengths, per_family=6):
-    """CCS-shaped targets (--trim-ccs inputs, itsxpress/SeqSample.py:48-91): kilobases of random sequence with full and PARTIAL copies of
-    a left and a right motif in tandem, a few error variants of each"""
-    acgt = np.frombuffer(b"ACGT", np.uint8)
-    lm = [m for m in synth.consensus_motifs(t_hmm_text, "3_") if len(m) == 45]
-    rm = [m for m in synth.consensus_motifs(t_hmm_text, "4_") if len(m) == 45]
-    seqs = []
-    for L in lengths:
-        base = acgt[rng.integers(0, 4, L)].copy()
-        a = int(rng.integers(50, 400))
-        while a + 400 < L:
-            l, r = lm[int(rng.integers(0, len(lm)))], rm[int(rng.integers(0, len(rm)))]
-            cut = int(rng.integers(0, 25))                                 # a partial copy now and then
-            base[a:a + 45 - cut] = np.frombuffer(l.encode(), np.uint8)[cut:]
-            b = a + 45 + int(rng.integers(100, 260))
-            base[b:b + 45] = np.frombuffer(r.encode(), np.uint8)
-            a = b + 45 + int(rng.integers(200, 3000))
-        for j in range(per_family):
-            v = base.copy()
-            for pos in rng.integers(0, L, 1 + j):
-                v[pos] = acgt[(np.searchsorted(acgt, v[pos]) + 1 + rng.integers(0, 3)) % 4]
-            if j == per_family - 1:
-                v[int(rng.integers(0, L))] = ord("N")
-            seqs.append(bytes(v).decode())
-    return seqs
-
-
 def test_lazy_equals_the_full_table_on_ccs_length_reads(engine, t_hmm_text, monkeypatch):
     """2-20 kb targets with tandem partial copies and one target at the engine's limit of 65 535 residues: the bound kernel stays within
     half the margin of HMMER's own Forward (the margin grows with the length: engine.hip, lazy_c), and the lazy coordinates are the full
@@ -293,25 +267,6 @@ def test_lazy_equals_the_full_table_on_ccs_length_reads(engine, t_hmm_text, monk
     # the same bound on the 2-20 kb targets alone (what the 0.02-bit margin has to cover)
     _, st = _coords(engine, hmm, seqs[:-2], "lazy")
     assert 0.0 <= st["lazy_bound_maxdiff"] < 0.5 * margin_nats(20000), st["lazy_bound_maxdiff"]
-
-
-def _without_match_to_delete(hmm_text, node, value="*"):
-    """the profiles of `hmm_text` with t(M_node -> D_node+1) = 0 ('*'; or exp(-value)) -- the delete path past that node lives on D -> D alone"""
-    out, k = [], None
-    for ln in hmm_text.split("\n"):
-        f = ln.split()
-        if ln.startswith("HMM "):
-            k = 0
-        elif k is not None and len(f) >= 5 and f[0].isdigit():
-            k = int(f[0])
-        elif k == node and len(f) == 7 and f[6] != "*" and not ln.lstrip().startswith("1.38629  1.38629"):
-            f[2] = value
-            ln = "          " + "  ".join("%7s" % x for x in f)
-            k = None
-        if ln.startswith("//"):
-            k = None
-        out.append(ln)
-    return "\n".join(out)
 
 
 def test_bound_kernel_folded_and_plain_recurrences(engine, t_hmm_text, monkeypatch):

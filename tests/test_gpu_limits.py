@@ -5,30 +5,10 @@ import pytest
 
 import orc
 import synth
+from edge_cases import _stretch
 from test_gpu_parity import _compare, _run_both
 
 pytestmark = pytest.mark.gpu
-
-
-def _stretch(block, M_new):
-    """a profile of M_new nodes made from a 45-node HMMER3/f block: the last node is repeated (the repeats take an inner
-    node's transitions, the final node keeps the terminal ones)"""
-    lines = block.split("\n")
-    i_leng = next(k for k, ln in enumerate(lines) if ln.startswith("LENG"))
-    M = int(lines[i_leng].split()[1])
-    lines[i_leng] = "LENG  %d" % M_new
-    i_hmm = next(k for k, ln in enumerate(lines) if ln.startswith("HMM "))
-    first = i_hmm + 5                         # HMM, header, COMPO, node-0 inserts, node-0 transitions
-    node = lambda k: lines[first + 3 * (k - 1): first + 3 * k]
-    inner_t = node(M - 1)[2]
-    out = lines[:first + 3 * (M - 1)]
-    last = node(M)
-    for k in range(M, M_new + 1):
-        m = last[0].split()
-        m[0] = str(k)
-        out += ["  " + "  ".join(m), last[1], inner_t if k < M_new else last[2]]
-    out += lines[first + 3 * M:]
-    return "\n".join(out).replace("NAME  ", "NAME  ", 1)
 
 
 def test_model_of_46_nodes_runs_and_47_is_refused(engine, mini_hmm_text):
