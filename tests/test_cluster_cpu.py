@@ -8,7 +8,7 @@ import numpy as np
 
 import orc
 
-_RC = str.maketrans("ACGTN", "TGCAN")
+_RC = str.maketrans("ACGTUNRYMKSWHBVD", "TGCAANYRKMSWDVBH")         # the complement of every IUPAC set (U is T)
 _IUPAC = {"A": 1, "C": 2, "G": 4, "T": 8, "U": 8, "R": 5, "Y": 10, "M": 3, "K": 12, "S": 6, "W": 9, "H": 11, "B": 14,
           "V": 7, "D": 13, "N": 15}
 
@@ -87,9 +87,9 @@ def py_words(s, masked=None):
     return {s[i:i + 8] for i in range(len(s) - 7) if all(ok[i:i + 8])}
 
 
-def py_cluster(reads, names, cid, strand_both=True, minlen=32, dust=True):
+def py_cluster(reads, names, cid, strand_both=True, minlen=32, dust=True, align=py_align, maxlen=50000):
     masks = [py_dust(r) if dust else None for r in reads]
-    order = sorted((i for i in range(len(reads)) if len(reads[i]) >= minlen), key=lambda i: (names[i].encode(), i))
+    order = sorted((i for i in range(len(reads)) if minlen <= len(reads[i]) <= maxlen), key=lambda i: (names[i].encode(), i))
     cents = []                                      # (read index, words, position)
     rep_of = [-1] * len(reads)
     strand = [1] * len(reads)
@@ -111,7 +111,7 @@ def py_cluster(reads, names, cid, strand_both=True, minlen=32, dust=True):
             for _, _, _, ci in sorted(cands):
                 if rejects >= 32:
                     break
-                sc, m, cols = py_align(q, reads[cents[ci][0]])
+                sc, m, cols = align(q, reads[cents[ci][0]])
                 pid = 100.0 * m / cols if cols > 0 else 0.0
                 if pid >= 100.0 * cid:
                     if best is None or pid > best[1]:
