@@ -303,6 +303,21 @@ int itsx_merge_pairs_load(itsx_ctx *ctx, const char *r1_path, const char *r2_pat
 int itsx_merge_pairs_load_text(itsx_ctx *ctx, const char *text1, int64_t nbytes1, const char *text2, int64_t nbytes2, int maxdiffs, double maxee, int allow_stagger,
                                int64_t *n_pairs, int64_t *n_merged);
 int itsx_merge_pair_index(const itsx_ctx *ctx, int32_t *index, int64_t n_pairs);
+/* f4 batching: the pairs of EVERY sample of a batch (q2_itsxpress.py:72-80 merges once per manifest row) in one call.  Sample s is
+ * r1_paths[s] / r2_paths[s] (FASTQ, plain / gzip / zstd, mixed freely; read and parsed side by side); the two must hold the same number
+ * of records (else ITSX_E_FORMAT, naming both).  All pairs go through ONE merge; the merged reads, in sample order and then pair order,
+ * become the context's read set in the state itsx_load_reads_files leaves: itsx_num_samples = n_samples, each read tied to its sample,
+ * labels = R1 identifiers up to the first blank, no dereplication or search results.  A sample may hold no records, or merge none.
+ * seq_out_paths: NULL, or per sample NULL (nothing written) or the path of that sample's merged records, byte for byte the file
+ * itsx_merge_pairs_files writes for the sample alone; merged bases and qualities leave the device only if at least one is given.
+ * n_pairs_per_sample / n_merged_per_sample: [n_samples], may be NULL.
+ * Afterwards itsx_merge_pair_index(ctx, index, total pairs) gives, for every pair of the batch in the same order (sample, then pair),
+ * the index of its merged read in the batch's read set (-1: not merged).
+ * On any error the context is left empty (no reads, one sample) and usable. */
+int itsx_merge_pairs_load_files(itsx_ctx *ctx, const char *const *r1_paths, const char *const *r2_paths,
+                                const char *const *seq_out_paths /* NULL, or entries NULL: nothing written for that sample */,
+                                int32_t n_samples, int maxdiffs, double maxee, int allow_stagger,
+                                int64_t *n_pairs_per_sample, int64_t *n_merged_per_sample);
 int itsx_merge_tables(double *q2p, double *match, double *mism, uint8_t *qsame, uint8_t *qdiff);
 
 /* ---- a1: SeqSample.deduplicate (itsxpress/SeqSample.py:93-131)
@@ -520,6 +535,9 @@ void itsx_io_cache_clear(void);
 /* ---- test hooks (parity tests only) */
 /* XXH64 of each read's packed forward / reverse-complement key, as computed on the device */
 int itsx_debug_read_hashes(itsx_ctx *ctx, uint64_t *fwd, uint64_t *rc);
+/* the sample of every read of a batch, [n_reads] each (either may be NULL): as the device kernels see it and as the host-side writers see
+ * it; all 0 when the context holds one sample */
+int itsx_debug_read_samples(itsx_ctx *ctx, int32_t *device_ids, int32_t *host_ids);
 /* packed representation of read i: words [ceil(len/16)], exception list (pos<<4|code) */
 int itsx_debug_packed_read(const itsx_ctx *ctx, int64_t i, uint32_t *words, int32_t *nwords,
                            uint32_t *exc, int32_t *nexc);

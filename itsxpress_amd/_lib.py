@@ -68,7 +68,7 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_search", "itsx_get_domz", "itsx_set_domz", "itsx_search_finalize", "itsx_num_domains",
            "itsx_get_domains", "itsx_num_pairtraces", "itsx_get_pairtraces", "itsx_trim_coords",
            "itsx_rep_coords", "itsx_write_uc", "itsx_write_rep_fasta", "itsx_write_domtbl", "itsx_get_stats", "itsx_switches", "itsx_switch_registry", "itsx_release_scratch",
-           "itsx_debug_read_hashes", "itsx_debug_packed_read", "itsx_debug_detmath", "itsx_debug_logf", "itsx_debug_dust", "itsx_debug_calibrate", "itsx_debug_issue", "itsx_shard_text", "itsx_shard_last_error", "itsx_owner_verdicts",
+           "itsx_debug_read_hashes", "itsx_debug_read_samples", "itsx_debug_packed_read", "itsx_debug_detmath", "itsx_debug_logf", "itsx_debug_dust", "itsx_debug_calibrate", "itsx_debug_issue", "itsx_shard_text", "itsx_shard_last_error", "itsx_owner_verdicts",
            "itsx_write_trimmed_fastq", "itsx_write_trimmed_paired", "itsx_trim_last_error",
            "itsx_merge_buffers", "itsx_merge_pairs_files", "itsx_merge_pairs_load", "itsx_merge_tables",
            "itsx_orient_load_db", "itsx_orient", "itsx_write_oriented_fastq",
@@ -80,7 +80,7 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_writers_last_error", "itsx_profile_params", "itsx_get_unique_seqs",
            "itsx_load_reads_text", "itsx_stream_open", "itsx_stream_next", "itsx_stream_close", "itsx_stream_last_error", "itsx_stream_records_bound",
            "itsx_stream_open_shared", "itsx_stream_open_threads", "itsx_stream_base", "itsx_stream_progress", "itsx_stream_next_records", "itsx_count_records",
-           "itsx_merge_pairs_load_text", "itsx_merge_pair_index", "itsx_twriter_set_mode", "itsx_write_range",
+           "itsx_merge_pairs_load_text", "itsx_merge_pair_index", "itsx_merge_pairs_load_files", "itsx_twriter_set_mode", "itsx_write_range",
            "itsx_keyset_create", "itsx_keyset_destroy", "itsx_keyset_size", "itsx_keyset_assign",
            "itsx_twriter_open", "itsx_twriter_text", "itsx_twriter_coords", "itsx_twriter_update", "itsx_twriter_close",
            "itsx_lazy_pending_uniques", "itsx_set_partial_coords", "itsx_set_kept_rows"]
@@ -129,6 +129,7 @@ def lib():
         "itsx_count_records": (i64, [vp, i64]),
         "itsx_merge_pairs_load_text": (i32, [vp, vp, i64, vp, i64, i32, f64, i32, vp, vp]),
         "itsx_merge_pair_index": (i32, [vp, vp, i64]),
+        "itsx_merge_pairs_load_files": (i32, [vp, vp, vp, vp, i32, i32, f64, i32, vp, vp]),
         "itsx_twriter_set_mode": (i32, [vp, i32]),
         "itsx_write_range": (i32, [cp, vp, i64]),
         "itsx_stream_last_error": (cp, []),
@@ -189,6 +190,7 @@ def lib():
         "itsx_release_scratch": (i32, [vp]),
         "itsx_switch_registry": (i64, [vp, i64]),
         "itsx_debug_read_hashes": (i32, [vp, vp, vp]),
+        "itsx_debug_read_samples": (i32, [vp, vp, vp]),
         "itsx_debug_packed_read": (i32, [vp, i64, vp, vp, vp, vp]),
         "itsx_debug_detmath": (i32, [vp, vp, i64, vp, vp]),
         "itsx_debug_logf": (i32, [vp, vp, i64, vp]),

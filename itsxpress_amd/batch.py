@@ -14,8 +14,14 @@ them -- one read set, one pass of every kernel -- while every sample keeps exact
   alone writes (tests/test_gpu_batch.py), and each `SeqSample`'s `uc_file` / `rep_file` / `dom_file` point at
   them, so the reference's `ItsPosition(...)` / `Dedup(...)` constructors and writers downstream stay as they are.
 
+Paired samples (the plugin's main case: `_set_fastqs_and_check` -> `sobj._merge_reads` once per manifest row,
+q2_itsxpress.py:72-80) join the batch UNMERGED: `merge_reads` sends the pairs of every sample through one merge kernel
+(`itsx_merge_pairs_load_files`) and leaves the merged reads of all samples on the device as the batch's read set, so
+`deduplicate` / `cluster_per_sample` go on from there without a `seq.fq` round trip; the per-sample `seq.fq` is written
+only where a consumer reads it (file-compatible mode, or `write_seq_files=True`).
+
 Nothing here computes: the grouping, the counters and the writers live behind the C ABI
-(`itsx_load_reads_files`, `itsx_set_samples`, `itsx_select_sample`; include/itsx_hip.h).
+(`itsx_load_reads_files`, `itsx_merge_pairs_load_files`, `itsx_set_samples`, `itsx_select_sample`; include/itsx_hip.h).
 """
 import logging
 import os
@@ -25,41 +31,98 @@ import numpy as np
 
 from .engine import Engine
 from ._lib import EngineError
-from .SeqSample import _REGION_PREFIX, _winners_from_env
+from .SeqSample import _REGION_PREFIX, _fast_from_env, _winners_from_env
+from .definitions import maxmismatches
 
 
 class SampleBatch:
     """Runs `deduplicate()` and `_search()` of many SeqSample objects as one engine pass.
 
-    samples: objects with `seq_file` and `tempdir` (the mirror's or the reference's SeqSample*, after
-    `_merge_reads` / `orient_reads` where those apply).  Method names and arguments follow SeqSample."""
+    samples: objects with `seq_file` and `tempdir` (the mirror's or the reference's SeqSample*, after `orient_reads` where
+    that applies), or paired samples that are not merged yet (`r1` and `fastq2` set, `seq_file` unset): those are merged
+    by `merge_reads`, all in one engine call.  Method names and arguments follow SeqSample."""
 
     def __init__(self, samples: Sequence, engine: Optional[Engine] = None, subdirs: Optional[Sequence[str]] = None) -> None:
         self.samples = list(samples)
         if not self.samples:
             raise ValueError("SampleBatch needs at least one sample")
         for s in self.samples:
-            if getattr(s, "seq_file", None) is None:
-                raise ValueError("every sample needs its seq_file before batching (merge paired reads first)")
+            paired = getattr(s, "r1", None) is not None and getattr(s, "fastq2", None) is not None
+            if getattr(s, "seq_file", None) is None and not paired:
+                raise ValueError("every sample needs its seq_file, or r1 and fastq2 for merge_reads(), before batching")
         self.engine = engine if engine is not None else Engine()
         # the plugin gives every sample the same tempdir and overwrites uc.txt / rep.fa / domtbl.txt per sample;
         # a batch holds them all at once, so each sample writes into its own sub-directory
         self.subdirs = list(subdirs) if subdirs is not None else ["sample_%04d" % i for i in range(len(self.samples))]
         self.counts: Optional[np.ndarray] = None       # reads per sample
         self.first: Optional[np.ndarray] = None        # index of each sample's first read in the batch
+        self.n_pairs: Optional[np.ndarray] = None      # after merge_reads: read pairs per sample
+        self._merged_into = None                       # the seq_files whose reads merge_reads left resident in the engine,
+        self._merged_read_set = None                   # and the engine's read-set number at that moment (the engine may be shared)
+        self._seq_written = False                      # whether merge_reads wrote them
 
     def _dir(self, i: int) -> str:
         d = os.path.join(self.samples[i].tempdir, self.subdirs[i])
         os.makedirs(d, exist_ok=True)
         return d
 
+    def _set_counts(self, counts) -> None:
+        self.counts = np.asarray(counts, np.int64)
+        self.first = np.concatenate([[0], np.cumsum(self.counts)[:-1]]).astype(np.int64)
+
+    def _load_reads(self) -> None:
+        """every sample's seq_file as one read set -- unless merge_reads left exactly these reads in the engine
+        (SeqSample._reads_loaded_from for a batch)"""
+        files = tuple(s.seq_file for s in self.samples)
+        if self._merged_into is not None and self._merged_into == files:
+            if getattr(self.engine, "read_set", None) == self._merged_read_set:
+                return
+            # something else loaded reads into the shared engine since: the merged reads are gone
+            if not all(self._seq_written and os.path.exists(f) for f in files):
+                raise EngineError(-1, "the engine no longer holds this batch's merged reads (another read set was loaded into it) and their "
+                                      "seq.fq files were not written: call merge_reads() again")
+        if any(f is None for f in files):
+            raise EngineError(-1, "the batch holds paired samples that were never merged: call merge_reads() before deduplicate() / cluster_per_sample()")
+        self._merged_into = None
+        self._set_counts(self.engine.load_reads_files(list(files)))
+
+    # -- f2 for all samples ------------------------------------------------------------------
+    def merge_reads(self, threads: Union[int, str] = 1, stagger: bool = False, write_seq_files: Optional[bool] = None) -> None:
+        """`_merge_reads` of every (paired) sample (SeqSample.py:266-365) in one engine call: one merge kernel over the pairs of all
+        samples, the merged reads left on the device as the batch's read set.  Every sample's `seq_file` becomes
+        `<its batch subdir>/seq.fq`; the file is written when write_seq_files is true (default: yes in file-compatible mode, no
+        with ITSXPRESS_ARRAYS=1), byte for byte what the sample's own `_merge_reads` writes."""
+        try:
+            for s in self.samples:
+                if getattr(s, "r1", None) is None or getattr(s, "fastq2", None) is None:
+                    raise ValueError("Both r1 and fastq2 paths must be defined to merge reads.")
+            eng = self.engine
+            write = (not _fast_from_env()) if write_seq_files is None else bool(write_seq_files)
+            seq_files = [os.path.join(self._dir(i), "seq.fq") for i in range(len(self.samples))]
+            self._merged_into = None
+            n, m = eng.merge_pairs_load_files([s.r1 for s in self.samples], [s.fastq2 for s in self.samples], seq_files if write else None,
+                                              maxdiffs=maxmismatches, maxee=2.0, allow_stagger=bool(stagger))
+            for s, f in zip(self.samples, seq_files):
+                s.seq_file = f
+            self.n_pairs = np.asarray(n, np.int64)
+            self._set_counts(m)
+            self._merged_into = tuple(seq_files)
+            self._merged_read_set = getattr(eng, "read_set", None)
+            self._seq_written = write
+            logging.info("itsx_hip batch merge: %d samples, %d pairs, %d merged", len(self.samples), int(self.n_pairs.sum()), int(self.counts.sum()))
+        except EngineError as e:
+            logging.exception("Could not perform read merging with the HIP engine: %s", e)
+            raise e
+        except FileNotFoundError as f:
+            logging.error("The HIP engine or its input was not found")
+            raise f
+
     # -- a1 for all samples ------------------------------------------------------------------
     def deduplicate(self, threads: Union[int, str] = 1) -> None:
         """`vsearch --fastx_uniques ... --strand both` of every sample (SeqSample.py:93-131), one device pass."""
         try:
             eng = self.engine
-            self.counts = np.asarray(eng.load_reads_files([s.seq_file for s in self.samples]), np.int64)
-            self.first = np.concatenate([[0], np.cumsum(self.counts)[:-1]]).astype(np.int64)
+            self._load_reads()
             n = eng.derep(strand_both=True, minseqlength=1)      # SeqSample.deduplicate's value (SeqSample.py:96 passes no --minseqlength; the mirror uses 1): a batch and a solo run must agree on short reads
             for i, s in enumerate(self.samples):
                 d = self._dir(i)
@@ -90,8 +153,7 @@ class SampleBatch:
         byte-identical to those of its own run (itsx_cluster_samples)."""
         try:
             eng = self.engine
-            self.counts = np.asarray(eng.load_reads_files([s.seq_file for s in self.samples]), np.int64)
-            self.first = np.concatenate([[0], np.cumsum(self.counts)[:-1]]).astype(np.int64)
+            self._load_reads()
             n = eng.cluster_samples(float(cluster_id), strand_both=True)
             for i, s in enumerate(self.samples):
                 d = self._dir(i)
@@ -150,4 +212,43 @@ class SampleBatch:
         for i in range(len(self.samples)):
             lo, hi = int(self.first[i]), int(self.first[i] + self.counts[i])
             out.append(tuple(x[lo:hi] for x in a))
+        return out
+
+    # -- the consumers of the coordinates, per sample -------------------------------------------
+    def _sample_range(self, i: int):
+        return int(self.first[i]), int(self.first[i] + self.counts[i])
+
+    def write_paired_trimmed(self, outfiles1: Sequence[str], outfiles2: Sequence[str], region: str, gzipped: bool = False,
+                             zstd_file: bool = False, trim_ccs: bool = False) -> List[int]:
+        """`Dedup.create_paired_trimmed_seqs` of every sample from the batch's arrays: the ORIGINAL r1 / fastq2 records of sample i,
+        sliced with its merged reads' coordinates, into outfiles1[i] / outfiles2[i].  Returns the pairs written per sample."""
+        from .trim import write_trimmed_paired
+        left, right = _REGION_PREFIX[region]
+        start, stop, tlen, _ = self.engine.trim_coords(left, right)
+        blob, offs = self.engine.read_names_raw()
+        out = []
+        for i, s in enumerate(self.samples):
+            if getattr(s, "r1", None) is None or getattr(s, "fastq2", None) is None:
+                raise ValueError("Both fastq and fastq2 paths must be defined to create paired trimmed sequences.")
+            lo, hi = self._sample_range(i)
+            names = (blob[int(offs[lo]):int(offs[hi])], offs[lo:hi + 1] - offs[lo])
+            out.append(write_trimmed_paired(s.r1, s.fastq2, outfiles1[i], outfiles2[i], names, start[lo:hi], stop[lo:hi], tlen[lo:hi],
+                                            gzipped=gzipped, trim_ccs=trim_ccs, zstd_file=zstd_file))
+        return out
+
+    def write_trimmed(self, outfiles: Sequence[str], region: str, gzipped: bool = False, zstd_file: bool = False,
+                      trim_ccs: bool = False) -> List[tuple]:
+        """`Dedup.create_trimmed_seqs` of every sample from the batch's arrays: record k of sample i's seq_file trimmed to its
+        coordinates, into outfiles[i].  A paired sample's seq_file is its merged reads: merge_reads must have written it."""
+        from .trim import write_trimmed_fastq
+        for s in self.samples:
+            if self._merged_into is not None and s.seq_file in self._merged_into and not (self._seq_written and os.path.exists(s.seq_file)):
+                raise EngineError(-1, "write_trimmed: the merged reads of this batch were never written (%s); "
+                                      "call merge_reads(write_seq_files=True)" % s.seq_file)
+        left, right = _REGION_PREFIX[region]
+        start, stop, _, _ = self.engine.trim_coords(left, right)
+        out = []
+        for i, s in enumerate(self.samples):
+            lo, hi = self._sample_range(i)
+            out.append(write_trimmed_fastq(s.seq_file, outfiles[i], start[lo:hi], stop[lo:hi], gzipped=gzipped, trim_ccs=trim_ccs, zstd_file=zstd_file))
         return out

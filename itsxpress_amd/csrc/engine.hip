@@ -327,6 +327,7 @@ struct itsx_ctx {
   itsx_io::Text h_bases;                 // original text (rep.fa keeps the input's case); not zero-filled when it grows
   const char *bases_view = "";           // = h_bases.data(), or the caller's buffer after itsx_set_reads_view
   const uint8_t *dev_bases = nullptr;    // after itsx_set_reads_device: the caller's device buffer (bases_view is fetched on demand)
+  DBuf<uint8_t> d_merged_text;           // after a merge-and-load: the gathered text dev_bases points at, kept until the host has fetched it or the next read set
   static constexpr int NSTAGE = 3;       // pinned / device staging of the hand-over (pack_and_upload)
   void *stage_pin[NSTAGE] = {nullptr, nullptr, nullptr}; DBuf<uint8_t> stage_dev[NSTAGE]; hipEvent_t stage_ev[NSTAGE] = {nullptr, nullptr, nullptr}; size_t stage_cap = 0;
   DBuf<int64_t> w_pk_off; DBuf<int8_t> w_pk_lut; DBuf<int32_t> w_pk_excnt, w_pk_exstart, w_pk_tmp; DBuf<long long> w_pk_bad;
@@ -830,6 +831,7 @@ static int pack_and_upload(itsx_ctx *ctx, const char *view = nullptr, const uint
   const auto tp0 = std::chrono::steady_clock::now();
   const int64_t n = ctx->N;
   ctx->dev_bases = dev_raw;
+  if (ctx->d_merged_text.p && dev_raw != ctx->d_merged_text.p) ctx->d_merged_text.release();      // the last merge's text: this read set is another
   ctx->bases_view = dev_raw ? nullptr : (view ? view : ctx->h_bases.data());
   const char *bases = ctx->bases_view;
   ctx->h_len.resize((size_t)n); ctx->h_woff.resize((size_t)n + 1);
@@ -1188,6 +1190,22 @@ int itsx_set_samples(itsx_ctx *ctx, const int32_t *sample_of_read, int32_t n_sam
   return ITSX_OK;
 }
 int itsx_num_samples(const itsx_ctx *ctx) { return ctx ? ctx->S : ITSX_E_ARG; }
+// test hook: every read's sample as the kernels see it (d_sample) and as the writers see it (h_sample)
+int itsx_debug_read_samples(itsx_ctx *ctx, int32_t *device_ids, int32_t *host_ids)
+{
+  CTXCHK(ctx);
+  const size_t n = (size_t)ctx->N;
+  if (ctx->S <= 1) {
+    if (device_ids) std::fill(device_ids, device_ids + n, 0);
+    if (host_ids) std::fill(host_ids, host_ids + n, 0);
+    return ITSX_OK;
+  }
+  if (ctx->h_sample.size() != n || ctx->d_sample.n < n) SET_ERR(ctx, ITSX_E_ARG, "the batch's sample vectors do not cover its reads");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (device_ids && n) { HIPCHK(hipMemcpyAsync(device_ids, ctx->d_sample.p, n * 4, hipMemcpyDeviceToHost, ctx->st)); HIPCHK(hipStreamSynchronize(ctx->st)); }
+  if (host_ids && n) memcpy(host_ids, ctx->h_sample.data(), n * 4);
+  return ITSX_OK;
+}
 int itsx_select_sample(itsx_ctx *ctx, int32_t sample)
 {
   CTXCHK(ctx);
@@ -3931,13 +3949,17 @@ int itsx_merge_tables(double *q2p, double *match, double *mism, uint8_t *qsame, 
   return ITSX_OK;
 }
 
-// keep_os (may be null): the merged bases stay in device memory (taken over by *keep_os; pair i's at foff[i] + roff[i]) and are not copied
-// back -- itsx_merge_pairs_load packs them where they are
+// what the merge kernel read and wrote, kept in device memory for the compaction that follows it (merge_load_core)
+struct MergeKeep { DBuf<uint8_t> os; DBuf<int64_t> fo, ro; DBuf<int32_t> len, reason; };
+extern "C++" { template <class T> static void dbuf_swap(DBuf<T> &a, DBuf<T> &b) { std::swap(a.p, b.p); std::swap(a.n, b.n); std::swap(a.cap, b.cap); } }
+// keep (may be null): the merged bases stay in device memory (pair i's at foff[i] + roff[i]) together with the pairs' offsets, lengths
+// and reasons, all taken over by *keep; the bases are copied back only if out_seq is given -- the merge-and-load calls pack them where
+// they are
 static int merge_core(itsx_ctx *ctx, const char *fseq, const char *fqual, const int64_t *foff, const char *rseq, const char *rqual,
                       const int64_t *roff, int64_t n, int maxdiffs, double maxee, int allow_stagger,
-                      char *out_seq, char *out_qual, int32_t *out_len, int32_t *reason, double *score, int32_t *shift, DBuf<uint8_t> *keep_os)
+                      char *out_seq, char *out_qual, int32_t *out_len, int32_t *reason, double *score, int32_t *shift, MergeKeep *keep)
 {
-  CTXCHK(ctx && foff && roff && n >= 0 && out_len && reason && (n == 0 || (fseq && fqual && rseq && rqual && (keep_os || (out_seq && out_qual)))));
+  CTXCHK(ctx && foff && roff && n >= 0 && out_len && reason && (n == 0 || (fseq && fqual && rseq && rqual && (keep || (out_seq && out_qual)))));
   HIPCHK(hipSetDevice(ctx->device));
   if (n == 0) return ITSX_OK;
   const int64_t fb = foff[n], rb = roff[n];
@@ -3986,7 +4008,7 @@ static int merge_core(itsx_ctx *ctx, const char *fseq, const char *fqual, const 
   if (score) HIPCHK(hipMemcpyAsync(score, d_score.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->st));
   if (shift) HIPCHK(hipMemcpyAsync(shift, d_shift.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
   HIPCHK(hipStreamSynchronize(ctx->st));
-  if (keep_os) { std::swap(keep_os->p, d_os.p); std::swap(keep_os->n, d_os.n); std::swap(keep_os->cap, d_os.cap); }
+  if (keep) { dbuf_swap(keep->os, d_os); dbuf_swap(keep->fo, d_fo); dbuf_swap(keep->ro, d_ro); dbuf_swap(keep->len, d_len); dbuf_swap(keep->reason, d_reason); }
   return ITSX_OK;
 }
 int itsx_merge_buffers(itsx_ctx *ctx, const char *fseq, const char *fqual, const int64_t *foff, const char *rseq, const char *rqual,
@@ -4056,6 +4078,145 @@ int itsx_merge_pairs_files(itsx_ctx *ctx, const char *r1_path, const char *r2_pa
   return ITSX_OK;
 }
 
+// one side of a paired sample: a file (text == nullptr) or a record-aligned piece of its text already in memory.  No shared state: the
+// sides of one sample, and the samples of a batch, are parsed side by side
+static int parse_fastq_side(const char *path, const char *text, int64_t nb, FastxPart &sd, std::string &perr)
+{
+  std::shared_ptr<const itsx_io::Text> tp;
+  itsx_io::Text view;
+  const itsx_io::Text *t = &view;
+  if (text) view.borrow(text, (size_t)nb);
+  else { tp = slurp(path, true, perr); if (!tp) return ITSX_E_IO; t = tp.get(); }
+  if (!t->empty() && (*t)[0] != '@') { perr = std::string("malformed FASTQ record 1 in ") + path; return ITSX_E_FORMAT; }
+  const int prc = parse_fastx(*t, true, true, sd, perr);
+  if (prc != ITSX_OK) perr += std::string(" in ") + path;
+  return prc;
+}
+
+// The pairs of one sample or of a batch of samples -> merged reads as the context's read set.  f / r: the forward and the reverse reads of
+// ALL pairs (offsets over the whole batch); pairs [pstart[s], pstart[s + 1]) are sample s's and their labels are ids[s]'s.  One merge
+// kernel for all of them; what it left on the device is compacted there (k_merge.hip: k_merge_compact), gathered into a gap-free text and
+// packed.  The host walks the pairs once, for the labels, while the gather runs.  seq_out_paths (may be null, entries may be null): the
+// sample's merged records as itsx_merge_pairs_files writes them -- the only case in which merged bases and qualities come back.
+static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r, const std::vector<const NameList *> &ids, const std::vector<int64_t> &pstart,
+                           const char *const *seq_out_paths, int maxdiffs, double maxee, int allow_stagger, double parse_ms, int64_t *n_merged_per_sample)
+{
+  const int32_t S = (int32_t)pstart.size() - 1;
+  const int64_t n = pstart[(size_t)S];
+  if (S > 1 && (int64_t)S * std::max(ctx->P, 1) > (1ll << 28)) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "too many samples x profiles for one batch");
+  static const bool trace = sw_get("ITSX_TRACE_ALLOC") != nullptr;
+  const auto tm1 = std::chrono::steady_clock::now();
+  bool want_text = false;
+  if (seq_out_paths) for (int32_t s = 0; s < S; s++) want_text = want_text || seq_out_paths[s] != nullptr;
+  std::vector<int32_t> olen((size_t)n + 1), reason((size_t)n + 1);
+  std::string oseq, oqual;
+  if (want_text) { oseq.assign((size_t)(f.seq.size() + r.seq.size()) + 1, '\0'); oqual = oseq; }
+  MergeKeep k;
+  int rc = merge_core(ctx, f.seq.data(), f.qual.data(), f.off.data(), r.seq.data(), r.qual.data(), r.off.data(), n, maxdiffs, maxee, allow_stagger,
+                      want_text ? &oseq[0] : nullptr, want_text ? &oqual[0] : nullptr, olen.data(), reason.data(), nullptr, nullptr, &k);
+  if (rc != ITSX_OK) return rc;
+  const auto tm2 = std::chrono::steady_clock::now();
+  hipStream_t st = ctx->st;
+  DBuf<int64_t> d_src, d_dst, d_blk, d_tot, d_scnt, d_pstart; DBuf<int32_t> d_pidx; DBuf<uint8_t> d_cmp;
+  int64_t tot[2] = {0, 0};                               // merged reads, the bytes of their text
+  std::vector<int64_t> scnt((size_t)S, 0);               // merged reads per sample
+  if (n > 0) {
+    const int64_t nb = merge_compact_blocks(n);
+    HIPCHK(d_src.alloc((size_t)n + 1)); HIPCHK(d_dst.alloc((size_t)n + 1)); HIPCHK(d_pidx.alloc((size_t)n)); HIPCHK(d_blk.alloc((size_t)nb * 2)); HIPCHK(d_tot.alloc(2));
+    MergeCompactArgs a{};
+    a.reason = k.reason.p; a.out_len = k.len.p; a.foff = k.fo.p; a.roff = k.ro.p; a.n = n; a.n_samples = S;
+    a.blk_cnt = d_blk.p; a.blk_len = d_blk.p + nb; a.pair_index = d_pidx.p; a.srcoff = d_src.p; a.dstoff = d_dst.p;
+    if (S > 1) {
+      HIPCHK(upload(d_pstart, pstart, st)); HIPCHK(d_scnt.alloc((size_t)S)); HIPCHK(ctx->d_sample.alloc((size_t)n + 1));
+      HIPCHK(hipMemsetAsync(d_scnt.p, 0, (size_t)S * 8, st));
+      a.pair_start = d_pstart.p; a.sample = ctx->d_sample.p; a.sample_count = d_scnt.p;
+    }
+    launch_merge_compact(a, d_tot.p, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(tot, d_tot.p, sizeof(tot), hipMemcpyDeviceToHost, st));
+    if (S > 1) HIPCHK(hipMemcpyAsync(scnt.data(), d_scnt.p, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  const int64_t m = tot[0];
+  if (m >= (1ll << 31) - 64) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "more than 2^31 reads in one context");
+  if (S == 1) scnt[0] = m;
+  ctx->h_off.assign((size_t)m + 1, 0);
+  ctx->h_merge_index.assign((size_t)n, -1);              // per pair: its merged read (itsx_merge_pair_index)
+  HIPCHK(d_cmp.alloc((size_t)tot[1] + 64));
+  if (m > 0) {
+    hipLaunchKernelGGL(k_gather_reads, dim3((unsigned)std::min<int64_t>((m + 3) / 4, 65535)), dim3(256), 0, st, k.os.p, d_src.p, d_dst.p, m, d_cmp.p);
+  }
+  // the gather has only been enqueued: the labels need `reason` alone.  (The copies back go into pageable memory and would hold the host
+  // until the stream reaches them, so they are issued after the loop.)
+  ctx->h_names.clear();
+  for (int32_t s = 0; s < S; s++) {
+    const NameList &nl = *ids[(size_t)s];
+    const int64_t p0 = pstart[(size_t)s], cnt = pstart[(size_t)s + 1] - p0;
+    for (int64_t i = 0; i < cnt; i++)
+      if (reason[(size_t)(p0 + i)] == 0) ctx->h_names.emplace_back(nl.ptr((size_t)i), nl.ptr((size_t)i) + nl.len((size_t)i));
+  }
+  if (m > 0) HIPCHK(hipMemcpyAsync(ctx->h_off.data(), d_dst.p, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (n > 0) HIPCHK(hipMemcpyAsync(ctx->h_merge_index.data(), d_pidx.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  if ((int64_t)ctx->h_names.size() != m) SET_ERR(ctx, ITSX_E_DEVICE, "the merged pairs counted on the device and on the host differ");
+  ctx->N = m;
+  itsx_io::Text().swap(ctx->h_bases);
+  static const uint8_t none = 0;
+  // rep.fa and the seeds' sequences fetch the text from dev_bases later (host_bases): the context owns it from here on
+  ctx->d_merged_text.release();
+  dbuf_swap(ctx->d_merged_text, d_cmp);
+  rc = pack_and_upload(ctx, nullptr, m > 0 ? ctx->d_merged_text.p : &none);
+  if (rc != ITSX_OK) return rc;
+  if (S > 1) {                                           // the state itsx_load_reads_files + itsx_set_samples leave (d_sample is filled already)
+    ctx->h_sample.resize((size_t)m);
+    int64_t at = 0;
+    for (int32_t s = 0; s < S; s++) { std::fill(ctx->h_sample.begin() + at, ctx->h_sample.begin() + at + scnt[(size_t)s], s); at += scnt[(size_t)s]; }
+    if (at != m) SET_ERR(ctx, ITSX_E_DEVICE, "the merged pairs counted per sample do not add up");
+    ctx->S = S;
+  }
+  const auto tm3 = std::chrono::steady_clock::now();
+  if (want_text) {
+    // seq.fq is read back by the reference's Dedup and by the single-file trimmer: written through the block writer, which also leaves
+    // its text in the reader's cache.  One file per sample, several at a time
+    std::vector<int32_t> todo;
+    for (int32_t s = 0; s < S; s++) if (seq_out_paths[s]) todo.push_back(s);
+    const int T = std::max(1, std::min<int>({itsx_io::io_threads(), 16, (int)todo.size()}));
+    std::vector<std::string> werrs((size_t)T);
+    std::atomic<size_t> next{0};
+    on_threads(T, [&](int t) {
+      itsx_io::IoThreadCap share(16 / T);                // the block writers' own pools: 16 threads in all
+      for (;;) {
+        const size_t q = next.fetch_add(1);
+        if (q >= todo.size()) break;
+        const int32_t s = todo[q];
+        const NameList &nl = *ids[(size_t)s];
+        itsx_io::BlockWriter bw;
+        std::string werr, buf;
+        if (!bw.open(seq_out_paths[s], itsx_io::PLAIN, werr, true)) { werrs[(size_t)t] = werr; continue; }
+        for (int64_t p = pstart[(size_t)s], i = 0; p < pstart[(size_t)s + 1]; p++, i++) {
+          if (reason[(size_t)p] != 0) continue;
+          const size_t o = (size_t)(f.off[(size_t)p] + r.off[(size_t)p]);
+          buf += '@'; buf.append(nl.ptr((size_t)i), nl.len((size_t)i)); buf += '\n';
+          buf.append(oseq.data() + o, (size_t)olen[(size_t)p]); buf += "\n+\n";
+          buf.append(oqual.data() + o, (size_t)olen[(size_t)p]); buf += '\n';
+          if (buf.size() >= (1u << 20)) { bw.put(buf); buf.clear(); }
+        }
+        bw.put(buf);
+        if (!bw.close(werr)) werrs[(size_t)t] = werr;
+      }
+    });
+    for (const std::string &e : werrs) if (!e.empty()) SET_ERR(ctx, ITSX_E_IO, e);
+  }
+  if (trace) {
+    const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    fprintf(stderr, "[itsx] merge + load (%d sample%s): read+inflate+parse %.0f ms, upload+kernel %.0f ms, compact+gather+pack %.0f ms, write %.0f ms\n",
+            (int)S, S == 1 ? "" : "s", parse_ms, ms(tm1, tm2), ms(tm2, tm3), ms(tm3, std::chrono::steady_clock::now()));
+  }
+  if (n_merged_per_sample) for (int32_t s = 0; s < S; s++) n_merged_per_sample[s] = scnt[(size_t)s];
+  return ITSX_OK;
+}
+
 // R1/R2 -> merged reads as THIS CONTEXT'S READ SET (arrays mode: nothing written, nothing parsed again).  The reference writes the merged
 // reads to tempdir/seq.fq and vsearch reads them back (SeqSample.py:266-365, 93-131); here the merge kernel's output is gathered into
 // a gap-free text on the device and packed where it is -- the merged bases never visit the host, the merged qualities are not needed at
@@ -4066,67 +4227,24 @@ int itsx_merge_pairs_files(itsx_ctx *ctx, const char *r1_path, const char *r2_pa
 static int merge_pairs_load_impl(itsx_ctx *ctx, const char *r1_path, const char *r2_path, const char *text1, int64_t nb1, const char *text2, int64_t nb2,
                                  int maxdiffs, double maxee, int allow_stagger, int64_t *n_pairs, int64_t *n_merged)
 {
-  typedef FastxPart Side;
-  auto parse = [](const char *path, const char *text, int64_t nb, Side &sd, std::string &perr) -> int {
-    std::shared_ptr<const itsx_io::Text> tp;
-    itsx_io::Text view;
-    const itsx_io::Text *t = &view;
-    if (text) view.borrow(text, (size_t)nb);
-    else { tp = slurp(path, true, perr); if (!tp) return ITSX_E_IO; t = tp.get(); }
-    if (!t->empty() && (*t)[0] != '@') { perr = std::string("malformed FASTQ record 1 in ") + path; return ITSX_E_FORMAT; }
-    const int prc = parse_fastx(*t, true, true, sd, perr);
-    if (prc != ITSX_OK) perr += std::string(" in ") + path;
-    return prc;
-  };
-  Side f, r;
+  FastxPart f, r;
   std::string ferr, rerr2;
   int rc2 = ITSX_OK;
-  static const bool trace = sw_get("ITSX_TRACE_ALLOC") != nullptr;
   const auto tm0 = std::chrono::steady_clock::now();
-  std::thread other([&] { rc2 = parse(r2_path, text2, nb2, r, rerr2); });
-  int rc = parse(r1_path, text1, nb1, f, ferr);
+  std::thread other([&] { rc2 = parse_fastq_side(r2_path, text2, nb2, r, rerr2); });
+  int rc = parse_fastq_side(r1_path, text1, nb1, f, ferr);
   other.join();
-  const auto tm1 = std::chrono::steady_clock::now();
   if (rc != ITSX_OK) { ctx->set_error(ferr); return rc; }
   if (rc2 != ITSX_OK) { ctx->set_error(rerr2); return rc2; }
   if (f.ids.size() != r.ids.size()) SET_ERR(ctx, ITSX_E_FORMAT, "R1 and R2 hold different numbers of records");
   const int64_t n = (int64_t)f.ids.size();
-  std::vector<int32_t> olen((size_t)n + 1), reason((size_t)n + 1);
-  DBuf<uint8_t> d_os;
-  rc = merge_core(ctx, f.seq.data(), f.qual.data(), f.off.data(), r.seq.data(), r.qual.data(), r.off.data(), n, maxdiffs, maxee, allow_stagger,
-                  nullptr, nullptr, olen.data(), reason.data(), nullptr, nullptr, &d_os);
+  int64_t m = 0;
+  rc = merge_load_core(ctx, f, r, {&f.ids}, {0, n}, nullptr, maxdiffs, maxee, allow_stagger,
+                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count(), &m);
   if (rc != ITSX_OK) return rc;
-  const auto tm2 = std::chrono::steady_clock::now();
-  hipStream_t st = ctx->st;
-  std::vector<int64_t> srcoff, dstoff(1, 0);
-  ctx->h_names.clear();
-  ctx->h_merge_index.assign((size_t)n, -1);              // per pair: its merged read (itsx_merge_pair_index)
-  for (int64_t i = 0; i < n; i++) {
-    if (reason[i] != 0) continue;
-    ctx->h_merge_index[(size_t)i] = (int32_t)srcoff.size();
-    srcoff.push_back(f.off[i] + r.off[i]);
-    dstoff.push_back(dstoff.back() + olen[i]);
-    ctx->h_names.emplace_back(f.ids.ptr((size_t)i), f.ids.ptr((size_t)i) + f.ids.len((size_t)i));
-  }
-  const int64_t m = (int64_t)srcoff.size();
-  if (m >= (1ll << 31) - 64) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "more than 2^31 reads in one context");
-  DBuf<int64_t> d_src, d_dst; DBuf<uint8_t> d_cmp;
-  HIPCHK(upload(d_src, srcoff, st)); HIPCHK(upload(d_dst, dstoff, st)); HIPCHK(d_cmp.alloc((size_t)dstoff.back() + 64));
-  if (m > 0) hipLaunchKernelGGL(k_gather_reads, dim3((unsigned)std::min<int64_t>((m + 3) / 4, 65535)), dim3(256), 0, st, d_os.p, d_src.p, d_dst.p, m, d_cmp.p);
-  HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipGetLastError());
-  ctx->N = m;
-  ctx->h_off.swap(dstoff);
-  itsx_io::Text().swap(ctx->h_bases);
-  static const uint8_t none = 0;
-  rc = pack_and_upload(ctx, nullptr, m > 0 ? d_cmp.p : &none);
-  if (trace) {
-    const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    fprintf(stderr, "[itsx] merge + load: read+inflate+parse %.0f ms, upload+kernel %.0f ms, gather+pack %.0f ms\n", ms(tm0, tm1), ms(tm1, tm2), ms(tm2, std::chrono::steady_clock::now()));
-  }
   if (n_pairs) *n_pairs = n;
   if (n_merged) *n_merged = m;
-  return rc;
+  return ITSX_OK;
 }
 int itsx_merge_pairs_load(itsx_ctx *ctx, const char *r1_path, const char *r2_path, int maxdiffs, double maxee, int allow_stagger, int64_t *n_pairs, int64_t *n_merged)
 {
@@ -4141,7 +4259,83 @@ int itsx_merge_pairs_load_text(itsx_ctx *ctx, const char *text1, int64_t nbytes1
   CTXCHK(ctx && text1 && text2 && nbytes1 >= 0 && nbytes2 >= 0);
   return merge_pairs_load_impl(ctx, "(R1 slice)", "(R2 slice)", text1, nbytes1, text2, nbytes2, maxdiffs, maxee, allow_stagger, n_pairs, n_merged);
 }
-// per pair of the last itsx_merge_pairs_load / _load_text: the index of its merged read in the context's read set, -1 = not merged
+// f4 batching: the read pairs of EVERY sample of a batch through one merge (the QIIME 2 plugin merges once per manifest row,
+// q2_itsxpress.py:72-80 -> SeqSample.py:266-365).  All files are read and parsed side by side on the I/O pool, all pairs go through one
+// merge_load_core, and the context ends up as itsx_load_reads_files leaves it: S = n_samples, reads in sample order and then pair order.
+static int merge_pairs_load_files_impl(itsx_ctx *ctx, const char *const *r1_paths, const char *const *r2_paths, const char *const *seq_out_paths,
+                                       int32_t S, int maxdiffs, double maxee, int allow_stagger, int64_t *n_pairs_per_sample, int64_t *n_merged_per_sample)
+{
+  const auto tm0 = std::chrono::steady_clock::now();
+  std::vector<FastxPart> fs((size_t)S), rs((size_t)S);
+  std::vector<std::string> errs((size_t)S * 2);
+  std::vector<int> rcs((size_t)S * 2, ITSX_OK);
+  const int T = std::max(1, std::min<int>({itsx_io::io_threads(), 16, (int)std::min<int64_t>((int64_t)S * 2, 16)}));
+  {
+    std::atomic<int64_t> next{0};
+    on_threads(T, [&](int) {
+      // at most 16 threads in all: a worker's reader, inflater and parser size their pools by io_threads(), so each gets the worker's
+      // share of the budget (16 workers: everything a worker calls runs on the worker itself)
+      itsx_io::IoThreadCap share(16 / T);
+      for (;;) {
+        const int64_t q = next.fetch_add(1);
+        if (q >= (int64_t)S * 2) break;
+        const size_t s = (size_t)(q >> 1);
+        rcs[(size_t)q] = (q & 1) ? parse_fastq_side(r2_paths[s], nullptr, 0, rs[s], errs[(size_t)q]) : parse_fastq_side(r1_paths[s], nullptr, 0, fs[s], errs[(size_t)q]);
+      }
+    });
+  }
+  for (size_t q = 0; q < (size_t)S * 2; q++) if (rcs[q] != ITSX_OK) { ctx->set_error(errs[q]); return rcs[q]; }
+  std::vector<int64_t> pstart((size_t)S + 1, 0);
+  std::vector<const NameList *> ids((size_t)S);
+  for (size_t s = 0; s < (size_t)S; s++) {
+    if (fs[s].ids.size() != rs[s].ids.size())
+      SET_ERR(ctx, ITSX_E_FORMAT, std::string("R1 and R2 hold different numbers of records: ") + r1_paths[s] + " (" + std::to_string(fs[s].ids.size()) + ") and " +
+              r2_paths[s] + " (" + std::to_string(rs[s].ids.size()) + ")");
+    pstart[s + 1] = pstart[s] + (int64_t)fs[s].ids.size();
+    ids[s] = &fs[s].ids;
+    if (n_pairs_per_sample) n_pairs_per_sample[s] = (int64_t)fs[s].ids.size();
+  }
+  const int64_t n = pstart[(size_t)S];
+  // the samples' reads side by side in one text per direction (one sample: its own)
+  FastxPart F, R;
+  bool oom = false;
+  auto join = [&](std::vector<FastxPart> &parts, FastxPart &out) {
+    std::vector<int64_t> sb((size_t)S + 1, 0);
+    for (size_t s = 0; s < (size_t)S; s++) sb[s + 1] = sb[s] + (int64_t)parts[s].seq.size();
+    if (!out.seq.resize((size_t)sb[(size_t)S]) || !out.qual.resize((size_t)sb[(size_t)S])) { oom = true; return; }
+    out.off.assign((size_t)n + 1, 0);
+    const int TJ = std::max(1, std::min(T, (int)S));
+    on_threads(TJ, [&](int t) {
+      for (size_t s = (size_t)t; s < (size_t)S; s += (size_t)TJ) {
+        FastxPart &p = parts[s];
+        if (p.seq.size()) { memcpy(out.seq.data() + sb[s], p.seq.data(), p.seq.size()); memcpy(out.qual.data() + sb[s], p.qual.data(), p.seq.size()); }
+        for (size_t i = 0; i < p.ids.size(); i++) out.off[(size_t)pstart[s] + i + 1] = sb[s] + p.off[i + 1];
+        itsx_io::Text().swap(p.seq); itsx_io::Text().swap(p.qual);
+      }
+    });
+  };
+  if (S > 1) { join(fs, F); if (!oom) join(rs, R); }
+  if (oom) SET_ERR(ctx, ITSX_E_NOMEM, "out of memory joining the samples' reads");
+  return merge_load_core(ctx, S > 1 ? F : fs[0], S > 1 ? R : rs[0], ids, pstart, seq_out_paths, maxdiffs, maxee, allow_stagger,
+                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count(), n_merged_per_sample);
+}
+int itsx_merge_pairs_load_files(itsx_ctx *ctx, const char *const *r1_paths, const char *const *r2_paths, const char *const *seq_out_paths,
+                                int32_t n_samples, int maxdiffs, double maxee, int allow_stagger, int64_t *n_pairs_per_sample, int64_t *n_merged_per_sample)
+{
+  CTXCHK(ctx && r1_paths && r2_paths && n_samples >= 1);
+  for (int32_t s = 0; s < n_samples; s++) CTXCHK(r1_paths[s] && r2_paths[s]);
+  const int rc = merge_pairs_load_files_impl(ctx, r1_paths, r2_paths, seq_out_paths, n_samples, maxdiffs, maxee, allow_stagger, n_pairs_per_sample, n_merged_per_sample);
+  if (rc != ITSX_OK) {                                   // whatever failed, the context is left empty (no reads, one sample) and usable
+    const std::string why = ctx->err;
+    const int64_t zero = 0;
+    (void)itsx_set_reads(ctx, nullptr, &zero, 0, nullptr, nullptr);
+    ctx->h_merge_index.clear();
+    ctx->set_error(why);
+  }
+  return rc;
+}
+// per pair of the last itsx_merge_pairs_load / _load_text / _load_files (there: the pairs of all samples, in sample order): the index of its
+// merged read in the context's read set, -1 = not merged
 int itsx_merge_pair_index(const itsx_ctx *ctx, int32_t *index, int64_t n_pairs)
 {
   CTXCHK(ctx && index);
@@ -4298,6 +4492,7 @@ static int host_bases(const itsx_ctx *cctx)
   ctx->h_bases.resize((size_t)ctx->h_off[(size_t)ctx->N]);
   if (!ctx->h_bases.empty()) HIPCHK(hipMemcpy(&ctx->h_bases[0], ctx->dev_bases, ctx->h_bases.size(), hipMemcpyDeviceToHost));
   ctx->bases_view = ctx->h_bases.data();
+  if (ctx->d_merged_text.p && ctx->dev_bases == ctx->d_merged_text.p) { ctx->d_merged_text.release(); ctx->dev_bases = nullptr; }     // the host has it now
   return ITSX_OK;
 }
 // sequences of the unique representatives in input order of the seeds (what rep.fa holds), concatenated; offsets[n_unique + 1];

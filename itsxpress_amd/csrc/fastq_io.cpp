@@ -336,10 +336,15 @@ int64_t parallel_inflates() { return g_parallel_inflates.load(); }
 
 int codec_flags() { codecs(); return (g_ld.ok ? 1 : 0) | (g_zs.ok ? 2 : 0); }
 
+static thread_local int tl_io_cap = 0;          // 0: none
+IoThreadCap::IoThreadCap(int cap) : prev_(tl_io_cap) { tl_io_cap = std::max(1, cap); }
+IoThreadCap::~IoThreadCap() { tl_io_cap = prev_; }
+
 int io_threads()
 {
   int n = env_int("ITSX_IO_THREADS", 0);
   if (n <= 0) { n = (int)std::thread::hardware_concurrency(); if (n <= 0) n = 4; n = std::min(n, 32); }
+  if (tl_io_cap > 0) n = std::min(n, tl_io_cap);
   return std::max(1, n);
 }
 

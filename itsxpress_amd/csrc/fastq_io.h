@@ -79,7 +79,17 @@ uint32_t crc32_fast(uint32_t crc, const void *p, size_t n);
 // Adopt `text` as the content of the file just written at `path` (temporary files the next stage reads back).
 void cache_put(const char *path, std::shared_ptr<const Text> text);
 
-int io_threads();               // ITSX_IO_THREADS or min(hardware threads, 32)
+int io_threads();               // ITSX_IO_THREADS or min(hardware threads, 32); on a thread that holds an IoThreadCap, at most its cap
+// While one lives, io_threads() on THIS thread returns at most `cap`: a worker of an outer pool hands its share of the thread budget to
+// the readers, inflaters, parsers and writers it calls, which size their own pools by io_threads() (cap 1: they run on the worker itself)
+struct IoThreadCap {
+  explicit IoThreadCap(int cap);
+  ~IoThreadCap();
+  IoThreadCap(const IoThreadCap &) = delete;
+  IoThreadCap &operator=(const IoThreadCap &) = delete;
+ private:
+  int prev_;
+};
 
 // run fn(t) on T host threads (the domain table of a large sample has millions of rows: ordering and formatting it on one
 // thread took longer than the whole GPU path)

@@ -133,6 +133,22 @@ struct MergeArgs {
   int32_t *out_len, *reason, *shift; double *score;
 };
 void launch_merge(const MergeArgs &a, hipStream_t st);
+// the merged pairs of a merge kernel's output, compacted: read j = the j-th pair with reason 0, in pair order
+struct MergeCompactArgs {
+  const int32_t *reason, *out_len;              // [n], as launch_merge left them
+  const int64_t *foff, *roff;                   // [n+1]: the merged read of pair i sits at foff[i] + roff[i]
+  int64_t n;
+  int32_t n_samples;                            // > 1: pairs [pair_start[s], pair_start[s + 1]) belong to sample s
+  const int64_t *pair_start;                    // [n_samples + 1], non-decreasing, pair_start[n_samples] = n (n_samples > 1 only)
+  int64_t *blk_cnt, *blk_len;                   // [merge_compact_blocks(n)] scratch
+  int32_t *pair_index;                          // [n]: the read of pair i, -1 = not merged
+  int64_t *srcoff, *dstoff;                     // [n+1]: read j's bases in the merge output / in the gap-free text (dstoff[reads] = its size)
+  int32_t *sample;                              // [n]: read j's sample (n_samples > 1 only)
+  int64_t *sample_count;                        // [n_samples], zeroed by the caller: merged reads per sample (n_samples > 1 only)
+};
+int64_t merge_compact_blocks(int64_t n);
+// total[0] = merged reads, total[1] = the bytes of their text (device memory)
+void launch_merge_compact(const MergeCompactArgs &a, int64_t *total, hipStream_t st);
 
 // ---- k_util.hip
 // exclusive prefix sum of n int32 values (n < 2^31); tmp must hold scan_tmp_elems(n) int32

@@ -158,4 +158,111 @@ void launch_merge(const MergeArgs &a, hipStream_t st)
   }
 }
 
+// ---- compaction of the merge kernel's output: which pairs merged, where their reads go ------------------------------------------
+// The merge kernel leaves pair i's read (if reason[i] == 0) at foff[i] + roff[i], out_len[i] bases long.  The read set wants the merged
+// reads gap-free, in pair order, and -- for a batch of samples -- to know each read's sample.  A two-level exclusive scan over the
+// pairs of (merged ? 1 : 0, merged ? out_len : 0): every block of MC_TILE pairs sums its tile (k_merge_compact<false>), one block scans
+// the tiles' sums (k_merge_compact_sums), and every block scans its tile again and scatters (k_merge_compact<true>).  Counts and byte
+// offsets are 64-bit throughout: a batch's text can pass 2^31 bytes.
+constexpr int MC_BLOCK = 256;
+constexpr int MC_ITEMS = 8;
+constexpr int MC_TILE = MC_BLOCK * MC_ITEMS;   // pairs per block; thread t owns MC_ITEMS consecutive pairs
+
+// exclusive prefix of (c, l) over the block's threads in thread order, and the block's sums: a wave64 shuffle scan, one LDS partial per
+// wave, nothing assumed across waves but the barrier.  May be called again: the partials are free when it returns.
+__device__ __forceinline__ void mc_block_scan(int64_t c, int64_t l, int64_t &ec, int64_t &el, int64_t &tc, int64_t &tl)
+{
+  __shared__ int64_t wc[MC_BLOCK / 64], wl[MC_BLOCK / 64];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  int64_t ic = c, il = l;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int64_t uc = __shfl_up(ic, d, 64), ul = __shfl_up(il, d, 64);
+    if (lane >= d) { ic += uc; il += ul; }
+  }
+  if (lane == 63) { wc[wid] = ic; wl[wid] = il; }
+  __syncthreads();
+  int64_t oc = 0, ol = 0;
+  tc = 0; tl = 0;
+#pragma unroll
+  for (int w = 0; w < MC_BLOCK / 64; w++) {
+    if (w < wid) { oc += wc[w]; ol += wl[w]; }
+    tc += wc[w]; tl += wl[w];
+  }
+  ec = oc + ic - c; el = ol + il - l;
+  __syncthreads();
+}
+
+template <bool SCATTER> __global__ __launch_bounds__(MC_BLOCK) void k_merge_compact(MergeCompactArgs a)
+{
+  const int64_t base = (int64_t)blockIdx.x * MC_TILE + (int64_t)threadIdx.x * MC_ITEMS;
+  int32_t len[MC_ITEMS];
+  int64_t c = 0, l = 0;
+#pragma unroll
+  for (int i = 0; i < MC_ITEMS; i++) {
+    const int64_t p = base + i;
+    const bool ok = p < a.n && a.reason[p] == 0;
+    len[i] = ok ? a.out_len[p] : -1;
+    if (ok) { c++; l += len[i]; }
+  }
+  int64_t ec, el, tc, tl;
+  mc_block_scan(c, l, ec, el, tc, tl);
+  if (!SCATTER) {
+    if (threadIdx.x == 0) { a.blk_cnt[blockIdx.x] = tc; a.blk_len[blockIdx.x] = tl; }
+    return;
+  }
+  int64_t j = a.blk_cnt[blockIdx.x] + ec, d = a.blk_len[blockIdx.x] + el;     // this thread's first read and its first byte
+  int32_t s = -1; unsigned long long run = 0;                               // the sample of the reads counted in `run`
+#pragma unroll
+  for (int i = 0; i < MC_ITEMS; i++) {
+    const int64_t p = base + i;
+    if (p >= a.n) break;
+    if (len[i] < 0) { a.pair_index[p] = -1; continue; }
+    a.pair_index[p] = (int32_t)j;
+    a.srcoff[j] = a.foff[p] + a.roff[p];
+    a.dstoff[j] = d;
+    if (a.n_samples > 1) {
+      if (s < 0 || p >= a.pair_start[s + 1]) {
+        if (run) atomicAdd(reinterpret_cast<unsigned long long *>(a.sample_count + s), run);
+        run = 0;
+        // the sample whose pairs [pair_start[s], pair_start[s + 1]) hold p (empty samples repeat a start: the last of them is taken)
+        int32_t lo = 0, hi = a.n_samples;
+        while (hi - lo > 1) { const int32_t mid = (lo + hi) >> 1; if (a.pair_start[mid] <= p) lo = mid; else hi = mid; }
+        s = lo;
+      }
+      a.sample[j] = s;
+      run++;
+    }
+    j++; d += len[i];
+  }
+  if (run) atomicAdd(reinterpret_cast<unsigned long long *>(a.sample_count + s), run);
+}
+
+// the tiles' sums -> their exclusive prefixes, in place; total[0] = merged reads, total[1] = their bytes; dstoff[total[0]] = total[1]
+__global__ __launch_bounds__(MC_BLOCK) void k_merge_compact_sums(int64_t *__restrict__ blk_cnt, int64_t *__restrict__ blk_len, int64_t nb,
+                                                                 int64_t *__restrict__ total, int64_t *__restrict__ dstoff)
+{
+  int64_t cc = 0, cl = 0;                        // the sums of the chunks before this one
+  for (int64_t b0 = 0; b0 < nb; b0 += MC_BLOCK) {
+    const int64_t b = b0 + threadIdx.x;
+    const int64_t c = b < nb ? blk_cnt[b] : 0, l = b < nb ? blk_len[b] : 0;
+    int64_t ec, el, tc, tl;
+    mc_block_scan(c, l, ec, el, tc, tl);
+    if (b < nb) { blk_cnt[b] = cc + ec; blk_len[b] = cl + el; }
+    cc += tc; cl += tl;
+  }
+  if (threadIdx.x == 0) { total[0] = cc; total[1] = cl; dstoff[cc] = cl; }
+}
+
+int64_t merge_compact_blocks(int64_t n) { return (n + MC_TILE - 1) / MC_TILE; }
+
+void launch_merge_compact(const MergeCompactArgs &a, int64_t *total, hipStream_t st)
+{
+  if (a.n <= 0) return;
+  const int64_t nb = merge_compact_blocks(a.n);
+  hipLaunchKernelGGL(k_merge_compact<false>, dim3((unsigned)nb), dim3(MC_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(k_merge_compact_sums, dim3(1), dim3(MC_BLOCK), 0, st, a.blk_cnt, a.blk_len, nb, total, a.dstoff);
+  hipLaunchKernelGGL(k_merge_compact<true>, dim3((unsigned)nb), dim3(MC_BLOCK), 0, st, a);
+}
+
 }  // namespace itsx

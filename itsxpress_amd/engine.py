@@ -46,11 +46,24 @@ class Engine:
             msg = self.L.itsx_last_error(None).decode()
             raise EngineError(-4, msg)
         self.device = int(device)
+        self.read_set = 0            # bumped whenever the context is given (or loses) a read set: see n_reads
         self.n_reads = 0
         self.n_unique = 0
         self.n_profiles = 0
         self.n_samples = 1
         self.rows_mode = -1
+
+    # Every call that changes the context's read set records the new count here, so the setter is where the read set's serial number
+    # advances: a caller that left reads resident (SampleBatch.merge_reads) keeps the number and can tell later whether the
+    # engine -- which may be shared -- still holds them
+    @property
+    def n_reads(self):
+        return self._n_reads
+
+    @n_reads.setter
+    def n_reads(self, v):
+        self._n_reads = v
+        self.read_set += 1
 
     def close(self):
         if getattr(self, "h", None):
@@ -286,6 +299,7 @@ class Engine:
         self._chk(self.L.itsx_merge_pairs_load(self.h, os.fsencode(r1), os.fsencode(r2), int(maxdiffs), float(maxee), int(allow_stagger),
                                                C.byref(n), C.byref(m)))
         self.n_reads, self.n_samples, self.n_unique = m.value, 1, 0
+        self._n_pairs = n.value
         self._last_merge = dict(r1=r1, r2=r2, maxdiffs=int(maxdiffs), maxee=float(maxee), allow_stagger=bool(allow_stagger))
         return n.value, m.value
 
@@ -297,9 +311,48 @@ class Engine:
         self._chk(self.L.itsx_merge_pairs_load_text(self.h, C.c_void_p(ptr1), int(nb1), C.c_void_p(ptr2), int(nb2), int(maxdiffs), float(maxee),
                                                     int(allow_stagger), C.byref(n), C.byref(m)))
         self.n_reads, self.n_samples, self.n_unique = m.value, 1, 0
+        self._n_pairs = n.value
         idx = np.zeros(max(1, n.value), np.int32)
         self._chk(self.L.itsx_merge_pair_index(self.h, idx.ctypes.data, n.value))
         return n.value, m.value, idx[:n.value]
+
+    def merge_pairs_load_files(self, r1s, r2s, seq_outs=None, maxdiffs=40, maxee=2.0, allow_stagger=False):
+        """The pairs of every sample of a batch (sample s = r1s[s] / r2s[s]) through one merge; the merged reads of all samples, in sample
+        order, become this engine's read set with one sample per file pair (as load_reads_files leaves it).  seq_outs: None, or per
+        sample None or the path its merged records are written to (what merge_pairs_files writes for it alone).
+        Returns (n_pairs[S], n_merged[S])."""
+        S = len(r1s)
+        if S < 1 or len(r2s) != S or (seq_outs is not None and len(seq_outs) != S):
+            raise ValueError("merge_pairs_load_files: one R1, one R2 (and one output or None) per sample, at least one sample")
+        for p in list(r1s) + list(r2s):
+            if not os.path.exists(p):
+                raise FileNotFoundError(p)
+        a1 = (C.c_char_p * S)(*[os.fsencode(p) for p in r1s])
+        a2 = (C.c_char_p * S)(*[os.fsencode(p) for p in r2s])
+        ao = None
+        if seq_outs is not None and any(p is not None for p in seq_outs):
+            ao = (C.c_char_p * S)(*[None if p is None else os.fsencode(p) for p in seq_outs])
+        n = np.zeros(S, np.int64)
+        m = np.zeros(S, np.int64)
+        self._last_merge = None
+        try:
+            self._chk(self.L.itsx_merge_pairs_load_files(self.h, a1, a2, ao, S, int(maxdiffs), float(maxee), int(allow_stagger),
+                                                         n.ctypes.data, m.ctypes.data))
+        except EngineError:
+            self.n_reads, self.n_samples, self.n_unique, self._n_pairs = 0, 1, 0, 0      # the context is left empty
+            raise
+        self.n_reads, self.n_unique = int(m.sum()), 0
+        self.n_samples = max(1, self.L.itsx_num_samples(self.h))
+        self._n_pairs = int(n.sum())
+        return n, m
+
+    def merge_pair_index(self):
+        """After merge_pairs_load_files: per pair of the batch (sample order, then pair order) the index of its merged read in the
+        batch's read set, -1 = not merged.  After merge_pairs_load: the same for that one sample's pairs."""
+        n = int(getattr(self, "_n_pairs", 0))
+        idx = np.zeros(max(1, n), np.int32)
+        self._chk(self.L.itsx_merge_pair_index(self.h, idx.ctypes.data, n))
+        return idx[:n]
 
     def write_merged_fastq(self, path):
         """After merge_pairs_load (which writes nothing): the merged records as a FASTQ file after all -- the same merge once more, in a
@@ -527,6 +580,13 @@ class Engine:
         r = np.zeros(self.n_reads, np.uint64)
         self._chk(self.L.itsx_debug_read_hashes(self.h, f.ctypes.data, r.ctypes.data))
         return f, r
+
+    def debug_read_samples(self):
+        """(device, host): the sample of every read as the kernels and as the writers see it"""
+        d = np.zeros(max(1, self.n_reads), np.int32)
+        h = np.zeros(max(1, self.n_reads), np.int32)
+        self._chk(self.L.itsx_debug_read_samples(self.h, d.ctypes.data, h.ctypes.data))
+        return d[:self.n_reads], h[:self.n_reads]
 
     def debug_packed_read(self, i):
         nw, ne = C.c_int32(0), C.c_int32(0)
