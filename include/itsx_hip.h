@@ -274,10 +274,21 @@ int itsx_select_sample(itsx_ctx *ctx, int32_t sample);
  * (12-mer presence counts on both strands, 4x rule; restated in oracle/orc_cluster.c, parity unpinned).
  * itsx_orient_load_db: FASTA (plain/gzip) of reference sequences -> 12-mer bitmap on the device.
  * itsx_orient: per loaded read strand = +1 forward, -1 reverse (to be reverse-complemented), 0 undetermined; counts may be NULL.
+ *   Reads of any length the engine loads (up to 65535 bases).
  * itsx_write_oriented_fastq (host, context-free): the FASTQ vsearch would write for those orientations. */
 int itsx_orient_load_db(itsx_ctx *ctx, const char *fasta_path, int64_t *n_sequences);
 int itsx_orient(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t *count_rev);
 int itsx_write_oriented_fastq(const char *seq_path, const char *out_path, const int8_t *strand, int64_t n_records, int64_t *n_written);
+/* itsx_orient_apply: orients the context's read set as itsx_orient does (S samples: itsx_load_reads_files, or itsx_set_reads +
+ * itsx_set_samples; S = 1 is one sample) and REPLACES it, on the device, by the reads vsearch --orient --fastqout keeps: forward reads as
+ * they are, reverse reads reverse-complemented (packed words, exception lists and the host text, whose case is kept), undetermined reads
+ * dropped; sample order, then input order.  Afterwards the context is in the state itsx_load_reads_files leaves after loading the S
+ * per-sample oriented.fq files that itsx_write_oriented_fastq writes for these strands: S unchanged (a sample that keeps nothing stays, without
+ * reads), no dereplication or search results.  strand / count_fwd / count_rev: [reads BEFORE the call], each may be NULL;
+ * n_kept_per_sample: [itsx_num_samples], may be NULL.  Reads without labels stay without.
+ * On any error (ITSX_E_ARG before itsx_orient_load_db, ITSX_E_NOMEM, ITSX_E_DEVICE) the context KEEPS the read set it had, with whatever
+ * results it held: the new read set is built beside it and swapped in only when it is complete. */
+int itsx_orient_apply(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t *count_rev, int64_t *n_kept_per_sample);
 
 /* ---- f2: SeqSample._merge_reads (itsxpress/SeqSample.py:266-365) = vsearch --fastq_mergepairs R1 --reverse R2
  * --fastqout seq.fq --fastq_maxdiffs 40 --fastq_maxee 2 --fastq_qmax 93 [--fastq_allowmergestagger]; restated in

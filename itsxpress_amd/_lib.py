@@ -71,7 +71,7 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_debug_read_hashes", "itsx_debug_read_samples", "itsx_debug_packed_read", "itsx_debug_detmath", "itsx_debug_logf", "itsx_debug_dust", "itsx_debug_calibrate", "itsx_debug_issue", "itsx_shard_text", "itsx_shard_last_error", "itsx_owner_verdicts",
            "itsx_write_trimmed_fastq", "itsx_write_trimmed_paired", "itsx_trim_last_error",
            "itsx_merge_buffers", "itsx_merge_pairs_files", "itsx_merge_pairs_load", "itsx_merge_tables",
-           "itsx_orient_load_db", "itsx_orient", "itsx_write_oriented_fastq",
+           "itsx_orient_load_db", "itsx_orient", "itsx_orient_apply", "itsx_write_oriented_fastq",
            "itsx_io_read", "itsx_io_free", "itsx_io_codecs", "itsx_fastq_ids",
            "itsx_load_reads_files", "itsx_set_samples", "itsx_num_samples", "itsx_select_sample",
            "itsx_io_parallel_inflates", "itsx_io_cache_clear", "itsx_get_read_names",
@@ -162,6 +162,7 @@ def lib():
         "itsx_merge_tables": (i32, [vp, vp, vp, vp, vp]),
         "itsx_orient_load_db": (i32, [vp, cp, vp]),
         "itsx_orient": (i32, [vp, vp, vp, vp]),
+        "itsx_orient_apply": (i32, [vp, vp, vp, vp, vp]),
         "itsx_write_oriented_fastq": (i32, [cp, cp, vp, i64, vp]),
         "itsx_unique_keys": (i32, [vp, C.c_uint64, vp, vp]),
         "itsx_set_active_uniques": (i32, [vp, vp]),

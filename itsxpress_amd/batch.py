@@ -20,8 +20,12 @@ q2_itsxpress.py:72-80) join the batch UNMERGED: `merge_reads` sends the pairs of
 `deduplicate` / `cluster_per_sample` go on from there without a `seq.fq` round trip; the per-sample `seq.fq` is written
 only where a consumer reads it (file-compatible mode, or `write_seq_files=True`).
 
+CCS samples (`trim_ccs`: the plugin calls `sobj.orient_reads()` first, q2_itsxpress.py:284-285) join the batch UNORIENTED:
+`orient_reads` orients the reads of every sample in one engine call (`itsx_orient_apply`) and leaves the oriented reads on the
+device as the batch's read set; each sample's `oriented.fq` is written by the host writer from its own file and strands.
+
 Nothing here computes: the grouping, the counters and the writers live behind the C ABI
-(`itsx_load_reads_files`, `itsx_merge_pairs_load_files`, `itsx_set_samples`, `itsx_select_sample`; include/itsx_hip.h).
+(`itsx_load_reads_files`, `itsx_merge_pairs_load_files`, `itsx_orient_apply`, `itsx_set_samples`, `itsx_select_sample`; include/itsx_hip.h).
 """
 import logging
 import os
@@ -38,9 +42,10 @@ from .definitions import maxmismatches
 class SampleBatch:
     """Runs `deduplicate()` and `_search()` of many SeqSample objects as one engine pass.
 
-    samples: objects with `seq_file` and `tempdir` (the mirror's or the reference's SeqSample*, after `orient_reads` where
-    that applies), or paired samples that are not merged yet (`r1` and `fastq2` set, `seq_file` unset): those are merged
-    by `merge_reads`, all in one engine call.  Method names and arguments follow SeqSample."""
+    samples: objects with `seq_file` and `tempdir` (the mirror's or the reference's SeqSample*), or paired samples that are not
+    merged yet (`r1` and `fastq2` set, `seq_file` unset): those are merged by `merge_reads`, all in one engine call.  CCS samples
+    (`trim_ccs`) join the batch unoriented and `orient_reads` orients them all in one engine call.  Method names and arguments
+    follow SeqSample."""
 
     def __init__(self, samples: Sequence, engine: Optional[Engine] = None, subdirs: Optional[Sequence[str]] = None) -> None:
         self.samples = list(samples)
@@ -57,9 +62,10 @@ class SampleBatch:
         self.counts: Optional[np.ndarray] = None       # reads per sample
         self.first: Optional[np.ndarray] = None        # index of each sample's first read in the batch
         self.n_pairs: Optional[np.ndarray] = None      # after merge_reads: read pairs per sample
-        self._merged_into = None                       # the seq_files whose reads merge_reads left resident in the engine,
-        self._merged_read_set = None                   # and the engine's read-set number at that moment (the engine may be shared)
-        self._seq_written = False                      # whether merge_reads wrote them
+        self._resident = None                          # the seq_files whose reads merge_reads / orient_reads left resident in the engine,
+        self._resident_read_set = None                 # and the engine's read-set number at that moment (the engine may be shared)
+        self._seq_written = False                      # whether they wrote those files
+        self._resident_from = "merge_reads"            # which of the two it was (for the messages)
 
     def _dir(self, i: int) -> str:
         d = os.path.join(self.samples[i].tempdir, self.subdirs[i])
@@ -71,20 +77,76 @@ class SampleBatch:
         self.first = np.concatenate([[0], np.cumsum(self.counts)[:-1]]).astype(np.int64)
 
     def _load_reads(self) -> None:
-        """every sample's seq_file as one read set -- unless merge_reads left exactly these reads in the engine
+        """every sample's seq_file as one read set -- unless merge_reads / orient_reads left exactly these reads in the engine
         (SeqSample._reads_loaded_from for a batch)"""
         files = tuple(s.seq_file for s in self.samples)
-        if self._merged_into is not None and self._merged_into == files:
-            if getattr(self.engine, "read_set", None) == self._merged_read_set:
+        if self._resident is not None and self._resident == files:
+            if getattr(self.engine, "read_set", None) == self._resident_read_set:
                 return
-            # something else loaded reads into the shared engine since: the merged reads are gone
+            # something else loaded reads into the shared engine since: the resident reads are gone
             if not all(self._seq_written and os.path.exists(f) for f in files):
-                raise EngineError(-1, "the engine no longer holds this batch's merged reads (another read set was loaded into it) and their "
-                                      "seq.fq files were not written: call merge_reads() again")
+                raise EngineError(-1, "the engine no longer holds this batch's %s reads (another read set was loaded into it) and their "
+                                      "files were not written: call %s() again"
+                                      % ("merged" if self._resident_from == "merge_reads" else "oriented", self._resident_from))
         if any(f is None for f in files):
             raise EngineError(-1, "the batch holds paired samples that were never merged: call merge_reads() before deduplicate() / cluster_per_sample()")
-        self._merged_into = None
+        self._resident = None
         self._set_counts(self.engine.load_reads_files(list(files)))
+
+    def _left_resident(self, files, written: bool, by: str) -> None:
+        """the engine holds exactly the reads of `files` (one per sample) from here on"""
+        self._resident = tuple(files)
+        self._resident_read_set = getattr(self.engine, "read_set", None)
+        self._seq_written = written
+        self._resident_from = by
+
+    # -- f4 for all samples ------------------------------------------------------------------
+    def orient_reads(self, threads: Union[int, str] = 1, write_seq_files: Optional[bool] = None) -> None:
+        """`orient_reads` of every sample (SeqSample.py:48-91; the plugin calls it per manifest row with trim_ccs, q2_itsxpress.py:284-285)
+        in one engine call: every sample's `fastq` loaded as one read set, the orientation database loaded once, one `orient_apply`,
+        which leaves the oriented reads of all samples on the device as the batch's read set -- `deduplicate` / `cluster_per_sample` go
+        on from there without loading `oriented.fq`.  Every sample's `fastq`, `seq_file` and `r1` become `<its batch subdir>/oriented.fq`;
+        the file -- byte for byte what the sample's own `orient_reads` writes -- is written unless write_seq_files is false (the default
+        is to write it in both modes: a single-end sample's trimmed output is cut from it).  `threads` is taken for the sake of
+        SeqSample's signature and ignored, as in `merge_reads`: the engine sizes its own I/O pool, and the files are written by
+        min(16, samples) writers at a time."""
+        try:
+            from concurrent.futures import ThreadPoolExecutor
+            from .definitions import ROOT_DIR
+            from .trim import write_oriented_fastq
+            for s in self.samples:
+                if getattr(s, "fastq", None) is None:
+                    raise ValueError("every sample needs its fastq path to orient its reads")
+            eng = self.engine
+            write = True if write_seq_files is None else bool(write_seq_files)
+            inputs = [s.fastq for s in self.samples]
+            outs = [os.path.join(self._dir(i), "oriented.fq") for i in range(len(self.samples))]
+            self._resident = None
+            before = np.asarray(eng.load_reads_files(inputs), np.int64)
+            eng.orient_load_db(os.path.join(ROOT_DIR, "universal_orient_ref_clean.fasta.gz"))
+            strand, _, _, kept = eng.orient_apply()
+            if write:
+                # the host writer, per sample, on the sample's own file and its slice of the strands (ctypes releases the GIL)
+                first = np.concatenate([[0], np.cumsum(before)]).astype(np.int64)
+                def one(i):
+                    return write_oriented_fastq(inputs[i], outs[i], strand[first[i]:first[i + 1]])
+                with ThreadPoolExecutor(max_workers=max(1, min(16, len(outs)))) as pool:
+                    written = list(pool.map(one, range(len(outs))))
+                if [int(w) for w in written] != [int(k) for k in kept[:len(outs)]]:
+                    raise EngineError(-4, "the oriented reads written and the oriented reads kept by the engine differ")
+            for s, f in zip(self.samples, outs):
+                s.fastq = f
+                s.seq_file = f
+                s.r1 = f
+            self._set_counts(kept[:len(outs)])
+            self._left_resident(outs, write, "orient_reads")
+            logging.info("itsx_hip batch orient: %d samples, %d reads, %d kept", len(self.samples), int(before.sum()), int(self.counts.sum()))
+        except EngineError as e:
+            logging.exception("Could not orient reads with the HIP engine: %s", e)
+            raise e
+        except FileNotFoundError as f:
+            logging.error("The HIP engine, the reads or the orientation reference were not found")
+            raise f
 
     # -- f2 for all samples ------------------------------------------------------------------
     def merge_reads(self, threads: Union[int, str] = 1, stagger: bool = False, write_seq_files: Optional[bool] = None) -> None:
@@ -99,16 +161,14 @@ class SampleBatch:
             eng = self.engine
             write = (not _fast_from_env()) if write_seq_files is None else bool(write_seq_files)
             seq_files = [os.path.join(self._dir(i), "seq.fq") for i in range(len(self.samples))]
-            self._merged_into = None
+            self._resident = None
             n, m = eng.merge_pairs_load_files([s.r1 for s in self.samples], [s.fastq2 for s in self.samples], seq_files if write else None,
                                               maxdiffs=maxmismatches, maxee=2.0, allow_stagger=bool(stagger))
             for s, f in zip(self.samples, seq_files):
                 s.seq_file = f
             self.n_pairs = np.asarray(n, np.int64)
             self._set_counts(m)
-            self._merged_into = tuple(seq_files)
-            self._merged_read_set = getattr(eng, "read_set", None)
-            self._seq_written = write
+            self._left_resident(seq_files, write, "merge_reads")
             logging.info("itsx_hip batch merge: %d samples, %d pairs, %d merged", len(self.samples), int(self.n_pairs.sum()), int(self.counts.sum()))
         except EngineError as e:
             logging.exception("Could not perform read merging with the HIP engine: %s", e)
@@ -242,9 +302,9 @@ class SampleBatch:
         coordinates, into outfiles[i].  A paired sample's seq_file is its merged reads: merge_reads must have written it."""
         from .trim import write_trimmed_fastq
         for s in self.samples:
-            if self._merged_into is not None and s.seq_file in self._merged_into and not (self._seq_written and os.path.exists(s.seq_file)):
-                raise EngineError(-1, "write_trimmed: the merged reads of this batch were never written (%s); "
-                                      "call merge_reads(write_seq_files=True)" % s.seq_file)
+            if self._resident is not None and s.seq_file in self._resident and not (self._seq_written and os.path.exists(s.seq_file)):
+                raise EngineError(-1, "write_trimmed: the %s reads of this batch were never written (%s); call %s(write_seq_files=True)"
+                                      % ("merged" if self._resident_from == "merge_reads" else "oriented", s.seq_file, self._resident_from))
         left, right = _REGION_PREFIX[region]
         start, stop, _, _ = self.engine.trim_coords(left, right)
         out = []

@@ -27,6 +27,7 @@
 #include "k_api.h"
 #include "cluster_multi.h"
 #include "fastq_io.h"
+#include "iupac.h"
 #include "writers.h"
 
 namespace itsx {
@@ -361,6 +362,8 @@ struct itsx_ctx {
   std::vector<int32_t> h_rep_of, h_uniq_of, h_seed_read, h_abund, h_sorted_uniq;
   std::vector<int8_t> h_strand;
   DBuf<uint32_t> d_orient_db; bool have_orient_db = false;   // f4: the orientation database's 12-mer bitmap
+  DBuf<uint32_t> w_orient_tab; DBuf<int32_t> w_orient_list;  // f4: the long reads' word sets (k_orient_long: empty between calls) and their work list
+  std::vector<int32_t> h_orient_longs;                        // (the work list on the host)
   bool clustered = false;                // last grouping came from itsx_cluster at id < 1 (uc rows carry identities)
   std::vector<double> h_pct;             // per read: identity of its H row, -1 for centroids / dropped reads
   std::vector<int32_t> h_order;          // kept reads in processing (label) order
@@ -3889,25 +3892,174 @@ int itsx_orient_load_db(itsx_ctx *ctx, const char *fasta_path, int64_t *n_sequen
   return ITSX_OK;
 }
 
+// strand and both counts of every read of the context, left in device memory (enqueued on ctx->st).  Reads of at most 12 011 bases are
+// k_orient's; it leaves the longer ones at 0 / 0, and those -- a work list of their indices -- go through k_orient_long (k_orient.hip),
+// whose word sets live in w_orient_tab: zeroed when the buffer is new, left empty by the kernel
+static int orient_enqueue(itsx_ctx *ctx, DBuf<int8_t> &d_s, DBuf<int32_t> &d_f, DBuf<int32_t> &d_r, DBuf<uint32_t> &dmask)
+{
+  const int64_t n = ctx->N;
+  HIPCHK(d_s.alloc((size_t)n)); HIPCHK(d_f.alloc((size_t)n)); HIPCHK(d_r.alloc((size_t)n));
+  const bool use_dust = qmask_dust();                        // vsearch --qmask dust (its default)
+  if (use_dust) { HIPCHK(dmask.alloc((size_t)ctx->h_woff[n] + 1)); launch_dust(ctx->rd, dmask.p, ctx->st); }
+  launch_orient(ctx->rd, ctx->d_orient_db.p, use_dust ? dmask.p : nullptr, d_s.p, d_f.p, d_r.p, ctx->st);
+  if (ctx->Lmax - 11 > 12000) {
+    std::vector<int32_t> &longs = ctx->h_orient_longs;      // (the context's: alive until the copy that upload() enqueues has run)
+    longs.clear();
+    for (int64_t r = 0; r < n; r++) if (ctx->h_len[(size_t)r] - 11 > 12000) longs.push_back((int32_t)r);
+    HIPCHK(upload(ctx->w_orient_list, longs, ctx->st));
+    const size_t tw = (size_t)orient_long_table_words((int64_t)longs.size());
+    const bool fresh = !ctx->w_orient_tab.p || ctx->w_orient_tab.cap < tw;
+    HIPCHK(ctx->w_orient_tab.alloc(tw));
+    if (fresh) HIPCHK(hipMemsetAsync(ctx->w_orient_tab.p, 0, ctx->w_orient_tab.cap * sizeof(uint32_t), ctx->st));
+    launch_orient_long(ctx->rd, ctx->w_orient_list.p, (int64_t)longs.size(), ctx->d_orient_db.p, use_dust ? dmask.p : nullptr, ctx->w_orient_tab.p,
+                       d_s.p, d_f.p, d_r.p, ctx->st);
+  }
+  HIPCHK(hipGetLastError());
+  return ITSX_OK;
+}
+
+// ... and fetched: strand (and the counts, where wanted) on the host when this returns.  The long reads' word sets are empty between
+// calls only if k_orient_long ran to its end: after any failure they are given up, and the next call starts from a zeroed buffer
+static int orient_device(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t *count_rev, DBuf<int8_t> &d_s)
+{
+  const int64_t n = ctx->N;
+  DBuf<int32_t> d_f, d_r; DBuf<uint32_t> dmask;
+  const int rc = [&]() -> int {
+    { const int rc1 = orient_enqueue(ctx, d_s, d_f, d_r, dmask); if (rc1 != ITSX_OK) return rc1; }
+    HIPCHK(hipMemcpyAsync(strand, d_s.p, (size_t)n, hipMemcpyDeviceToHost, ctx->st));
+    if (count_fwd) HIPCHK(hipMemcpyAsync(count_fwd, d_f.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
+    if (count_rev) HIPCHK(hipMemcpyAsync(count_rev, d_r.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    HIPCHK(hipGetLastError());
+    return ITSX_OK;
+  }();
+  if (rc != ITSX_OK) ctx->w_orient_tab.release();
+  return rc;
+}
+
 int itsx_orient(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t *count_rev)
 {
   CTXCHK(ctx && strand);
   if (!ctx->have_orient_db) SET_ERR(ctx, ITSX_E_ARG, "itsx_orient called before itsx_orient_load_db");
-  if (ctx->Lmax - 11 > 12000) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "reads longer than 12011 bases are not supported by the orientation kernel");
   HIPCHK(hipSetDevice(ctx->device));
   const int64_t n = ctx->N;
   if (n == 0) return ITSX_OK;
-  DBuf<int8_t> d_s; DBuf<int32_t> d_f, d_r;
-  HIPCHK(d_s.alloc((size_t)n)); HIPCHK(d_f.alloc((size_t)n)); HIPCHK(d_r.alloc((size_t)n));
-  DBuf<uint32_t> dmask;
-  const bool use_dust = qmask_dust();                        // vsearch --qmask dust (its default)
-  if (use_dust) { HIPCHK(dmask.alloc((size_t)ctx->h_woff[n] + 1)); launch_dust(ctx->rd, dmask.p, ctx->st); }
-  launch_orient(ctx->rd, ctx->d_orient_db.p, use_dust ? dmask.p : nullptr, d_s.p, d_f.p, d_r.p, ctx->st);
+  DBuf<int8_t> d_s;
+  return orient_device(ctx, strand, count_fwd, count_rev, d_s);
+}
+
+extern "C++" { template <class T> static void dbuf_swap(DBuf<T> &a, DBuf<T> &b) { std::swap(a.p, b.p); std::swap(a.n, b.n); std::swap(a.cap, b.cap); } }
+static int host_bases(const itsx_ctx *cctx);
+
+// The context's reads oriented and replaced, where they are, by the reads vsearch --orient --fastqout keeps: the state
+// itsx_load_reads_files leaves after loading the samples' oriented.fq files.  The device side is a plan (what each kept read's words and
+// exceptions are and where they go) and a scatter into fresh buffers (k_orient.hip); the host needs the strand vector alone and compacts
+// its labels, offsets and text -- the reverse reads' text reverse-complemented with the table the oriented FASTQ writer uses -- while
+// those kernels run.  Everything is built beside the read set and swapped in at the end: whatever fails, the context keeps what it had.
+int itsx_orient_apply(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t *count_rev, int64_t *n_kept_per_sample)
+{
+  CTXCHK(ctx);
+  if (!ctx->have_orient_db) SET_ERR(ctx, ITSX_E_ARG, "itsx_orient_apply called before itsx_orient_load_db");
+  HIPCHK(hipSetDevice(ctx->device));
+  const int64_t n = ctx->N;
+  const int32_t S = ctx->S;
+  if (!ctx->bases_view) { const int rc = host_bases(ctx); if (rc != ITSX_OK) return rc; }      // reads handed over in device memory: their text comes back first
+  hipStream_t st = ctx->st;
+  std::vector<int8_t> hs((size_t)n + 1, 0);
+  DBuf<int8_t> d_s;
+  if (n > 0) { const int rc = orient_device(ctx, hs.data(), count_fwd, count_rev, d_s); if (rc != ITSX_OK) return rc; }
+  // ---- what the host knows from the strands: the kept reads, their offsets, their words
+  int64_t m = 0;
+  for (int64_t r = 0; r < n; r++) m += hs[(size_t)r] != 0;
+  std::vector<int64_t> off((size_t)m + 1, 0), woff((size_t)m + 1, 0); std::vector<int32_t> len((size_t)m), smp, from((size_t)m);
+  std::vector<int64_t> scnt((size_t)S, 0);
+  if (S > 1) smp.resize((size_t)m);
+  int Lmax = 0;
+  {
+    int64_t j = 0;
+    for (int64_t r = 0; r < n; r++) {
+      if (!hs[(size_t)r]) continue;
+      const int32_t L = ctx->h_len[(size_t)r];
+      from[(size_t)j] = (int32_t)r; len[(size_t)j] = L; Lmax = std::max(Lmax, (int)L);
+      off[(size_t)j + 1] = off[(size_t)j] + L;
+      woff[(size_t)j + 1] = woff[(size_t)j] + (ctx->h_woff[(size_t)r + 1] - ctx->h_woff[(size_t)r]);
+      if (S > 1) { smp[(size_t)j] = ctx->h_sample[(size_t)r]; scnt[(size_t)smp[(size_t)j]]++; }
+      j++;
+    }
+    if (S == 1) scnt[0] = m;
+  }
+  // ---- the device side, enqueued: plan and scatter into fresh buffers
+  DBuf<uint32_t> n_words, n_exc; DBuf<int64_t> n_woff, n_excoff, d_blk, d_tot, d_scnt; DBuf<int32_t> n_len, n_sample, d_src;
+  HIPCHK(n_words.alloc((size_t)woff[(size_t)m] + 1)); HIPCHK(n_exc.alloc(std::max<size_t>(ctx->d_exc.n, 1)));
+  HIPCHK(n_woff.alloc((size_t)m + 1)); HIPCHK(n_excoff.alloc((size_t)m + 1)); HIPCHK(n_len.alloc((size_t)m + 1));
+  if (S > 1) HIPCHK(n_sample.alloc((size_t)m + 1));
+  int64_t tot[3] = {0, 0, 0};
+  std::vector<int64_t> dcnt((size_t)S, 0);
+  if (n > 0) {
+    const int64_t nb = orient_apply_blocks(n);
+    HIPCHK(d_blk.alloc((size_t)nb * 3)); HIPCHK(d_tot.alloc(3)); HIPCHK(d_src.alloc((size_t)m + 1));
+    OrientApplyArgs a{};
+    a.rd = ctx->rd; a.strand = d_s.p; a.blk = d_blk.p; a.total = d_tot.p; a.src = d_src.p;
+    a.woff = n_woff.p; a.excoff = n_excoff.p; a.len = n_len.p; a.words = n_words.p; a.exc = n_exc.p;
+    if (S > 1) {
+      HIPCHK(d_scnt.alloc((size_t)S)); HIPCHK(hipMemsetAsync(d_scnt.p, 0, (size_t)S * 8, st));
+      a.sample = ctx->d_sample.p; a.osample = n_sample.p; a.sample_count = d_scnt.p;
+    }
+    launch_orient_apply_plan(a, st);
+    launch_orient_apply_scatter(a, m, st);
+    HIPCHK(hipGetLastError());
+  } else { HIPCHK(hipMemsetAsync(n_woff.p, 0, 8, st)); HIPCHK(hipMemsetAsync(n_excoff.p, 0, 8, st)); }
+  // ---- the host side meanwhile: labels and text of the kept reads
+  NameList names;
+  if (!ctx->h_names.empty()) {
+    names.off.resize((size_t)m + 1);
+    int64_t nbytes = 0;
+    for (int64_t j = 0; j < m; j++) { names.off[(size_t)j] = nbytes; nbytes += (int64_t)ctx->h_names.len((size_t)from[(size_t)j]); }
+    names.off[(size_t)m] = nbytes;
+    names.blob.resize((size_t)nbytes);
+    for (int64_t j = 0; j < m; j++) { const size_t r = (size_t)from[(size_t)j]; if (ctx->h_names.len(r)) memcpy(names.blob.data() + names.off[(size_t)j], ctx->h_names.ptr(r), ctx->h_names.len(r)); }
+  }
+  itsx_io::Text text;
+  if (!text.resize((size_t)off[(size_t)m])) SET_ERR(ctx, ITSX_E_NOMEM, "out of memory orienting the reads' text");
+  {
+    const char *comp = itsx::iupac_complement();
+    const char *srcb = ctx->bases_view;
+    char *dst = text.data();
+    const int T = off[(size_t)m] >= (4 << 20) ? std::max(1, std::min(8, itsx_io::io_threads())) : 1;
+    on_threads(T, [&](int t) {
+      for (int64_t j = m * t / T, hi = m * (t + 1) / T; j < hi; j++) {
+        const size_t r = (size_t)from[(size_t)j];
+        const char *sb = srcb + ctx->h_off[r];
+        char *db = dst + off[(size_t)j];
+        const int64_t L = len[(size_t)j];
+        if (hs[r] > 0) memcpy(db, sb, (size_t)L);
+        else for (int64_t k = 0; k < L; k++) db[k] = comp[(unsigned char)sb[L - 1 - k]];
+      }
+    });
+  }
+  // ---- the device's own count of what it kept, and the swap
+  if (n > 0) {
+    HIPCHK(hipMemcpyAsync(tot, d_tot.p, sizeof(tot), hipMemcpyDeviceToHost, st));
+    if (S > 1) HIPCHK(hipMemcpyAsync(dcnt.data(), d_scnt.p, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(strand, d_s.p, (size_t)n, hipMemcpyDeviceToHost, ctx->st));
-  if (count_fwd) HIPCHK(hipMemcpyAsync(count_fwd, d_f.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
-  if (count_rev) HIPCHK(hipMemcpyAsync(count_rev, d_r.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
-  HIPCHK(hipStreamSynchronize(ctx->st));
+  if (n > 0 && (tot[0] != m || tot[1] != woff[(size_t)m] || (S > 1 && dcnt != scnt)))
+    SET_ERR(ctx, ITSX_E_DEVICE, "the oriented reads counted on the device and on the host differ");
+  dbuf_swap(ctx->d_words, n_words); dbuf_swap(ctx->d_exc, n_exc); dbuf_swap(ctx->d_woff, n_woff); dbuf_swap(ctx->d_excoff, n_excoff); dbuf_swap(ctx->d_len, n_len);
+  if (S > 1) dbuf_swap(ctx->d_sample, n_sample);
+  ctx->rd.words = ctx->d_words.p; ctx->rd.woff = ctx->d_woff.p; ctx->rd.len = ctx->d_len.p;
+  ctx->rd.excoff = ctx->d_excoff.p; ctx->rd.exc = ctx->d_exc.p; ctx->rd.n = m;
+  ctx->N = m; ctx->Lmax = Lmax;
+  ctx->h_off.swap(off); ctx->h_woff.swap(woff); ctx->h_len.swap(len); ctx->h_names.swap(names);
+  if (S > 1) ctx->h_sample.swap(smp);
+  ctx->h_bases.swap(text); ctx->bases_view = ctx->h_bases.data();
+  ctx->dev_bases = nullptr; ctx->d_merged_text.release();      // the text of the read set that was: this one's is on the host
+  ctx->have_derep = ctx->have_search = ctx->have_final = false;
+  ctx->order_cache_ok = false; ctx->sel_sample = -1; ctx->h_usample.clear();
+  ctx->stats.n_reads = m;
+  if (strand && n > 0) memcpy(strand, hs.data(), (size_t)n);
+  if (n_kept_per_sample) for (int32_t s = 0; s < S; s++) n_kept_per_sample[s] = scnt[(size_t)s];
   return ITSX_OK;
 }
 
@@ -3951,7 +4103,6 @@ int itsx_merge_tables(double *q2p, double *match, double *mism, uint8_t *qsame, 
 
 // what the merge kernel read and wrote, kept in device memory for the compaction that follows it (merge_load_core)
 struct MergeKeep { DBuf<uint8_t> os; DBuf<int64_t> fo, ro; DBuf<int32_t> len, reason; };
-extern "C++" { template <class T> static void dbuf_swap(DBuf<T> &a, DBuf<T> &b) { std::swap(a.p, b.p); std::swap(a.n, b.n); std::swap(a.cap, b.cap); } }
 // keep (may be null): the merged bases stay in device memory (pair i's at foff[i] + roff[i]) together with the pairs' offsets, lengths
 // and reasons, all taken over by *keep; the bases are copied back only if out_seq is given -- the merge-and-load calls pack them where
 // they are

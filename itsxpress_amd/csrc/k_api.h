@@ -119,6 +119,28 @@ void launch_cl_finalize(int32_t nk, const int32_t *order, const int32_t *res_col
 // ---- f4: read orientation (k_cluster.hip)
 void launch_orient(const ReadsDev &rd, const uint32_t *dbbits /*4^12 bits*/, const uint32_t *dmask /*k_dust, or nullptr*/, int8_t *strand, int32_t *cfwd, int32_t *crev, hipStream_t st);
 void launch_dust(const ReadsDev &rd, uint32_t *dmask, hipStream_t st);
+// k_orient.hip: the reads launch_orient leaves at 0 / 0 (more than 12 011 bases), from a work list of their indices; tabs = the blocks' word
+// sets, orient_long_table_words(n_long) words that are ZERO when the kernel starts and zero again when it ends
+int64_t orient_long_table_words(int64_t n_long);
+void launch_orient_long(const ReadsDev &rd, const int32_t *list, int64_t n_long, const uint32_t *dbbits, const uint32_t *dmask, uint32_t *tabs,
+                        int8_t *strand, int32_t *cfwd, int32_t *crev, hipStream_t st);
+// k_orient.hip: the reads with strand != 0 as a new read set, the reverse ones reverse-complemented (itsx_orient_apply).  m = the kept reads.
+struct OrientApplyArgs {
+  ReadsDev rd;                                  // the read set as it is
+  const int8_t *strand;                         // [n]
+  const int32_t *sample;                        // [n] or nullptr (one sample)
+  int64_t *blk;                                 // [3 x orient_apply_blocks(n)] scratch
+  int64_t *total;                               // [3] kept reads, their words, their exceptions
+  int32_t *src;                                 // [m] the input read of output read j
+  int64_t *woff, *excoff;                       // [m + 1]
+  int32_t *len, *osample;                       // [m]; osample with `sample` only
+  int64_t *sample_count;                        // [samples], zeroed by the caller (with `sample` only)
+  uint32_t *words, *exc;                        // the output's words (as many as the kept reads hold) and exceptions (at most the input's)
+};
+int64_t orient_apply_blocks(int64_t n);
+int orient_apply_tile();
+void launch_orient_apply_plan(const OrientApplyArgs &a, hipStream_t st);
+void launch_orient_apply_scatter(const OrientApplyArgs &a, int64_t m, hipStream_t st);
 
 // ---- k_merge.hip (paired-end merge)
 struct MergeArgs {

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include "engine.h"
 #include "k_api.h"
+#include "k_scan.h"
 
 namespace itsx {
 
@@ -168,29 +169,13 @@ constexpr int MC_BLOCK = 256;
 constexpr int MC_ITEMS = 8;
 constexpr int MC_TILE = MC_BLOCK * MC_ITEMS;   // pairs per block; thread t owns MC_ITEMS consecutive pairs
 
-// exclusive prefix of (c, l) over the block's threads in thread order, and the block's sums: a wave64 shuffle scan, one LDS partial per
-// wave, nothing assumed across waves but the barrier.  May be called again: the partials are free when it returns.
+// exclusive prefix of (c, l) over the block's threads in thread order, and the block's sums (k_scan.h)
 __device__ __forceinline__ void mc_block_scan(int64_t c, int64_t l, int64_t &ec, int64_t &el, int64_t &tc, int64_t &tl)
 {
-  __shared__ int64_t wc[MC_BLOCK / 64], wl[MC_BLOCK / 64];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int64_t ic = c, il = l;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t uc = __shfl_up(ic, d, 64), ul = __shfl_up(il, d, 64);
-    if (lane >= d) { ic += uc; il += ul; }
-  }
-  if (lane == 63) { wc[wid] = ic; wl[wid] = il; }
-  __syncthreads();
-  int64_t oc = 0, ol = 0;
-  tc = 0; tl = 0;
-#pragma unroll
-  for (int w = 0; w < MC_BLOCK / 64; w++) {
-    if (w < wid) { oc += wc[w]; ol += wl[w]; }
-    tc += wc[w]; tl += wl[w];
-  }
-  ec = oc + ic - c; el = ol + il - l;
-  __syncthreads();
+  const int64_t v[2] = {c, l};
+  int64_t ex[2], tot[2];
+  block_scan64<2, MC_BLOCK>(v, ex, tot);
+  ec = ex[0]; el = ex[1]; tc = tot[0]; tl = tot[1];
 }
 
 template <bool SCATTER> __global__ __launch_bounds__(MC_BLOCK) void k_merge_compact(MergeCompactArgs a)

@@ -28,6 +28,7 @@
 #include <unistd.h>
 #include "../../include/itsx_hip.h"
 #include "fastq_io.h"
+#include "iupac.h"
 
 namespace {
 
@@ -751,14 +752,7 @@ int itsx_write_oriented_fastq(const char *seq_path, const char *out_path, const 
   Records in; Writer out;
   if (!in.open(seq_path)) return ITSX_E_IO;
   if (!out.open(out_path, itsx_io::PLAIN, true)) return ITSX_E_IO;      // oriented.fq is read back by the loader and the trimmer
-  static char comp[256];
-  static bool init = false;
-  if (!init) {
-    for (int i = 0; i < 256; i++) comp[i] = (char)i;
-    const char *a = "ACGTURYMKSWHBVDNacgturymkswhbvdn", *b = "TGCAAYRKMSWDVBHNtgcaayrkmswdvbhn";
-    for (int i = 0; a[i]; i++) comp[(unsigned char)a[i]] = b[i];
-    init = true;
-  }
+  const char *comp = itsx::iupac_complement();      // (iupac.h: itsx_orient_apply orients the host text with the same table)
   Rec rec; int64_t i = 0, nw = 0; int rc;
   std::string t, q;
   while ((rc = in.next(rec)) == 1) {

@@ -248,6 +248,21 @@ class Engine:
         self._chk(self.L.itsx_orient(self.h, strand.ctypes.data, cf.ctypes.data, cr.ctypes.data))
         return strand[:self.n_reads], cf[:self.n_reads], cr[:self.n_reads]
 
+    def orient_apply(self):
+        """orient the loaded reads (every sample of a batch) and make the reads `vsearch --orient --fastqout` keeps this engine's read
+        set, on the device: forward reads as they are, reverse ones reverse-complemented, undetermined ones dropped -- the state
+        load_reads_files leaves after loading the samples' oriented.fq files.  Returns (strand, count_fwd, count_rev) of the reads
+        BEFORE the call and the reads kept per sample."""
+        n = self.n_reads
+        strand = np.zeros(max(1, n), np.int8)
+        cf = np.zeros(max(1, n), np.int32)
+        cr = np.zeros(max(1, n), np.int32)
+        kept = np.zeros(max(1, self.n_samples), np.int64)
+        self._chk(self.L.itsx_orient_apply(self.h, strand.ctypes.data, cf.ctypes.data, cr.ctypes.data, kept.ctypes.data))
+        kept = kept[:max(1, self.n_samples)]
+        self.n_reads, self.n_unique = int(kept.sum()), 0
+        return strand[:n], cf[:n], cr[:n], kept
+
     def orient_file(self, fastq):
         """load a FASTQ file and orient its reads (what SeqSample.orient_reads needs in one call)"""
         self.load_reads_file(fastq)

@@ -6,7 +6,13 @@ Checks that both give the same per-read coordinates.  Usage: python scripts/batc
 (`SeqSamplePairedNotInterleaved._merge_reads` + `deduplicate` + `_search`, what q2_itsxpress.py:72-80 + 273-333 do per manifest
 row) against `SampleBatch.merge_reads` + `deduplicate` + `_search`, in one process on one shared context; checks that every sample's
 seq.fq (where written) / uc.txt / rep.fa / domtbl.txt are the same bytes.  ITSXPRESS_ARRAYS / ITSXPRESS_DOMTBL apply as usual.
-Usage: python scripts/batch_bench.py --paired [n_samples] [pairs_per_sample]"""
+Usage: python scripts/batch_bench.py --paired [n_samples] [pairs_per_sample]
+
+--orient: the same comparison for single-end CCS-style samples that are oriented first (the plugin with trim_ccs, q2_itsxpress.py:284-285):
+S samples of n reads cut from the orientation database's sequences, some reverse-complemented, one by one
+(`SeqSampleNotPaired.orient_reads` + `deduplicate` + `_search`) against `SampleBatch.orient_reads` + `deduplicate` + `_search`; checks
+that every sample's oriented.fq / uc.txt / rep.fa / domtbl.txt are the same bytes.
+Usage: python scripts/batch_bench.py --orient [n_samples] [reads_per_sample]"""
 import gzip
 import hashlib
 import json
@@ -26,7 +32,8 @@ from bench import its2_profiles  # noqa: E402
 from itsxpress_amd import Engine  # noqa: E402
 
 PAIRED = "--paired" in sys.argv
-argv = [a for a in sys.argv[1:] if a != "--paired"]
+ORIENT = "--orient" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--paired", "--orient")]
 S = int(argv[0]) if len(argv) > 0 else 96
 n = int(argv[1]) if len(argv) > 1 else 10000
 thmm = gzip.open(ROOT + "/tests/golden/T.hmm.gz", "rt").read()
@@ -138,9 +145,118 @@ def paired_main():
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def write_orient_sample(d, s, n_reads, db):
+    """one sample's reads (plain FASTQ): stretches of 300-900 bases of the orientation database's sequences with 0.5 % substitutions,
+    two of five reverse-complemented, every fifth read sequenced twice (something to dereplicate)"""
+    rng = np.random.default_rng(2000 + s)
+    comp = bytes.maketrans(b"ACGTURYMKSWHBVDN", b"TGCAAYRKMSWDVBHN")
+    recs = []
+    for i in range(n_reads):
+        if i % 5 == 4 and recs:
+            seq = recs[int(rng.integers(0, len(recs)))][1]
+        else:
+            src = db[int(rng.integers(0, len(db)))]
+            L = min(len(src), int(rng.integers(300, 901)))
+            a = int(rng.integers(0, len(src) - L + 1))
+            seq = bytearray(src[a:a + L])
+            for p in np.nonzero(rng.random(L) < 0.005)[0]:
+                seq[p] = b"ACGT"[int(rng.integers(0, 4))]
+            seq = bytes(seq)
+            if i % 5 in (1, 3):
+                seq = seq.translate(comp)[::-1]
+        recs.append((b"s%04d_%07d" % (s, i), seq))
+    path = os.path.join(d, "s%04d_ccs.fastq" % s)
+    with open(path, "wb") as f:
+        for name, seq in recs:
+            f.write(b"@" + name + b"\n" + seq + b"\n+\n" + b"I" * len(seq) + b"\n")
+    return path
+
+
+def orient_main():
+    import importlib
+    import itsxpress_amd.definitions as definitions
+    os.environ.setdefault("ITSXPRESS_DB_DIR", ROOT + "/tests/golden")      # where the orientation database lies unless the caller says otherwise
+    importlib.reload(definitions)
+    from itsxpress_amd import SeqSampleNotPaired
+    from itsxpress_amd.SeqSample import _fast_from_env
+    from itsxpress_amd.batch import SampleBatch
+    from itsxpress_amd.definitions import ROOT_DIR
+    from itsxpress_amd.trim import cache_clear
+    db, cur = [], []
+    for line in gzip.open(os.path.join(ROOT_DIR, "universal_orient_ref_clean.fasta.gz"), "rb"):
+        if line.startswith(b">"):
+            if cur:
+                db.append(b"".join(cur))
+            cur = []
+        else:
+            cur.append(line.strip().upper())
+    if cur:
+        db.append(b"".join(cur))
+    tmp = tempfile.mkdtemp(prefix="itsx_batch_bench_")
+    try:
+        files = [write_orient_sample(tmp, s, n, db) for s in range(S)]
+        hmm = os.path.join(tmp, "its2.hmm")
+        with open(hmm, "w") as f:
+            f.write(its2_profiles(thmm))
+        eng = Engine(0)
+        kinds = ("seq_file", "uc_file", "rep_file", "dom_file")
+
+        def digest(objs):                      # per sample, one hash per file: a difference names its file
+            return [[hashlib.sha256(open(str(getattr(o, k)), "rb").read() if os.path.exists(str(getattr(o, k))) else b"-").hexdigest() for k in kinds]
+                    for o in objs]
+
+        def one_by_one(fs, tag):
+            objs = []
+            for k, f in enumerate(fs):
+                o = SeqSampleNotPaired(f, os.path.join(tmp, tag, "%04d" % k))
+                o._engine = eng
+                o.orient_reads(threads=1)
+                o.deduplicate(threads=1)
+                o._search(hmmfile=hmm, threads=1)
+                objs.append(o)
+            return objs
+
+        def batched(fs, tag):
+            objs = [SeqSampleNotPaired(f, os.path.join(tmp, tag)) for f in fs]
+            b = SampleBatch(objs, engine=eng)
+            b.orient_reads(threads=1)
+            b.deduplicate(threads=1)
+            b._search(hmmfile=hmm, threads=1)
+            return objs, b
+
+        one_by_one(files[:2], "warm1")         # warm-up on two samples: first-touch costs outside the timed legs
+        eng.set_rows_mode(None)
+        batched(files[:2], "warm2")
+        cache_clear()                          # each leg starts with an empty text cache
+        t0 = time.perf_counter()
+        solo = one_by_one(files, "solo")
+        t_one = time.perf_counter() - t0
+        d_one = digest(solo) if not _fast_from_env() else None
+        eng.set_rows_mode(None)
+        cache_clear()
+        t0 = time.perf_counter()
+        objs, b = batched(files, "batch")
+        t_bat = time.perf_counter() - t0
+        d_bat = digest(objs) if d_one is not None else None
+        same = None if d_one is None else d_one == d_bat
+        if same is False:                      # which files of which samples differ
+            bad = [(i, k) for i, (x, y) in enumerate(zip(d_one, d_bat)) for k, a, c in zip(kinds, x, y) if a != c]
+            print("differing files (sample, kind), the first of %d: %s" % (len(bad), bad[:12]), file=sys.stderr)
+        print(json.dumps({"orient": True, "samples": S, "reads_per_sample": n, "oriented_reads": int(b.counts.sum()),
+                          "arrays_mode": _fast_from_env(), "domtbl": os.environ.get("ITSXPRESS_DOMTBL", "full"),
+                          "one_by_one_s": round(t_one, 3), "batched_s": round(t_bat, 3), "one_by_one_over_batched": round(t_one / t_bat, 2),
+                          "reads_per_s_one_by_one": round(S * n / t_one), "reads_per_s_batched": round(S * n / t_bat),
+                          "identical_files": same}))
+        return 1 if same is False else 0       # the files of the two legs must be the same bytes
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 if PAIRED:
     paired_main()
     sys.exit(0)
+if ORIENT:
+    sys.exit(orient_main())
 eng = Engine(0)
 eng.load_profiles(text=its2_profiles(thmm))
 parts = [synth.make_reads(thmm, n, config=2, seed=synth.SEED + 100 + s) for s in range(S)]
