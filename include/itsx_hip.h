@@ -6,6 +6,9 @@
  * coordinates.  In the reference this path is three Python methods that shell
  * out to vsearch / hmmsearch and two parsers that re-read their output files.
  * Every entry point below names the reference interface it replaces.
+ * A batch of samples goes from raw files to trimmed FASTQ in a handful of calls: with itsx_keep_records on, the read set that
+ * itsx_load_reads_files / itsx_merge_pairs_load_files / itsx_orient_apply leave also keeps its FASTQ records on the device, and
+ * itsx_write_trimmed_samples cuts every sample's output from them -- no seq.fq / oriented.fq in between.
  *
  * Conventions: plain C types only; every call returns 0 on success or a negative
  * ITSX_E_* code, with text available from itsx_last_error(); the caller owns all
@@ -330,6 +333,30 @@ int itsx_merge_pairs_load_files(itsx_ctx *ctx, const char *const *r1_paths, cons
                                 int32_t n_samples, int maxdiffs, double maxee, int allow_stagger,
                                 int64_t *n_pairs_per_sample, int64_t *n_merged_per_sample);
 int itsx_merge_tables(double *q2p, double *match, double *mism, uint8_t *qsame, uint8_t *qdiff);
+
+/* ---- a read set that keeps its records (opt-in; off by default, and off costs nothing).  While on, every read set made by
+ * itsx_load_reads_files (FASTQ only: a FASTA file is ITSX_E_FORMAT, naming it), itsx_merge_pairs_load_files / itsx_merge_pairs_load and
+ * itsx_orient_apply also keeps, in device memory, what a FASTQ record needs beyond the packed words: the ASCII bases as in the input
+ * (case and IUPAC symbols; a merge's bases are upper case, as seq.fq's), the ASCII qualities (a merge's: the merged ones) and the whole
+ * title line ('@', identifier, comment; a merge's: '@' + the R1 identifier up to the first blank, as itsx_merge_pairs_files writes it;
+ * no CR).  One owned copy per read set, released with it; +2 bytes per base plus the titles.  itsx_orient_apply turns the records as
+ * itsx_write_oriented_fastq writes them (reverse reads: IUPAC-complemented reversed bases, reversed qualities; undetermined reads
+ * dropped; titles unchanged), and a failed call keeps the old read set AND its records.  A read set made any other way
+ * (itsx_set_reads*, itsx_load_reads_file / _text / _file_shard, itsx_merge_pairs_load_text) has no records. */
+int itsx_keep_records(itsx_ctx *ctx, int on);
+/* f1 for a batch: Dedup.create_trimmed_seqs (itsxpress/SeqSample.py:886-949) of every sample in one call, from the records the
+ * context keeps (itsx_keep_records).  out_paths[s] receives exactly the records itsx_write_trimmed_fastq writes for sample s's
+ * own sequence file and its slice of the coordinates (an entry may be NULL: that sample is skipped; a sample that writes nothing
+ * still gets its empty file).
+ * Coordinates: either left_prefix / right_prefix (the per-read coordinates of the finalized search, taken where they are on the
+ * device, as itsx_trim_coords_device gives them), or start / stop [n_reads] from the caller -- exactly one of the two.
+ * compression: 0 plain, 1 gzip, 2 zstd.  n_written_per_sample / total_len_per_sample: [n_samples], may be NULL.
+ * ITSX_E_ARG: no records (the message names itsx_keep_records), n_samples != itsx_num_samples, both or neither coordinate source,
+ * prefixes before itsx_search_finalize.  ITSX_E_IO: a file could not be written whole (it is removed, never left short).
+ * The text of the whole batch is made on the device (csrc/k_trim.hip) and fetched in pieces; the context's results are untouched. */
+int itsx_write_trimmed_samples(itsx_ctx *ctx, const char *const *out_paths, int32_t n_samples, int compression, int trim_ccs,
+                               const char *left_prefix, const char *right_prefix, const int32_t *start, const int32_t *stop,
+                               int64_t *n_written_per_sample, int64_t *total_len_per_sample);
 
 /* ---- a1: SeqSample.deduplicate (itsxpress/SeqSample.py:93-131)
  * = vsearch --fastx_uniques --strand both; vsearch's --minseqlength default is 1 for this command (32 for the clustering

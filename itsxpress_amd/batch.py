@@ -47,7 +47,8 @@ class SampleBatch:
     (`trim_ccs`) join the batch unoriented and `orient_reads` orients them all in one engine call.  Method names and arguments
     follow SeqSample."""
 
-    def __init__(self, samples: Sequence, engine: Optional[Engine] = None, subdirs: Optional[Sequence[str]] = None) -> None:
+    def __init__(self, samples: Sequence, engine: Optional[Engine] = None, subdirs: Optional[Sequence[str]] = None,
+                 keep_records: bool = False) -> None:
         self.samples = list(samples)
         if not self.samples:
             raise ValueError("SampleBatch needs at least one sample")
@@ -66,6 +67,10 @@ class SampleBatch:
         self._resident_read_set = None                 # and the engine's read-set number at that moment (the engine may be shared)
         self._seq_written = False                      # whether they wrote those files
         self._resident_from = "merge_reads"            # which of the two it was (for the messages)
+        # keep_records: the read sets this batch makes keep their FASTQ records on the device (itsx_keep_records) and write_trimmed cuts
+        # every sample's output from them in one engine call -- no seq.fq / oriented.fq in between
+        self.keep_records = bool(keep_records)
+        self._records_read_set = None                  # the engine's read-set number while it holds this batch's reads WITH records
 
     def _dir(self, i: int) -> str:
         d = os.path.join(self.samples[i].tempdir, self.subdirs[i])
@@ -91,7 +96,9 @@ class SampleBatch:
         if any(f is None for f in files):
             raise EngineError(-1, "the batch holds paired samples that were never merged: call merge_reads() before deduplicate() / cluster_per_sample()")
         self._resident = None
+        self.engine.keep_records(self.keep_records)
         self._set_counts(self.engine.load_reads_files(list(files)))
+        self._records_read_set = self.engine.read_set if self.keep_records else None
 
     def _left_resident(self, files, written: bool, by: str) -> None:
         """the engine holds exactly the reads of `files` (one per sample) from here on"""
@@ -99,6 +106,7 @@ class SampleBatch:
         self._resident_read_set = getattr(self.engine, "read_set", None)
         self._seq_written = written
         self._resident_from = by
+        self._records_read_set = self._resident_read_set if self.keep_records else None
 
     # -- f4 for all samples ------------------------------------------------------------------
     def orient_reads(self, threads: Union[int, str] = 1, write_seq_files: Optional[bool] = None) -> None:
@@ -107,7 +115,8 @@ class SampleBatch:
         which leaves the oriented reads of all samples on the device as the batch's read set -- `deduplicate` / `cluster_per_sample` go
         on from there without loading `oriented.fq`.  Every sample's `fastq`, `seq_file` and `r1` become `<its batch subdir>/oriented.fq`;
         the file -- byte for byte what the sample's own `orient_reads` writes -- is written unless write_seq_files is false (the default
-        is to write it in both modes: a single-end sample's trimmed output is cut from it).  `threads` is taken for the sake of
+        is to write it in both modes: a single-end sample's trimmed output is cut from it -- except in a batch with keep_records, which
+        cuts it from the records on the device and so defaults to not writing the file).  `threads` is taken for the sake of
         SeqSample's signature and ignored, as in `merge_reads`: the engine sizes its own I/O pool, and the files are written by
         min(16, samples) writers at a time."""
         try:
@@ -118,10 +127,11 @@ class SampleBatch:
                 if getattr(s, "fastq", None) is None:
                     raise ValueError("every sample needs its fastq path to orient its reads")
             eng = self.engine
-            write = True if write_seq_files is None else bool(write_seq_files)
+            write = (not self.keep_records) if write_seq_files is None else bool(write_seq_files)
             inputs = [s.fastq for s in self.samples]
             outs = [os.path.join(self._dir(i), "oriented.fq") for i in range(len(self.samples))]
             self._resident = None
+            eng.keep_records(self.keep_records)
             before = np.asarray(eng.load_reads_files(inputs), np.int64)
             eng.orient_load_db(os.path.join(ROOT_DIR, "universal_orient_ref_clean.fasta.gz"))
             strand, _, _, kept = eng.orient_apply()
@@ -153,15 +163,16 @@ class SampleBatch:
         """`_merge_reads` of every (paired) sample (SeqSample.py:266-365) in one engine call: one merge kernel over the pairs of all
         samples, the merged reads left on the device as the batch's read set.  Every sample's `seq_file` becomes
         `<its batch subdir>/seq.fq`; the file is written when write_seq_files is true (default: yes in file-compatible mode, no
-        with ITSXPRESS_ARRAYS=1), byte for byte what the sample's own `_merge_reads` writes."""
+        with ITSXPRESS_ARRAYS=1 or in a batch with keep_records), byte for byte what the sample's own `_merge_reads` writes."""
         try:
             for s in self.samples:
                 if getattr(s, "r1", None) is None or getattr(s, "fastq2", None) is None:
                     raise ValueError("Both r1 and fastq2 paths must be defined to merge reads.")
             eng = self.engine
-            write = (not _fast_from_env()) if write_seq_files is None else bool(write_seq_files)
+            write = (not _fast_from_env() and not self.keep_records) if write_seq_files is None else bool(write_seq_files)
             seq_files = [os.path.join(self._dir(i), "seq.fq") for i in range(len(self.samples))]
             self._resident = None
+            eng.keep_records(self.keep_records)
             n, m = eng.merge_pairs_load_files([s.r1 for s in self.samples], [s.fastq2 for s in self.samples], seq_files if write else None,
                                               maxdiffs=maxmismatches, maxee=2.0, allow_stagger=bool(stagger))
             for s, f in zip(self.samples, seq_files):
@@ -299,13 +310,18 @@ class SampleBatch:
     def write_trimmed(self, outfiles: Sequence[str], region: str, gzipped: bool = False, zstd_file: bool = False,
                       trim_ccs: bool = False) -> List[tuple]:
         """`Dedup.create_trimmed_seqs` of every sample from the batch's arrays: record k of sample i's seq_file trimmed to its
-        coordinates, into outfiles[i].  A paired sample's seq_file is its merged reads: merge_reads must have written it."""
+        coordinates, into outfiles[i].  A paired sample's seq_file is its merged reads: merge_reads must have written it -- unless the
+        batch keeps records (keep_records=True) and the engine still holds its read set: then every sample's output is cut from the
+        records on the device in one engine call (itsx_write_trimmed_samples), the same bytes."""
         from .trim import write_trimmed_fastq
+        left, right = _REGION_PREFIX[region]
+        if self.keep_records and self._records_read_set is not None and getattr(self.engine, "read_set", None) == self._records_read_set:
+            return self.engine.write_trimmed_samples(list(outfiles), region_prefixes=(left, right), gzipped=gzipped, zstd_file=zstd_file,
+                                                     trim_ccs=trim_ccs)
         for s in self.samples:
             if self._resident is not None and s.seq_file in self._resident and not (self._seq_written and os.path.exists(s.seq_file)):
                 raise EngineError(-1, "write_trimmed: the %s reads of this batch were never written (%s); call %s(write_seq_files=True)"
                                       % ("merged" if self._resident_from == "merge_reads" else "oriented", s.seq_file, self._resident_from))
-        left, right = _REGION_PREFIX[region]
         start, stop, _, _ = self.engine.trim_coords(left, right)
         out = []
         for i, s in enumerate(self.samples):

@@ -446,6 +446,18 @@ struct itsx_ctx {
   std::vector<unsigned long long> h_zneed;
   bool prev_lazy = false; int prev_P = 0; int64_t prev_U = 0, prev_Uc = 0;      // the last search's chunking (itsx_search)
   std::vector<int32_t> h_merge_index;      // per pair of the last merge-and-load: its merged read, -1 = not merged
+  // ---- the records of the read set (itsx_keep_records; consumer: itsx_write_trimmed_samples): what a FASTQ record needs beyond the
+  // packed words -- ASCII bases as in the input, qualities, whole title lines -- one owned copy, dropped with the read set
+  bool keep_records = false;
+  struct Records {
+    bool have = false;
+    DBuf<uint8_t> seq, qual, titles;       // bases / qualities of read r at off[r]; its title line ('@' included, no newline) at toff[r]
+    const uint8_t *seq_p = nullptr;        // the bases plane: seq.p, or after a merge d_merged_text.p (that text IS the plane)
+    DBuf<int64_t> off, toff;               // [N + 1]
+    NameList h_titles;                     // the titles on the host (itsx_orient_apply compacts them)
+    void drop() { have = false; seq_p = nullptr; seq.release(); qual.release(); titles.release(); off.release(); toff.release(); h_titles.clear(); }
+  } rec;
+  DBuf<TrimRec> w_trec; DBuf<int64_t> w_tcnt, w_ttot, w_tblk, w_tfirst, w_tbounds; DBuf<int32_t> w_tstart, w_tstop; DBuf<uint32_t> w_tout;   // itsx_write_trimmed_samples
   bool two_on = false; int share_maxrd = 0; int32_t Ub = 0; size_t sh_gslots_off = 0;
   DBuf<uint8_t> sh_rdepth_s, sh_rdepth; DBuf<unsigned long long> sh_rmask_s, sh_rmask, sh_keys, sh_keys2;
   DBuf<int32_t> sh_rparent_s, sh_rparent, sh_jlev_s, sh_jown_s, sh_endrow_s, sh_rsteps_s, sh_rnn_s, sh_rnode0_s, sh_endrow, sh_jlev, sh_jsrc, sh_jownb;
@@ -828,9 +840,24 @@ static void init_codes()
 // Hand-over of the reads: the ASCII bases travel in chunks of whole reads through three pinned staging buffers (a pool of
 // host threads copies chunk c+1 into its buffer while chunk c is on the bus and chunk c-1 is being packed), and are packed on
 // the device chunk by chunk (k_util.hip).  A pageable hipMemcpy of the whole text moved 4.4 GB (10 M merged reads) at ~5 GB/s.
+// the three pinned / device staging buffers, at least `bytes` each
+static int stage_reserve(itsx_ctx *ctx, int64_t bytes)
+{
+  if ((int64_t)ctx->stage_cap >= bytes) return ITSX_OK;
+  for (int k = 0; k < itsx_ctx::NSTAGE; k++) {
+    if (ctx->stage_pin[k]) { (void)hipHostFree(ctx->stage_pin[k]); ctx->stage_pin[k] = nullptr; }
+    HIPCHK(hipHostMalloc(&ctx->stage_pin[k], (size_t)bytes, hipHostMallocDefault));
+    HIPCHK(ctx->stage_dev[k].alloc((size_t)bytes + 16, true));
+    if (!ctx->stage_ev[k]) HIPCHK(hipEventCreateWithFlags(&ctx->stage_ev[k], hipEventDisableTiming));
+  }
+  ctx->stage_cap = (size_t)bytes;
+  return ITSX_OK;
+}
+
 static int pack_and_upload(itsx_ctx *ctx, const char *view = nullptr, const uint8_t *dev_raw = nullptr)
 {
   init_codes();
+  ctx->rec.drop();                                       // a new read set: whoever keeps records installs them after this
   const auto tp0 = std::chrono::steady_clock::now();
   const int64_t n = ctx->N;
   ctx->dev_bases = dev_raw;
@@ -876,15 +903,7 @@ static int pack_and_upload(itsx_ctx *ctx, const char *view = nullptr, const uint
   if (const char *e = sw_get("ITSX_PACK_CHUNK")) CH = std::max<int64_t>(70000, atoll(e));       // bytes; a read has at most 65535
   CH = std::min<int64_t>(CH, std::max<int64_t>(nb, 70000));
   constexpr int K = itsx_ctx::NSTAGE;
-  if (!dev_raw && (int64_t)ctx->stage_cap < CH) {
-    for (int k = 0; k < K; k++) {
-      if (ctx->stage_pin[k]) { (void)hipHostFree(ctx->stage_pin[k]); ctx->stage_pin[k] = nullptr; }
-      HIPCHK(hipHostMalloc(&ctx->stage_pin[k], (size_t)CH, hipHostMallocDefault));
-      HIPCHK(ctx->stage_dev[k].alloc((size_t)CH + 16, true));
-      if (!ctx->stage_ev[k]) HIPCHK(hipEventCreateWithFlags(&ctx->stage_ev[k], hipEventDisableTiming));
-    }
-    ctx->stage_cap = (size_t)CH;
-  }
+  if (!dev_raw) { const int src = stage_reserve(ctx, CH); if (src != ITSX_OK) return src; }
   DBuf<int64_t> &d_off = ctx->w_pk_off; DBuf<int8_t> &d_lut = ctx->w_pk_lut; DBuf<int32_t> &d_excnt = ctx->w_pk_excnt, &d_exstart = ctx->w_pk_exstart, &d_tmp = ctx->w_pk_tmp;
   DBuf<long long> &d_bad = ctx->w_pk_bad;
   HIPCHK(d_off.alloc((size_t)n + 1)); HIPCHK(d_lut.alloc(256)); HIPCHK(d_excnt.alloc((size_t)n + 2)); HIPCHK(d_exstart.alloc((size_t)n + 2));
@@ -1097,14 +1116,17 @@ static int parse_fastx(const itsx_io::Text &text, bool want_qual, bool upper, Fa
 }
 
 // appended to the context's host-side read set
-static int parse_fastx_append(itsx_ctx *ctx, const itsx_io::Text &text)
+// qual (may be null): the records' qualities are appended to it as the bases are to the read set's text
+static int parse_fastx_append(itsx_ctx *ctx, const itsx_io::Text &text, itsx_io::Text *qual = nullptr)
 {
   FastxPart part;
   part.seq.swap(ctx->h_bases); part.off.swap(ctx->h_off); part.ids.swap(ctx->h_names);
+  if (qual) part.qual.swap(*qual);
   if (part.off.empty()) part.off.assign(1, 0);
   std::string err;
-  const int rc = parse_fastx(text, false, false, part, err);
+  const int rc = parse_fastx(text, qual != nullptr, false, part, err);
   ctx->h_bases.swap(part.seq); ctx->h_off.swap(part.off); ctx->h_names.swap(part.ids);
+  if (qual) part.qual.swap(*qual);
   if (rc != ITSX_OK) SET_ERR(ctx, rc, err);
   return ITSX_OK;
 }
@@ -1217,26 +1239,84 @@ int itsx_select_sample(itsx_ctx *ctx, int32_t sample)
   ctx->order_cache_ok = false;
   return ITSX_OK;
 }
+// the title lines of a FASTQ text the parser has accepted ('@' to the end of the line, CR dropped), appended to `titles`
+static void fastq_titles(const itsx_io::Text &text, NameList &titles)
+{
+  const char *s = text.data(), *end = s + text.size();
+  auto line = [&](const char *&b, const char *&e) -> bool {
+    if (s >= end) return false;
+    b = s; const char *nl = (const char *)memchr(s, '\n', (size_t)(end - s));
+    e = nl ? nl : end; s = nl ? nl + 1 : end;
+    if (e > b && e[-1] == '\r') e--;
+    return true;
+  };
+  const char *b, *e, *x, *y;
+  while (line(b, e)) {
+    if (b == e) continue;
+    titles.emplace_back(b, e);
+    if (!line(x, y) || !line(x, y) || !line(x, y)) break;
+  }
+}
+
+// the records of the read set the context has just been given, from host planes (bases: the read set's own text and offsets)
+static int install_records(itsx_ctx *ctx, const itsx_io::Text &qual, NameList &titles)
+{
+  itsx_ctx::Records &r = ctx->rec;
+  const size_t n = (size_t)ctx->N, nb = n ? (size_t)ctx->h_off[n] : 0;
+  if (qual.size() != nb || titles.size() != n) SET_ERR(ctx, ITSX_E_FORMAT, "the records kept for the read set do not match its reads");
+  hipStream_t st = ctx->st;
+  HIPCHK(r.seq.alloc(nb + 64)); HIPCHK(r.qual.alloc(nb + 64)); HIPCHK(r.titles.alloc(titles.blob.size() + 64));
+  HIPCHK(r.off.alloc(n + 1)); HIPCHK(r.toff.alloc(n + 1));
+  if (nb) { HIPCHK(hipMemcpyAsync(r.seq.p, ctx->bases_view, nb, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(r.qual.p, qual.data(), nb, hipMemcpyHostToDevice, st)); }
+  if (!titles.blob.empty()) HIPCHK(hipMemcpyAsync(r.titles.p, titles.blob.data(), titles.blob.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(r.off.p, ctx->h_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(r.toff.p, titles.off.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  r.h_titles.swap(titles);
+  r.seq_p = r.seq.p; r.have = true;
+  return ITSX_OK;
+}
+
+int itsx_keep_records(itsx_ctx *ctx, int on)
+{
+  CTXCHK(ctx);
+  ctx->keep_records = on != 0;
+  return ITSX_OK;
+}
+
 int itsx_load_reads_files(itsx_ctx *ctx, const char *const *paths, int32_t n_paths, int64_t *n_reads_per_file)
 {
   CTXCHK(ctx && paths && n_paths >= 1);
   ctx->h_bases.clear(); ctx->h_off.assign(1, 0); ctx->h_names.clear();
   std::vector<int32_t> smp;
+  const bool records = ctx->keep_records;
+  itsx_io::Text qual; NameList titles;
   for (int32_t f = 0; f < n_paths; f++) {
     CTXCHK(paths[f]);
     std::string rerr;
     const auto tp = slurp(paths[f], true, rerr);
     if (!tp) SET_ERR(ctx, ITSX_E_IO, rerr);
     const size_t before = ctx->h_names.size();
-    { const int prc = parse_fastx_append(ctx, *tp); if (prc != ITSX_OK) { ctx->set_error(ctx->err + " (" + paths[f] + ")"); return prc; } }
+    if (records) {
+      size_t first = 0;
+      while (first < tp->size() && ((*tp)[first] == '\n' || (*tp)[first] == '\r')) first++;
+      if (first < tp->size() && (*tp)[first] == '>') SET_ERR(ctx, ITSX_E_FORMAT, std::string("records are kept (itsx_keep_records) and this file is FASTA, which has no qualities: ") + paths[f]);
+    }
+    { const int prc = parse_fastx_append(ctx, *tp, records ? &qual : nullptr); if (prc != ITSX_OK) { ctx->set_error(ctx->err + " (" + paths[f] + ")"); return prc; } }
+    if (records) {
+      fastq_titles(*tp, titles);
+      if (titles.size() != ctx->h_names.size()) SET_ERR(ctx, ITSX_E_FORMAT, std::string("records are kept (itsx_keep_records) and this file is not FASTQ throughout: ") + paths[f]);
+    }
     if (n_reads_per_file) n_reads_per_file[f] = (int64_t)(ctx->h_names.size() - before);
     smp.resize(ctx->h_names.size(), f);
   }
   ctx->N = (int64_t)ctx->h_names.size();
   if (ctx->N >= (1ll << 31) - 64) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "more than 2^31 reads in one context");
-  const int rc = pack_and_upload(ctx);
+  int rc = pack_and_upload(ctx);
   if (rc != ITSX_OK) return rc;
-  return itsx_set_samples(ctx, smp.data(), n_paths);
+  rc = itsx_set_samples(ctx, smp.data(), n_paths);
+  if (rc != ITSX_OK || !records) return rc;
+  return install_records(ctx, qual, titles);
 }
 
 // ------------------------------------------------------------------------------ derep
@@ -4009,6 +4089,27 @@ int itsx_orient_apply(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t
     launch_orient_apply_scatter(a, m, st);
     HIPCHK(hipGetLastError());
   } else { HIPCHK(hipMemsetAsync(n_woff.p, 0, 8, st)); HIPCHK(hipMemsetAsync(n_excoff.p, 0, 8, st)); }
+  // ---- the records of the kept reads (itsx_keep_records), beside the old ones like everything else: what itsx_write_oriented_fastq writes
+  const bool records = ctx->rec.have;
+  DBuf<uint8_t> r_seq, r_qual, r_titles, d_comp; DBuf<int64_t> r_off, r_toff; NameList r_names;
+  if (records) {
+    HIPCHK(r_seq.alloc((size_t)off[(size_t)m] + 64)); HIPCHK(r_qual.alloc((size_t)off[(size_t)m] + 64)); HIPCHK(r_off.alloc((size_t)m + 1)); HIPCHK(r_toff.alloc((size_t)m + 1));
+    HIPCHK(d_comp.alloc(256));
+    HIPCHK(hipMemcpyAsync(d_comp.p, itsx::iupac_complement(), 256, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(r_off.p, off.data(), ((size_t)m + 1) * 8, hipMemcpyHostToDevice, st));
+    if (m > 0) launch_trim_orient(ctx->rec.seq_p, ctx->rec.qual.p, ctx->rec.off.p, d_src.p, d_s.p, d_comp.p, r_off.p, m, r_seq.p, r_qual.p, st);
+    const NameList &ot = ctx->rec.h_titles;
+    r_names.off.resize((size_t)m + 1);
+    int64_t nbytes = 0;
+    for (int64_t j = 0; j < m; j++) { r_names.off[(size_t)j] = nbytes; nbytes += (int64_t)ot.len((size_t)from[(size_t)j]); }
+    r_names.off[(size_t)m] = nbytes;
+    r_names.blob.resize((size_t)nbytes);
+    for (int64_t j = 0; j < m; j++) { const size_t r = (size_t)from[(size_t)j]; if (ot.len(r)) memcpy(r_names.blob.data() + r_names.off[(size_t)j], ot.ptr(r), ot.len(r)); }
+    HIPCHK(r_titles.alloc((size_t)nbytes + 64));
+    if (nbytes) HIPCHK(hipMemcpyAsync(r_titles.p, r_names.blob.data(), (size_t)nbytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(r_toff.p, r_names.off.data(), ((size_t)m + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipGetLastError());
+  }
   // ---- the host side meanwhile: labels and text of the kept reads
   NameList names;
   if (!ctx->h_names.empty()) {
@@ -4054,6 +4155,11 @@ int itsx_orient_apply(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t
   ctx->h_off.swap(off); ctx->h_woff.swap(woff); ctx->h_len.swap(len); ctx->h_names.swap(names);
   if (S > 1) ctx->h_sample.swap(smp);
   ctx->h_bases.swap(text); ctx->bases_view = ctx->h_bases.data();
+  if (records) {
+    itsx_ctx::Records &rr = ctx->rec;
+    dbuf_swap(rr.seq, r_seq); dbuf_swap(rr.qual, r_qual); dbuf_swap(rr.titles, r_titles); dbuf_swap(rr.off, r_off); dbuf_swap(rr.toff, r_toff);
+    rr.h_titles.swap(r_names); rr.seq_p = rr.seq.p;
+  }
   ctx->dev_bases = nullptr; ctx->d_merged_text.release();      // the text of the read set that was: this one's is on the host
   ctx->have_derep = ctx->have_search = ctx->have_final = false;
   ctx->order_cache_ok = false; ctx->sel_sample = -1; ctx->h_usample.clear();
@@ -4102,7 +4208,7 @@ int itsx_merge_tables(double *q2p, double *match, double *mism, uint8_t *qsame, 
 }
 
 // what the merge kernel read and wrote, kept in device memory for the compaction that follows it (merge_load_core)
-struct MergeKeep { DBuf<uint8_t> os; DBuf<int64_t> fo, ro; DBuf<int32_t> len, reason; };
+struct MergeKeep { DBuf<uint8_t> os, oq; DBuf<int64_t> fo, ro; DBuf<int32_t> len, reason; bool want_oq = false; };      // oq: the merged qualities, only where records are kept
 // keep (may be null): the merged bases stay in device memory (pair i's at foff[i] + roff[i]) together with the pairs' offsets, lengths
 // and reasons, all taken over by *keep; the bases are copied back only if out_seq is given -- the merge-and-load calls pack them where
 // they are
@@ -4159,7 +4265,7 @@ static int merge_core(itsx_ctx *ctx, const char *fseq, const char *fqual, const 
   if (score) HIPCHK(hipMemcpyAsync(score, d_score.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->st));
   if (shift) HIPCHK(hipMemcpyAsync(shift, d_shift.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
   HIPCHK(hipStreamSynchronize(ctx->st));
-  if (keep) { dbuf_swap(keep->os, d_os); dbuf_swap(keep->fo, d_fo); dbuf_swap(keep->ro, d_ro); dbuf_swap(keep->len, d_len); dbuf_swap(keep->reason, d_reason); }
+  if (keep) { dbuf_swap(keep->os, d_os); if (keep->want_oq) dbuf_swap(keep->oq, d_oq); dbuf_swap(keep->fo, d_fo); dbuf_swap(keep->ro, d_ro); dbuf_swap(keep->len, d_len); dbuf_swap(keep->reason, d_reason); }
   return ITSX_OK;
 }
 int itsx_merge_buffers(itsx_ctx *ctx, const char *fseq, const char *fqual, const int64_t *foff, const char *rseq, const char *rqual,
@@ -4250,7 +4356,8 @@ static int parse_fastq_side(const char *path, const char *text, int64_t nb, Fast
 // packed.  The host walks the pairs once, for the labels, while the gather runs.  seq_out_paths (may be null, entries may be null): the
 // sample's merged records as itsx_merge_pairs_files writes them -- the only case in which merged bases and qualities come back.
 static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r, const std::vector<const NameList *> &ids, const std::vector<int64_t> &pstart,
-                           const char *const *seq_out_paths, int maxdiffs, double maxee, int allow_stagger, double parse_ms, int64_t *n_merged_per_sample)
+                           const char *const *seq_out_paths, int maxdiffs, double maxee, int allow_stagger, double parse_ms, int64_t *n_merged_per_sample,
+                           bool records = false)
 {
   const int32_t S = (int32_t)pstart.size() - 1;
   const int64_t n = pstart[(size_t)S];
@@ -4263,6 +4370,7 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
   std::string oseq, oqual;
   if (want_text) { oseq.assign((size_t)(f.seq.size() + r.seq.size()) + 1, '\0'); oqual = oseq; }
   MergeKeep k;
+  k.want_oq = records;
   int rc = merge_core(ctx, f.seq.data(), f.qual.data(), f.off.data(), r.seq.data(), r.qual.data(), r.off.data(), n, maxdiffs, maxee, allow_stagger,
                       want_text ? &oseq[0] : nullptr, want_text ? &oqual[0] : nullptr, olen.data(), reason.data(), nullptr, nullptr, &k);
   if (rc != ITSX_OK) return rc;
@@ -4297,6 +4405,12 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
   if (m > 0) {
     hipLaunchKernelGGL(k_gather_reads, dim3((unsigned)std::min<int64_t>((m + 3) / 4, 65535)), dim3(256), 0, st, k.os.p, d_src.p, d_dst.p, m, d_cmp.p);
   }
+  // records: the merged qualities through the same compaction, into a plane beside the text
+  DBuf<uint8_t> r_qual;
+  if (records) {
+    HIPCHK(r_qual.alloc((size_t)tot[1] + 64));
+    if (m > 0) hipLaunchKernelGGL(k_gather_reads, dim3((unsigned)std::min<int64_t>((m + 3) / 4, 65535)), dim3(256), 0, st, k.oq.p, d_src.p, d_dst.p, m, r_qual.p);
+  }
   // the gather has only been enqueued: the labels need `reason` alone.  (The copies back go into pageable memory and would hold the host
   // until the stream reaches them, so they are issued after the loop.)
   ctx->h_names.clear();
@@ -4319,6 +4433,24 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
   dbuf_swap(ctx->d_merged_text, d_cmp);
   rc = pack_and_upload(ctx, nullptr, m > 0 ? ctx->d_merged_text.p : &none);
   if (rc != ITSX_OK) return rc;
+  if (records) {                                         // bases = the gathered text, titles = '@' + label (what itsx_merge_pairs_files writes)
+    itsx_ctx::Records &rr = ctx->rec;
+    NameList &t = rr.h_titles;
+    t.off.resize((size_t)m + 1); t.blob.resize(ctx->h_names.blob.size() + (size_t)m);
+    for (int64_t j = 0; j < m; j++) {
+      t.off[(size_t)j] = ctx->h_names.off[(size_t)j] + j;
+      t.blob[(size_t)t.off[(size_t)j]] = '@';
+      if (ctx->h_names.len((size_t)j)) memcpy(t.blob.data() + t.off[(size_t)j] + 1, ctx->h_names.ptr((size_t)j), ctx->h_names.len((size_t)j));
+    }
+    t.off[(size_t)m] = (int64_t)t.blob.size();
+    HIPCHK(rr.titles.alloc(t.blob.size() + 64)); HIPCHK(rr.toff.alloc((size_t)m + 1)); HIPCHK(rr.off.alloc((size_t)m + 1));
+    if (!t.blob.empty()) HIPCHK(hipMemcpyAsync(rr.titles.p, t.blob.data(), t.blob.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rr.toff.p, t.off.data(), ((size_t)m + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(rr.off.p, ctx->h_off.data(), ((size_t)m + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    dbuf_swap(rr.qual, r_qual);
+    rr.seq_p = ctx->d_merged_text.p; rr.have = true;
+  }
   if (S > 1) {                                           // the state itsx_load_reads_files + itsx_set_samples leave (d_sample is filled already)
     ctx->h_sample.resize((size_t)m);
     int64_t at = 0;
@@ -4391,7 +4523,7 @@ static int merge_pairs_load_impl(itsx_ctx *ctx, const char *r1_path, const char 
   const int64_t n = (int64_t)f.ids.size();
   int64_t m = 0;
   rc = merge_load_core(ctx, f, r, {&f.ids}, {0, n}, nullptr, maxdiffs, maxee, allow_stagger,
-                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count(), &m);
+                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count(), &m, ctx->keep_records && !text1);
   if (rc != ITSX_OK) return rc;
   if (n_pairs) *n_pairs = n;
   if (n_merged) *n_merged = m;
@@ -4468,7 +4600,7 @@ static int merge_pairs_load_files_impl(itsx_ctx *ctx, const char *const *r1_path
   if (S > 1) { join(fs, F); if (!oom) join(rs, R); }
   if (oom) SET_ERR(ctx, ITSX_E_NOMEM, "out of memory joining the samples' reads");
   return merge_load_core(ctx, S > 1 ? F : fs[0], S > 1 ? R : rs[0], ids, pstart, seq_out_paths, maxdiffs, maxee, allow_stagger,
-                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count(), n_merged_per_sample);
+                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count(), n_merged_per_sample, ctx->keep_records);
 }
 int itsx_merge_pairs_load_files(itsx_ctx *ctx, const char *const *r1_paths, const char *const *r2_paths, const char *const *seq_out_paths,
                                 int32_t n_samples, int maxdiffs, double maxee, int allow_stagger, int64_t *n_pairs_per_sample, int64_t *n_merged_per_sample)
@@ -4582,6 +4714,110 @@ static int coords_device(itsx_ctx *ctx, const char *lp, const char *rp, bool per
 }
 int itsx_trim_coords_device(itsx_ctx *ctx, const char *lp, const char *rp, int32_t **d_rows, int64_t *n_rows) { return coords_device(ctx, lp, rp, true, d_rows, n_rows); }
 int itsx_rep_coords_device(itsx_ctx *ctx, const char *lp, const char *rp, int32_t **d_rows, int64_t *n_rows) { return coords_device(ctx, lp, rp, false, d_rows, n_rows); }
+// ------------------------------------------------------------------------------ f1 for a batch (k_trim.hip)
+// The trimmed FASTQ of every sample from the records the context keeps: one plan (lengths, 64-bit scan) and one copy kernel make the
+// text of the whole batch in device memory; it comes back through the pinned staging buffers in pieces, and each sample's byte range
+// goes through a BlockWriter of its own, several samples at a time.  A file that could not be written whole is removed.
+int itsx_write_trimmed_samples(itsx_ctx *ctx, const char *const *out_paths, int32_t n_samples, int compression, int trim_ccs,
+                               const char *left_prefix, const char *right_prefix, const int32_t *start, const int32_t *stop,
+                               int64_t *n_written_per_sample, int64_t *total_len_per_sample)
+{
+  CTXCHK(ctx && out_paths);
+  if (!ctx->rec.have) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_samples: the read set keeps no records; call itsx_keep_records(ctx, 1) before the reads are loaded, merged or oriented");
+  if (n_samples != ctx->S) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_samples: " + std::to_string(n_samples) + " output paths for " + std::to_string(ctx->S) + " sample(s)");
+  if (compression < 0 || compression > 2) SET_ERR(ctx, ITSX_E_ARG, "compression must be 0 (plain), 1 (gzip) or 2 (zstd)");
+  const bool by_prefix = left_prefix || right_prefix, by_arrays = start || stop;
+  if (by_prefix == by_arrays || (by_prefix && !(left_prefix && right_prefix)) || (by_arrays && !(start && stop)))
+    SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_samples: give either left_prefix and right_prefix or start and stop");
+  if (by_prefix && !ctx->have_final) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_samples: prefixes given before itsx_search_finalize");
+  { itsx_io::PieceCompressor probe(compression); if (!probe.ok()) SET_ERR(ctx, ITSX_E_IO, "zstd output requested but libzstd.so.1 could not be loaded"); }
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  const int64_t n = ctx->N; const int32_t S = ctx->S;
+  TrimPlanArgs pa{};
+  if (by_prefix) {
+    int32_t *rows = nullptr; int64_t nrows = 0;
+    const int rc = coords_device(ctx, left_prefix, right_prefix, true, &rows, &nrows);
+    if (rc != ITSX_OK) return rc;
+    pa.start = rows; pa.stop = rows + 1; pa.stride = 4;
+  } else {
+    HIPCHK(ctx->w_tstart.alloc((size_t)n + 1)); HIPCHK(ctx->w_tstop.alloc((size_t)n + 1));
+    if (n > 0) { HIPCHK(hipMemcpyAsync(ctx->w_tstart.p, start, (size_t)n * 4, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(ctx->w_tstop.p, stop, (size_t)n * 4, hipMemcpyHostToDevice, st)); }
+    pa.start = ctx->w_tstart.p; pa.stop = ctx->w_tstop.p; pa.stride = 1;
+  }
+  // samples are contiguous in the read set: sample s is reads [first[s], first[s + 1])
+  std::vector<int64_t> first((size_t)S + 1, 0), bounds((size_t)(S + 1) * 3, 0);
+  if (S > 1) { for (int64_t r = 0; r < n; r++) first[(size_t)ctx->h_sample[(size_t)r] + 1]++; for (int32_t s = 0; s < S; s++) first[(size_t)s + 1] += first[(size_t)s]; }
+  else first[1] = n;
+  HIPCHK(upload(ctx->w_tfirst, first, st));
+  HIPCHK(ctx->w_trec.alloc((size_t)n + 1)); HIPCHK(ctx->w_tcnt.alloc((size_t)n + 1)); HIPCHK(ctx->w_ttot.alloc((size_t)n + 1));
+  HIPCHK(ctx->w_tblk.alloc((size_t)trim_plan_blocks(n) * 3 + 3)); HIPCHK(ctx->w_tbounds.alloc(bounds.size()));
+  pa.off = ctx->rec.off.p; pa.toff = ctx->rec.toff.p; pa.n = n; pa.ccs = trim_ccs ? 1 : 0;
+  pa.blk = ctx->w_tblk.p; pa.rec = ctx->w_trec.p; pa.cnt = ctx->w_tcnt.p; pa.tot = ctx->w_ttot.p;
+  launch_trim_plan(pa, ctx->w_tfirst.p, S, ctx->w_tbounds.p, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(bounds.data(), ctx->w_tbounds.p, bounds.size() * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const int64_t *bo = bounds.data(), *bc = bo + (S + 1), *bt = bc + (S + 1);
+  const int64_t total = bo[S];
+  HIPCHK(ctx->w_tout.alloc((size_t)(trim_copy_bytes(total) / 4) + 16));
+  TrimCopyArgs ca{};
+  ca.rec = ctx->w_trec.p; ca.n = n; ca.seq = ctx->rec.seq_p; ca.qual = ctx->rec.qual.p; ca.titles = ctx->rec.titles.p;
+  ca.total = total; ca.ccs = pa.ccs; ca.out = ctx->w_tout.p;
+  launch_trim_copy(ca, st);
+  HIPCHK(hipGetLastError());
+  // ---- the text to the host: pieces through the pinned staging buffers, copied on while the next piece is on the bus
+  itsx_io::Text text;
+  if (!text.resize((size_t)total)) SET_ERR(ctx, ITSX_E_NOMEM, "out of memory for the batch's trimmed text");
+  if (total > 0) {
+    const int64_t CH = std::min<int64_t>(64ll << 20, std::max<int64_t>(total, 70000));
+    { const int rc = stage_reserve(ctx, CH); if (rc != ITSX_OK) return rc; }
+    const int64_t piece = (int64_t)ctx->stage_cap;
+    const int64_t np = (total + piece - 1) / piece;
+    constexpr int K = itsx_ctx::NSTAGE;
+    const uint8_t *dsrc = reinterpret_cast<const uint8_t *>(ctx->w_tout.p);
+    auto drain = [&](int64_t c) -> int {       // piece c has been enqueued: wait for it and copy it on
+      HIPCHK(hipEventSynchronize(ctx->stage_ev[c % K]));
+      const int64_t o = c * piece, b = std::min(piece, total - o);
+      memcpy(text.data() + o, ctx->stage_pin[c % K], (size_t)b);
+      return ITSX_OK;
+    };
+    for (int64_t c = 0; c < np; c++) {
+      if (c >= K) { const int rc = drain(c - K); if (rc != ITSX_OK) return rc; }
+      const int64_t o = c * piece, b = std::min(piece, total - o);
+      HIPCHK(hipMemcpyAsync(ctx->stage_pin[c % K], dsrc + o, (size_t)b, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipEventRecord(ctx->stage_ev[c % K], st));
+    }
+    for (int64_t c = std::max<int64_t>(0, np - K); c < np; c++) { const int rc = drain(c); if (rc != ITSX_OK) return rc; }
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  // ---- one file per sample, several at a time (16 threads in all, the block writers' own pools included)
+  std::vector<int32_t> todo;
+  for (int32_t s = 0; s < S; s++) if (out_paths[s]) todo.push_back(s);
+  const int T = std::max(1, std::min<int>({itsx_io::io_threads(), 16, (int)todo.size()}));
+  std::vector<std::string> werrs((size_t)T);
+  std::atomic<size_t> next{0};
+  on_threads(T, [&](int t) {
+    itsx_io::IoThreadCap share(16 / T);
+    for (;;) {
+      const size_t q = next.fetch_add(1);
+      if (q >= todo.size()) break;
+      const int32_t s = todo[q];
+      itsx_io::BlockWriter bw;
+      std::string werr;
+      if (!bw.open(out_paths[s], compression, werr)) { werrs[(size_t)t] = werr; continue; }
+      for (int64_t o = bo[s]; o < bo[s + 1]; o += (1 << 20)) bw.put(text.data() + o, (size_t)std::min<int64_t>(1 << 20, bo[s + 1] - o));
+      if (!bw.close(werr)) { werrs[(size_t)t] = werr; (void)remove(out_paths[s]); }      // never a short file
+    }
+  });
+  for (const std::string &e : werrs) if (!e.empty()) SET_ERR(ctx, ITSX_E_IO, e);
+  for (int32_t s = 0; s < S; s++) {
+    if (n_written_per_sample) n_written_per_sample[s] = bc[s + 1] - bc[s];
+    if (total_len_per_sample) total_len_per_sample[s] = bt[s + 1] - bt[s];
+  }
+  return ITSX_OK;
+}
 int itsx_derep_device(itsx_ctx *ctx, const int32_t **d_rep_of, const int32_t **d_uniq_of, const int8_t **d_strand, const int32_t **d_seed_read)
 {
   CTXCHK(ctx && ctx->have_derep);
@@ -4643,7 +4879,8 @@ static int host_bases(const itsx_ctx *cctx)
   ctx->h_bases.resize((size_t)ctx->h_off[(size_t)ctx->N]);
   if (!ctx->h_bases.empty()) HIPCHK(hipMemcpy(&ctx->h_bases[0], ctx->dev_bases, ctx->h_bases.size(), hipMemcpyDeviceToHost));
   ctx->bases_view = ctx->h_bases.data();
-  if (ctx->d_merged_text.p && ctx->dev_bases == ctx->d_merged_text.p) { ctx->d_merged_text.release(); ctx->dev_bases = nullptr; }     // the host has it now
+  // the host has it now -- unless it is the bases plane of the read set's records
+  if (ctx->d_merged_text.p && ctx->dev_bases == ctx->d_merged_text.p && !(ctx->rec.have && ctx->rec.seq_p == ctx->d_merged_text.p)) { ctx->d_merged_text.release(); ctx->dev_bases = nullptr; }
   return ITSX_OK;
 }
 // sequences of the unique representatives in input order of the seeds (what rep.fa holds), concatenated; offsets[n_unique + 1];

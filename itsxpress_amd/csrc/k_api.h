@@ -172,6 +172,35 @@ int64_t merge_compact_blocks(int64_t n);
 // total[0] = merged reads, total[1] = the bytes of their text (device memory)
 void launch_merge_compact(const MergeCompactArgs &a, int64_t *total, hipStream_t st);
 
+// ---- k_trim.hip (SURVEY 8f row f1 for a batch: the trimmed FASTQ text of every sample from the records the context keeps)
+struct alignas(16) TrimRec {                    // read r's record in the batch's text
+  int64_t out;                                  // where it starts (a read that is not written starts where the next one starts)
+  int64_t src;                                  // its first kept base / quality in the records' planes
+  int64_t toff;                                 // its title line in the title blob
+  int32_t tl, slen;                             // bytes of the title, bases kept
+};
+static_assert(sizeof(TrimRec) == 32, "k_trim_copy reads a record as two 16-byte loads");
+struct TrimPlanArgs {
+  const int32_t *start, *stop; int32_t stride;  // read r's coordinates at [r * stride] (4: the rows itsx_trim_coords_device leaves)
+  const int64_t *off, *toff;                    // [n + 1] the records' bases / qualities and titles
+  int64_t n; int32_t ccs;
+  int64_t *blk;                                 // [3 x trim_plan_blocks(n)] scratch
+  TrimRec *rec; int64_t *cnt, *tot;             // [n + 1]: before read r, the text's bytes (rec.out), the records written, their total_len
+};
+int64_t trim_plan_blocks(int64_t n);
+// bounds[3][S + 1]: bytes / records / total_len before the first read of each sample (first[S + 1], first[S] = n; device memory)
+void launch_trim_plan(const TrimPlanArgs &a, const int64_t *first, int32_t S, int64_t *bounds, hipStream_t st);
+struct TrimCopyArgs {
+  const TrimRec *rec; int64_t n;
+  const uint8_t *seq, *qual, *titles;           // every plane readable 8 bytes past its end
+  int64_t total, ntiles; int32_t ccs;           // bytes of the text (ntiles: set by the launcher)
+  uint32_t *out;                                // trim_copy_bytes(total) bytes
+};
+int64_t trim_copy_bytes(int64_t total);
+void launch_trim_copy(TrimCopyArgs a, hipStream_t st);
+void launch_trim_orient(const uint8_t *seq, const uint8_t *qual, const int64_t *off, const int32_t *from, const int8_t *strand, const uint8_t *comp,
+                        const int64_t *noff, int64_t m, uint8_t *nseq, uint8_t *nqual, hipStream_t st);
+
 // ---- k_util.hip
 // exclusive prefix sum of n int32 values (n < 2^31); tmp must hold scan_tmp_elems(n) int32
 int64_t scan_tmp_elems(int64_t n);

@@ -1,0 +1,218 @@
+// k_trim.hip -- SURVEY section 8f row f1 for a batch: the trimmed FASTQ text of every sample, made on the device from the records the
+// context keeps (itsx_keep_records): Dedup.create_trimmed_seqs (itsxpress/SeqSample.py:886-949) as trim_host.cpp states it.
+//
+// Read i is written iff start >= 0 && stop >= 0 && start < stop, as title \n [primer] bases[start:stop] [primer] \n+\n [17 x ~] quals[start:stop]
+// [17 x ~] \n, the slice clamped to the read as Python clamps it.  Three steps:
+//   plan   one output length per read (0: not written), then a two-level exclusive scan in 64-bit offsets (k_scan.h, as k_merge.hip's
+//          compaction): TrimRec[r] says where read r's record starts in the batch's text and where its three sources are.  Samples are
+//          contiguous in the read set, so a sample's file is one byte range of that text (k_trim_bounds reads the ranges off the scan).
+//   copy   OUTPUT-stationary: a block owns 16 KiB of the text, a wave-instruction stores 256 contiguous aligned bytes (one dword per lane).
+//          A lane finds the record of its dword by bisection between the records of the tile's first and last byte; where the four bytes
+//          come from one source (title, bases, qualities) they are two aligned loads and a funnel shift -- the misalignment of source
+//          against destination falls on the loads -- and at the seams (newlines, '+', primers, record ends) they are assembled byte by
+//          byte.  Work follows output bytes, not records: a 65 535-base read is spread over the blocks like anything else.
+//   orient the records of the reads itsx_orient_apply keeps: reverse reads with IUPAC-complemented reversed bases and reversed qualities.
+#include <algorithm>
+#include "engine.h"
+#include "k_api.h"
+#include "k_scan.h"
+
+namespace itsx {
+
+constexpr int TR_BLOCK = 256;
+constexpr int TR_ITEMS = 4;
+constexpr int TR_TILE = TR_BLOCK * TR_ITEMS;     // reads per block of the plan's scan; thread t owns TR_ITEMS consecutive reads
+constexpr int TC_BLOCK = 256;
+constexpr int TC_DWORDS = 16;                    // dwords per lane of a copy tile
+constexpr int64_t TC_TILE = (int64_t)TC_BLOCK * TC_DWORDS * 4;   // bytes of the text per block
+
+__device__ __forceinline__ void trim_plan_one(const TrimPlanArgs &a, int64_t r, int32_t &tl, int32_t &lo, int32_t &slen, bool &w)
+{
+  const int32_t s = a.start[r * a.stride], e = a.stop[r * a.stride];
+  const int64_t L = a.off[r + 1] - a.off[r];
+  w = s >= 0 && e >= 0 && s < e;
+  tl = (int32_t)(a.toff[r + 1] - a.toff[r]);
+  const int64_t l = s < L ? s : L, h = e < L ? e : L;          // Python's [s:e] for 0 <= s < e
+  lo = (int32_t)l; slen = (int32_t)(h > l ? h - l : 0);
+}
+
+template <bool SCATTER> __global__ __launch_bounds__(TR_BLOCK) void k_trim_plan(TrimPlanArgs a)
+{
+  const int64_t base = (int64_t)blockIdx.x * TR_TILE + (int64_t)threadIdx.x * TR_ITEMS;
+  const int64_t extra = a.ccs ? 34 : 0;
+  int32_t tl[TR_ITEMS], lo[TR_ITEMS], sl[TR_ITEMS]; bool w[TR_ITEMS];
+  int64_t v[3] = {0, 0, 0};                      // bytes of text, records, total_len as trim_host.cpp's emit counts it
+#pragma unroll
+  for (int i = 0; i < TR_ITEMS; i++) {
+    const int64_t r = base + i;
+    w[i] = false; tl[i] = lo[i] = sl[i] = 0;
+    if (r < a.n) trim_plan_one(a, r, tl[i], lo[i], sl[i], w[i]);
+    if (w[i]) { v[0] += (int64_t)tl[i] + 5 + 2 * ((int64_t)sl[i] + extra); v[1]++; v[2] += (int64_t)sl[i] + extra; }
+  }
+  int64_t ex[3], tot[3];
+  block_scan64<3, TR_BLOCK>(v, ex, tot);
+  if (!SCATTER) {
+    if (threadIdx.x == 0) { a.blk[blockIdx.x * 3 + 0] = tot[0]; a.blk[blockIdx.x * 3 + 1] = tot[1]; a.blk[blockIdx.x * 3 + 2] = tot[2]; }
+    return;
+  }
+  int64_t o = a.blk[blockIdx.x * 3 + 0] + ex[0], c = a.blk[blockIdx.x * 3 + 1] + ex[1], t = a.blk[blockIdx.x * 3 + 2] + ex[2];
+#pragma unroll
+  for (int i = 0; i < TR_ITEMS; i++) {
+    const int64_t r = base + i;
+    if (r >= a.n) break;
+    TrimRec q;
+    q.out = o; q.src = a.off[r] + lo[i]; q.toff = a.toff[r]; q.tl = tl[i]; q.slen = sl[i];
+    a.rec[r] = q; a.cnt[r] = c; a.tot[r] = t;
+    if (w[i]) { o += (int64_t)tl[i] + 5 + 2 * ((int64_t)sl[i] + extra); c++; t += (int64_t)sl[i] + extra; }
+  }
+}
+
+// the tiles' sums -> their exclusive prefixes, in place; entry n of rec / cnt / tot = the batch's totals
+__global__ __launch_bounds__(TR_BLOCK) void k_trim_plan_sums(TrimPlanArgs a, int64_t nb)
+{
+  int64_t carry[3] = {0, 0, 0};
+  for (int64_t b0 = 0; b0 < nb; b0 += TR_BLOCK) {
+    const int64_t b = b0 + threadIdx.x;
+    int64_t v[3], ex[3], tot[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) v[k] = b < nb ? a.blk[b * 3 + k] : 0;
+    block_scan64<3, TR_BLOCK>(v, ex, tot);
+#pragma unroll
+    for (int k = 0; k < 3; k++) { if (b < nb) a.blk[b * 3 + k] = carry[k] + ex[k]; carry[k] += tot[k]; }
+  }
+  if (threadIdx.x == 0) {
+    TrimRec q;
+    q.out = carry[0]; q.src = 0; q.toff = 0; q.tl = 0; q.slen = 0;
+    a.rec[a.n] = q; a.cnt[a.n] = carry[1]; a.tot[a.n] = carry[2];
+  }
+}
+
+// bounds[k][s] for k = 0 (byte offset), 1 (records), 2 (total_len) at the first read of sample s, s = 0 .. S (first[S] = n)
+__global__ void k_trim_bounds(const TrimRec *__restrict__ rec, const int64_t *__restrict__ cnt, const int64_t *__restrict__ tot, const int64_t *__restrict__ first,
+                              int32_t S, int64_t *__restrict__ bounds)
+{
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s > S) return;
+  const int64_t r = first[s];
+  bounds[s] = rec[r].out; bounds[(S + 1) + s] = cnt[r]; bounds[2 * (S + 1) + s] = tot[r];
+}
+
+int64_t trim_plan_blocks(int64_t n) { return (n + TR_TILE - 1) / TR_TILE; }
+
+void launch_trim_plan(const TrimPlanArgs &a, const int64_t *first, int32_t S, int64_t *bounds, hipStream_t st)
+{
+  const int64_t nb = trim_plan_blocks(a.n);
+  if (nb > 0) hipLaunchKernelGGL(k_trim_plan<false>, dim3((unsigned)nb), dim3(TR_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(k_trim_plan_sums, dim3(1), dim3(TR_BLOCK), 0, st, a, nb);
+  if (nb > 0) hipLaunchKernelGGL(k_trim_plan<true>, dim3((unsigned)nb), dim3(TR_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(k_trim_bounds, dim3((unsigned)((S + 1 + 255) / 256)), dim3(256), 0, st, a.rec, a.cnt, a.tot, first, S, bounds);
+}
+
+// ---- the copy ------------------------------------------------------------------------------------------------------------------
+__device__ const char TRIM_CCS_FWD[18] = "GACAGGTACAAGAAGGA", TRIM_CCS_REV[18] = "TTAACCCAGTCTCCAGT";
+
+// the last record of [lo, hi) that starts at or before byte o (rec[lo].out <= o): it holds o when o is below the batch's total, because
+// a record that is not written starts where its successor starts and so is never the last
+__device__ __forceinline__ int64_t trim_find(const TrimRec *__restrict__ rec, int64_t lo, int64_t hi, int64_t o)
+{
+  while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (rec[mid].out <= o) lo = mid; else hi = mid; }
+  return lo;
+}
+// four bytes at any address: the two aligned dwords that hold them, shifted (every source plane is padded past its end)
+__device__ __forceinline__ uint32_t trim_load4(const uint8_t *p)
+{
+  const uint32_t *w = reinterpret_cast<const uint32_t *>(reinterpret_cast<uintptr_t>(p) & ~(uintptr_t)3);
+  const uint64_t both = ((uint64_t)w[1] << 32) | w[0];
+  return (uint32_t)(both >> (8 * (unsigned)(reinterpret_cast<uintptr_t>(p) & 3)));
+}
+// byte p of record q's text
+__device__ __forceinline__ uint32_t trim_byte(const TrimCopyArgs &a, const TrimRec &q, int64_t p)
+{
+  const int64_t pre = a.ccs ? 17 : 0;
+  if (p < q.tl) return a.titles[q.toff + p];
+  p -= q.tl;
+  if (p == 0) return '\n';
+  p -= 1;
+  if (p < q.slen + 2 * pre) {
+    if (p < pre) return (uint8_t)TRIM_CCS_FWD[p];
+    p -= pre;
+    return p < q.slen ? a.seq[q.src + p] : (uint8_t)TRIM_CCS_REV[p - q.slen];
+  }
+  p -= q.slen + 2 * pre;
+  if (p < 3) return p == 1 ? '+' : '\n';
+  p -= 3;
+  if (p < q.slen + 2 * pre) {
+    p -= pre;
+    return (p >= 0 && p < q.slen) ? a.qual[q.src + p] : '~';
+  }
+  return '\n';
+}
+
+__global__ __launch_bounds__(TC_BLOCK) void k_trim_copy(TrimCopyArgs a)
+{
+  const int64_t pre = a.ccs ? 17 : 0;
+  for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const int64_t t0 = tile * TC_TILE, t1 = t0 + TC_TILE < a.total ? t0 + TC_TILE : a.total;
+    const int64_t rlo = trim_find(a.rec, 0, a.n, t0), rhi = trim_find(a.rec, rlo, a.n, t1 - 1);      // the same in every lane
+#pragma unroll 4
+    for (int j = 0; j < TC_DWORDS; j++) {
+      const int64_t o = t0 + ((int64_t)j * TC_BLOCK + threadIdx.x) * 4;
+      if (o >= t1) break;
+      int64_t r = trim_find(a.rec, rlo, rhi + 1, o);
+      TrimRec q = a.rec[r];
+      int64_t next = a.rec[r + 1].out;
+      const int64_t p = o - q.out;
+      const uint8_t *src = nullptr;
+      if (o + 4 <= next) {                       // the dword lies in one record: in one of its three sources?
+        const int64_t ps = p - q.tl - 1 - pre, pq = ps - q.slen - 2 * pre - 3;
+        if (p + 4 <= q.tl) src = a.titles + q.toff + p;
+        else if (ps >= 0 && ps + 4 <= q.slen) src = a.seq + q.src + ps;
+        else if (pq >= 0 && pq + 4 <= q.slen) src = a.qual + q.src + pq;
+      }
+      uint32_t v = 0;
+      if (src) v = trim_load4(src);
+      else {
+        for (int b = 0; b < 4; b++) {
+          const int64_t ob = o + b;
+          if (ob >= a.total) break;              // the text's last dword: the bytes past its end stay 0 (the buffer is padded to whole tiles)
+          while (ob >= next) { r++; q = a.rec[r]; next = a.rec[r + 1].out; }
+          v |= trim_byte(a, q, ob - q.out) << (8 * b);
+        }
+      }
+      a.out[o >> 2] = v;
+    }
+  }
+}
+
+int64_t trim_copy_bytes(int64_t total) { return (total + TC_TILE - 1) / TC_TILE * TC_TILE; }
+
+void launch_trim_copy(TrimCopyArgs a, hipStream_t st)
+{
+  if (a.total <= 0) return;
+  a.ntiles = (a.total + TC_TILE - 1) / TC_TILE;
+  const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, 256 * 8);
+  hipLaunchKernelGGL(k_trim_copy, dim3(grid), dim3(TC_BLOCK), 0, st, a);
+}
+
+// ---- itsx_orient_apply with records: kept read j = read from[j] of the old planes, reversed (bases complemented) where its strand is -1;
+// one wave per read, lanes along it
+__global__ __launch_bounds__(256) void k_trim_orient(const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual, const int64_t *__restrict__ off,
+                                                     const int32_t *__restrict__ from, const int8_t *__restrict__ strand, const uint8_t *__restrict__ comp,
+                                                     const int64_t *__restrict__ noff, int64_t m, uint8_t *__restrict__ nseq, uint8_t *__restrict__ nqual)
+{
+  const int lane = threadIdx.x & 63;
+  for (int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); j < m; j += (int64_t)gridDim.x * 4) {
+    const int64_t r = from[j], so = off[r], d0 = noff[j], len = noff[j + 1] - d0;
+    if (strand[r] > 0) for (int64_t k = lane; k < len; k += 64) { nseq[d0 + k] = seq[so + k]; nqual[d0 + k] = qual[so + k]; }
+    else for (int64_t k = lane; k < len; k += 64) { nseq[d0 + k] = comp[seq[so + len - 1 - k]]; nqual[d0 + k] = qual[so + len - 1 - k]; }
+  }
+}
+
+void launch_trim_orient(const uint8_t *seq, const uint8_t *qual, const int64_t *off, const int32_t *from, const int8_t *strand, const uint8_t *comp,
+                        const int64_t *noff, int64_t m, uint8_t *nseq, uint8_t *nqual, hipStream_t st)
+{
+  if (m <= 0) return;
+  hipLaunchKernelGGL(k_trim_orient, dim3((unsigned)std::min<int64_t>((m + 3) / 4, 65535)), dim3(256), 0, st, seq, qual, off, from, strand, comp, noff, m, nseq, nqual);
+}
+
+}  // namespace itsx

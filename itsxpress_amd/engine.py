@@ -560,6 +560,38 @@ class Engine:
     def rep_coords(self, left, right):
         return self._coords(self.L.itsx_rep_coords, self.n_unique, left, right)
 
+    # ---- f1 for a batch: trimmed FASTQ from the records the context keeps
+    def keep_records(self, on=True):
+        """From now on the read sets that load_reads_files / merge_pairs_load(_files) / orient_apply leave also keep their FASTQ
+        records (bases as in the input, qualities, title lines) on the device: what write_trimmed_samples cuts from."""
+        self._chk(self.L.itsx_keep_records(self.h, int(bool(on))))
+
+    def write_trimmed_samples(self, paths, region_prefixes=None, start=None, stop=None, gzipped=False, zstd_file=False, trim_ccs=False):
+        """The trimmed FASTQ of every sample of the batch (paths[s]; None skips a sample) in one call, from the records the context
+        keeps.  Coordinates: region_prefixes = (left, right) of the finalized search, or start / stop arrays over the reads --
+        exactly one of the two.  Returns the per-sample (n_written, total_len) pairs."""
+        from .trim import _compression
+        S = len(paths)
+        arr = (C.c_char_p * max(1, S))(*[None if p is None else os.fsencode(p) for p in paths])
+        left = right = None
+        if region_prefixes is not None:
+            left, right = (x.encode() for x in region_prefixes)
+        keep = []
+        for a in (start, stop):
+            if a is None:
+                keep.append(None)
+                continue
+            a = np.ascontiguousarray(a, np.int32)
+            if a.shape[0] != self.n_reads:
+                raise ValueError("write_trimmed_samples: start / stop hold one entry per read")
+            keep.append(a if a.size else np.zeros(1, np.int32))
+        nw = np.zeros(max(1, S), np.int64)
+        tot = np.zeros(max(1, S), np.int64)
+        self._chk(self.L.itsx_write_trimmed_samples(self.h, arr, S, _compression(gzipped, zstd_file), int(bool(trim_ccs)), left, right,
+                                                    None if keep[0] is None else keep[0].ctypes.data,
+                                                    None if keep[1] is None else keep[1].ctypes.data, nw.ctypes.data, tot.ctypes.data))
+        return [(int(nw[s]), int(tot[s])) for s in range(S)]
+
     # ---- writers
     def write_uc(self, path):
         self._chk(self.L.itsx_write_uc(self.h, os.fsencode(path)))

@@ -12,7 +12,13 @@ Usage: python scripts/batch_bench.py --paired [n_samples] [pairs_per_sample]
 S samples of n reads cut from the orientation database's sequences, some reverse-complemented, one by one
 (`SeqSampleNotPaired.orient_reads` + `deduplicate` + `_search`) against `SampleBatch.orient_reads` + `deduplicate` + `_search`; checks
 that every sample's oriented.fq / uc.txt / rep.fa / domtbl.txt are the same bytes.
-Usage: python scripts/batch_bench.py --orient [n_samples] [reads_per_sample]"""
+Usage: python scripts/batch_bench.py --orient [n_samples] [reads_per_sample]
+
+--trim: paired samples from raw files to each sample's trimmed merged reads, file to file: `merge_reads(write_seq_files=True)` +
+`deduplicate` + `_search` + `write_trimmed` (every seq.fq written, then parsed again by the host writer) against
+`SampleBatch(keep_records=True)` (the records stay on the device, one `itsx_write_trimmed_samples`).  Warm context, the two legs
+alternating, medians and the spread of each; checks that every sample's output is the same bytes.
+Usage: python scripts/batch_bench.py --trim [n_samples] [pairs_per_sample] [repeats]"""
 import gzip
 import hashlib
 import json
@@ -33,7 +39,8 @@ from itsxpress_amd import Engine  # noqa: E402
 
 PAIRED = "--paired" in sys.argv
 ORIENT = "--orient" in sys.argv
-argv = [a for a in sys.argv[1:] if a not in ("--paired", "--orient")]
+TRIM = "--trim" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--paired", "--orient", "--trim")]
 S = int(argv[0]) if len(argv) > 0 else 96
 n = int(argv[1]) if len(argv) > 1 else 10000
 thmm = gzip.open(ROOT + "/tests/golden/T.hmm.gz", "rt").read()
@@ -252,6 +259,75 @@ def orient_main():
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def trim_main():
+    import torch
+    from itsxpress_amd import SeqSamplePairedNotInterleaved
+    from itsxpress_amd.batch import SampleBatch
+    from itsxpress_amd.trim import cache_clear
+    os.environ["ITSXPRESS_ARRAYS"] = "0"
+    repeats = int(argv[2]) if len(argv) > 2 else 5
+    tmp = tempfile.mkdtemp(prefix="itsx_batch_bench_")
+    try:
+        files = [write_paired_sample(tmp, s, n) for s in range(S)]
+        hmm = os.path.join(tmp, "its2.hmm")
+        with open(hmm, "w") as f:
+            f.write(its2_profiles(thmm))
+        eng = Engine(0)
+
+        def leg(fs, tag, keep):
+            objs = [SeqSamplePairedNotInterleaved(r1, os.path.join(tmp, tag), r2) for r1, r2 in fs]
+            b = SampleBatch(objs, engine=eng, keep_records=keep)
+            if keep:
+                b.merge_reads(threads=1, stagger=False)
+            else:
+                b.merge_reads(threads=1, stagger=False, write_seq_files=True)
+            torch.cuda.synchronize()
+            used = torch.cuda.mem_get_info()[1] - torch.cuda.mem_get_info()[0]
+            b.deduplicate(threads=1)
+            b._search(hmmfile=hmm, threads=1)
+            outs = [os.path.join(tmp, tag, "trimmed_%04d.fq" % k) for k in range(len(objs))]
+            t0 = time.perf_counter()
+            ret = b.write_trimmed(outs, "ITS2")
+            return outs, ret, time.perf_counter() - t0, used, int(b.counts.sum())
+
+        leg(files[:2], "warm_files", False)    # warm-up on two samples: first-touch costs outside the timed legs
+        leg(files[:2], "warm_kept", True)
+        times = {False: [], True: []}
+        wtimes = {False: [], True: []}
+        used = {}
+        digests = {}
+        for r in range(repeats):               # the legs alternate; each starts with an empty text cache
+            for keep in (False, True):
+                cache_clear()
+                tag = "%s_%d" % ("kept" if keep else "files", r)
+                t0 = time.perf_counter()
+                outs, ret, tw, mem, merged = leg(files, tag, keep)
+                times[keep].append(time.perf_counter() - t0)
+                wtimes[keep].append(tw)
+                used[keep] = mem
+                if r == 0:
+                    digests[keep] = ([hashlib.sha256(open(p, "rb").read()).hexdigest() for p in outs], [tuple(x) for x in ret])
+                    nbytes = sum(os.path.getsize(p) for p in outs)
+                shutil.rmtree(os.path.join(tmp, tag), ignore_errors=True)
+        same = digests[False] == digests[True]
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        print(json.dumps({"trim": True, "samples": S, "pairs_per_sample": n, "merged_reads": merged, "repeats": repeats, "trimmed_bytes": nbytes,
+                          "files_path_s": [round(x, 3) for x in times[False]], "records_path_s": [round(x, 3) for x in times[True]],
+                          "files_path_median_s": round(med[False], 3), "records_path_median_s": round(med[True], 3),
+                          "files_path_spread_s": round(max(times[False]) - min(times[False]), 3),
+                          "write_trimmed_files_median_s": round(float(np.median(wtimes[False])), 3),
+                          "write_trimmed_records_median_s": round(float(np.median(wtimes[True])), 3),
+                          "device_bytes_after_merge_files": used[False], "device_bytes_after_merge_records": used[True],
+                          "identical_outputs": same}))
+        return 0 if same else 1
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+if TRIM:
+    if len(argv) < 1:
+        S, n = 384, 2000
+    sys.exit(trim_main())
 if PAIRED:
     paired_main()
     sys.exit(0)
