@@ -93,9 +93,11 @@ typedef struct {
   float   ms_decode_kernel;  int32_t n_batches;          /* launches of each DP kernel in the last search */
   float   ms_cluster;        int32_t pad0;               /* itsx_cluster at id < 1: whole call */
   int64_t cl_windows, cl_cuts, cl_alignments;            /* speculative windows, windows cut by validation, alignments */
-  float   ms_merge;          int32_t pad1;               /* k_merge of the last itsx_merge_* call */
+  float   ms_merge;                                      /* k_merge of the last itsx_merge_* call */
+  float   ms_trim_plan;                                  /* the plan kernels of the last itsx_write_trimmed_paired_samples call (was padding) */
   int64_t cl_certified;                                  /* candidate alignments proven rejections without the full DP */
-  float   ms_pack;           int32_t pad2;               /* last hand-over of reads: staging + upload + device packing, host wall time */
+  float   ms_pack;                                       /* last hand-over of reads: staging + upload + device packing, host wall time */
+  float   ms_trim_copy;                                  /* k_trim_copy of that call, both sides together (was padding) */
   /* parity-risk counters of the last itsx_trim_coords / itsx_rep_coords call (the prefixes decide which domains count):
    * uniques / reads whose winning left or right domain came from a region hmmsearch resolves by stochastic clustering
    * (itsx_domain.flags bit 0), and uniques / reads with a (representative, profile) pair that had more regions than
@@ -357,6 +359,32 @@ int itsx_keep_records(itsx_ctx *ctx, int on);
 int itsx_write_trimmed_samples(itsx_ctx *ctx, const char *const *out_paths, int32_t n_samples, int compression, int trim_ccs,
                                const char *left_prefix, const char *right_prefix, const int32_t *start, const int32_t *stop,
                                int64_t *n_written_per_sample, int64_t *total_len_per_sample);
+/* ---- a merged read set that keeps its ORIGINAL pairs (opt-in; off by default; independent of itsx_keep_records).  While on,
+ * itsx_merge_pairs_load and itsx_merge_pairs_load_files also keep, in device memory beside the merged read set, every pair's R1 and
+ * R2 record: the bases and qualities as the merge kernel read them (its own upload, taken over instead of freed), both whole title lines ('@' and any comment included, no CR), and per pair the merged read whose
+ * coordinates it is sliced with -- the read that R1's identifier (the title after '@' up to the first blank or TAB) NAMES among
+ * the merged reads of the SAME sample, the first of equal labels, as Dedup looks record1.id up in the sample's dictionary; a pair
+ * that did not merge but carries a merged pair's identifier has one.  The merge reads upper-case bases, so pairs whose files hold a
+ * lower-case base keep NO pair records (slices of the upload would not be the input's bytes): itsx_write_trimmed_paired_samples
+ * then returns ITSX_E_ARG and the caller uses itsx_write_trimmed_paired.  itsx_merge_pairs_load_text keeps none.  Released with the
+ * read set (whatever replaces it) and by itsx_orient_apply.  Cost: R1 + R2 bases, qualities and titles stay resident. */
+int itsx_keep_pair_records(itsx_ctx *ctx, int on);
+/* f1 for a batch of paired samples: Dedup.create_paired_trimmed_seqs (itsxpress/SeqSample.py:564-790) of every sample in one call,
+ * from the pair records the context keeps (itsx_keep_pair_records).  out1_paths[s] / out2_paths[s] receive exactly the records
+ * itsx_write_trimmed_paired writes for sample s's own R1 / R2 files, its merged reads' labels and its slice of the coordinates:
+ * a pair is written (both sides) iff its read has start >= 0, stop >= 0 and start < stop; R1[start:stop] ([start:] where
+ * stop > tlen) and R2[tlen - stop : tlen - start], clamped as Python clamps a slice.  Both entries NULL: that sample is skipped;
+ * a sample that writes nothing still gets its two empty files (gzip / zstd: a valid empty member).
+ * Coordinates: either left_prefix / right_prefix (the finalized search's per-read coordinates, taken where they are on the
+ * device), or start / stop / tlen [n_reads] from the caller -- exactly one of the two, and all three arrays.
+ * compression: 0 plain, 1 gzip, 2 zstd.  n_written_per_sample: [n_samples] pairs written, may be NULL.
+ * ITSX_E_ARG: no pair records (the message names itsx_keep_pair_records), n_samples != itsx_num_samples, one path of a sample's two
+ * NULL, both, neither or part of a coordinate source, prefixes before itsx_search_finalize.  ITSX_E_IO: zstd requested but not
+ * available, or a file could not be written whole: then every file this call was given is removed (R1's files are written before
+ * R2's, so no half of a pair of files is left behind). */
+int itsx_write_trimmed_paired_samples(itsx_ctx *ctx, const char *const *out1_paths, const char *const *out2_paths, int32_t n_samples,
+                                      int compression, int trim_ccs, const char *left_prefix, const char *right_prefix,
+                                      const int32_t *start, const int32_t *stop, const int32_t *tlen, int64_t *n_written_per_sample);
 
 /* ---- a1: SeqSample.deduplicate (itsxpress/SeqSample.py:93-131)
  * = vsearch --fastx_uniques --strand both; vsearch's --minseqlength default is 1 for this command (32 for the clustering

@@ -45,7 +45,7 @@ STATS_FIELDS = [("n_reads", "<i8"), ("n_unique", "<i8"), ("n_dropped_short", "<i
                 ("fwd_rows", "<i8"), ("ms_env_kernel", "<f4"), ("ms_bias_kernel", "<f4"), ("env_rows", "<i8"),
                 ("n_env_unique", "<i8"), ("ms_decode_kernel", "<f4"), ("n_batches", "<i4"), ("ms_cluster", "<f4"),
                 ("pad0", "<i4"), ("cl_windows", "<i8"), ("cl_cuts", "<i8"), ("cl_alignments", "<i8"), ("ms_merge", "<f4"),
-                ("pad1", "<i4"), ("cl_certified", "<i8"), ("ms_pack", "<f4"), ("pad2", "<i4"),
+                ("ms_trim_plan", "<f4"), ("cl_certified", "<i8"), ("ms_pack", "<f4"), ("ms_trim_copy", "<f4"),
                 ("n_uniq_multi_winner", "<i8"), ("n_reads_multi_winner", "<i8"), ("n_uniq_region_cap", "<i8"),
                 ("n_reads_region_cap", "<i8"), ("n_mr_clustered", "<i8"), ("n_mr_failed", "<i8"), ("n_mr_envelopes", "<i8"),
                 ("ms_ensemble", "<f4"), ("pad3", "<i4"), ("n_mr_distinct", "<i8"), ("n_slab_shrinks", "<i8"), ("ms_vit_kernel", "<f4"), ("pad4", "<i4"),
@@ -84,7 +84,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_keyset_create", "itsx_keyset_destroy", "itsx_keyset_size", "itsx_keyset_assign",
            "itsx_twriter_open", "itsx_twriter_text", "itsx_twriter_coords", "itsx_twriter_update", "itsx_twriter_close",
            "itsx_lazy_pending_uniques", "itsx_set_partial_coords", "itsx_set_kept_rows",
-           "itsx_keep_records", "itsx_write_trimmed_samples"]
+           "itsx_keep_records", "itsx_write_trimmed_samples",
+           "itsx_keep_pair_records", "itsx_write_trimmed_paired_samples"]
 
 
 def lib():
@@ -148,6 +149,8 @@ def lib():
         "itsx_set_kept_rows": (i32, [vp, i32]),
         "itsx_keep_records": (i32, [vp, i32]),
         "itsx_write_trimmed_samples": (i32, [vp, vp, i32, i32, i32, cp, cp, vp, vp, vp, vp]),
+        "itsx_keep_pair_records": (i32, [vp, i32]),
+        "itsx_write_trimmed_paired_samples": (i32, [vp, vp, vp, i32, i32, i32, cp, cp, vp, vp, vp, vp]),
         "itsx_unique_keys128": (i32, [vp, C.c_uint64, C.c_uint64, i64, vp]),
         "itsx_write_derep_arrays": (i32, [cp, cp, i64, vp, vp, vp, vp, vp, vp, vp, i64]),
         "itsx_write_domtbl_arrays": (i32, [cp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp]),

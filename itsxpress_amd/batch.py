@@ -48,7 +48,7 @@ class SampleBatch:
     follow SeqSample."""
 
     def __init__(self, samples: Sequence, engine: Optional[Engine] = None, subdirs: Optional[Sequence[str]] = None,
-                 keep_records: bool = False) -> None:
+                 keep_records: Union[bool, str] = False) -> None:
         self.samples = list(samples)
         if not self.samples:
             raise ValueError("SampleBatch needs at least one sample")
@@ -69,8 +69,15 @@ class SampleBatch:
         self._resident_from = "merge_reads"            # which of the two it was (for the messages)
         # keep_records: the read sets this batch makes keep their FASTQ records on the device (itsx_keep_records) and write_trimmed cuts
         # every sample's output from them in one engine call -- no seq.fq / oriented.fq in between
+        # keep_records="pairs": all of that, and merge_reads also keeps the ORIGINAL R1 / R2 records of every pair on the device
+        # (itsx_keep_pair_records): write_paired_trimmed cuts every sample's two files from them in one engine call, so the inputs are
+        # read once
+        if isinstance(keep_records, str) and keep_records != "pairs":
+            raise ValueError('keep_records is False, True or "pairs"')
         self.keep_records = bool(keep_records)
+        self.keep_pair_records = keep_records == "pairs"
         self._records_read_set = None                  # the engine's read-set number while it holds this batch's reads WITH records
+        self._pair_records_read_set = None             # ... and while it holds the pairs those reads were merged from (merge_reads only)
 
     def _dir(self, i: int) -> str:
         d = os.path.join(self.samples[i].tempdir, self.subdirs[i])
@@ -173,13 +180,20 @@ class SampleBatch:
             seq_files = [os.path.join(self._dir(i), "seq.fq") for i in range(len(self.samples))]
             self._resident = None
             eng.keep_records(self.keep_records)
-            n, m = eng.merge_pairs_load_files([s.r1 for s in self.samples], [s.fastq2 for s in self.samples], seq_files if write else None,
-                                              maxdiffs=maxmismatches, maxee=2.0, allow_stagger=bool(stagger))
+            if self.keep_pair_records:
+                eng.keep_pair_records(True)
+            try:
+                n, m = eng.merge_pairs_load_files([s.r1 for s in self.samples], [s.fastq2 for s in self.samples], seq_files if write else None,
+                                                  maxdiffs=maxmismatches, maxee=2.0, allow_stagger=bool(stagger))
+            finally:
+                if self.keep_pair_records:
+                    eng.keep_pair_records(False)           # (the flag is the engine's: a later merge of somebody else's keeps none)
             for s, f in zip(self.samples, seq_files):
                 s.seq_file = f
             self.n_pairs = np.asarray(n, np.int64)
             self._set_counts(m)
             self._left_resident(seq_files, write, "merge_reads")
+            self._pair_records_read_set = self._resident_read_set if self.keep_pair_records else None
             logging.info("itsx_hip batch merge: %d samples, %d pairs, %d merged", len(self.samples), int(self.n_pairs.sum()), int(self.counts.sum()))
         except EngineError as e:
             logging.exception("Could not perform read merging with the HIP engine: %s", e)
@@ -292,9 +306,24 @@ class SampleBatch:
     def write_paired_trimmed(self, outfiles1: Sequence[str], outfiles2: Sequence[str], region: str, gzipped: bool = False,
                              zstd_file: bool = False, trim_ccs: bool = False) -> List[int]:
         """`Dedup.create_paired_trimmed_seqs` of every sample from the batch's arrays: the ORIGINAL r1 / fastq2 records of sample i,
-        sliced with its merged reads' coordinates, into outfiles1[i] / outfiles2[i].  Returns the pairs written per sample."""
+        sliced with its merged reads' coordinates, into outfiles1[i] / outfiles2[i].  Returns the pairs written per sample.
+        The host writer reads and parses every sample's two files again -- unless the batch keeps the pair records
+        (keep_records="pairs") and the engine still holds its read set: then every sample's two files are cut from the records on the
+        device in one engine call (itsx_write_trimmed_paired_samples), the same bytes.  (Inputs with lower-case bases keep no pair records
+        -- the merge reads them in upper case -- and take the host loop.)"""
         from .trim import write_trimmed_paired
         left, right = _REGION_PREFIX[region]
+        if self.keep_pair_records and self._pair_records_read_set is not None and getattr(self.engine, "read_set", None) == self._pair_records_read_set:
+            try:
+                return self.engine.write_trimmed_paired_samples(list(outfiles1), list(outfiles2), region_prefixes=(left, right), gzipped=gzipped,
+                                                                zstd_file=zstd_file, trim_ccs=trim_ccs)
+            except EngineError as e:
+                # the merge kept no pair records after all: the inputs hold lower-case bases, which the merge's upper-case upload cannot
+                # give back.  The host writer copies the input's bytes.
+                # (The C ABI has no query for it; the engine's message for exactly this case names the switch -- engine.hip says so there.)
+                if e.code != -1 or "itsx_keep_pair_records" not in str(e):
+                    raise
+                self._pair_records_read_set = None
         start, stop, tlen, _ = self.engine.trim_coords(left, right)
         blob, offs = self.engine.read_names_raw()
         out = []

@@ -21,7 +21,9 @@
 #include <atomic>
 #include <condition_variable>
 #include <mutex>
+#include <string_view>
 #include <thread>
+#include <unordered_map>
 #include "detmath.h"
 #include "engine.h"
 #include "k_api.h"
@@ -457,6 +459,23 @@ struct itsx_ctx {
     NameList h_titles;                     // the titles on the host (itsx_orient_apply compacts them)
     void drop() { have = false; seq_p = nullptr; seq.release(); qual.release(); titles.release(); off.release(); toff.release(); h_titles.clear(); }
   } rec;
+  // ---- the ORIGINAL pair records of a merge-and-load (itsx_keep_pair_records; consumer: itsx_write_trimmed_paired_samples): R1's and
+  // R2's bases and qualities as the merge kernel read them (taken over from merge_core, not uploaded again), their whole title lines,
+  // and per pair the read whose coordinates it is sliced with.  Pairs are sample-contiguous (pstart).  Dropped with the read set.
+  bool keep_pair_records = false;
+  struct PairRecords {
+    bool have = false; int64_t n = 0;
+    DBuf<uint8_t> s1, q1, t1, s2, q2, t2;  // bases / qualities of pair p's R1 at o1[p], its title line at to1[p]; R2 alike
+    DBuf<int64_t> o1, to1, o2, to2;        // [n + 1]
+    DBuf<int32_t> pair_read;               // [n] the read NAMED by R1's identifier among the sample's merged reads (the first of equal labels), -1: none
+    std::vector<int64_t> pstart;           // [S + 1] sample s's pairs
+    void drop()
+    {
+      have = false; n = 0; pstart.clear(); pair_read.release();
+      s1.release(); q1.release(); t1.release(); s2.release(); q2.release(); t2.release(); o1.release(); to1.release(); o2.release(); to2.release();
+    }
+  } prec;
+  DBuf<TrimRec> w_trec2; DBuf<int32_t> w_ttlen;          // itsx_write_trimmed_paired_samples (beside the buffers below)
   DBuf<TrimRec> w_trec; DBuf<int64_t> w_tcnt, w_ttot, w_tblk, w_tfirst, w_tbounds; DBuf<int32_t> w_tstart, w_tstop; DBuf<uint32_t> w_tout;   // itsx_write_trimmed_samples
   bool two_on = false; int share_maxrd = 0; int32_t Ub = 0; size_t sh_gslots_off = 0;
   DBuf<uint8_t> sh_rdepth_s, sh_rdepth; DBuf<unsigned long long> sh_rmask_s, sh_rmask, sh_keys, sh_keys2;
@@ -857,7 +876,7 @@ static int stage_reserve(itsx_ctx *ctx, int64_t bytes)
 static int pack_and_upload(itsx_ctx *ctx, const char *view = nullptr, const uint8_t *dev_raw = nullptr)
 {
   init_codes();
-  ctx->rec.drop();                                       // a new read set: whoever keeps records installs them after this
+  ctx->rec.drop(); ctx->prec.drop();                     // a new read set: whoever keeps records installs them after this
   const auto tp0 = std::chrono::steady_clock::now();
   const int64_t n = ctx->N;
   ctx->dev_bases = dev_raw;
@@ -1020,6 +1039,8 @@ int itsx_set_reads_device(itsx_ctx *ctx, const void *d_bases, const int64_t *off
 // starts and parsed by the I/O pool; the pieces are joined in order, so the result is the serial parser's.
 struct FastxPart {
   itsx_io::Text seq, qual; std::vector<int64_t> off{0}; NameList ids;
+  NameList titles;                       // whole title lines, only where a caller collects them (parse_fastq_side)
+  bool lower = false;                    // upper-casing changed a base: the text no longer holds the input's bytes
   int rc = ITSX_OK; std::string err;
 };
 
@@ -1035,7 +1056,7 @@ static void parse_fastx_range(const char *s, const char *end, bool want_qual, bo
   auto put_seq = [&](const char *b, const char *e) {
     const size_t o = out.seq.size();
     out.seq.append(b, e);
-    if (upper) { char *q = out.seq.data(); for (size_t i = o; i < out.seq.size(); i++) q[i] = (char)toupper((unsigned char)q[i]); }
+    if (upper) { char *q = out.seq.data(); for (size_t i = o; i < out.seq.size(); i++) { const char u = (char)toupper((unsigned char)q[i]); if (u != q[i]) { q[i] = u; out.lower = true; } } }
   };
   // (a FASTQ record is about half sequence: room for it up front instead of a dozen doublings with their copies)
   if (end > s && (size_t)(end - s) > ((size_t)1 << 20)) { out.seq.reserve(out.seq.size() + (size_t)(end - s) / 2 + 4096); if (want_qual) out.qual.reserve(out.qual.size() + (size_t)(end - s) / 2 + 4096); out.ids.blob.reserve(out.ids.blob.size() + (size_t)(end - s) / 8); }
@@ -1094,6 +1115,7 @@ static int parse_fastx(const itsx_io::Text &text, bool want_qual, bool upper, Fa
   for (size_t k = 0; k < np; k++) {
     if (parts[k].rc != ITSX_OK) { err = parts[k].err + " near read " + std::to_string(nrec + parts[k].ids.size()); return parts[k].rc; }
     nrec += parts[k].ids.size(); nseq += parts[k].seq.size();
+    out.lower = out.lower || parts[k].lower;
   }
   const size_t rec0 = out.ids.size(), seq0 = out.seq.size(), nam0 = out.ids.blob.size();
   size_t nnam = 0;
@@ -1281,6 +1303,13 @@ int itsx_keep_records(itsx_ctx *ctx, int on)
 {
   CTXCHK(ctx);
   ctx->keep_records = on != 0;
+  return ITSX_OK;
+}
+
+int itsx_keep_pair_records(itsx_ctx *ctx, int on)
+{
+  CTXCHK(ctx);
+  ctx->keep_pair_records = on != 0;
   return ITSX_OK;
 }
 
@@ -4155,6 +4184,7 @@ int itsx_orient_apply(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t
   ctx->h_off.swap(off); ctx->h_woff.swap(woff); ctx->h_len.swap(len); ctx->h_names.swap(names);
   if (S > 1) ctx->h_sample.swap(smp);
   ctx->h_bases.swap(text); ctx->bases_view = ctx->h_bases.data();
+  ctx->prec.drop();                                      // the pairs' map named the reads that were
   if (records) {
     itsx_ctx::Records &rr = ctx->rec;
     dbuf_swap(rr.seq, r_seq); dbuf_swap(rr.qual, r_qual); dbuf_swap(rr.titles, r_titles); dbuf_swap(rr.off, r_off); dbuf_swap(rr.toff, r_toff);
@@ -4208,7 +4238,10 @@ int itsx_merge_tables(double *q2p, double *match, double *mism, uint8_t *qsame, 
 }
 
 // what the merge kernel read and wrote, kept in device memory for the compaction that follows it (merge_load_core)
-struct MergeKeep { DBuf<uint8_t> os, oq; DBuf<int64_t> fo, ro; DBuf<int32_t> len, reason; bool want_oq = false; };      // oq: the merged qualities, only where records are kept
+struct MergeKeep {
+  DBuf<uint8_t> os, oq; DBuf<int64_t> fo, ro; DBuf<int32_t> len, reason; bool want_oq = false;      // oq: the merged qualities, only where records are kept
+  DBuf<uint8_t> fs, fq, rs, rq; bool want_pairs = false;       // the kernel's inputs, only where the pair records are kept
+};
 // keep (may be null): the merged bases stay in device memory (pair i's at foff[i] + roff[i]) together with the pairs' offsets, lengths
 // and reasons, all taken over by *keep; the bases are copied back only if out_seq is given -- the merge-and-load calls pack them where
 // they are
@@ -4242,7 +4275,9 @@ static int merge_core(itsx_ctx *ctx, const char *fseq, const char *fqual, const 
   }
   const MergeTables &t = merge_tables();
   DBuf<uint8_t> d_fs, d_fq, d_rs, d_rq, d_os, d_oq, d_qs, d_qd; DBuf<int64_t> d_fo, d_ro; DBuf<int32_t> d_len, d_reason, d_shift; DBuf<double> d_q2p, d_m, d_x, d_score;
-  HIPCHK(d_fs.alloc((size_t)fb + 1)); HIPCHK(d_fq.alloc((size_t)fb + 1)); HIPCHK(d_rs.alloc((size_t)rb + 1)); HIPCHK(d_rq.alloc((size_t)rb + 1));
+  // (kept planes are read by k_trim_copy, whose trim_load4 reads two aligned dwords: 8 bytes past the end must be readable)
+  const size_t pad = keep && keep->want_pairs ? 64 : 1;
+  HIPCHK(d_fs.alloc((size_t)fb + pad)); HIPCHK(d_fq.alloc((size_t)fb + pad)); HIPCHK(d_rs.alloc((size_t)rb + pad)); HIPCHK(d_rq.alloc((size_t)rb + pad));
   HIPCHK(d_os.alloc((size_t)(fb + rb) + 1)); HIPCHK(d_oq.alloc((size_t)(fb + rb) + 1));
   HIPCHK(d_fo.alloc((size_t)n + 1)); HIPCHK(d_ro.alloc((size_t)n + 1)); HIPCHK(d_len.alloc((size_t)n)); HIPCHK(d_reason.alloc((size_t)n)); HIPCHK(d_shift.alloc((size_t)n)); HIPCHK(d_score.alloc((size_t)n));
   HIPCHK(upload(d_q2p, t.q2p, ctx->st)); HIPCHK(upload(d_m, t.match, ctx->st)); HIPCHK(upload(d_x, t.mism, ctx->st));
@@ -4266,6 +4301,7 @@ static int merge_core(itsx_ctx *ctx, const char *fseq, const char *fqual, const 
   if (shift) HIPCHK(hipMemcpyAsync(shift, d_shift.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
   HIPCHK(hipStreamSynchronize(ctx->st));
   if (keep) { dbuf_swap(keep->os, d_os); if (keep->want_oq) dbuf_swap(keep->oq, d_oq); dbuf_swap(keep->fo, d_fo); dbuf_swap(keep->ro, d_ro); dbuf_swap(keep->len, d_len); dbuf_swap(keep->reason, d_reason); }
+  if (keep && keep->want_pairs) { dbuf_swap(keep->fs, d_fs); dbuf_swap(keep->fq, d_fq); dbuf_swap(keep->rs, d_rs); dbuf_swap(keep->rq, d_rq); }
   return ITSX_OK;
 }
 int itsx_merge_buffers(itsx_ctx *ctx, const char *fseq, const char *fqual, const int64_t *foff, const char *rseq, const char *rqual,
@@ -4337,7 +4373,8 @@ int itsx_merge_pairs_files(itsx_ctx *ctx, const char *r1_path, const char *r2_pa
 
 // one side of a paired sample: a file (text == nullptr) or a record-aligned piece of its text already in memory.  No shared state: the
 // sides of one sample, and the samples of a batch, are parsed side by side
-static int parse_fastq_side(const char *path, const char *text, int64_t nb, FastxPart &sd, std::string &perr)
+// titles: the records' whole title lines are collected too (sd.titles; the pair records of itsx_keep_pair_records)
+static int parse_fastq_side(const char *path, const char *text, int64_t nb, FastxPart &sd, std::string &perr, bool titles = false)
 {
   std::shared_ptr<const itsx_io::Text> tp;
   itsx_io::Text view;
@@ -4346,7 +4383,11 @@ static int parse_fastq_side(const char *path, const char *text, int64_t nb, Fast
   else { tp = slurp(path, true, perr); if (!tp) return ITSX_E_IO; t = tp.get(); }
   if (!t->empty() && (*t)[0] != '@') { perr = std::string("malformed FASTQ record 1 in ") + path; return ITSX_E_FORMAT; }
   const int prc = parse_fastx(*t, true, true, sd, perr);
-  if (prc != ITSX_OK) perr += std::string(" in ") + path;
+  if (prc != ITSX_OK) { perr += std::string(" in ") + path; return prc; }
+  if (titles) {
+    fastq_titles(*t, sd.titles);
+    if (sd.titles.size() != sd.ids.size()) { perr = std::string("pair records are kept (itsx_keep_pair_records) and this file is not FASTQ throughout: ") + path; return ITSX_E_FORMAT; }
+  }
   return prc;
 }
 
@@ -4357,7 +4398,7 @@ static int parse_fastq_side(const char *path, const char *text, int64_t nb, Fast
 // sample's merged records as itsx_merge_pairs_files writes them -- the only case in which merged bases and qualities come back.
 static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r, const std::vector<const NameList *> &ids, const std::vector<int64_t> &pstart,
                            const char *const *seq_out_paths, int maxdiffs, double maxee, int allow_stagger, double parse_ms, int64_t *n_merged_per_sample,
-                           bool records = false)
+                           bool records = false, bool pair_records = false)
 {
   const int32_t S = (int32_t)pstart.size() - 1;
   const int64_t n = pstart[(size_t)S];
@@ -4370,7 +4411,7 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
   std::string oseq, oqual;
   if (want_text) { oseq.assign((size_t)(f.seq.size() + r.seq.size()) + 1, '\0'); oqual = oseq; }
   MergeKeep k;
-  k.want_oq = records;
+  k.want_oq = records; k.want_pairs = pair_records;
   int rc = merge_core(ctx, f.seq.data(), f.qual.data(), f.off.data(), r.seq.data(), r.qual.data(), r.off.data(), n, maxdiffs, maxee, allow_stagger,
                       want_text ? &oseq[0] : nullptr, want_text ? &oqual[0] : nullptr, olen.data(), reason.data(), nullptr, nullptr, &k);
   if (rc != ITSX_OK) return rc;
@@ -4451,6 +4492,49 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
     dbuf_swap(rr.qual, r_qual);
     rr.seq_p = ctx->d_merged_text.p; rr.have = true;
   }
+  if (pair_records) {
+    // the ORIGINAL pairs beside the merged reads: the planes the merge kernel read, the title lines, and per pair the read its R1
+    // identifier NAMES among its sample's merged reads -- Dedup looks record1.id up in the sample's dictionary, so a pair that did not
+    // merge but carries a merged pair's identifier is sliced with that read's coordinates, and of equal labels the first wins
+    // (trim_host.cpp: NameIndex).  h_merge_index is not that map.
+    itsx_ctx::PairRecords &pr = ctx->prec;
+    if ((int64_t)f.titles.size() != n || (int64_t)r.titles.size() != n) SET_ERR(ctx, ITSX_E_FORMAT, "the title lines kept for the pairs do not match the pairs");
+    std::vector<int32_t> pread((size_t)n, -1);
+    {
+      std::vector<int64_t> rfirst((size_t)S + 1, 0);
+      for (int32_t s = 0; s < S; s++) rfirst[(size_t)s + 1] = rfirst[(size_t)s] + scnt[(size_t)s];
+      const int T = std::max(1, std::min<int>({itsx_io::io_threads(), 16, (int)S}));
+      on_threads(T, [&](int t) {
+        std::unordered_map<std::string_view, int32_t> named;
+        for (int32_t s = t; s < S; s += T) {
+          const NameList &nl = *ids[(size_t)s];
+          const int64_t p0 = pstart[(size_t)s], cnt = pstart[(size_t)s + 1] - p0;
+          named.clear(); named.reserve((size_t)scnt[(size_t)s] * 2);
+          int64_t j = rfirst[(size_t)s];
+          for (int64_t i = 0; i < cnt; i++)
+            if (reason[(size_t)(p0 + i)] == 0) named.emplace(std::string_view(nl.ptr((size_t)i), nl.len((size_t)i)), (int32_t)j++);      // (emplace keeps the first)
+          for (int64_t i = 0; i < cnt; i++) {
+            const auto it = named.find(std::string_view(nl.ptr((size_t)i), nl.len((size_t)i)));
+            if (it != named.end()) pread[(size_t)(p0 + i)] = it->second;
+          }
+        }
+      });
+    }
+    if (n == 0) {                                        // merge_core had nothing to upload
+      HIPCHK(k.fs.alloc(64)); HIPCHK(k.fq.alloc(64)); HIPCHK(k.rs.alloc(64)); HIPCHK(k.rq.alloc(64)); HIPCHK(k.fo.alloc(1)); HIPCHK(k.ro.alloc(1));
+      HIPCHK(hipMemsetAsync(k.fo.p, 0, 8, st)); HIPCHK(hipMemsetAsync(k.ro.p, 0, 8, st));
+    }
+    HIPCHK(pr.t1.alloc(f.titles.blob.size() + 64)); HIPCHK(pr.t2.alloc(r.titles.blob.size() + 64));
+    HIPCHK(pr.to1.alloc((size_t)n + 1)); HIPCHK(pr.to2.alloc((size_t)n + 1)); HIPCHK(pr.pair_read.alloc((size_t)n + 1));
+    if (!f.titles.blob.empty()) HIPCHK(hipMemcpyAsync(pr.t1.p, f.titles.blob.data(), f.titles.blob.size(), hipMemcpyHostToDevice, st));
+    if (!r.titles.blob.empty()) HIPCHK(hipMemcpyAsync(pr.t2.p, r.titles.blob.data(), r.titles.blob.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pr.to1.p, f.titles.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pr.to2.p, r.titles.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    if (n > 0) HIPCHK(hipMemcpyAsync(pr.pair_read.p, pread.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    dbuf_swap(pr.s1, k.fs); dbuf_swap(pr.q1, k.fq); dbuf_swap(pr.s2, k.rs); dbuf_swap(pr.q2, k.rq); dbuf_swap(pr.o1, k.fo); dbuf_swap(pr.o2, k.ro);
+    pr.pstart = pstart; pr.n = n; pr.have = true;
+  }
   if (S > 1) {                                           // the state itsx_load_reads_files + itsx_set_samples leave (d_sample is filled already)
     ctx->h_sample.resize((size_t)m);
     int64_t at = 0;
@@ -4514,8 +4598,9 @@ static int merge_pairs_load_impl(itsx_ctx *ctx, const char *r1_path, const char 
   std::string ferr, rerr2;
   int rc2 = ITSX_OK;
   const auto tm0 = std::chrono::steady_clock::now();
-  std::thread other([&] { rc2 = parse_fastq_side(r2_path, text2, nb2, r, rerr2); });
-  int rc = parse_fastq_side(r1_path, text1, nb1, f, ferr);
+  const bool pair_records = ctx->keep_pair_records && !text1;      // (a streamed piece keeps none, as with itsx_keep_records)
+  std::thread other([&] { rc2 = parse_fastq_side(r2_path, text2, nb2, r, rerr2, pair_records); });
+  int rc = parse_fastq_side(r1_path, text1, nb1, f, ferr, pair_records);
   other.join();
   if (rc != ITSX_OK) { ctx->set_error(ferr); return rc; }
   if (rc2 != ITSX_OK) { ctx->set_error(rerr2); return rc2; }
@@ -4523,7 +4608,8 @@ static int merge_pairs_load_impl(itsx_ctx *ctx, const char *r1_path, const char 
   const int64_t n = (int64_t)f.ids.size();
   int64_t m = 0;
   rc = merge_load_core(ctx, f, r, {&f.ids}, {0, n}, nullptr, maxdiffs, maxee, allow_stagger,
-                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count(), &m, ctx->keep_records && !text1);
+                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count(), &m, ctx->keep_records && !text1,
+                       pair_records && !f.lower && !r.lower);      // (lower-case bases: see merge_pairs_load_files_impl)
   if (rc != ITSX_OK) return rc;
   if (n_pairs) *n_pairs = n;
   if (n_merged) *n_merged = m;
@@ -4550,6 +4636,7 @@ static int merge_pairs_load_files_impl(itsx_ctx *ctx, const char *const *r1_path
 {
   const auto tm0 = std::chrono::steady_clock::now();
   std::vector<FastxPart> fs((size_t)S), rs((size_t)S);
+  const bool pair_records = ctx->keep_pair_records;
   std::vector<std::string> errs((size_t)S * 2);
   std::vector<int> rcs((size_t)S * 2, ITSX_OK);
   const int T = std::max(1, std::min<int>({itsx_io::io_threads(), 16, (int)std::min<int64_t>((int64_t)S * 2, 16)}));
@@ -4563,7 +4650,7 @@ static int merge_pairs_load_files_impl(itsx_ctx *ctx, const char *const *r1_path
         const int64_t q = next.fetch_add(1);
         if (q >= (int64_t)S * 2) break;
         const size_t s = (size_t)(q >> 1);
-        rcs[(size_t)q] = (q & 1) ? parse_fastq_side(r2_paths[s], nullptr, 0, rs[s], errs[(size_t)q]) : parse_fastq_side(r1_paths[s], nullptr, 0, fs[s], errs[(size_t)q]);
+        rcs[(size_t)q] = (q & 1) ? parse_fastq_side(r2_paths[s], nullptr, 0, rs[s], errs[(size_t)q], pair_records) : parse_fastq_side(r1_paths[s], nullptr, 0, fs[s], errs[(size_t)q], pair_records);
       }
     });
   }
@@ -4579,6 +4666,11 @@ static int merge_pairs_load_files_impl(itsx_ctx *ctx, const char *const *r1_path
     if (n_pairs_per_sample) n_pairs_per_sample[s] = (int64_t)fs[s].ids.size();
   }
   const int64_t n = pstart[(size_t)S];
+  // The pair records' bases are the merge's own upload, which is upper case.  Where that changed a base, slices of them would not be the
+  // input's bytes, which the host writer and the reference copy: such a batch keeps no pair records and its trimmed pairs come from the
+  // host writer.
+  bool lower = false;
+  for (size_t s = 0; s < (size_t)S; s++) lower = lower || fs[s].lower || rs[s].lower;
   // the samples' reads side by side in one text per direction (one sample: its own)
   FastxPart F, R;
   bool oom = false;
@@ -4596,11 +4688,18 @@ static int merge_pairs_load_files_impl(itsx_ctx *ctx, const char *const *r1_path
         itsx_io::Text().swap(p.seq); itsx_io::Text().swap(p.qual);
       }
     });
+    if (pair_records) for (size_t s = 0; s < (size_t)S; s++) {      // the title lines, in the same order
+      NameList &t = parts[s].titles;
+      const int64_t b0 = (int64_t)out.titles.blob.size();
+      out.titles.blob.insert(out.titles.blob.end(), t.blob.begin(), t.blob.end());
+      for (size_t i = 0; i < t.size(); i++) out.titles.off.push_back(b0 + t.off[i + 1]);
+      NameList().swap(t);
+    }
   };
   if (S > 1) { join(fs, F); if (!oom) join(rs, R); }
   if (oom) SET_ERR(ctx, ITSX_E_NOMEM, "out of memory joining the samples' reads");
   return merge_load_core(ctx, S > 1 ? F : fs[0], S > 1 ? R : rs[0], ids, pstart, seq_out_paths, maxdiffs, maxee, allow_stagger,
-                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count(), n_merged_per_sample, ctx->keep_records);
+                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count(), n_merged_per_sample, ctx->keep_records, pair_records && !lower);
 }
 int itsx_merge_pairs_load_files(itsx_ctx *ctx, const char *const *r1_paths, const char *const *r2_paths, const char *const *seq_out_paths,
                                 int32_t n_samples, int maxdiffs, double maxee, int allow_stagger, int64_t *n_pairs_per_sample, int64_t *n_merged_per_sample)
@@ -4714,6 +4813,61 @@ static int coords_device(itsx_ctx *ctx, const char *lp, const char *rp, bool per
 }
 int itsx_trim_coords_device(itsx_ctx *ctx, const char *lp, const char *rp, int32_t **d_rows, int64_t *n_rows) { return coords_device(ctx, lp, rp, true, d_rows, n_rows); }
 int itsx_rep_coords_device(itsx_ctx *ctx, const char *lp, const char *rp, int32_t **d_rows, int64_t *n_rows) { return coords_device(ctx, lp, rp, false, d_rows, n_rows); }
+// the second half of the batch writers: the text k_trim_copy left in w_tout (total bytes; sample s's file is bytes [bo[s], bo[s + 1]))
+// comes back through the pinned staging buffers in pieces, and each sample's range goes through a BlockWriter of its own, several samples
+// at a time (a null path: that sample is skipped).  A file that could not be written whole is removed; the other samples' files stay.
+static int trim_text_to_files(itsx_ctx *ctx, int64_t total, const int64_t *bo, const char *const *out_paths, int compression)
+{
+  hipStream_t st = ctx->st;
+  const int32_t S = ctx->S;
+  // ---- the text to the host: pieces through the pinned staging buffers, copied on while the next piece is on the bus
+  itsx_io::Text text;
+  if (!text.resize((size_t)total)) SET_ERR(ctx, ITSX_E_NOMEM, "out of memory for the batch's trimmed text");
+  if (total > 0) {
+    const int64_t CH = std::min<int64_t>(64ll << 20, std::max<int64_t>(total, 70000));
+    { const int rc = stage_reserve(ctx, CH); if (rc != ITSX_OK) return rc; }
+    const int64_t piece = (int64_t)ctx->stage_cap;
+    const int64_t np = (total + piece - 1) / piece;
+    constexpr int K = itsx_ctx::NSTAGE;
+    const uint8_t *dsrc = reinterpret_cast<const uint8_t *>(ctx->w_tout.p);
+    auto drain = [&](int64_t c) -> int {       // piece c has been enqueued: wait for it and copy it on
+      HIPCHK(hipEventSynchronize(ctx->stage_ev[c % K]));
+      const int64_t o = c * piece, b = std::min(piece, total - o);
+      memcpy(text.data() + o, ctx->stage_pin[c % K], (size_t)b);
+      return ITSX_OK;
+    };
+    for (int64_t c = 0; c < np; c++) {
+      if (c >= K) { const int rc = drain(c - K); if (rc != ITSX_OK) return rc; }
+      const int64_t o = c * piece, b = std::min(piece, total - o);
+      HIPCHK(hipMemcpyAsync(ctx->stage_pin[c % K], dsrc + o, (size_t)b, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipEventRecord(ctx->stage_ev[c % K], st));
+    }
+    for (int64_t c = std::max<int64_t>(0, np - K); c < np; c++) { const int rc = drain(c); if (rc != ITSX_OK) return rc; }
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  // ---- one file per sample, several at a time (16 threads in all, the block writers' own pools included)
+  std::vector<int32_t> todo;
+  for (int32_t s = 0; s < S; s++) if (out_paths[s]) todo.push_back(s);
+  const int T = std::max(1, std::min<int>({itsx_io::io_threads(), 16, (int)todo.size()}));
+  std::vector<std::string> werrs((size_t)T);
+  std::atomic<size_t> next{0};
+  on_threads(T, [&](int t) {
+    itsx_io::IoThreadCap share(16 / T);
+    for (;;) {
+      const size_t q = next.fetch_add(1);
+      if (q >= todo.size()) break;
+      const int32_t s = todo[q];
+      itsx_io::BlockWriter bw;
+      std::string werr;
+      if (!bw.open(out_paths[s], compression, werr)) { werrs[(size_t)t] = werr; continue; }
+      for (int64_t o = bo[s]; o < bo[s + 1]; o += (1 << 20)) bw.put(text.data() + o, (size_t)std::min<int64_t>(1 << 20, bo[s + 1] - o));
+      if (!bw.close(werr)) { werrs[(size_t)t] = werr; (void)remove(out_paths[s]); }      // never a short file
+    }
+  });
+  for (const std::string &e : werrs) if (!e.empty()) SET_ERR(ctx, ITSX_E_IO, e);
+  return ITSX_OK;
+}
 // ------------------------------------------------------------------------------ f1 for a batch (k_trim.hip)
 // The trimmed FASTQ of every sample from the records the context keeps: one plan (lengths, 64-bit scan) and one copy kernel make the
 // text of the whole batch in device memory; it comes back through the pinned staging buffers in pieces, and each sample's byte range
@@ -4766,56 +4920,88 @@ int itsx_write_trimmed_samples(itsx_ctx *ctx, const char *const *out_paths, int3
   ca.total = total; ca.ccs = pa.ccs; ca.out = ctx->w_tout.p;
   launch_trim_copy(ca, st);
   HIPCHK(hipGetLastError());
-  // ---- the text to the host: pieces through the pinned staging buffers, copied on while the next piece is on the bus
-  itsx_io::Text text;
-  if (!text.resize((size_t)total)) SET_ERR(ctx, ITSX_E_NOMEM, "out of memory for the batch's trimmed text");
-  if (total > 0) {
-    const int64_t CH = std::min<int64_t>(64ll << 20, std::max<int64_t>(total, 70000));
-    { const int rc = stage_reserve(ctx, CH); if (rc != ITSX_OK) return rc; }
-    const int64_t piece = (int64_t)ctx->stage_cap;
-    const int64_t np = (total + piece - 1) / piece;
-    constexpr int K = itsx_ctx::NSTAGE;
-    const uint8_t *dsrc = reinterpret_cast<const uint8_t *>(ctx->w_tout.p);
-    auto drain = [&](int64_t c) -> int {       // piece c has been enqueued: wait for it and copy it on
-      HIPCHK(hipEventSynchronize(ctx->stage_ev[c % K]));
-      const int64_t o = c * piece, b = std::min(piece, total - o);
-      memcpy(text.data() + o, ctx->stage_pin[c % K], (size_t)b);
-      return ITSX_OK;
-    };
-    for (int64_t c = 0; c < np; c++) {
-      if (c >= K) { const int rc = drain(c - K); if (rc != ITSX_OK) return rc; }
-      const int64_t o = c * piece, b = std::min(piece, total - o);
-      HIPCHK(hipMemcpyAsync(ctx->stage_pin[c % K], dsrc + o, (size_t)b, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipEventRecord(ctx->stage_ev[c % K], st));
-    }
-    for (int64_t c = std::max<int64_t>(0, np - K); c < np; c++) { const int rc = drain(c); if (rc != ITSX_OK) return rc; }
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipGetLastError());
-  // ---- one file per sample, several at a time (16 threads in all, the block writers' own pools included)
-  std::vector<int32_t> todo;
-  for (int32_t s = 0; s < S; s++) if (out_paths[s]) todo.push_back(s);
-  const int T = std::max(1, std::min<int>({itsx_io::io_threads(), 16, (int)todo.size()}));
-  std::vector<std::string> werrs((size_t)T);
-  std::atomic<size_t> next{0};
-  on_threads(T, [&](int t) {
-    itsx_io::IoThreadCap share(16 / T);
-    for (;;) {
-      const size_t q = next.fetch_add(1);
-      if (q >= todo.size()) break;
-      const int32_t s = todo[q];
-      itsx_io::BlockWriter bw;
-      std::string werr;
-      if (!bw.open(out_paths[s], compression, werr)) { werrs[(size_t)t] = werr; continue; }
-      for (int64_t o = bo[s]; o < bo[s + 1]; o += (1 << 20)) bw.put(text.data() + o, (size_t)std::min<int64_t>(1 << 20, bo[s + 1] - o));
-      if (!bw.close(werr)) { werrs[(size_t)t] = werr; (void)remove(out_paths[s]); }      // never a short file
-    }
-  });
-  for (const std::string &e : werrs) if (!e.empty()) SET_ERR(ctx, ITSX_E_IO, e);
+  { const int rc = trim_text_to_files(ctx, total, bo, out_paths, compression); if (rc != ITSX_OK) return rc; }
   for (int32_t s = 0; s < S; s++) {
     if (n_written_per_sample) n_written_per_sample[s] = bc[s + 1] - bc[s];
     if (total_len_per_sample) total_len_per_sample[s] = bt[s + 1] - bt[s];
   }
+  return ITSX_OK;
+}
+// f1 for a batch of PAIRED samples: Dedup.create_paired_trimmed_seqs (SeqSample.py:564-790) of every sample in one call, from the pair
+// records the context keeps (itsx_keep_pair_records).  One plan for both sides; then per side the copy kernel with that side's planes and
+// the text's way back to the files, R1's first.
+int itsx_write_trimmed_paired_samples(itsx_ctx *ctx, const char *const *out1_paths, const char *const *out2_paths, int32_t n_samples, int compression,
+                                      int trim_ccs, const char *left_prefix, const char *right_prefix, const int32_t *start, const int32_t *stop,
+                                      const int32_t *tlen, int64_t *n_written_per_sample)
+{
+  CTXCHK(ctx && out1_paths && out2_paths);
+  const itsx_ctx::PairRecords &pr = ctx->prec;
+  // (SampleBatch.write_paired_trimmed falls back to the host writer when this message names itsx_keep_pair_records: keep the name in it)
+  if (!pr.have) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_paired_samples: the read set keeps no pair records; call itsx_keep_pair_records(ctx, 1) before the pairs are merged (pairs with lower-case bases keep none)");
+  if (n_samples != ctx->S || (size_t)n_samples + 1 != pr.pstart.size())
+    SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_paired_samples: " + std::to_string(n_samples) + " pairs of output paths for " + std::to_string(ctx->S) + " sample(s)");
+  for (int32_t s = 0; s < n_samples; s++)
+    if ((out1_paths[s] == nullptr) != (out2_paths[s] == nullptr)) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_paired_samples: sample " + std::to_string(s) + " has one output path of its two");
+  if (compression < 0 || compression > 2) SET_ERR(ctx, ITSX_E_ARG, "compression must be 0 (plain), 1 (gzip) or 2 (zstd)");
+  const bool by_prefix = left_prefix || right_prefix, by_arrays = start || stop || tlen;
+  if (by_prefix == by_arrays || (by_prefix && !(left_prefix && right_prefix)) || (by_arrays && !(start && stop && tlen)))
+    SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_paired_samples: give either left_prefix and right_prefix or start, stop and tlen");
+  if (by_prefix && !ctx->have_final) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_paired_samples: prefixes given before itsx_search_finalize");
+  { itsx_io::PieceCompressor probe(compression); if (!probe.ok()) SET_ERR(ctx, ITSX_E_IO, "zstd output requested but libzstd.so.1 could not be loaded"); }
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  const int64_t nr = ctx->N, n = pr.n; const int32_t S = ctx->S;
+  TrimPairPlanArgs pa{};
+  if (by_prefix) {
+    int32_t *rows = nullptr; int64_t nrows = 0;
+    const int rc = coords_device(ctx, left_prefix, right_prefix, true, &rows, &nrows);
+    if (rc != ITSX_OK) return rc;
+    pa.start = rows; pa.stop = rows + 1; pa.tlen = rows + 2; pa.stride = 4;
+  } else {
+    HIPCHK(ctx->w_tstart.alloc((size_t)nr + 1)); HIPCHK(ctx->w_tstop.alloc((size_t)nr + 1)); HIPCHK(ctx->w_ttlen.alloc((size_t)nr + 1));
+    if (nr > 0) {
+      HIPCHK(hipMemcpyAsync(ctx->w_tstart.p, start, (size_t)nr * 4, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(ctx->w_tstop.p, stop, (size_t)nr * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(ctx->w_ttlen.p, tlen, (size_t)nr * 4, hipMemcpyHostToDevice, st));
+    }
+    pa.start = ctx->w_tstart.p; pa.stop = ctx->w_tstop.p; pa.tlen = ctx->w_ttlen.p; pa.stride = 1;
+  }
+  std::vector<int64_t> bounds((size_t)(S + 1) * 3, 0);
+  HIPCHK(upload(ctx->w_tfirst, pr.pstart, st));          // sample s is pairs [pstart[s], pstart[s + 1])
+  HIPCHK(ctx->w_trec.alloc((size_t)n + 1)); HIPCHK(ctx->w_trec2.alloc((size_t)n + 1)); HIPCHK(ctx->w_tcnt.alloc((size_t)n + 1));
+  HIPCHK(ctx->w_tblk.alloc((size_t)trim_plan_blocks(n) * 3 + 3)); HIPCHK(ctx->w_tbounds.alloc(bounds.size()));
+  pa.pair_read = pr.pair_read.p; pa.n_reads = nr; pa.off1 = pr.o1.p; pa.toff1 = pr.to1.p; pa.off2 = pr.o2.p; pa.toff2 = pr.to2.p;
+  pa.n = n; pa.ccs = trim_ccs ? 1 : 0;
+  pa.blk = ctx->w_tblk.p; pa.rec1 = ctx->w_trec.p; pa.rec2 = ctx->w_trec2.p; pa.cnt = ctx->w_tcnt.p;
+  {
+    StageTimer tm(st);
+    launch_trim_pair_plan(pa, ctx->w_tfirst.p, S, ctx->w_tbounds.p, st);
+    ctx->stats.ms_trim_plan = tm.stop();
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(bounds.data(), ctx->w_tbounds.p, bounds.size() * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const int64_t *bc = bounds.data() + 2 * (S + 1);
+  HIPCHK(ctx->w_tout.alloc((size_t)(trim_copy_bytes(std::max(bounds[(size_t)S], bounds[(size_t)(S + 1) + (size_t)S])) / 4) + 16));
+  ctx->stats.ms_trim_copy = 0;
+  for (int side = 0; side < 2; side++) {
+    const int64_t *bo = bounds.data() + (size_t)side * (size_t)(S + 1);
+    TrimCopyArgs ca{};
+    ca.rec = side ? ctx->w_trec2.p : ctx->w_trec.p; ca.n = n;
+    ca.seq = side ? pr.s2.p : pr.s1.p; ca.qual = side ? pr.q2.p : pr.q1.p; ca.titles = side ? pr.t2.p : pr.t1.p;
+    ca.total = bo[S]; ca.ccs = pa.ccs; ca.out = ctx->w_tout.p;
+    {
+      StageTimer tm(st);
+      launch_trim_copy(ca, st);
+      ctx->stats.ms_trim_copy += tm.stop();
+    }
+    HIPCHK(hipGetLastError());
+    const int rc = trim_text_to_files(ctx, ca.total, bo, side ? out2_paths : out1_paths, compression);
+    if (rc != ITSX_OK) {                                   // R1's files come first: a failed call leaves no half of a pair of files behind
+      for (int32_t s = 0; s < S; s++) if (out1_paths[s]) { (void)remove(out1_paths[s]); (void)remove(out2_paths[s]); }
+      return rc;
+    }
+  }
+  if (n_written_per_sample) for (int32_t s = 0; s < S; s++) n_written_per_sample[s] = bc[s + 1] - bc[s];
   return ITSX_OK;
 }
 int itsx_derep_device(itsx_ctx *ctx, const int32_t **d_rep_of, const int32_t **d_uniq_of, const int8_t **d_strand, const int32_t **d_seed_read)

@@ -198,6 +198,19 @@ struct TrimCopyArgs {
 };
 int64_t trim_copy_bytes(int64_t total);
 void launch_trim_copy(TrimCopyArgs a, hipStream_t st);
+// the paired plan (itsx_write_trimmed_paired_samples): the ORIGINAL R1 / R2 records of pair p, sliced with the coordinates of read
+// pair_read[p] (-1: the pair is not written) as Dedup.create_paired_trimmed_seqs slices them; one TrimRec per pair AND side, so that
+// k_trim_copy makes each side's text as it is (one launch with R1's planes, one with R2's)
+struct TrimPairPlanArgs {
+  const int32_t *start, *stop, *tlen; int32_t stride;   // READ k's coordinates at [k * stride]
+  const int32_t *pair_read; int64_t n_reads;    // [n]; an entry outside [0, n_reads) is "not written"
+  const int64_t *off1, *toff1, *off2, *toff2;   // [n + 1] R1's and R2's bases / qualities and titles
+  int64_t n; int32_t ccs;                       // pairs
+  int64_t *blk;                                 // [3 x trim_plan_blocks(n)] scratch
+  TrimRec *rec1, *rec2; int64_t *cnt;           // [n + 1]: before pair p, each side's bytes of text (rec.out) and the pairs written
+};
+// bounds[3][S + 1]: R1's bytes / R2's bytes / pairs written before the first pair of each sample (first[S + 1], first[S] = n)
+void launch_trim_pair_plan(const TrimPairPlanArgs &a, const int64_t *first, int32_t S, int64_t *bounds, hipStream_t st);
 void launch_trim_orient(const uint8_t *seq, const uint8_t *qual, const int64_t *off, const int32_t *from, const int8_t *strand, const uint8_t *comp,
                         const int64_t *noff, int64_t m, uint8_t *nseq, uint8_t *nqual, hipStream_t st);
 

@@ -11,6 +11,9 @@
 //          come from one source (title, bases, qualities) they are two aligned loads and a funnel shift -- the misalignment of source
 //          against destination falls on the loads -- and at the seams (newlines, '+', primers, record ends) they are assembled byte by
 //          byte.  Work follows output bytes, not records: a 65 535-base read is spread over the blocks like anything else.
+//   pairs  the paired plan (itsx_keep_pair_records): Dedup.create_paired_trimmed_seqs (SeqSample.py:564-790) -- the ORIGINAL R1 / R2 records
+//          of a pair sliced with the coordinates of the merged read its R1 identifier names.  One TrimRec per pair and side, the same scan
+//          shape, and the copy kernel as it is, once per side.
 //   orient the records of the reads itsx_orient_apply keeps: reverse reads with IUPAC-complemented reversed bases and reversed qualities.
 #include <algorithm>
 #include "engine.h"
@@ -68,18 +71,23 @@ template <bool SCATTER> __global__ __launch_bounds__(TR_BLOCK) void k_trim_plan(
 }
 
 // the tiles' sums -> their exclusive prefixes, in place; entry n of rec / cnt / tot = the batch's totals
-__global__ __launch_bounds__(TR_BLOCK) void k_trim_plan_sums(TrimPlanArgs a, int64_t nb)
+__device__ __forceinline__ void trim_scan_tiles(int64_t *__restrict__ blk, int64_t nb, int64_t (&carry)[3])
 {
-  int64_t carry[3] = {0, 0, 0};
+  carry[0] = carry[1] = carry[2] = 0;
   for (int64_t b0 = 0; b0 < nb; b0 += TR_BLOCK) {
     const int64_t b = b0 + threadIdx.x;
     int64_t v[3], ex[3], tot[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) v[k] = b < nb ? a.blk[b * 3 + k] : 0;
+    for (int k = 0; k < 3; k++) v[k] = b < nb ? blk[b * 3 + k] : 0;
     block_scan64<3, TR_BLOCK>(v, ex, tot);
 #pragma unroll
-    for (int k = 0; k < 3; k++) { if (b < nb) a.blk[b * 3 + k] = carry[k] + ex[k]; carry[k] += tot[k]; }
+    for (int k = 0; k < 3; k++) { if (b < nb) blk[b * 3 + k] = carry[k] + ex[k]; carry[k] += tot[k]; }
   }
+}
+__global__ __launch_bounds__(TR_BLOCK) void k_trim_plan_sums(TrimPlanArgs a, int64_t nb)
+{
+  int64_t carry[3];
+  trim_scan_tiles(a.blk, nb, carry);
   if (threadIdx.x == 0) {
     TrimRec q;
     q.out = carry[0]; q.src = 0; q.toff = 0; q.tl = 0; q.slen = 0;
@@ -106,6 +114,97 @@ void launch_trim_plan(const TrimPlanArgs &a, const int64_t *first, int32_t S, in
   hipLaunchKernelGGL(k_trim_plan_sums, dim3(1), dim3(TR_BLOCK), 0, st, a, nb);
   if (nb > 0) hipLaunchKernelGGL(k_trim_plan<true>, dim3((unsigned)nb), dim3(TR_BLOCK), 0, st, a);
   hipLaunchKernelGGL(k_trim_bounds, dim3((unsigned)((S + 1 + 255) / 256)), dim3(256), 0, st, a.rec, a.cnt, a.tot, first, S, bounds);
+}
+
+// ---- the paired plan ------------------------------------------------------------------------------------------------------------
+// Python's seq[a:b] of a sequence of n (open: no upper bound), as trim_host.cpp's py_slice states it: a negative bound gets n added and
+// is clamped at 0, a bound past the end is clamped at n, and the slice is empty when it ends before it starts
+__device__ __forceinline__ void trim_py_slice(int64_t n, int64_t a, int64_t b, bool open, int32_t &lo, int32_t &slen)
+{
+  if (a < 0) { a += n; if (a < 0) a = 0; } else if (a > n) a = n;
+  if (open) b = n;
+  else if (b < 0) { b += n; if (b < 0) b = 0; } else if (b > n) b = n;
+  lo = (int32_t)a; slen = (int32_t)(b > a ? b - a : 0);
+}
+// pair p: whether it is written, and per side the title's bytes, the slice's first base and its length
+__device__ __forceinline__ void trim_pair_one(const TrimPairPlanArgs &a, int64_t p, int32_t (&tl)[2], int32_t (&lo)[2], int32_t (&sl)[2], bool &w)
+{
+  const int64_t k = a.pair_read[p];
+  tl[0] = (int32_t)(a.toff1[p + 1] - a.toff1[p]); tl[1] = (int32_t)(a.toff2[p + 1] - a.toff2[p]);
+  lo[0] = lo[1] = sl[0] = sl[1] = 0;
+  w = false;
+  if (k < 0 || k >= a.n_reads) return;
+  const int64_t s = a.start[k * a.stride], e = a.stop[k * a.stride], t = a.tlen[k * a.stride];
+  w = s >= 0 && e >= 0 && s < e;
+  if (!w) return;
+  trim_py_slice(a.off1[p + 1] - a.off1[p], s, e, e > t, lo[0], sl[0]);            // R1[start:stop], [start:] where stop > tlen
+  trim_py_slice(a.off2[p + 1] - a.off2[p], t - e, t - s, (t - s) > t, lo[1], sl[1]);      // R2[tlen - stop : tlen - start]
+}
+
+template <bool SCATTER> __global__ __launch_bounds__(TR_BLOCK) void k_trim_pair_plan(TrimPairPlanArgs a)
+{
+  const int64_t base = (int64_t)blockIdx.x * TR_TILE + (int64_t)threadIdx.x * TR_ITEMS;
+  const int64_t extra = a.ccs ? 34 : 0;
+  int32_t tl[TR_ITEMS][2], lo[TR_ITEMS][2], sl[TR_ITEMS][2]; bool w[TR_ITEMS];
+  int64_t v[3] = {0, 0, 0};                      // bytes of R1's text, of R2's text, pairs written
+#pragma unroll
+  for (int i = 0; i < TR_ITEMS; i++) {
+    const int64_t p = base + i;
+    w[i] = false; tl[i][0] = tl[i][1] = lo[i][0] = lo[i][1] = sl[i][0] = sl[i][1] = 0;
+    if (p < a.n) trim_pair_one(a, p, tl[i], lo[i], sl[i], w[i]);
+    if (w[i]) { v[0] += (int64_t)tl[i][0] + 5 + 2 * ((int64_t)sl[i][0] + extra); v[1] += (int64_t)tl[i][1] + 5 + 2 * ((int64_t)sl[i][1] + extra); v[2]++; }
+  }
+  int64_t ex[3], tot[3];
+  block_scan64<3, TR_BLOCK>(v, ex, tot);
+  if (!SCATTER) {
+    if (threadIdx.x == 0) { a.blk[blockIdx.x * 3 + 0] = tot[0]; a.blk[blockIdx.x * 3 + 1] = tot[1]; a.blk[blockIdx.x * 3 + 2] = tot[2]; }
+    return;
+  }
+  int64_t o1 = a.blk[blockIdx.x * 3 + 0] + ex[0], o2 = a.blk[blockIdx.x * 3 + 1] + ex[1], c = a.blk[blockIdx.x * 3 + 2] + ex[2];
+#pragma unroll
+  for (int i = 0; i < TR_ITEMS; i++) {
+    const int64_t p = base + i;
+    if (p >= a.n) break;
+    TrimRec q;
+    q.out = o1; q.src = a.off1[p] + lo[i][0]; q.toff = a.toff1[p]; q.tl = tl[i][0]; q.slen = sl[i][0];
+    a.rec1[p] = q;
+    q.out = o2; q.src = a.off2[p] + lo[i][1]; q.toff = a.toff2[p]; q.tl = tl[i][1]; q.slen = sl[i][1];
+    a.rec2[p] = q;
+    a.cnt[p] = c;
+    if (w[i]) { o1 += (int64_t)tl[i][0] + 5 + 2 * ((int64_t)sl[i][0] + extra); o2 += (int64_t)tl[i][1] + 5 + 2 * ((int64_t)sl[i][1] + extra); c++; }
+  }
+}
+
+__global__ __launch_bounds__(TR_BLOCK) void k_trim_pair_plan_sums(TrimPairPlanArgs a, int64_t nb)
+{
+  int64_t carry[3];
+  trim_scan_tiles(a.blk, nb, carry);
+  if (threadIdx.x == 0) {
+    TrimRec q;
+    q.src = 0; q.toff = 0; q.tl = 0; q.slen = 0;
+    q.out = carry[0]; a.rec1[a.n] = q;
+    q.out = carry[1]; a.rec2[a.n] = q;
+    a.cnt[a.n] = carry[2];
+  }
+}
+
+// bounds[k][s] for k = 0 (R1's byte offset), 1 (R2's), 2 (pairs written) at the first pair of sample s, s = 0 .. S (first[S] = n)
+__global__ void k_trim_pair_bounds(const TrimRec *__restrict__ rec1, const TrimRec *__restrict__ rec2, const int64_t *__restrict__ cnt,
+                                   const int64_t *__restrict__ first, int32_t S, int64_t *__restrict__ bounds)
+{
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s > S) return;
+  const int64_t p = first[s];
+  bounds[s] = rec1[p].out; bounds[(S + 1) + s] = rec2[p].out; bounds[2 * (S + 1) + s] = cnt[p];
+}
+
+void launch_trim_pair_plan(const TrimPairPlanArgs &a, const int64_t *first, int32_t S, int64_t *bounds, hipStream_t st)
+{
+  const int64_t nb = trim_plan_blocks(a.n);
+  if (nb > 0) hipLaunchKernelGGL(k_trim_pair_plan<false>, dim3((unsigned)nb), dim3(TR_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(k_trim_pair_plan_sums, dim3(1), dim3(TR_BLOCK), 0, st, a, nb);
+  if (nb > 0) hipLaunchKernelGGL(k_trim_pair_plan<true>, dim3((unsigned)nb), dim3(TR_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(k_trim_pair_bounds, dim3((unsigned)((S + 1 + 255) / 256)), dim3(256), 0, st, a.rec1, a.rec2, a.cnt, first, S, bounds);
 }
 
 // ---- the copy ------------------------------------------------------------------------------------------------------------------

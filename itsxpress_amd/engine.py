@@ -592,6 +592,43 @@ class Engine:
                                                     None if keep[1] is None else keep[1].ctypes.data, nw.ctypes.data, tot.ctypes.data))
         return [(int(nw[s]), int(tot[s])) for s in range(S)]
 
+    # ---- f1 for a batch of paired samples: trimmed R1 / R2 FASTQ from the pair records the context keeps
+    def keep_pair_records(self, on=True):
+        """From now on merge_pairs_load(_files) also keeps the ORIGINAL pairs on the device beside the merged read set (R1's and R2's
+        bases, qualities and title lines, and which read each pair is sliced with): what write_trimmed_paired_samples cuts from.
+        Independent of keep_records."""
+        self._chk(self.L.itsx_keep_pair_records(self.h, int(bool(on))))
+
+    def write_trimmed_paired_samples(self, paths1, paths2, region_prefixes=None, start=None, stop=None, tlen=None, gzipped=False,
+                                     zstd_file=False, trim_ccs=False):
+        """The trimmed R1 / R2 FASTQ of every paired sample of the batch (paths1[s], paths2[s]; None for both skips a sample) in one
+        call, from the pair records the context keeps.  Coordinates: region_prefixes = (left, right) of the finalized search, or
+        start / stop / tlen arrays over the merged reads -- exactly one of the two.  Returns the pairs written per sample.
+        The given paths belong to the call: if any file cannot be written, EVERY path it was given is removed, also one that held a
+        file before the call and had not been opened yet, so that no half of a pair of files is left behind."""
+        from .trim import _compression
+        S = len(paths1)
+        if len(paths2) != S:
+            raise ValueError("write_trimmed_paired_samples: one R1 and one R2 path per sample")
+        arr1 = (C.c_char_p * max(1, S))(*[None if p is None else os.fsencode(p) for p in paths1])
+        arr2 = (C.c_char_p * max(1, S))(*[None if p is None else os.fsencode(p) for p in paths2])
+        left = right = None
+        if region_prefixes is not None:
+            left, right = (x.encode() for x in region_prefixes)
+        keep = []
+        for a in (start, stop, tlen):
+            if a is None:
+                keep.append(None)
+                continue
+            a = np.ascontiguousarray(a, np.int32)
+            if a.shape[0] != self.n_reads:
+                raise ValueError("write_trimmed_paired_samples: start / stop / tlen hold one entry per merged read")
+            keep.append(a if a.size else np.zeros(1, np.int32))
+        nw = np.zeros(max(1, S), np.int64)
+        self._chk(self.L.itsx_write_trimmed_paired_samples(self.h, arr1, arr2, S, _compression(gzipped, zstd_file), int(bool(trim_ccs)), left, right,
+                                                           *[None if k is None else k.ctypes.data for k in keep], nw.ctypes.data))
+        return [int(nw[s]) for s in range(S)]
+
     # ---- writers
     def write_uc(self, path):
         self._chk(self.L.itsx_write_uc(self.h, os.fsencode(path)))

@@ -18,7 +18,14 @@ Usage: python scripts/batch_bench.py --orient [n_samples] [reads_per_sample]
 `deduplicate` + `_search` + `write_trimmed` (every seq.fq written, then parsed again by the host writer) against
 `SampleBatch(keep_records=True)` (the records stay on the device, one `itsx_write_trimmed_samples`).  Warm context, the two legs
 alternating, medians and the spread of each; checks that every sample's output is the same bytes.
-Usage: python scripts/batch_bench.py --trim [n_samples] [pairs_per_sample] [repeats]"""
+Usage: python scripts/batch_bench.py --trim [n_samples] [pairs_per_sample] [repeats]
+
+--trim-paired: the plugin's main case, `trim_pair_output_unmerged`, on one warm context: a `SampleBatch(keep_records=True)` is merged,
+dereplicated and searched, and its `write_paired_trimmed` -- the host loop: every sample's R1 / R2 read and parsed again by
+`itsx_write_trimmed_paired` -- runs `repeats` times with the text cache as the merge left it and `repeats` times with it emptied first;
+then the same for a `SampleBatch(keep_records="pairs")`, whose `write_paired_trimmed` is one `itsx_write_trimmed_paired_samples` from the
+pair records on the device.  Medians, the plan's and the copy's device times, and a check that every sample's two files are the same bytes.
+Usage: python scripts/batch_bench.py --trim-paired [n_samples] [pairs_per_sample] [repeats]"""
 import gzip
 import hashlib
 import json
@@ -40,7 +47,8 @@ from itsxpress_amd import Engine  # noqa: E402
 PAIRED = "--paired" in sys.argv
 ORIENT = "--orient" in sys.argv
 TRIM = "--trim" in sys.argv
-argv = [a for a in sys.argv[1:] if a not in ("--paired", "--orient", "--trim")]
+TRIM_PAIRED = "--trim-paired" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--paired", "--orient", "--trim", "--trim-paired")]
 S = int(argv[0]) if len(argv) > 0 else 96
 n = int(argv[1]) if len(argv) > 1 else 10000
 thmm = gzip.open(ROOT + "/tests/golden/T.hmm.gz", "rt").read()
@@ -324,6 +332,80 @@ def trim_main():
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def trim_paired_main():
+    from itsxpress_amd import SeqSamplePairedNotInterleaved
+    from itsxpress_amd.batch import SampleBatch
+    from itsxpress_amd.trim import cache_clear
+    os.environ["ITSXPRESS_ARRAYS"] = "0"
+    repeats = int(argv[2]) if len(argv) > 2 else 5
+    tmp = tempfile.mkdtemp(prefix="itsx_batch_bench_")
+    try:
+        files = [write_paired_sample(tmp, s, n) for s in range(S)]
+        hmm = os.path.join(tmp, "its2.hmm")
+        with open(hmm, "w") as f:
+            f.write(its2_profiles(thmm))
+        eng = Engine(0)
+
+        def searched(fs, tag, keep):
+            objs = [SeqSamplePairedNotInterleaved(r1, os.path.join(tmp, tag), r2) for r1, r2 in fs]
+            b = SampleBatch(objs, engine=eng, keep_records=keep)
+            b.merge_reads(threads=1, stagger=False)
+            b.deduplicate(threads=1)
+            b._search(hmmfile=hmm, threads=1)
+            return b
+
+        def write(b, tag):
+            d = os.path.join(tmp, tag)
+            os.makedirs(d, exist_ok=True)
+            o1 = [os.path.join(d, "t_%04d_R1.fq" % k) for k in range(len(b.samples))]
+            o2 = [os.path.join(d, "t_%04d_R2.fq" % k) for k in range(len(b.samples))]
+            t0 = time.perf_counter()
+            ret = b.write_paired_trimmed(o1, o2, "ITS2")
+            return o1 + o2, [int(x) for x in ret], time.perf_counter() - t0
+
+        for keep in (True, "pairs"):           # warm-up on two samples: first-touch costs outside the timed calls
+            write(searched(files[:2], "warm_%s" % keep, keep), "warm_out_%s" % keep)
+        times = {"host": [], "host_cold_cache": [], "device": []}
+        kernels = []
+        digests = {}
+        # a read set is one batch's at a time: first the batch that keeps no pair records (write_paired_trimmed is the host loop, with
+        # the text cache as the merge left it and emptied first), then the batch that keeps them -- the same warm context and inputs
+        for keep, legs in ((True, ("host", "host_cold_cache")), ("pairs", ("device",))):
+            b = searched(files, "batch_%s" % keep, keep)
+            for r in range(repeats):
+                for leg in legs:
+                    if leg == "host_cold_cache":
+                        cache_clear()
+                    tag = "%s_%d" % (leg, r)
+                    outs, ret, dt = write(b, tag)
+                    times[leg].append(dt)
+                    if leg == "device":
+                        st = eng.stats()
+                        kernels.append((st["ms_trim_plan"], st["ms_trim_copy"]))
+                    if r == 0:
+                        digests[leg] = ([hashlib.sha256(open(p, "rb").read()).hexdigest() for p in outs], ret)
+                        nbytes = sum(os.path.getsize(p) for p in outs)
+                    shutil.rmtree(os.path.join(tmp, tag), ignore_errors=True)
+        same = digests["host"] == digests["device"] == digests["host_cold_cache"]
+        print(json.dumps({"trim_paired": True, "samples": S, "pairs_per_sample": n, "merged_reads": int(b.counts.sum()), "repeats": repeats,
+                          "pairs_written": int(sum(digests["device"][1])), "trimmed_bytes": nbytes,
+                          "host_s": [round(x, 3) for x in times["host"]], "host_cold_cache_s": [round(x, 3) for x in times["host_cold_cache"]],
+                          "device_s": [round(x, 3) for x in times["device"]],
+                          "host_median_s": round(float(np.median(times["host"])), 3),
+                          "host_cold_cache_median_s": round(float(np.median(times["host_cold_cache"])), 3),
+                          "device_median_s": round(float(np.median(times["device"])), 3),
+                          "plan_kernels_median_ms": round(float(np.median([k[0] for k in kernels])), 3),
+                          "copy_kernels_median_ms": round(float(np.median([k[1] for k in kernels])), 3),
+                          "identical_outputs": same}))
+        return 0 if same else 1
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+if TRIM_PAIRED:
+    if len(argv) < 1:
+        S, n = 384, 2000
+    sys.exit(trim_paired_main())
 if TRIM:
     if len(argv) < 1:
         S, n = 384, 2000
