@@ -302,6 +302,7 @@ int itsx_orient_apply(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t
  * rseq/rqual[roff[i]..roff[i+1]); the merged read of pair i is written at out_seq/out_qual[foff[i] + roff[i]] with
  * length out_len[i]; reason[i]: 0 merged, 1 no shared 5-mers, 2 several candidate alignments, 3 score < 16,
  * 4 > maxdiffs, 5 overlap < 10, 6 staggered, 7 expected errors > maxee, 8 empty/too long.  score/shift may be NULL.
+ * Every merge entry point reads bases in upper case and writes upper-case merged reads: a lower-case base is its upper case.
  * itsx_merge_pairs_files: FASTQ (plain/gzip) in, plain FASTQ out, labels = forward identifier up to the first blank.
  * itsx_merge_tables: the score / quality tables (context-free; tests compare them with the oracle's). */
 int itsx_merge_buffers(itsx_ctx *ctx, const char *fseq, const char *fqual, const int64_t *foff, const char *rseq, const char *rqual,

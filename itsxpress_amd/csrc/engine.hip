@@ -4206,18 +4206,22 @@ struct MergeTables {
   std::vector<double> q2p, match, mism; std::vector<uint8_t> qsame, qdiff;
   MergeTables() : q2p(128, 0.0), match(128 * 128, 0.0), mism(128 * 128, 0.0), qsame(128 * 128, 0), qdiff(128 * 128, 0)
   {
-    // quality-aware scores and merged qualities of vsearch --fastq_mergepairs (Edgar & Flyvbjerg 2015), host libm
-    auto q_to_p = [](int c) { const int x = c - 33; return x < 2 ? 0.75 : pow(10.0, -(double)x / 10.0); };
-    auto qual_of = [](double p) { double q = rint(-10.0 * log10(p)); if (q > 41.0) q = 41.0; if (q < 0.0) q = 0.0; return (uint8_t)(33 + (int)q); };
+    // quality-aware scores and merged qualities of vsearch --fastq_mergepairs (Edgar & Flyvbjerg 2015), host libm.  Worked out in
+    // long double and rounded once, as the oracle does: in double a log-odds next to 0 carries the rounding of 1 - px - py whole
+    // (up to 27 ulp of the entry at Q2) and pow(10, -x/10) the rounding of x/10
+    auto q_to_p = [](int c) -> long double { const int x = c - 33; return x < 2 ? 0.75L : powl(10.0L, -(long double)x / 10.0L); };
+    auto qual_of = [](long double p) { long double q = rintl(-10.0L * log10l(p)); if (q > 41.0L) q = 41.0L; if (q < 0.0L) q = 0.0L; return (uint8_t)(33 + (int)q); };
     for (int x = 33; x < 127; x++) {
-      const double px = q_to_p(x);
-      q2p[x] = px;
+      const long double px = q_to_p(x);
+      q2p[x] = (double)px;
       for (int y = 33; y < 127; y++) {
-        const double py = q_to_p(y);
-        qsame[x * 128 + y] = qual_of(px * py / 3.0 / (1.0 - px - py + 4.0 * px * py / 3.0));
-        qdiff[x * 128 + y] = qual_of(px * (1.0 - py / 3.0) / (px + py - 4.0 * px * py / 3.0));
-        match[x * 128 + y] = log2((1.0 - px - py + px * py * 4.0 / 3.0) / 0.25);
-        mism[x * 128 + y] = log2(((px + py) / 3.0 - px * py * 4.0 / 9.0) / 0.25);
+        const long double py = q_to_p(y);
+        qsame[x * 128 + y] = qual_of(px * py / 3.0L / (1.0L - px - py + 4.0L * px * py / 3.0L));
+        qdiff[x * 128 + y] = qual_of(px * (1.0L - py / 3.0L) / (px + py - 4.0L * px * py / 3.0L));
+        match[x * 128 + y] = (double)log2l((1.0L - px - py + px * py * 4.0L / 3.0L) / 0.25L);
+        mism[x * 128 + y] = (double)log2l(((px + py) / 3.0L - px * py * 4.0L / 9.0L) / 0.25L);
+        // beside an error of 3/4 both probabilities are exactly 1/4: log-odds 0, which the rounded expressions miss
+        if (x < 35 || y < 35) match[x * 128 + y] = mism[x * 128 + y] = 0.0;
       }
     }
   }

@@ -20,6 +20,8 @@
 
 namespace itsx {
 
+// the kernel's view of a base is its upper case (include/itsx_hip.h): applied where a read enters LDS
+__device__ __forceinline__ uint8_t upper_base(uint8_t c) { return (c >= 'a' && c <= 'z') ? (uint8_t)(c - 32) : c; }
 __device__ __forceinline__ int base_code(uint8_t c)
 {
   return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : (c == 'T' || c == 'U') ? 3 : 4;
@@ -50,8 +52,8 @@ template <bool INDEXED> __global__ __launch_bounds__(64) void k_merge(MergeArgs 
     uint16_t *r5 = f5 + fl;
     int32_t *head = reinterpret_cast<int32_t *>(lds + ((5 * (fl + rl) + 8) & ~3));      // INDEXED only: [1024], then next[fl], diag[fl + rl - 1]
     int32_t *nextp = head + 1024, *diag = nextp + fl;
-    for (int p = lane; p < fl; p += 64) { fs[p] = a.fseq[fo + p]; fq[p] = a.fqual[fo + p]; }
-    for (int j = lane; j < rl; j += 64) { rs[j] = comp_base(a.rseq[ro + rl - 1 - j]); rq[j] = a.rqual[ro + rl - 1 - j]; }
+    for (int p = lane; p < fl; p += 64) { fs[p] = upper_base(a.fseq[fo + p]); fq[p] = a.fqual[fo + p]; }
+    for (int j = lane; j < rl; j += 64) { rs[j] = comp_base(upper_base(a.rseq[ro + rl - 1 - j])); rq[j] = a.rqual[ro + rl - 1 - j]; }
     __syncthreads();
     for (int p = lane; p < fl; p += 64) {
       int v = 0; bool ok = p + 5 <= fl;

@@ -173,6 +173,9 @@ int64_t orc_cluster(const uint8_t *codes, const int64_t *offsets, int64_t n, con
 /* ---- paired-end merging (vsearch --fastq_mergepairs restated; orc_merge.c; PARITY UNPINNED) ---- */
 int  orc_merge_pair(const char *f, const char *fq, int fl, const char *r, const char *rq, int rl, int maxdiffs, double maxee,
                     int allow_stagger, char *out_seq, char *out_qual, int *out_len, double *ret_score, int *ret_shift);
+/* the same, and the mismatches of the reported diagonal (ret_diffs may be NULL) */
+int  orc_merge_pair_ex(const char *f, const char *fq, int fl, const char *r, const char *rq, int rl, int maxdiffs, double maxee,
+                       int allow_stagger, char *out_seq, char *out_qual, int *out_len, double *ret_score, int *ret_shift, int *ret_diffs);
 void orc_merge_tables(double *q2p, double *match, double *mism, unsigned char *qsame, unsigned char *qdiff);
 
 /* DUST soft mask as vsearch applies it to seeds (--qmask dust / --dbmask dust): masked[pos] = 1 */

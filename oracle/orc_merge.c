@@ -23,6 +23,8 @@
  *    p = px py / 3 / (1 - px - py + 4 px py / 3); different bases keep the higher-quality one (the reverse read's
  *    on a tie) with p = px (1 - py/3) / (px + py - 4 px py / 3), px the smaller error; an N yields to the other
  *    read; q = round(-10 log10 p) clamped to [0, 41];
+ *  - bases are upper-cased on input and the merged read is upper case (what is not A, C, G, T or U after that is no
+ *    base of a 5-mer and is complemented to N; symbols are compared as they are, so U differs from T and N equals N);
  *  - the merged read is kept when its expected errors (sum of 10^(-q/10) over the merged qualities) <= maxee.
  */
 #include <math.h>
@@ -34,26 +36,32 @@ static int    g_init = 0;
 static double g_q2p[128], g_match[128][128], g_mism[128][128];
 static unsigned char g_qsame[128][128], g_qdiff[128][128];
 
-static double q_to_p(int c) { const int x = c - 33; return x < 2 ? 0.75 : pow(10.0, -(double)x / 10.0); }
-static unsigned char qual_of(double p)
+/* The tables are worked out in long double and rounded once: a log-odds next to 0 is the log of a number next to 1, which in
+   double carries the rounding of 1 - px - py (an ulp of 1/4) whole -- up to 27 ulp of the entry at Q2 -- and pow(10, -x/10)
+   the rounding of x/10.  From long double every entry is the double nearest its exact value, or its neighbour. */
+static long double q_to_p(int c) { const int x = c - 33; return x < 2 ? 0.75L : powl(10.0L, -(long double)x / 10.0L); }
+static unsigned char qual_of(long double p)
 {
-  double q = rint(-10.0 * log10(p));
-  if (q > 41.0) q = 41.0;
-  if (q < 0.0) q = 0.0;
+  long double q = rintl(-10.0L * log10l(p));
+  if (q > 41.0L) q = 41.0L;
+  if (q < 0.0L) q = 0.0L;
   return (unsigned char)(33 + (int)q);
 }
 static void init_tables(void)
 {
   if (g_init) return;
   for (int x = 33; x < 127; x++) {
-    const double px = q_to_p(x);
-    g_q2p[x] = px;
+    const long double px = q_to_p(x);
+    g_q2p[x] = (double)px;
     for (int y = 33; y < 127; y++) {
-      const double py = q_to_p(y);
-      g_qsame[x][y] = qual_of(px * py / 3.0 / (1.0 - px - py + 4.0 * px * py / 3.0));
-      g_qdiff[x][y] = qual_of(px * (1.0 - py / 3.0) / (px + py - 4.0 * px * py / 3.0));
-      g_match[x][y] = log2((1.0 - px - py + px * py * 4.0 / 3.0) / 0.25);
-      g_mism[x][y] = log2(((px + py) / 3.0 - px * py * 4.0 / 9.0) / 0.25);
+      const long double py = q_to_p(y);
+      g_qsame[x][y] = qual_of(px * py / 3.0L / (1.0L - px - py + 4.0L * px * py / 3.0L));
+      g_qdiff[x][y] = qual_of(px * (1.0L - py / 3.0L) / (px + py - 4.0L * px * py / 3.0L));
+      g_match[x][y] = (double)log2l((1.0L - px - py + px * py * 4.0L / 3.0L) / 0.25L);
+      g_mism[x][y] = (double)log2l(((px + py) / 3.0L - px * py * 4.0L / 9.0L) / 0.25L);
+      /* beside an error of 3/4 both probabilities are 1/4 whatever the other quality is (1 - 3/4 - py + py; 1/4 + py/3 - py/3):
+         the log-odds are exactly 0, which the rounded expressions miss in a third of these entries */
+      if (x < 35 || y < 35) g_match[x][y] = g_mism[x][y] = 0.0;
     }
   }
   g_init = 1;
@@ -66,15 +74,15 @@ void orc_merge_tables(double *q2p, double *match, double *mism, unsigned char *q
   memcpy(qsame, g_qsame, sizeof(g_qsame)); memcpy(qdiff, g_qdiff, sizeof(g_qdiff));
 }
 
+/* bases are read in upper case (the file entry points upper-case while parsing; the buffer entry point does it here) */
+static char up_of(char c) { return (c >= 'a' && c <= 'z') ? (char)(c - 32) : c; }
 static int code_of(char c)
 {
-  switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2;
-               case 'T': case 't': case 'U': case 'u': return 3; default: return 4; }
+  switch (c) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': case 'U': return 3; default: return 4; }
 }
 static char comp_of(char c)
 {
   switch (c) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; case 'U': return 'A';
-               case 'a': return 't'; case 'c': return 'g'; case 'g': return 'c'; case 't': return 'a'; case 'u': return 'a';
                default: return 'N'; }
 }
 
@@ -86,17 +94,19 @@ enum { MRG_OK = 0, MRG_NOKMERS = 1, MRG_REPEAT = 2, MRG_MINSCORE = 3, MRG_MAXDIF
  * One pair.  f/fq: forward read and its qualities (ASCII), r/rq: reverse read as it is in the file.
  * out_seq/out_qual need flen + rlen bytes.  Returns the reason (0 = merged, *out_len set).
  */
-int orc_merge_pair(const char *f, const char *fq, int fl, const char *r, const char *rq, int rl, int maxdiffs, double maxee,
-                   int allow_stagger, char *out_seq, char *out_qual, int *out_len, double *ret_score, int *ret_shift)
+int orc_merge_pair_ex(const char *f_in, const char *fq, int fl, const char *r, const char *rq, int rl, int maxdiffs, double maxee,
+                      int allow_stagger, char *out_seq, char *out_qual, int *out_len, double *ret_score, int *ret_shift, int *ret_diffs)
 {
   init_tables();
   *out_len = 0;
   if (ret_score) *ret_score = 0.0;
   if (ret_shift) *ret_shift = 0;
+  if (ret_diffs) *ret_diffs = 0;
   if (fl < 1 || rl < 1) return MRG_EMPTY;
-  char *rc = (char *)malloc((size_t)rl), *rcq = (char *)malloc((size_t)rl);
+  char *f = (char *)malloc((size_t)fl), *rc = (char *)malloc((size_t)rl), *rcq = (char *)malloc((size_t)rl);
+  for (int p = 0; p < fl; p++) f[p] = up_of(f_in[p]);
   int *f5 = (int *)malloc(sizeof(int) * (size_t)fl), *r5 = (int *)malloc(sizeof(int) * (size_t)rl);
-  for (int j = 0; j < rl; j++) { rc[j] = comp_of(r[rl - 1 - j]); rcq[j] = rq[rl - 1 - j]; }
+  for (int j = 0; j < rl; j++) { rc[j] = comp_of(up_of(r[rl - 1 - j])); rcq[j] = rq[rl - 1 - j]; }
   for (int p = 0; p < fl; p++) {                    /* 5-mer starting at p, -1 when it holds an N or runs off the end */
     f5[p] = -1;
     if (p + 5 <= fl) { int v = 0, ok = 1; for (int t = 0; t < 5; t++) { const int c = code_of(f[p + t]); if (c > 3) ok = 0; v = v * 4 + c; } if (ok) f5[p] = v; }
@@ -138,6 +148,7 @@ int orc_merge_pair(const char *f, const char *fq, int fl, const char *r, const c
   else if (!allow_stagger && best_shift < 0) reason = MRG_STAGGERED;          /* the reverse read's 3' end overhangs the forward read's 5' end */
   if (ret_score) *ret_score = have ? best : 0.0;
   if (ret_shift) *ret_shift = best_shift;
+  if (ret_diffs) *ret_diffs = best_diffs;          /* the mismatches of the reported diagonal (0 without one) */
   if (reason == MRG_OK) {
     int n = 0;
     double ee = 0.0;
@@ -159,6 +170,11 @@ int orc_merge_pair(const char *f, const char *fq, int fl, const char *r, const c
     if (ee > maxee) reason = MRG_MAXEE;
     else *out_len = n;
   }
-  free(rc); free(rcq); free(f5); free(r5);
+  free(f); free(rc); free(rcq); free(f5); free(r5);
   return reason;
+}
+int orc_merge_pair(const char *f, const char *fq, int fl, const char *r, const char *rq, int rl, int maxdiffs, double maxee,
+                   int allow_stagger, char *out_seq, char *out_qual, int *out_len, double *ret_score, int *ret_shift)
+{
+  return orc_merge_pair_ex(f, fq, fl, r, rq, rl, maxdiffs, maxee, allow_stagger, out_seq, out_qual, out_len, ret_score, ret_shift, NULL);
 }

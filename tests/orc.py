@@ -106,6 +106,8 @@ def lib():
     L.orc_merge_pair.restype = C.c_int
     L.orc_merge_pair.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.orc_merge_pair_ex.restype = C.c_int
+    L.orc_merge_pair_ex.argtypes = L.orc_merge_pair.argtypes + [C.c_void_p]
     L.orc_merge_tables.restype = None
     L.orc_merge_tables.argtypes = [C.c_void_p] * 5
     L.orc_orient_db_add.restype = None
@@ -289,6 +291,18 @@ def merge_pair(f, fq, r, rq, maxdiffs=40, maxee=2.0, allow_stagger=False):
     rc = lib().orc_merge_pair(fb, fqb, len(fb), rb, rqb, len(rb), maxdiffs, maxee, int(allow_stagger), out_s, out_q,
                               C.byref(n), C.byref(sc), C.byref(sh))
     return MERGE_REASONS[rc], out_s.raw[:n.value].decode(), out_q.raw[:n.value].decode(), sc.value, sh.value
+
+
+def merge_pair_ex(f, fq, r, rq, maxdiffs=40, maxee=2.0, allow_stagger=False):
+    """merge_pair, and the mismatches of the reported diagonal: (reason, merged_seq, merged_qual, score, shift, diffs).
+    Qualities are passed as bytes 0..255 (latin-1)."""
+    fb, fqb, rb, rqb = f.encode(), fq.encode("latin-1"), r.encode(), rq.encode("latin-1")
+    out_s = C.create_string_buffer(len(fb) + len(rb) + 1)
+    out_q = C.create_string_buffer(len(fb) + len(rb) + 1)
+    n, sc, sh, df = C.c_int(0), C.c_double(0.0), C.c_int(0), C.c_int(0)
+    rc = lib().orc_merge_pair_ex(fb, fqb, len(fb), rb, rqb, len(rb), maxdiffs, maxee, int(allow_stagger), out_s, out_q,
+                                 C.byref(n), C.byref(sc), C.byref(sh), C.byref(df))
+    return MERGE_REASONS[rc], out_s.raw[:n.value].decode(), out_q.raw[:n.value].decode("latin-1"), sc.value, sh.value, df.value
 
 
 def merge_tables():
