@@ -615,7 +615,8 @@ int itsx_debug_calibrate(itsx_ctx *ctx, int pattern, double gbytes, int iters, i
 /* VALU issue-rate probe behind bench.py's valu_issue_frac (profiles/round5_valu_issue.md): op 0 v_fma_f32, 1 v_pk_fma_f32, 2 v_pk_max_i16,
  * 3 v_pk_add_u16, 4 v_pk_mul_f32, 5 v_pk_add_f32, 6 s_nop 0, 7 v_mul_f32, 8 v_pk_mov_b32, 9 v_max_i16; 10 the scalar-cache probe: two
  * s_load_dwordx8 of a 1-KB table per step, waited for one step later (what k_fwd_bound asks per pair of nodes), 11 the same under 12
- * v_pk_fma_f32 per step (scripts/scalar_probe.py); 64 x iters independent instructions (steps) per
+ * v_pk_fma_f32 per step (scripts/scalar_probe.py); 12 v_pk_add_i16 ... clamp (the MSV filter's saturating row add); 64 x iters independent
+ * instructions (steps) per
  * wave, waves_per_simd (1-4, 6, 8) waves on every SIMD; cycles_per_instr as one wave sees them (shader clock ticks, median over the waves) */
 int itsx_debug_issue(itsx_ctx *ctx, int op, int waves_per_simd, int iters, double *cycles_per_instr, double *ms);
 /* deterministic log/exp evaluated ON THE DEVICE for n inputs */

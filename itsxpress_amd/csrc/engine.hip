@@ -5270,7 +5270,7 @@ int itsx_debug_calibrate(itsx_ctx *ctx, int pattern, double gbytes, int iters, i
 // sees them (divide by waves_per_simd for the SIMD's issue interval); ms = the launch.
 int itsx_debug_issue(itsx_ctx *ctx, int op, int waves_per_simd, int iters, double *cycles_per_instr, double *ms)
 {
-  CTXCHK(ctx && op >= 0 && op <= 11 && waves_per_simd >= 1 && waves_per_simd <= 8 && (waves_per_simd <= 4 || waves_per_simd % 2 == 0) && iters >= 1);
+  CTXCHK(ctx && op >= 0 && op <= 12 && waves_per_simd >= 1 && waves_per_simd <= 8 && (waves_per_simd <= 4 || waves_per_simd % 2 == 0) && iters >= 1);
   HIPCHK(hipSetDevice(ctx->device));
   int ncu = 256;
   { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, ctx->device) == hipSuccess) ncu = pr.multiProcessorCount; }

@@ -330,7 +330,7 @@ struct alignas(16) ChainRec {
 static_assert(sizeof(ChainRec) == 64, "k_fwd_bound / k_bwd_bound read a chain's record as four 16-byte loads");
 void launch_chain_recs(int32_t n, const ReadsDev &rd, const int32_t *order /*global unique by position*/, const int32_t *seed_read, const int32_t *src, const int32_t *node0,
                        const unsigned long long *mask, const int32_t *endrow, const int32_t *jlev, const int32_t *jsrc, ChainRec *out, hipStream_t st);
-constexpr int MSV_STATE_Q = 8;             // 23 packed registers + xJ, xB, xEmax, padded to one 128-byte line
+constexpr int MSV_STATE_Q = 8;             // 23 packed registers + xJ, xB, 0 (was xEmax), padded to one 128-byte line
 constexpr int FWD_STATE_Q = 36;            // M, I, D of 46 nodes + xN xJ xC xB + the scale's logarithm (double)
 // lazy searches only: a chain whose own pair failed the MSV filter still has to run for a profile when a chain below it needs its state
 void launch_need_bits(const uint16_t *res, int32_t U, int32_t P, int32_t W, uint32_t *pass, uint32_t *need, hipStream_t st);

@@ -15,18 +15,34 @@
 //   * each lane keeps the DP row in 23 VGPRs, two cells per register as packed int16 (v_pk_max_i16 / v_pk_add_u16),
 //     STRIPED: register r holds cells r (low half) and r + 23 (high half), so the cell before both halves of register r is
 //     register r - 1 as it stands; only register 0 takes its predecessors from a shifted copy of the old register 22.
-//     Three packed instructions per two cells (max with xB, add the emission, max into xE); the row is updated in place.
+//     The row is updated in place.
+//   * THE FLOORED ROW.  xB is a per-lane floor that almost never moves (xJ never falls, so xB = max(xJ - tjbm, bm0) never falls), and a
+//     cell is only ever used through max(cell, xB') with a later xB' >= xB.  So a register keeps  c'' = max(c, xB) - xB - 32768  and
+//     "max with xB, then add the emission" is ONE saturating add (v_pk_add_i16 ... clamp): it saturates at -32768, which is
+//     max(prev, xB) + e floored at xB.  Two packed instructions per two cells (saturating add, max into xE) instead of three (max with
+//     xB, add, max into xE: the plain row, still here as the start-up row and behind ITSX_MSV_FLOOR=0).  The cell before node 1 is the
+//     floor; xE's halves start at the floor and the real xE is their maximum + xB + 32768.
+//       - start-up: with floored cells a row whose cells all fell below xB reads xE = xB where the plain row reads the true, smaller,
+//         maximum.  That moves xJ only when xB - tec > xJ, which (xB = max(xJ - tjbm, bm0), tjbm + tec >= 0) needs xJ < bm0 - tec: the
+//         first rows of a chain until some cell had a non-negative emission (reads that begin with N).  xJ >= bm0 - tec is monotone, so
+//         a wave runs the plain row while any of its working lanes is below it (normally one row), converts its registers once
+//         (max with xB, subtract xB + 32768) and goes on with the floored row.  A restored chain makes the same test on its restored xJ.
+//       - when xB rises by delta the lane's cells lose delta by a saturating subtract (cells that reach the new floor stay on it, exact
+//         by the argument above), under a wave-uniform branch: xJ passes the base only inside a strong hit.
+//       - saved states, restores and the join are in real units: c = c'' + xB + 32768 at the block boundary, in the lanes that save or
+//         join.  A saved cell is then max(c, xB), not c: a child only uses it through max(cell, xB') with xB' >= xB.
 //   * degenerate residues come from the read's exception list (position, code): one compare per row against the lane's
 //     next exception; their emission rows are in the same LDS table.
 //   * HMMER's unsigned arithmetic floors cells at 0; cells here are signed and unfloored, which is equivalent because
 //     every cell is max'ed with xB >= 0 before it is used and xE starts at 0.  HMMER returns at the first row whose
-//     xE + bias reaches 255; here the row maximum of xE is kept and tested once at the end -- after that row nothing
-//     else of the lane's state is used.
+//     xE + bias reaches 255; here that is tested once at the end, on xJ: by the recurrence xJ = max(0, max_i xE_i - tec), so the
+//     largest row maximum is xJ + tec whenever xJ > 0 -- after the overflowing row nothing else of the lane's state is used.
 //   * the P-value test is folded into a per-(length, profile) threshold on the final xJ byte, computed on the host with
 //     the same double arithmetic hmmsearch uses.
 //   * results go to res[profile][sorted position]: consecutive lanes, consecutive halfwords.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include "engine.h"
 #include "k_api.h"
 
@@ -37,11 +53,14 @@ typedef short s2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ s2 as_s2(uint32_t u) { return __builtin_bit_cast(s2, u); }
 __device__ __forceinline__ uint32_t as_u(s2 v) { return __builtin_bit_cast(uint32_t, v); }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// what a floored register c'' = c - xB - 32768 gains (wrapping) to be real again; nothing when the registers are real
+__device__ __forceinline__ s2 real_off(bool floored, int xB) { return as_s2(floored ? (uint32_t)((xB + 32768) & 0xffff) * 0x10001u : 0u); }
 
 // SHARE (k_share.hip): the block's sequences are chains that start at the same depth -- the rows before come from the state the parent
-// chain saved (23 packed registers, xJ, xB, xEmax: MSV_STATE_Q uint4 per (node, profile)), and a chain saves its own state where a
+// chain saved (23 packed registers, xJ, xB: MSV_STATE_Q uint4 per (node, profile)), and a chain saves its own state where a
 // later chain branches off.  Integer arithmetic on the same operands: the xJ bytes are those of the unshared kernel.
-template <bool SHARE>
+// FLOOR: the floored row (above); false: the plain three-instruction row on every row (ITSX_MSV_FLOOR=0, A/B and cross-check)
+template <bool SHARE, bool FLOOR>
 __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
 {
   __shared__ __attribute__((aligned(16))) uint32_t tab[2][16 * MSV_TW];
@@ -73,7 +92,10 @@ __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
   // after row `myend` = jlev * B and takes the rest of the maximum over paths from that representative's saved BACKWARD state
   // (k_msv_bwd below).  The filter is max-plus arithmetic on integers -- every cell is a maximum over paths of sums -- so
   //     final xJ = max over the state's components (cell_k + g_k, xJ + gJ, xB + gB, g0)
-  // is the unshared kernel's xJ exactly, and xEmax follows from it (xJ = max(0, max_i xE_i - tec) by the recurrence).
+  // is the unshared kernel's xJ exactly, and the overflow test follows from it (xJ = max(0, max_i xE_i - tec) by the recurrence).
+  // It stays exact with floored cells max(cell_k, xB): gB = max_k w_k >= g_k for every k (k_msv_bwd), hence
+  //     max(cell_k, xB) + g_k <= max(cell_k + g_k, xB + gB)
+  // and both terms on the right are components of the maximum already.
   int myend = L, jlev = -1; int64_t jnode = 0;
   if constexpr (SHARE) {
     if (valid && a.sl.endrow) { myend = a.sl.endrow[s]; jlev = a.sl.jlev[s]; jnode = (int64_t)a.sl.jsrc[s] - a.sl.gnode_base; }
@@ -95,7 +117,7 @@ __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
     const int bias = uni(a.pbias[p]), tec = uni(a.ptec[p]), tbm = uni(a.ptbm[p]);
     const int tjbm = tjb + tbm;
     int bm0 = base - tjbm; bm0 = bm0 < 0 ? 0 : bm0;          // xB while xJ is below the base
-    int xJ = 0, xB = bm0, xEmax = 0;
+    int xJ = 0, xB = bm0;
     uint32_t dp[MSV_REGS];
 #pragma unroll
     for (int i = 0; i < MSV_REGS; i++) dp[i] = 0;
@@ -110,15 +132,25 @@ __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
           dp[4 * q] = v.x; dp[4 * q + 1] = v.y; dp[4 * q + 2] = v.z; if (4 * q + 3 < MSV_REGS) dp[4 * q + 3] = v.w;
         }
         const uint4 v = src[6];
-        xJ = (int)v.x; xB = (int)v.y; xEmax = (int)v.z;
+        xJ = (int)v.x; xB = (int)v.y;
       }
     }
     int ei = 0;
     int next_exc = nexc > 0 ? (int)(ep[0] >> 4) : 0x7fffffff;        // (a chain has no exception above its start: k_share.hip)
     uint32_t w = 0;
     const int lend = myend;
-    int jxJ = -1, jem = 0;                           // the joined result, if the chain joins
-    for (int pos = row0; pos <= Lw; pos++) {
+    int jxJ = -1;                                    // the joined result, if the chain joins
+    int pos = row0;
+    // the rows from `pos` on, FAST: with the floored row (the registers hold c''), else with the plain one.  Two loops, not one loop with
+    // a flag: where both rows' registers meet again the compiler copies all 23 of them, every row.  The plain loop of a FLOOR kernel
+    // returns true at the top of the first row that the start-up rule lets the floored row take.
+    auto rows = [&](auto fast_c) -> bool {
+    constexpr bool FAST = decltype(fast_c)::value;
+    for (; pos <= Lw; pos++) {
+      if constexpr (FLOOR && !FAST) {
+        // the start-up rule: no working lane of the wave is below bm0 - tec any more (monotone: it stays so)
+        if (__builtin_amdgcn_ballot_w64(pos < lend && xJ + tec < bm0) == 0ull) return true;
+      }
       const int sh = (pos & 15) * 2;
       if (sh == 0) {
         if constexpr (SHARE) {
@@ -129,32 +161,36 @@ __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
             if (pos > row0 && pos < L && d < 64 && ((m >> d) & 1ull)) {       // (a mask has no bit above the chain's last level)
               const int64_t node = (int64_t)a.sl.node0[s] + __popcll(m & ((1ull << d) - 1ull)) - a.sl.node_base;
               uint4 *dst = (uint4 *)a.sl.slots + (node * a.sl.Pb + (pj - a.pfirst)) * MSV_STATE_Q;
+              const s2 ru = real_off(FAST, xB);
 #pragma unroll
-              for (int q = 0; q < 6; q++) dst[q] = make_uint4(dp[4 * q], dp[4 * q + 1], dp[4 * q + 2], (4 * q + 3 < MSV_REGS) ? dp[(4 * q + 3) % MSV_REGS] : 0u);
-              dst[6] = make_uint4((uint32_t)xJ, (uint32_t)xB, (uint32_t)xEmax, 0u);
+              for (int q = 0; q < 6; q++)
+                dst[q] = make_uint4(as_u(as_s2(dp[4 * q]) + ru), as_u(as_s2(dp[4 * q + 1]) + ru), as_u(as_s2(dp[4 * q + 2]) + ru),
+                                    (4 * q + 3 < MSV_REGS) ? as_u(as_s2(dp[(4 * q + 3) % MSV_REGS]) + ru) : 0u);
+              dst[6] = make_uint4((uint32_t)xJ, (uint32_t)xB, 0u, 0u);
             }
             if (d == jlev) {
               // the join (saturating adds: a suffix that overflows stays an overflow)
               const uint4 *g = (const uint4 *)a.sl.gslots + (jnode * a.sl.Pb + (pj - a.pfirst)) * MSV_STATE_Q;
               s2 mx = as_s2(0x80008000u);
+              const s2 ru = real_off(FAST, xB);
 #pragma unroll
               for (int q = 0; q < 6; q++) {
                 const uint4 v = g[q];
-                mx = __builtin_elementwise_max(mx, __builtin_elementwise_add_sat(as_s2(dp[4 * q]), as_s2(v.x)));
-                mx = __builtin_elementwise_max(mx, __builtin_elementwise_add_sat(as_s2(dp[4 * q + 1]), as_s2(v.y)));
-                mx = __builtin_elementwise_max(mx, __builtin_elementwise_add_sat(as_s2(dp[4 * q + 2]), as_s2(v.z)));
-                if (4 * q + 3 < MSV_REGS) mx = __builtin_elementwise_max(mx, __builtin_elementwise_add_sat(as_s2(dp[4 * q + 3]), as_s2(v.w)));
+                mx = __builtin_elementwise_max(mx, __builtin_elementwise_add_sat(as_s2(dp[4 * q]) + ru, as_s2(v.x)));
+                mx = __builtin_elementwise_max(mx, __builtin_elementwise_add_sat(as_s2(dp[4 * q + 1]) + ru, as_s2(v.y)));
+                mx = __builtin_elementwise_max(mx, __builtin_elementwise_add_sat(as_s2(dp[4 * q + 2]) + ru, as_s2(v.z)));
+                if (4 * q + 3 < MSV_REGS) mx = __builtin_elementwise_max(mx, __builtin_elementwise_add_sat(as_s2(dp[4 * q + 3]) + ru, as_s2(v.w)));
               }
               const uint4 t = g[6];
               int xf = (int)mx.x > (int)mx.y ? (int)mx.x : (int)mx.y;
               const int c1 = xJ + (int)t.x, c2 = xB + (int)t.y, c3 = (int)t.z;
               xf = xf > c1 ? xf : c1; xf = xf > c2 ? xf : c2; xf = xf > c3 ? xf : c3;
-              jxJ = xf; jem = xf + tec;               // (xf + tec = the largest row maximum of the whole read when xf > 0); the chain may walk
+              jxJ = xf;                               // (xf + tec = the largest row maximum of the whole read when xf > 0); the chain may walk
                                                       // on for the states its prefix children start from
             }
           }
         }
-        if (pos >= Lw) break;
+        if (pos >= Lw) return false;
         // the lane's packed words, 16 at a time (256 rows) through LDS: one contiguous 64-byte piece of the read per load instead of a
         // dword every 16 rows -- every one of those dwords cost a whole line once 49 k lanes' lines no longer fit the XCD's L2
         // (75.6 GB fetched per 1 M reads in round 4 against 0.1-0.4 GB of packed reads; profiles/round5_pmc_hbm_traffic_1M.md)
@@ -176,29 +212,62 @@ __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
         uint32_t e[MSV_TW];
 #pragma unroll
         for (int q = 0; q < MSV_TW / 4; q++) { const uint4 v = e4[q]; e[4 * q] = v.x; e[4 * q + 1] = v.y; e[4 * q + 2] = v.z; e[4 * q + 3] = v.w; }
-        const s2 xBv = as_s2((uint32_t)xB * 0x10001u);
-        const uint32_t wrap = dp[MSV_REGS - 1] << 16;
-        s2 xEa = as_s2(0u), xEb = as_s2(0u);
+        if constexpr (FAST) {
+          const uint32_t wrap = (dp[MSV_REGS - 1] << 16) | 0x8000u;      // the cell before node 1 is the floor
+          s2 xEa = as_s2(0x80008000u), xEb = as_s2(0x80008000u);
 #pragma unroll
-        for (int r = MSV_REGS - 1; r >= 0; r--) {
-          const uint32_t prev = (r > 0) ? dp[r > 0 ? r - 1 : 0] : wrap;
-          const s2 sv = __builtin_elementwise_max(as_s2(prev), xBv) + as_s2(e[r]);
-          if (r & 1) xEb = __builtin_elementwise_max(xEb, sv); else xEa = __builtin_elementwise_max(xEa, sv);
-          dp[r] = as_u(sv);
+          for (int r = MSV_REGS - 1; r >= 0; r--) {
+            const uint32_t prev = (r > 0) ? dp[r > 0 ? r - 1 : 0] : wrap;
+            const s2 sv = __builtin_elementwise_add_sat(as_s2(prev), as_s2(e[r]));
+            if (r & 1) xEb = __builtin_elementwise_max(xEb, sv); else xEa = __builtin_elementwise_max(xEa, sv);
+            dp[r] = as_u(sv);
+          }
+          const uint32_t xe2 = as_u(__builtin_elementwise_max(xEa, xEb));
+          const int xEl = (int)(int16_t)(xe2 & 0xffffu), xEh = (int)xe2 >> 16;
+          const int xE = (xEl > xEh ? xEl : xEh) + xB + (32768 - tec);   // the real xE - tec
+          xJ = xJ > xE ? xJ : xE;
+          int nb = xJ - tjbm; nb = nb > bm0 ? nb : bm0;
+          const int delta = nb - xB;
+          xB = nb;
+          if (__builtin_amdgcn_ballot_w64(delta > 0) != 0ull) {          // xB rose (inside a strong hit): the cells sink by as much
+            const s2 dv = as_s2((uint32_t)((-delta) & 0xffff) * 0x10001u);
+#pragma unroll
+            for (int i = 0; i < MSV_REGS; i++) dp[i] = as_u(__builtin_elementwise_add_sat(as_s2(dp[i]), dv));
+          }
+        } else {
+          const s2 xBv = as_s2((uint32_t)xB * 0x10001u);
+          const uint32_t wrap = dp[MSV_REGS - 1] << 16;
+          s2 xEa = as_s2(0u), xEb = as_s2(0u);
+#pragma unroll
+          for (int r = MSV_REGS - 1; r >= 0; r--) {
+            const uint32_t prev = (r > 0) ? dp[r > 0 ? r - 1 : 0] : wrap;
+            const s2 sv = __builtin_elementwise_max(as_s2(prev), xBv) + as_s2(e[r]);
+            if (r & 1) xEb = __builtin_elementwise_max(xEb, sv); else xEa = __builtin_elementwise_max(xEa, sv);
+            dp[r] = as_u(sv);
+          }
+          const uint32_t xe2 = as_u(__builtin_elementwise_max(xEa, xEb));
+          int xE = (int)(xe2 & 0xffffu);
+          const int xEh = (int)(xe2 >> 16);
+          xE = xE > xEh ? xE : xEh;
+          xE -= tec;
+          xJ = xJ > xE ? xJ : xE;
+          xB = xJ - tjbm; xB = xB > bm0 ? xB : bm0;            // = max(max(base, xJ) - tjbm, 0)
         }
-        const uint32_t xe2 = as_u(__builtin_elementwise_max(xEa, xEb));
-        int xE = (int)(xe2 & 0xffffu);
-        const int xEh = (int)(xe2 >> 16);
-        xE = xE > xEh ? xE : xEh;
-        xEmax = xEmax > xE ? xEmax : xE;
-        xE -= tec;
-        xJ = xJ > xE ? xJ : xE;
-        xB = xJ - tjbm; xB = xB > bm0 ? xB : bm0;            // = max(max(base, xJ) - tjbm, 0)
       }
     }
+    return false;
+    };
+    if (rows(std::false_type())) {
+      // into the floored form, once: max with xB, subtract xB + 32768
+      const s2 xBv = as_s2((uint32_t)xB * 0x10001u);
+      const s2 dn = as_s2((uint32_t)((-(xB + 32768)) & 0xffff) * 0x10001u);
+#pragma unroll
+      for (int i = 0; i < MSV_REGS; i++) dp[i] = as_u(__builtin_elementwise_max(as_s2(dp[i]), xBv) + dn);
+      rows(std::true_type());
+    }
     if (valid) {
-      if (jxJ >= 0) { xJ = jxJ; xEmax = xEmax > jem ? xEmax : jem; }
-      const int ovf = (xEmax + bias >= 255);
+      if (jxJ >= 0) xJ = jxJ;
+      const int ovf = (xJ > 0 && xJ + tec + bias >= 255);      // (the largest row maximum is xJ + tec)
       const int thr = a.thr[(size_t)Lt * Ppad + p];
       const int pass = ovf | (xJ >= thr);
       const int xj = ovf ? 255 : xJ;
@@ -342,9 +411,13 @@ void launch_msv(const MsvArgs &a0, hipStream_t st, int lds_pad)
   static const bool bwd_whole = sw_get("ITSX_MSV_BWD_WHOLE") && atoi(sw_get("ITSX_MSV_BWD_WHOLE")) != 0;
   if (a.share == 2 && !bwd_whole) a.wtl = MSV_WT;
   const size_t lds = std::max<size_t>((size_t)lds_pad, (a.share == 2 && !bwd_whole) ? 0 : (size_t)a.wtl * 256 * sizeof(uint32_t));
+  // ITSX_MSV_FLOOR=0: the plain three-instruction row on every row (A/B, and the cross-check of the floored row; read at every launch)
+  const bool floored = !(sw_get("ITSX_MSV_FLOOR") && atoi(sw_get("ITSX_MSV_FLOOR")) == 0);
   if (a.share == 2) hipLaunchKernelGGL(k_msv_bwd, grid, dim3(256), lds, st, a);
-  else if (a.share) hipLaunchKernelGGL(k_msv<true>, grid, dim3(256), lds, st, a);
-  else hipLaunchKernelGGL(k_msv<false>, grid, dim3(256), lds, st, a);
+  else if (a.share && floored) hipLaunchKernelGGL((k_msv<true, true>), grid, dim3(256), lds, st, a);
+  else if (a.share) hipLaunchKernelGGL((k_msv<true, false>), grid, dim3(256), lds, st, a);
+  else if (floored) hipLaunchKernelGGL((k_msv<false, true>), grid, dim3(256), lds, st, a);
+  else hipLaunchKernelGGL((k_msv<false, false>), grid, dim3(256), lds, st, a);
 }
 
 // ---------------------------------------------------------------------------------------

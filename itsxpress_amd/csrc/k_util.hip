@@ -133,6 +133,7 @@ __device__ __forceinline__ void issue16(float (&x)[32], float a, float b)
     else if (OP == 7) asm volatile("v_mul_f32 %0, %0, %1" : "+v"(x[i]) : "v"(a));
     else if (OP == 8) asm volatile("v_pk_mov_b32 %0, %1, %1 op_sel:[0,1]" : "=v"(*(float2 *)&x[2 * i]) : "v"(*(float2 *)&x[(2 * i + 2) & 31]));
     else if (OP == 9) asm volatile("v_max_i16 %0, %0, %1" : "+v"(x[i]) : "v"(a));
+    else if (OP == 12) asm volatile("v_pk_add_i16 %0, %0, %1 clamp" : "+v"(x[i]) : "v"(a));       // k_msv's floored row, k_msv_bwd
   }
 }
 // ---- scalar-cache probe: what k_fwd_bound asks of it per pair of nodes -- 64 B of wave-uniform transitions through two
@@ -160,7 +161,7 @@ __global__ void __launch_bounds__(1024) k_issue(int iters, unsigned long long *_
   const float a = 0.999999f, b = 1e-7f;
   __syncthreads();
   const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-  if constexpr (OP >= 10) { for (int it = 0; it < iters; it++) { sload16<OP>(x, sink); sload16<OP>(x, sink); sload16<OP>(x, sink); sload16<OP>(x, sink); } }
+  if constexpr (OP == 10 || OP == 11) { for (int it = 0; it < iters; it++) { sload16<OP>(x, sink); sload16<OP>(x, sink); sload16<OP>(x, sink); sload16<OP>(x, sink); } }
   else for (int it = 0; it < iters; it++) { issue16<OP>(x, a, b); issue16<OP>(x, a, b); issue16<OP>(x, a, b); issue16<OP>(x, a, b); }
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 0" ::: "memory");
   const unsigned long long t1 = __builtin_amdgcn_s_memtime();
@@ -189,7 +190,8 @@ void launch_issue(int op, int waves_per_simd, int iters, int blocks, unsigned lo
     case 8: hipLaunchKernelGGL(k_issue<8>, g, b, lds, st, iters, ticks, sink); break;
     case 9: hipLaunchKernelGGL(k_issue<9>, g, b, lds, st, iters, ticks, sink); break;
     case 10: hipLaunchKernelGGL(k_issue<10>, g, b, lds, st, iters, ticks, sink); break;
-    default: hipLaunchKernelGGL(k_issue<11>, g, b, lds, st, iters, ticks, sink); break;
+    case 11: hipLaunchKernelGGL(k_issue<11>, g, b, lds, st, iters, ticks, sink); break;
+    default: hipLaunchKernelGGL(k_issue<12>, g, b, lds, st, iters, ticks, sink); break;
   }
 }
 

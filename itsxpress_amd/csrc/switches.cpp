@@ -49,6 +49,7 @@ static const Switch g_sw[] = {
   {"ITSX_MSV_OVERLAP", SW_TUNING, "=0: the next chunk's MSV filter does not run beside the domain stage"},
   {"ITSX_MSV_PAD", SW_TUNING, "dynamic LDS of the overlapped MSV launch (an occupancy cap)"},
   {"ITSX_MSV_WHOLE", SW_TUNING, "=0: MSV stages 16 words at a time even when the whole read fits LDS"},
+  {"ITSX_MSV_FLOOR", SW_TUNING, "=0: the MSV filter's plain three-instruction row on every row instead of the floored two-instruction one (A/B arm: same cells; read at every launch)"},
   {"ITSX_BIAS_OVERLAP", SW_TUNING, "=0: the bias filter does not run on the second stream"},
   {"ITSX_ST2_PRIO", SW_TUNING, "priority of the second stream"},
   {"ITSX_LOAD_PRIORITY", SW_TUNING, "=0: loads do not use the high-priority stream"},
