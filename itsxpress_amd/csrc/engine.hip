@@ -3986,7 +3986,8 @@ int itsx_orient_load_db(itsx_ctx *ctx, const char *fasta_path, int64_t *n_sequen
   bool header = false;
   for (size_t i = 0; i < text.size(); i++) {
     const char c = text[i];
-    if (c == '>') { add_seq(); header = true; nseq++; continue; }
+    // a record starts at a '>' that begins a line: one inside a header is the header's, one inside a sequence line breaks words as N does
+    if (c == '>' && !header && (i == 0 || text[i - 1] == '\n')) { add_seq(); header = true; nseq++; continue; }
     if (c == '\n') { header = false; continue; }
     if (header || c == '\r') continue;
     const int code = g_code[(unsigned char)c];

@@ -294,6 +294,8 @@ int64_t orc_cluster(const uint8_t *codes, const int64_t *offsets, int64_t n, con
  * count_rev >= 1 and count_rev >= 4 * count_fwd, otherwise undetermined (not written).  Query and database sequences are
  * DUST-masked first (vsearch's defaults --qmask dust --dbmask dust; orc_dust above): words that touch a masked symbol are
  * left out on both sides; ORC_QMASK=none switches the masking off.
+ * Held, exactly, to an independent statement of this procedure on strings and sets (tests/orient_exact.py) at the rule's edges
+ * -- f = 4 v, f = 4 v - 1, (1, 0), (0, 1) and their mirrors -- by tests/test_orient_edges_cpu.py.
  *   dbbits: 4^12 bits (2 MB), bit k set when 12-mer k (first base in the low bits) occurs in the database.
  */
 static inline uint32_t rc24(uint32_t k)

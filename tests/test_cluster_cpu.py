@@ -7,6 +7,7 @@ so that the thing the GPU engine is compared with (tests/test_gpu_cluster.py) is
 import numpy as np
 
 import orc
+from dust_exact import py_dust          # the independent DUST statement, shared with the orientation model
 
 _RC = str.maketrans("ACGTUNRYMKSWHBVD", "TGCAANYRKMSWDVBH")         # the complement of every IUPAC set (U is T)
 _IUPAC = {"A": 1, "C": 2, "G": 4, "T": 8, "U": 8, "R": 5, "Y": 10, "M": 3, "K": 12, "S": 6, "W": 9, "H": 11, "B": 14,
@@ -46,40 +47,6 @@ def py_align(q, t):
             H[i][j] = best
     s, m, c = H[Lq][Lt]
     return s, m, -c
-
-
-def py_dust(seq):
-    """vsearch's DUST soft mask (mask.cc dust()/wo(), after Tatusov & Lipman), stated independently of orc_dust: windows of 64
-    that advance by 32, 3-mer repeat score 10 * sum / j, masked above 20, the first best interval in (i, j) order"""
-    code = {"A": 0, "C": 1, "G": 2, "T": 3, "U": 3}
-    s = [code.get(c, 0) for c in seq.upper()]
-    masked = [False] * len(s)
-    i = 0
-    while i < len(s):
-        win = s[i:i + 64]
-        n = len(win)
-        best = (0, 0, 0)
-        if n - 7 >= 0:
-            tri = [((win[j - 2] if j >= 2 else 0) << 4 | (win[j - 1] if j >= 1 else 0) << 2 | win[j]) for j in range(n)]
-            for a in range(n - 7):
-                seen, total = {}, 0
-                for j in range(2, n - a):
-                    w = tri[a + j]
-                    c = seen.get(w, 0)
-                    if c:
-                        total += c
-                        v = 10 * total // j
-                        if v > best[0]:
-                            best = (v, a, j)
-                    seen[w] = c + 1
-        v, a, j = best
-        if v > 20:
-            for k in range(a + i, a + j + i + 1):
-                masked[k] = True
-            if a + j < 32:
-                i += 32 - (a + j)
-        i += 32
-    return masked
 
 
 def py_words(s, masked=None):
