@@ -106,7 +106,7 @@ typedef struct {
   /* multidomain regions of the last search: resolved by stochastic traceback clustering (k_ensemble.hip), of which
    * n_mr_failed hit a bookkeeping limit or an unsampleable matrix and yielded nothing; envelopes the clustering defined */
   int64_t n_mr_clustered, n_mr_failed, n_mr_envelopes;
-  float   ms_ensemble;       int32_t pad3;
+  float   ms_ensemble;       float   ms_deflate;         /* k_deflate of the last device deflate, all waves together (was padding) */
   int64_t n_mr_distinct;     /* distinct (profile, target length, residues) multidomain regions actually sampled */
   int64_t n_slab_shrinks;    /* times the DP slab budget was halved because the device could not supply it */
   float   ms_vit_kernel;     int32_t pad4;               /* Viterbi filter (F2 < F1 only) */
@@ -353,7 +353,7 @@ int itsx_keep_records(itsx_ctx *ctx, int on);
  * still gets its empty file).
  * Coordinates: either left_prefix / right_prefix (the per-read coordinates of the finalized search, taken where they are on the
  * device, as itsx_trim_coords_device gives them), or start / stop [n_reads] from the caller -- exactly one of the two.
- * compression: 0 plain, 1 gzip, 2 zstd.  n_written_per_sample / total_len_per_sample: [n_samples], may be NULL.
+ * compression: 0 plain, 1 gzip, 2 zstd, 3 gzip deflated on the device (below).  n_written_per_sample / total_len_per_sample: [n_samples], may be NULL.
  * ITSX_E_ARG: no records (the message names itsx_keep_records), n_samples != itsx_num_samples, both or neither coordinate source,
  * prefixes before itsx_search_finalize.  ITSX_E_IO: a file could not be written whole (it is removed, never left short).
  * The text of the whole batch is made on the device (csrc/k_trim.hip) and fetched in pieces; the context's results are untouched. */
@@ -378,7 +378,7 @@ int itsx_keep_pair_records(itsx_ctx *ctx, int on);
  * a sample that writes nothing still gets its two empty files (gzip / zstd: a valid empty member).
  * Coordinates: either left_prefix / right_prefix (the finalized search's per-read coordinates, taken where they are on the
  * device), or start / stop / tlen [n_reads] from the caller -- exactly one of the two, and all three arrays.
- * compression: 0 plain, 1 gzip, 2 zstd.  n_written_per_sample: [n_samples] pairs written, may be NULL.
+ * compression: 0 plain, 1 gzip, 2 zstd, 3 gzip deflated on the device (below).  n_written_per_sample: [n_samples] pairs written, may be NULL.
  * ITSX_E_ARG: no pair records (the message names itsx_keep_pair_records), n_samples != itsx_num_samples, one path of a sample's two
  * NULL, both, neither or part of a coordinate source, prefixes before itsx_search_finalize.  ITSX_E_IO: zstd requested but not
  * available, or a file could not be written whole: then every file this call was given is removed (R1's files are written before
@@ -386,6 +386,27 @@ int itsx_keep_pair_records(itsx_ctx *ctx, int on);
 int itsx_write_trimmed_paired_samples(itsx_ctx *ctx, const char *const *out1_paths, const char *const *out2_paths, int32_t n_samples,
                                       int compression, int trim_ccs, const char *left_prefix, const char *right_prefix,
                                       const int32_t *start, const int32_t *stop, const int32_t *tlen, int64_t *n_written_per_sample);
+/* ---- gzip output deflated on the device (opt-in).  compression == 3 in the two calls above means "gzip, deflated on the device":
+ * the text k_trim.hip leaves in device memory is cut into blocks of at most itsx_deflate_block_bytes() bytes, none across two files,
+ * csrc/k_deflate.hip turns every block into one independent gzip member (greedy LZ77 matches from a 4-byte hash, dynamic Huffman
+ * codes, stored blocks where those are not larger; CRC-32 and ISIZE per member), and only the members come back to the host, where a
+ * file is its members written one after another -- the "concatenated gzip members" the host writers make too.  Same records, other
+ * bytes, a ratio like a fast deflate level's; the same input gives the same bytes on every run.  An empty file is one empty member.
+ * Everything else about the two calls stays: a NULL path is skipped, a file that could not be written whole is removed, and a failed
+ * paired call leaves neither file of a pair.  With ITSX_DEVICE_DEFLATE=1 in the environment, compression == 1 takes this path in these
+ * two calls.  The host-only writers (itsx_write_trimmed_fastq, itsx_write_trimmed_paired, itsx_twriter_*) have no device text and
+ * refuse 3.  Device memory: a fixed scratch of about 0.4 GB for any size of batch.  itsx_stats.ms_deflate: the kernel's time. */
+int64_t itsx_deflate_block_bytes(void);
+/* the most bytes itsx_deflate_device can write for nbytes of text in n_ranges ranges (host only) */
+int64_t itsx_deflate_bound(int64_t nbytes, int32_t n_ranges);
+/* The coder by itself, for any bytes: ranges [bounds[r], bounds[r + 1]) of text (bounds[0] = 0, bounds[n_ranges] = nbytes, non-decreasing)
+ * go to the device and range r's members arrive in out[out_bounds[r], out_bounds[r + 1]) (out_bounds: n_ranges + 1 entries).
+ * ITSX_E_ARG: out_cap below itsx_deflate_bound(nbytes, n_ranges), or bounds that do not tile the text. */
+int itsx_deflate_device(itsx_ctx *ctx, const char *text, int64_t nbytes, const int64_t *bounds, int32_t n_ranges, char *out, int64_t out_cap,
+                        int64_t *out_bounds);
+/* csrc/deflate_codes.h on the host (no context, no device): the code lengths the kernel gives n <= 288 symbols of these counts (sum
+ * below 2^32) under a limit of maxbits (1..15, n <= 2^maxbits).  lengths: [n]. */
+int itsx_debug_huffman_lengths(const uint32_t *freq, int32_t n, int32_t maxbits, uint8_t *lengths);
 
 /* ---- a1: SeqSample.deduplicate (itsxpress/SeqSample.py:93-131)
  * = vsearch --fastx_uniques --strand both; vsearch's --minseqlength default is 1 for this command (32 for the clustering

@@ -48,7 +48,7 @@ STATS_FIELDS = [("n_reads", "<i8"), ("n_unique", "<i8"), ("n_dropped_short", "<i
                 ("ms_trim_plan", "<f4"), ("cl_certified", "<i8"), ("ms_pack", "<f4"), ("ms_trim_copy", "<f4"),
                 ("n_uniq_multi_winner", "<i8"), ("n_reads_multi_winner", "<i8"), ("n_uniq_region_cap", "<i8"),
                 ("n_reads_region_cap", "<i8"), ("n_mr_clustered", "<i8"), ("n_mr_failed", "<i8"), ("n_mr_envelopes", "<i8"),
-                ("ms_ensemble", "<f4"), ("pad3", "<i4"), ("n_mr_distinct", "<i8"), ("n_slab_shrinks", "<i8"), ("ms_vit_kernel", "<f4"), ("pad4", "<i4"),
+                ("ms_ensemble", "<f4"), ("ms_deflate", "<f4"), ("n_mr_distinct", "<i8"), ("n_slab_shrinks", "<i8"), ("ms_vit_kernel", "<f4"), ("pad4", "<i4"),
                 ("n_mr_fail_kind", "<i8", (8,)), ("n_rows_resident", "<i8"),
                 ("lazy", "<i4"), ("n_bound_launches", "<i4"), ("n_lazy_pending_profiles", "<i8"), ("n_lazy_completed", "<i8"), ("n_lazy_completed_profiles", "<i8"), ("n_mr_overflow", "<i8"), ("ms_lazy_complete", "<f4"), ("lazy_bound_maxdiff", "<f4"), ("n_lazy_evaluated", "<i8"), ("n_lazy_round1", "<i8"),
                 ("n_lazy_pending", "<i8"), ("n_lazy_reruns", "<i8"), ("bound_rows", "<i8"), ("ms_bound_kernel", "<f4"),
@@ -85,7 +85,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_twriter_open", "itsx_twriter_text", "itsx_twriter_coords", "itsx_twriter_update", "itsx_twriter_close",
            "itsx_lazy_pending_uniques", "itsx_set_partial_coords", "itsx_set_kept_rows",
            "itsx_keep_records", "itsx_write_trimmed_samples",
-           "itsx_keep_pair_records", "itsx_write_trimmed_paired_samples"]
+           "itsx_keep_pair_records", "itsx_write_trimmed_paired_samples",
+           "itsx_deflate_block_bytes", "itsx_deflate_bound", "itsx_deflate_device", "itsx_debug_huffman_lengths"]
 
 
 def lib():
@@ -151,6 +152,10 @@ def lib():
         "itsx_write_trimmed_samples": (i32, [vp, vp, i32, i32, i32, cp, cp, vp, vp, vp, vp]),
         "itsx_keep_pair_records": (i32, [vp, i32]),
         "itsx_write_trimmed_paired_samples": (i32, [vp, vp, vp, i32, i32, i32, cp, cp, vp, vp, vp, vp]),
+        "itsx_deflate_block_bytes": (i64, []),
+        "itsx_deflate_bound": (i64, [i64, i32]),
+        "itsx_deflate_device": (i32, [vp, vp, i64, vp, i32, vp, i64, vp]),
+        "itsx_debug_huffman_lengths": (i32, [vp, i32, i32, vp]),
         "itsx_unique_keys128": (i32, [vp, C.c_uint64, C.c_uint64, i64, vp]),
         "itsx_write_derep_arrays": (i32, [cp, cp, i64, vp, vp, vp, vp, vp, vp, vp, i64]),
         "itsx_write_domtbl_arrays": (i32, [cp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp]),

@@ -300,6 +300,23 @@ class SampleBatch:
         return out
 
     # -- the consumers of the coordinates, per sample -------------------------------------------
+    # Where write_trimmed / write_paired_trimmed make the bytes of gzip output when they cut the files from records on the device:
+    # the engine's own setting (Engine.deflate, "host" by default), under the batch's name.  The host loops have no device text:
+    # with "device" they still write with the host's deflate and say so.
+    @property
+    def deflate(self) -> str:
+        return getattr(self.engine, "deflate", "host")
+
+    @deflate.setter
+    def deflate(self, where: str):
+        self.engine.deflate = where
+
+    def _device_deflate_falls_back(self, who, gzipped, zstd_file):
+        if self.deflate == "device":
+            from .engine import _batch_compression
+            _batch_compression(gzipped, zstd_file, "device", who)           # the same ValueError as on the device path
+            logging.info("%s: no records on the device to cut the files from, so the host writes and deflates them (deflate = \"device\" has no device text here)", who)
+
     def _sample_range(self, i: int):
         return int(self.first[i]), int(self.first[i] + self.counts[i])
 
@@ -310,7 +327,8 @@ class SampleBatch:
         The host writer reads and parses every sample's two files again -- unless the batch keeps the pair records
         (keep_records="pairs") and the engine still holds its read set: then every sample's two files are cut from the records on the
         device in one engine call (itsx_write_trimmed_paired_samples), the same bytes.  (Inputs with lower-case bases keep no pair records
-        -- the merge reads them in upper case -- and take the host loop.)"""
+        -- the merge reads them in upper case -- and take the host loop.)
+        With self.deflate = "device" the engine call makes the gzip bytes (gzipped=True) on the device."""
         from .trim import write_trimmed_paired
         left, right = _REGION_PREFIX[region]
         if self.keep_pair_records and self._pair_records_read_set is not None and getattr(self.engine, "read_set", None) == self._pair_records_read_set:
@@ -324,6 +342,7 @@ class SampleBatch:
                 if e.code != -1 or "itsx_keep_pair_records" not in str(e):
                     raise
                 self._pair_records_read_set = None
+        self._device_deflate_falls_back("write_paired_trimmed", gzipped, zstd_file)
         start, stop, tlen, _ = self.engine.trim_coords(left, right)
         blob, offs = self.engine.read_names_raw()
         out = []
@@ -341,12 +360,14 @@ class SampleBatch:
         """`Dedup.create_trimmed_seqs` of every sample from the batch's arrays: record k of sample i's seq_file trimmed to its
         coordinates, into outfiles[i].  A paired sample's seq_file is its merged reads: merge_reads must have written it -- unless the
         batch keeps records (keep_records=True) and the engine still holds its read set: then every sample's output is cut from the
-        records on the device in one engine call (itsx_write_trimmed_samples), the same bytes."""
+        records on the device in one engine call (itsx_write_trimmed_samples), the same bytes.
+        With self.deflate = "device" that call makes the gzip bytes (gzipped=True) on the device: the same records in other bytes."""
         from .trim import write_trimmed_fastq
         left, right = _REGION_PREFIX[region]
         if self.keep_records and self._records_read_set is not None and getattr(self.engine, "read_set", None) == self._records_read_set:
             return self.engine.write_trimmed_samples(list(outfiles), region_prefixes=(left, right), gzipped=gzipped, zstd_file=zstd_file,
                                                      trim_ccs=trim_ccs)
+        self._device_deflate_falls_back("write_trimmed", gzipped, zstd_file)
         for s in self.samples:
             if self._resident is not None and s.seq_file in self._resident and not (self._seq_written and os.path.exists(s.seq_file)):
                 raise EngineError(-1, "write_trimmed: the %s reads of this batch were never written (%s); call %s(write_seq_files=True)"

@@ -27,6 +27,7 @@
 #include "detmath.h"
 #include "engine.h"
 #include "k_api.h"
+#include "deflate_codes.h"
 #include "cluster_multi.h"
 #include "fastq_io.h"
 #include "iupac.h"
@@ -477,6 +478,7 @@ struct itsx_ctx {
   } prec;
   DBuf<TrimRec> w_trec2; DBuf<int32_t> w_ttlen;          // itsx_write_trimmed_paired_samples (beside the buffers below)
   DBuf<TrimRec> w_trec; DBuf<int64_t> w_tcnt, w_ttot, w_tblk, w_tfirst, w_tbounds; DBuf<int32_t> w_tstart, w_tstop; DBuf<uint32_t> w_tout;   // itsx_write_trimmed_samples
+  DBuf<DeflateBlock> w_dblk; DBuf<uint32_t> w_dtok, w_dtext; DBuf<uint8_t> w_dslots, w_dpacked; DBuf<int32_t> w_dsizes; DBuf<int64_t> w_ddst;   // deflate_ranges
   bool two_on = false; int share_maxrd = 0; int32_t Ub = 0; size_t sh_gslots_off = 0;
   DBuf<uint8_t> sh_rdepth_s, sh_rdepth; DBuf<unsigned long long> sh_rmask_s, sh_rmask, sh_keys, sh_keys2;
   DBuf<int32_t> sh_rparent_s, sh_rparent, sh_jlev_s, sh_jown_s, sh_endrow_s, sh_rsteps_s, sh_rnn_s, sh_rnode0_s, sh_endrow, sh_jlev, sh_jsrc, sh_jownb;
@@ -4818,27 +4820,22 @@ static int coords_device(itsx_ctx *ctx, const char *lp, const char *rp, bool per
 }
 int itsx_trim_coords_device(itsx_ctx *ctx, const char *lp, const char *rp, int32_t **d_rows, int64_t *n_rows) { return coords_device(ctx, lp, rp, true, d_rows, n_rows); }
 int itsx_rep_coords_device(itsx_ctx *ctx, const char *lp, const char *rp, int32_t **d_rows, int64_t *n_rows) { return coords_device(ctx, lp, rp, false, d_rows, n_rows); }
-// the second half of the batch writers: the text k_trim_copy left in w_tout (total bytes; sample s's file is bytes [bo[s], bo[s + 1]))
-// comes back through the pinned staging buffers in pieces, and each sample's range goes through a BlockWriter of its own, several samples
-// at a time (a null path: that sample is skipped).  A file that could not be written whole is removed; the other samples' files stay.
-static int trim_text_to_files(itsx_ctx *ctx, int64_t total, const int64_t *bo, const char *const *out_paths, int compression)
+// ITSX_DEVICE_DEFLATE=1: the batch writers' gzip output (compression 1) takes the device path (compression 3); read at every call
+static bool device_deflate_switch() { const char *e = sw_get("ITSX_DEVICE_DEFLATE"); return e && atoi(e) == 1; }
+// nbytes of device memory to the host: pieces through the pinned staging buffers, copied on while the next piece is on the bus
+static int fetch_staged(itsx_ctx *ctx, const uint8_t *dsrc, int64_t total, char *dst)
 {
   hipStream_t st = ctx->st;
-  const int32_t S = ctx->S;
-  // ---- the text to the host: pieces through the pinned staging buffers, copied on while the next piece is on the bus
-  itsx_io::Text text;
-  if (!text.resize((size_t)total)) SET_ERR(ctx, ITSX_E_NOMEM, "out of memory for the batch's trimmed text");
   if (total > 0) {
     const int64_t CH = std::min<int64_t>(64ll << 20, std::max<int64_t>(total, 70000));
     { const int rc = stage_reserve(ctx, CH); if (rc != ITSX_OK) return rc; }
     const int64_t piece = (int64_t)ctx->stage_cap;
     const int64_t np = (total + piece - 1) / piece;
     constexpr int K = itsx_ctx::NSTAGE;
-    const uint8_t *dsrc = reinterpret_cast<const uint8_t *>(ctx->w_tout.p);
     auto drain = [&](int64_t c) -> int {       // piece c has been enqueued: wait for it and copy it on
       HIPCHK(hipEventSynchronize(ctx->stage_ev[c % K]));
       const int64_t o = c * piece, b = std::min(piece, total - o);
-      memcpy(text.data() + o, ctx->stage_pin[c % K], (size_t)b);
+      memcpy(dst + o, ctx->stage_pin[c % K], (size_t)b);
       return ITSX_OK;
     };
     for (int64_t c = 0; c < np; c++) {
@@ -4851,9 +4848,108 @@ static int trim_text_to_files(itsx_ctx *ctx, int64_t total, const int64_t *bo, c
   }
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
-  // ---- one file per sample, several at a time (16 threads in all, the block writers' own pools included)
+  return ITSX_OK;
+}
+// ------------------------------------------------------------------------------ gzip members made on the device (k_deflate.hip)
+// Ranges [lo, hi) of a device text (readable 8 bytes past the last range), each cut into blocks of at most DEFLATE_BLOCK_BYTES; every
+// block becomes one gzip member (an empty range: one empty member), and range r's members end up one after another in
+// z[zb[r], zb[r + 1]).  The blocks go through the device in waves of at most DEFLATE_WAVE, so the scratch (worst-case slots, the
+// packed members, the token slots of the resident workgroups) is a fixed budget of about 0.4 GB whatever the text's size; only
+// compressed bytes come back, through the pinned staging buffers.  stats.ms_deflate: the wave kernels' time, by device events.
+constexpr int32_t DEFLATE_WAVE = 2048;
+static int64_t deflate_bound(int64_t nbytes, int64_t n_ranges)
+{ return nbytes + (nbytes / DEFLATE_BLOCK_BYTES + n_ranges) * (int64_t)(DEFLATE_SLOT_BYTES - DEFLATE_BLOCK_BYTES); }
+static int deflate_ranges(itsx_ctx *ctx, const uint8_t *dtext, const std::vector<std::pair<int64_t, int64_t>> &ranges, std::vector<char> &z,
+                          std::vector<int64_t> &zb)
+{
+  hipStream_t st = ctx->st;
+  std::vector<DeflateBlock> blocks; std::vector<int32_t> owner;
+  for (size_t r = 0; r < ranges.size(); r++) {
+    int64_t o = ranges[r].first;
+    do {
+      const int64_t b = std::min<int64_t>(DEFLATE_BLOCK_BYTES, ranges[r].second - o);
+      blocks.push_back(DeflateBlock{o, (int32_t)b, 0}); owner.push_back((int32_t)r);
+      o += b;
+    } while (o < ranges[r].second);
+  }
+  zb.assign(ranges.size() + 1, 0); z.clear();
+  ctx->stats.ms_deflate = 0;
+  if (blocks.empty()) return ITSX_OK;
+  int ncu = 256;
+  { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, ctx->device) == hipSuccess && pr.multiProcessorCount > 0) ncu = pr.multiProcessorCount; }
+  const int32_t wave = (int32_t)std::min<size_t>(blocks.size(), (size_t)DEFLATE_WAVE);
+  const int grid = std::min<int>(wave, ncu);                                 // one workgroup's LDS is most of a CU's
+  HIPCHK(ctx->w_dblk.alloc((size_t)wave)); HIPCHK(ctx->w_dsizes.alloc((size_t)wave)); HIPCHK(ctx->w_ddst.alloc((size_t)wave));
+  HIPCHK(ctx->w_dtok.alloc((size_t)grid * DEFLATE_TOKEN_SLOT));
+  HIPCHK(ctx->w_dslots.alloc((size_t)wave * DEFLATE_SLOT_BYTES)); HIPCHK(ctx->w_dpacked.alloc((size_t)wave * DEFLATE_SLOT_BYTES));
+  std::vector<int32_t> sizes((size_t)wave); std::vector<int64_t> dst((size_t)wave);
+  std::vector<int64_t> rsize(ranges.size(), 0);
+  for (size_t b0 = 0; b0 < blocks.size(); b0 += (size_t)wave) {
+    const int32_t nb = (int32_t)std::min<size_t>((size_t)wave, blocks.size() - b0);
+    HIPCHK(hipMemcpyAsync(ctx->w_dblk.p, blocks.data() + b0, (size_t)nb * sizeof(DeflateBlock), hipMemcpyHostToDevice, st));
+    DeflateArgs da{};
+    da.text = dtext; da.blk = ctx->w_dblk.p; da.nblk = nb; da.tokens = ctx->w_dtok.p; da.slots = ctx->w_dslots.p; da.sizes = ctx->w_dsizes.p;
+    {
+      StageTimer tm(st);
+      launch_deflate(da, grid, st);
+      ctx->stats.ms_deflate += tm.stop();
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sizes.data(), ctx->w_dsizes.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int64_t packed = 0;
+    for (int32_t k = 0; k < nb; k++) {
+      if (sizes[(size_t)k] < 20 || sizes[(size_t)k] > DEFLATE_SLOT_BYTES - 2) SET_ERR(ctx, ITSX_E_DEVICE, "the device deflate left a member of " + std::to_string(sizes[(size_t)k]) + " bytes");
+      dst[(size_t)k] = packed; packed += sizes[(size_t)k]; rsize[(size_t)owner[b0 + (size_t)k]] += sizes[(size_t)k];
+    }
+    HIPCHK(hipMemcpyAsync(ctx->w_ddst.p, dst.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+    launch_deflate_pack(ctx->w_dslots.p, ctx->w_dsizes.p, ctx->w_ddst.p, nb, ctx->w_dpacked.p, st);
+    HIPCHK(hipGetLastError());
+    const size_t at = z.size();
+    try { z.resize(at + (size_t)packed); } catch (const std::bad_alloc &) { SET_ERR(ctx, ITSX_E_NOMEM, "out of memory for the batch's compressed text"); }
+    { const int rc = fetch_staged(ctx, ctx->w_dpacked.p, packed, z.data() + at); if (rc != ITSX_OK) return rc; }
+  }
+  for (size_t r = 0; r < ranges.size(); r++) zb[r + 1] = zb[r] + rsize[r];
+  return ITSX_OK;
+}
+// the second half of the batch writers: the text k_trim_copy left in w_tout (total bytes; sample s's file is bytes [bo[s], bo[s + 1]))
+// comes back through the pinned staging buffers in pieces, and each sample's range goes through a BlockWriter of its own, several samples
+// at a time (a null path: that sample is skipped).  A file that could not be written whole is removed; the other samples' files stay.
+// compression 3: the text stays where it is, its samples' ranges are deflated on the device (deflate_ranges) and the files are plain
+// writes of the gzip members that come back.
+static int trim_text_to_files(itsx_ctx *ctx, int64_t total, const int64_t *bo, const char *const *out_paths, int compression)
+{
+  const int32_t S = ctx->S;
   std::vector<int32_t> todo;
   for (int32_t s = 0; s < S; s++) if (out_paths[s]) todo.push_back(s);
+  if (compression == 3) {
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    for (int32_t s : todo) ranges.emplace_back(bo[s], bo[s + 1]);
+    std::vector<char> z; std::vector<int64_t> zb;
+    { const int rc = deflate_ranges(ctx, reinterpret_cast<const uint8_t *>(ctx->w_tout.p), ranges, z, zb); if (rc != ITSX_OK) return rc; }
+    const int T = std::max(1, std::min<int>({itsx_io::io_threads(), 16, (int)todo.size()}));
+    std::vector<std::string> werrs((size_t)T);
+    std::atomic<size_t> next{0};
+    on_threads(T, [&](int t) {
+      for (;;) {
+        const size_t q = next.fetch_add(1);
+        if (q >= todo.size()) break;
+        const char *path = out_paths[todo[q]];
+        const size_t nz = (size_t)(zb[q + 1] - zb[q]);
+        FILE *fp = fopen(path, "wb");
+        if (!fp) { werrs[(size_t)t] = std::string("cannot open ") + path + " for writing"; continue; }
+        const bool short_write = fwrite(z.data() + zb[q], 1, nz, fp) != nz;
+        if (fclose(fp) != 0 || short_write) { werrs[(size_t)t] = std::string("could not write ") + path; (void)remove(path); }      // never a short file
+      }
+    });
+    for (const std::string &e : werrs) if (!e.empty()) SET_ERR(ctx, ITSX_E_IO, e);
+    return ITSX_OK;
+  }
+  // ---- the text to the host
+  itsx_io::Text text;
+  if (!text.resize((size_t)total)) SET_ERR(ctx, ITSX_E_NOMEM, "out of memory for the batch's trimmed text");
+  { const int rc = fetch_staged(ctx, reinterpret_cast<const uint8_t *>(ctx->w_tout.p), total, text.data()); if (rc != ITSX_OK) return rc; }
+  // ---- one file per sample, several at a time (16 threads in all, the block writers' own pools included)
   const int T = std::max(1, std::min<int>({itsx_io::io_threads(), 16, (int)todo.size()}));
   std::vector<std::string> werrs((size_t)T);
   std::atomic<size_t> next{0};
@@ -4884,12 +4980,13 @@ int itsx_write_trimmed_samples(itsx_ctx *ctx, const char *const *out_paths, int3
   CTXCHK(ctx && out_paths);
   if (!ctx->rec.have) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_samples: the read set keeps no records; call itsx_keep_records(ctx, 1) before the reads are loaded, merged or oriented");
   if (n_samples != ctx->S) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_samples: " + std::to_string(n_samples) + " output paths for " + std::to_string(ctx->S) + " sample(s)");
-  if (compression < 0 || compression > 2) SET_ERR(ctx, ITSX_E_ARG, "compression must be 0 (plain), 1 (gzip) or 2 (zstd)");
+  if (compression < 0 || compression > 3) SET_ERR(ctx, ITSX_E_ARG, "compression must be 0 (plain), 1 (gzip), 2 (zstd) or 3 (gzip, deflated on the device)");
+  if (compression == 1 && device_deflate_switch()) compression = 3;
   const bool by_prefix = left_prefix || right_prefix, by_arrays = start || stop;
   if (by_prefix == by_arrays || (by_prefix && !(left_prefix && right_prefix)) || (by_arrays && !(start && stop)))
     SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_samples: give either left_prefix and right_prefix or start and stop");
   if (by_prefix && !ctx->have_final) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_samples: prefixes given before itsx_search_finalize");
-  { itsx_io::PieceCompressor probe(compression); if (!probe.ok()) SET_ERR(ctx, ITSX_E_IO, "zstd output requested but libzstd.so.1 could not be loaded"); }
+  if (compression != 3) { itsx_io::PieceCompressor probe(compression); if (!probe.ok()) SET_ERR(ctx, ITSX_E_IO, "zstd output requested but libzstd.so.1 could not be loaded"); }
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->st;
   const int64_t n = ctx->N; const int32_t S = ctx->S;
@@ -4947,12 +5044,13 @@ int itsx_write_trimmed_paired_samples(itsx_ctx *ctx, const char *const *out1_pat
     SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_paired_samples: " + std::to_string(n_samples) + " pairs of output paths for " + std::to_string(ctx->S) + " sample(s)");
   for (int32_t s = 0; s < n_samples; s++)
     if ((out1_paths[s] == nullptr) != (out2_paths[s] == nullptr)) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_paired_samples: sample " + std::to_string(s) + " has one output path of its two");
-  if (compression < 0 || compression > 2) SET_ERR(ctx, ITSX_E_ARG, "compression must be 0 (plain), 1 (gzip) or 2 (zstd)");
+  if (compression < 0 || compression > 3) SET_ERR(ctx, ITSX_E_ARG, "compression must be 0 (plain), 1 (gzip), 2 (zstd) or 3 (gzip, deflated on the device)");
+  if (compression == 1 && device_deflate_switch()) compression = 3;
   const bool by_prefix = left_prefix || right_prefix, by_arrays = start || stop || tlen;
   if (by_prefix == by_arrays || (by_prefix && !(left_prefix && right_prefix)) || (by_arrays && !(start && stop && tlen)))
     SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_paired_samples: give either left_prefix and right_prefix or start, stop and tlen");
   if (by_prefix && !ctx->have_final) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_paired_samples: prefixes given before itsx_search_finalize");
-  { itsx_io::PieceCompressor probe(compression); if (!probe.ok()) SET_ERR(ctx, ITSX_E_IO, "zstd output requested but libzstd.so.1 could not be loaded"); }
+  if (compression != 3) { itsx_io::PieceCompressor probe(compression); if (!probe.ok()) SET_ERR(ctx, ITSX_E_IO, "zstd output requested but libzstd.so.1 could not be loaded"); }
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->st;
   const int64_t nr = ctx->N, n = pr.n; const int32_t S = ctx->S;
@@ -5007,6 +5105,40 @@ int itsx_write_trimmed_paired_samples(itsx_ctx *ctx, const char *const *out1_pat
     }
   }
   if (n_written_per_sample) for (int32_t s = 0; s < S; s++) n_written_per_sample[s] = bc[s + 1] - bc[s];
+  return ITSX_OK;
+}
+// ---- the device deflate by itself
+int64_t itsx_deflate_block_bytes(void) { return DEFLATE_BLOCK_BYTES; }
+int64_t itsx_deflate_bound(int64_t nbytes, int32_t n_ranges) { return deflate_bound(std::max<int64_t>(nbytes, 0), std::max<int32_t>(n_ranges, 0)); }
+int itsx_deflate_device(itsx_ctx *ctx, const char *text, int64_t nbytes, const int64_t *bounds, int32_t n_ranges, char *out, int64_t out_cap,
+                        int64_t *out_bounds)
+{
+  CTXCHK(ctx && bounds && out_bounds && n_ranges >= 0 && nbytes >= 0 && (text || nbytes == 0) && (out || out_cap == 0));
+  if (n_ranges > 0 && (bounds[0] != 0 || bounds[n_ranges] != nbytes)) SET_ERR(ctx, ITSX_E_ARG, "itsx_deflate_device: bounds must run from 0 to nbytes");
+  for (int32_t r = 0; r < n_ranges; r++) if (bounds[r] > bounds[r + 1]) SET_ERR(ctx, ITSX_E_ARG, "itsx_deflate_device: bounds must not decrease");
+  if (out_cap < itsx_deflate_bound(nbytes, n_ranges)) SET_ERR(ctx, ITSX_E_ARG, "itsx_deflate_device: out_cap is below itsx_deflate_bound(nbytes, n_ranges)");
+  HIPCHK(hipSetDevice(ctx->device));
+  out_bounds[0] = 0;
+  if (n_ranges == 0) return ITSX_OK;
+  HIPCHK(ctx->w_dtext.alloc((size_t)(nbytes / 4) + 16));
+  if (nbytes > 0) HIPCHK(hipMemcpyAsync(ctx->w_dtext.p, text, (size_t)nbytes, hipMemcpyHostToDevice, ctx->st));
+  std::vector<std::pair<int64_t, int64_t>> ranges;
+  for (int32_t r = 0; r < n_ranges; r++) ranges.emplace_back(bounds[r], bounds[r + 1]);
+  std::vector<char> z; std::vector<int64_t> zb;
+  { const int rc = deflate_ranges(ctx, reinterpret_cast<const uint8_t *>(ctx->w_dtext.p), ranges, z, zb); if (rc != ITSX_OK) return rc; }
+  if ((int64_t)z.size() > out_cap) SET_ERR(ctx, ITSX_E_DEVICE, "the device deflate went past its bound");
+  if (!z.empty()) memcpy(out, z.data(), z.size());
+  for (int32_t r = 0; r <= n_ranges; r++) out_bounds[r] = zb[(size_t)r];
+  return ITSX_OK;
+}
+int itsx_debug_huffman_lengths(const uint32_t *freq, int32_t n, int32_t maxbits, uint8_t *lengths)
+{
+  if (!freq || !lengths || n < 1 || n > itsx_dc::MAX_SYMS || maxbits < 1 || maxbits > 15 || (maxbits < 9 && n > (1 << maxbits))) return ITSX_E_ARG;
+  uint64_t sum = 0;
+  for (int32_t i = 0; i < n; i++) sum += freq[i];
+  if (sum >> 32) return ITSX_E_ARG;
+  uint32_t work[itsx_dc::WORK_WORDS];
+  itsx_dc::dc_huffman_lengths(freq, n, maxbits, lengths, work);
   return ITSX_OK;
 }
 int itsx_derep_device(itsx_ctx *ctx, const int32_t **d_rep_of, const int32_t **d_uniq_of, const int8_t **d_strand, const int32_t **d_seed_read)

@@ -214,6 +214,22 @@ void launch_trim_pair_plan(const TrimPairPlanArgs &a, const int64_t *first, int3
 void launch_trim_orient(const uint8_t *seq, const uint8_t *qual, const int64_t *off, const int32_t *from, const int8_t *strand, const uint8_t *comp,
                         const int64_t *noff, int64_t m, uint8_t *nseq, uint8_t *nqual, hipStream_t st);
 
+// ---- k_deflate.hip (the batch writers' gzip output made on the device: one gzip member per block of text)
+constexpr int DEFLATE_BLOCK_BYTES = 65535;      // text of one member at most: what ONE stored block holds, so a member never costs more than len + 5 + 18
+constexpr int DEFLATE_SLOT_BYTES = 65600;       // where a member is built: its stored form (text + 5 + 18) after 2 bytes of lead, whole dwords
+constexpr int DEFLATE_TOKEN_SLOT = 65536;       // tokens of one block at most (one per byte), rounded up
+struct DeflateBlock { int64_t src; int32_t len, pad; };      // text bytes [src, src + len), len <= DEFLATE_BLOCK_BYTES (0: an empty member)
+struct DeflateArgs {
+  const uint8_t *text;                          // readable 8 bytes past the last block's end
+  const DeflateBlock *blk; int32_t nblk;
+  uint32_t *tokens;                             // [workgroups of the launch][DEFLATE_TOKEN_SLOT] scratch
+  uint8_t *slots;                               // [nblk][DEFLATE_SLOT_BYTES], 4-byte aligned: block b's member from byte 2 of its slot
+  int32_t *sizes;                               // [nblk] bytes of each member
+};
+void launch_deflate(const DeflateArgs &a, int grid, hipStream_t st);
+// member b (sizes[b] bytes) from its slot to out + dst[b]
+void launch_deflate_pack(const uint8_t *slots, const int32_t *sizes, const int64_t *dst, int32_t nblk, uint8_t *out, hipStream_t st);
+
 // ---- k_util.hip
 // exclusive prefix sum of n int32 values (n < 2^31); tmp must hold scan_tmp_elems(n) int32
 int64_t scan_tmp_elems(int64_t n);

@@ -36,6 +36,17 @@ def _devtensor(ptr, shape, typestr, device):
     return torch.as_tensor(_DevArray(ptr, shape, typestr), device=device)
 
 
+def _batch_compression(gzipped, zstd_file, deflate, who):
+    """The batch writers' compression kind: the reference's two flags, and 3 (gzip members made on the device) where deflate is
+    "device" -- which goes with gzip output only."""
+    from .trim import _compression
+    if deflate == "device":
+        if zstd_file or not gzipped:
+            raise ValueError('%s: deflate = "device" makes gzip output: it goes with gzipped=True and without zstd_file' % who)
+        return 3
+    return _compression(gzipped, zstd_file)
+
+
 class Engine:
     def __init__(self, device=None):
         self.L = _lib.lib()
@@ -52,6 +63,20 @@ class Engine:
         self.n_profiles = 0
         self.n_samples = 1
         self.rows_mode = -1
+
+    # Where the batch writers (write_trimmed_samples, write_trimmed_paired_samples) make the bytes of gzip output: "host" (the
+    # default: the text comes back and the host's deflate writes it, byte for byte what it always wrote) or "device" (the gzip
+    # members are made on the device, csrc/k_deflate.hip, and only they come back: the same records in other bytes, at a fast
+    # level's ratio).  Stays until set again; "device" asks for gzipped=True without zstd_file and is a ValueError otherwise.
+    @property
+    def deflate(self):
+        return getattr(self, "_deflate", "host")
+
+    @deflate.setter
+    def deflate(self, where):
+        if where not in ("host", "device"):
+            raise ValueError('Engine.deflate is "host" or "device", not %r' % (where,))
+        self._deflate = where
 
     # Every call that changes the context's read set records the new count here, so the setter is where the read set's serial number
     # advances: a caller that left reads resident (SampleBatch.merge_reads) keeps the number and can tell later whether the
@@ -569,8 +594,9 @@ class Engine:
     def write_trimmed_samples(self, paths, region_prefixes=None, start=None, stop=None, gzipped=False, zstd_file=False, trim_ccs=False):
         """The trimmed FASTQ of every sample of the batch (paths[s]; None skips a sample) in one call, from the records the context
         keeps.  Coordinates: region_prefixes = (left, right) of the finalized search, or start / stop arrays over the reads --
-        exactly one of the two.  Returns the per-sample (n_written, total_len) pairs."""
-        from .trim import _compression
+        exactly one of the two.  Returns the per-sample (n_written, total_len) pairs.
+        With self.deflate = "device" the gzip bytes (gzipped=True) are made on the device."""
+        kind = _batch_compression(gzipped, zstd_file, self.deflate, "write_trimmed_samples")
         S = len(paths)
         arr = (C.c_char_p * max(1, S))(*[None if p is None else os.fsencode(p) for p in paths])
         left = right = None
@@ -587,7 +613,7 @@ class Engine:
             keep.append(a if a.size else np.zeros(1, np.int32))
         nw = np.zeros(max(1, S), np.int64)
         tot = np.zeros(max(1, S), np.int64)
-        self._chk(self.L.itsx_write_trimmed_samples(self.h, arr, S, _compression(gzipped, zstd_file), int(bool(trim_ccs)), left, right,
+        self._chk(self.L.itsx_write_trimmed_samples(self.h, arr, S, kind, int(bool(trim_ccs)), left, right,
                                                     None if keep[0] is None else keep[0].ctypes.data,
                                                     None if keep[1] is None else keep[1].ctypes.data, nw.ctypes.data, tot.ctypes.data))
         return [(int(nw[s]), int(tot[s])) for s in range(S)]
@@ -605,8 +631,9 @@ class Engine:
         call, from the pair records the context keeps.  Coordinates: region_prefixes = (left, right) of the finalized search, or
         start / stop / tlen arrays over the merged reads -- exactly one of the two.  Returns the pairs written per sample.
         The given paths belong to the call: if any file cannot be written, EVERY path it was given is removed, also one that held a
-        file before the call and had not been opened yet, so that no half of a pair of files is left behind."""
-        from .trim import _compression
+        file before the call and had not been opened yet, so that no half of a pair of files is left behind.
+        With self.deflate = "device" the gzip bytes (gzipped=True) are made on the device."""
+        kind = _batch_compression(gzipped, zstd_file, self.deflate, "write_trimmed_paired_samples")
         S = len(paths1)
         if len(paths2) != S:
             raise ValueError("write_trimmed_paired_samples: one R1 and one R2 path per sample")
@@ -625,9 +652,24 @@ class Engine:
                 raise ValueError("write_trimmed_paired_samples: start / stop / tlen hold one entry per merged read")
             keep.append(a if a.size else np.zeros(1, np.int32))
         nw = np.zeros(max(1, S), np.int64)
-        self._chk(self.L.itsx_write_trimmed_paired_samples(self.h, arr1, arr2, S, _compression(gzipped, zstd_file), int(bool(trim_ccs)), left, right,
+        self._chk(self.L.itsx_write_trimmed_paired_samples(self.h, arr1, arr2, S, kind, int(bool(trim_ccs)), left, right,
                                                            *[None if k is None else k.ctypes.data for k in keep], nw.ctypes.data))
         return [int(nw[s]) for s in range(S)]
+
+    # ---- the device deflate by itself
+    def deflate_device(self, data, bounds):
+        """Ranges [bounds[r], bounds[r + 1]) of data (bounds[0] = 0, bounds[-1] = len(data)) as gzip files made on the device: one
+        bytes object per range, each the concatenated gzip members of that range's blocks (an empty range: one empty member)."""
+        data = bytes(data)
+        b = np.ascontiguousarray(bounds, np.int64)
+        if b.ndim != 1 or b.size < 1:
+            raise ValueError("deflate_device: bounds holds at least one entry")
+        R = int(b.size) - 1
+        cap = int(self.L.itsx_deflate_bound(len(data), R))
+        out = np.empty(max(cap, 1), np.uint8)
+        ob = np.zeros(R + 1, np.int64)
+        self._chk(self.L.itsx_deflate_device(self.h, data, len(data), b.ctypes.data, R, out.ctypes.data, cap, ob.ctypes.data))
+        return [out[int(ob[r]):int(ob[r + 1])].tobytes() for r in range(R)]
 
     # ---- writers
     def write_uc(self, path):
