@@ -91,7 +91,7 @@ typedef struct {
   float   ms_env_kernel;  float ms_bias_kernel;  int64_t env_rows;    /* the three envelope sweeps together; lane-rows per sweep */
   int64_t n_env_unique;           /* distinct (profile, length, envelope subsequence) actually re-scored */
   float   ms_decode_kernel;  int32_t n_batches;          /* launches of each DP kernel in the last search */
-  float   ms_cluster;        int32_t pad0;               /* itsx_cluster at id < 1: whole call */
+  float   ms_cluster;        int32_t n_tw_units_device;  /* itsx_cluster at id < 1: whole call | a context lent to streamed writers (itsx_twriter_set_device): units indexed, planned and copied on the device (was padding) */
   int64_t cl_windows, cl_cuts, cl_alignments;            /* speculative windows, windows cut by validation, alignments */
   float   ms_merge;                                      /* k_merge of the last itsx_merge_* call */
   float   ms_trim_plan;                                  /* the plan kernels of the last itsx_write_trimmed_paired_samples call (was padding) */
@@ -109,7 +109,7 @@ typedef struct {
   float   ms_ensemble;       float   ms_deflate;         /* k_deflate of the last device deflate, all waves together (was padding) */
   int64_t n_mr_distinct;     /* distinct (profile, target length, residues) multidomain regions actually sampled */
   int64_t n_slab_shrinks;    /* times the DP slab budget was halved because the device could not supply it */
-  float   ms_vit_kernel;     int32_t pad4;               /* Viterbi filter (F2 < F1 only) */
+  float   ms_vit_kernel;     int32_t n_tw_units_host;    /* Viterbi filter (F2 < F1 only) | a lent context: units the HOST sliced (lines not 4 per record, a malformed record, 2^31 bytes, the test hook) whose text the device deflated (was padding) */
   /* multidomain regions of the last search whose Forward matrix could not be sampled, by kind: [1] probabilities not normalised,
    * [5] a path left the region -- the cases in which hmmsearch's own stochastic traceback throws; itsx_search then returns
    * ITSX_E_UNSUPPORTED.  The former bookkeeping limits ([2] more than 8 domains in one sampled path, [4] more than 512 distinct
@@ -394,8 +394,8 @@ int itsx_write_trimmed_paired_samples(itsx_ctx *ctx, const char *const *out1_pat
  * bytes, a ratio like a fast deflate level's; the same input gives the same bytes on every run.  An empty file is one empty member.
  * Everything else about the two calls stays: a NULL path is skipped, a file that could not be written whole is removed, and a failed
  * paired call leaves neither file of a pair.  With ITSX_DEVICE_DEFLATE=1 in the environment, compression == 1 takes this path in these
- * two calls.  The host-only writers (itsx_write_trimmed_fastq, itsx_write_trimmed_paired, itsx_twriter_*) have no device text and
- * refuse 3.  Device memory: a fixed scratch of about 0.4 GB for any size of batch.  itsx_stats.ms_deflate: the kernel's time. */
+ * two calls.  The host-only writers (itsx_write_trimmed_fastq, itsx_write_trimmed_paired) have no device text and refuse 3; so does
+ * itsx_twriter_open, whose writer takes the device path through itsx_twriter_set_device instead (below).  Device memory: a fixed scratch of about 0.4 GB for any size of batch.  itsx_stats.ms_deflate: the kernel's time. */
 int64_t itsx_deflate_block_bytes(void);
 /* the most bytes itsx_deflate_device can write for nbytes of text in n_ranges ranges (host only) */
 int64_t itsx_deflate_bound(int64_t nbytes, int32_t n_ranges);
@@ -594,6 +594,21 @@ int itsx_twriter_open(const char *out_path, int compression, int trim_ccs, itsx_
 /* mode 1 (a paired run's mates, itsxpress/SeqSample.py:587-670): (start, stop) are Python slice bounds as they come -- start may be
  * negative, stop == INT32_MAX = open end, stop == INT32_MIN = the record is not written */
 int itsx_twriter_set_mode(itsx_twriter *w, int32_t mode);
+/* The writer's gzip output made on the device (opt-in): a unit that is ready has its raw text and coordinates uploaded, its lines
+ * indexed, its records planned, copied and deflated by the context (csrc/k_trim.hip, csrc/k_deflate.hip: members of at most
+ * itsx_deflate_block_bytes() bytes of text, cut from the start of the unit's output), and only compressed bytes come back; the host
+ * keeps the count pass.  A unit with a blank line between records (or of 2^31 bytes or more) is sliced on the host and deflated on the
+ * device all the same, so the file's bytes depend on the units' output text alone -- not on the arrival of text and coordinates,
+ * and they are the same on every run (they differ from the host deflate's; the records do not).  Valid only on a writer opened with
+ * compression 1, before any text or coordinates arrive: ITSX_E_ARG otherwise.  The writer BORROWS ctx: it must outlive
+ * itsx_twriter_close and serve nothing else meanwhile, except further writers (a paired run's R1 and R2 share one: their use of it is
+ * serialised).  The device buffers (a unit of text, its index and output, the deflate scratch of about 0.4 GB) are allocated here.  All
+ * device work happens on one thread of the writer's own.  A HIP error marks the writer failed, nothing more is started on the device,
+ * itsx_twriter_close returns ITSX_E_DEVICE and itsx_trim_last_error() names the step.  itsx_stats of ctx: ms_deflate = the deflate
+ * kernel's time summed over the units so far; n_tw_units_device / n_tw_units_host = units that took the device's index, plan and copy /
+ * units the host sliced.  Growth past what was reserved here (a unit of one long record, many short CCS records) allocates in mid-run and
+ * can fail with ITSX_E_DEVICE when the chunk contexts have taken the memory. */
+int itsx_twriter_set_device(itsx_twriter *w, itsx_ctx *ctx);
 int itsx_twriter_text(itsx_twriter *w, const char *text, int64_t avail, int32_t last);
 int itsx_twriter_coords(itsx_twriter *w, int64_t first_record, int64_t n, const int32_t *start, const int32_t *stop, const uint8_t *decided);
 int itsx_twriter_update(itsx_twriter *w, const int64_t *records, int64_t m, const int32_t *start, const int32_t *stop);

@@ -44,11 +44,11 @@ STATS_FIELDS = [("n_reads", "<i8"), ("n_unique", "<i8"), ("n_dropped_short", "<i
                 ("msv_cells", "<i8"), ("msv_launches", "<i8"), ("ms_fwd_kernel", "<f4"), ("ms_bwd_kernel", "<f4"),
                 ("fwd_rows", "<i8"), ("ms_env_kernel", "<f4"), ("ms_bias_kernel", "<f4"), ("env_rows", "<i8"),
                 ("n_env_unique", "<i8"), ("ms_decode_kernel", "<f4"), ("n_batches", "<i4"), ("ms_cluster", "<f4"),
-                ("pad0", "<i4"), ("cl_windows", "<i8"), ("cl_cuts", "<i8"), ("cl_alignments", "<i8"), ("ms_merge", "<f4"),
+                ("n_tw_units_device", "<i4"), ("cl_windows", "<i8"), ("cl_cuts", "<i8"), ("cl_alignments", "<i8"), ("ms_merge", "<f4"),
                 ("ms_trim_plan", "<f4"), ("cl_certified", "<i8"), ("ms_pack", "<f4"), ("ms_trim_copy", "<f4"),
                 ("n_uniq_multi_winner", "<i8"), ("n_reads_multi_winner", "<i8"), ("n_uniq_region_cap", "<i8"),
                 ("n_reads_region_cap", "<i8"), ("n_mr_clustered", "<i8"), ("n_mr_failed", "<i8"), ("n_mr_envelopes", "<i8"),
-                ("ms_ensemble", "<f4"), ("ms_deflate", "<f4"), ("n_mr_distinct", "<i8"), ("n_slab_shrinks", "<i8"), ("ms_vit_kernel", "<f4"), ("pad4", "<i4"),
+                ("ms_ensemble", "<f4"), ("ms_deflate", "<f4"), ("n_mr_distinct", "<i8"), ("n_slab_shrinks", "<i8"), ("ms_vit_kernel", "<f4"), ("n_tw_units_host", "<i4"),
                 ("n_mr_fail_kind", "<i8", (8,)), ("n_rows_resident", "<i8"),
                 ("lazy", "<i4"), ("n_bound_launches", "<i4"), ("n_lazy_pending_profiles", "<i8"), ("n_lazy_completed", "<i8"), ("n_lazy_completed_profiles", "<i8"), ("n_mr_overflow", "<i8"), ("ms_lazy_complete", "<f4"), ("lazy_bound_maxdiff", "<f4"), ("n_lazy_evaluated", "<i8"), ("n_lazy_round1", "<i8"),
                 ("n_lazy_pending", "<i8"), ("n_lazy_reruns", "<i8"), ("bound_rows", "<i8"), ("ms_bound_kernel", "<f4"),
@@ -86,7 +86,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_lazy_pending_uniques", "itsx_set_partial_coords", "itsx_set_kept_rows",
            "itsx_keep_records", "itsx_write_trimmed_samples",
            "itsx_keep_pair_records", "itsx_write_trimmed_paired_samples",
-           "itsx_deflate_block_bytes", "itsx_deflate_bound", "itsx_deflate_device", "itsx_debug_huffman_lengths"]
+           "itsx_deflate_block_bytes", "itsx_deflate_bound", "itsx_deflate_device", "itsx_debug_huffman_lengths",
+           "itsx_twriter_set_device"]
 
 
 def lib():
@@ -141,6 +142,7 @@ def lib():
         "itsx_keyset_size": (i64, [vp]),
         "itsx_keyset_assign": (i32, [vp, vp, i64, i32, vp, vp]),
         "itsx_twriter_open": (i32, [cp, i32, i32, vp]),
+        "itsx_twriter_set_device": (i32, [vp, vp]),
         "itsx_twriter_text": (i32, [vp, vp, i64, i32]),
         "itsx_twriter_coords": (i32, [vp, i64, i64, vp, vp, vp]),
         "itsx_twriter_update": (i32, [vp, vp, i64, vp, vp]),

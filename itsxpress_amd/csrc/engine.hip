@@ -28,6 +28,7 @@
 #include "engine.h"
 #include "k_api.h"
 #include "deflate_codes.h"
+#include "twriter_dev.h"
 #include "cluster_multi.h"
 #include "fastq_io.h"
 #include "iupac.h"
@@ -479,6 +480,10 @@ struct itsx_ctx {
   DBuf<TrimRec> w_trec2; DBuf<int32_t> w_ttlen;          // itsx_write_trimmed_paired_samples (beside the buffers below)
   DBuf<TrimRec> w_trec; DBuf<int64_t> w_tcnt, w_ttot, w_tblk, w_tfirst, w_tbounds; DBuf<int32_t> w_tstart, w_tstop; DBuf<uint32_t> w_tout;   // itsx_write_trimmed_samples
   DBuf<DeflateBlock> w_dblk; DBuf<uint32_t> w_dtok, w_dtext; DBuf<uint8_t> w_dslots, w_dpacked; DBuf<int32_t> w_dsizes; DBuf<int64_t> w_ddst;   // deflate_ranges
+  // a streamed writer's device path (twdev_*, for itsx_twriter_set_device): a unit's raw text, its line index and the plan's scratch
+  // (records, output text and deflate scratch are the batch writers' buffers above); tw_mu serialises the writers that share the context
+  DBuf<uint8_t> tw_raw; DBuf<int32_t> tw_ls, tw_le; DBuf<int64_t> tw_lblk, tw_qsrc, tw_info;
+  std::mutex tw_mu; bool tw_failed = false; float tw_ms_deflate = 0;
   bool two_on = false; int share_maxrd = 0; int32_t Ub = 0; size_t sh_gslots_off = 0;
   DBuf<uint8_t> sh_rdepth_s, sh_rdepth; DBuf<unsigned long long> sh_rmask_s, sh_rmask, sh_keys, sh_keys2;
   DBuf<int32_t> sh_rparent_s, sh_rparent, sh_jlev_s, sh_jown_s, sh_endrow_s, sh_rsteps_s, sh_rnn_s, sh_rnode0_s, sh_endrow, sh_jlev, sh_jsrc, sh_jownb;
@@ -5131,6 +5136,146 @@ int itsx_deflate_device(itsx_ctx *ctx, const char *text, int64_t nbytes, const i
   for (int32_t r = 0; r <= n_ranges; r++) out_bounds[r] = zb[(size_t)r];
   return ITSX_OK;
 }
+// ---- a streamed writer's device path (twriter_dev.h; the writer object itself is trim_host.cpp's)
+}  // extern "C"
+// nbytes of host memory to the device through the pinned staging buffers, in pieces: a piece is copied into its buffer while the one
+// before it is on the bus (a pageable copy of a text moves at ~5 GB/s, the staged one at ~35)
+static int put_staged(itsx_ctx *ctx, const char *src, int64_t total, uint8_t *ddst)
+{
+  if (total <= 0) return ITSX_OK;
+  { const int rc = stage_reserve(ctx, 4 << 20); if (rc != ITSX_OK) return rc; }
+  const int64_t piece = std::min<int64_t>((int64_t)ctx->stage_cap, 4 << 20);
+  constexpr int K = itsx_ctx::NSTAGE;
+  for (int64_t c = 0, o = 0; o < total; c++, o += piece) {
+    const int64_t b = std::min(piece, total - o);
+    HIPCHK(hipEventSynchronize(ctx->stage_ev[c % K]));      // what this buffer held last is on the device (an event never recorded: no wait)
+    memcpy(ctx->stage_pin[c % K], src + o, (size_t)b);
+    HIPCHK(hipMemcpyAsync(ddst + o, ctx->stage_pin[c % K], (size_t)b, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipEventRecord(ctx->stage_ev[c % K], ctx->st));
+  }
+  return ITSX_OK;
+}
+// the scratch deflate_ranges takes for a text of nbytes in one range, held before the first unit arrives
+static int deflate_reserve(itsx_ctx *ctx, int64_t nbytes)
+{
+  int ncu = 256;
+  { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, ctx->device) == hipSuccess && pr.multiProcessorCount > 0) ncu = pr.multiProcessorCount; }
+  const size_t wave = (size_t)std::min<int64_t>(DEFLATE_WAVE, nbytes / DEFLATE_BLOCK_BYTES + 1);
+  HIPCHK(ctx->w_dblk.alloc(wave)); HIPCHK(ctx->w_dsizes.alloc(wave)); HIPCHK(ctx->w_ddst.alloc(wave));
+  HIPCHK(ctx->w_dtok.alloc((size_t)std::min<size_t>(wave, (size_t)ncu) * DEFLATE_TOKEN_SLOT));
+  HIPCHK(ctx->w_dslots.alloc(wave * DEFLATE_SLOT_BYTES)); HIPCHK(ctx->w_dpacked.alloc(wave * DEFLATE_SLOT_BYTES));
+  return ITSX_OK;
+}
+static int tw_alloc_unit(itsx_ctx *ctx, int64_t nbytes, int64_t count)
+{
+  HIPCHK(ctx->tw_raw.alloc((size_t)((nbytes + 15) / 16 * 16 + 16)));
+  HIPCHK(ctx->tw_ls.alloc((size_t)(4 * count + 1))); HIPCHK(ctx->tw_le.alloc((size_t)(4 * count + 1)));
+  HIPCHK(ctx->tw_lblk.alloc((size_t)trim_index_blocks(nbytes) + 1)); HIPCHK(ctx->tw_info.alloc(TRIM_UNIT_INFO));
+  HIPCHK(ctx->w_tstart.alloc((size_t)count + 1)); HIPCHK(ctx->w_tstop.alloc((size_t)count + 1));
+  HIPCHK(ctx->w_trec.alloc((size_t)count + 1)); HIPCHK(ctx->tw_qsrc.alloc((size_t)count + 1));
+  HIPCHK(ctx->w_tblk.alloc((size_t)trim_plan_blocks(count) * 3 + 3));
+  return ITSX_OK;
+}
+// one text in w_tout -> its gzip members
+static int tw_deflate(itsx_ctx *ctx, int64_t total, std::string &comp)
+{
+  std::vector<std::pair<int64_t, int64_t>> ranges(1, std::make_pair((int64_t)0, total));
+  std::vector<char> z; std::vector<int64_t> zb;
+  const int rc = deflate_ranges(ctx, reinterpret_cast<const uint8_t *>(ctx->w_tout.p), ranges, z, zb);
+  ctx->tw_ms_deflate += ctx->stats.ms_deflate; ctx->stats.ms_deflate = ctx->tw_ms_deflate;      // (a lent context reports the sum over its writers' units)
+  if (rc != ITSX_OK) return rc;
+  comp.assign(z.data(), z.size());
+  return ITSX_OK;
+}
+static int tw_unit(itsx_ctx *ctx, const itsx::TwUnit &u, bool &fits, std::string &comp, int64_t &nw, int64_t &tot, const char *&step)
+{
+  step = "hipSetDevice";
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  const int64_t nbytes = (int64_t)u.nbytes, n = u.count;
+  step = "allocating the unit's buffers";
+  { const int rc = tw_alloc_unit(ctx, nbytes, n); if (rc != ITSX_OK) return rc; }
+  step = "uploading the unit's text and coordinates";
+  { const int rc = put_staged(ctx, u.text, nbytes, ctx->tw_raw.p); if (rc != ITSX_OK) return rc; }
+  { const int rc = put_staged(ctx, reinterpret_cast<const char *>(u.start), n * 4, reinterpret_cast<uint8_t *>(ctx->w_tstart.p)); if (rc != ITSX_OK) return rc; }
+  { const int rc = put_staged(ctx, reinterpret_cast<const char *>(u.stop), n * 4, reinterpret_cast<uint8_t *>(ctx->w_tstop.p)); if (rc != ITSX_OK) return rc; }
+  step = "the unit's line index and plan";
+  TrimUnitArgs ua{};
+  ua.text = ctx->tw_raw.p; ua.nbytes = nbytes; ua.count = n; ua.ls = ctx->tw_ls.p; ua.le = ctx->tw_le.p;
+  ua.start = ctx->w_tstart.p; ua.stop = ctx->w_tstop.p; ua.mode = u.mode; ua.ccs = u.ccs ? 1 : 0;
+  ua.lblk = ctx->tw_lblk.p; ua.blk = ctx->w_tblk.p; ua.rec = ctx->w_trec.p; ua.qsrc = ctx->tw_qsrc.p; ua.info = ctx->tw_info.p;
+  launch_trim_unit(ua, st);
+  HIPCHK(hipGetLastError());
+  int64_t info[TRIM_UNIT_INFO];
+  HIPCHK(hipMemcpyAsync(info, ctx->tw_info.p, sizeof(info), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  fits = info[0] == 4 * n && info[1] == 0;
+  if (!fits) return ITSX_OK;
+  ctx->stats.n_tw_units_device++;
+  const int64_t total = info[2];
+  nw = info[3]; tot = info[4];
+  comp.clear();
+  if (total <= 0) return ITSX_OK;
+  step = "copying the unit's records";
+  HIPCHK(ctx->w_tout.alloc((size_t)(trim_copy_bytes(total) / 4) + 16));
+  TrimCopyArgs ca{};
+  ca.rec = ctx->w_trec.p; ca.n = n; ca.seq = ca.qual = ca.titles = ctx->tw_raw.p; ca.qsrc = ctx->tw_qsrc.p;
+  ca.total = total; ca.ccs = ua.ccs; ca.out = ctx->w_tout.p;
+  launch_trim_copy(ca, st);
+  HIPCHK(hipGetLastError());
+  step = "deflating the unit's output";
+  return tw_deflate(ctx, total, comp);
+}
+static int tw_text(itsx_ctx *ctx, const char *text, size_t nbytes, std::string &comp, const char *&step)
+{
+  step = "hipSetDevice";
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->stats.n_tw_units_host++;
+  step = "uploading the unit's output";
+  HIPCHK(ctx->w_tout.alloc((size_t)(trim_copy_bytes((int64_t)nbytes) / 4) + 16));
+  { const int rc = put_staged(ctx, text, (int64_t)nbytes, reinterpret_cast<uint8_t *>(ctx->w_tout.p)); if (rc != ITSX_OK) return rc; }
+  step = "deflating the unit's output";
+  return tw_deflate(ctx, (int64_t)nbytes, comp);
+}
+namespace itsx {
+template <class F> static int tw_call(itsx_ctx *ctx, std::string &err, F &&f)
+{
+  std::lock_guard<std::mutex> lk(ctx->tw_mu);
+  if (ctx->tw_failed) { err = "device writer: an earlier step on this context failed (" + ctx->err + ")"; return ITSX_E_DEVICE; }
+  const char *step = "";
+  const int rc = f(step);
+  if (rc != ITSX_OK) {
+    if (rc == ITSX_E_DEVICE) ctx->tw_failed = true;
+    err = std::string("device writer: ") + step + ": " + ctx->err;
+  }
+  return rc;
+}
+int twdev_reserve(itsx_ctx *ctx, size_t unit_bytes, std::string &err)
+{
+  return tw_call(ctx, err, [&](const char *&step) -> int {
+    step = "allocating the device buffers";
+    HIPCHK(hipSetDevice(ctx->device));
+    // a unit ends at the first record start past its size, reads are a few hundred bytes, a record of 4 lines is at least 7 bytes
+    const int64_t nbytes = (int64_t)std::min<size_t>(unit_bytes + unit_bytes / 8 + 65536, ((size_t)1 << 31) - 1);
+    // records of 32 bytes of text or more (a read of 10 bases); the output of a unit is its text at most, plus --trim-ccs's 68 bytes per record
+    const int64_t nrec = nbytes / 32 + 1, nout = nbytes + 68 * nrec;
+    { const int rc = tw_alloc_unit(ctx, nbytes, nrec); if (rc != ITSX_OK) return rc; }
+    HIPCHK(ctx->w_tout.alloc((size_t)(trim_copy_bytes(nout) / 4) + 16));
+    { const int rc = stage_reserve(ctx, std::min<int64_t>(64ll << 20, std::max<int64_t>(nout, 4 << 20))); if (rc != ITSX_OK) return rc; }      // (what fetch_staged asks for at most)
+    return deflate_reserve(ctx, nout);
+  });
+}
+int twdev_unit(itsx_ctx *ctx, const TwUnit &u, bool &fits, std::string &comp, int64_t &nw, int64_t &tot, std::string &err)
+{
+  fits = false; nw = tot = 0;
+  return tw_call(ctx, err, [&](const char *&step) -> int { return tw_unit(ctx, u, fits, comp, nw, tot, step); });
+}
+int twdev_text(itsx_ctx *ctx, const char *text, size_t nbytes, std::string &comp, std::string &err)
+{
+  return tw_call(ctx, err, [&](const char *&step) -> int { return tw_text(ctx, text, nbytes, comp, step); });
+}
+}  // namespace itsx
+extern "C" {
 int itsx_debug_huffman_lengths(const uint32_t *freq, int32_t n, int32_t maxbits, uint8_t *lengths)
 {
   if (!freq || !lengths || n < 1 || n > itsx_dc::MAX_SYMS || maxbits < 1 || maxbits > 15 || (maxbits < 9 && n > (1 << maxbits))) return ITSX_E_ARG;

@@ -195,6 +195,7 @@ struct TrimCopyArgs {
   const uint8_t *seq, *qual, *titles;           // every plane readable 8 bytes past its end
   int64_t total, ntiles; int32_t ccs;           // bytes of the text (ntiles: set by the launcher)
   uint32_t *out;                                // trim_copy_bytes(total) bytes
+  const int64_t *qsrc = nullptr;                // [n] record r's first kept quality where it does not sit at rec[r].src of `qual` (a unit of raw text)
 };
 int64_t trim_copy_bytes(int64_t total);
 void launch_trim_copy(TrimCopyArgs a, hipStream_t st);
@@ -211,6 +212,24 @@ struct TrimPairPlanArgs {
 };
 // bounds[3][S + 1]: R1's bytes / R2's bytes / pairs written before the first pair of each sample (first[S + 1], first[S] = n)
 void launch_trim_pair_plan(const TrimPairPlanArgs &a, const int64_t *first, int32_t S, int64_t *bounds, hipStream_t st);
+// ---- a unit of raw FASTQ text (the streamed writers' device path, itsx_twriter_set_device): its line index, then its plan.
+// info[0] = lines of the unit, [1] = 1 where a record is not "@title / bases / +... / as many qualities", [2] bytes of the unit's output,
+// [3] records written, [4] their total_len.  The index is filled, and the plan made, only where info[0] == 4 x count: record r is then
+// lines 4 r .. 4 r + 3 (a blank line between records makes the count larger: that unit is sliced on the host).
+constexpr int TRIM_UNIT_INFO = 8;
+struct TrimUnitArgs {
+  const uint8_t *text; int64_t nbytes;          // readable to the next multiple of 16 past its end, nbytes < 2^31
+  int64_t count;                                // records the host counted
+  int32_t *ls, *le;                             // [4 count + 1] line k is text[ls[k], le[k]) (its newline and a '\r' before it left out)
+  const int32_t *start, *stop;                  // [count]
+  int32_t mode, ccs;                            // itsx_twriter_set_mode's mode
+  int64_t *lblk;                                // [trim_index_blocks(nbytes) + 1] scratch
+  int64_t *blk;                                 // [3 x trim_plan_blocks(count) + 3] scratch
+  TrimRec *rec; int64_t *qsrc;                  // [count + 1]: the records of k_trim_copy, all three planes = text
+  int64_t *info;                                // [TRIM_UNIT_INFO], zeroed by the launcher
+};
+int64_t trim_index_blocks(int64_t nbytes);
+void launch_trim_unit(const TrimUnitArgs &a, hipStream_t st);
 void launch_trim_orient(const uint8_t *seq, const uint8_t *qual, const int64_t *off, const int32_t *from, const int8_t *strand, const uint8_t *comp,
                         const int64_t *noff, int64_t m, uint8_t *nseq, uint8_t *nqual, hipStream_t st);
 

@@ -14,6 +14,9 @@
 //   pairs  the paired plan (itsx_keep_pair_records): Dedup.create_paired_trimmed_seqs (SeqSample.py:564-790) -- the ORIGINAL R1 / R2 records
 //          of a pair sliced with the coordinates of the merged read its R1 identifier names.  One TrimRec per pair and side, the same scan
 //          shape, and the copy kernel as it is, once per side.
+//   unit   a unit of RAW FASTQ text (the streamed writers' device path, itsx_twriter_set_device): the line index from its newline bytes
+//          (popcount per thread, two scans), trusted where the unit has 4 lines per record; the plan of itsx_twriter::work's two modes;
+//          and the copy kernel with all three planes = that text and a quality source of its own per record (k_trim_copy<true>).
 //   orient the records of the reads itsx_orient_apply keeps: reverse reads with IUPAC-complemented reversed bases and reversed qualities.
 #include <algorithm>
 #include "engine.h"
@@ -224,8 +227,8 @@ __device__ __forceinline__ uint32_t trim_load4(const uint8_t *p)
   const uint64_t both = ((uint64_t)w[1] << 32) | w[0];
   return (uint32_t)(both >> (8 * (unsigned)(reinterpret_cast<uintptr_t>(p) & 3)));
 }
-// byte p of record q's text
-__device__ __forceinline__ uint32_t trim_byte(const TrimCopyArgs &a, const TrimRec &q, int64_t p)
+// byte p of record q's text (qs: its first kept quality in a.qual)
+__device__ __forceinline__ uint32_t trim_byte(const TrimCopyArgs &a, const TrimRec &q, int64_t qs, int64_t p)
 {
   const int64_t pre = a.ccs ? 17 : 0;
   if (p < q.tl) return a.titles[q.toff + p];
@@ -242,12 +245,13 @@ __device__ __forceinline__ uint32_t trim_byte(const TrimCopyArgs &a, const TrimR
   p -= 3;
   if (p < q.slen + 2 * pre) {
     p -= pre;
-    return (p >= 0 && p < q.slen) ? a.qual[q.src + p] : '~';
+    return (p >= 0 && p < q.slen) ? a.qual[qs + p] : '~';
   }
   return '\n';
 }
 
-__global__ __launch_bounds__(TC_BLOCK) void k_trim_copy(TrimCopyArgs a)
+// QS: a record's qualities start at a.qsrc[r] (a unit of raw text, where all three planes are that text), not at rec[r].src
+template <bool QS> __global__ __launch_bounds__(TC_BLOCK) void k_trim_copy(TrimCopyArgs a)
 {
   const int64_t pre = a.ccs ? 17 : 0;
   for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
@@ -266,7 +270,7 @@ __global__ __launch_bounds__(TC_BLOCK) void k_trim_copy(TrimCopyArgs a)
         const int64_t ps = p - q.tl - 1 - pre, pq = ps - q.slen - 2 * pre - 3;
         if (p + 4 <= q.tl) src = a.titles + q.toff + p;
         else if (ps >= 0 && ps + 4 <= q.slen) src = a.seq + q.src + ps;
-        else if (pq >= 0 && pq + 4 <= q.slen) src = a.qual + q.src + pq;
+        else if (pq >= 0 && pq + 4 <= q.slen) src = a.qual + (QS ? a.qsrc[r] : q.src) + pq;
       }
       uint32_t v = 0;
       if (src) v = trim_load4(src);
@@ -275,7 +279,7 @@ __global__ __launch_bounds__(TC_BLOCK) void k_trim_copy(TrimCopyArgs a)
           const int64_t ob = o + b;
           if (ob >= a.total) break;              // the text's last dword: the bytes past its end stay 0 (the buffer is padded to whole tiles)
           while (ob >= next) { r++; q = a.rec[r]; next = a.rec[r + 1].out; }
-          v |= trim_byte(a, q, ob - q.out) << (8 * b);
+          v |= trim_byte(a, q, QS ? a.qsrc[r] : q.src, ob - q.out) << (8 * b);
         }
       }
       a.out[o >> 2] = v;
@@ -290,7 +294,148 @@ void launch_trim_copy(TrimCopyArgs a, hipStream_t st)
   if (a.total <= 0) return;
   a.ntiles = (a.total + TC_TILE - 1) / TC_TILE;
   const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, 256 * 8);
-  hipLaunchKernelGGL(k_trim_copy, dim3(grid), dim3(TC_BLOCK), 0, st, a);
+  if (a.qsrc) hipLaunchKernelGGL(k_trim_copy<true>, dim3(grid), dim3(TC_BLOCK), 0, st, a);
+  else hipLaunchKernelGGL(k_trim_copy<false>, dim3(grid), dim3(TC_BLOCK), 0, st, a);
+}
+
+// ---- a unit of raw FASTQ text (itsx_twriter_set_device) -------------------------------------------------------------------------
+// The line index: a thread looks at 16 bytes (one aligned load), the newlines among them are a 16-bit mask, its popcount goes through
+// the block's scan and the tiles' sums through one more, and the newline that is the k-th of the unit ends line k and starts line k + 1.
+// As Records::line of trim_host.cpp: a '\r' before the newline is not part of the line, a last line without a newline counts.
+constexpr int LI_BLOCK = 256;
+constexpr int64_t LI_TILE = (int64_t)LI_BLOCK * 16;
+
+__device__ __forceinline__ uint32_t trim_newlines16(const uint8_t *__restrict__ text, int64_t nbytes, int64_t p0)
+{
+  if (p0 >= nbytes) return 0;
+  const uint4 v = *reinterpret_cast<const uint4 *>(text + p0);
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  uint32_t m = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+#pragma unroll
+    for (int b = 0; b < 4; b++) if (((w[k] >> (8 * b)) & 255u) == (uint32_t)'\n') m |= 1u << (4 * k + b);
+  }
+  const int64_t left = nbytes - p0;
+  if (left < 16) m &= (1u << (int)left) - 1u;
+  return m;
+}
+
+template <bool SCATTER> __global__ __launch_bounds__(LI_BLOCK) void k_trim_index(TrimUnitArgs a)
+{
+  if (SCATTER && a.info[0] != 4 * a.count) return;             // (the same in every thread)
+  const int64_t p0 = (int64_t)blockIdx.x * LI_TILE + (int64_t)threadIdx.x * 16;
+  uint32_t m = trim_newlines16(a.text, a.nbytes, p0);
+  int64_t v[1] = {(int64_t)__popc(m)}, ex[1], tot[1];
+  block_scan64<1, LI_BLOCK>(v, ex, tot);
+  if (!SCATTER) { if (threadIdx.x == 0) a.lblk[blockIdx.x] = tot[0]; return; }
+  const int64_t cap = 4 * a.count;
+  int64_t k = a.lblk[blockIdx.x] + ex[0];
+  while (m) {
+    const int64_t p = p0 + (__ffs((int)m) - 1);
+    m &= m - 1;
+    if (k < cap) { a.le[k] = (int32_t)(p - ((p > 0 && a.text[p - 1] == '\r') ? 1 : 0)); a.ls[k + 1] = (int32_t)(p + 1); }
+    k++;
+  }
+}
+// the tiles' newline counts -> their exclusive prefixes, in place; info[0] = the unit's lines; the first line's start and, where the
+// text does not end in a newline, the last line's end
+__global__ __launch_bounds__(LI_BLOCK) void k_trim_index_sums(TrimUnitArgs a, int64_t nb)
+{
+  int64_t carry = 0;
+  for (int64_t b0 = 0; b0 < nb; b0 += LI_BLOCK) {
+    const int64_t b = b0 + threadIdx.x;
+    int64_t v[1] = {b < nb ? a.lblk[b] : 0}, ex[1], tot[1];
+    block_scan64<1, LI_BLOCK>(v, ex, tot);
+    if (b < nb) a.lblk[b] = carry + ex[0];
+    carry += tot[0];
+  }
+  if (threadIdx.x == 0) {
+    const bool open = a.nbytes > 0 && a.text[a.nbytes - 1] != '\n';
+    const int64_t lines = carry + (open ? 1 : 0);
+    a.info[0] = lines;
+    if (lines == 4 * a.count && a.count > 0) {
+      a.ls[0] = 0;
+      if (open) a.le[carry] = (int32_t)(a.nbytes - (a.text[a.nbytes - 1] == '\r' ? 1 : 0));
+    }
+  }
+}
+
+// record r of the unit = lines 4 r .. 4 r + 3: whether it is written and its slice, as itsx_twriter::work decides both (mode 0: written
+// iff start >= 0 && stop >= 0 && start < stop; mode 1: iff stop != INT32_MIN, INT32_MAX an open end), and whether it is a record at all
+struct TrimUnitOne { int32_t t0, s0, q0, tl, lo, sl; bool w, bad; };
+__device__ __forceinline__ TrimUnitOne trim_unit_one(const TrimUnitArgs &a, int64_t r)
+{
+  TrimUnitOne u;
+  const int32_t p0 = a.ls[4 * r + 2];
+  u.t0 = a.ls[4 * r]; u.s0 = a.ls[4 * r + 1]; u.q0 = a.ls[4 * r + 3];
+  u.tl = a.le[4 * r] - u.t0;
+  const int32_t L = a.le[4 * r + 1] - u.s0, pl = a.le[4 * r + 2] - p0, ql = a.le[4 * r + 3] - u.q0;
+  u.bad = u.tl <= 0 || a.text[u.t0] != '@' || pl <= 0 || a.text[p0] != '+' || ql != L;
+  const int64_t s = a.start[r], e = a.stop[r];
+  if (a.mode == 1) { u.w = e != (int64_t)INT32_MIN; trim_py_slice(L, s, e, e == (int64_t)INT32_MAX, u.lo, u.sl); }
+  else { u.w = s >= 0 && e >= 0 && s < e; trim_py_slice(L, s, e, false, u.lo, u.sl); }
+  if (u.bad) { u.w = false; u.lo = u.sl = 0; }
+  return u;
+}
+
+template <bool SCATTER> __global__ __launch_bounds__(TR_BLOCK) void k_trim_unit_plan(TrimUnitArgs a)
+{
+  if (a.info[0] != 4 * a.count) return;                        // (the same in every thread)
+  const int64_t base = (int64_t)blockIdx.x * TR_TILE + (int64_t)threadIdx.x * TR_ITEMS;
+  const int64_t extra = a.ccs ? 34 : 0;
+  TrimUnitOne u[TR_ITEMS];
+  int64_t v[3] = {0, 0, 0};                      // bytes of text, records, total_len as itsx_twriter::work counts it
+#pragma unroll
+  for (int i = 0; i < TR_ITEMS; i++) {
+    const int64_t r = base + i;
+    u[i].w = false; u[i].bad = false;
+    if (r < a.count) u[i] = trim_unit_one(a, r);
+    if (u[i].w) { v[0] += (int64_t)u[i].tl + 5 + 2 * ((int64_t)u[i].sl + extra); v[1]++; v[2] += (int64_t)u[i].sl + extra; }
+    if (!SCATTER && u[i].bad) a.info[1] = 1;
+  }
+  int64_t ex[3], tot[3];
+  block_scan64<3, TR_BLOCK>(v, ex, tot);
+  if (!SCATTER) {
+    if (threadIdx.x == 0) { a.blk[blockIdx.x * 3 + 0] = tot[0]; a.blk[blockIdx.x * 3 + 1] = tot[1]; a.blk[blockIdx.x * 3 + 2] = tot[2]; }
+    return;
+  }
+  int64_t o = a.blk[blockIdx.x * 3 + 0] + ex[0];
+#pragma unroll
+  for (int i = 0; i < TR_ITEMS; i++) {
+    const int64_t r = base + i;
+    if (r >= a.count) break;
+    TrimRec q;
+    q.out = o; q.src = (int64_t)u[i].s0 + u[i].lo; q.toff = u[i].t0; q.tl = u[i].tl; q.slen = u[i].sl;
+    a.rec[r] = q; a.qsrc[r] = (int64_t)u[i].q0 + u[i].lo;
+    if (u[i].w) o += (int64_t)u[i].tl + 5 + 2 * ((int64_t)u[i].sl + extra);
+  }
+}
+__global__ __launch_bounds__(TR_BLOCK) void k_trim_unit_plan_sums(TrimUnitArgs a, int64_t nb)
+{
+  if (a.info[0] != 4 * a.count) return;
+  int64_t carry[3];
+  trim_scan_tiles(a.blk, nb, carry);
+  if (threadIdx.x == 0) {
+    TrimRec q;
+    q.out = carry[0]; q.src = 0; q.toff = 0; q.tl = 0; q.slen = 0;
+    a.rec[a.count] = q; a.qsrc[a.count] = 0;
+    a.info[2] = carry[0]; a.info[3] = carry[1]; a.info[4] = carry[2];
+  }
+}
+
+int64_t trim_index_blocks(int64_t nbytes) { return (nbytes + LI_TILE - 1) / LI_TILE; }
+
+void launch_trim_unit(const TrimUnitArgs &a, hipStream_t st)
+{
+  (void)hipMemsetAsync(a.info, 0, sizeof(int64_t) * TRIM_UNIT_INFO, st);
+  const int64_t nbi = trim_index_blocks(a.nbytes), nbp = trim_plan_blocks(a.count);
+  if (nbi > 0) hipLaunchKernelGGL(k_trim_index<false>, dim3((unsigned)nbi), dim3(LI_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(k_trim_index_sums, dim3(1), dim3(LI_BLOCK), 0, st, a, nbi);
+  if (nbi > 0) hipLaunchKernelGGL(k_trim_index<true>, dim3((unsigned)nbi), dim3(LI_BLOCK), 0, st, a);
+  if (nbp > 0) hipLaunchKernelGGL(k_trim_unit_plan<false>, dim3((unsigned)nbp), dim3(TR_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(k_trim_unit_plan_sums, dim3(1), dim3(TR_BLOCK), 0, st, a, nbp);
+  if (nbp > 0) hipLaunchKernelGGL(k_trim_unit_plan<true>, dim3((unsigned)nbp), dim3(TR_BLOCK), 0, st, a);
 }
 
 // ---- itsx_orient_apply with records: kept read j = read from[j] of the old planes, reversed (bases complemented) where its strand is -1;

@@ -16,13 +16,14 @@ static const Switch g_sw[] = {
   {"ITSX_COMPACT_ZMAX", SW_HOOK, "largest domZ the compact / lazy modes call a row 'certain' for (default 1e9); a value below the data's domZ can drop a winner"},
   {"ITSX_COMPACT_DOME_MIN", SW_HOOK, "smallest --domE the compact / lazy modes call a row 'certain' for (default 1e-2)"},
   {"ITSX_PASSA_DBG", SW_HOOK, "pass A diagnostic bits (no rows / no restore / no join): timings only, scores are garbage"},
+  {"ITSX_TWRITER_HOST_SLICE", SW_HOOK, "=1: a streamed writer with a device (itsx_twriter_set_device) slices every unit on the host, as it does a unit its line index does not fit (same file bytes)"},
   // ---- MODEs
   {"ITSX_ROWS", SW_MODE, "rows mode when the caller did not call itsx_set_rows_mode: full | compact | lazy (coordinates identical in all three)"},
   {"ITSX_COMPACT_ROWS", SW_MODE, "=1: rows mode compact (older spelling of ITSX_ROWS=compact)"},
   {"ITSX_QMASK", SW_MODE, "=none: vsearch's --qmask none for cluster_size / orient seeds (default dust, as vsearch)"},
   {"ITSX_KEEP_TRACE", SW_MODE, "keeps per-pair filter traces for itsx_get_pairtraces (forces the compact path of a lazy search)"},
   {"ITSX_GZIP_LEVEL", SW_MODE, "deflate level of the trimmed-FASTQ writers (default 6; output bytes differ, records do not)"},
-  {"ITSX_DEVICE_DEFLATE", SW_MODE, "=1: the batch writers deflate gzip output on the device (output bytes differ, records do not)"},
+  {"ITSX_DEVICE_DEFLATE", SW_MODE, "=1: the batch writers deflate gzip output on the device, and so do the outputs a StreamEngine plans (output bytes differ, records do not)"},
   // ---- DIAGnostics
   {"ITSX_TEST_HOOKS", SW_DIAG, "=1: honour the HOOK switches above"},
   {"ITSX_SHARE_CHECK", SW_DIAG, "runs the unshared kernels beside the shared ones and counts differences (itsx_stats.share_mismatch, join_maxdiff)"},

@@ -29,6 +29,7 @@
 #include "../../include/itsx_hip.h"
 #include "fastq_io.h"
 #include "iupac.h"
+#include "twriter_dev.h"
 
 namespace {
 
@@ -243,6 +244,11 @@ struct itsx_twriter {
   std::condition_variable cv_work, cv_idle;
   std::deque<std::pair<int, size_t>> jobs;  // (0 count | 1 slice, unit)
   int busy = 0; bool quit = false;
+  // the device path (itsx_twriter_set_device): the units that are ready go to ONE thread of the writer's own, which has the borrowed
+  // context index, plan, copy and deflate them (twriter_dev.h); the pool keeps the count pass
+  itsx_ctx *dev = nullptr; bool dev_host_slice = false, dev_failed = false;
+  std::deque<size_t> djobs;
+  std::thread dev_thread;
 
   // ---- all of these with `mu` held
   void cut_units()
@@ -283,11 +289,13 @@ struct itsx_twriter {
       if (u.state != 0) continue;
       if (u.first + u.count > (int64_t)start.size()) break;      // its coordinates have not arrived
       if (u.undecided < 0) { int64_t c = 0; for (int64_t i = u.first; i < u.first + u.count; i++) c += decided[(size_t)i] == 0; u.undecided = c; }
-      if (u.undecided == 0) { u.state = 1; jobs.emplace_back(1, k); }
+      if (u.undecided == 0) { u.state = 1; if (dev) djobs.push_back(k); else jobs.emplace_back(1, k); }
     }
     cv_work.notify_all();
   }
   void work();
+  void work_device();
+  int slice(size_t lo, size_t hi, int64_t first, std::string &out, int64_t &n_out, int64_t &t_out) const;
   // writes every finished unit that is next in order (called without the lock)
   void flush_ready()
   {
@@ -340,6 +348,90 @@ struct itsx_twriter {
   }
 };
 
+// the records of text [lo, hi) (the first is record `first`) sliced into `out`; 0, or -1 at a malformed record
+int itsx_twriter::slice(size_t lo, size_t hi, int64_t first, std::string &out, int64_t &n_out, int64_t &t_out) const
+{
+  Records r; r.s = base + lo; r.end = base + hi;
+  Rec rec; int rc;
+  out.clear();
+  out.reserve((hi - lo) / 2 + 4096);
+  static const char *fwd = "GACAGGTACAAGAAGGA", *rev = "TTAACCCAGTCTCCAGT";
+  int64_t i = first;
+  n_out = t_out = 0;
+  while ((rc = r.next(rec)) == 1) {
+    const int64_t a = start[(size_t)i], b = stop[(size_t)i];      // (rows of decided records are not written to any more)
+    i++;
+    int64_t l, h;
+    if (mode == 1) {
+      if (b == INT32_MIN) continue;
+      py_slice((int64_t)rec.seq.size(), a, b, b == INT32_MAX, l, h);
+    } else {
+      if (a < 0 || b < 0 || !(a < b)) continue;
+      py_slice((int64_t)rec.seq.size(), a, b, false, l, h);
+    }
+    out.append(rec.title.p, rec.title.n); out += '\n';
+    if (ccs) out += fwd;
+    out.append(rec.seq.p + l, (size_t)(h - l));
+    if (ccs) out += rev;
+    out += "\n+\n";
+    if (ccs) out.append(17, '~');
+    out.append(rec.qual.p + l, (size_t)(h - l));
+    if (ccs) out.append(17, '~');
+    out += '\n';
+    n_out++; t_out += (h - l) + (ccs ? 34 : 0);
+  }
+  return rc;
+}
+
+// the device writer's own thread: a ready unit goes through the context (index, plan, copy, deflate); a unit the line index does not
+// fit (a blank line between records), one of 2^31 bytes or more and every unit under ITSX_TWRITER_HOST_SLICE is sliced here as the pool
+// slices it and its text deflated on the device all the same -- the file's bytes are a function of the units' output text alone.
+// After a HIP error nothing more is started on the device: the units left are marked done and close reports the error.
+void itsx_twriter::work_device()
+{
+  std::string out, comp, e;
+  std::vector<int32_t> a, b;
+  for (;;) {
+    size_t k, lo, hi; int64_t first, count; bool skip, host;
+    {
+      std::unique_lock<std::mutex> lk(mu);
+      cv_work.wait(lk, [&] { return quit || !djobs.empty(); });
+      if (djobs.empty()) return;
+      k = djobs.front(); djobs.pop_front();
+      busy++;
+      lo = units[k].lo; hi = units[k].hi; first = units[k].first; count = units[k].count;
+      skip = dev_failed; host = dev_host_slice || malformed || hi - lo >= ((size_t)1 << 31);
+    }
+    int64_t n_out = 0, t_out = 0;
+    int rc = ITSX_OK; bool bad = false;
+    comp.clear();
+    if (!skip && count > 0) {
+      bool fits = false;
+      if (!host) {
+        a.resize((size_t)count); b.resize((size_t)count);
+        for (int64_t i = 0; i < count; i++) { a[(size_t)i] = start[(size_t)(first + i)]; b[(size_t)i] = stop[(size_t)(first + i)]; }
+        itsx::TwUnit u{base + lo, hi - lo, a.data(), b.data(), count, mode, ccs ? 1 : 0};
+        rc = itsx::twdev_unit(dev, u, fits, comp, n_out, t_out, e);
+      }
+      if (rc == ITSX_OK && !fits) {
+        bad = slice(lo, hi, first, out, n_out, t_out) < 0;
+        if (!bad && !out.empty()) rc = itsx::twdev_text(dev, out.data(), out.size(), comp, e);
+      }
+    }
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      Unit &u = units[k];
+      if (bad) malformed = true;
+      if (rc != ITSX_OK && !dev_failed) { dev_failed = true; err = e; }
+      if (bad || rc != ITSX_OK || skip) { comp.clear(); n_out = t_out = 0; }
+      u.comp.swap(comp); u.nw = n_out; u.tot = t_out; u.state = 2;
+    }
+    flush_ready();
+    { std::lock_guard<std::mutex> lk(mu); busy--; }
+    cv_idle.notify_all();
+  }
+}
+
 void itsx_twriter::work()
 {
   itsx_io::PieceCompressor pc(kind);
@@ -368,32 +460,8 @@ void itsx_twriter::work()
       cv_idle.notify_all();
       continue;
     }
-    out.clear();
-    out.reserve((hi - lo) / 2 + 4096);
-    static const char *fwd = "GACAGGTACAAGAAGGA", *rev = "TTAACCCAGTCTCCAGT";
-    int64_t i = first, n_out = 0, t_out = 0;
-    while ((rc = r.next(rec)) == 1) {
-      const int64_t a = start[(size_t)i], b = stop[(size_t)i];      // (rows of decided records are not written to any more)
-      i++;
-      int64_t l, h;
-      if (mode == 1) {
-        if (b == INT32_MIN) continue;
-        py_slice((int64_t)rec.seq.size(), a, b, b == INT32_MAX, l, h);
-      } else {
-        if (a < 0 || b < 0 || !(a < b)) continue;
-        py_slice((int64_t)rec.seq.size(), a, b, false, l, h);
-      }
-      out.append(rec.title.p, rec.title.n); out += '\n';
-      if (ccs) out += fwd;
-      out.append(rec.seq.p + l, (size_t)(h - l));
-      if (ccs) out += rev;
-      out += "\n+\n";
-      if (ccs) out.append(17, '~');
-      out.append(rec.qual.p + l, (size_t)(h - l));
-      if (ccs) out.append(17, '~');
-      out += '\n';
-      n_out++; t_out += (h - l) + (ccs ? 34 : 0);
-    }
+    int64_t n_out = 0, t_out = 0;
+    rc = slice(lo, hi, first, out, n_out, t_out);
     std::string comp;
     bool ok = rc == 0;
     if (ok && !out.empty()) ok = pc.run(out, comp);
@@ -435,6 +503,23 @@ int itsx_twriter_set_mode(itsx_twriter *w, int32_t mode)
   if (!w || mode < 0 || mode > 1) { g_trim_error = "itsx_twriter_set_mode: mode must be 0 or 1"; return ITSX_E_ARG; }
   std::lock_guard<std::mutex> lk(w->mu);
   w->mode = mode;
+  return ITSX_OK;
+}
+// The writer's gzip members made on the device: a unit that is ready goes to the borrowed context (twriter_dev.h) instead of the pool.
+// Valid on a gzip writer that has seen neither text nor coordinates; the context must outlive itsx_twriter_close.
+int itsx_twriter_set_device(itsx_twriter *w, itsx_ctx *ctx)
+{
+  if (!w || !ctx) { g_trim_error = "itsx_twriter_set_device: null writer or context"; return ITSX_E_ARG; }
+  std::lock_guard<std::mutex> lk(w->mu);
+  if (w->kind != 1) { g_trim_error = "itsx_twriter_set_device: the device makes gzip members: the writer must have been opened with compression 1"; return ITSX_E_ARG; }
+  if (w->dev) { g_trim_error = "itsx_twriter_set_device: the writer has a device already"; return ITSX_E_ARG; }
+  if (w->base || w->avail > 0 || w->text_done || w->start.size() > 0) { g_trim_error = "itsx_twriter_set_device: call it before any text or coordinates arrive"; return ITSX_E_ARG; }
+  std::string e;
+  const int rc = itsx::twdev_reserve(ctx, w->unit_bytes, e);
+  if (rc != ITSX_OK) { g_trim_error = e; return rc; }
+  w->dev = ctx;
+  { const char *h = sw_get("ITSX_TWRITER_HOST_SLICE"); w->dev_host_slice = h && atoi(h) == 1; }
+  w->dev_thread = std::thread([w] { w->work_device(); });
   return ITSX_OK;
 }
 int itsx_twriter_text(itsx_twriter *w, const char *base, int64_t avail, int32_t last)
@@ -487,8 +572,9 @@ int itsx_twriter_close(itsx_twriter *w, int64_t *n_written, int64_t *total_len)
     if (!w->text_done) { g_trim_error = "itsx_twriter_close: the text is not complete"; rc = ITSX_E_ARG; }
     else {
       // everything that can run does; then every unit must be done
-      w->cv_idle.wait(lk, [&] { return w->jobs.empty() && w->busy == 0; });
+      w->cv_idle.wait(lk, [&] { return w->jobs.empty() && w->djobs.empty() && w->busy == 0; });
       if (w->malformed) { g_trim_error = "malformed FASTQ record"; rc = ITSX_E_FORMAT; }
+      else if (w->dev_failed) { g_trim_error = w->err; rc = ITSX_E_DEVICE; }
       else if (w->records_cut > (int64_t)w->start.size() || w->counted_prefix < w->units.size()) { g_trim_error = "more records in the file than coordinates"; rc = ITSX_E_ARG; }
       else if (w->next_write < w->units.size()) { g_trim_error = "itsx_twriter_close: records whose coordinates were never decided"; rc = ITSX_E_ARG; }
     }
@@ -496,6 +582,7 @@ int itsx_twriter_close(itsx_twriter *w, int64_t *n_written, int64_t *total_len)
   }
   w->cv_work.notify_all();
   for (auto &t : w->workers) t.join();
+  if (w->dev_thread.joinable()) w->dev_thread.join();
   if (rc == ITSX_OK && !w->wrote_any && w->kind != 0) {          // an empty file is still one valid member / frame
     itsx_io::PieceCompressor pc(w->kind);
     std::string c;

@@ -105,9 +105,19 @@ class _Output:
     def __init__(self, L, plan):
         self.L, self.plan = L, plan
         self.w = C.c_void_p()
+        self.dev_eng = None
+        self.ms_deflate = 0.0          # deflate = "device": the deflate kernel's time over the whole output
+        self.units_device = self.units_host = 0      # ... and the units the device indexed and sliced / the units the host sliced
         rc = L.itsx_twriter_open(os.fsencode(plan["out"]), plan["kind"], 1 if plan["ccs"] else 0, C.byref(self.w))
         if rc != 0:
             raise EngineError(rc, L.itsx_trim_last_error().decode())
+        try:
+            self._lend_device([self.w])
+        except BaseException:
+            L.itsx_twriter_close(self.w, None, None)
+            self.w = None
+            self._return_device()
+            raise
         self.g_start = np.full(1 << 20, -1, np.int32)
         self.g_stop = np.full(1 << 20, -1, np.int32)
         self.g_dec = np.ones(1 << 20, np.uint8)
@@ -120,6 +130,25 @@ class _Output:
     def _chk(self, rc):
         if rc != 0:
             raise EngineError(rc, self.L.itsx_trim_last_error().decode())
+
+    def _lend_device(self, writers):
+        """deflate = "device": one small Engine of the writers' own, lent to each of them (itsx_twriter_set_device) before the first
+        chunk's context sizes itself by the memory that is free; it is closed after the writers"""
+        if self.plan.get("deflate") != "device":
+            return
+        self.dev_eng = Engine(self.plan["device"])
+        for w in writers:
+            self._chk(self.L.itsx_twriter_set_device(w, self.dev_eng.h))
+
+    def _return_device(self):
+        eng, self.dev_eng = self.dev_eng, None
+        if eng is not None:
+            try:
+                st = eng.stats()
+                self.ms_deflate = float(st["ms_deflate"])
+                self.units_device, self.units_host = int(st["n_tw_units_device"]), int(st["n_tw_units_host"])
+            finally:
+                eng.close()
 
     def _grow(self, n):
         if n > self.g_start.shape[0]:
@@ -195,7 +224,10 @@ class _Output:
         if self.result is None:
             n, tot = C.c_int64(0), C.c_int64(0)
             w, self.w = self.w, None
-            self._chk(self.L.itsx_twriter_close(w, C.byref(n), C.byref(tot)))
+            try:
+                self._chk(self.L.itsx_twriter_close(w, C.byref(n), C.byref(tot)))
+            finally:
+                self._return_device()
             self.result = (n.value, tot.value)
         return self.result
 
@@ -203,6 +235,7 @@ class _Output:
         if self.w:
             w, self.w = self.w, None
             self.L.itsx_twriter_close(w, None, None)
+            self._return_device()
             try:
                 os.remove(self.plan["out"])
             except OSError:
@@ -221,6 +254,9 @@ class _OutputPaired(_Output):
     def __init__(self, L, plan):
         self.L, self.plan = L, plan
         self.w = self.w2 = None
+        self.dev_eng = None
+        self.ms_deflate = 0.0
+        self.units_device = self.units_host = 0
         ws = []
         try:
             for path in (plan["out"], plan["out2"]):
@@ -230,9 +266,11 @@ class _OutputPaired(_Output):
                     raise EngineError(rc, L.itsx_trim_last_error().decode())
                 ws.append(w)
                 self._chk(L.itsx_twriter_set_mode(w, 1))
+            self._lend_device(ws)
         except BaseException:
             for w in ws:
                 L.itsx_twriter_close(w, None, None)
+            self._return_device()
             raise
         self.w, self.w2 = ws
         self.g_start = np.full(1 << 20, -1, np.int32)
@@ -338,12 +376,18 @@ class _OutputPaired(_Output):
     def finish(self):
         if self.result is None:
             res = []
-            for name in ("w", "w2"):
-                n, tot = C.c_int64(0), C.c_int64(0)
-                w = getattr(self, name)
-                setattr(self, name, None)
-                self._chk(self.L.itsx_twriter_close(w, C.byref(n), C.byref(tot)))
-                res.append((n.value, tot.value))
+            try:
+                for name in ("w", "w2"):
+                    n, tot = C.c_int64(0), C.c_int64(0)
+                    w = getattr(self, name)
+                    setattr(self, name, None)
+                    self._chk(self.L.itsx_twriter_close(w, C.byref(n), C.byref(tot)))
+                    res.append((n.value, tot.value))
+            finally:
+                if self.w2:                                  # R1's close failed: R2's writer goes before the context it borrows
+                    w, self.w2 = self.w2, None
+                    self.L.itsx_twriter_close(w, None, None)
+                self._return_device()
             self.result = (res[0][0], res[0][1] + res[1][1])
         return self.result
 
@@ -357,6 +401,7 @@ class _OutputPaired(_Output):
                     os.remove(self.plan[key])
                 except OSError:
                     pass
+        self._return_device()
 
 
 class StreamEngine(ShardedOps):
@@ -393,6 +438,32 @@ class StreamEngine(ShardedOps):
         self._stream2 = None
         self._last_merge = None
         self.n_pairs = 0
+
+    # Where the planned outputs' gzip bytes are made (plan_output, plan_output_paired with gzipped=True): "host" (the default: the
+    # writer's pool deflates, byte for byte what it always wrote) or "device" (one small Engine of the writers' own indexes, slices and
+    # deflates every unit, csrc/k_trim.hip and csrc/k_deflate.hip: the same records in other bytes, at a fast level's ratio).  Nothing
+    # set: ITSX_DEVICE_DEFLATE=1 in the environment selects "device".  "device" with zstd or plain output is a ValueError at plan time.
+    @property
+    def deflate(self):
+        d = getattr(self, "_deflate", None)
+        if d is None:
+            d = "device" if os.environ.get("ITSX_DEVICE_DEFLATE", "").strip() == "1" else "host"
+        return d
+
+    @deflate.setter
+    def deflate(self, where):
+        if where not in ("host", "device"):
+            raise ValueError('StreamEngine.deflate is "host" or "device", not %r' % (where,))
+        self._deflate = where
+
+    def _plan_deflate(self, gzipped, zstd_file, who):
+        if self.deflate != "device":
+            return "host"
+        if getattr(self, "_deflate", None) is None and not (gzipped and not zstd_file):
+            return "host"                                 # (the environment's switch is about gzip output: other outputs stay as they are)
+        if zstd_file or not gzipped:
+            raise ValueError('%s: deflate = "device" makes gzip output: it goes with gzipped=True and without zstd_file' % who)
+        return "device"
 
     # -- plumbing: the handlers of multi.py's workers, called in process
     @property
@@ -442,13 +513,15 @@ class StreamEngine(ShardedOps):
         them): the writer then works on the chunks that are done while the GPU scores the next ones.  finalize(domE) must use the
         same domE; finish_output() returns (records written, summed length) once finalize() has run."""
         self._plan = {"out": outfile, "left": left, "right": right, "kind": 1 if gzipped else (2 if zstd_file else 0),
-                      "ccs": bool(trim_ccs), "domE": float(domE)}
+                      "ccs": bool(trim_ccs), "domE": float(domE),
+                      "deflate": self._plan_deflate(gzipped, zstd_file, "plan_output"), "device": self.device}
 
     def plan_output_paired(self, outfile1, outfile2, left, right, gzipped=False, zstd_file=False, domE=10.0):
         """A paired sample (merge_pairs_load): say BEFORE search() where the two mates' trimmed files go; they are then written while the
         chunks are scored (class _OutputPaired)."""
         self._plan = {"out": outfile1, "out2": outfile2, "left": left, "right": right, "kind": 1 if gzipped else (2 if zstd_file else 0),
-                      "ccs": False, "domE": float(domE)}
+                      "ccs": False, "domE": float(domE),
+                      "deflate": self._plan_deflate(gzipped, zstd_file, "plan_output_paired"), "device": self.device}
 
     def output_planned_paired(self, outfile1, outfile2, left, right, gzipped=False, zstd_file=False):
         p = self._plan

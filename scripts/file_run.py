@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--stream", action="store_true", help="file-order chunks scored while the file is inflated (itsxpress_amd/stream.py)")
     ap.add_argument("--chunk-mb", type=float, default=0.0, help="--stream: text per chunk (0: about a tenth of the file)")
     ap.add_argument("--stream-write", action="store_true", help="--stream: the writer inside the pipeline too (provisional thresholds per chunk)")
+    ap.add_argument("--deflate", default="host", choices=["host", "device"], help="--stream --stream-write with gz output: where the writer's gzip members are made (StreamEngine.deflate)")
     ap.add_argument("--check", action="store_true", help="--stream: compare the coordinates with one context on the whole file")
     ap.add_argument("--input-dir", default="", help="keep the generated in.fastq.gz here and use it again when it is there (several arms over one file)")
     args = ap.parse_args()
@@ -86,6 +87,7 @@ def main():
             se.set_rows_mode(args.rows)
             out = os.path.join(tmp, "trimmed.fastq" + {"gz": ".gz", "zst": ".zst", "plain": ""}[args.out_kind])
             if args.stream_write:
+                se.deflate = args.deflate
                 se.plan_output(out, "3_", "4_", gzipped=args.out_kind == "gz", zstd_file=args.out_kind == "zst")
             se.load_reads_file(fq)
             se.derep()
@@ -107,7 +109,10 @@ def main():
                 sw = se.finish_output()
                 t["write (the part left after the pipeline)"] = time.perf_counter() - t0
                 extra_w = {"late_uniques": se._out.n_late_uniques}
-            extra = {"stream_chunks": se.world, "stream_timeline_s(chunk, text ready, loaded, searched)": se.timeline,
+                extra["deflate"] = se._out.plan["deflate"]
+                extra["ms_deflate"] = round(se._out.ms_deflate, 1)          # (device: the deflate kernel's time over all units)
+                extra["units_device"], extra["units_host_sliced"] = se._out.units_device, se._out.units_host      # (which path was timed)
+            extra = {**extra, "stream_chunks": se.world, "stream_timeline_s(chunk, text ready, loaded, searched)": se.timeline,
                      "chunk_load_s": [st.get("load_s") for _, st in se._engs], "finalize_s": getattr(se, "finalize_s", None)}
             if args.check:                              # the same file through one context: identical coordinates
                 e1 = Engine(0)
@@ -135,8 +140,12 @@ def main():
             if args.check:                              # the one-go writer on the same coordinates: the same bytes
                 ref_out = out + ".ref"
                 assert write_trimmed_fastq(fq, ref_out, start, stop, gzipped=args.out_kind == "gz", zstd_file=args.out_kind == "zst") == (nw, tot)
-                extra["output_bytes_equal_one_go_writer"] = open(ref_out, "rb").read() == open(out, "rb").read()
-                assert extra["output_bytes_equal_one_go_writer"]
+                if args.deflate == "device":                # (other bytes, the same records)
+                    extra["output_text_equal_one_go_writer"] = read_text(ref_out) == read_text(out)
+                    assert extra["output_text_equal_one_go_writer"]
+                else:
+                    extra["output_bytes_equal_one_go_writer"] = open(ref_out, "rb").read() == open(out, "rb").read()
+                    assert extra["output_bytes_equal_one_go_writer"]
         else:
             t0 = time.perf_counter()
             nw, tot = write_trimmed_fastq(fq, out, start, stop, gzipped=args.out_kind == "gz", zstd_file=args.out_kind == "zst")
@@ -154,9 +163,14 @@ def main():
             i = int(kept[k])
             assert lines[4 * k] == b"@read%d 1:N:0:1" % i
             assert lines[4 * k + 1] == bases[offs[i]:offs[i + 1]].tobytes()[start[i]:stop[i]]
+        # the output's text: per written record its title line, "\n", bases, "\n+\n", qualities, "\n" = title + 5 + 2 x (bases kept), summed
+        # (the titles are the b"@read%d 1:N:0:1" written above: the fixed part plus the digits of the read's number)
+        digits = np.searchsorted(10 ** np.arange(1, 12), kept, side="right") + 1
+        text_bytes = int(digits.sum()) + (len(b"@read 1:N:0:1") + 5) * int(nw) + 2 * int(tot)
         print(json.dumps({
             "reads": n, "shape": args.shape, "rows": args.rows, "unique": int(nu), "written": int(nw), "out_kind": args.out_kind,
             "input_MB": round(in_bytes / 1e6, 1), "input_gz_MB": round(in_gz / 1e6, 1), "output_MB": round(os.path.getsize(out) / 1e6, 1),
+            "output_text_MB": round(text_bytes / 1e6, 1),
             "stages_s": {k: round(v, 3) for k, v in t.items()}, "s_total": round(total, 3), **extra,
             "reads_per_s_file_to_file": round(n / total), "io_threads": int(os.environ.get("ITSX_IO_THREADS", 0)) or min(os.cpu_count(), 32),
             "codecs": _lib.lib().itsx_io_codecs()}))

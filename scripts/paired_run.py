@@ -26,12 +26,17 @@ def main():
     ap.add_argument("--array-path", action="store_true", help="skip uc.txt / rep.fa / domtbl.txt (the in-memory hand-off, f3)")
     ap.add_argument("--stream", action="store_true", help="round 6: after the staged run, the same files through the STREAMED paired pipeline "
                                                           "(ITSXPRESS_STREAM=1 ITSXPRESS_ARRAYS=1, SeqSample.plan_output_paired) and its wall time")
+    ap.add_argument("--deflate", default="host", help="--stream: where the streamed writers' gzip members are made, host | device (StreamEngine.deflate); "
+                                                      "a comma-separated list runs the streamed leg once per entry over the same files (arms of a comparison)")
     ap.add_argument("--check", action="store_true", help="--stream: the two outputs (inflated) must equal the staged run's byte for byte")
     args = ap.parse_args()
-    print(json.dumps(run(args.pairs, args.array_path, args.stream, args.check)))
+    arms = args.deflate.split(",")
+    if any(a not in ("host", "device") for a in arms):
+        ap.error("--deflate takes host, device or a comma-separated list of them")
+    print(json.dumps(run(args.pairs, args.array_path, args.stream, args.check, arms)))
 
 
-def stream_leg(paths, hmm, tmp):
+def stream_leg(paths, hmm, tmp, deflate="host"):
     """the reference's call sequence (main.py:513-519, 534-554, 556-624) through the mirror with the streaming engine: R1 / R2 inflated side
     by side, merged chunk by chunk on the device, scored, the two outputs deflated while later chunks are scored"""
     import importlib
@@ -45,6 +50,7 @@ def stream_leg(paths, hmm, tmp):
     try:
         t0 = time.perf_counter()
         sobj = S.SeqSamplePairedNotInterleaved(fastq=paths[0], tempdir=os.path.join(tmp, "swork"), fastq2=paths[1])
+        sobj.engine.deflate = deflate
         sobj.plan_output_paired(o1, o2, "ITS2", gzipped=True)
         sobj._merge_reads(threads=1, stagger=False)
         sobj.deduplicate(threads=1)
@@ -55,7 +61,10 @@ def stream_leg(paths, hmm, tmp):
         dd.create_paired_trimmed_seqs(o1, o2, gzipped=True, zstd_file=False, itspos=its_pos, wri_file=True)
         total = time.perf_counter() - t0
         eng = sobj._engine
-        return {"s_total": round(total, 3), "s_merge+derep+search (streamed)": round(t_pipe, 3), "s_finalize+write tail": round(total - t_pipe, 3),
+        outp = getattr(eng, "_out", None)
+        return {"deflate": deflate, "ms_deflate": round(getattr(outp, "ms_deflate", 0.0), 1),
+                "units_device": getattr(outp, "units_device", 0), "units_host_sliced": getattr(outp, "units_host", 0),
+                "s_total": round(total, 3), "s_merge+derep+search (streamed)": round(t_pipe, 3), "s_finalize+write tail": round(total - t_pipe, 3),
                 "chunks": int(eng.world), "pairs": int(getattr(eng, "n_pairs", 0)), "merged": int(eng.n_reads),
                 "timeline_s(chunk, text ready, loaded, searched)": [list(x) for x in eng.timeline],
                 "output_gz_MB": round((os.path.getsize(o1) + os.path.getsize(o2)) / 1e6, 1)}, (o1, o2)
@@ -69,7 +78,7 @@ def stream_leg(paths, hmm, tmp):
                 os.environ[k] = v
 
 
-def run(pairs, array_path=True, stream=False, check=False):
+def run(pairs, array_path=True, stream=False, check=False, arms=("host",)):
     """the run as a function (bench.py --paired-pairs calls it for its `paired_file_to_file` key): the stage times as a dict"""
     args = argparse.Namespace(pairs=int(pairs), array_path=bool(array_path))
     import synth
@@ -180,11 +189,17 @@ def run(pairs, array_path=True, stream=False, check=False):
             eng.close()
             # (a leg that does not end is reported by every thread's stack after two minutes)
             import faulthandler
-            faulthandler.dump_traceback_later(120, exit=True)
-            streamed, (s1, s2) = stream_leg(paths, hmm, tmp)
-            faulthandler.cancel_dump_traceback_later()
-            note("streamed run done: %.2f s" % streamed["s_total"])
-            streamed["pairs_per_s_file_to_file"] = round(n / streamed["s_total"])
+            legs = []
+            for arm in arms:
+                faulthandler.dump_traceback_later(120, exit=True)
+                streamed, (s1, s2) = stream_leg(paths, hmm, tmp, arm)
+                faulthandler.cancel_dump_traceback_later()
+                note("streamed run (%s deflate) done: %.2f s" % (arm, streamed["s_total"]))
+                streamed["pairs_per_s_file_to_file"] = round(n / streamed["s_total"])
+                legs.append(streamed)
+            streamed = legs[-1]
+            if len(legs) > 1:
+                streamed = dict(streamed, legs=legs)
             if check:
                 for a, b in ((o1, s1), (o2, s2)):
                     with gzip.open(a, "rb") as fa, gzip.open(b, "rb") as fb:
