@@ -152,6 +152,11 @@ typedef struct {
    * that part is ALSO accumulated into ms_filters / ms_domains, like the stages itsx_lazy_complete re-runs (it took the place of a
    * padding word: the structure's size and every other offset are unchanged) */
   int64_t n_lazy_topup;      float ms_lazy_topup;       float ms_lazy_topup_stages;
+  /* the device inflate (itsx_inflate_device, the loaders of a context that opted in): the two kernels' time and the members of the last
+   * call; files the device inflated and files it declined since the context was created (the structure grew at its end: every earlier
+   * offset is unchanged) */
+  float   ms_inflate;        int32_t n_inflate_members;
+  int64_t n_inflate_device, n_inflate_declined;
 } itsx_stats;
 
 int         itsx_abi_version(void);
@@ -404,6 +409,30 @@ int64_t itsx_deflate_bound(int64_t nbytes, int32_t n_ranges);
  * ITSX_E_ARG: out_cap below itsx_deflate_bound(nbytes, n_ranges), or bounds that do not tile the text. */
 int itsx_deflate_device(itsx_ctx *ctx, const char *text, int64_t nbytes, const int64_t *bounds, int32_t n_ranges, char *out, int64_t out_cap,
                         int64_t *out_bounds);
+/* ---- gzip input inflated on the device (opt-in).  A gzip file made of independent members -- what this library's writers produce
+ * (one member per 4 MiB of text from the host writer, one per itsx_deflate_block_bytes() from the device deflate), what bgzip produces,
+ * any cat a.gz b.gz -- is as parallel as it has members: csrc/k_inflate.hip finds the member starts with a strict test of every
+ * position, plans the text from the members' ISIZE fields and decodes one member per wave, each verifying its own length, CRC-32
+ * and ISIZE.  A general single-stream file is not taken (ITSX_INFLATE_MEMBER_KB, default 8192: the longest compressed member).
+ * gzip of independent members -> text, on the device.  The text stays in a buffer of the context.
+ * ITSX_OK: the device did the work.  ITSX_E_UNSUPPORTED: it DECLINED (not gzip, byte 0 no member start, a member too long, a member
+ * that did not verify, no memory); itsx_last_error names the reason and the member, and nothing half-made is left behind.
+ * itsx_stats.ms_inflate: the kernels' time; n_inflate_device / n_inflate_declined count the files of either kind. */
+int itsx_inflate_device(itsx_ctx *ctx, const char *gz, int64_t nbytes, int64_t *text_len, int64_t *n_members);
+/* the text of the last successful itsx_inflate_device (ITSX_E_ARG: there is none, or out_cap is below its length) */
+int itsx_inflate_fetch(itsx_ctx *ctx, char *out, int64_t out_cap);
+/* inflate_codes.h on the host, one thread, no device: the same routine member by member (tests, sanitizer program).  *reason: 0 or
+ * the refusal's code; text_len / n_members count the members that verified, and out holds their text alone. */
+int itsx_debug_inflate_host(const char *gz, int64_t nbytes, char *out, int64_t out_cap, int64_t *text_len, int64_t *n_members, int32_t *reason);
+/* the strict member-start test (inflate_codes.h: ic_candidate) at every position, on the host: the number of positions that pass; the
+ * first cap of them to positions (tests) */
+int64_t itsx_debug_inflate_candidates(const char *gz, int64_t nbytes, int64_t *positions, int64_t cap);
+/* after a successful itsx_inflate_device of n members: per member (file order) workgroup << 32 | the number of members that workgroup
+ * of k_inflate had decoded before it (tests: which members followed which on one workgroup) */
+int itsx_debug_inflate_where(itsx_ctx *ctx, int64_t *where, int64_t n);
+/* opt in per context: the context's whole-file loaders (itsx_load_reads_file, itsx_load_reads_files, the merge loaders) try the device
+ * first for a gzip file; a file it declines is inflated by the host exactly as without this.  ITSX_DEVICE_INFLATE=1 does the same. */
+int itsx_set_device_inflate(itsx_ctx *ctx, int on);
 /* csrc/deflate_codes.h on the host (no context, no device): the code lengths the kernel gives n <= 288 symbols of these counts (sum
  * below 2^32) under a limit of maxbits (1..15, n <= 2^maxbits).  lengths: [n]. */
 int itsx_debug_huffman_lengths(const uint32_t *freq, int32_t n, int32_t maxbits, uint8_t *lengths);

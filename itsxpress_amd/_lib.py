@@ -57,7 +57,8 @@ STATS_FIELDS = [("n_reads", "<i8"), ("n_unique", "<i8"), ("n_dropped_short", "<i
                 ("bound_rows_full", "<i8"), ("n_share_helpers", "<i8"), ("share_mismatch", "<i8"), ("ms_share_build", "<f4"), ("share_frac", "<f4"),
                 ("two_sided", "<i4"), ("n_bwd_launches", "<i4"), ("n_joined", "<i8"), ("bwd_chains", "<i8"), ("gamma_nodes", "<i8"), ("bwd_rows", "<i8"),
                 ("two_fwd_rows", "<i8"), ("two_bwd_rows", "<i8"), ("two_rows_full", "<i8"), ("join_maxdiff", "<f4"), ("ms_bwd_bound", "<f4"),
-                ("n_lazy_topup", "<i8"), ("ms_lazy_topup", "<f4"), ("ms_lazy_topup_stages", "<f4")]
+                ("n_lazy_topup", "<i8"), ("ms_lazy_topup", "<f4"), ("ms_lazy_topup_stages", "<f4"),
+                ("ms_inflate", "<f4"), ("n_inflate_members", "<i4"), ("n_inflate_device", "<i8"), ("n_inflate_declined", "<i8")]
 STATS_DTYPE = np.dtype(STATS_FIELDS, align=True)
 
 # every symbol include/itsx_hip.h declares
@@ -87,7 +88,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_keep_records", "itsx_write_trimmed_samples",
            "itsx_keep_pair_records", "itsx_write_trimmed_paired_samples",
            "itsx_deflate_block_bytes", "itsx_deflate_bound", "itsx_deflate_device", "itsx_debug_huffman_lengths",
-           "itsx_twriter_set_device"]
+           "itsx_twriter_set_device",
+           "itsx_inflate_device", "itsx_inflate_fetch", "itsx_debug_inflate_host", "itsx_debug_inflate_candidates", "itsx_debug_inflate_where", "itsx_set_device_inflate"]
 
 
 def lib():
@@ -158,6 +160,12 @@ def lib():
         "itsx_deflate_bound": (i64, [i64, i32]),
         "itsx_deflate_device": (i32, [vp, vp, i64, vp, i32, vp, i64, vp]),
         "itsx_debug_huffman_lengths": (i32, [vp, i32, i32, vp]),
+        "itsx_inflate_device": (i32, [vp, vp, i64, vp, vp]),
+        "itsx_inflate_fetch": (i32, [vp, vp, i64]),
+        "itsx_debug_inflate_host": (i32, [vp, i64, vp, i64, vp, vp, vp]),
+        "itsx_debug_inflate_candidates": (i64, [vp, i64, vp, i64]),
+        "itsx_debug_inflate_where": (i32, [vp, vp, i64]),
+        "itsx_set_device_inflate": (i32, [vp, i32]),
         "itsx_unique_keys128": (i32, [vp, C.c_uint64, C.c_uint64, i64, vp]),
         "itsx_write_derep_arrays": (i32, [cp, cp, i64, vp, vp, vp, vp, vp, vp, vp, i64]),
         "itsx_write_domtbl_arrays": (i32, [cp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp]),

@@ -311,6 +311,15 @@ class SampleBatch:
     def deflate(self, where: str):
         self.engine.deflate = where
 
+    # Where the engine's whole-file loaders inflate gzip input: the engine's own setting (Engine.inflate), under the batch's name
+    @property
+    def inflate(self) -> str:
+        return getattr(self.engine, "inflate", "host")
+
+    @inflate.setter
+    def inflate(self, where: str):
+        self.engine.inflate = where
+
     def _device_deflate_falls_back(self, who, gzipped, zstd_file):
         if self.deflate == "device":
             from .engine import _batch_compression

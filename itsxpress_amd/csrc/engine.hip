@@ -28,6 +28,7 @@
 #include "engine.h"
 #include "k_api.h"
 #include "deflate_codes.h"
+#include "inflate_codes.h"
 #include "twriter_dev.h"
 #include "cluster_multi.h"
 #include "fastq_io.h"
@@ -484,6 +485,10 @@ struct itsx_ctx {
   // (records, output text and deflate scratch are the batch writers' buffers above); tw_mu serialises the writers that share the context
   DBuf<uint8_t> tw_raw; DBuf<int32_t> tw_ls, tw_le; DBuf<int64_t> tw_lblk, tw_qsrc, tw_info;
   std::mutex tw_mu; bool tw_failed = false; float tw_ms_deflate = 0;
+  // the device inflate (inflate_file): the uploaded file, the candidate scan's tiles and list, the members and their statuses, and the
+  // text of the last successful call (inf_len bytes; -1: none).  inf_mu serialises the loader threads that share the context.
+  DBuf<uint8_t> inf_gz, inf_text; DBuf<int64_t> inf_counts, inf_base, inf_list, inf_where; DBuf<InflateMember> inf_mem; DBuf<int32_t> inf_status;
+  int64_t inf_len = -1, n_inf_device = 0, n_inf_declined = 0; bool device_inflate = false; std::mutex inf_mu;
   bool two_on = false; int share_maxrd = 0; int32_t Ub = 0; size_t sh_gslots_off = 0;
   DBuf<uint8_t> sh_rdepth_s, sh_rdepth; DBuf<unsigned long long> sh_rmask_s, sh_rmask, sh_keys, sh_keys2;
   DBuf<int32_t> sh_rparent_s, sh_rparent, sh_jlev_s, sh_jown_s, sh_endrow_s, sh_rsteps_s, sh_rnn_s, sh_rnode0_s, sh_endrow, sh_jlev, sh_jsrc, sh_jownb;
@@ -816,8 +821,16 @@ int itsx_load_profiles_mem(itsx_ctx *ctx, const char *text, int64_t len, int *n_
 }
 
 // whole file, decompressed by its magic bytes (fastq_io.h); read files stay in the text cache for the writers
-static std::shared_ptr<const itsx_io::Text> slurp(const char *path, bool cacheable, std::string &err)
+// ctx: a context that opted in (itsx_set_device_inflate, ITSX_DEVICE_INFLATE=1) tries a gzip file on the device first (inflate_file,
+// below); a file the device declines goes the host's way exactly as without it
+static bool inflate_for_loader(itsx_ctx *ctx, const itsx_io::Text &raw, itsx_io::Text &out);
+static bool device_inflate_on(const itsx_ctx *ctx);
+static std::shared_ptr<const itsx_io::Text> slurp(const char *path, bool cacheable, std::string &err, itsx_ctx *ctx = nullptr)
 {
+  if (ctx && device_inflate_on(ctx)) {
+    const itsx_io::InflateFirst first = [ctx](const itsx_io::Text &raw, itsx_io::Text &out) { return inflate_for_loader(ctx, raw, out); };
+    return itsx_io::read_text(path, err, cacheable, &first);
+  }
   return itsx_io::read_text(path, err, cacheable);
 }
 
@@ -1166,7 +1179,7 @@ int itsx_load_reads_file(itsx_ctx *ctx, const char *path, int64_t *n_reads)
   std::string rerr;
   static const bool trace = sw_get("ITSX_TRACE_ALLOC") != nullptr;
   const auto tt0 = std::chrono::steady_clock::now();
-  const auto tp = slurp(path, true, rerr);
+  const auto tp = slurp(path, true, rerr, ctx);
   if (!tp) SET_ERR(ctx, ITSX_E_IO, rerr);
   const auto tt1 = std::chrono::steady_clock::now();
   ctx->h_bases.clear(); ctx->h_off.assign(1, 0); ctx->h_names.clear();
@@ -1330,7 +1343,7 @@ int itsx_load_reads_files(itsx_ctx *ctx, const char *const *paths, int32_t n_pat
   for (int32_t f = 0; f < n_paths; f++) {
     CTXCHK(paths[f]);
     std::string rerr;
-    const auto tp = slurp(paths[f], true, rerr);
+    const auto tp = slurp(paths[f], true, rerr, ctx);
     if (!tp) SET_ERR(ctx, ITSX_E_IO, rerr);
     const size_t before = ctx->h_names.size();
     if (records) {
@@ -4330,8 +4343,8 @@ int itsx_merge_pairs_files(itsx_ctx *ctx, const char *r1_path, const char *r2_pa
 {
   CTXCHK(ctx && r1_path && r2_path && out_path);
   typedef FastxPart Side;
-  auto parse = [](const char *path, Side &sd, std::string &perr) -> int {      // no shared state: the two files are read side by side
-    const auto tp = slurp(path, true, perr);
+  auto parse = [ctx](const char *path, Side &sd, std::string &perr) -> int {   // no shared state: the two files are read side by side
+    const auto tp = slurp(path, true, perr, ctx);
     if (!tp) return ITSX_E_IO;
     if (!tp->empty() && (*tp)[0] != '@') { perr = std::string("malformed FASTQ record 1 in ") + path; return ITSX_E_FORMAT; }
     const int prc = parse_fastx(*tp, true, true, sd, perr);
@@ -4386,13 +4399,13 @@ int itsx_merge_pairs_files(itsx_ctx *ctx, const char *r1_path, const char *r2_pa
 // one side of a paired sample: a file (text == nullptr) or a record-aligned piece of its text already in memory.  No shared state: the
 // sides of one sample, and the samples of a batch, are parsed side by side
 // titles: the records' whole title lines are collected too (sd.titles; the pair records of itsx_keep_pair_records)
-static int parse_fastq_side(const char *path, const char *text, int64_t nb, FastxPart &sd, std::string &perr, bool titles = false)
+static int parse_fastq_side(const char *path, const char *text, int64_t nb, FastxPart &sd, std::string &perr, bool titles = false, itsx_ctx *ctx = nullptr)
 {
   std::shared_ptr<const itsx_io::Text> tp;
   itsx_io::Text view;
   const itsx_io::Text *t = &view;
   if (text) view.borrow(text, (size_t)nb);
-  else { tp = slurp(path, true, perr); if (!tp) return ITSX_E_IO; t = tp.get(); }
+  else { tp = slurp(path, true, perr, ctx); if (!tp) return ITSX_E_IO; t = tp.get(); }
   if (!t->empty() && (*t)[0] != '@') { perr = std::string("malformed FASTQ record 1 in ") + path; return ITSX_E_FORMAT; }
   const int prc = parse_fastx(*t, true, true, sd, perr);
   if (prc != ITSX_OK) { perr += std::string(" in ") + path; return prc; }
@@ -4611,8 +4624,8 @@ static int merge_pairs_load_impl(itsx_ctx *ctx, const char *r1_path, const char 
   int rc2 = ITSX_OK;
   const auto tm0 = std::chrono::steady_clock::now();
   const bool pair_records = ctx->keep_pair_records && !text1;      // (a streamed piece keeps none, as with itsx_keep_records)
-  std::thread other([&] { rc2 = parse_fastq_side(r2_path, text2, nb2, r, rerr2, pair_records); });
-  int rc = parse_fastq_side(r1_path, text1, nb1, f, ferr, pair_records);
+  std::thread other([&] { rc2 = parse_fastq_side(r2_path, text2, nb2, r, rerr2, pair_records, ctx); });
+  int rc = parse_fastq_side(r1_path, text1, nb1, f, ferr, pair_records, ctx);
   other.join();
   if (rc != ITSX_OK) { ctx->set_error(ferr); return rc; }
   if (rc2 != ITSX_OK) { ctx->set_error(rerr2); return rc2; }
@@ -4662,7 +4675,7 @@ static int merge_pairs_load_files_impl(itsx_ctx *ctx, const char *const *r1_path
         const int64_t q = next.fetch_add(1);
         if (q >= (int64_t)S * 2) break;
         const size_t s = (size_t)(q >> 1);
-        rcs[(size_t)q] = (q & 1) ? parse_fastq_side(r2_paths[s], nullptr, 0, rs[s], errs[(size_t)q], pair_records) : parse_fastq_side(r1_paths[s], nullptr, 0, fs[s], errs[(size_t)q], pair_records);
+        rcs[(size_t)q] = (q & 1) ? parse_fastq_side(r2_paths[s], nullptr, 0, rs[s], errs[(size_t)q], pair_records, ctx) : parse_fastq_side(r1_paths[s], nullptr, 0, fs[s], errs[(size_t)q], pair_records, ctx);
       }
     });
   }
@@ -5155,6 +5168,168 @@ static int put_staged(itsx_ctx *ctx, const char *src, int64_t total, uint8_t *dd
   }
   return ITSX_OK;
 }
+// ------------------------------------------------------------------------------ gzip members inflated on the device (k_inflate.hip)
+// A gzip file made of independent members (this project's writers', bgzip's, any cat a.gz b.gz): the bytes go up through the pinned
+// staging buffers, k_inflate_find lists the positions that pass the strict member-start test, the list IS the plan -- member i spans
+// [c_i, c_i+1), its ISIZE is its span's last 4 bytes (read from the caller's copy: four bytes a member, no walk), the text offsets are
+// the 64-bit scan of the ISIZEs -- and k_inflate decodes one member per wave, longest spans first.  Every member verifies its own
+// length, CRC-32 and ISIZE; one refusal declines the whole file (ITSX_E_UNSUPPORTED, the reason and the member named), as do a file
+// whose byte 0 is no member start, a member longer than ITSX_INFLATE_MEMBER_KB (it would be one wave's serial work), more text than
+// deflate can expand to, and a text that cannot be allocated.  A decline leaves no text behind.  stats.ms_inflate: the kernels' time.
+static bool device_inflate_on(const itsx_ctx *ctx) { const char *e = sw_get("ITSX_DEVICE_INFLATE"); return ctx->device_inflate || (e && atoi(e) == 1); }
+static int64_t inflate_member_cap()
+{
+  const char *e = sw_get("ITSX_INFLATE_MEMBER_KB");
+  const long long kb = e ? atoll(e) : 8192;                  // twice the host writer's 4 MiB block of text: its members always pass
+  return (int64_t)std::min<long long>(std::max<long long>(kb, 1), 2097151) * 1024;      // (a stored run's offset is 32 bits)
+}
+static int inflate_file(itsx_ctx *ctx, const char *gz, int64_t nbytes, int64_t *text_len, int64_t *n_members)
+{
+  using namespace itsx_ic;
+  hipStream_t st = ctx->st;
+  ctx->inf_len = -1; ctx->stats.ms_inflate = 0; ctx->stats.n_inflate_members = 0;
+  auto decline = [&](int32_t why, int64_t member, const std::string &more = std::string()) {
+    ctx->n_inf_declined++;
+    ctx->set_error(std::string("the device inflate declined the file: ") + ic_reason_name(why) + (member >= 0 ? " (member " + std::to_string(member) + ")" : std::string()) + more);
+    return (int)ITSX_E_UNSUPPORTED;
+  };
+  const uint8_t *g = reinterpret_cast<const uint8_t *>(gz);
+  if (nbytes < 2 || g[0] != 0x1f || g[1] != 0x8b) return decline(IC_E_NOT_GZIP, -1);
+  if (nbytes < IC_MIN_MEMBER) return decline(IC_E_INPUT, 0);
+  // byte 0 is no member start: the reason its header gives (these few bytes are read here, nothing is walked), else just that
+  auto first_reason = [&]() { int32_t why = IC_OK; (void)ic_header(g, nbytes, &why); return why ? why : (int32_t)IC_E_FIRST; };
+  // device memory that cannot be had is a decline like any other ("no memory"), whichever buffer it is
+  auto room = [&](hipError_t e) { if (e != hipSuccess) { (void)hipGetLastError(); } return e == hipSuccess; };
+  // ---- up, and the member starts
+  if (!room(ctx->inf_gz.alloc((size_t)nbytes + 16))) return decline(IC_E_NOMEM, -1, ": the file's " + std::to_string(nbytes) + " bytes");
+  { const int rc = put_staged(ctx, gz, nbytes, ctx->inf_gz.p); if (rc != ITSX_OK) return rc; }
+  const int64_t ntiles = (nbytes + INFLATE_FIND_TILE - 1) / INFLATE_FIND_TILE;
+  if (!room(ctx->inf_counts.alloc((size_t)ntiles)) || !room(ctx->inf_base.alloc((size_t)ntiles + 1))) return decline(IC_E_NOMEM, -1, ": the member search");
+  int64_t M = 0;
+  {
+    StageTimer tm(st);
+    launch_inflate_find(ctx->inf_gz.p, nbytes, ctx->inf_counts.p, nullptr, nullptr, st);
+    launch_inflate_scan(ctx->inf_counts.p, ntiles, ctx->inf_base.p, ctx->inf_base.p + ntiles, st);
+    ctx->stats.ms_inflate += tm.stop();
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&M, ctx->inf_base.p + ntiles, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (M <= 0) return decline(first_reason(), -1);
+  if (M > 0x7fffffff) return decline(IC_E_NOMEM, -1, ": more than 2^31 members");
+  if (!room(ctx->inf_list.alloc((size_t)M))) return decline(IC_E_NOMEM, -1, ": the list of " + std::to_string(M) + " members");
+  {
+    StageTimer tm(st);
+    launch_inflate_find(ctx->inf_gz.p, nbytes, ctx->inf_counts.p, ctx->inf_base.p, ctx->inf_list.p, st);
+    ctx->stats.ms_inflate += tm.stop();
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<int64_t> start((size_t)M + 1);
+  HIPCHK(hipMemcpyAsync(start.data(), ctx->inf_list.p, (size_t)M * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  start[(size_t)M] = nbytes;
+  if (start[0] != 0) return decline(first_reason(), -1);
+  // ---- the plan
+  const int64_t cap = inflate_member_cap();
+  std::vector<InflateMember> mem((size_t)M);
+  int64_t total = 0;
+  for (int64_t i = 0; i < M; i++) {
+    const int64_t c = start[(size_t)i], ce = start[(size_t)i + 1];
+    if (c < 0 || ce <= c || ce > nbytes) SET_ERR(ctx, ITSX_E_DEVICE, "the device inflate's member list is not increasing");
+    if (ce - c < IC_MIN_MEMBER) return decline(IC_E_INPUT, i);
+    if (ce - c > cap) return decline(IC_E_MEMBER_LONG, i, ": " + std::to_string(ce - c) + " compressed bytes, the cap (ITSX_INFLATE_MEMBER_KB) is " + std::to_string(cap));
+    const uint8_t *q = g + ce - 4;
+    const uint32_t isize = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+    mem[(size_t)i] = InflateMember{c, ce, total, isize, (int32_t)i};
+    total += isize;
+    if (total > 1032 * nbytes + 64 * M) return decline(IC_E_EXPANSION, i);
+  }
+  if (!room(ctx->inf_text.alloc((size_t)total + 16))) return decline(IC_E_NOMEM, -1, ": the text's " + std::to_string(total) + " bytes");
+  std::stable_sort(mem.begin(), mem.end(), [](const InflateMember &x, const InflateMember &y) { return x.c_end - x.c > y.c_end - y.c; });
+  if (!room(ctx->inf_mem.alloc((size_t)M)) || !room(ctx->inf_status.alloc((size_t)M)) || !room(ctx->inf_where.alloc((size_t)M))) return decline(IC_E_NOMEM, -1, ": the plan of " + std::to_string(M) + " members");
+  HIPCHK(hipMemcpyAsync(ctx->inf_mem.p, mem.data(), (size_t)M * sizeof(InflateMember), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(ctx->inf_status.p, 0xff, (size_t)M * 4, st));        // a member no workgroup reached is not a verified one
+  int ncu = 256;
+  { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, ctx->device) == hipSuccess && pr.multiProcessorCount > 0) ncu = pr.multiProcessorCount; }
+  InflateArgs ia{};
+  ia.gz = ctx->inf_gz.p; ia.mem = ctx->inf_mem.p; ia.nmem = (int32_t)M; ia.text = ctx->inf_text.p; ia.status = ctx->inf_status.p; ia.where = ctx->inf_where.p;
+  int64_t grid = std::min<int64_t>(M, (int64_t)ncu * 4);                               // four workgroups' LDS fit a CU
+  if (const char *e = sw_get("ITSX_INFLATE_GRID")) grid = std::max<int64_t>(1, std::min<int64_t>(grid, atoll(e)));
+  {
+    StageTimer tm(st);
+    launch_inflate(ia, (int)grid, st);
+    ctx->stats.ms_inflate += tm.stop();
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<int32_t> status((size_t)M);
+  HIPCHK(hipMemcpyAsync(status.data(), ctx->inf_status.p, (size_t)M * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < M; i++) if (status[(size_t)i] != 0) return decline(status[(size_t)i], i);
+  ctx->inf_len = total; ctx->n_inf_device++; ctx->stats.n_inflate_members = (int32_t)M;
+  if (text_len) *text_len = total;
+  if (n_members) *n_members = M;
+  return ITSX_OK;
+}
+// read_text's "try this inflater first" for a context that opted in: false = the host path continues exactly as without it
+static bool inflate_for_loader(itsx_ctx *ctx, const itsx_io::Text &raw, itsx_io::Text &out)
+{
+  std::lock_guard<std::mutex> g(ctx->inf_mu);
+  if (hipSetDevice(ctx->device) != hipSuccess) return false;
+  int64_t n = 0;
+  if (inflate_file(ctx, raw.data(), (int64_t)raw.size(), &n, nullptr) != ITSX_OK) return false;
+  if (!out.resize((size_t)n)) return false;
+  return fetch_staged(ctx, ctx->inf_text.p, n, out.data()) == ITSX_OK;
+}
+extern "C" {
+int itsx_inflate_device(itsx_ctx *ctx, const char *gz, int64_t nbytes, int64_t *text_len, int64_t *n_members)
+{
+  CTXCHK(ctx && gz && nbytes >= 0);
+  std::lock_guard<std::mutex> g(ctx->inf_mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  return inflate_file(ctx, gz, nbytes, text_len, n_members);
+}
+int itsx_inflate_fetch(itsx_ctx *ctx, char *out, int64_t out_cap)
+{
+  CTXCHK(ctx);
+  std::lock_guard<std::mutex> g(ctx->inf_mu);
+  if (ctx->inf_len < 0) SET_ERR(ctx, ITSX_E_ARG, "itsx_inflate_fetch: no text (the last itsx_inflate_device did not succeed, or there was none)");
+  if (out_cap < ctx->inf_len || (!out && ctx->inf_len > 0)) SET_ERR(ctx, ITSX_E_ARG, "itsx_inflate_fetch: out_cap is below the text's " + std::to_string(ctx->inf_len) + " bytes");
+  HIPCHK(hipSetDevice(ctx->device));
+  return fetch_staged(ctx, ctx->inf_text.p, ctx->inf_len, out);
+}
+int itsx_set_device_inflate(itsx_ctx *ctx, int on)
+{
+  CTXCHK(ctx);
+  ctx->device_inflate = on != 0;
+  return ITSX_OK;
+}
+int itsx_debug_inflate_where(itsx_ctx *ctx, int64_t *where, int64_t n)
+{
+  CTXCHK(ctx && where && n >= 0);
+  std::lock_guard<std::mutex> g(ctx->inf_mu);
+  if (ctx->inf_len < 0 || n != (int64_t)ctx->stats.n_inflate_members) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_inflate_where: n is not the member count of a successful itsx_inflate_device");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipMemcpyAsync(where, ctx->inf_where.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->st));
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  return ITSX_OK;
+}
+int64_t itsx_debug_inflate_candidates(const char *gz, int64_t nbytes, int64_t *positions, int64_t cap)
+{
+  if (!gz || nbytes < 0 || cap < 0 || (!positions && cap > 0)) return ITSX_E_ARG;
+  int64_t n = 0;
+  for (int64_t at = 0; at < nbytes; at++)
+    if (itsx_ic::ic_candidate(reinterpret_cast<const uint8_t *>(gz), nbytes, at)) { if (n < cap) positions[n] = at; n++; }
+  return n;
+}
+int itsx_debug_inflate_host(const char *gz, int64_t nbytes, char *out, int64_t out_cap, int64_t *text_len, int64_t *n_members, int32_t *reason)
+{
+  if (!gz || nbytes < 0 || out_cap < 0 || (!out && out_cap > 0) || !text_len || !n_members || !reason) return ITSX_E_ARG;
+  std::unique_ptr<itsx_ic::IcHostScratch> w(new (std::nothrow) itsx_ic::IcHostScratch);
+  if (!w) return ITSX_E_NOMEM;
+  *reason = itsx_ic::ic_inflate_file_host(reinterpret_cast<const uint8_t *>(gz), nbytes, reinterpret_cast<uint8_t *>(out), out_cap, text_len, n_members, *w);
+  return *reason ? ITSX_E_UNSUPPORTED : ITSX_OK;
+}
+}  // extern "C"
 // the scratch deflate_ranges takes for a text of nbytes in one range, held before the first unit arrives
 static int deflate_reserve(itsx_ctx *ctx, int64_t nbytes)
 {
@@ -5490,6 +5665,7 @@ int itsx_get_stats(const itsx_ctx *ctx, itsx_stats *out, int64_t out_size)
   CTXCHK(ctx && out);
   if (out_size != (int64_t)sizeof(itsx_stats)) SET_ERR(ctx, ITSX_E_ARG, "itsx_get_stats: the caller's itsx_stats has " + std::to_string(out_size) + " bytes, this library's " + std::to_string(sizeof(itsx_stats)) + " (header and library from different sources)");
   *out = ctx->stats;
+  out->n_inflate_device = ctx->n_inf_device; out->n_inflate_declined = ctx->n_inf_declined;
   return ITSX_OK;
 }
 

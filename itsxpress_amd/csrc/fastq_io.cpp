@@ -398,7 +398,7 @@ static bool read_raw(const char *path, int64_t fsize, Text &raw, std::string &er
   return true;
 }
 
-std::shared_ptr<const Text> read_text(const char *path, std::string &err, bool cacheable)
+std::shared_ptr<const Text> read_text(const char *path, std::string &err, bool cacheable, const InflateFirst *first)
 {
   codecs();
   int64_t fsize = 0, mtime = 0;
@@ -419,20 +419,21 @@ std::shared_ptr<const Text> read_text(const char *path, std::string &err, bool c
   if (!read_raw(path, fsize, raw, err)) return nullptr;
   const auto c1 = std::chrono::steady_clock::now();
   auto text = std::make_shared<Text>();
-  bool par = false;
+  bool par = false, dev = false;
   if (is_gzip(raw)) {
     // large single-member files: block-parallel inflate, accepted only on a CRC-32 and length match (pinflate.cpp)
-    if (env_int("ITSX_PARALLEL_INFLATE", 1) != 0 && io_threads() > 1) {
+    if (first && *first) { dev = (*first)(raw, *text); if (!dev) text->clear(); }      // the caller's inflater first; it declined: on as ever
+    if (!dev && env_int("ITSX_PARALLEL_INFLATE", 1) != 0 && io_threads() > 1) {
       par = gunzip_parallel(raw.data(), raw.size(), *text, io_threads());
       if (par) g_parallel_inflates.fetch_add(1);
     }
-    const bool ok = par || (g_ld.ok ? gunzip_libdeflate(raw, *text, err) : gunzip_zlib(raw, *text, err));
+    const bool ok = dev || par || (g_ld.ok ? gunzip_libdeflate(raw, *text, err) : gunzip_zlib(raw, *text, err));
     if (!ok) { err += std::string(" in ") + path; return nullptr; }
   } else if (is_zstd(raw)) {
     if (!unzstd(raw, *text, err)) { err += std::string(" in ") + path; return nullptr; }
   } else text->swap(raw);
   if (text->capacity() > text->size() + text->size() / 4 + (1 << 20)) text->shrink_to_fit();      // a copy: only when it frees a lot
-  if (trace) fprintf(stderr, "[itsx] read %s: file %.0f ms, decode%s %.0f ms (%.1f MB -> %.1f MB)\n", path, std::chrono::duration<double, std::milli>(c1 - c0).count(), par ? " (block-parallel)" : "",
+  if (trace) fprintf(stderr, "[itsx] read %s: file %.0f ms, decode%s %.0f ms (%.1f MB -> %.1f MB)\n", path, std::chrono::duration<double, std::milli>(c1 - c0).count(), dev ? " (caller's inflater)" : par ? " (block-parallel)" : "",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c1).count(), raw.size() / 1e6, text->size() / 1e6);
   if (cacheable && budget > 0 && (double)text->size() <= budget) cache_insert(path, fsize, mtime, text, budget);
   return text;

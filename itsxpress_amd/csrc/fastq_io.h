@@ -72,7 +72,10 @@ class Text {
 };
 
 // Returns the decompressed content or nullptr (err set).  cacheable: keep / look up the text in the process-wide cache.
-std::shared_ptr<const Text> read_text(const char *path, std::string &err, bool cacheable);
+// first (may be null): an inflater tried on a gzip file's bytes before the host's own (the engine's device inflate); false = it declined,
+// and the host path continues exactly as without it.
+using InflateFirst = std::function<bool(const Text &raw, Text &out)>;
+std::shared_ptr<const Text> read_text(const char *path, std::string &err, bool cacheable, const InflateFirst *first = nullptr);
 void cache_clear();
 // CRC-32 (the gzip polynomial), continuing from `crc` (0 to start): libdeflate's when the library is there, else zlib's
 uint32_t crc32_fast(uint32_t crc, const void *p, size_t n);

@@ -249,6 +249,21 @@ void launch_deflate(const DeflateArgs &a, int grid, hipStream_t st);
 // member b (sizes[b] bytes) from its slot to out + dst[b]
 void launch_deflate_pack(const uint8_t *slots, const int32_t *sizes, const int64_t *dst, int32_t nblk, uint8_t *out, hipStream_t st);
 
+// ---- k_inflate.hip (gzip files of independent members inflated on the device: one wave per member)
+constexpr int INFLATE_FIND_TILE = 4096;         // positions one block of k_inflate_find tests per turn
+struct InflateMember { int64_t c, c_end, o; uint32_t isize; int32_t id; };      // compressed bytes [c, c_end) -> text bytes [o, o + isize); id: its place in the file
+struct InflateArgs {
+  const uint8_t *gz;                            // the file's bytes
+  const InflateMember *mem; int32_t nmem;       // in the order the workgroups take them
+  uint8_t *text;                                // 4-byte aligned
+  int32_t *status;                              // [nmem] by id: 0, or the reason (inflate_codes.h) the member was refused for
+  int64_t *where;                               // [nmem] by id: workgroup << 32 | members that workgroup had decoded before (tests)
+};
+// list null: counts[tile] = member-start candidates among the tile's positions; else the positions themselves to list[base[tile] ...]
+void launch_inflate_find(const uint8_t *gz, int64_t n, int64_t *counts, const int64_t *base, int64_t *list, hipStream_t st);
+void launch_inflate_scan(const int64_t *counts, int64_t ntiles, int64_t *base, int64_t *total, hipStream_t st);
+void launch_inflate(const InflateArgs &a, int grid, hipStream_t st);
+
 // ---- k_util.hip
 // exclusive prefix sum of n int32 values (n < 2^31); tmp must hold scan_tmp_elems(n) int32
 int64_t scan_tmp_elems(int64_t n);

@@ -78,6 +78,22 @@ class Engine:
             raise ValueError('Engine.deflate is "host" or "device", not %r' % (where,))
         self._deflate = where
 
+    # Where the context's whole-file loaders (load_reads_file, load_reads_files, the merge loaders) inflate a gzip input: "host" (the
+    # default: libdeflate / zlib / the block-parallel inflater on the I/O threads, as ever) or "device" (a file made of independent
+    # gzip members -- this package's writers', bgzip's -- is inflated by csrc/k_inflate.hip first; a file the device declines goes the
+    # host's way).  The same text either way.  Stays until set again.
+    @property
+    def inflate(self):
+        return getattr(self, "_inflate", "host")
+
+    @inflate.setter
+    def inflate(self, where):
+        if where not in ("host", "device"):
+            raise ValueError('Engine.inflate is "host" or "device", not %r' % (where,))
+        if getattr(self, "h", None):
+            self._chk(self.L.itsx_set_device_inflate(self.h, int(where == "device")))
+        self._inflate = where
+
     # Every call that changes the context's read set records the new count here, so the setter is where the read set's serial number
     # advances: a caller that left reads resident (SampleBatch.merge_reads) keeps the number and can tell later whether the
     # engine -- which may be shared -- still holds them
@@ -670,6 +686,18 @@ class Engine:
         ob = np.zeros(R + 1, np.int64)
         self._chk(self.L.itsx_deflate_device(self.h, data, len(data), b.ctypes.data, R, out.ctypes.data, cap, ob.ctypes.data))
         return [out[int(ob[r]):int(ob[r + 1])].tobytes() for r in range(R)]
+
+    # ---- the device inflate by itself
+    def inflate_device(self, data):
+        """The text of a gzip file made of independent members, inflated on the device.  EngineError with code -5 when the device
+        declined (not such a file, a member too long, a member that did not verify); the message names the reason and the member."""
+        data = bytes(data)
+        n, m = C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.itsx_inflate_device(self.h, data, len(data), C.byref(n), C.byref(m)))
+        out = np.empty(max(n.value, 1), np.uint8)
+        self._chk(self.L.itsx_inflate_fetch(self.h, out.ctypes.data, n.value))
+        self.inflate_members = int(m.value)
+        return out[:n.value].tobytes()
 
     # ---- writers
     def write_uc(self, path):

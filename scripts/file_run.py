@@ -30,9 +30,12 @@ def main():
     ap.add_argument("--chunk-mb", type=float, default=0.0, help="--stream: text per chunk (0: about a tenth of the file)")
     ap.add_argument("--stream-write", action="store_true", help="--stream: the writer inside the pipeline too (provisional thresholds per chunk)")
     ap.add_argument("--deflate", default="host", choices=["host", "device"], help="--stream --stream-write with gz output: where the writer's gzip members are made (StreamEngine.deflate)")
+    ap.add_argument("--inflate", default="host", choices=["host", "device"], help="where the whole-file load inflates the input (Engine.inflate); not with --stream")
     ap.add_argument("--check", action="store_true", help="--stream: compare the coordinates with one context on the whole file")
     ap.add_argument("--input-dir", default="", help="keep the generated in.fastq.gz here and use it again when it is there (several arms over one file)")
     args = ap.parse_args()
+    if args.inflate == "device" and args.stream:
+        ap.error("--inflate device is the whole-file loaders' mode: the streamed loaders inflate on the host (not with --stream)")
     import synth
     from bench import its2_profiles
     from itsxpress_amd import Engine, _lib
@@ -124,9 +127,13 @@ def main():
                 assert extra["coordinates_equal_one_context"]
                 e1.close()
         else:
+            eng.inflate = args.inflate
             t0 = time.perf_counter()
             eng.load_reads_file(fq)
             t["load"] = time.perf_counter() - t0
+            st = eng.stats()
+            extra = {**extra, "inflate": args.inflate, "ms_inflate": round(st["ms_inflate"], 1), "inflate_members": st["n_inflate_members"],
+                     "inflate_files_device": st["n_inflate_device"], "inflate_files_declined": st["n_inflate_declined"]}
             t0 = time.perf_counter()
             nu = eng.derep()
             eng.search()
