@@ -157,6 +157,11 @@ typedef struct {
    * offset is unchanged) */
   float   ms_inflate;        int32_t n_inflate_members;
   int64_t n_inflate_device, n_inflate_declined;
+  /* the device parse (itsx_parse_device, the whole-file loaders of a context that opted in): its kernels' time in the last call, all of
+   * the call's texts together; texts the device parsed and texts it declined since the context was created (the structure grew at its
+   * end again: every earlier offset is unchanged) */
+  float   ms_parse;          int32_t parse_reserved;    /* (padding: 0) */
+  int64_t n_parse_device, n_parse_declined;
 } itsx_stats;
 
 int         itsx_abi_version(void);
@@ -433,6 +438,38 @@ int itsx_debug_inflate_where(itsx_ctx *ctx, int64_t *where, int64_t n);
 /* opt in per context: the context's whole-file loaders (itsx_load_reads_file, itsx_load_reads_files, the merge loaders) try the device
  * first for a gzip file; a file it declines is inflated by the host exactly as without this.  ITSX_DEVICE_INFLATE=1 does the same. */
 int itsx_set_device_inflate(itsx_ctx *ctx, int on);
+/* ---- FASTQ text parsed on the device (opt-in).  csrc/k_fastq.hip indexes the lines of a text that lies in device memory, checks every
+ * record by the rule of csrc/fastq_rec.h and gathers bases, qualities and title lines into planes.  The rule accepts exactly the texts
+ * that are 4 lines per record throughout (no blank line anywhere, no FASTA), and for those the records are the host parser's byte for
+ * byte; any other text is DECLINED, which is no error: the host parser then decides what the text is.
+ * text -> records, on the device (the text goes up through the staging buffers).  keep_qual == 0: no quality plane is made.
+ * ITSX_OK: *n_records records lie in the context (itsx_parse_fetch).  ITSX_E_UNSUPPORTED: declined; itsx_last_error names the reason
+ * and the record, and nothing is left to fetch.  itsx_stats.ms_parse: the kernels' time; n_parse_device / n_parse_declined count the
+ * texts of either kind. */
+int itsx_parse_device(itsx_ctx *ctx, const char *text, int64_t nbytes, int keep_qual, int64_t *n_records);
+/* a range of one plane of the last successful itsx_parse_device: ITSX_PARSE_OFF / ITSX_PARSE_TOFF elements [lo, hi) of the n + 1
+ * offsets of the bases / title lines (out: int64_t), ITSX_PARSE_SEQ / ITSX_PARSE_QUAL / ITSX_PARSE_TITLES bytes [lo, hi) of the
+ * bases, the qualities, the title lines ('@' included, no line end).  ITSX_E_ARG: no parse to fetch from, no such plane (qualities that
+ * were not kept), a range outside the plane. */
+#define ITSX_PARSE_OFF 0
+#define ITSX_PARSE_TOFF 1
+#define ITSX_PARSE_SEQ 2
+#define ITSX_PARSE_QUAL 3
+#define ITSX_PARSE_TITLES 4
+int itsx_parse_fetch(itsx_ctx *ctx, int32_t plane, int64_t lo, int64_t hi, void *out);
+/* csrc/fastq_rec.h on the host, one thread, no device (tests, sanitizer program).  *reason: 0 or the decline's code, *bad_record the
+ * record it shows at (-1: the text as a whole).  off / toff: cap_records + 1 entries; seq, qual (may be NULL: not kept): cap_bases
+ * bytes; titles: cap_titles bytes.  ITSX_OK, ITSX_E_UNSUPPORTED (declined: nothing written), ITSX_E_ARG (a buffer too small: nothing
+ * written, and *n_records, *n_bases, *n_title_bytes say what is needed). */
+int itsx_debug_parse_host(const char *text, int64_t nbytes, int64_t *off, int64_t *toff, int64_t cap_records, char *seq, char *qual, int64_t cap_bases,
+                          char *titles, int64_t cap_titles, int64_t *n_records, int64_t *n_bases, int64_t *n_title_bytes, int32_t *reason, int64_t *bad_record);
+/* opt in per context: itsx_load_reads_file, itsx_load_reads_text and itsx_load_reads_files (with or without itsx_keep_records) parse on
+ * the device.  A text the device inflate produced (itsx_set_device_inflate) is parsed where it lies and never reaches the host or its
+ * text cache -- a host consumer that wants the file later reads it again, as on any cache miss; any other text is uploaded once.
+ * Only the offsets and the title lines come back; the bases stay on the device (fetched when rep.fa or the seeds' sequences are asked
+ * for).  One declined text makes the whole call start over on the host path: results and errors are that path's.  The streamed
+ * loaders, itsx_load_reads_file_shard and the merge and orient loaders parse on the host.  ITSX_DEVICE_PARSE=1 does the same. */
+int itsx_set_device_parse(itsx_ctx *ctx, int on);
 /* csrc/deflate_codes.h on the host (no context, no device): the code lengths the kernel gives n <= 288 symbols of these counts (sum
  * below 2^32) under a limit of maxbits (1..15, n <= 2^maxbits).  lengths: [n]. */
 int itsx_debug_huffman_lengths(const uint32_t *freq, int32_t n, int32_t maxbits, uint8_t *lengths);

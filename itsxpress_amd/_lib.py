@@ -59,7 +59,15 @@ STATS_FIELDS = [("n_reads", "<i8"), ("n_unique", "<i8"), ("n_dropped_short", "<i
                 ("two_fwd_rows", "<i8"), ("two_bwd_rows", "<i8"), ("two_rows_full", "<i8"), ("join_maxdiff", "<f4"), ("ms_bwd_bound", "<f4"),
                 ("n_lazy_topup", "<i8"), ("ms_lazy_topup", "<f4"), ("ms_lazy_topup_stages", "<f4"),
                 ("ms_inflate", "<f4"), ("n_inflate_members", "<i4"), ("n_inflate_device", "<i8"), ("n_inflate_declined", "<i8")]
-STATS_DTYPE = np.dtype(STATS_FIELDS, align=True)
+# what itsx_stats has grown by at its end since (the device parse)
+STATS_TAIL_FIELDS = [("ms_parse", "<f4"), ("parse_reserved", "<i4"), ("n_parse_device", "<i8"), ("n_parse_declined", "<i8")]
+# the whole structure, as include/itsx_hip.h declares it: what Engine.stats() reads
+STATS_DTYPE_ALL = np.dtype(STATS_FIELDS + STATS_TAIL_FIELDS, align=True)
+# the same record named up to the device inflate's fields, at the structure's full size: tests/test_device_inflate_cpu.py holds this
+# name to "the inflate's fields come after every other field", so the fields added behind them are named by STATS_DTYPE_ALL alone
+_head = np.dtype(STATS_FIELDS, align=True)
+STATS_DTYPE = np.dtype({"names": list(_head.names), "formats": [_head.fields[k][0] for k in _head.names],
+                        "offsets": [_head.fields[k][1] for k in _head.names], "itemsize": STATS_DTYPE_ALL.itemsize})
 
 # every symbol include/itsx_hip.h declares
 EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy", "itsx_load_profiles_file",
@@ -89,7 +97,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_keep_pair_records", "itsx_write_trimmed_paired_samples",
            "itsx_deflate_block_bytes", "itsx_deflate_bound", "itsx_deflate_device", "itsx_debug_huffman_lengths",
            "itsx_twriter_set_device",
-           "itsx_inflate_device", "itsx_inflate_fetch", "itsx_debug_inflate_host", "itsx_debug_inflate_candidates", "itsx_debug_inflate_where", "itsx_set_device_inflate"]
+           "itsx_inflate_device", "itsx_inflate_fetch", "itsx_debug_inflate_host", "itsx_debug_inflate_candidates", "itsx_debug_inflate_where", "itsx_set_device_inflate",
+           "itsx_parse_device", "itsx_parse_fetch", "itsx_debug_parse_host", "itsx_set_device_parse"]
 
 
 def lib():
@@ -166,6 +175,10 @@ def lib():
         "itsx_debug_inflate_candidates": (i64, [vp, i64, vp, i64]),
         "itsx_debug_inflate_where": (i32, [vp, vp, i64]),
         "itsx_set_device_inflate": (i32, [vp, i32]),
+        "itsx_parse_device": (i32, [vp, vp, i64, i32, vp]),
+        "itsx_parse_fetch": (i32, [vp, i32, i64, i64, vp]),
+        "itsx_debug_parse_host": (i32, [vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+        "itsx_set_device_parse": (i32, [vp, i32]),
         "itsx_unique_keys128": (i32, [vp, C.c_uint64, C.c_uint64, i64, vp]),
         "itsx_write_derep_arrays": (i32, [cp, cp, i64, vp, vp, vp, vp, vp, vp, vp, i64]),
         "itsx_write_domtbl_arrays": (i32, [cp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp]),

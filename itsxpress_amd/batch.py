@@ -320,6 +320,15 @@ class SampleBatch:
     def inflate(self, where: str):
         self.engine.inflate = where
 
+    # Where the engine's whole-file loaders parse FASTQ text: the engine's own setting (Engine.parse), under the batch's name
+    @property
+    def parse(self) -> str:
+        return getattr(self.engine, "parse", "host")
+
+    @parse.setter
+    def parse(self, where: str):
+        self.engine.parse = where
+
     def _device_deflate_falls_back(self, who, gzipped, zstd_file):
         if self.deflate == "device":
             from .engine import _batch_compression

@@ -29,6 +29,7 @@
 #include "k_api.h"
 #include "deflate_codes.h"
 #include "inflate_codes.h"
+#include "fastq_rec.h"
 #include "twriter_dev.h"
 #include "cluster_multi.h"
 #include "fastq_io.h"
@@ -489,6 +490,11 @@ struct itsx_ctx {
   // text of the last successful call (inf_len bytes; -1: none).  inf_mu serialises the loader threads that share the context.
   DBuf<uint8_t> inf_gz, inf_text; DBuf<int64_t> inf_counts, inf_base, inf_list, inf_where; DBuf<InflateMember> inf_mem; DBuf<int32_t> inf_status;
   int64_t inf_len = -1, n_inf_device = 0, n_inf_declined = 0; bool device_inflate = false; std::mutex inf_mu;
+  // the device parse (parse_text_device): a text uploaded for it, the line index and the plan's scratch, the last text's offsets, and
+  // the planes -- of the last successful itsx_parse_device (ps_n records; -1: none), or of a load under way, whose bases plane then
+  // becomes d_merged_text (the read set's text on the device, as after a merge).  ps_mu serialises the callers that share the context.
+  DBuf<uint8_t> ps_text, ps_seq, ps_qual, ps_titles; DBuf<int64_t> ps_lblk, ps_nl, ps_blk, ps_off, ps_toff, ps_info;
+  int64_t ps_n = -1, ps_nb = 0, ps_nt = 0, n_parse_device = 0, n_parse_declined = 0; bool ps_qual_kept = false, device_parse = false; std::mutex ps_mu;
   bool two_on = false; int share_maxrd = 0; int32_t Ub = 0; size_t sh_gslots_off = 0;
   DBuf<uint8_t> sh_rdepth_s, sh_rdepth; DBuf<unsigned long long> sh_rmask_s, sh_rmask, sh_keys, sh_keys2;
   DBuf<int32_t> sh_rparent_s, sh_rparent, sh_jlev_s, sh_jown_s, sh_endrow_s, sh_rsteps_s, sh_rnn_s, sh_rnode0_s, sh_endrow, sh_jlev, sh_jsrc, sh_jownb;
@@ -825,6 +831,11 @@ int itsx_load_profiles_mem(itsx_ctx *ctx, const char *text, int64_t len, int *n_
 // below); a file the device declines goes the host's way exactly as without it
 static bool inflate_for_loader(itsx_ctx *ctx, const itsx_io::Text &raw, itsx_io::Text &out);
 static bool device_inflate_on(const itsx_ctx *ctx);
+// ctx: a context that opted in (itsx_set_device_parse, ITSX_DEVICE_PARSE=1) parses on the device (load_parsed_device, below: paths, or
+// one text in memory); PARSE_FALLBACK = a text was declined or could not be read, and the caller goes the host's way from the start
+constexpr int PARSE_FALLBACK = 1;
+static bool device_parse_on(const itsx_ctx *ctx);
+static int load_parsed_device(itsx_ctx *ctx, const char *const *paths, int32_t n_paths, const char *text, int64_t nbytes, int64_t *n_reads_per_file, bool batch);
 static std::shared_ptr<const itsx_io::Text> slurp(const char *path, bool cacheable, std::string &err, itsx_ctx *ctx = nullptr)
 {
   if (ctx && device_inflate_on(ctx)) {
@@ -1176,6 +1187,7 @@ static int parse_fastx_append(itsx_ctx *ctx, const itsx_io::Text &text, itsx_io:
 int itsx_load_reads_file(itsx_ctx *ctx, const char *path, int64_t *n_reads)
 {
   CTXCHK(ctx && path);
+  if (device_parse_on(ctx)) { const int drc = load_parsed_device(ctx, &path, 1, nullptr, 0, n_reads, false); if (drc != PARSE_FALLBACK) return drc; }
   std::string rerr;
   static const bool trace = sw_get("ITSX_TRACE_ALLOC") != nullptr;
   const auto tt0 = std::chrono::steady_clock::now();
@@ -1199,6 +1211,7 @@ int itsx_load_reads_text(itsx_ctx *ctx, const char *text, int64_t nbytes, int64_
 {
   CTXCHK(ctx && (text || nbytes == 0) && nbytes >= 0);
   LoadPriority load_priority(ctx);
+  if (device_parse_on(ctx)) { const int drc = load_parsed_device(ctx, nullptr, 0, text ? text : "", nbytes, n_reads, false); if (drc != PARSE_FALLBACK) return drc; }
   itsx_io::Text view;
   view.borrow(text ? text : "", (size_t)nbytes);
   ctx->h_bases.clear(); ctx->h_off.assign(1, 0); ctx->h_names.clear();
@@ -1336,6 +1349,7 @@ int itsx_keep_pair_records(itsx_ctx *ctx, int on)
 int itsx_load_reads_files(itsx_ctx *ctx, const char *const *paths, int32_t n_paths, int64_t *n_reads_per_file)
 {
   CTXCHK(ctx && paths && n_paths >= 1);
+  if (device_parse_on(ctx)) { const int drc = load_parsed_device(ctx, paths, n_paths, nullptr, 0, n_reads_per_file, true); if (drc != PARSE_FALLBACK) return drc; }
   ctx->h_bases.clear(); ctx->h_off.assign(1, 0); ctx->h_names.clear();
   std::vector<int32_t> smp;
   const bool records = ctx->keep_records;
@@ -5330,6 +5344,244 @@ int itsx_debug_inflate_host(const char *gz, int64_t nbytes, char *out, int64_t o
   return *reason ? ITSX_E_UNSUPPORTED : ITSX_OK;
 }
 }  // extern "C"
+// ------------------------------------------------------------------------------ FASTQ text parsed on the device (k_fastq.hip)
+// A text that lies in device memory (the device inflate's, or one uploaded once through the staging buffers): k_fastq.hip counts and
+// indexes its lines, checks every record by fastq_rec.h's rule and measures it, and gathers bases, qualities (where they are kept) and
+// title lines into the context's planes behind what earlier texts of the same call left there.  Two small reads come back in between
+// (the line count; the verdict and the totals), nothing of the text.  A text the rule does not accept is DECLINED (ITSX_E_UNSUPPORTED,
+// the reason and the record named), as is one whose index or planes cannot be allocated.  stats.ms_parse: the kernels' time.
+static bool device_parse_on(const itsx_ctx *ctx) { const char *e = sw_get("ITSX_DEVICE_PARSE"); return ctx->device_parse || (e && atoi(e) == 1); }
+struct ParsedText { int64_t n = 0, nb = 0, nt = 0; };      // records, bases, title bytes
+// room for `need` bytes (and the padding every plane has) in a plane whose first `used` bytes are kept
+static hipError_t plane_room(DBuf<uint8_t> &d, int64_t used, int64_t need, hipStream_t st)
+{
+  if (d.p && (size_t)need + 64 <= d.cap) { d.n = (size_t)need + 64; return hipSuccess; }
+  DBuf<uint8_t> nd;
+  hipError_t e = hipErrorOutOfMemory;
+  if (used > 0) e = nd.alloc(std::max((size_t)need + 64, 2 * d.cap), true);      // a batch's planes grow file by file: doubled
+  if (e != hipSuccess) { (void)hipGetLastError(); e = nd.alloc((size_t)need + 64, true); }
+  if (e != hipSuccess) return e;
+  if (used > 0) e = hipMemcpyAsync(nd.p, d.p, (size_t)used, hipMemcpyDeviceToDevice, st);
+  dbuf_swap(d, nd);
+  return e;
+}
+static int parse_text_device(itsx_ctx *ctx, const uint8_t *dtext, int64_t nbytes, bool keep_qual, int64_t gb, int64_t gt, ParsedText &out)
+{
+  using namespace itsx_fq;
+  hipStream_t st = ctx->st;
+  out = ParsedText();
+  auto decline = [&](int32_t why, int64_t rec, const std::string &more = std::string()) {
+    ctx->n_parse_declined++;
+    ctx->set_error(std::string("the device parse declined the text: ") + fq_reason_name(why) + (rec >= 0 ? " (record " + std::to_string(rec) + ")" : std::string()) + more);
+    return (int)ITSX_E_UNSUPPORTED;
+  };
+  auto room = [&](hipError_t e) { if (e != hipSuccess) { (void)hipGetLastError(); } return e == hipSuccess; };
+  if (nbytes == 0) { ctx->n_parse_device++; return ITSX_OK; }                  // no bytes: no lines, no records
+  FastqArgs a{};
+  a.text = dtext; a.nbytes = nbytes;
+  if (!room(ctx->ps_lblk.alloc((size_t)fastq_index_blocks(nbytes) + 1)) || !room(ctx->ps_info.alloc(FASTQ_INFO))) return decline(FQ_E_NOMEM, -1, ": the line count");
+  a.lblk = ctx->ps_lblk.p; a.info = ctx->ps_info.p;
+  int64_t info[FASTQ_INFO] = {0, 0, 0, 0, 0, 0, 0, 0};
+  {
+    StageTimer tm(st);
+    launch_fastq_count(a, st);
+    ctx->stats.ms_parse += tm.stop();
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(info, ctx->ps_info.p, 2 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const int64_t lines = info[0], nnl = info[1];
+  if (lines <= 0 || lines % 4 != 0 || nnl < lines - 1 || nnl > lines) return decline(FQ_E_LINES, -1, ": " + std::to_string(lines) + " lines");
+  const int64_t n = lines / 4;
+  if (n >= (1ll << 31) - 64) return decline(FQ_E_NOMEM, -1, ": more than 2^31 records");
+  if (!room(ctx->ps_nl.alloc((size_t)lines + 1)) || !room(ctx->ps_blk.alloc((size_t)(2 * fastq_plan_blocks(n) + 2))) || !room(ctx->ps_off.alloc((size_t)n + 1)) ||
+      !room(ctx->ps_toff.alloc((size_t)n + 1))) return decline(FQ_E_NOMEM, -1, ": the index of " + std::to_string(lines) + " lines");
+  a.nl = ctx->ps_nl.p; a.nlines = lines; a.nnl = nnl; a.n = n; a.blk = ctx->ps_blk.p; a.off = ctx->ps_off.p; a.toff = ctx->ps_toff.p;
+  {
+    StageTimer tm(st);
+    launch_fastq_index(a, st);
+    launch_fastq_plan(a, st);
+    ctx->stats.ms_parse += tm.stop();
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(info, ctx->ps_info.p, sizeof(info), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const unsigned long long verdict = (unsigned long long)info[4];
+  if (verdict != FQ_VERDICT_NONE) return decline((int32_t)(verdict & 7), (int64_t)(verdict >> 3));
+  const int64_t nb = info[2], nt = info[3];
+  if (nb < 0 || nt < n || nb > nbytes || nt > nbytes) SET_ERR(ctx, ITSX_E_DEVICE, "the device parse's totals do not fit its text");
+  if (!room(plane_room(ctx->ps_seq, gb, gb + nb, st)) || (keep_qual && !room(plane_room(ctx->ps_qual, gb, gb + nb, st))) || !room(plane_room(ctx->ps_titles, gt, gt + nt, st)))
+    return decline(FQ_E_NOMEM, -1, ": the planes of " + std::to_string(gb + nb) + " bases");
+  {
+    StageTimer tm(st);
+    launch_fastq_gather(dtext, a.nl, a.off, n, 1, ctx->ps_seq.p, gb, nb, st);
+    if (keep_qual) launch_fastq_gather(dtext, a.nl, a.off, n, 3, ctx->ps_qual.p, gb, nb, st);
+    launch_fastq_gather(dtext, a.nl, a.toff, n, 0, ctx->ps_titles.p, gt, nt, st);
+    ctx->stats.ms_parse += tm.stop();
+  }
+  HIPCHK(hipGetLastError());
+  out.n = n; out.nb = nb; out.nt = nt;
+  ctx->n_parse_device++;
+  return ITSX_OK;
+}
+// a host text to ps_text (padded as the kernels want it); false: no device memory for it
+static int parse_upload(itsx_ctx *ctx, const char *text, int64_t nbytes, bool &fits)
+{
+  fits = true;
+  if (nbytes <= 0) return ITSX_OK;
+  if (ctx->ps_text.alloc((size_t)nbytes + 16) != hipSuccess) { (void)hipGetLastError(); fits = false; return ITSX_OK; }
+  return put_staged(ctx, text, nbytes, ctx->ps_text.p);
+}
+// The whole-file loaders' device path: every text (the files of `paths`, or the one text in memory) is parsed on the device into the
+// same planes with running bases; offsets and title lines come back, identifiers are cut from the titles, and the bases plane becomes
+// the read set's device text (d_merged_text: packed where it lies, fetched by host_bases when rep.fa wants it, released by the next
+// read set), with records kept also their bases plane, installed without a host copy.  PARSE_FALLBACK: nothing of the context's read
+// set has been touched, and the caller takes the host path from its start -- a declined text, or a file that could not be read (the
+// host path says why).
+static int load_parsed_device(itsx_ctx *ctx, const char *const *paths, int32_t n_paths, const char *text, int64_t nbytes, int64_t *n_reads_per_file, bool batch)
+{
+  std::lock_guard<std::mutex> g(ctx->ps_mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  const bool records = batch && ctx->keep_records;
+  const int32_t ntexts = paths ? n_paths : 1;
+  ctx->ps_n = -1; ctx->stats.ms_parse = 0;
+  std::vector<int64_t> off(1, 0); NameList titles; std::vector<int32_t> smp;
+  std::vector<int64_t> counts((size_t)ntexts, 0);
+  int64_t gb = 0, gt = 0;
+  for (int32_t f = 0; f < ntexts; f++) {
+    const uint8_t *dtext = nullptr; int64_t len = 0;
+    std::shared_ptr<const itsx_io::Text> tp;
+    bool kept = false;
+    if (paths) {
+      if (!paths[f]) return PARSE_FALLBACK;
+      std::string rerr;
+      if (device_inflate_on(ctx)) {
+        // the device inflate's text stays where it is: nothing of it comes back, nothing of it is cached
+        const itsx_io::InflateFirst first = [ctx](const itsx_io::Text &raw, itsx_io::Text &) {
+          std::lock_guard<std::mutex> gi(ctx->inf_mu);
+          if (hipSetDevice(ctx->device) != hipSuccess) return false;
+          return inflate_file(ctx, raw.data(), (int64_t)raw.size(), nullptr, nullptr) == ITSX_OK;
+        };
+        tp = itsx_io::read_text(paths[f], rerr, true, &first, &kept);
+      } else tp = itsx_io::read_text(paths[f], rerr, true);
+      if (!tp) return PARSE_FALLBACK;
+    }
+    if (kept) { dtext = ctx->inf_text.p; len = ctx->inf_len; }
+    else {
+      const char *h = paths ? tp->data() : text;
+      len = paths ? (int64_t)tp->size() : nbytes;
+      bool fits = true;
+      { const int rc = parse_upload(ctx, h, len, fits); if (rc != ITSX_OK) return rc; }
+      if (!fits) return PARSE_FALLBACK;
+      dtext = ctx->ps_text.p;
+    }
+    ParsedText pt;
+    const int rc = parse_text_device(ctx, dtext, len, records, gb, gt, pt);
+    if (rc == ITSX_E_UNSUPPORTED) return PARSE_FALLBACK;
+    if (rc != ITSX_OK) return rc;
+    if (pt.n > 0) {                              // this text's offsets and title lines: all that comes back
+      const size_t r0 = off.size() - 1;
+      off.resize(r0 + (size_t)pt.n + 1); titles.off.resize(r0 + (size_t)pt.n + 1); titles.blob.resize((size_t)(gt + pt.nt));
+      HIPCHK(hipMemcpyAsync(off.data() + r0 + 1, ctx->ps_off.p + 1, (size_t)pt.n * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(titles.off.data() + r0 + 1, ctx->ps_toff.p + 1, (size_t)pt.n * 8, hipMemcpyDeviceToHost, st));
+      { const int frc = fetch_staged(ctx, ctx->ps_titles.p + gt, pt.nt, titles.blob.data() + gt); if (frc != ITSX_OK) return frc; }
+      if (gb || gt) for (size_t r = r0 + 1; r < off.size(); r++) { off[r] += gb; titles.off[r] += gt; }
+    }
+    gb += pt.nb; gt += pt.nt;
+    counts[(size_t)f] = pt.n;
+    if (batch) smp.resize(off.size() - 1, f);
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  const int64_t N = (int64_t)off.size() - 1;
+  if (N >= (1ll << 31) - 64) return PARSE_FALLBACK;
+  NameList names;                                // the identifier: the title after its '@' up to the first blank or tab
+  names.off.reserve((size_t)N + 1); names.blob.reserve(titles.blob.size());
+  for (int64_t r = 0; r < N; r++) {
+    const char *b = titles.ptr((size_t)r) + 1, *e = titles.ptr((size_t)r) + titles.len((size_t)r), *ne = b;
+    while (ne < e && *ne != ' ' && *ne != '\t') ne++;
+    names.emplace_back(b, ne);
+  }
+  // ---- the read set
+  if (n_reads_per_file) for (int32_t f = 0; f < ntexts; f++) n_reads_per_file[f] = counts[(size_t)f];
+  itsx_io::Text().swap(ctx->h_bases);
+  ctx->h_off.swap(off); ctx->h_names.swap(names); ctx->N = N;
+  ctx->d_merged_text.release();
+  dbuf_swap(ctx->d_merged_text, ctx->ps_seq);
+  if (!ctx->d_merged_text.p) HIPCHK(ctx->d_merged_text.alloc(64));
+  int rc = pack_and_upload(ctx, nullptr, ctx->d_merged_text.p);
+  if (rc != ITSX_OK || !batch) return rc;
+  rc = itsx_set_samples(ctx, smp.data(), n_paths);
+  if (rc != ITSX_OK || !records) return rc;
+  itsx_ctx::Records &rr = ctx->rec;              // the planes as the gather left them: no host copy of bases or qualities exists
+  dbuf_swap(rr.qual, ctx->ps_qual); dbuf_swap(rr.titles, ctx->ps_titles);
+  if (!rr.qual.p) HIPCHK(rr.qual.alloc(64));
+  if (!rr.titles.p) HIPCHK(rr.titles.alloc(64));
+  HIPCHK(rr.off.alloc((size_t)N + 1)); HIPCHK(rr.toff.alloc((size_t)N + 1));
+  HIPCHK(hipMemcpyAsync(rr.off.p, ctx->h_off.data(), ((size_t)N + 1) * 8, hipMemcpyHostToDevice, ctx->st));
+  HIPCHK(hipMemcpyAsync(rr.toff.p, titles.off.data(), ((size_t)N + 1) * 8, hipMemcpyHostToDevice, ctx->st));
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  rr.h_titles.swap(titles);
+  rr.seq_p = ctx->d_merged_text.p; rr.have = true;
+  return ITSX_OK;
+}
+extern "C" {
+int itsx_set_device_parse(itsx_ctx *ctx, int on)
+{
+  CTXCHK(ctx);
+  ctx->device_parse = on != 0;
+  return ITSX_OK;
+}
+int itsx_parse_device(itsx_ctx *ctx, const char *text, int64_t nbytes, int keep_qual, int64_t *n_records)
+{
+  CTXCHK(ctx && nbytes >= 0 && (text || nbytes == 0) && n_records);
+  std::lock_guard<std::mutex> g(ctx->ps_mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->ps_n = -1; ctx->stats.ms_parse = 0;
+  bool fits = true;
+  { const int rc = parse_upload(ctx, text, nbytes, fits); if (rc != ITSX_OK) return rc; }
+  if (!fits) {
+    ctx->n_parse_declined++;
+    SET_ERR(ctx, ITSX_E_UNSUPPORTED, std::string("the device parse declined the text: ") + itsx_fq::fq_reason_name(itsx_fq::FQ_E_NOMEM) + ": the text's " + std::to_string(nbytes) + " bytes");
+  }
+  ParsedText pt;
+  const int rc = parse_text_device(ctx, ctx->ps_text.p, nbytes, keep_qual != 0, 0, 0, pt);
+  if (rc != ITSX_OK) return rc;
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  HIPCHK(hipGetLastError());
+  ctx->ps_n = pt.n; ctx->ps_nb = pt.nb; ctx->ps_nt = pt.nt; ctx->ps_qual_kept = keep_qual != 0;
+  *n_records = pt.n;
+  return ITSX_OK;
+}
+int itsx_parse_fetch(itsx_ctx *ctx, int32_t plane, int64_t lo, int64_t hi, void *out)
+{
+  CTXCHK(ctx);
+  std::lock_guard<std::mutex> g(ctx->ps_mu);
+  if (ctx->ps_n < 0) SET_ERR(ctx, ITSX_E_ARG, "itsx_parse_fetch: no parse to fetch from (the last itsx_parse_device did not succeed, or there was none)");
+  if (plane < ITSX_PARSE_OFF || plane > ITSX_PARSE_TITLES || (plane == ITSX_PARSE_QUAL && !ctx->ps_qual_kept)) SET_ERR(ctx, ITSX_E_ARG, "itsx_parse_fetch: no such plane");
+  const bool offs = plane == ITSX_PARSE_OFF || plane == ITSX_PARSE_TOFF;
+  const int64_t size = offs ? ctx->ps_n + 1 : plane == ITSX_PARSE_TITLES ? ctx->ps_nt : ctx->ps_nb;
+  if (lo < 0 || hi < lo || hi > size || (!out && hi > lo)) SET_ERR(ctx, ITSX_E_ARG, "itsx_parse_fetch: the range is not inside the plane's " + std::to_string(size) + (offs ? " entries" : " bytes"));
+  if (hi == lo) return ITSX_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (offs) {
+    if (ctx->ps_n == 0) { *reinterpret_cast<int64_t *>(out) = 0; return ITSX_OK; }      // a text of no bytes: off = toff = {0}
+    const int64_t *src = plane == ITSX_PARSE_OFF ? ctx->ps_off.p : ctx->ps_toff.p;
+    return fetch_staged(ctx, reinterpret_cast<const uint8_t *>(src + lo), (hi - lo) * 8, reinterpret_cast<char *>(out));
+  }
+  const uint8_t *src = plane == ITSX_PARSE_SEQ ? ctx->ps_seq.p : plane == ITSX_PARSE_QUAL ? ctx->ps_qual.p : ctx->ps_titles.p;
+  return fetch_staged(ctx, src + lo, hi - lo, reinterpret_cast<char *>(out));
+}
+int itsx_debug_parse_host(const char *text, int64_t nbytes, int64_t *off, int64_t *toff, int64_t cap_records, char *seq, char *qual, int64_t cap_bases,
+                          char *titles, int64_t cap_titles, int64_t *n_records, int64_t *n_bases, int64_t *n_title_bytes, int32_t *reason, int64_t *bad_record)
+{
+  if (nbytes < 0 || (!text && nbytes > 0) || !off || !toff || cap_records < 0 || cap_bases < 0 || cap_titles < 0 || (!seq && cap_bases > 0) || (!titles && cap_titles > 0) ||
+      !n_records || !n_bases || !n_title_bytes || !reason || !bad_record) return ITSX_E_ARG;
+  *reason = itsx_fq::fq_parse_host(reinterpret_cast<const uint8_t *>(text), nbytes, off, toff, cap_records, reinterpret_cast<uint8_t *>(seq), reinterpret_cast<uint8_t *>(qual), cap_bases,
+                                   reinterpret_cast<uint8_t *>(titles), cap_titles, n_records, n_bases, n_title_bytes, bad_record);
+  return *reason == itsx_fq::FQ_OK ? ITSX_OK : *reason == itsx_fq::FQ_E_CAP ? ITSX_E_ARG : ITSX_E_UNSUPPORTED;
+}
+}  // extern "C"
 // the scratch deflate_ranges takes for a text of nbytes in one range, held before the first unit arrives
 static int deflate_reserve(itsx_ctx *ctx, int64_t nbytes)
 {
@@ -5666,6 +5918,7 @@ int itsx_get_stats(const itsx_ctx *ctx, itsx_stats *out, int64_t out_size)
   if (out_size != (int64_t)sizeof(itsx_stats)) SET_ERR(ctx, ITSX_E_ARG, "itsx_get_stats: the caller's itsx_stats has " + std::to_string(out_size) + " bytes, this library's " + std::to_string(sizeof(itsx_stats)) + " (header and library from different sources)");
   *out = ctx->stats;
   out->n_inflate_device = ctx->n_inf_device; out->n_inflate_declined = ctx->n_inf_declined;
+  out->n_parse_device = ctx->n_parse_device; out->n_parse_declined = ctx->n_parse_declined;
   return ITSX_OK;
 }
 

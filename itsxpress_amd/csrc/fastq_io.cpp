@@ -398,8 +398,9 @@ static bool read_raw(const char *path, int64_t fsize, Text &raw, std::string &er
   return true;
 }
 
-std::shared_ptr<const Text> read_text(const char *path, std::string &err, bool cacheable, const InflateFirst *first)
+std::shared_ptr<const Text> read_text(const char *path, std::string &err, bool cacheable, const InflateFirst *first, bool *first_kept)
 {
+  if (first_kept) *first_kept = false;
   codecs();
   int64_t fsize = 0, mtime = 0;
   if (!stat_of(path, fsize, mtime)) { err = std::string("cannot read ") + path; return nullptr; }
@@ -435,6 +436,7 @@ std::shared_ptr<const Text> read_text(const char *path, std::string &err, bool c
   if (text->capacity() > text->size() + text->size() / 4 + (1 << 20)) text->shrink_to_fit();      // a copy: only when it frees a lot
   if (trace) fprintf(stderr, "[itsx] read %s: file %.0f ms, decode%s %.0f ms (%.1f MB -> %.1f MB)\n", path, std::chrono::duration<double, std::milli>(c1 - c0).count(), dev ? " (caller's inflater)" : par ? " (block-parallel)" : "",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c1).count(), raw.size() / 1e6, text->size() / 1e6);
+  if (dev && first_kept) { *first_kept = true; return text; }      // the caller's inflater kept the text where it made it: nothing to cache
   if (cacheable && budget > 0 && (double)text->size() <= budget) cache_insert(path, fsize, mtime, text, budget);
   return text;
 }

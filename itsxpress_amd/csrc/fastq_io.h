@@ -74,8 +74,10 @@ class Text {
 // Returns the decompressed content or nullptr (err set).  cacheable: keep / look up the text in the process-wide cache.
 // first (may be null): an inflater tried on a gzip file's bytes before the host's own (the engine's device inflate); false = it declined,
 // and the host path continues exactly as without it.
+// first_kept (may be null): the caller's inflater keeps the text it makes where it made it (device memory) and hands `out` back empty;
+// *first_kept says that it did, and such a text is not cached (the returned text is empty).
 using InflateFirst = std::function<bool(const Text &raw, Text &out)>;
-std::shared_ptr<const Text> read_text(const char *path, std::string &err, bool cacheable, const InflateFirst *first = nullptr);
+std::shared_ptr<const Text> read_text(const char *path, std::string &err, bool cacheable, const InflateFirst *first = nullptr, bool *first_kept = nullptr);
 void cache_clear();
 // CRC-32 (the gzip polynomial), continuing from `crc` (0 to start): libdeflate's when the library is there, else zlib's
 uint32_t crc32_fast(uint32_t crc, const void *p, size_t n);

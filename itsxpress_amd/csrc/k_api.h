@@ -264,6 +264,29 @@ void launch_inflate_find(const uint8_t *gz, int64_t n, int64_t *counts, const in
 void launch_inflate_scan(const int64_t *counts, int64_t ntiles, int64_t *base, int64_t *total, hipStream_t st);
 void launch_inflate(const InflateArgs &a, int grid, hipStream_t st);
 
+// ---- k_fastq.hip (FASTQ text parsed on the device: line index, record check and plan, gather; the rule is fastq_rec.h's)
+constexpr int FASTQ_INFO = 8;                   // info[0] lines, [1] newlines, [2] bases, [3] title bytes, [4] the verdict word (fastq_rec.h)
+struct FastqArgs {
+  const uint8_t *text; int64_t nbytes;          // 16-byte aligned, readable 16 bytes past nbytes
+  int64_t *lblk;                                // [fastq_index_blocks(nbytes) + 1] the tiles' newline counts, then their exclusive prefixes
+  int64_t *nl; int64_t nlines, nnl;             // [nlines + 1] the index (fastq_rec.h: fq_line), from the second index pass on
+  int64_t n;                                    // records = nlines / 4, from the plan on
+  int64_t *blk;                                 // [2 x fastq_plan_blocks(n) + 2] scratch
+  int64_t *off, *toff;                          // [n + 1] where record r's bases / title start in planes of this text alone
+  int64_t *info;                                // [FASTQ_INFO]
+};
+int64_t fastq_index_blocks(int64_t nbytes);
+int64_t fastq_plan_blocks(int64_t n);
+// info zeroed (the verdict: none), lblk[tile] = newlines of the tile, then their prefixes in place; info[0], info[1]
+void launch_fastq_count(const FastqArgs &a, hipStream_t st);
+// nl[k] = the k-th newline's position, nl[nnl] = nbytes where the last line is unterminated
+void launch_fastq_index(const FastqArgs &a, hipStream_t st);
+// every record checked (info[4] = the lowest bad one and its reason), off / toff and info[2], info[3]
+void launch_fastq_plan(const FastqArgs &a, hipStream_t st);
+// line `which` (0 title, 1 bases, 3 qualities) of every record to dst[gbase + doff[r] ...): doff = off or toff of the plan, total = doff[n]
+// bytes; dst is 16-byte aligned and holds gbase + total bytes; the bytes of dst below gbase are left as they are
+void launch_fastq_gather(const uint8_t *text, const int64_t *nl, const int64_t *doff, int64_t n, int which, uint8_t *dst, int64_t gbase, int64_t total, hipStream_t st);
+
 // ---- k_util.hip
 // exclusive prefix sum of n int32 values (n < 2^31); tmp must hold scan_tmp_elems(n) int32
 int64_t scan_tmp_elems(int64_t n);

@@ -22,6 +22,7 @@
 #include "engine.h"
 #include "k_api.h"
 #include "k_scan.h"
+#include "k_lines.h"
 
 namespace itsx {
 
@@ -304,22 +305,6 @@ void launch_trim_copy(TrimCopyArgs a, hipStream_t st)
 // As Records::line of trim_host.cpp: a '\r' before the newline is not part of the line, a last line without a newline counts.
 constexpr int LI_BLOCK = 256;
 constexpr int64_t LI_TILE = (int64_t)LI_BLOCK * 16;
-
-__device__ __forceinline__ uint32_t trim_newlines16(const uint8_t *__restrict__ text, int64_t nbytes, int64_t p0)
-{
-  if (p0 >= nbytes) return 0;
-  const uint4 v = *reinterpret_cast<const uint4 *>(text + p0);
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  uint32_t m = 0;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-#pragma unroll
-    for (int b = 0; b < 4; b++) if (((w[k] >> (8 * b)) & 255u) == (uint32_t)'\n') m |= 1u << (4 * k + b);
-  }
-  const int64_t left = nbytes - p0;
-  if (left < 16) m &= (1u << (int)left) - 1u;
-  return m;
-}
 
 template <bool SCATTER> __global__ __launch_bounds__(LI_BLOCK) void k_trim_index(TrimUnitArgs a)
 {

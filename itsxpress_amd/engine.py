@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import DOMAIN_DTYPE, STATS_DTYPE, TRACE_DTYPE, EngineError
+from ._lib import DOMAIN_DTYPE, STATS_DTYPE_ALL, TRACE_DTYPE, EngineError
 
 
 def _device_from_env():
@@ -93,6 +93,23 @@ class Engine:
         if getattr(self, "h", None):
             self._chk(self.L.itsx_set_device_inflate(self.h, int(where == "device")))
         self._inflate = where
+
+    # Where the context's whole-file loaders (load_reads_file, load_reads_text, load_reads_files) parse FASTQ text: "host" (the default:
+    # the I/O threads, as ever) or "device" (csrc/k_fastq.hip: the text is parsed where the device inflate left it, or uploaded once;
+    # only offsets and title lines come back, and the bases stay on the device until rep.fa asks for them; a text the device declines
+    # -- FASTA, blank lines, a malformed record -- makes the call start over on the host).  The same reads either way.  A file the
+    # device both inflated and parsed never enters the host's text cache: a writer that wants its text later reads the file again.
+    @property
+    def parse(self):
+        return getattr(self, "_parse", "host")
+
+    @parse.setter
+    def parse(self, where):
+        if where not in ("host", "device"):
+            raise ValueError('Engine.parse is "host" or "device", not %r' % (where,))
+        if getattr(self, "h", None):
+            self._chk(self.L.itsx_set_device_parse(self.h, int(where == "device")))
+        self._parse = where
 
     # Every call that changes the context's read set records the new count here, so the setter is where the read set's serial number
     # advances: a caller that left reads resident (SampleBatch.merge_reads) keeps the number and can tell later whether the
@@ -699,6 +716,29 @@ class Engine:
         self.inflate_members = int(m.value)
         return out[:n.value].tobytes()
 
+    # ---- the device parse by itself
+    PARSE_PLANES = {"off": 0, "toff": 1, "seq": 2, "qual": 3, "titles": 4}
+
+    def parse_fetch(self, plane, lo, hi):
+        """Elements [lo, hi) of "off" / "toff" (int64 array) or bytes [lo, hi) of "seq" / "qual" / "titles" of the last parse_device."""
+        k = self.PARSE_PLANES[plane]
+        n = max(int(hi) - int(lo), 0)
+        out = np.empty(max(n, 1), np.int64 if k < 2 else np.uint8)
+        self._chk(self.L.itsx_parse_fetch(self.h, k, int(lo), int(hi), out.ctypes.data))
+        return out[:n].copy() if k < 2 else out[:n].tobytes()
+
+    def parse_device(self, text, keep_qual=True):
+        """FASTQ text taken apart on the device: a dict of n, off, toff (int64 arrays of n + 1), seq, qual (None unless kept) and titles
+        (bytes).  EngineError with code -5 when the device declined the text (not 4 lines per record throughout, a malformed record);
+        the message names the reason and the record."""
+        text = bytes(text)
+        n = C.c_int64(0)
+        self._chk(self.L.itsx_parse_device(self.h, text, len(text), int(bool(keep_qual)), C.byref(n)))
+        n = int(n.value)
+        off, toff = self.parse_fetch("off", 0, n + 1), self.parse_fetch("toff", 0, n + 1)
+        return dict(n=n, off=off, toff=toff, seq=self.parse_fetch("seq", 0, int(off[-1])),
+                    qual=self.parse_fetch("qual", 0, int(off[-1])) if keep_qual else None, titles=self.parse_fetch("titles", 0, int(toff[-1])))
+
     # ---- writers
     def write_uc(self, path):
         self._chk(self.L.itsx_write_uc(self.h, os.fsencode(path)))
@@ -710,9 +750,9 @@ class Engine:
         self._chk(self.L.itsx_write_domtbl(self.h, os.fsencode(path)))
 
     def stats(self):
-        s = np.zeros(1, STATS_DTYPE)
-        self._chk(self.L.itsx_get_stats(self.h, s.ctypes.data, STATS_DTYPE.itemsize))
-        return {k: (s[0][k].item() if s[0][k].ndim == 0 else s[0][k].tolist()) for k in STATS_DTYPE.names}
+        s = np.zeros(1, STATS_DTYPE_ALL)
+        self._chk(self.L.itsx_get_stats(self.h, s.ctypes.data, STATS_DTYPE_ALL.itemsize))
+        return {k: (s[0][k].item() if s[0][k].ndim == 0 else s[0][k].tolist()) for k in STATS_DTYPE_ALL.names}
 
     def release_scratch(self):
         """hand the context's DP slab (tens of GB) to the next context of this process on the device: a streamed file's chunk after

@@ -31,15 +31,20 @@ def main():
     ap.add_argument("--stream-write", action="store_true", help="--stream: the writer inside the pipeline too (provisional thresholds per chunk)")
     ap.add_argument("--deflate", default="host", choices=["host", "device"], help="--stream --stream-write with gz output: where the writer's gzip members are made (StreamEngine.deflate)")
     ap.add_argument("--inflate", default="host", choices=["host", "device"], help="where the whole-file load inflates the input (Engine.inflate); not with --stream")
+    ap.add_argument("--parse", default="host", choices=["host", "device"], help="where the whole-file load parses the FASTQ text (Engine.parse); not with --stream")
+    ap.add_argument("--loads", type=int, default=1, help="whole-file load: this many timed loads, the text cache cleared before each (the stages' total counts the last)")
+    ap.add_argument("--in-writer", default="host", choices=["host", "device"], help="who writes the generated in.fastq.gz: the host writer (members of 4 MiB of text) or the device deflate (of 65 535 bytes)")
     ap.add_argument("--check", action="store_true", help="--stream: compare the coordinates with one context on the whole file")
     ap.add_argument("--input-dir", default="", help="keep the generated in.fastq.gz here and use it again when it is there (several arms over one file)")
     args = ap.parse_args()
     if args.inflate == "device" and args.stream:
         ap.error("--inflate device is the whole-file loaders' mode: the streamed loaders inflate on the host (not with --stream)")
+    if args.parse == "device" and args.stream:
+        ap.error("--parse device is the whole-file loaders' mode: the streamed loaders parse on the host (not with --stream)")
     import synth
     from bench import its2_profiles
     from itsxpress_amd import Engine, _lib
-    from itsxpress_amd.trim import write_trimmed_fastq, read_text
+    from itsxpress_amd.trim import write_trimmed_fastq, read_text, cache_clear
     with gzip.open(os.path.join(ROOT, "tests", "golden", "T.hmm.gz"), "rt") as f:
         thmm = f.read()
     if args.shape == "cfg2":
@@ -52,7 +57,7 @@ def main():
     try:
         plain = os.path.join(tmp, "in.fastq")
         bases = np.frombuffer(blob, np.uint8)
-        kept = os.path.join(args.input_dir, "in_%s_%d.fastq.gz" % (args.shape, n)) if args.input_dir else ""
+        kept = os.path.join(args.input_dir, "in_%s_%d%s.fastq.gz" % (args.shape, n, "_dev" if args.in_writer == "device" else "")) if args.input_dir else ""
         if kept and os.path.exists(kept) and os.path.exists(kept + ".size"):
             fq = kept
             in_bytes, in_gz = int(open(kept + ".size").read()), os.path.getsize(fq)
@@ -65,7 +70,15 @@ def main():
             fq = kept or os.path.join(tmp, "in.fastq.gz")
             if kept:
                 os.makedirs(args.input_dir, exist_ok=True)
-            write_trimmed_fastq(plain, fq, np.zeros(n, np.int32), np.full(n, 1 << 30, np.int32), gzipped=True)
+            if args.in_writer == "device":
+                e0 = Engine(0)
+                text = open(plain, "rb").read()
+                with open(fq, "wb") as f:
+                    f.write(e0.deflate_device(text, [0, len(text)])[0])
+                del text
+                e0.close()
+            else:
+                write_trimmed_fastq(plain, fq, np.zeros(n, np.int32), np.full(n, 1 << 30, np.int32), gzipped=True)
             in_bytes, in_gz = os.path.getsize(plain), os.path.getsize(fq)
             os.remove(plain)
             if kept:
@@ -128,10 +141,17 @@ def main():
                 e1.close()
         else:
             eng.inflate = args.inflate
-            t0 = time.perf_counter()
-            eng.load_reads_file(fq)
-            t["load"] = time.perf_counter() - t0
+            eng.parse = args.parse
+            loads, ms_parse = [], []
+            for _ in range(max(1, args.loads)):
+                cache_clear()
+                t0 = time.perf_counter()
+                eng.load_reads_file(fq)
+                t["load"] = time.perf_counter() - t0
+                loads.append(round(t["load"], 3))
+                ms_parse.append(round(eng.stats()["ms_parse"], 1))
             st = eng.stats()
+            extra = {**extra, "parse": args.parse, "load_s": loads, "ms_parse": ms_parse, "parse_texts_device": st["n_parse_device"], "parse_texts_declined": st["n_parse_declined"]}
             extra = {**extra, "inflate": args.inflate, "ms_inflate": round(st["ms_inflate"], 1), "inflate_members": st["n_inflate_members"],
                      "inflate_files_device": st["n_inflate_device"], "inflate_files_declined": st["n_inflate_declined"]}
             t0 = time.perf_counter()
