@@ -702,6 +702,20 @@ int64_t itsx_io_parallel_inflates(void);
 void itsx_io_cache_clear(void);
 
 /* ---- test hooks (parity tests only) */
+/* a hand-made domain table in place of a search's results (tests of the stage that decides every trimmed read: the domain threshold,
+ * ItsPosition's argmax, the compact and lazy rows modes).  Needs loaded profiles and a finished itsx_derep / itsx_cluster.  rows[n_rows]
+ * lie in n_segs segments of seg_rows[s] rows (a segment = the rows one chunk of a search leaves; empty ones allowed).  A row with
+ * dom_idx < 0 is padding and stays as given; every other row must name a representative (rep < n_unique) and a profile (prof <
+ * n_profiles): ITSX_E_ARG otherwise, and the context keeps what it had.  mode = ITSX_ROWS_FULL, ITSX_ROWS_COMPACT (each segment goes
+ * through the compaction a search's chunk goes through, ITSX_COMPACT_ZMAX / ITSX_COMPACT_DOME_MIN honoured) or ITSX_ROWS_LAZY (the rows
+ * are the kept rows).  Afterwards the context is as itsx_search leaves it in that mode, with all [sample][profile] counters zero (twice
+ * as many after lazy) and dom_reported still to be set: itsx_set_domz, then itsx_search_finalize and everything behind it.  Nothing
+ * can be evaluated again: itsx_search_finalize of a lazy table without itsx_set_domz, and itsx_lazy_complete, are ITSX_E_ARG. */
+int itsx_debug_set_domains(itsx_ctx *ctx, const itsx_domain *rows, int64_t n_rows, const int64_t *seg_rows, int32_t n_segs, int mode);
+/* the rows the context holds as they lie in its segments (segment after segment, padding included; after ITSX_ROWS_COMPACT the kept
+ * rows; dom_reported as the last itsx_search_finalize left it, 2 = undecided after a lazy one): returns their number, and copies them
+ * when cap holds them all; negative on error */
+int64_t itsx_debug_get_rows(itsx_ctx *ctx, itsx_domain *rows, int64_t cap);
 /* XXH64 of each read's packed forward / reverse-complement key, as computed on the device */
 int itsx_debug_read_hashes(itsx_ctx *ctx, uint64_t *fwd, uint64_t *rc);
 /* the sample of every read of a batch, [n_reads] each (either may be NULL): as the device kernels see it and as the host-side writers see

@@ -376,6 +376,7 @@ struct itsx_ctx {
 
   // ---- search
   bool have_search = false, have_final = false;
+  bool injected = false;                 // the row table came from itsx_debug_set_domains, not from a search: nothing can be evaluated again
   double T = 10.0;
   int64_t npairs_padded = 0;
   DBuf<PairRec> d_pairs;
@@ -2146,6 +2147,52 @@ static int run_chunks(itsx_ctx *ctx, double T, double F1, double F3)
   return ITSX_OK;
 }
 
+// What a compact / lazy search assumes and keeps per (representative, class): the assumptions (ITSX_COMPACT_ZMAX, ITSX_COMPACT_DOME_MIN),
+// the profiles' classes and the cleared best-certain-row table.  Called by itsx_search and by itsx_debug_set_domains.
+static int compact_setup(itsx_ctx *ctx)
+{
+  hipStream_t st = ctx->st;
+  const int P = ctx->P;
+  ctx->compact_zmax = 1e9; ctx->compact_dome_min = 1e-2;          // hmmsearch's --domE is 10 unless given; 1e9 reported targets per profile is a lot of data
+  if (const char *e = sw_get("ITSX_COMPACT_ZMAX")) ctx->compact_zmax = std::max(1.0, atof(e));
+  if (const char *e = sw_get("ITSX_COMPACT_DOME_MIN")) ctx->compact_dome_min = std::max(1e-300, atof(e));
+  ctx->compact_lnp = log(ctx->compact_dome_min / ctx->compact_zmax) - 1e-6;       // certain: exp(lnP) * Zmax <= domE_min, with room for exp's last bit
+  // classes = the distinct 2-character NAME prefixes (what create_runtime_hmm and ItsPosition select by: 1_ 2_ 3_ 4_)
+  std::vector<int8_t> cls((size_t)P, 0); std::vector<std::string> seen;
+  for (int p = 0; p < P; p++) {
+    const std::string pre = ctx->profs[p].name.substr(0, 2);
+    size_t k = 0; while (k < seen.size() && seen[k] != pre) k++;
+    if (k == seen.size()) seen.push_back(pre);
+    if (k > 126) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "ITSX_COMPACT_ROWS: more than 127 distinct 2-character profile name prefixes");
+    cls[p] = (int8_t)k;
+  }
+  ctx->compact_ncls = (int)seen.size();
+  HIPCHK(upload(ctx->w_cls, cls, st));
+  HIPCHK(ctx->w_bestc.alloc((size_t)ctx->U * ctx->compact_ncls + 1));
+  HIPCHK(hipMemsetAsync(ctx->w_bestc.p, 0, ((size_t)ctx->U * ctx->compact_ncls + 1) * sizeof(unsigned long long), st));
+  return ITSX_OK;
+}
+
+// The compaction of one segment of domain rows (a search's chunk, or a segment handed to itsx_debug_set_domains): of the NR rows at d_rows
+// keep what can still win once domZ is known (k_compact_*), in row order, in dom_bufs[di]; the best certain rows accumulate in w_bestc
+static int compact_segment(itsx_ctx *ctx, const itsx_domain *d_rows, int64_t NR, size_t di)
+{
+  hipStream_t st = ctx->st;
+  launch_compact_best(d_rows, NR, ctx->w_cls.p, ctx->compact_ncls, ctx->compact_lnp, ctx->w_bestc.p, st);
+  HIPCHK(ctx->w_keep.alloc((size_t)NR + 1)); HIPCHK(ctx->w_keeppos.alloc((size_t)NR + 1)); HIPCHK(ctx->w_keeptmp.alloc((size_t)scan_tmp_elems(NR + 1)));
+  launch_compact_mark(d_rows, NR, ctx->w_cls.p, ctx->compact_ncls, ctx->compact_lnp, ctx->w_bestc.p, ctx->w_keep.p, st);
+  launch_exclusive_scan(ctx->w_keep.p, ctx->w_keeppos.p, NR + 1, ctx->w_keeptmp.p, st);
+  int32_t kept = 0;
+  HIPCHK(hipMemcpyAsync(&kept, ctx->w_keeppos.p + NR, sizeof(kept), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  DBuf<itsx_domain> &small = *ctx->dom_bufs[di];
+  HIPCHK(small.alloc((size_t)std::max<int32_t>(kept, 1), true));
+  launch_compact_scatter(d_rows, NR, ctx->w_keep.p, ctx->w_keeppos.p, small.p, st);
+  ctx->rows_before_compaction += NR;
+  ctx->dom_n[di] = kept;
+  return ITSX_OK;
+}
+
 int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
 {
   CTXCHK(ctx);
@@ -2163,7 +2210,7 @@ int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
   S.n_pairs = (int64_t)U * P; S.n_past_msv = S.n_past_bias = S.n_past_fwd = S.n_regions = S.n_multidomain = S.n_domains = S.n_domain_overflow = 0;
   S.ms_msv = S.ms_filters = S.ms_domains = S.ms_msv_kernel = S.ms_fwd_kernel = S.ms_bwd_kernel = S.ms_env_kernel = S.ms_bias_kernel = S.ms_decode_kernel = 0; S.n_batches = 0; S.ms_ensemble = 0; S.n_mr_clustered = S.n_mr_distinct = S.n_mr_failed = S.n_mr_envelopes = 0; S.n_slab_shrinks = 0; S.n_mr_overflow = 0; S.ms_vit_kernel = 0; for (int k = 0; k < 8; k++) S.n_mr_fail_kind[k] = 0; S.n_rows_resident = 0; S.msv_cells = 0; S.msv_launches = 0; S.fwd_rows = 0; S.env_rows = 0; S.n_env_unique = 0;
   ctx->npairs_padded = 0; ctx->dom_n.clear(); ctx->trace_u0 = 0; ctx->n_chunks = 0;
-  ctx->have_search = true; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false;
+  ctx->have_search = true; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->injected = false;
   // rows mode: what the caller selected (itsx_set_rows_mode), else the environment (ITSX_ROWS=full|compact|lazy; ITSX_COMPACT_ROWS=1)
   int mode = ctx->rows_mode;
   if (mode < 0) {
@@ -2179,25 +2226,7 @@ int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
   if (ctx->compact_rows)                    // a full table of an earlier search (80 B x ~130 per representative) goes back to the device
     for (auto &b : ctx->dom_bufs) if (b && b->cap * sizeof(itsx_domain) > ((size_t)256 << 20)) b->release();
   S.lazy = ctx->lazy; S.n_lazy_evaluated = S.n_lazy_round1 = S.n_lazy_pending = S.n_lazy_reruns = 0; S.n_lazy_completed = S.n_lazy_completed_profiles = S.n_lazy_pending_profiles = 0; S.ms_lazy_complete = 0; S.lazy_bound_maxdiff = 0; S.ms_bound_kernel = S.ms_lazy_select = 0; S.bound_rows = 0; S.n_bound_launches = 0; S.n_lazy_topup = 0; S.ms_lazy_topup = 0; S.ms_lazy_topup_stages = 0;
-  if (ctx->compact_rows && U > 0) {
-    ctx->compact_zmax = 1e9; ctx->compact_dome_min = 1e-2;          // hmmsearch's --domE is 10 unless given; 1e9 reported targets per profile is a lot of data
-    if (const char *e = sw_get("ITSX_COMPACT_ZMAX")) ctx->compact_zmax = std::max(1.0, atof(e));
-    if (const char *e = sw_get("ITSX_COMPACT_DOME_MIN")) ctx->compact_dome_min = std::max(1e-300, atof(e));
-    ctx->compact_lnp = log(ctx->compact_dome_min / ctx->compact_zmax) - 1e-6;       // certain: exp(lnP) * Zmax <= domE_min, with room for exp's last bit
-    // classes = the distinct 2-character NAME prefixes (what create_runtime_hmm and ItsPosition select by: 1_ 2_ 3_ 4_)
-    std::vector<int8_t> cls((size_t)P, 0); std::vector<std::string> seen;
-    for (int p = 0; p < P; p++) {
-      const std::string pre = ctx->profs[p].name.substr(0, 2);
-      size_t k = 0; while (k < seen.size() && seen[k] != pre) k++;
-      if (k == seen.size()) seen.push_back(pre);
-      if (k > 126) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "ITSX_COMPACT_ROWS: more than 127 distinct 2-character profile name prefixes");
-      cls[p] = (int8_t)k;
-    }
-    ctx->compact_ncls = (int)seen.size();
-    HIPCHK(upload(ctx->w_cls, cls, st));
-    HIPCHK(ctx->w_bestc.alloc((size_t)ctx->U * ctx->compact_ncls + 1));
-    HIPCHK(hipMemsetAsync(ctx->w_bestc.p, 0, ((size_t)ctx->U * ctx->compact_ncls + 1) * sizeof(unsigned long long), st));
-  }
+  if (ctx->compact_rows && U > 0) { const int rc = compact_setup(ctx); if (rc != ITSX_OK) return rc; }
   if (U == 0) return ITSX_OK;
 
   // ---- per-length constants (host libm, as hmmsearch computes them per target)
@@ -2859,19 +2888,8 @@ static int domain_pipeline(itsx_ctx *ctx, const PairList &pl, const int32_t *d_s
     sa.domz = ctx->d_domz32.p; sa.usample = ctx->dev_usample(); sa.P = ctx->P;
     launch_score(sa, st);
     if (ctx->compact_rows) {
-      // keep what can still win once domZ is known (k_compact_*), in row order; the chunk's full rows are scratch
-      launch_compact_best(d_dom.p, NR, ctx->w_cls.p, ctx->compact_ncls, ctx->compact_lnp, ctx->w_bestc.p, st);
-      HIPCHK(ctx->w_keep.alloc((size_t)NR + 1)); HIPCHK(ctx->w_keeppos.alloc((size_t)NR + 1)); HIPCHK(ctx->w_keeptmp.alloc((size_t)scan_tmp_elems(NR + 1)));
-      launch_compact_mark(d_dom.p, NR, ctx->w_cls.p, ctx->compact_ncls, ctx->compact_lnp, ctx->w_bestc.p, ctx->w_keep.p, st);
-      launch_exclusive_scan(ctx->w_keep.p, ctx->w_keeppos.p, NR + 1, ctx->w_keeptmp.p, st);
-      int32_t kept = 0;
-      HIPCHK(hipMemcpyAsync(&kept, ctx->w_keeppos.p + NR, sizeof(kept), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      DBuf<itsx_domain> &small = *ctx->dom_bufs[di];
-      HIPCHK(small.alloc((size_t)std::max<int32_t>(kept, 1), true));
-      launch_compact_scatter(d_dom.p, NR, ctx->w_keep.p, ctx->w_keeppos.p, small.p, st);
-      ctx->rows_before_compaction += NR;
-      ctx->dom_n[di] = kept;
+      // keep what can still win once domZ is known, in row order; the chunk's full rows are scratch
+      { const int rc = compact_segment(ctx, d_dom.p, NR, di); if (rc != ITSX_OK) return rc; }
     }
   }
   S.ms_domains += tm_dom.stop();
@@ -3482,6 +3500,7 @@ int itsx_lazy_complete(itsx_ctx *ctx, const int32_t *flags)
 {
   CTXCHK(ctx && flags && ctx->have_search);
   if (!ctx->lazy) SET_ERR(ctx, ITSX_E_ARG, "itsx_lazy_complete: the last search was not a lazy one");
+  if (ctx->injected) SET_ERR(ctx, ITSX_E_ARG, "itsx_lazy_complete: the row table was handed in (itsx_debug_set_domains): there are no pairs to evaluate");
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->st;
   const int P = ctx->P;
@@ -3554,6 +3573,89 @@ int itsx_domz_device(itsx_ctx *ctx, int64_t **d_domz, int64_t *n)
   *d_domz = ctx->d_domz64.p;
   if (n) *n = (int64_t)mm;
   return ITSX_OK;
+}
+
+// Test hook: a hand-made domain table in place of a search's results.  rows[n_rows] in n_segs segments of seg_rows[s] rows each (a
+// segment = what one chunk of a search leaves; empty ones are allowed); rows with dom_idx < 0 are padding and stay as given, every
+// other row names a representative of the finished dereplication and a loaded profile.  mode = ITSX_ROWS_FULL: the segments stay as
+// they are; ITSX_ROWS_COMPACT: each goes through compact_segment, as a chunk does; ITSX_ROWS_LAZY: they are the rows a lazy search
+// kept.  The counters ([S][P], twice that for lazy) are zero: the caller gives them with itsx_set_domz, then itsx_search_finalize.
+int itsx_debug_set_domains(itsx_ctx *ctx, const itsx_domain *rows, int64_t n_rows, const int64_t *seg_rows, int32_t n_segs, int mode)
+{
+  CTXCHK(ctx);
+  if (!ctx->have_derep) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_set_domains called before itsx_derep / itsx_cluster");
+  if (ctx->P <= 0) SET_ERR(ctx, ITSX_E_ARG, "no profiles loaded");
+  if (mode < ITSX_ROWS_FULL || mode > ITSX_ROWS_LAZY) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_set_domains: mode must be 0 (full), 1 (compact) or 2 (lazy)");
+  if (n_rows < 0 || n_segs < 0 || (n_rows > 0 && !rows) || (n_segs > 0 && !seg_rows)) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_set_domains: missing arrays");
+  int64_t sum = 0;
+  for (int32_t s = 0; s < n_segs; s++) {
+    if (seg_rows[s] < 0 || seg_rows[s] > (int64_t)INT32_MAX - 4096) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_set_domains: segment " + std::to_string(s) + " has a row count outside [0, 2^31 - 4096]");
+    sum += seg_rows[s];
+  }
+  if (sum != n_rows) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_set_domains: the segments hold " + std::to_string(sum) + " rows, " + std::to_string(n_rows) + " were given");
+  for (int64_t i = 0; i < n_rows; i++) {
+    const itsx_domain &d = rows[i];
+    if (d.dom_idx < 0) continue;
+    if (d.rep < 0 || d.rep >= ctx->U) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_set_domains: row " + std::to_string(i) + " names representative " + std::to_string(d.rep) + " of " + std::to_string(ctx->U));
+    if (d.prof < 0 || d.prof >= ctx->P) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_set_domains: row " + std::to_string(i) + " names profile " + std::to_string(d.prof) + " of " + std::to_string(ctx->P));
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  const size_t m = (size_t)ctx->P * ctx->S;
+  ctx->switches_at_search = sw_report();
+  ctx->h_dom.clear(); ctx->h_trace.clear(); ctx->trace_sorted = false;
+  ctx->domz.assign(m, 0); ctx->domz_ub.assign(m, 0); ctx->domz_loc.assign(m, 0); ctx->domz_ub_loc.assign(m, 0);
+  ctx->npairs_padded = 0; ctx->dom_n.clear(); ctx->n_chunks = n_segs;
+  ctx->have_search = false; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->injected = true;
+  ctx->compact_rows = mode != ITSX_ROWS_FULL; ctx->lazy = mode == ITSX_ROWS_LAZY;
+  ctx->lazy_pending = 0; ctx->domz_exchanged = false; ctx->lazy_pending_prof.clear();
+  itsx_stats &S = ctx->stats;
+  S.lazy = ctx->lazy; S.n_domains = 0; S.n_lazy_pending = S.n_lazy_reruns = S.n_lazy_topup = S.n_lazy_completed = S.n_lazy_completed_profiles = S.n_lazy_pending_profiles = 0;
+  for (int64_t i = 0; i < n_rows; i++) S.n_domains += rows[i].dom_idx >= 0;
+  HIPCHK(ctx->d_domz32.alloc(std::max<size_t>(m, 1)));
+  HIPCHK(hipMemsetAsync(ctx->d_domz32.p, 0, std::max<size_t>(m, 1) * 4, st));
+  if (ctx->compact_rows) { const int rc = compact_setup(ctx); if (rc != ITSX_OK) return rc; }
+  int64_t o = 0;
+  for (int32_t s = 0; s < n_segs; s++) {
+    const size_t di = ctx->dom_n.size();
+    const int64_t NR = seg_rows[s];
+    ctx->dom_n.push_back(0);
+    while (ctx->dom_bufs.size() <= di) ctx->dom_bufs.emplace_back(new DBuf<itsx_domain>());
+    if (NR > 0) {
+      DBuf<itsx_domain> &d_dom = mode == ITSX_ROWS_COMPACT ? ctx->w_domscratch : *ctx->dom_bufs[di];
+      HIPCHK(d_dom.alloc((size_t)NR));
+      HIPCHK(hipMemcpyAsync(d_dom.p, rows + o, (size_t)NR * sizeof(itsx_domain), hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));
+      ctx->dom_n[di] = NR;
+      if (mode == ITSX_ROWS_COMPACT) { const int rc = compact_segment(ctx, d_dom.p, NR, di); if (rc != ITSX_OK) return rc; }
+    }
+    o += NR;
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  S.n_rows_resident = 0;
+  for (int64_t r : ctx->dom_n) S.n_rows_resident += r;
+  ctx->have_search = true;
+  return ITSX_OK;
+}
+
+// Test hook: the rows the context holds as they lie in its segments (segment after segment, padding rows included, dom_reported as the
+// last finalize left it -- 2 = undecided after a lazy one): the count; the rows too when cap holds them all.  Negative on error.
+int64_t itsx_debug_get_rows(itsx_ctx *ctx, itsx_domain *rows, int64_t cap)
+{
+  if (!ctx || !ctx->have_search) return ITSX_E_ARG;
+  int64_t n = 0;
+  for (int64_t r : ctx->dom_n) n += std::max<int64_t>(r, 0);
+  if (!rows || cap < n) return n;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  int64_t o = 0;
+  for (size_t c = 0; c < ctx->dom_n.size(); c++) {
+    if (ctx->dom_n[c] <= 0) continue;
+    HIPCHK(hipMemcpy(rows + o, ctx->dom_bufs[c]->p, (size_t)ctx->dom_n[c] * sizeof(itsx_domain), hipMemcpyDeviceToHost));
+    o += ctx->dom_n[c];
+  }
+  return n;
 }
 
 // thresholds of a lazy search: rows both bounds decide alike are final; ctx->lazy_pending = undecided rows that could matter
@@ -3775,6 +3877,8 @@ int itsx_search_finalize(itsx_ctx *ctx, double domE)
 {
   CTXCHK(ctx && ctx->have_search);
   HIPCHK(hipSetDevice(ctx->device));
+  if (ctx->injected && ctx->lazy && !ctx->domz_exchanged)
+    SET_ERR(ctx, ITSX_E_ARG, "itsx_search_finalize: a lazy row table that was handed in (itsx_debug_set_domains) has no counters of its own: give both bounds with itsx_set_domz first");
   StageTimer tm(ctx->st);
   ctx->h_dom.clear();
   auto check_compaction = [&](const std::vector<int64_t> &z) -> int {       // the rows were thinned out under two assumptions: check them against what finalize was given

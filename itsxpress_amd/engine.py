@@ -769,6 +769,27 @@ class Engine:
         return dict(line.split("=", 1) for line in buf.value.decode().split("\n") if "=" in line)
 
     # ---- test hooks
+    def debug_set_domains(self, rows, seg_rows=None, mode="full"):
+        """a hand-made domain table (DOMAIN_DTYPE rows, in segments of seg_rows rows; None: one segment) in place of a search's
+        results, in rows mode "full" / "compact" / "lazy": then set_domz(), finalize() and everything behind them"""
+        rows = np.ascontiguousarray(rows, DOMAIN_DTYPE)
+        seg = np.ascontiguousarray([len(rows)] if seg_rows is None else seg_rows, np.int64)
+        m = {"full": 0, "compact": 1, "lazy": 2}.get(mode, mode)
+        self._chk(self.L.itsx_debug_set_domains(self.h, rows.ctypes.data if rows.size else None, len(rows),
+                                                seg.ctypes.data if seg.size else None, len(seg), int(m)))
+
+    def debug_get_rows(self):
+        """the rows the context holds as they lie in its segments (padding included; the kept rows after "compact"; dom_reported as the
+        last finalize() left it, 2 = undecided after a lazy one)"""
+        n = int(self.L.itsx_debug_get_rows(self.h, None, 0))
+        if n < 0:
+            raise EngineError(n, self.L.itsx_last_error(self.h).decode())
+        out = np.zeros(max(n, 1), DOMAIN_DTYPE)
+        got = int(self.L.itsx_debug_get_rows(self.h, out.ctypes.data, n))
+        if got != n:
+            raise EngineError(min(got, -1), self.L.itsx_last_error(self.h).decode())
+        return out[:n]
+
     def debug_read_hashes(self):
         f = np.zeros(self.n_reads, np.uint64)
         r = np.zeros(self.n_reads, np.uint64)
