@@ -145,6 +145,22 @@ int64_t      orc_results_ntrace(const orc_results *r);
 const orc_pairtrace *orc_results_trace(const orc_results *r);
 void         orc_results_counts(const orc_results *r, int64_t *out5);
 
+/* ---- the multidomain ensemble stage, opened up for tests (tests/ensemble_exact.py); the search itself records nothing ----
+ * one step of a sampled path: the state before and after it, and k, i as they stand right after it (before the N/J/C loop's
+ * decrement of i); ndraw = the generator calls the step made (1; more when a choice fell back to its uniform draws; 0 in N) */
+typedef struct { int32_t trace, s0, s1, k, i, ndraw; } orc_ens_step;
+typedef struct orc_ens_debug orc_ens_debug;
+/* codes: the target's L digital codes (no sentinels).  One pair, single-threaded, every filter passed. */
+orc_ens_debug *orc_ensemble_debug(const orc_hmmset *hs, int prof, const uint8_t *codes, int L);
+int   orc_ens_nregions(const orc_ens_debug *g);
+void  orc_ens_region(const orc_ens_debug *g, int r, int64_t *out5 /* ireg, jreg, generator start state, steps, envelopes */);
+const orc_ens_step *orc_ens_steps(const orc_ens_debug *g, int r);      /* all 200 paths, in order */
+const float *orc_ens_n2sc(const orc_ens_debug *g, int r);              /* [jreg - ireg + 1], after the logf */
+const int   *orc_ens_envs(const orc_ens_debug *g, int r);              /* [envelopes][2], absolute, ordered by start */
+void  orc_ens_free(orc_ens_debug *g);
+/* p7_spensemble_Cluster alone: n (trace, i, j, k, m) tuples out of 200 paths, a trace's tuples adjacent -> envelopes */
+int   orc_spensemble_cluster(const int32_t *tuples, int n, int32_t *env /*[cap][2]*/, int cap);
+
 /* ItsPosition semantics on thresholded results: -1 = None. left/right given by name prefixes. */
 void orc_positions(const orc_results *r, const orc_hmmset *hs, int64_t nseq,
                    const char *leftprefix, const char *rightprefix,

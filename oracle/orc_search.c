@@ -537,7 +537,9 @@ static void res_push_trace(orc_results *r, const orc_pairtrace *t)
   r->trace[r->n_trace++] = *t;
 }
 
+struct orc_ens_debug;
 typedef struct {
+  struct orc_ens_debug *dbg;    /* orc_ensemble_debug's sink; NULL in the search */
   xrow *xf, *xb, *ef, *eb;      /* parser specials; envelope specials */
   float *btot, *etot, *mocc, *n2sc;
   v4 *frows, *brows;            /* envelope M/I rows */
@@ -678,16 +680,31 @@ static int fchoose(orc_rng *r, const float *pv, int n)
 enum { ST_M = 1, ST_D, ST_I, ST_S, ST_N, ST_B, ST_E, ST_C, ST_T, ST_J };
 typedef struct { int idx, i, j, k, m; float prob; } spcoord;
 
+/* what orc_ensemble_debug hands out (tests/ensemble_exact.py replays it against a float64 model): every step of every sampled
+ * path, and per region its bounds, the generator's start state, the per-residue null2 scores and the envelopes */
+typedef struct { orc_ens_step *v; int64_t n, cap; int trace; } ens_rec;
+typedef struct { int ireg, jreg, nenv; uint32_t rng0; int64_t step0, nstep; float *n2sc; int *env; } ens_region;
+struct orc_ens_debug { ens_rec rec; ens_region *reg; int nreg, capreg; };
+static void rec_push(ens_rec *rec, int s0, int s1, int k, int i, uint32_t x0, uint32_t x1)
+{
+  if (rec->n == rec->cap) { rec->cap = rec->cap ? 2 * rec->cap : 4096; rec->v = (orc_ens_step *)realloc(rec->v, sizeof(orc_ens_step) * rec->cap); }
+  int nd = 0;
+  while (x0 != x1) { x0 = x0 * 69069u + 1u; nd++; }          /* the draws of this step: the generator is stepped until it arrives */
+  orc_ens_step *e = &rec->v[rec->n++];
+  e->trace = rec->trace; e->s0 = s0; e->s1 = s1; e->k = k; e->i = i; e->ndraw = nd;
+}
+
 #define FULLV(row, q, s) full[((size_t)(row) * Q + (q)) * 3 + (s)]      /* s: 0 M, 1 D, 2 I */
 #define TFVQ(idx) v4_ld(p->tfv + (size_t)(idx) * 4)
 /* sample one path through the region's Forward matrix; reports its domains last-first through cb arrays */
 static int stochastic_trace(orc_rng *rng, const orc_profile *p, const v4 *full, const xrow *xf, int Lr, float pmove, float ploop,
-                            int *dfrom, int *dto, int *dk, int *dm, float *cntM /*[ndom][Q*4]*/, float *cntI, int maxdom)
+                            int *dfrom, int *dto, int *dk, int *dm, float *cntM /*[ndom][Q*4]*/, float *cntI, int maxdom, ens_rec *rec)
 {
   const int Q = p->Q;
   int i = Lr, k = 0, s0 = ST_C, s1, nd = 0, cur = -1;
   while (s0 != ST_S) {
     float path[4];
+    const uint32_t x0 = rec ? rng->x : 0u;
     switch (s0) {
     case ST_M: {
       const int q = (k - 1) % Q, r = (k - 1) / Q;
@@ -768,6 +785,7 @@ static int stochastic_trace(orc_rng *rng, const orc_profile *p, const v4 *full, 
       break;
     default: return -3;
     }
+    if (rec) rec_push(rec, s0, s1, k, i, x0, rng->x);
     /* the appended state (s1, k, i): match and insert states carry the coordinates p7_trace_Index / p7_Null2_ByTrace read */
     if (s1 == ST_M) {
       if (dto[cur] == 0) { dto[cur] = i; dm[cur] = k; }     /* first seen = last in the path */
@@ -800,8 +818,6 @@ static int link_samples(const spcoord *h1, const spcoord *h2)
   return 0;
 }
 
-/* region ireg..jreg of dsq[1..L]: fills n2sc[ireg..jreg] and returns the cluster envelopes (absolute coordinates),
- * ordered by start; ret < 0 if the ensemble could not be sampled (the region then yields no envelope) */
 /* regions that ran into one of the bookkeeping limits below, by kind (the engine's MrOut.status codes): 1 unsampleable matrix,
  * 2 more than 8 domains in one path, 4 more than 512 distinct tuples, 6 more than 32 clusters, 7 more than 4 envelopes */
 static long long g_mr_fail_kind[8];
@@ -814,70 +830,10 @@ static void mr_fail(int kind)
 #pragma omp atomic
   g_mr_fail_kind[kind]++;
 }
-static int region_trace_ensemble(const orc_profile *p, const uint8_t *dsq, int L, int ireg, int jreg, workspace *w, int **env_i, int **env_j, int *envcap)
+/* p7_spensemble_Cluster on the sampled (trace, i, j, k, m) tuples (each trace's tuples adjacent): the envelopes, ordered by start;
+ * span bounds every coordinate (the end point histograms' size) */
+static int cluster_samples(const spcoord *sp, int n, int nsamples, int span, int **env_i, int **env_j, int *envcap)
 {
-  const int Q = p->Q, Lr = jreg - ireg + 1, nsamples = 200;
-  const float pmove = (2.0f + 1.0f) / ((float)L + 2.0f + 1.0f), ploop = 1.0f - pmove;   /* multihit, length model of the whole target */
-  float fsc;
-  fwd_engine_x(p, dsq + ireg - 1, Lr, pmove, ploop, 0.5f, 0.5f, w->ef, NULL, w->full, &fsc);
-  for (int pos = ireg; pos <= jreg; pos++) w->n2sc[pos] = 0.0f;
-  orc_rng rng; rng_init(&rng, 42);
-  /* no bookkeeping limit, as in hmmsearch (p7_domaindef.c / p7_spensemble.c grow their lists): a path of a region of Lr residues
-   * has at most Lr domains; every list below is sized by that or grows.  (Until round 3 the device kernel's fixed sizes -- 8 domains
-   * per path, 512 distinct tuples, 4 envelopes -- were mirrored here; its overflow path has none.)  What remains is what makes
-   * hmmsearch itself throw: a matrix that cannot be sampled (kinds 1 and 5 below). */
-  const int MAXD = Lr + 1;
-  int *dfrom = (int *)malloc(sizeof(int) * 4 * (size_t)MAXD), *dto = dfrom + MAXD, *dk = dto + MAXD, *dm = dk + MAXD;
-  float *cntM = (float *)malloc(sizeof(float) * (size_t)MAXD * QMAX * 4 * 2), *cntI = cntM + (size_t)MAXD * QMAX * 4;
-  int cap = 1024, n = 0;
-  spcoord *sp = (spcoord *)malloc(sizeof(spcoord) * cap);
-  const uint8_t *degen = orc_degen_table();
-  int bad = 0;
-  for (int t = 0; t < nsamples && !bad; t++) {
-    const int nd = stochastic_trace(&rng, p, w->full, w->ef, Lr, pmove, ploop, dfrom, dto, dk, dm, cntM, cntI, MAXD);
-    if (nd < 0) { bad = 1; mr_fail(nd == -2 ? 2 : nd == -3 ? 5 : 1); break; }
-    int hi = Lr;                                   /* positions above hi have had their contribution of this trace */
-    for (int d = 0; d < nd; d++) {                 /* domains last-first */
-      if (n == cap) { cap *= 2; sp = (spcoord *)realloc(sp, sizeof(spcoord) * cap); }
-      sp[n].idx = t; sp[n].i = dfrom[d] + ireg - 1; sp[n].j = dto[d] + ireg - 1; sp[n].k = dk[d]; sp[n].m = dm[d]; sp[n].prob = 0.f; n++;
-      /* p7_Null2_ByTrace over the domain's B..E segment: only match and insert states emit there */
-      const float *cm = cntM + (size_t)d * QMAX * 4, *ci = cntI + (size_t)d * QMAX * 4;
-      int Ld = 0;
-      for (int z = 0; z < Q * 4; z++) Ld += (int)cm[z] + (int)ci[z];
-      const float norm = (float)(1.0 / (double)(float)Ld);
-      float null2[ORC_KP];
-      const float xfactor = (0.0f * norm + 0.0f * norm) + 0.0f * norm;
-      for (int x = 0; x < 4; x++) {
-        v4 sv = v4_zero();
-        const float *rp = p->rfv + (size_t)x * Q * 4;
-        for (int q = 0; q < Q; q++) {
-          v4 mv = v4_mul(v4_ld(cm + q * 4), v4_set1(norm)), iv = v4_mul(v4_ld(ci + q * 4), v4_set1(norm));
-          sv = v4_add(sv, v4_mul(mv, v4_ld(rp))); rp += 4;
-          sv = v4_add(sv, iv);
-        }
-        null2[x] = v4_hsum(sv);
-        null2[x] += xfactor;
-      }
-      for (int x = 5; x <= 15; x++) {
-        float result = 0.f; int ndg = 0;
-        for (int y = 0; y < 4; y++) if (degen[x] & (1 << y)) { result += null2[y]; ndg++; }
-        null2[x] = result / (float)ndg;
-      }
-      null2[4] = null2[16] = null2[17] = 1.0f;
-      /* as published: residues up to AND INCLUDING the domain's first one count as outside (+1), the rest of it by null2 */
-      for (int pos = hi; pos > dto[d]; pos--) w->n2sc[ireg + pos - 1] += 1.0f;
-      for (int pos = dto[d]; pos > dfrom[d]; pos--) w->n2sc[ireg + pos - 1] += null2[dsq[ireg + pos - 1]];
-      hi = dfrom[d];
-    }
-    for (int pos = hi; pos >= 1; pos--) w->n2sc[ireg + pos - 1] += 1.0f;
-  }
-  if (bad) {          /* HMMER would have thrown; keep the region without envelopes and without a null2 correction */
-    for (int pos = ireg; pos <= jreg; pos++) w->n2sc[pos] = 0.0f;
-    free(cntM); free(sp); free(dfrom);
-    return -1;
-  }
-  for (int pos = ireg; pos <= jreg; pos++) w->n2sc[pos] = orc_logf(w->n2sc[pos] / (float)nsamples);
-
   /* single-linkage clustering of the sampled (i, j, k, m); components numbered by their smallest member */
   int *comp = (int *)malloc(sizeof(int) * (n + 1)), *stack = (int *)malloc(sizeof(int) * (n + 1));
   for (int h = 0; h < n; h++) comp[h] = -1;
@@ -893,7 +849,7 @@ static int region_trace_ensemble(const orc_profile *p, const uint8_t *dsq, int L
   }
   spcoord *sig = (spcoord *)malloc(sizeof(spcoord) * (nc + 1));
   int nsig = 0;
-  int *epc = (int *)malloc(sizeof(int) * (L + p->M + 8));
+  int *epc = (int *)malloc(sizeof(int) * (span + 8));
   for (int c = 0; c < nc; c++) {
     int ninc = 0, last = -1;
     for (int h = 0; h < n; h++) if (comp[h] == c) { if (sp[h].idx != last) ninc++; last = sp[h].idx; }
@@ -948,11 +904,94 @@ static int region_trace_ensemble(const orc_profile *p, const uint8_t *dsq, int L
       if ((float)nov / (float)nn >= 0.8f) { if (sig[d].prob > sig[d2].prob) dominated[d2] = 1; else dominated[d] = 1; }
     }
   int ne = 0;
-  for (int d = 0; d < nsig && !bad; d++) if (!dominated[d]) {
+  for (int d = 0; d < nsig; d++) if (!dominated[d]) {
     if (ne >= *envcap) { *envcap = 2 * *envcap + 8; *env_i = (int *)realloc(*env_i, sizeof(int) * *envcap); *env_j = (int *)realloc(*env_j, sizeof(int) * *envcap); }
     (*env_i)[ne] = sig[d].i; (*env_j)[ne] = sig[d].j; ne++;
   }
-  free(dominated); free(epc); free(sig); free(comp); free(stack); free(cntM); free(sp); free(dfrom);
+  free(dominated); free(epc); free(sig); free(comp); free(stack);
+  return ne;
+}
+
+/* region ireg..jreg of dsq[1..L]: fills n2sc[ireg..jreg] and returns the cluster envelopes (absolute coordinates),
+ * ordered by start; ret < 0 if the ensemble could not be sampled (the region then yields no envelope) */
+static int region_trace_ensemble(const orc_profile *p, const uint8_t *dsq, int L, int ireg, int jreg, workspace *w, int **env_i, int **env_j, int *envcap)
+{
+  const int Q = p->Q, Lr = jreg - ireg + 1, nsamples = 200;
+  const float pmove = (2.0f + 1.0f) / ((float)L + 2.0f + 1.0f), ploop = 1.0f - pmove;   /* multihit, length model of the whole target */
+  float fsc;
+  fwd_engine_x(p, dsq + ireg - 1, Lr, pmove, ploop, 0.5f, 0.5f, w->ef, NULL, w->full, &fsc);
+  for (int pos = ireg; pos <= jreg; pos++) w->n2sc[pos] = 0.0f;
+  orc_rng rng; rng_init(&rng, 42);
+  ens_rec *rec = w->dbg ? &w->dbg->rec : NULL;
+  const uint32_t rng0 = rng.x; const int64_t step0 = rec ? rec->n : 0;
+  /* no bookkeeping limit, as in hmmsearch (p7_domaindef.c / p7_spensemble.c grow their lists): a path of a region of Lr residues
+   * has at most Lr domains; every list below is sized by that or grows.  (Until round 3 the device kernel's fixed sizes -- 8 domains
+   * per path, 512 distinct tuples, 4 envelopes -- were mirrored here; its overflow path has none.)  What remains is what makes
+   * hmmsearch itself throw: a matrix that cannot be sampled (kinds 1 and 5 below). */
+  const int MAXD = Lr + 1;
+  int *dfrom = (int *)malloc(sizeof(int) * 4 * (size_t)MAXD), *dto = dfrom + MAXD, *dk = dto + MAXD, *dm = dk + MAXD;
+  float *cntM = (float *)malloc(sizeof(float) * (size_t)MAXD * QMAX * 4 * 2), *cntI = cntM + (size_t)MAXD * QMAX * 4;
+  int cap = 1024, n = 0;
+  spcoord *sp = (spcoord *)malloc(sizeof(spcoord) * cap);
+  const uint8_t *degen = orc_degen_table();
+  int bad = 0;
+  for (int t = 0; t < nsamples && !bad; t++) {
+    if (rec) rec->trace = t;
+    const int nd = stochastic_trace(&rng, p, w->full, w->ef, Lr, pmove, ploop, dfrom, dto, dk, dm, cntM, cntI, MAXD, rec);
+    if (nd < 0) { bad = 1; mr_fail(nd == -2 ? 2 : nd == -3 ? 5 : 1); break; }
+    int hi = Lr;                                   /* positions above hi have had their contribution of this trace */
+    for (int d = 0; d < nd; d++) {                 /* domains last-first */
+      if (n == cap) { cap *= 2; sp = (spcoord *)realloc(sp, sizeof(spcoord) * cap); }
+      sp[n].idx = t; sp[n].i = dfrom[d] + ireg - 1; sp[n].j = dto[d] + ireg - 1; sp[n].k = dk[d]; sp[n].m = dm[d]; sp[n].prob = 0.f; n++;
+      /* p7_Null2_ByTrace over the domain's B..E segment: only match and insert states emit there */
+      const float *cm = cntM + (size_t)d * QMAX * 4, *ci = cntI + (size_t)d * QMAX * 4;
+      int Ld = 0;
+      for (int z = 0; z < Q * 4; z++) Ld += (int)cm[z] + (int)ci[z];
+      const float norm = (float)(1.0 / (double)(float)Ld);
+      float null2[ORC_KP];
+      const float xfactor = (0.0f * norm + 0.0f * norm) + 0.0f * norm;
+      for (int x = 0; x < 4; x++) {
+        v4 sv = v4_zero();
+        const float *rp = p->rfv + (size_t)x * Q * 4;
+        for (int q = 0; q < Q; q++) {
+          v4 mv = v4_mul(v4_ld(cm + q * 4), v4_set1(norm)), iv = v4_mul(v4_ld(ci + q * 4), v4_set1(norm));
+          sv = v4_add(sv, v4_mul(mv, v4_ld(rp))); rp += 4;
+          sv = v4_add(sv, iv);
+        }
+        null2[x] = v4_hsum(sv);
+        null2[x] += xfactor;
+      }
+      for (int x = 5; x <= 15; x++) {
+        float result = 0.f; int ndg = 0;
+        for (int y = 0; y < 4; y++) if (degen[x] & (1 << y)) { result += null2[y]; ndg++; }
+        null2[x] = result / (float)ndg;
+      }
+      null2[4] = null2[16] = null2[17] = 1.0f;
+      /* as published: residues up to AND INCLUDING the domain's first one count as outside (+1), the rest of it by null2 */
+      for (int pos = hi; pos > dto[d]; pos--) w->n2sc[ireg + pos - 1] += 1.0f;
+      for (int pos = dto[d]; pos > dfrom[d]; pos--) w->n2sc[ireg + pos - 1] += null2[dsq[ireg + pos - 1]];
+      hi = dfrom[d];
+    }
+    for (int pos = hi; pos >= 1; pos--) w->n2sc[ireg + pos - 1] += 1.0f;
+  }
+  if (bad) {          /* HMMER would have thrown; keep the region without envelopes and without a null2 correction */
+    for (int pos = ireg; pos <= jreg; pos++) w->n2sc[pos] = 0.0f;
+    free(cntM); free(sp); free(dfrom);
+    return -1;
+  }
+  for (int pos = ireg; pos <= jreg; pos++) w->n2sc[pos] = orc_logf(w->n2sc[pos] / (float)nsamples);
+
+  const int ne = cluster_samples(sp, n, nsamples, L + p->M, env_i, env_j, envcap);
+  if (w->dbg) {
+    struct orc_ens_debug *g = w->dbg;
+    if (g->nreg == g->capreg) { g->capreg = 2 * g->capreg + 8; g->reg = (ens_region *)realloc(g->reg, sizeof(ens_region) * g->capreg); }
+    ens_region *e = &g->reg[g->nreg++];
+    e->ireg = ireg; e->jreg = jreg; e->nenv = ne; e->rng0 = rng0; e->step0 = step0; e->nstep = rec->n - step0;
+    e->n2sc = (float *)malloc(sizeof(float) * Lr); memcpy(e->n2sc, w->n2sc + ireg, sizeof(float) * Lr);
+    e->env = (int *)malloc(sizeof(int) * 2 * (ne + 1));
+    for (int d = 0; d < ne; d++) { e->env[2 * d] = (*env_i)[d]; e->env[2 * d + 1] = (*env_j)[d]; }
+  }
+  free(cntM); free(sp); free(dfrom);
   return ne;
 }
 #undef FULLV
@@ -1112,6 +1151,58 @@ static void pipeline_pair(const orc_profile *p, int prof, int64_t seq, const uin
   }
   free(doms); free(ei); free(ej);
 #undef PUSH_DOM
+}
+
+/* ------------------------------------------------------------------ the ensemble stage, opened up for tests
+ * One (profile, target) pair through the same pipeline_pair as the search, every filter passed (F = 2), single-threaded, FTZ | DAZ as
+ * orc_search sets them; every multidomain region leaves its record (see orc.h). */
+orc_ens_debug *orc_ensemble_debug(const orc_hmmset *hs, int prof, const uint8_t *codes, int L)
+{
+  flogsum_init();
+  orc_ens_debug *g = (orc_ens_debug *)calloc(1, sizeof(*g));
+  if (L <= 0 || prof < 0 || prof >= hs->n) return g;
+  const unsigned int csr = _mm_getcsr();
+  _mm_setcsr(csr | 0x8040);
+  workspace w; memset(&w, 0, sizeof(w));
+  w.dbg = g;
+  orc_results r; memset(&r, 0, sizeof(r));
+  uint8_t *dsq = (uint8_t *)malloc((size_t)L + 2);
+  dsq[0] = 17; memcpy(dsq + 1, codes, L); dsq[L + 1] = 17;
+  pipeline_pair(&hs->p[prof], prof, 0, dsq, L, 10.0, 2.0, 2.0, 2.0, &w, &r, 0, log((double)(1.0f / 256.0f)));
+  free(dsq); free(r.dom); free(r.trace); ws_free(&w);
+  _mm_setcsr(csr);
+  return g;
+}
+int orc_ens_nregions(const orc_ens_debug *g) { return g->nreg; }
+void orc_ens_region(const orc_ens_debug *g, int r, int64_t *out)
+{
+  const ens_region *e = &g->reg[r];
+  out[0] = e->ireg; out[1] = e->jreg; out[2] = e->rng0; out[3] = e->nstep; out[4] = e->nenv;
+}
+const orc_ens_step *orc_ens_steps(const orc_ens_debug *g, int r) { return g->rec.v + g->reg[r].step0; }
+const float *orc_ens_n2sc(const orc_ens_debug *g, int r) { return g->reg[r].n2sc; }
+const int *orc_ens_envs(const orc_ens_debug *g, int r) { return g->reg[r].env; }
+void orc_ens_free(orc_ens_debug *g)
+{
+  if (!g) return;
+  for (int r = 0; r < g->nreg; r++) { free(g->reg[r].n2sc); free(g->reg[r].env); }
+  free(g->reg); free(g->rec.v); free(g);
+}
+/* the clustering alone, on n hand-made (trace, i, j, k, m) tuples out of 200 paths: writes up to cap envelopes, returns their number */
+int orc_spensemble_cluster(const int32_t *tuples, int n, int32_t *env, int cap)
+{
+  spcoord *sp = (spcoord *)malloc(sizeof(spcoord) * (n + 1));
+  int span = 0;
+  for (int h = 0; h < n; h++) {
+    sp[h].idx = tuples[5 * h]; sp[h].i = tuples[5 * h + 1]; sp[h].j = tuples[5 * h + 2]; sp[h].k = tuples[5 * h + 3]; sp[h].m = tuples[5 * h + 4];
+    sp[h].prob = 0.f;
+    for (int z = 1; z < 5; z++) if (tuples[5 * h + z] > span) span = tuples[5 * h + z];
+  }
+  int *ei = NULL, *ej = NULL, envcap = 0;
+  const int ne = cluster_samples(sp, n, 200, span, &ei, &ej, &envcap);
+  for (int d = 0; d < ne && d < cap; d++) { env[2 * d] = ei[d]; env[2 * d + 1] = ej[d]; }
+  free(ei); free(ej); free(sp);
+  return ne;
 }
 
 static int cmp_dom(const void *a, const void *b)

@@ -183,6 +183,15 @@ def multidomain(t, mini, allt, fx, scale):
             parts += [cons3[int(rng.integers(0, len(cons3)))], _rnd(rng, int(rng.integers(3, 40))), cons4[int(rng.integers(0, len(cons4)))],
                       _rnd(rng, int(rng.integers(3, 60)))]
         seqs.append(_sprinkle(rng, "".join(parts), 0.01, "A"))
+    # the copies above lie far enough apart for a region each; TANDEM PARTIAL copies (concatemer-like, as the adversarial reads of
+    # tests/test_gpu_caps.py) do form multidomain regions, which the traceback ensemble resolves
+    for j in range(6):
+        c = (cons3 if j % 2 == 0 else cons4)[int(rng.integers(0, 3))]
+        parts = [_rnd(rng, int(rng.integers(0, 40)))]
+        for _ in range(int(rng.integers(3, 7))):
+            a = int(rng.integers(0, len(c) // 2))
+            parts.append(c[a:int(rng.integers(a + len(c) // 3, len(c) + 1))])
+        seqs.append("".join(parts) + _rnd(rng, int(rng.integers(0, 40))))
     return mini, seqs, True
 
 

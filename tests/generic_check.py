@@ -4,7 +4,8 @@ tests/hmm_generic.py, shared by tests/test_generic_cpu.py and tests/test_gpu_gen
 Scores must agree within tol(L) = max(2e-3, 6 (L + M) 2^-24) nats: the per-row rounding budget of a float32 Forward over L + M steps
 that the lazy margin (engine.hip, lazy_c) already assumes.  A discrete outcome (a filter's pass, the number of regions, an envelope,
 a reporting decision, a per-read winner) must equal the float64 decision unless the float64 value lies within tol of its threshold;
-such pairs are counted and listed, never dropped silently."""
+such pairs are counted and listed, never dropped silently.  The envelopes of a multidomain region take their null2 from sampled
+paths: their domcorrection and the pair's seq_score are stated by tests/ensemble_exact.py's model of that stage (check(ens=...))."""
 import math
 import os
 import tempfile
@@ -133,10 +134,23 @@ class Report:
         return self.line()
 
 
-def check(name, hm, seqs, trace, dom, seqfield, pool, sample=None, seed=0, msv_all=False):
+def ensemble_models(hs, hm, seqs, trace, seqfield, pool):
+    """the float64 model of the traceback ensemble (tests/ensemble_exact.py) for every pair of the result that reached the domain
+    stage: what check() takes as `ens`.  hs: orc.HmmSet of the same profile text (the model replays the oracle's sampled paths)."""
+    import ensemble_exact as EX
+    pairs = [(int(r[seqfield]), int(r["prof"])) for r in trace if r["pass_fwd"] and r["nregions"] > 0]
+    md = EX.model_pairs(hs, hm, seqs, pairs, pool)
+    rolls, exc, msg = EX.verdict([r for lst in md.values() for _, r in lst])
+    assert msg is None, msg
+    return {k: [r for _, r in lst] for k, lst in md.items()}
+
+
+def check(name, hm, seqs, trace, dom, seqfield, pool, sample=None, seed=0, msv_all=False, ens=None):
     """Every check of the float64 statement on one search result.  trace / dom: PairTrace / Domain rows; seqfield: "seq" (oracle) or
-    "rep" (engine); sample: at most this many pairs past the Forward filter are decoded (fixed seed), None = all.  Returns
-    (Report, float64 domain rows) -- the rows carry float64 scores at the result's own envelopes and float64 reporting."""
+    "rep" (engine); sample: at most this many pairs past the Forward filter are decoded (fixed seed), None = all; ens: the float64
+    model's multidomain regions per pair (ensemble_models), whose per-residue null2 scores state an ensemble envelope's
+    domcorrection and the pair's seq_score.  Returns (Report, float64 domain rows) -- the rows carry float64 scores at the result's
+    own envelopes and float64 reporting."""
     for i, h in enumerate(hm):
         h["_i"] = i
     rep = Report(name, len(trace))
@@ -208,14 +222,25 @@ def check(name, hm, seqs, trace, dom, seqfield, pool, sample=None, seed=0, msv_a
         lnn3 = math.log(L / (L + 3.0))
         env_sc, cor_sum, ld_sum = 0.0, 0.0, 0
         cors = []
+        mregs = ens.get((s, p)) if ens is not None else None           # the ensemble model's regions of this pair, or None
+        stated = mregs is not None
         for d, (bits, corr, envsc) in zip(ds, x["doms"]):
             Ld = int(d["jenv"]) - int(d["ienv"]) + 1
             w2 = what + " envelope %d-%d" % (d["ienv"], d["jenv"])
             rep.dev("envsc", float(d["envsc"]) - envsc, tl, w2)
             if d["flags"] & 1:
-                # an ensemble envelope: HMMER takes its null2 from the sampled traces (p7_Null2_ByTrace), which no float64
-                # statement can repeat; its bit score must still follow from its own correction in closed form
-                corr = float(d["domcorrection"])
+                # an ensemble envelope: HMMER takes its null2 from the sampled traces (p7_Null2_ByTrace): the sum of the model's
+                # per-residue scores over the envelope.  Where the region was not modelled (no `ens`, or a matrix that could not be
+                # sampled) the bit score must still follow from the result's own correction in closed form
+                mr = [m for m in mregs or () if m["ireg"] <= d["ienv"] and d["jenv"] <= m["jreg"] and (int(d["ienv"]), int(d["jenv"])) in m["envs"]]
+                if mr:
+                    corr = float(mr[0]["n2sc"][int(d["ienv"]) - mr[0]["ireg"]:int(d["jenv"]) - mr[0]["ireg"] + 1].sum())
+                    rep.dev("ens_domcorrection", float(d["domcorrection"]) - corr, tol(Ld, M), w2)
+                else:
+                    if mregs is not None:
+                        rep.fail.append("%s: ensemble envelope is not one of the model's at %s" % (name, w2))
+                    stated = False
+                    corr = float(d["domcorrection"])
                 bits = (envsc + (L - Ld) * lnn3 - ns - math.log1p(math.exp(math.log(1 / 256.0) + corr))) / LN2
             else:
                 rep.dev("domcorrection", float(d["domcorrection"]) - corr, tol(Ld, M), w2)
@@ -231,15 +256,18 @@ def check(name, hm, seqs, trace, dom, seqfield, pool, sample=None, seed=0, msv_a
                              bitscore=bits, lnP=-lam * (bits - tau) if bits > tau else 0.0, lam=lam, tl=tl,
                              got_seq=int(d["seq_reported"]), got_dom=int(d["dom_reported"])))
         if ds:
-            allcor = sum(cors)
+            # the whole-sequence null2 sums the per-residue scores of every region: a single envelope's correction, and ALL of a
+            # multidomain region's trace-based scores, the residues between its envelopes included
+            allcor = sum(c for c, d in zip(cors, ds) if not d["flags"] & 1 or not stated) + \
+                (sum(float(m["n2sc"].sum()) for m in mregs) if stated else 0.0)
             whole = (x["fwd"] - ns - math.log1p(math.exp(math.log(1 / 256.0) + allcor))) / LN2
             sc, recon = whole, -math.inf
             if ld_sum > 0:
                 recon = (env_sc + (L - ld_sum) * lnn3 - ns - math.log1p(math.exp(math.log(1 / 256.0) + cor_sum))) / LN2
                 sc = max(whole, recon)
-            if any(d["flags"] & 1 for d in ds):
-                # the whole-sequence null2 then sums trace-based per-residue scores over the residues the sampled traces cover,
-                # which the domain rows do not carry: not stated here (counted); reporting takes the result's own score for it
+            if any(d["flags"] & 1 for d in ds) and not stated:
+                # without the model the trace-based per-residue scores between the envelopes are unknown (the domain rows do not
+                # carry them): not stated (counted); reporting takes the result's own score for it
                 rep.unstated += 1
                 sc = float(ds[0]["seq_score"])
             else:

@@ -127,6 +127,17 @@ def lib():
     L.orc_tjb_b.restype = C.c_uint8
     L.orc_tjb_b.argtypes = [C.c_int]
     L.orc_flogsum_table.restype = C.c_void_p
+    L.orc_ensemble_debug.restype = C.c_void_p
+    L.orc_ensemble_debug.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.orc_ens_nregions.argtypes = [C.c_void_p]
+    L.orc_ens_region.restype = None
+    L.orc_ens_region.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    for f in ("orc_ens_steps", "orc_ens_n2sc", "orc_ens_envs"):
+        getattr(L, f).restype = C.c_void_p
+        getattr(L, f).argtypes = [C.c_void_p, C.c_int]
+    L.orc_ens_free.restype = None
+    L.orc_ens_free.argtypes = [C.c_void_p]
+    L.orc_spensemble_cluster.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     _LIB = L
     return L
 
@@ -346,3 +357,45 @@ def dust(seq):
     lib().orc_dust.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
     lib().orc_dust(codes.ctypes.data, len(seq), out.ctypes.data)
     return out[:len(seq)].astype(bool)
+
+
+ENS_STEP_DTYPE = np.dtype([("trace", "<i4"), ("s0", "<i4"), ("s1", "<i4"), ("k", "<i4"), ("i", "<i4"), ("ndraw", "<i4")])
+# the oracle's state codes (orc_search.c)
+ST_M, ST_D, ST_I, ST_S, ST_N, ST_B, ST_E, ST_C, ST_T, ST_J = range(1, 11)
+
+
+def _view(ptr, n, dtype):
+    dtype = np.dtype(dtype)
+    if n <= 0:
+        return np.zeros(0, dtype)
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n * dtype.itemsize,)).view(dtype).copy()
+
+
+def ensemble_debug(hs, prof, seq):
+    """what the oracle's ensemble stage sampled for one (profile, target) pair, every filter passed: one dict per multidomain
+    region with ireg, jreg, rng0 (the generator's start state), steps (ENS_STEP_DTYPE rows of all 200 paths), n2sc (float32 per
+    residue of the region, after the logf) and envs [(i, j), ...]"""
+    L = lib()
+    codes, _ = digitize([seq])
+    g = L.orc_ensemble_debug(hs.h, prof, codes.ctypes.data, len(seq))
+    try:
+        out = []
+        for r in range(L.orc_ens_nregions(g)):
+            v = np.zeros(5, np.int64)
+            L.orc_ens_region(g, r, v.ctypes.data)
+            ireg, jreg, rng0, nstep, nenv = (int(x) for x in v)
+            envs = _view(L.orc_ens_envs(g, r), 2 * max(0, nenv), np.int32).reshape(-1, 2)
+            out.append(dict(ireg=ireg, jreg=jreg, rng0=rng0, steps=_view(L.orc_ens_steps(g, r), nstep, ENS_STEP_DTYPE),
+                            n2sc=_view(L.orc_ens_n2sc(g, r), jreg - ireg + 1, np.float32),
+                            envs=[(int(a), int(b)) for a, b in envs]))
+        return out
+    finally:
+        L.orc_ens_free(g)
+
+
+def spensemble_cluster(tuples):
+    """the oracle's clustering of hand-made (trace, i, j, k, m) tuples out of 200 paths (a trace's tuples adjacent) -> [(i, j), ...]"""
+    t = np.ascontiguousarray(tuples, np.int32).reshape(-1, 5)
+    env = np.zeros((len(t) + 1, 2), np.int32)
+    ne = lib().orc_spensemble_cluster(t.ctypes.data, len(t), env.ctypes.data, len(env))
+    return [(int(a), int(b)) for a, b in env[:ne]]

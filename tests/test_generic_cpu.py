@@ -72,7 +72,11 @@ def test_oracle_agrees_with_float64(name, pool, t_hmm_text, mini_hmm_text, all_i
     codes, o = orc.digitize(seqs)
     res = orc.SearchResult(hs, codes, o, keep_trace=2, threads=8)
     assert len(res.trace) == hs.n * len(seqs)
-    rep, rows = GC.check(name, hm, seqs, res.trace, res.domains, "seq", pool, sample=None if edge else 40, seed=7)
+    ens = GC.ensemble_models(hs, hm, seqs, res.trace, "seq", pool)
+    rep, rows = GC.check(name, hm, seqs, res.trace, res.domains, "seq", pool, sample=None if edge else 40, seed=7, ens=ens)
+    assert rep.unstated == 0
+    if name == "multidomain":
+        assert res.counts["multidomain"] > 0 and "ens_domcorrection" in rep.worst      # the case reaches the ensemble stage
     # the oracle's per-read winners == ItsPosition fed a float64 domain table
     names = ["r%d" % i for i in range(len(seqs))]
     for left, right in (("3_", "4_"), ("1_", "2_")):

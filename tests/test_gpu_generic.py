@@ -9,6 +9,7 @@ import pytest
 import edge_cases
 import generic_check as GC
 import hmm_generic as G
+import orc
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +43,13 @@ def test_engine_agrees_with_float64(name, engine, pool, monkeypatch, t_hmm_text,
         engine.set_rows_mode(None)
     assert [h["M"] for h in hm] == [engine.profile_tables(i)["M"] for i in range(engine.n_profiles)]
     useqs = [seqs[int(i)] for i in seed]
-    rep, rows = GC.check(name, hm, useqs, tr, dom, "rep", pool, sample=None if edge else 40, seed=7)
+    n_multi = engine.stats()["n_multidomain"]
+    # the ensemble stage's float64 model replays the paths the CPU oracle sampled for the same pairs (tests/ensemble_exact.py)
+    ens = GC.ensemble_models(orc.HmmSet(text=hmm), hm, useqs, tr, "rep", pool)
+    rep, rows = GC.check(name, hm, useqs, tr, dom, "rep", pool, sample=None if edge else 40, seed=7, ens=ens)
+    assert rep.unstated == 0
+    if name == "multidomain":
+        assert n_multi > 0 and "ens_domcorrection" in rep.worst                       # the case reaches the ensemble stage
     # the production default: no hooks, no trace
     monkeypatch.delenv("ITSX_KEEP_TRACE")
     seed2 = _run(engine, hmm, seqs)
