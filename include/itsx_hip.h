@@ -741,6 +741,24 @@ int itsx_debug_detmath(itsx_ctx *ctx, const double *x, int64_t n, double *out_lo
 int itsx_debug_logf(itsx_ctx *ctx, const float *x, int64_t n, float *out);
 /* the DUST soft mask (vsearch --qmask dust) the device computes for the current reads: masked[sum of lengths], 1 = masked */
 int itsx_debug_dust(itsx_ctx *ctx, uint8_t *masked);
+/* launch_exclusive_scan (k_util.hip) over n int32 values: out[i] = in[0] + ... + in[i - 1]; in_place != 0: the device scans the input
+ * buffer onto itself */
+int itsx_debug_scan(itsx_ctx *ctx, const int32_t *in, int64_t n, int32_t *out, int in_place);
+/* One selection of the lazy stage (k_lazy.hip) over a pair list of the caller's: pairs[NP][4] = (useq, prof, xj, L), prof < 0 = padding;
+ * profile p's pairs lie in [seg_start[p], seg_start[p + 1]), every bound a multiple of 64.  mode 0 / 1: round 0 / round 1 of the lazy
+ * rounds -- group[n_group] is gtop indexed by useq * ncls + cls[prof] (mode 0), or bestc indexed by sorted_uniq[useq] * ncls + cls[prof]
+ * (mode 1); mode 2: the top-up round's marking with slot_of_prof[P] and cutoff[2 n_slots]; mode 3: the top-up round's key list.
+ * Modes 0-2: done[NP] is updated, out_seg[P + 1] receives the selected list's segments (padded to 64), *out_n its length and, when
+ * out_cap holds it, out_pairs the list itself (padding records are all 0xFF).  Mode 3: *out_n = the marked pairs, out_keys / out_vals
+ * (when out_cap holds them) their keys (slot << 32 | ~b10) and indices in list order.  An index that points outside a table is ITSX_E_ARG. */
+int itsx_debug_select(itsx_ctx *ctx, int mode, const int32_t *pairs, int64_t NP, const int64_t *seg_start, int32_t P, uint8_t *done, const uint32_t *b10,
+                      const int8_t *cls, int32_t ncls, const unsigned long long *group, int64_t n_group, const int32_t *sorted_uniq, int64_t n_sorted,
+                      const int32_t *slot_of_prof, const uint32_t *cutoff, int32_t n_slots, int64_t *out_seg, int32_t *out_pairs, int64_t out_cap,
+                      unsigned long long *out_keys, int32_t *out_vals, int64_t *out_n);
+/* The envelope memoisation's table (k_derep.hip: k_region_keys, k_region_resolve) over regions of the loaded reads: regions[n][4] =
+ * (pair, ienv, jenv, multi), pair < 0 = none; pairs[n_pairs][4] as above with useq = the READ's index.  rep_region[g] = the smallest
+ * region with g's profile, L and residues (-1: no region), is_uniq[g] = (rep_region[g] == g).  The table has the size a search gives it. */
+int itsx_debug_region_keys(itsx_ctx *ctx, const int32_t *regions, int64_t n_regions, const int32_t *pairs, int64_t n_pairs, int32_t *rep_region, int32_t *is_uniq);
 
 #ifdef __cplusplus
 }

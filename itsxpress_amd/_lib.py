@@ -99,7 +99,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_twriter_set_device",
            "itsx_inflate_device", "itsx_inflate_fetch", "itsx_debug_inflate_host", "itsx_debug_inflate_candidates", "itsx_debug_inflate_where", "itsx_set_device_inflate",
            "itsx_parse_device", "itsx_parse_fetch", "itsx_debug_parse_host", "itsx_set_device_parse",
-           "itsx_debug_set_domains", "itsx_debug_get_rows"]
+           "itsx_debug_set_domains", "itsx_debug_get_rows",
+           "itsx_debug_scan", "itsx_debug_select", "itsx_debug_region_keys"]
 
 
 def lib():
@@ -233,6 +234,9 @@ def lib():
         "itsx_debug_detmath": (i32, [vp, vp, i64, vp, vp]),
         "itsx_debug_logf": (i32, [vp, vp, i64, vp]),
         "itsx_debug_dust": (i32, [vp, vp]),
+        "itsx_debug_scan": (i32, [vp, vp, i64, vp, i32]),
+        "itsx_debug_select": (i32, [vp, i32, vp, i64, vp, i32, vp, vp, vp, i32, vp, i64, vp, i64, vp, vp, i32, vp, vp, i64, vp, vp, vp]),
+        "itsx_debug_region_keys": (i32, [vp, vp, i64, vp, i64, vp, vp]),
         "itsx_debug_calibrate": (i32, [vp, i32, f64, i32, vp, vp]),
         "itsx_debug_issue": (i32, [vp, i32, i32, i32, vp, vp]),
         "itsx_shard_text": (i32, [C.c_char_p, i32, vp, C.c_char_p, vp, vp]),

@@ -120,6 +120,20 @@ __global__ void k_gather_i32(const int32_t *src, const int64_t *idx, int n, int3
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = src[idx[i]];
 }
+// slots of the envelope memoisation's table (k_derep.hip: k_region_keys) for n regions: a power of two, never more than half full
+static uint64_t region_table_size(int64_t n)
+{
+  uint64_t tsize = 1024;
+  while (tsize < (uint64_t)n * 2 + 16) tsize <<= 1;
+  return tsize;
+}
+
+// out[i] = src[idx[i] / 64]: the selection's chunk scan (k_lazy.hip) at the start of each profile segment
+__global__ void k_gather_chunk_i32(const int32_t *src, const int64_t *idx, int n, int32_t *out)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = src[idx[i] >> 6];
+}
 __global__ void k_rep_coords(int32_t U, const unsigned long long *bl, const unsigned long long *br, const int32_t *cl, const int32_t *cr,
                              const int32_t *seed_read, const int32_t *len, int32_t *start, int32_t *stop, int32_t *tlen)
 {
@@ -408,7 +422,7 @@ struct itsx_ctx {
   bool completing = false;               // itsx_lazy_complete: every pair of the profiles in plist goes through the domain pipeline
   std::vector<int32_t> h_plist; DBuf<int32_t> d_plist;
   int64_t s_Uc = 0; int s_Lcap = 0;       // the last search's chunk size and length cap (the completion walks the same chunks)
-  DBuf<float> l_fb; DBuf<uint32_t> l_b10; DBuf<uint8_t> l_done; DBuf<int32_t> l_flag, l_pos, l_scan, l_has; DBuf<unsigned long long> l_gtop, l_sure;
+  DBuf<float> l_fb; DBuf<uint32_t> l_b10; DBuf<uint8_t> l_done; DBuf<unsigned long long> l_smask; DBuf<int32_t> l_scnt, l_spos, l_scan, l_has; DBuf<unsigned long long> l_gtop, l_sure;
   DBuf<PairRec> l_pairs; DBuf<int64_t> l_seg, l_zub; DBuf<int32_t> l_pflag; DBuf<uint8_t> l_uflag; bool partial_coords = false; bool kept_rows = false; std::vector<int32_t> lazy_pending_prof;
   std::vector<uint16_t> thr_memo; std::vector<char> thr_memo_have; double thr_memo_F1 = -1.0; int thr_memo_Ppad = 0;   // MSV thresholds by length, kept between searches
   DBuf<int32_t> w_coords4; DBuf<int64_t> w_keys128; DBuf<uint64_t> w_hf1, w_hr1;
@@ -2326,8 +2340,8 @@ int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
     // (buffers only grow).  ~64 B per pair, a third of what is free plus what the lazy lists hold already.
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
-      const double held = (double)ctx->d_pairs.cap * sizeof(PairRec) + (double)ctx->l_fb.cap * 4 + (double)ctx->l_b10.cap * 4 + (double)ctx->l_flag.cap * 4 +
-                          (double)ctx->l_pos.cap * 4 + (double)ctx->l_done.cap + (double)ctx->w_res.cap * 2;
+      const double held = (double)ctx->d_pairs.cap * sizeof(PairRec) + (double)ctx->l_fb.cap * 4 + (double)ctx->l_b10.cap * 4 + (double)ctx->l_smask.cap * 8 +
+                          (double)ctx->l_scnt.cap * 4 + (double)ctx->l_spos.cap * 4 + (double)ctx->l_done.cap + (double)ctx->w_res.cap * 2;
       lazy_budget = std::min<int64_t>(lazy_budget, (int64_t)(((double)fr + held) / 3.0 / 64.0));
       lazy_budget = std::max<int64_t>(lazy_budget, (int64_t)1 << 20);
     }
@@ -2596,7 +2610,7 @@ static int domain_pipeline(itsx_ctx *ctx, const PairList &pl, const int32_t *d_s
       // ---- memoisation: distinct (profile, target length, residues) regions
       DBuf<unsigned long long> &rkeys = ctx->w_keys; DBuf<int32_t> &rvals = ctx->w_vals; DBuf<uint32_t> &rslot = ctx->w_slot_of;
       DBuf<int32_t> &rrep = ctx->w_rrep, &ruq = ctx->w_ruq, &rurank = ctx->w_rurank, &rscan = ctx->w_scan_tmp;
-      uint64_t tsize = 1024; while (tsize < (uint64_t)NMR * 2 + 16) tsize <<= 1;
+      const uint64_t tsize = region_table_size(NMR);
       HIPCHK(rkeys.alloc(tsize)); HIPCHK(rvals.alloc(tsize)); HIPCHK(rslot.alloc((size_t)NMR + 1));
       HIPCHK(rrep.alloc((size_t)NMR + 1)); HIPCHK(ruq.alloc((size_t)NMR + 1)); HIPCHK(rurank.alloc((size_t)NMR + 1)); HIPCHK(rscan.alloc((size_t)scan_tmp_elems(NMR + 1)));
       HIPCHK(hipMemsetAsync(rkeys.p, 0, tsize * sizeof(unsigned long long), st));
@@ -2804,7 +2818,7 @@ static int domain_pipeline(itsx_ctx *ctx, const PairList &pl, const int32_t *d_s
     // ---- envelope memoisation: only distinct (profile, L, residues) envelopes are re-scored
     DBuf<unsigned long long> &rkeys = ctx->w_keys; DBuf<int32_t> &rvals = ctx->w_vals; DBuf<uint32_t> &rslot = ctx->w_slot_of;
     DBuf<int32_t> &rrep = ctx->w_rrep, &ruq = ctx->w_ruq, &rurank = ctx->w_rurank, &rscan = ctx->w_scan_tmp;
-    uint64_t tsize = 1024; while (tsize < (uint64_t)NR * 2 + 16) tsize <<= 1;
+    const uint64_t tsize = region_table_size(NR);
     HIPCHK(rkeys.alloc(tsize)); HIPCHK(rvals.alloc(tsize)); HIPCHK(rslot.alloc((size_t)NR + 1));
     HIPCHK(rrep.alloc((size_t)NR + 1)); HIPCHK(ruq.alloc((size_t)NR + 1)); HIPCHK(rurank.alloc((size_t)NR + 1));
     HIPCHK(rscan.alloc((size_t)scan_tmp_elems(NR + 1))); HIPCHK(ctx->d_upos.alloc((size_t)NR + 1));
@@ -2910,10 +2924,10 @@ static int domain_pipeline(itsx_ctx *ctx, const PairList &pl, const int32_t *d_s
 
 
 namespace itsx {
-__global__ void k_dbg_group_count(const PairRec *__restrict__ pairs, int64_t NP, const int32_t *__restrict__ flag, const int8_t *__restrict__ cls, int ncls, unsigned long long *__restrict__ cnt)
+__global__ void k_dbg_group_count(const PairRec *__restrict__ pairs, int64_t NP, const unsigned long long *__restrict__ smask, const int8_t *__restrict__ cls, int ncls, unsigned long long *__restrict__ cnt)
 {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= NP || !flag[i]) return;
+  if (i >= NP || !((smask[i >> 6] >> (i & 63)) & 1ull)) return;
   const PairRec pr = pairs[i];
   if (pr.prof < 0) return;
   atomicAdd(&cnt[(size_t)pr.useq * ncls + cls[pr.prof]], 1ull);
@@ -2930,6 +2944,45 @@ __global__ void k_dbg_group_hist(const unsigned long long *__restrict__ cnt, int
 }
 }  // namespace itsx
 
+// The pairs that a marking kernel (k_lazy_mark, k_topup_mark) set a bit for, as a list of their own in l_pairs / d_pout: the chunk counts
+// are scanned, the profiles' totals read at their segments' first chunks, and the set bits scattered.  Each profile keeps its segment,
+// padded to 64 with 0xFF records, and its pairs their order.  nsel = pairs selected; sub.NP == 0: none (nothing was allocated).
+static int select_compact(itsx_ctx *ctx, const PairRec *pairs, int64_t NP, int P, const std::vector<int64_t> &seg_start, const int64_t *d_seg_start, PairList &sub, int64_t &nsel)
+{
+  hipStream_t st = ctx->st;
+  const int64_t nch = (NP + 63) >> 6;
+  launch_exclusive_scan(ctx->l_scnt.p, ctx->l_spos.p, nch + 1, ctx->l_scan.p, st);
+  std::vector<int32_t> bound((size_t)P + 1);
+  {
+    DBuf<int64_t> &d_idx = ctx->w_idx; DBuf<int32_t> &d_b = ctx->w_b;
+    HIPCHK(upload(d_idx, seg_start, st)); HIPCHK(d_b.alloc((size_t)P + 1));
+    hipLaunchKernelGGL(k_gather_chunk_i32, dim3((P + 1 + 255) / 256), dim3(256), 0, st, ctx->l_spos.p, d_idx.p, P + 1, d_b.p);
+    HIPCHK(hipMemcpyAsync(bound.data(), d_b.p, ((size_t)P + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  sub.seg_start.assign((size_t)P + 1, 0); sub.total.assign((size_t)P, 0);
+  for (int p = 0; p < P; p++) { sub.total[(size_t)p] = bound[(size_t)p + 1] - bound[(size_t)p]; sub.seg_start[(size_t)p + 1] = sub.seg_start[(size_t)p] + ((int64_t)sub.total[(size_t)p] + 63) / 64 * 64; }
+  sub.NP = sub.seg_start[(size_t)P];
+  nsel = (int64_t)bound[(size_t)P] - bound[0];
+  if (sub.NP == 0) return ITSX_OK;
+  HIPCHK(ctx->l_pairs.alloc((size_t)sub.NP)); HIPCHK(ctx->d_pout.alloc((size_t)sub.NP));
+  HIPCHK(hipMemsetAsync(ctx->l_pairs.p, 0xFF, (size_t)sub.NP * sizeof(PairRec), st));
+  HIPCHK(hipMemsetAsync(ctx->d_pout.p, 0, (size_t)sub.NP * sizeof(PairOut), st));
+  HIPCHK(upload(ctx->l_seg, sub.seg_start, st));
+  launch_lazy_scatter(pairs, NP, ctx->l_smask.p, ctx->l_spos.p, d_seg_start, ctx->l_seg.p, ctx->l_pairs.p, st);
+  sub.pairs = ctx->l_pairs.p; sub.pout = ctx->d_pout.p; sub.d_seg_start = ctx->l_seg.p;
+  return ITSX_OK;
+}
+// the selection's chunk buffers for a list of NP pairs (NP a multiple of 64: every segment is padded)
+static int select_alloc(itsx_ctx *ctx, int64_t NP)
+{
+  if (NP & 63) SET_ERR(ctx, ITSX_E_DEVICE, "lazy stage: the pair list is not padded to whole chunks of 64");
+  const int64_t nch = NP >> 6;                                  // one mask word and one count each (k_lazy.hip)
+  HIPCHK(ctx->l_smask.alloc((size_t)nch + 1)); HIPCHK(ctx->l_scnt.alloc((size_t)nch + 2)); HIPCHK(ctx->l_spos.alloc((size_t)nch + 2));
+  HIPCHK(ctx->l_scan.alloc((size_t)scan_tmp_elems(nch + 2)));
+  return ITSX_OK;
+}
+
 // The lazy domain stage (k_lazy.hip): Forward scores for every pair of the chunk, then two rounds of the domain pipeline over
 // the pairs that can still win ItsPosition's argmax.
 static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorted, int32_t u0, int32_t Uc, double T, double F1, double F3, const std::function<int()> *next_msv)
@@ -2940,7 +2993,7 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
   const int64_t NP = pl.NP;
   // ---- pass A: the Forward score of every pair (nothing else is kept)
   HIPCHK(ctx->l_fb.alloc((size_t)NP + 1)); HIPCHK(ctx->l_b10.alloc((size_t)NP + 1)); HIPCHK(ctx->l_done.alloc((size_t)NP + 1));
-  HIPCHK(ctx->l_flag.alloc((size_t)NP + 2)); HIPCHK(ctx->l_pos.alloc((size_t)NP + 2)); HIPCHK(ctx->l_scan.alloc((size_t)scan_tmp_elems(NP + 2)));
+  { const int rc = select_alloc(ctx, NP); if (rc != ITSX_OK) return rc; }
   HIPCHK(ctx->l_gtop.alloc((size_t)Uc * ncls + 1));
   HIPCHK(hipMemsetAsync(ctx->l_done.p, 0, (size_t)NP + 1, st));
   HIPCHK(hipMemsetAsync(ctx->l_gtop.p, 0, ((size_t)Uc * ncls + 1) * sizeof(unsigned long long), st));
@@ -3218,7 +3271,7 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
   StageTimer tm_sel(st);
   LazyArgs la{};
   la.pairs = pl.pairs; la.NP = NP; la.fb = ctx->l_fb.p; la.lt = ctx->d_lt.p; la.cls = ctx->w_cls.p; la.ncls = ncls; la.sorted_uniq = d_sorted;
-  la.b10 = ctx->l_b10.p; la.gtop = ctx->l_gtop.p; la.bestc = ctx->w_bestc.p; la.done = ctx->l_done.p; la.flag = ctx->l_flag.p;
+  la.b10 = ctx->l_b10.p; la.gtop = ctx->l_gtop.p; la.bestc = ctx->w_bestc.p; la.done = ctx->l_done.p; la.smask = ctx->l_smask.p; la.scnt = ctx->l_scnt.p; la.ngroups = (int64_t)Uc * ncls;
   launch_lazy_bound(la, st);
   float ms_sel = tm_sel.stop();
   for (int round = 0; round < 2; round++) {
@@ -3227,7 +3280,7 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
     if (round == 1 && sw_get("ITSX_LAZY_HIST")) {      // experiment: how many candidates a group sends into round 2
       const int64_t ng = (int64_t)Uc * ncls;
       HIPCHK(hipMemsetAsync(ctx->l_gtop.p, 0, (size_t)ng * 8, st));
-      hipLaunchKernelGGL(k_dbg_group_count, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, st, pl.pairs, NP, ctx->l_flag.p, ctx->w_cls.p, ncls, ctx->l_gtop.p);
+      hipLaunchKernelGGL(k_dbg_group_count, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, st, pl.pairs, NP, ctx->l_smask.p, ctx->w_cls.p, ncls, ctx->l_gtop.p);
       DBuf<unsigned long long> hist; HIPCHK(hist.alloc(16)); HIPCHK(hipMemsetAsync(hist.p, 0, 16 * 8, st));
       hipLaunchKernelGGL(k_dbg_group_hist, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, ctx->l_gtop.p, ng, hist.p);
       unsigned long long h[16];
@@ -3235,32 +3288,14 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
       fprintf(stderr, "[itsx] round 2 candidates per group: 0:%llu 1:%llu 2:%llu 3:%llu 4:%llu 5-8:%llu 9-16:%llu 17+:%llu; pairs beyond a group's first %llu, beyond its second %llu\n",
               h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9]);
     }
-    launch_exclusive_scan(ctx->l_flag.p, ctx->l_pos.p, NP + 1, ctx->l_scan.p, st);
-    std::vector<int32_t> bound((size_t)P + 1);
-    {
-      DBuf<int64_t> &d_idx = ctx->w_idx; DBuf<int32_t> &d_b = ctx->w_b;
-      HIPCHK(upload(d_idx, pl.seg_start, st)); HIPCHK(d_b.alloc((size_t)P + 1));
-      hipLaunchKernelGGL(k_gather_i32, dim3((P + 1 + 255) / 256), dim3(256), 0, st, ctx->l_pos.p, d_idx.p, P + 1, d_b.p);
-      HIPCHK(hipMemcpyAsync(bound.data(), d_b.p, ((size_t)P + 1) * 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-    }
-    PairList sub;
-    sub.seg_start.assign((size_t)P + 1, 0); sub.total.assign((size_t)P, 0);
-    for (int p = 0; p < P; p++) { sub.total[(size_t)p] = bound[(size_t)p + 1] - bound[(size_t)p]; sub.seg_start[(size_t)p + 1] = sub.seg_start[(size_t)p] + ((int64_t)sub.total[(size_t)p] + 63) / 64 * 64; }
-    sub.NP = sub.seg_start[(size_t)P];
-    const int64_t nsel = (int64_t)bound[(size_t)P] - bound[0];
+    PairList sub; int64_t nsel = 0;
+    { const int rc = select_compact(ctx, pl.pairs, NP, P, pl.seg_start, pl.d_seg_start, sub, nsel); if (rc != ITSX_OK) return rc; }
     const bool last = round == 1;
     if (sub.NP == 0) {
       ms_sel += tm_r.stop();
       if (last && next_msv) { const int rc = (*next_msv)(); if (rc != ITSX_OK) return rc; }
       continue;
     }
-    HIPCHK(ctx->l_pairs.alloc((size_t)sub.NP)); HIPCHK(ctx->d_pout.alloc((size_t)sub.NP));
-    HIPCHK(hipMemsetAsync(ctx->l_pairs.p, 0xFF, (size_t)sub.NP * sizeof(PairRec), st));
-    HIPCHK(hipMemsetAsync(ctx->d_pout.p, 0, (size_t)sub.NP * sizeof(PairOut), st));
-    HIPCHK(upload(ctx->l_seg, sub.seg_start, st));
-    launch_lazy_scatter(pl.pairs, NP, ctx->l_flag.p, ctx->l_pos.p, pl.d_seg_start, ctx->l_seg.p, ctx->l_pairs.p, st);
-    sub.pairs = ctx->l_pairs.p; sub.pout = ctx->d_pout.p; sub.d_seg_start = ctx->l_seg.p;
     ms_sel += tm_r.stop();
     S.n_lazy_evaluated += nsel;
     if (round == 0) S.n_lazy_round1 += nsel;
@@ -3758,17 +3793,18 @@ static int lazy_topup(itsx_ctx *ctx, double domE, bool *ran)
   std::vector<unsigned long long> ndone;
   { const int rc = count_done(ndone); if (rc != ITSX_OK) return rc; }
   // the unevaluated pairs of those profiles, compact (a few per cent of the list), then ordered by (profile, bound descending)
-  launch_topup_keys(ctx->d_pairs.p, NP, ctx->l_done.p, ctx->l_b10.p, ctx->l_slot.p, ctx->l_flag.p, nullptr, nullptr, nullptr, st);
-  launch_exclusive_scan(ctx->l_flag.p, ctx->l_pos.p, NP + 1, ctx->l_scan.p, st);
+  const int64_t nch = (NP + 63) >> 6;                           // (the chunk buffers are lazy_rounds' own: the same list)
+  launch_topup_keys(ctx->d_pairs.p, NP, ctx->l_done.p, ctx->l_b10.p, ctx->l_slot.p, ctx->l_smask.p, ctx->l_scnt.p, nullptr, nullptr, nullptr, st);
+  launch_exclusive_scan(ctx->l_scnt.p, ctx->l_spos.p, nch + 1, ctx->l_scan.p, st);
   int32_t M32 = 0;
-  HIPCHK(hipMemcpyAsync(&M32, ctx->l_pos.p + NP, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&M32, ctx->l_spos.p + nch, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   const int64_t M = M32;
   if (M <= 0) return ITSX_OK;
   HIPCHK(ctx->sh_keys.alloc((size_t)M + 1)); HIPCHK(ctx->sh_keys2.alloc((size_t)M + 1)); HIPCHK(ctx->sh_vals.alloc((size_t)M + 1)); HIPCHK(ctx->sh_uorder.alloc((size_t)M + 1));
   const size_t sort_bytes = order_sort_bytes(M);
   HIPCHK(ctx->sh_sorttmp.alloc(sort_bytes));
-  launch_topup_keys(ctx->d_pairs.p, NP, ctx->l_done.p, ctx->l_b10.p, ctx->l_slot.p, ctx->l_flag.p, ctx->l_pos.p, ctx->sh_keys.p, ctx->sh_vals.p, st);
+  launch_topup_keys(ctx->d_pairs.p, NP, ctx->l_done.p, ctx->l_b10.p, ctx->l_slot.p, ctx->l_smask.p, ctx->l_scnt.p, ctx->l_spos.p, ctx->sh_keys.p, ctx->sh_vals.p, st);
   if (order_sort(ctx->sh_sorttmp.p, sort_bytes, ctx->sh_keys.p, ctx->sh_keys2.p, ctx->sh_vals.p, ctx->sh_uorder.p, M, st) != 0) SET_ERR(ctx, ITSX_E_DEVICE, "top-up round: the radix sort failed");
   HIPCHK(hipStreamSynchronize(st));
   auto lower = [&](unsigned long long key, int64_t &pos) -> int {       // binary search over device memory: ~24 eight-byte copies per probe
@@ -3827,28 +3863,10 @@ static int lazy_topup(itsx_ctx *ctx, double domE, bool *ran)
   }
   if (!any) return ITSX_OK;
   HIPCHK(upload(ctx->l_cut, cut, st));
-  launch_topup_mark(ctx->d_pairs.p, NP, ctx->l_done.p, ctx->l_b10.p, ctx->l_slot.p, ctx->l_cut.p, ctx->l_flag.p, st);
-  launch_exclusive_scan(ctx->l_flag.p, ctx->l_pos.p, NP + 1, ctx->l_scan.p, st);
-  std::vector<int32_t> bound((size_t)P + 1);
-  {
-    DBuf<int32_t> &d_b = ctx->w_b;
-    HIPCHK(d_b.alloc((size_t)P + 1));
-    hipLaunchKernelGGL(k_gather_i32, dim3((P + 1 + 255) / 256), dim3(256), 0, st, ctx->l_pos.p, ctx->w_idx.p, P + 1, d_b.p);
-    HIPCHK(hipMemcpyAsync(bound.data(), d_b.p, ((size_t)P + 1) * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  PairList sub;
-  sub.seg_start.assign((size_t)P + 1, 0); sub.total.assign((size_t)P, 0);
-  for (int p = 0; p < P; p++) { sub.total[(size_t)p] = bound[(size_t)p + 1] - bound[(size_t)p]; sub.seg_start[(size_t)p + 1] = sub.seg_start[(size_t)p] + ((int64_t)sub.total[(size_t)p] + 63) / 64 * 64; }
-  sub.NP = sub.seg_start[(size_t)P];
-  const int64_t nsel = (int64_t)bound[(size_t)P] - bound[0];
+  launch_topup_mark(ctx->d_pairs.p, NP, ctx->l_done.p, ctx->l_b10.p, ctx->l_slot.p, ctx->l_cut.p, ctx->l_smask.p, ctx->l_scnt.p, st);
+  PairList sub; int64_t nsel = 0;
+  { const int rc = select_compact(ctx, ctx->d_pairs.p, NP, P, tu.seg_start, ctx->w_seg_start.p, sub, nsel); if (rc != ITSX_OK) return rc; }
   if (sub.NP == 0) return ITSX_OK;
-  HIPCHK(ctx->l_pairs.alloc((size_t)sub.NP)); HIPCHK(ctx->d_pout.alloc((size_t)sub.NP));
-  HIPCHK(hipMemsetAsync(ctx->l_pairs.p, 0xFF, (size_t)sub.NP * sizeof(PairRec), st));
-  HIPCHK(hipMemsetAsync(ctx->d_pout.p, 0, (size_t)sub.NP * sizeof(PairOut), st));
-  HIPCHK(upload(ctx->l_seg, sub.seg_start, st));
-  launch_lazy_scatter(ctx->d_pairs.p, NP, ctx->l_flag.p, ctx->l_pos.p, ctx->w_seg_start.p, ctx->l_seg.p, ctx->l_pairs.p, st);
-  sub.pairs = ctx->l_pairs.p; sub.pout = ctx->d_pout.p; sub.d_seg_start = ctx->l_seg.p;
   const int32_t *d_sorted = (ctx->share_on ? ctx->sh_order.p : ctx->d_sorted_uniq.p) + tu.u0;
   ctx->trace_u0 = tu.u0;
   { StageTimer tp(st); const int rc = domain_pipeline(ctx, sub, d_sorted, ctx->T, ctx->sF1, ctx->sF3, nullptr); if (rc != ITSX_OK) return rc; S.ms_lazy_topup_stages += tp.stop(); }
@@ -6149,6 +6167,135 @@ int itsx_debug_logf(itsx_ctx *ctx, const float *x, int64_t n, float *out)
     HIPCHK(hipMemcpyAsync(out, dy.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
   }
   HIPCHK(hipStreamSynchronize(ctx->st));
+  return ITSX_OK;
+}
+
+int itsx_debug_scan(itsx_ctx *ctx, const int32_t *in, int64_t n, int32_t *out, int in_place)
+{
+  CTXCHK(ctx && n >= 0 && n < ((int64_t)1 << 31) && (n == 0 || (in && out)));
+  HIPCHK(hipSetDevice(ctx->device));
+  if (n == 0) return ITSX_OK;
+  DBuf<int32_t> din, dout, tmp;
+  HIPCHK(din.alloc((size_t)n)); HIPCHK(dout.alloc((size_t)n)); HIPCHK(tmp.alloc((size_t)scan_tmp_elems(n)));
+  HIPCHK(hipMemcpyAsync(din.p, in, (size_t)n * 4, hipMemcpyHostToDevice, ctx->st));
+  int32_t *res = in_place ? din.p : dout.p;
+  launch_exclusive_scan(din.p, res, n, tmp.p, ctx->st);
+  HIPCHK(hipMemcpyAsync(out, res, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  HIPCHK(hipGetLastError());
+  return ITSX_OK;
+}
+
+int itsx_debug_select(itsx_ctx *ctx, int mode, const int32_t *pairs, int64_t NP, const int64_t *seg_start, int32_t P, uint8_t *done, const uint32_t *b10,
+                      const int8_t *cls, int32_t ncls, const unsigned long long *group, int64_t n_group, const int32_t *sorted_uniq, int64_t n_sorted,
+                      const int32_t *slot_of_prof, const uint32_t *cutoff, int32_t n_slots, int64_t *out_seg, int32_t *out_pairs, int64_t out_cap,
+                      unsigned long long *out_keys, int32_t *out_vals, int64_t *out_n)
+{
+  CTXCHK(ctx && mode >= 0 && mode <= 3 && pairs && NP > 0 && NP < ((int64_t)1 << 31) && seg_start && P > 0 && done && b10 && out_n && out_cap >= 0);
+  CTXCHK(mode > 1 || (cls && ncls > 0 && group && n_group > 0 && (mode == 0 || (sorted_uniq && n_sorted > 0))));
+  CTXCHK(mode <= 1 || (slot_of_prof && n_slots > 0 && (mode == 3 || cutoff)));
+  CTXCHK(mode <= 2 ? (out_seg && out_pairs) : (out_keys && out_vals));
+  // every index a kernel follows is checked here: the lists are a test's own
+  const PairRec *hp = (const PairRec *)pairs;
+  if (seg_start[0] != 0 || seg_start[P] != NP) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_select: the segments do not cover the list");
+  for (int p = 0; p < P; p++) {
+    if (seg_start[p + 1] < seg_start[p] || (seg_start[p + 1] & 63)) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_select: segment " + std::to_string(p) + " is not a whole number of chunks of 64");
+    if (mode >= 2 && (slot_of_prof[p] < -1 || slot_of_prof[p] >= n_slots)) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_select: slot of profile " + std::to_string(p));
+    if (mode <= 1 && (cls[p] < 0 || cls[p] >= ncls)) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_select: class of profile " + std::to_string(p));
+    for (int64_t i = seg_start[p]; i < seg_start[p + 1]; i++) {
+      const PairRec &r = hp[i];
+      if (r.prof < 0) continue;
+      bool ok = r.prof == p && r.useq >= 0;
+      if (ok && mode == 0) ok = (int64_t)r.useq * ncls + cls[p] < n_group;
+      if (ok && mode == 1) ok = r.useq < n_sorted && sorted_uniq[r.useq] >= 0 && (int64_t)sorted_uniq[r.useq] * ncls + cls[p] < n_group;
+      if (!ok) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_select: pair " + std::to_string(i) + " points outside the tables");
+    }
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  DBuf<PairRec> dp; DBuf<uint8_t> dd; DBuf<uint32_t> db, dcut; DBuf<int8_t> dcls; DBuf<unsigned long long> dg; DBuf<int32_t> dsu, dslot; DBuf<int64_t> dseg;
+  HIPCHK(dp.alloc((size_t)NP)); HIPCHK(dd.alloc((size_t)NP)); HIPCHK(db.alloc((size_t)NP)); HIPCHK(dseg.alloc((size_t)P + 1));
+  HIPCHK(hipMemcpyAsync(dp.p, pairs, (size_t)NP * sizeof(PairRec), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dd.p, done, (size_t)NP, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(db.p, b10, (size_t)NP * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dseg.p, seg_start, ((size_t)P + 1) * 8, hipMemcpyHostToDevice, st));
+  if (mode <= 1) {
+    HIPCHK(dcls.alloc((size_t)P)); HIPCHK(dg.alloc((size_t)n_group));
+    HIPCHK(hipMemcpyAsync(dcls.p, cls, (size_t)P, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dg.p, group, (size_t)n_group * 8, hipMemcpyHostToDevice, st));
+    if (mode == 1) { HIPCHK(dsu.alloc((size_t)n_sorted)); HIPCHK(hipMemcpyAsync(dsu.p, sorted_uniq, (size_t)n_sorted * 4, hipMemcpyHostToDevice, st)); }
+  } else {
+    HIPCHK(dslot.alloc((size_t)P)); HIPCHK(dcut.alloc((size_t)2 * n_slots));
+    HIPCHK(hipMemcpyAsync(dslot.p, slot_of_prof, (size_t)P * 4, hipMemcpyHostToDevice, st));
+    if (cutoff) HIPCHK(hipMemcpyAsync(dcut.p, cutoff, (size_t)2 * n_slots * 4, hipMemcpyHostToDevice, st));
+  }
+  { const int rc = select_alloc(ctx, NP); if (rc != ITSX_OK) return rc; }
+  if (mode == 3) {
+    const int64_t nch = NP >> 6;
+    launch_topup_keys(dp.p, NP, dd.p, db.p, dslot.p, ctx->l_smask.p, ctx->l_scnt.p, nullptr, nullptr, nullptr, st);
+    launch_exclusive_scan(ctx->l_scnt.p, ctx->l_spos.p, nch + 1, ctx->l_scan.p, st);
+    int32_t M = 0;
+    HIPCHK(hipMemcpyAsync(&M, ctx->l_spos.p + nch, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *out_n = M;
+    if (M > 0 && M <= out_cap) {
+      DBuf<unsigned long long> dk; DBuf<int32_t> dv;
+      HIPCHK(dk.alloc((size_t)M)); HIPCHK(dv.alloc((size_t)M));
+      launch_topup_keys(dp.p, NP, dd.p, db.p, dslot.p, ctx->l_smask.p, ctx->l_scnt.p, ctx->l_spos.p, dk.p, dv.p, st);
+      HIPCHK(hipMemcpyAsync(out_keys, dk.p, (size_t)M * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(out_vals, dv.p, (size_t)M * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+    HIPCHK(hipGetLastError());
+    return ITSX_OK;
+  }
+  if (mode <= 1) {
+    LazyArgs la{};
+    la.pairs = dp.p; la.NP = NP; la.cls = dcls.p; la.ncls = ncls; la.sorted_uniq = dsu.p; la.b10 = db.p;
+    la.gtop = mode == 0 ? dg.p : nullptr; la.ngroups = mode == 0 ? n_group : 0; la.bestc = mode == 1 ? dg.p : nullptr; la.done = dd.p; la.smask = ctx->l_smask.p; la.scnt = ctx->l_scnt.p;
+    launch_lazy_mark(la, mode, st);
+  } else launch_topup_mark(dp.p, NP, dd.p, db.p, dslot.p, dcut.p, ctx->l_smask.p, ctx->l_scnt.p, st);
+  PairList sub; int64_t nsel = 0;
+  const std::vector<int64_t> hseg(seg_start, seg_start + P + 1);
+  { const int rc = select_compact(ctx, dp.p, NP, P, hseg, dseg.p, sub, nsel); if (rc != ITSX_OK) return rc; }
+  for (int p = 0; p <= P; p++) out_seg[p] = sub.seg_start[(size_t)p];
+  *out_n = sub.NP;
+  HIPCHK(hipMemcpyAsync(done, dd.p, (size_t)NP, hipMemcpyDeviceToHost, st));
+  if (sub.NP > 0 && sub.NP <= out_cap) HIPCHK(hipMemcpyAsync(out_pairs, sub.pairs, (size_t)sub.NP * sizeof(PairRec), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  return ITSX_OK;
+}
+
+int itsx_debug_region_keys(itsx_ctx *ctx, const int32_t *regions, int64_t n_regions, const int32_t *pairs, int64_t n_pairs, int32_t *rep_region, int32_t *is_uniq)
+{
+  CTXCHK(ctx && regions && n_regions > 0 && n_regions < ((int64_t)1 << 30) && pairs && n_pairs > 0 && rep_region && is_uniq);
+  if (ctx->N <= 0) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_region_keys: no reads are loaded");
+  const RegionRec *hr = (const RegionRec *)regions; const PairRec *hp = (const PairRec *)pairs;
+  for (int64_t g = 0; g < n_regions; g++) {
+    if (hr[g].pair < 0) continue;
+    bool ok = hr[g].pair < n_pairs;
+    if (ok) { const PairRec &r = hp[hr[g].pair]; ok = r.useq >= 0 && r.useq < ctx->N && hr[g].ienv >= 1 && hr[g].jenv >= hr[g].ienv && hr[g].jenv <= ctx->h_len[(size_t)r.useq]; }
+    if (!ok) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_region_keys: region " + std::to_string(g) + " points outside its read");
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  std::vector<int32_t> ident((size_t)ctx->N);
+  std::iota(ident.begin(), ident.end(), 0);
+  DBuf<RegionRec> dr; DBuf<PairRec> dp; DBuf<int32_t> did, dvals, drep, duq; DBuf<unsigned long long> dkeys; DBuf<uint32_t> dslot;
+  const uint64_t tsize = region_table_size(n_regions);
+  HIPCHK(dr.alloc((size_t)n_regions)); HIPCHK(dp.alloc((size_t)n_pairs)); HIPCHK(upload(did, ident, st));
+  HIPCHK(dkeys.alloc(tsize)); HIPCHK(dvals.alloc(tsize)); HIPCHK(dslot.alloc((size_t)n_regions)); HIPCHK(drep.alloc((size_t)n_regions)); HIPCHK(duq.alloc((size_t)n_regions));
+  HIPCHK(hipMemcpyAsync(dr.p, regions, (size_t)n_regions * sizeof(RegionRec), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dp.p, pairs, (size_t)n_pairs * sizeof(PairRec), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(dkeys.p, 0, tsize * sizeof(unsigned long long), st));
+  HIPCHK(hipMemsetAsync(dvals.p, 0x7f, tsize * sizeof(int32_t), st));
+  launch_region_keys(ctx->rd, dr.p, n_regions, dp.p, did.p, did.p, dkeys.p, dvals.p, tsize - 1, dslot.p, st);
+  launch_region_resolve(ctx->rd, dr.p, n_regions, dp.p, did.p, did.p, dvals.p, dslot.p, drep.p, duq.p, st);
+  HIPCHK(hipMemcpyAsync(rep_region, drep.p, (size_t)n_regions * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(is_uniq, duq.p, (size_t)n_regions * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
   return ITSX_OK;
 }
 

@@ -654,13 +654,16 @@ struct LazyArgs {
   const int32_t *sorted_uniq;      // chunk-relative useq -> global unique index
   uint32_t *b10;                   // [NP] largest %.1f tenths (+ LAZY_TENTHS_BIAS) a domain of the pair can print; 0 = no pair here
   unsigned long long *gtop;        // [chunk uniques x ncls] (b10 << 32 | ~pair) of the group's best-bound pair
+  int64_t ngroups;                 // chunk uniques x ncls
   const unsigned long long *bestc; // [uniques x ncls] rank key of the best CERTAIN row so far (k_compact_best)
   uint8_t *done;                   // [NP] the pair went through the domain stage already
-  int32_t *flag;                   // [NP + 1] selected for this round
+  unsigned long long *smask;       // [NP / 64] selected for this round: one bit per pair, one word per chunk of 64 pairs
+  int32_t *scnt;                   // [NP / 64 + 1] set bits of each chunk (the last one 0)
 };
 void launch_lazy_bound(const LazyArgs &a, hipStream_t st);
 void launch_lazy_mark(const LazyArgs &a, int round, hipStream_t st);
-void launch_lazy_scatter(const PairRec *pairs, int64_t NP, const int32_t *flag, const int32_t *pos, const int64_t *seg_old, const int64_t *seg_new,
+// spos = the exclusive scan of scnt; profile segments (seg_old) start at multiples of 64
+void launch_lazy_scatter(const PairRec *pairs, int64_t NP, const unsigned long long *smask, const int32_t *spos, const int64_t *seg_old, const int64_t *seg_new,
                          PairRec *out, hipStream_t st);
 // three-valued thresholds with bounds on hmmsearch's domZ: dom_reported = 1 reported for every domZ in [zlb, zub], 0 for none, 2 = depends
 void launch_finalize_lazy(itsx_domain *dom, int64_t n, const int64_t *zlb, const int64_t *zub, double domE, const int32_t *usample, int P, hipStream_t st);
@@ -669,8 +672,8 @@ void launch_lazy_sure(const itsx_domain *dom, int64_t n, const int8_t *cls, int 
 void launch_lazy_pending(const itsx_domain *dom, int64_t n, const int8_t *cls, int ncls, const unsigned long long *sure, const int32_t *has,
                          unsigned long long *count, int32_t *prof_flag, uint8_t *uniq_flag, unsigned long long *zneed /*[2 P] or nullptr*/, const unsigned long long *zsplit /*[P]*/, double domE, hipStream_t st);
 void launch_topup_count(const uint8_t *done, const int64_t *seg_start, const int32_t *total, const int32_t *prof_of_slot, int nslots, unsigned long long *cnt, hipStream_t st);
-void launch_topup_keys(const PairRec *pairs, int64_t NP, const uint8_t *done, const uint32_t *b10, const int32_t *slot_of_prof, int32_t *flag, const int32_t *pos /*nullptr: flags only*/,
+void launch_topup_keys(const PairRec *pairs, int64_t NP, const uint8_t *done, const uint32_t *b10, const int32_t *slot_of_prof, unsigned long long *smask, int32_t *scnt, const int32_t *spos /*nullptr: marks only*/,
                        unsigned long long *keys, int32_t *vals, hipStream_t st);
-void launch_topup_mark(const PairRec *pairs, int64_t NP, uint8_t *done, const uint32_t *b10, const int32_t *slot_of_prof, const uint32_t *cutoff, int32_t *flag, hipStream_t st);
+void launch_topup_mark(const PairRec *pairs, int64_t NP, uint8_t *done, const uint32_t *b10, const int32_t *slot_of_prof, const uint32_t *cutoff, unsigned long long *smask, int32_t *scnt, hipStream_t st);
 
 }  // namespace itsx

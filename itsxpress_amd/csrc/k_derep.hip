@@ -347,24 +347,53 @@ __device__ __forceinline__ RegKey make_regkey(const ReadsDev &rd, int read, int 
   return k;
 }
 
+// Amplicon regions are massive duplicates: most regions find their key in the table already, under a smaller index.  So the lanes of a
+// wave that hold the same key send ONE of them (the lowest lane = the smallest index: g ascends with the lane) to the table, that lane
+// reads the slot before it issues an atomic -- no CAS where the key stands already, no atomicMin where the index there is already
+// smaller (it only ever falls: a stale read costs a redundant atomic, never a wrong one) --, and the others take its slot.
 __global__ void __launch_bounds__(256) k_region_keys(ReadsDev rd, const RegionRec *__restrict__ regions, int64_t nr, const PairRec *__restrict__ pairs,
                                                      const int32_t *__restrict__ sorted_uniq, const int32_t *__restrict__ seed_read,
                                                      unsigned long long *__restrict__ keys, int32_t *__restrict__ vals, uint64_t mask,
                                                      uint32_t *__restrict__ slot_of)
 {
-  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < nr; g += (int64_t)gridDim.x * blockDim.x) {
-    const RegionRec rg = regions[g];
-    if (rg.pair < 0) { slot_of[g] = 0xFFFFFFFFu; continue; }
-    const PairRec pr = pairs[rg.pair];
-    const RegKey rk = make_regkey(rd, seed_read[sorted_uniq[pr.useq]], rg.ienv, rg.jenv, pr.prof, pr.L);
-    uint64_t key = xxh64_words(rk, rk.nwd + rk.nex_in + 3, 0x9E3779B97F4A7C15ULL);
-    if (key == 0) key = 1;
-    uint64_t slot = (key * 0x9E3779B97F4A7C15ULL >> 20) & mask;
-    for (;;) {
-      const unsigned long long old = atomicCAS(&keys[slot], 0ull, (unsigned long long)key);
-      if (old == 0ull || old == key) { atomicMin(&vals[slot], (int32_t)g); slot_of[g] = (uint32_t)slot; break; }
-      slot = (slot + 1) & mask;
+  const int lane = threadIdx.x & 63;
+  // (whole waves walk the loop together: the block and the stride are multiples of 64)
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g - lane < nr; g += (int64_t)gridDim.x * blockDim.x) {
+    uint64_t key = 0;                                           // 0: no region here
+    if (g < nr) {
+      const RegionRec rg = regions[g];
+      if (rg.pair < 0) slot_of[g] = 0xFFFFFFFFu;
+      else {
+        const PairRec pr = pairs[rg.pair];
+        const RegKey rk = make_regkey(rd, seed_read[sorted_uniq[pr.useq]], rg.ienv, rg.jenv, pr.prof, pr.L);
+        key = xxh64_words(rk, rk.nwd + rk.nex_in + 3, 0x9E3779B97F4A7C15ULL);
+        if (key == 0) key = 1;
+      }
     }
+    // the lowest lane of every distinct key leads it
+    unsigned long long todo = __ballot(key != 0);
+    int leader = lane;
+    while (todo) {
+      const int l0 = __builtin_ctzll(todo);
+      const uint64_t k0 = ((uint64_t)(uint32_t)__shfl((int)(key >> 32), l0, 64) << 32) | (uint64_t)(uint32_t)__shfl((int)key, l0, 64);
+      const unsigned long long same = __ballot(key == k0) & todo;
+      if (key == k0) leader = l0;
+      todo &= ~same;
+    }
+    uint32_t myslot = 0;
+    if (key != 0 && leader == lane) {
+      uint64_t slot = (key * 0x9E3779B97F4A7C15ULL >> 20) & mask;
+      for (;;) {
+        unsigned long long cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == 0ull) { cur = atomicCAS(&keys[slot], 0ull, (unsigned long long)key); if (cur == 0ull) cur = key; }
+        if (cur == key) break;
+        slot = (slot + 1) & mask;
+      }
+      if (__hip_atomic_load(&vals[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (int32_t)g) atomicMin(&vals[slot], (int32_t)g);
+      myslot = (uint32_t)slot;
+    }
+    myslot = (uint32_t)__shfl((int)myslot, leader, 64);
+    if (key != 0) slot_of[g] = myslot;
   }
 }
 // rep_region[g] = smallest region index with the same key AND the same content; is_uniq[g] = (rep == g).

@@ -502,37 +502,78 @@ __global__ void __launch_bounds__(256) k_lazy_bound(LazyArgs a)
   atomicMax(&a.gtop[g], ((unsigned long long)b << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i));
 }
 
-// round 0: the best-bound pair of each group.  round 1: everything not yet evaluated that could still beat (or tie with) the
-// group's best certain row; all of a group that has none.
-__global__ void __launch_bounds__(256) k_lazy_mark(LazyArgs a, int round)
+// ---- selection: a round's pairs are marked in ONE bit each (smask[c] = the ballot of chunk c = pairs [64 c, 64 c + 64), scnt[c] its
+// popcount; scnt[nch] = 0 so that the scan's last element is the total), the chunk counts are scanned (NP / 64 elements), and the set
+// bits are scattered.  Profile segments start at multiples of 64: a chunk lies inside one segment, and the rank of a pair inside its
+// profile is spos[its chunk] + the set bits below it - spos[the segment's first chunk].
+__device__ __forceinline__ void select_store(int64_t i, int64_t nch, int f, unsigned long long *__restrict__ smask, int32_t *__restrict__ scnt)
+{
+  const unsigned long long m = __ballot(f);
+  if ((threadIdx.x & 63) == 0) {
+    const int64_t c = i >> 6;
+    if (c < nch) smask[c] = m;
+    scnt[c] = (int32_t)__popcll(m);      // (chunk nch: no pair, 0)
+  }
+}
+
+// round 0: the best-bound pair of each group, taken from the GROUPS (a few per cent as many as there are pairs): gtop names the pair,
+// the pair's record confirms that it is one of the group's (so the selection is what asking every pair "am I my group's best?" gives,
+// whatever the table holds), and its bit goes into the zeroed masks; k_select_count then counts each chunk's bits.
+__global__ void __launch_bounds__(256) k_lazy_first(LazyArgs a)
+{
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= a.ngroups) return;
+  const unsigned long long top = a.gtop[g];
+  const int64_t i = (int64_t)(0xFFFFFFFFu - (uint32_t)(top & 0xFFFFFFFFull));
+  if (i >= a.NP) return;                                        // (an empty group: top == 0)
+  const PairRec pr = a.pairs[i];
+  if (pr.prof < 0 || a.done[i] || (int64_t)pr.useq * a.ncls + a.cls[pr.prof] != g) return;
+  a.done[i] = 1;
+  atomicOr(&a.smask[i >> 6], 1ull << (i & 63));
+}
+__global__ void __launch_bounds__(256) k_select_count(const unsigned long long *__restrict__ smask, int64_t nch, int32_t *__restrict__ scnt)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c <= nch) scnt[c] = c < nch ? (int32_t)__popcll(smask[c]) : 0;
+}
+// round 1: everything not yet evaluated that could still beat (or tie with) the group's best certain row; all of a group that has none.
+__global__ void __launch_bounds__(256) k_lazy_mark(LazyArgs a)
 {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > a.NP) return;
+  const int64_t nch = (a.NP + 63) >> 6;
+  if ((i >> 6) > nch) return;                                   // (whole waves)
   int f = 0;
   if (i < a.NP) {
     const PairRec pr = a.pairs[i];
     if (pr.prof >= 0 && !a.done[i]) {
-      const int c = a.cls[pr.prof];
-      if (round == 0) f = (uint32_t)(a.gtop[(size_t)pr.useq * a.ncls + c] & 0xFFFFFFFFull) == 0xFFFFFFFFu - (uint32_t)i;
-      else {
-        const unsigned long long bc = a.bestc[(size_t)a.sorted_uniq[pr.useq] * a.ncls + c];
-        f = bc == 0ull || a.b10[i] >= (uint32_t)(bc >> 40);
-      }
+      const unsigned long long bc = a.bestc[(size_t)a.sorted_uniq[pr.useq] * a.ncls + a.cls[pr.prof]];
+      f = bc == 0ull || a.b10[i] >= (uint32_t)(bc >> 40);
       if (f) a.done[i] = 1;
     }
   }
-  a.flag[i] = f;
+  select_store(i, nch, f, a.smask, a.scnt);
 }
 
-// selected pairs keep their profile segment and their order inside it (ascending length): out[seg_new[p] + rank inside p]
-__global__ void __launch_bounds__(256) k_lazy_scatter(const PairRec *__restrict__ pairs, int64_t NP, const int32_t *__restrict__ flag,
-                                                      const int32_t *__restrict__ pos, const int64_t *__restrict__ seg_old,
+// selected pairs keep their profile segment and their order inside it (ascending length): out[seg_new[p] + rank inside p].
+// One wave takes SCATTER_CHUNKS chunks, one after the other; a chunk without a set bit costs it one 8-byte load.
+constexpr int SCATTER_CHUNKS = 16;
+__global__ void __launch_bounds__(256) k_lazy_scatter(const PairRec *__restrict__ pairs, int64_t NP, const unsigned long long *__restrict__ smask,
+                                                      const int32_t *__restrict__ spos, const int64_t *__restrict__ seg_old,
                                                       const int64_t *__restrict__ seg_new, PairRec *__restrict__ out)
 {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= NP || !flag[i]) return;
-  const PairRec pr = pairs[i];
-  out[seg_new[pr.prof] + (int64_t)(pos[i] - pos[seg_old[pr.prof]])] = pr;
+  const int lane = threadIdx.x & 63;
+  const int64_t nch = (NP + 63) >> 6;
+  const int64_t c0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * SCATTER_CHUNKS;
+  for (int k = 0; k < SCATTER_CHUNKS; k++) {
+    const int64_t c = c0 + k;
+    if (c >= nch) return;
+    const unsigned long long m = smask[c];
+    if (!((m >> lane) & 1ull)) continue;
+    const int64_t i = c * 64 + lane;                            // (< NP: a bit is set only for a pair)
+    const PairRec pr = pairs[i];
+    const int32_t rank = spos[c] + (int32_t)__popcll(m & ((1ull << lane) - 1ull)) - spos[seg_old[pr.prof] >> 6];
+    out[seg_new[pr.prof] + (int64_t)rank] = pr;
+  }
 }
 
 __global__ void __launch_bounds__(256) k_finalize_lazy(itsx_domain *__restrict__ dom, int64_t n, const int64_t *__restrict__ zlb,
@@ -602,12 +643,18 @@ void launch_lazy_bound(const LazyArgs &a, hipStream_t st)
 }
 void launch_lazy_mark(const LazyArgs &a, int round, hipStream_t st)
 {
-  hipLaunchKernelGGL(k_lazy_mark, dim3((unsigned)((a.NP + 1 + 255) / 256)), dim3(256), 0, st, a, round);
+  const int64_t nch = (a.NP + 63) >> 6;
+  if (round == 0) {
+    (void)hipMemsetAsync(a.smask, 0, (size_t)nch * sizeof(unsigned long long), st);
+    if (a.ngroups > 0) hipLaunchKernelGGL(k_lazy_first, dim3((unsigned)((a.ngroups + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_select_count, dim3((unsigned)((nch + 1 + 255) / 256)), dim3(256), 0, st, a.smask, nch, a.scnt);
+  } else hipLaunchKernelGGL(k_lazy_mark, dim3((unsigned)((nch * 64 + 64 + 255) / 256)), dim3(256), 0, st, a);
 }
-void launch_lazy_scatter(const PairRec *pairs, int64_t NP, const int32_t *flag, const int32_t *pos, const int64_t *seg_old, const int64_t *seg_new,
+void launch_lazy_scatter(const PairRec *pairs, int64_t NP, const unsigned long long *smask, const int32_t *spos, const int64_t *seg_old, const int64_t *seg_new,
                          PairRec *out, hipStream_t st)
 {
-  if (NP > 0) hipLaunchKernelGGL(k_lazy_scatter, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, st, pairs, NP, flag, pos, seg_old, seg_new, out);
+  const int64_t nch = (NP + 63) >> 6, per_block = 4 * SCATTER_CHUNKS;
+  if (NP > 0) hipLaunchKernelGGL(k_lazy_scatter, dim3((unsigned)((nch + per_block - 1) / per_block)), dim3(256), 0, st, pairs, NP, smask, spos, seg_old, seg_new, out);
 }
 void launch_finalize_lazy(itsx_domain *dom, int64_t n, const int64_t *zlb, const int64_t *zub, double domE, const int32_t *usample, int P, hipStream_t st)
 {
@@ -639,28 +686,40 @@ void launch_topup_count(const uint8_t *done, const int64_t *seg_start, const int
 }
 
 // ---- the top-up round (itsx_search_finalize): the unevaluated pairs of the profiles that have undecided rows, best bound first
-// pass 0 (pos == nullptr): flag[i] = the pair belongs to a profile with undecided rows and has not been evaluated; pass 1: its key
-// [slot | ~bound] into the compact list at pos[i]
+// pass 0 (spos == nullptr): the bit of pair i = it belongs to a profile with undecided rows and has not been evaluated (smask / scnt as in
+// k_lazy_mark); pass 1: the key [slot | ~bound] of every marked pair into the compact list at its rank
 __global__ void __launch_bounds__(256) k_topup_keys(const PairRec *__restrict__ pairs, int64_t NP, const uint8_t *__restrict__ done, const uint32_t *__restrict__ b10,
-                                                    const int32_t *__restrict__ slot_of_prof, int32_t *__restrict__ flag, const int32_t *__restrict__ pos,
-                                                    unsigned long long *__restrict__ keys, int32_t *__restrict__ vals)
+                                                    const int32_t *__restrict__ slot_of_prof, unsigned long long *__restrict__ smask, int32_t *__restrict__ scnt,
+                                                    const int32_t *__restrict__ spos, unsigned long long *__restrict__ keys, int32_t *__restrict__ vals)
 {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > NP) return;
-  int f = 0, sl = -1;
-  if (i < NP) {
-    const PairRec pr = pairs[i];
-    if (pr.prof >= 0 && pr.xj >= 0 && !done[i]) { sl = slot_of_prof[pr.prof]; f = sl >= 0; }
+  const int64_t nch = (NP + 63) >> 6;
+  if ((i >> 6) > nch) return;
+  if (!spos) {
+    int f = 0;
+    if (i < NP) {
+      const PairRec pr = pairs[i];
+      if (pr.prof >= 0 && pr.xj >= 0 && !done[i]) f = slot_of_prof[pr.prof] >= 0;
+    }
+    select_store(i, nch, f, smask, scnt);
+    return;
   }
-  if (!pos) { flag[i] = f; return; }
-  if (f) { keys[pos[i]] = ((unsigned long long)sl << 32) | (unsigned long long)(0xFFFFFFFFu - b10[i]); vals[pos[i]] = (int32_t)i; }
+  if ((i >> 6) >= nch) return;
+  const int lane = threadIdx.x & 63;
+  const unsigned long long m = smask[i >> 6];
+  if (!((m >> lane) & 1ull)) return;
+  const int32_t at = spos[i >> 6] + (int32_t)__popcll(m & ((1ull << lane) - 1ull));
+  const int sl = slot_of_prof[pairs[i].prof];
+  keys[at] = ((unsigned long long)sl << 32) | (unsigned long long)(0xFFFFFFFFu - b10[i]); vals[at] = (int32_t)i;
 }
 __global__ void __launch_bounds__(256) k_topup_mark(const PairRec *__restrict__ pairs, int64_t NP, uint8_t *__restrict__ done, const uint32_t *__restrict__ b10,
-                                                    const int32_t *__restrict__ slot_of_prof, const uint32_t *__restrict__ cutoff, int32_t *__restrict__ flag)
+                                                    const int32_t *__restrict__ slot_of_prof, const uint32_t *__restrict__ cutoff,
+                                                    unsigned long long *__restrict__ smask, int32_t *__restrict__ scnt)
 {
   // cutoff[2 slot] > 0: the pairs whose bound is at least that (the best ones); cutoff[2 slot + 1] > 0: those whose bound is at most that
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > NP) return;
+  const int64_t nch = (NP + 63) >> 6;
+  if ((i >> 6) > nch) return;
   int f = 0;
   if (i < NP) {
     const PairRec pr = pairs[i];
@@ -670,16 +729,19 @@ __global__ void __launch_bounds__(256) k_topup_mark(const PairRec *__restrict__ 
     }
     if (f) done[i] = 1;
   }
-  flag[i] = f;
+  select_store(i, nch, f, smask, scnt);
 }
-void launch_topup_keys(const PairRec *pairs, int64_t NP, const uint8_t *done, const uint32_t *b10, const int32_t *slot_of_prof, int32_t *flag, const int32_t *pos,
-                       unsigned long long *keys, int32_t *vals, hipStream_t st)
+// (every marking launch covers chunk nch as well: its count, 0, makes the scan's last element the total)
+static inline unsigned select_grid(int64_t NP) { return (unsigned)((((NP + 63) >> 6) * 64 + 64 + 255) / 256); }
+void launch_topup_keys(const PairRec *pairs, int64_t NP, const uint8_t *done, const uint32_t *b10, const int32_t *slot_of_prof, unsigned long long *smask, int32_t *scnt,
+                       const int32_t *spos, unsigned long long *keys, int32_t *vals, hipStream_t st)
 {
-  hipLaunchKernelGGL(k_topup_keys, dim3((unsigned)((NP + 1 + 255) / 256)), dim3(256), 0, st, pairs, NP, done, b10, slot_of_prof, flag, pos, keys, vals);
+  hipLaunchKernelGGL(k_topup_keys, dim3(select_grid(NP)), dim3(256), 0, st, pairs, NP, done, b10, slot_of_prof, smask, scnt, spos, keys, vals);
 }
-void launch_topup_mark(const PairRec *pairs, int64_t NP, uint8_t *done, const uint32_t *b10, const int32_t *slot_of_prof, const uint32_t *cutoff, int32_t *flag, hipStream_t st)
+void launch_topup_mark(const PairRec *pairs, int64_t NP, uint8_t *done, const uint32_t *b10, const int32_t *slot_of_prof, const uint32_t *cutoff,
+                       unsigned long long *smask, int32_t *scnt, hipStream_t st)
 {
-  hipLaunchKernelGGL(k_topup_mark, dim3((unsigned)((NP + 1 + 255) / 256)), dim3(256), 0, st, pairs, NP, done, b10, slot_of_prof, cutoff, flag);
+  hipLaunchKernelGGL(k_topup_mark, dim3(select_grid(NP)), dim3(256), 0, st, pairs, NP, done, b10, slot_of_prof, cutoff, smask, scnt);
 }
 
 }  // namespace itsx
