@@ -755,6 +755,16 @@ int itsx_debug_select(itsx_ctx *ctx, int mode, const int32_t *pairs, int64_t NP,
                       const int8_t *cls, int32_t ncls, const unsigned long long *group, int64_t n_group, const int32_t *sorted_uniq, int64_t n_sorted,
                       const int32_t *slot_of_prof, const uint32_t *cutoff, int32_t n_slots, int64_t *out_seg, int32_t *out_pairs, int64_t out_cap,
                       unsigned long long *out_keys, int32_t *out_vals, int64_t *out_n);
+/* The lazy stage's pair list with pass A's scores and the bounds made from them (k_lazy.hip: k_fwd_bound, k_lazy_bound), as the last
+ * itsx_search left them: only after a lazy search that ran as ONE chunk of one sample (what the top-up round of itsx_search_finalize
+ * reads, so also after that call unless it had to count a profile in full); any other state is ITSX_E_ARG.  Records come as they lie in
+ * the list, padding (prof < 0) and the pairs that ran for their row states only (xj < 0) included.  rep = the representative's index in
+ * itsx_get_uniques order (-1 on padding), fb = pass A's Forward score (nats), b10 = the biased %.1f tenths no domain of the pair can
+ * exceed (0 on padding and helpers), done = the pair went through the domain stage, nullsc / lazy_c = LenTables[L] as k_lazy_bound read
+ * them.  Returns the number of records (out is filled when cap holds them), or a negative ITSX_E_*; *tenths_bias (may be NULL) = the
+ * bias of b10. */
+typedef struct { int64_t rep; int32_t prof, L, xj; float fb; uint32_t b10; int32_t done; float nullsc, lazy_c; } itsx_lazy_pair;
+int64_t itsx_debug_lazy_pairs(itsx_ctx *ctx, itsx_lazy_pair *out, int64_t cap, int32_t *tenths_bias);
 /* The envelope memoisation's table (k_derep.hip: k_region_keys, k_region_resolve) over regions of the loaded reads: regions[n][4] =
  * (pair, ienv, jenv, multi), pair < 0 = none; pairs[n_pairs][4] as above with useq = the READ's index.  rep_region[g] = the smallest
  * region with g's profile, L and residues (-1: no region), is_uniq[g] = (rep_region[g] == g).  The table has the size a search gives it. */

@@ -32,6 +32,8 @@ DOMAIN_DTYPE = np.dtype([("rep", "<i8"), ("prof", "<i4"), ("tlen", "<i4"), ("ien
                          ("domcorrection", "<f4"), ("dombias", "<f4"), ("bitscore", "<f4"), ("lnP", "<f8"),
                          ("seq_score", "<f4"), ("seq_bias", "<f4"), ("seq_reported", "<i4"),
                          ("dom_reported", "<i4")], align=True)
+LAZY_PAIR_DTYPE = np.dtype([("rep", "<i8"), ("prof", "<i4"), ("L", "<i4"), ("xj", "<i4"), ("fb", "<f4"), ("b10", "<u4"), ("done", "<i4"),
+                            ("nullsc", "<f4"), ("lazy_c", "<f4")], align=True)      # itsx_lazy_pair (itsx_debug_lazy_pairs)
 TRACE_DTYPE = np.dtype([("rep", "<i8"), ("prof", "<i4"), ("msv_xj", "<i4"), ("pass_msv", "<i4"),
                         ("pass_bias", "<i4"), ("pass_fwd", "<i4"), ("msv_sc", "<f4"), ("filtersc", "<f4"),
                         ("fwdsc", "<f4"), ("bcksc", "<f4"), ("nullsc", "<f4"), ("nregions", "<i4"),
@@ -100,7 +102,7 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_inflate_device", "itsx_inflate_fetch", "itsx_debug_inflate_host", "itsx_debug_inflate_candidates", "itsx_debug_inflate_where", "itsx_set_device_inflate",
            "itsx_parse_device", "itsx_parse_fetch", "itsx_debug_parse_host", "itsx_set_device_parse",
            "itsx_debug_set_domains", "itsx_debug_get_rows",
-           "itsx_debug_scan", "itsx_debug_select", "itsx_debug_region_keys"]
+           "itsx_debug_scan", "itsx_debug_select", "itsx_debug_region_keys", "itsx_debug_lazy_pairs"]
 
 
 def lib():
@@ -237,6 +239,7 @@ def lib():
         "itsx_debug_scan": (i32, [vp, vp, i64, vp, i32]),
         "itsx_debug_select": (i32, [vp, i32, vp, i64, vp, i32, vp, vp, vp, i32, vp, i64, vp, i64, vp, vp, i32, vp, vp, i64, vp, vp, vp]),
         "itsx_debug_region_keys": (i32, [vp, vp, i64, vp, i64, vp, vp]),
+        "itsx_debug_lazy_pairs": (i64, [vp, vp, i64, vp]),
         "itsx_debug_calibrate": (i32, [vp, i32, f64, i32, vp, vp]),
         "itsx_debug_issue": (i32, [vp, i32, i32, i32, vp, vp]),
         "itsx_shard_text": (i32, [C.c_char_p, i32, vp, C.c_char_p, vp, vp]),

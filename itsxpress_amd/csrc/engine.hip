@@ -462,7 +462,7 @@ struct itsx_ctx {
   // batches' first positions (sh_bsegk_h), the slots of the saved Backward states behind the Forward ones in the DP slab
   std::string switches_at_search;
   // the top-up round of itsx_search_finalize (round 6): the last search's pair list, while it is still in the buffers (one chunk, one sample)
-  struct TopUp { bool valid = false; int64_t NP = 0; std::vector<int64_t> seg_start; std::vector<int32_t> total; int32_t u0 = 0, Uc = 0; } topup;
+  struct TopUp { bool valid = false, list_live = false /* d_pairs, l_fb, l_b10 and l_done still hold the list (itsx_debug_lazy_pairs) */; int64_t NP = 0; std::vector<int64_t> seg_start; std::vector<int32_t> total; int32_t u0 = 0, Uc = 0; } topup;
   DBuf<unsigned long long> l_zneed, l_zsplit, l_tcnt; DBuf<int32_t> l_slot, l_pslot; DBuf<uint32_t> l_cut;
   std::vector<unsigned long long> h_zneed;
   bool prev_lazy = false; int prev_P = 0; int64_t prev_U = 0, prev_Uc = 0;      // the last search's chunking (itsx_search)
@@ -2224,7 +2224,7 @@ int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
   S.n_pairs = (int64_t)U * P; S.n_past_msv = S.n_past_bias = S.n_past_fwd = S.n_regions = S.n_multidomain = S.n_domains = S.n_domain_overflow = 0;
   S.ms_msv = S.ms_filters = S.ms_domains = S.ms_msv_kernel = S.ms_fwd_kernel = S.ms_bwd_kernel = S.ms_env_kernel = S.ms_bias_kernel = S.ms_decode_kernel = 0; S.n_batches = 0; S.ms_ensemble = 0; S.n_mr_clustered = S.n_mr_distinct = S.n_mr_failed = S.n_mr_envelopes = 0; S.n_slab_shrinks = 0; S.n_mr_overflow = 0; S.ms_vit_kernel = 0; for (int k = 0; k < 8; k++) S.n_mr_fail_kind[k] = 0; S.n_rows_resident = 0; S.msv_cells = 0; S.msv_launches = 0; S.fwd_rows = 0; S.env_rows = 0; S.n_env_unique = 0;
   ctx->npairs_padded = 0; ctx->dom_n.clear(); ctx->trace_u0 = 0; ctx->n_chunks = 0;
-  ctx->have_search = true; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->injected = false;
+  ctx->have_search = true; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->topup.list_live = false; ctx->injected = false;
   // rows mode: what the caller selected (itsx_set_rows_mode), else the environment (ITSX_ROWS=full|compact|lazy; ITSX_COMPACT_ROWS=1)
   int mode = ctx->rows_mode;
   if (mode < 0) {
@@ -3304,7 +3304,7 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
   S.ms_lazy_select += ms_sel; S.ms_filters += ms_sel;
   // (the list, the bounds and the done flags stay where they are: the top-up round of itsx_search_finalize reads them when this was the
   // search's only chunk)
-  ctx->topup.valid = !ctx->completing; ctx->topup.NP = NP; ctx->topup.seg_start = pl.seg_start; ctx->topup.total = pl.total; ctx->topup.u0 = u0; ctx->topup.Uc = Uc;
+  ctx->topup.valid = !ctx->completing; ctx->topup.list_live = !ctx->completing; ctx->topup.NP = NP; ctx->topup.seg_start = pl.seg_start; ctx->topup.total = pl.total; ctx->topup.u0 = u0; ctx->topup.Uc = Uc;
   return ITSX_OK;
 }
 
@@ -3464,6 +3464,7 @@ static int search_chunk(itsx_ctx *ctx, int ci, int32_t u0, int32_t U, int Lcap, 
   if (NP >= (1ll << 31)) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "more than 2^31 surviving (representative, profile) pairs");
   DBuf<int64_t> &d_seg_start = ctx->w_seg_start;
   HIPCHK(upload(d_seg_start, seg_start, st));
+  ctx->topup.list_live = false;
   HIPCHK(ctx->d_pairs.alloc((size_t)NP));
   HIPCHK(hipMemsetAsync(ctx->d_pairs.p, 0xFF, (size_t)NP * sizeof(PairRec), st));
   if (!lazy_now) {                                 // (the lazy stage keeps a PairOut only for the pairs it evaluates)
@@ -3641,7 +3642,7 @@ int itsx_debug_set_domains(itsx_ctx *ctx, const itsx_domain *rows, int64_t n_row
   ctx->h_dom.clear(); ctx->h_trace.clear(); ctx->trace_sorted = false;
   ctx->domz.assign(m, 0); ctx->domz_ub.assign(m, 0); ctx->domz_loc.assign(m, 0); ctx->domz_ub_loc.assign(m, 0);
   ctx->npairs_padded = 0; ctx->dom_n.clear(); ctx->n_chunks = n_segs;
-  ctx->have_search = false; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->injected = true;
+  ctx->have_search = false; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->topup.list_live = false; ctx->injected = true;
   ctx->compact_rows = mode != ITSX_ROWS_FULL; ctx->lazy = mode == ITSX_ROWS_LAZY;
   ctx->lazy_pending = 0; ctx->domz_exchanged = false; ctx->lazy_pending_prof.clear();
   itsx_stats &S = ctx->stats;
@@ -6265,6 +6266,41 @@ int itsx_debug_select(itsx_ctx *ctx, int mode, const int32_t *pairs, int64_t NP,
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
   return ITSX_OK;
+}
+
+int64_t itsx_debug_lazy_pairs(itsx_ctx *ctx, itsx_lazy_pair *out, int64_t cap, int32_t *tenths_bias)
+{
+  if (!ctx) return ITSX_E_ARG;
+  if (tenths_bias) *tenths_bias = LAZY_TENTHS_BIAS;
+  const auto &tu = ctx->topup;
+  // the buffers lazy_rounds left (what the top-up round reads): only a lazy search of one chunk still has its whole list in them
+  if (!ctx->have_search || !ctx->lazy || ctx->injected || !tu.list_live || ctx->n_chunks != 1 || ctx->S != 1 || tu.NP <= 0)
+    SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_lazy_pairs: the pair list of a lazy search of one chunk and one sample is not in the buffers");
+  const int64_t NP = tu.NP;
+  if (!out || cap < NP) return NP;
+  if (ctx->d_pairs.n < (size_t)NP || ctx->l_fb.n < (size_t)NP || ctx->l_b10.n < (size_t)NP || ctx->l_done.n < (size_t)NP || ctx->s_Lcap <= 0 || ctx->d_lt.n < (size_t)ctx->s_Lcap)
+    SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_lazy_pairs: the lazy stage's buffers are smaller than its list");
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  std::vector<PairRec> hp((size_t)NP); std::vector<float> fb((size_t)NP); std::vector<uint32_t> b10((size_t)NP); std::vector<uint8_t> done((size_t)NP);
+  std::vector<int32_t> sorted((size_t)std::max(tu.Uc, 1)); std::vector<LenTables> lt((size_t)ctx->s_Lcap);
+  const int32_t *d_sorted = (ctx->share_on ? ctx->sh_order.p : ctx->d_sorted_uniq.p) + tu.u0;
+  HIPCHK(hipMemcpyAsync(hp.data(), ctx->d_pairs.p, (size_t)NP * sizeof(PairRec), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(fb.data(), ctx->l_fb.p, (size_t)NP * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(b10.data(), ctx->l_b10.p, (size_t)NP * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(done.data(), ctx->l_done.p, (size_t)NP, hipMemcpyDeviceToHost, st));
+  if (tu.Uc > 0) HIPCHK(hipMemcpyAsync(sorted.data(), d_sorted, (size_t)tu.Uc * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(lt.data(), ctx->d_lt.p, (size_t)ctx->s_Lcap * sizeof(LenTables), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < NP; i++) {
+    const PairRec &r = hp[(size_t)i];
+    itsx_lazy_pair &o = out[i];
+    memset(&o, 0, sizeof(o));
+    o.rep = (r.prof >= 0 && r.useq >= 0 && r.useq < tu.Uc) ? (int64_t)sorted[(size_t)r.useq] : -1;
+    o.prof = r.prof; o.L = r.L; o.xj = r.xj; o.fb = fb[(size_t)i]; o.b10 = b10[(size_t)i]; o.done = done[(size_t)i];
+    if (r.prof >= 0 && r.L > 0 && r.L < ctx->s_Lcap) { o.nullsc = lt[(size_t)r.L].nullsc; o.lazy_c = lt[(size_t)r.L].lazy_c; }
+  }
+  return NP;
 }
 
 int itsx_debug_region_keys(itsx_ctx *ctx, const int32_t *regions, int64_t n_regions, const int32_t *pairs, int64_t n_pairs, int32_t *rep_region, int32_t *is_uniq)

@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import DOMAIN_DTYPE, STATS_DTYPE_ALL, TRACE_DTYPE, EngineError
+from ._lib import DOMAIN_DTYPE, LAZY_PAIR_DTYPE, STATS_DTYPE_ALL, TRACE_DTYPE, EngineError
 
 
 def _device_from_env():
@@ -789,6 +789,20 @@ class Engine:
         if got != n:
             raise EngineError(min(got, -1), self.L.itsx_last_error(self.h).decode())
         return out[:n]
+
+    def debug_lazy_pairs(self):
+        """(records, bias): the lazy stage's pair list after a lazy search that ran as one chunk -- LAZY_PAIR_DTYPE records as they lie
+        (padding: prof < 0; row-state helpers: xj < 0), rep in get_uniques() order, pass A's score fb, the bound b10 = biased %.1f
+        tenths, done, and the nullsc / lazy_c k_lazy_bound read for the pair's L; bias = LAZY_TENTHS_BIAS.  EngineError in any other state."""
+        bias = C.c_int32(0)
+        n = int(self.L.itsx_debug_lazy_pairs(self.h, None, 0, C.byref(bias)))
+        if n < 0:
+            raise EngineError(n, self.L.itsx_last_error(self.h).decode())
+        out = np.zeros(max(n, 1), LAZY_PAIR_DTYPE)
+        got = int(self.L.itsx_debug_lazy_pairs(self.h, out.ctypes.data, n, C.byref(bias)))
+        if got != n:
+            raise EngineError(min(got, -1), self.L.itsx_last_error(self.h).decode())
+        return out[:n], int(bias.value)
 
     def debug_read_hashes(self):
         f = np.zeros(self.n_reads, np.uint64)
