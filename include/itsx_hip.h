@@ -721,6 +721,9 @@ int itsx_debug_read_hashes(itsx_ctx *ctx, uint64_t *fwd, uint64_t *rc);
 /* the sample of every read of a batch, [n_reads] each (either may be NULL): as the device kernels see it and as the host-side writers see
  * it; all 0 when the context holds one sample */
 int itsx_debug_read_samples(itsx_ctx *ctx, int32_t *device_ids, int32_t *host_ids);
+/* the length-ordered list of uniques the HMM stages walk, copied from the device (not from the host mirror): out[n_unique]; returns the
+ * number of entries written (all uniques after itsx_derep / itsx_cluster, the active ones after itsx_set_active_uniques) or an error */
+int itsx_debug_sorted_uniques(itsx_ctx *ctx, int32_t *out);
 /* packed representation of read i: words [ceil(len/16)], exception list (pos<<4|code) */
 int itsx_debug_packed_read(const itsx_ctx *ctx, int64_t i, uint32_t *words, int32_t *nwords,
                            uint32_t *exc, int32_t *nexc);

@@ -79,7 +79,7 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_search", "itsx_get_domz", "itsx_set_domz", "itsx_search_finalize", "itsx_num_domains",
            "itsx_get_domains", "itsx_num_pairtraces", "itsx_get_pairtraces", "itsx_trim_coords",
            "itsx_rep_coords", "itsx_write_uc", "itsx_write_rep_fasta", "itsx_write_domtbl", "itsx_get_stats", "itsx_switches", "itsx_switch_registry", "itsx_release_scratch",
-           "itsx_debug_read_hashes", "itsx_debug_read_samples", "itsx_debug_packed_read", "itsx_debug_detmath", "itsx_debug_logf", "itsx_debug_dust", "itsx_debug_calibrate", "itsx_debug_issue", "itsx_shard_text", "itsx_shard_last_error", "itsx_owner_verdicts",
+           "itsx_debug_read_hashes", "itsx_debug_read_samples", "itsx_debug_sorted_uniques", "itsx_debug_packed_read", "itsx_debug_detmath", "itsx_debug_logf", "itsx_debug_dust", "itsx_debug_calibrate", "itsx_debug_issue", "itsx_shard_text", "itsx_shard_last_error", "itsx_owner_verdicts",
            "itsx_write_trimmed_fastq", "itsx_write_trimmed_paired", "itsx_trim_last_error",
            "itsx_merge_buffers", "itsx_merge_pairs_files", "itsx_merge_pairs_load", "itsx_merge_tables",
            "itsx_orient_load_db", "itsx_orient", "itsx_orient_apply", "itsx_write_oriented_fastq",
@@ -232,6 +232,7 @@ def lib():
         "itsx_switch_registry": (i64, [vp, i64]),
         "itsx_debug_read_hashes": (i32, [vp, vp, vp]),
         "itsx_debug_read_samples": (i32, [vp, vp, vp]),
+        "itsx_debug_sorted_uniques": (i32, [vp, vp]),
         "itsx_debug_packed_read": (i32, [vp, i64, vp, vp, vp, vp]),
         "itsx_debug_detmath": (i32, [vp, vp, i64, vp, vp]),
         "itsx_debug_logf": (i32, [vp, vp, i64, vp]),

@@ -1301,6 +1301,16 @@ int itsx_debug_read_samples(itsx_ctx *ctx, int32_t *device_ids, int32_t *host_id
   if (host_ids && n) memcpy(host_ids, ctx->h_sample.data(), n * 4);
   return ITSX_OK;
 }
+// test hook: the length-ordered unique list as it lies on the device (d_sorted_uniq, its first U_active entries)
+int itsx_debug_sorted_uniques(itsx_ctx *ctx, int32_t *out)
+{
+  CTXCHK(ctx && ctx->have_derep && (out || ctx->U_active == 0));
+  const size_t m = (size_t)ctx->U_active;
+  if (ctx->d_sorted_uniq.n < m) SET_ERR(ctx, ITSX_E_ARG, "the length-ordered list does not cover the active uniques");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (m) { HIPCHK(hipMemcpyAsync(out, ctx->d_sorted_uniq.p, m * 4, hipMemcpyDeviceToHost, ctx->st)); HIPCHK(hipStreamSynchronize(ctx->st)); }
+  return (int)m;
+}
 int itsx_select_sample(itsx_ctx *ctx, int32_t sample)
 {
   CTXCHK(ctx);

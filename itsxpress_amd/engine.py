@@ -817,6 +817,14 @@ class Engine:
         self._chk(self.L.itsx_debug_read_samples(self.h, d.ctypes.data, h.ctypes.data))
         return d[:self.n_reads], h[:self.n_reads]
 
+    def debug_sorted_uniques(self):
+        """the length-ordered list of (active) uniques the HMM stages walk, as it lies on the device: get_uniques() numbers"""
+        out = np.zeros(max(1, self.n_unique), np.int32)
+        m = int(self.L.itsx_debug_sorted_uniques(self.h, out.ctypes.data))
+        if m < 0:
+            raise EngineError(m, self.L.itsx_last_error(self.h).decode())
+        return out[:m]
+
     def debug_packed_read(self, i):
         nw, ne = C.c_int32(0), C.c_int32(0)
         self._chk(self.L.itsx_debug_packed_read(self.h, i, None, C.byref(nw), None, C.byref(ne)))
