@@ -463,12 +463,37 @@ int itsx_parse_fetch(itsx_ctx *ctx, int32_t plane, int64_t lo, int64_t hi, void 
  * written, and *n_records, *n_bases, *n_title_bytes say what is needed). */
 int itsx_debug_parse_host(const char *text, int64_t nbytes, int64_t *off, int64_t *toff, int64_t cap_records, char *seq, char *qual, int64_t cap_bases,
                           char *titles, int64_t cap_titles, int64_t *n_records, int64_t *n_bases, int64_t *n_title_bytes, int32_t *reason, int64_t *bad_record);
+/* ---- a PAIR of texts (R1, R2) parsed on the device: each text into a plane set of its own (side 0: R1, side 1: R2) by the same rule,
+ * then one pass over both sides' planes (csrc/k_fastq.hip: k_fastq_pairs) does what the host path does between its parser and the merge
+ * kernel: bases 'a'..'z' become upper case in place, every quality byte is held against 33..126, the longest pair is measured.  Nothing
+ * is merged.  *flags: bit 0 / 1 = upper-casing changed a base of R1 / R2, bit 2 / 3 = a quality of R1 / R2 lies outside 33..126;
+ * *max_total: the largest R1 + R2 length of a pair (no pairs: 0).  ITSX_E_UNSUPPORTED: declined -- a text the rule declines, or texts of
+ * unequal record counts; itsx_last_error names the reason, and nothing is left to fetch.  Counters as itsx_parse_device, per text. */
+int itsx_parse_pairs_device(itsx_ctx *ctx, const char *text1, int64_t nbytes1, const char *text2, int64_t nbytes2, int64_t *n_pairs, int32_t *flags, int64_t *max_total);
+/* itsx_parse_fetch for one side (0: R1, 1: R2) of the last successful itsx_parse_pairs_device; the qualities are always kept */
+int itsx_parse_pairs_fetch(itsx_ctx *ctx, int32_t side, int32_t plane, int64_t lo, int64_t hi, void *out);
+/* the same result on the host, one thread, no device (tests, sanitizer program): csrc/fastq_rec.h's fq_parse_host per text and the host
+ * twin of the pass.  Buffers per side as itsx_debug_parse_host's, the caps hold for either side; sizes[4]: bases and title bytes of R1,
+ * then of R2.  *reason: 0, a text's decline code (*bad_side 0 / 1, *bad_record as there) or 7: unequal record counts (*bad_side -1).
+ * ITSX_OK, ITSX_E_UNSUPPORTED (declined: nothing written), ITSX_E_ARG (a buffer too small: nothing written, *n_pairs and sizes say what
+ * is needed). */
+int itsx_debug_parse_pairs_host(const char *text1, int64_t nbytes1, const char *text2, int64_t nbytes2, int64_t *off1, int64_t *toff1, char *seq1, char *qual1, char *titles1,
+                                int64_t *off2, int64_t *toff2, char *seq2, char *qual2, char *titles2, int64_t cap_records, int64_t cap_bases, int64_t cap_titles,
+                                int64_t *n_pairs, int64_t *sizes, int32_t *flags, int64_t *max_total, int32_t *reason, int32_t *bad_side, int64_t *bad_record);
+/* the host twin of the pass alone, over one side's planes of nbytes bytes: seq is upper-cased in place, *flags = bit 0 (a base changed)
+ * | bit 2 (a quality outside 33..126) */
+int itsx_debug_pair_pass_host(char *seq, const char *qual, int64_t nbytes, int32_t *flags);
 /* opt in per context: itsx_load_reads_file, itsx_load_reads_text and itsx_load_reads_files (with or without itsx_keep_records) parse on
  * the device.  A text the device inflate produced (itsx_set_device_inflate) is parsed where it lies and never reaches the host or its
  * text cache -- a host consumer that wants the file later reads it again, as on any cache miss; any other text is uploaded once.
  * Only the offsets and the title lines come back; the bases stay on the device (fetched when rep.fa or the seeds' sequences are asked
- * for).  One declined text makes the whole call start over on the host path: results and errors are that path's.  The streamed
- * loaders, itsx_load_reads_file_shard and the merge and orient loaders parse on the host.  ITSX_DEVICE_PARSE=1 does the same. */
+ * for).  One declined text makes the whole call start over on the host path: results and errors are that path's.
+ * The paired merge loaders (itsx_merge_pairs_load, itsx_merge_pairs_load_files, itsx_merge_pairs_load_text) do the same with both texts
+ * of every sample: R1 and R2 go into a plane set each, k_fastq_pairs upper-cases and checks them there, the merge kernel reads them where
+ * they lie and itsx_keep_pair_records keeps them; only offsets, R1's title lines and the counts come back.  They start over on the host
+ * path also where R1 and R2 of a sample differ in their record counts, a quality lies outside 33..126 or a pair is longer than 12000
+ * bases, so those errors are the host path's too.  The streamed loaders, itsx_load_reads_file_shard, itsx_merge_pairs_files and the
+ * orient loaders parse on the host.  ITSX_DEVICE_PARSE=1 does the same. */
 int itsx_set_device_parse(itsx_ctx *ctx, int on);
 /* csrc/deflate_codes.h on the host (no context, no device): the code lengths the kernel gives n <= 288 symbols of these counts (sum
  * below 2^32) under a limit of maxbits (1..15, n <= 2^maxbits).  lengths: [n]. */

@@ -101,6 +101,7 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_twriter_set_device",
            "itsx_inflate_device", "itsx_inflate_fetch", "itsx_debug_inflate_host", "itsx_debug_inflate_candidates", "itsx_debug_inflate_where", "itsx_set_device_inflate",
            "itsx_parse_device", "itsx_parse_fetch", "itsx_debug_parse_host", "itsx_set_device_parse",
+           "itsx_parse_pairs_device", "itsx_parse_pairs_fetch", "itsx_debug_parse_pairs_host", "itsx_debug_pair_pass_host",
            "itsx_debug_set_domains", "itsx_debug_get_rows",
            "itsx_debug_scan", "itsx_debug_select", "itsx_debug_region_keys", "itsx_debug_lazy_pairs"]
 
@@ -183,6 +184,10 @@ def lib():
         "itsx_parse_fetch": (i32, [vp, i32, i64, i64, vp]),
         "itsx_debug_parse_host": (i32, [vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
         "itsx_set_device_parse": (i32, [vp, i32]),
+        "itsx_parse_pairs_device": (i32, [vp, vp, i64, vp, i64, vp, vp, vp]),
+        "itsx_parse_pairs_fetch": (i32, [vp, i32, i32, i64, i64, vp]),
+        "itsx_debug_parse_pairs_host": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "itsx_debug_pair_pass_host": (i32, [vp, vp, i64, vp]),
         "itsx_debug_set_domains": (i32, [vp, vp, i64, vp, i32, i32]),
         "itsx_debug_get_rows": (i64, [vp, vp, i64]),
         "itsx_unique_keys128": (i32, [vp, C.c_uint64, C.c_uint64, i64, vp]),

@@ -170,7 +170,9 @@ class SampleBatch:
         """`_merge_reads` of every (paired) sample (SeqSample.py:266-365) in one engine call: one merge kernel over the pairs of all
         samples, the merged reads left on the device as the batch's read set.  Every sample's `seq_file` becomes
         `<its batch subdir>/seq.fq`; the file is written when write_seq_files is true (default: yes in file-compatible mode, no
-        with ITSXPRESS_ARRAYS=1 or in a batch with keep_records), byte for byte what the sample's own `_merge_reads` writes."""
+        with ITSXPRESS_ARRAYS=1 or in a batch with keep_records), byte for byte what the sample's own `_merge_reads` writes.
+        With parse = "device" R1 and R2 of every sample are parsed on the device and merged where the parser left them (with
+        inflate = "device" from text that never left it); a batch the device declines is merged from the host's parse, the same."""
         try:
             for s in self.samples:
                 if getattr(s, "r1", None) is None or getattr(s, "fastq2", None) is None:
@@ -320,7 +322,8 @@ class SampleBatch:
     def inflate(self, where: str):
         self.engine.inflate = where
 
-    # Where the engine's whole-file loaders parse FASTQ text: the engine's own setting (Engine.parse), under the batch's name
+    # Where the engine's whole-file loaders and its paired merge loaders (merge_reads) parse FASTQ text: the engine's own setting
+    # (Engine.parse), under the batch's name
     @property
     def parse(self) -> str:
         return getattr(self.engine, "parse", "host")

@@ -510,6 +510,11 @@ struct itsx_ctx {
   // becomes d_merged_text (the read set's text on the device, as after a merge).  ps_mu serialises the callers that share the context.
   DBuf<uint8_t> ps_text, ps_seq, ps_qual, ps_titles; DBuf<int64_t> ps_lblk, ps_nl, ps_blk, ps_off, ps_toff, ps_info;
   int64_t ps_n = -1, ps_nb = 0, ps_nt = 0, n_parse_device = 0, n_parse_declined = 0; bool ps_qual_kept = false, device_parse = false; std::mutex ps_mu;
+  // a PAIR of texts needs the plane set once per side (itsx_parse_pairs_device, merge_pairs_load_device): a side's planes are moved into
+  // ps_seq / ps_qual / ps_titles while its texts are parsed and back here afterwards.  off / toff: the offsets of the last successful
+  // itsx_parse_pairs_device (pp_n pairs; -1: none); pp_info: k_fastq_pairs' two words
+  struct PairSide { DBuf<uint8_t> seq, qual, titles; DBuf<int64_t> off, toff; int64_t nb = 0, nt = 0; } pp[2];
+  int64_t pp_n = -1; DBuf<unsigned long long> pp_info;
   bool two_on = false; int share_maxrd = 0; int32_t Ub = 0; size_t sh_gslots_off = 0;
   DBuf<uint8_t> sh_rdepth_s, sh_rdepth; DBuf<unsigned long long> sh_rmask_s, sh_rmask, sh_keys, sh_keys2;
   DBuf<int32_t> sh_rparent_s, sh_rparent, sh_jlev_s, sh_jown_s, sh_endrow_s, sh_rsteps_s, sh_rnn_s, sh_rnode0_s, sh_endrow, sh_jlev, sh_jsrc, sh_jownb;
@@ -851,6 +856,11 @@ static bool device_inflate_on(const itsx_ctx *ctx);
 constexpr int PARSE_FALLBACK = 1;
 static bool device_parse_on(const itsx_ctx *ctx);
 static int load_parsed_device(itsx_ctx *ctx, const char *const *paths, int32_t n_paths, const char *text, int64_t nbytes, int64_t *n_reads_per_file, bool batch);
+// the same for the paired merge loaders (S samples from files, or one sample's two texts in memory); PARSE_FALLBACK also where R1 and R2
+// of a sample differ in their record counts, a quality lies outside 33..126 or a pair is longer than the merge kernel takes
+static int merge_pairs_load_device(itsx_ctx *ctx, const char *const *r1_paths, const char *const *r2_paths, const char *const *seq_out_paths, int32_t S,
+                                   const char *text1, int64_t nb1, const char *text2, int64_t nb2, int maxdiffs, double maxee, int allow_stagger,
+                                   int64_t *n_pairs_per_sample, int64_t *n_merged_per_sample, bool batch);
 static std::shared_ptr<const itsx_io::Text> slurp(const char *path, bool cacheable, std::string &err, itsx_ctx *ctx = nullptr)
 {
   if (ctx && device_inflate_on(ctx)) {
@@ -4414,9 +4424,40 @@ struct MergeKeep {
   DBuf<uint8_t> os, oq; DBuf<int64_t> fo, ro; DBuf<int32_t> len, reason; bool want_oq = false;      // oq: the merged qualities, only where records are kept
   DBuf<uint8_t> fs, fq, rs, rq; bool want_pairs = false;       // the kernel's inputs, only where the pair records are kept
 };
-// keep (may be null): the merged bases stay in device memory (pair i's at foff[i] + roff[i]) together with the pairs' offsets, lengths
-// and reasons, all taken over by *keep; the bases are copied back only if out_seq is given -- the merge-and-load calls pack them where
-// they are
+// The device step of a merge: bases, qualities and offsets of both sides lie in device memory (fb / rb bytes a side, max_total = the
+// longest pair, at least 2); the kernel runs and the results are copied back.  keep (may be null): the merged bases stay in device
+// memory (pair i's at foff[i] + roff[i]) with the pairs' lengths and reasons, taken over by *keep (the inputs stay the caller's); the
+// bases are copied back only if out_seq is given -- the merge-and-load calls pack them where they are
+static int merge_device(itsx_ctx *ctx, const uint8_t *d_fs, const uint8_t *d_fq, const int64_t *d_fo, const uint8_t *d_rs, const uint8_t *d_rq, const int64_t *d_ro,
+                        int64_t n, int64_t fb, int64_t rb, int64_t max_total, int maxdiffs, double maxee, int allow_stagger,
+                        char *out_seq, char *out_qual, int32_t *out_len, int32_t *reason, double *score, int32_t *shift, MergeKeep *keep)
+{
+  const MergeTables &t = merge_tables();
+  DBuf<uint8_t> d_os, d_oq, d_qs, d_qd; DBuf<int32_t> d_len, d_reason, d_shift; DBuf<double> d_q2p, d_m, d_x, d_score;
+  HIPCHK(d_os.alloc((size_t)(fb + rb) + 1)); HIPCHK(d_oq.alloc((size_t)(fb + rb) + 1));
+  HIPCHK(d_len.alloc((size_t)n)); HIPCHK(d_reason.alloc((size_t)n)); HIPCHK(d_shift.alloc((size_t)n)); HIPCHK(d_score.alloc((size_t)n));
+  HIPCHK(upload(d_q2p, t.q2p, ctx->st)); HIPCHK(upload(d_m, t.match, ctx->st)); HIPCHK(upload(d_x, t.mism, ctx->st));
+  HIPCHK(upload(d_qs, t.qsame, ctx->st)); HIPCHK(upload(d_qd, t.qdiff, ctx->st));
+  MergeArgs a{};
+  a.fseq = d_fs; a.fqual = d_fq; a.rseq = d_rs; a.rqual = d_rq; a.foff = d_fo; a.roff = d_ro; a.n = n; a.max_total = (int32_t)max_total;
+  a.maxdiffs = maxdiffs; a.allow_stagger = allow_stagger ? 1 : 0; a.maxee = maxee;
+  a.q2p = d_q2p.p; a.match = d_m.p; a.mism = d_x.p; a.qsame = d_qs.p; a.qdiff = d_qd.p;
+  a.out_seq = d_os.p; a.out_qual = d_oq.p; a.out_len = d_len.p; a.reason = d_reason.p; a.shift = d_shift.p; a.score = d_score.p;
+  StageTimer tm(ctx->st);
+  launch_merge(a, ctx->st);
+  ctx->stats.ms_merge = tm.stop();
+  HIPCHK(hipGetLastError());
+  if (out_seq) HIPCHK(hipMemcpyAsync(out_seq, d_os.p, (size_t)(fb + rb), hipMemcpyDeviceToHost, ctx->st));
+  if (out_qual) HIPCHK(hipMemcpyAsync(out_qual, d_oq.p, (size_t)(fb + rb), hipMemcpyDeviceToHost, ctx->st));
+  HIPCHK(hipMemcpyAsync(out_len, d_len.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st)); HIPCHK(hipMemcpyAsync(reason, d_reason.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
+  if (score) HIPCHK(hipMemcpyAsync(score, d_score.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->st));
+  if (shift) HIPCHK(hipMemcpyAsync(shift, d_shift.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  if (keep) { dbuf_swap(keep->os, d_os); if (keep->want_oq) dbuf_swap(keep->oq, d_oq); dbuf_swap(keep->len, d_len); dbuf_swap(keep->reason, d_reason); }
+  return ITSX_OK;
+}
+// The upload step: host planes are checked (offsets, the 12 000-base limit, the quality range) and go up, then merge_device runs on
+// them.  keep (may be null) also takes over the pairs' offsets and, where the pair records are kept, the uploaded planes.
 static int merge_core(itsx_ctx *ctx, const char *fseq, const char *fqual, const int64_t *foff, const char *rseq, const char *rqual,
                       const int64_t *roff, int64_t n, int maxdiffs, double maxee, int allow_stagger,
                       char *out_seq, char *out_qual, int32_t *out_len, int32_t *reason, double *score, int32_t *shift, MergeKeep *keep)
@@ -4445,34 +4486,18 @@ static int merge_core(itsx_ctx *ctx, const char *fseq, const char *fqual, const 
     if (badf) SET_ERR(ctx, ITSX_E_FORMAT, "forward quality outside ASCII 33..126 (--fastq_qmax 93)");
     if (badr) SET_ERR(ctx, ITSX_E_FORMAT, "reverse quality outside ASCII 33..126 (--fastq_qmax 93)");
   }
-  const MergeTables &t = merge_tables();
-  DBuf<uint8_t> d_fs, d_fq, d_rs, d_rq, d_os, d_oq, d_qs, d_qd; DBuf<int64_t> d_fo, d_ro; DBuf<int32_t> d_len, d_reason, d_shift; DBuf<double> d_q2p, d_m, d_x, d_score;
+  DBuf<uint8_t> d_fs, d_fq, d_rs, d_rq; DBuf<int64_t> d_fo, d_ro;
   // (kept planes are read by k_trim_copy, whose trim_load4 reads two aligned dwords: 8 bytes past the end must be readable)
   const size_t pad = keep && keep->want_pairs ? 64 : 1;
   HIPCHK(d_fs.alloc((size_t)fb + pad)); HIPCHK(d_fq.alloc((size_t)fb + pad)); HIPCHK(d_rs.alloc((size_t)rb + pad)); HIPCHK(d_rq.alloc((size_t)rb + pad));
-  HIPCHK(d_os.alloc((size_t)(fb + rb) + 1)); HIPCHK(d_oq.alloc((size_t)(fb + rb) + 1));
-  HIPCHK(d_fo.alloc((size_t)n + 1)); HIPCHK(d_ro.alloc((size_t)n + 1)); HIPCHK(d_len.alloc((size_t)n)); HIPCHK(d_reason.alloc((size_t)n)); HIPCHK(d_shift.alloc((size_t)n)); HIPCHK(d_score.alloc((size_t)n));
-  HIPCHK(upload(d_q2p, t.q2p, ctx->st)); HIPCHK(upload(d_m, t.match, ctx->st)); HIPCHK(upload(d_x, t.mism, ctx->st));
-  HIPCHK(upload(d_qs, t.qsame, ctx->st)); HIPCHK(upload(d_qd, t.qdiff, ctx->st));
+  HIPCHK(d_fo.alloc((size_t)n + 1)); HIPCHK(d_ro.alloc((size_t)n + 1));
   HIPCHK(hipMemcpyAsync(d_fs.p, fseq, (size_t)fb, hipMemcpyHostToDevice, ctx->st)); HIPCHK(hipMemcpyAsync(d_fq.p, fqual, (size_t)fb, hipMemcpyHostToDevice, ctx->st));
   HIPCHK(hipMemcpyAsync(d_rs.p, rseq, (size_t)rb, hipMemcpyHostToDevice, ctx->st)); HIPCHK(hipMemcpyAsync(d_rq.p, rqual, (size_t)rb, hipMemcpyHostToDevice, ctx->st));
   HIPCHK(hipMemcpyAsync(d_fo.p, foff, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->st)); HIPCHK(hipMemcpyAsync(d_ro.p, roff, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->st));
-  MergeArgs a{};
-  a.fseq = d_fs.p; a.fqual = d_fq.p; a.rseq = d_rs.p; a.rqual = d_rq.p; a.foff = d_fo.p; a.roff = d_ro.p; a.n = n; a.max_total = (int32_t)max_total;
-  a.maxdiffs = maxdiffs; a.allow_stagger = allow_stagger ? 1 : 0; a.maxee = maxee;
-  a.q2p = d_q2p.p; a.match = d_m.p; a.mism = d_x.p; a.qsame = d_qs.p; a.qdiff = d_qd.p;
-  a.out_seq = d_os.p; a.out_qual = d_oq.p; a.out_len = d_len.p; a.reason = d_reason.p; a.shift = d_shift.p; a.score = d_score.p;
-  StageTimer tm(ctx->st);
-  launch_merge(a, ctx->st);
-  ctx->stats.ms_merge = tm.stop();
-  HIPCHK(hipGetLastError());
-  if (out_seq) HIPCHK(hipMemcpyAsync(out_seq, d_os.p, (size_t)(fb + rb), hipMemcpyDeviceToHost, ctx->st));
-  if (out_qual) HIPCHK(hipMemcpyAsync(out_qual, d_oq.p, (size_t)(fb + rb), hipMemcpyDeviceToHost, ctx->st));
-  HIPCHK(hipMemcpyAsync(out_len, d_len.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st)); HIPCHK(hipMemcpyAsync(reason, d_reason.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
-  if (score) HIPCHK(hipMemcpyAsync(score, d_score.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->st));
-  if (shift) HIPCHK(hipMemcpyAsync(shift, d_shift.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
-  HIPCHK(hipStreamSynchronize(ctx->st));
-  if (keep) { dbuf_swap(keep->os, d_os); if (keep->want_oq) dbuf_swap(keep->oq, d_oq); dbuf_swap(keep->fo, d_fo); dbuf_swap(keep->ro, d_ro); dbuf_swap(keep->len, d_len); dbuf_swap(keep->reason, d_reason); }
+  const int rc = merge_device(ctx, d_fs.p, d_fq.p, d_fo.p, d_rs.p, d_rq.p, d_ro.p, n, fb, rb, max_total, maxdiffs, maxee, allow_stagger,
+                              out_seq, out_qual, out_len, reason, score, shift, keep);
+  if (rc != ITSX_OK) return rc;
+  if (keep) { dbuf_swap(keep->fo, d_fo); dbuf_swap(keep->ro, d_ro); }
   if (keep && keep->want_pairs) { dbuf_swap(keep->fs, d_fs); dbuf_swap(keep->fq, d_fq); dbuf_swap(keep->rs, d_rs); dbuf_swap(keep->rq, d_rq); }
   return ITSX_OK;
 }
@@ -4568,9 +4593,16 @@ static int parse_fastq_side(const char *path, const char *text, int64_t nb, Fast
 // kernel for all of them; what it left on the device is compacted there (k_merge.hip: k_merge_compact), gathered into a gap-free text and
 // packed.  The host walks the pairs once, for the labels, while the gather runs.  seq_out_paths (may be null, entries may be null): the
 // sample's merged records as itsx_merge_pairs_files writes them -- the only case in which merged bases and qualities come back.
+// dev (may be null; the device parse's loader, merge_pairs_load_device): the planes already lie in device memory, upper-cased and checked
+// (k_fastq.hip: k_fastq_pairs); of f and r only `off` is filled, and the title planes and their offsets are dev's.
+struct MergeDev {
+  DBuf<uint8_t> *fs, *fq, *rs, *rq, *t1, *t2; DBuf<int64_t> *fo, *ro;      // taken over where they are kept, left alone otherwise
+  const std::vector<int64_t> *to1, *to2;                                  // [n + 1] the title lines' offsets
+  int64_t max_total;
+};
 static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r, const std::vector<const NameList *> &ids, const std::vector<int64_t> &pstart,
                            const char *const *seq_out_paths, int maxdiffs, double maxee, int allow_stagger, double parse_ms, int64_t *n_merged_per_sample,
-                           bool records = false, bool pair_records = false)
+                           bool records = false, bool pair_records = false, MergeDev *dev = nullptr)
 {
   const int32_t S = (int32_t)pstart.size() - 1;
   const int64_t n = pstart[(size_t)S];
@@ -4581,11 +4613,20 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
   if (seq_out_paths) for (int32_t s = 0; s < S; s++) want_text = want_text || seq_out_paths[s] != nullptr;
   std::vector<int32_t> olen((size_t)n + 1), reason((size_t)n + 1);
   std::string oseq, oqual;
-  if (want_text) { oseq.assign((size_t)(f.seq.size() + r.seq.size()) + 1, '\0'); oqual = oseq; }
+  if (want_text) { oseq.assign((dev ? (size_t)(f.off[(size_t)n] + r.off[(size_t)n]) : (size_t)(f.seq.size() + r.seq.size())) + 1, '\0'); oqual = oseq; }
   MergeKeep k;
   k.want_oq = records; k.want_pairs = pair_records;
-  int rc = merge_core(ctx, f.seq.data(), f.qual.data(), f.off.data(), r.seq.data(), r.qual.data(), r.off.data(), n, maxdiffs, maxee, allow_stagger,
-                      want_text ? &oseq[0] : nullptr, want_text ? &oqual[0] : nullptr, olen.data(), reason.data(), nullptr, nullptr, &k);
+  int rc = ITSX_OK;
+  if (!dev) rc = merge_core(ctx, f.seq.data(), f.qual.data(), f.off.data(), r.seq.data(), r.qual.data(), r.off.data(), n, maxdiffs, maxee, allow_stagger,
+                            want_text ? &oseq[0] : nullptr, want_text ? &oqual[0] : nullptr, olen.data(), reason.data(), nullptr, nullptr, &k);
+  else if (n > 0) {
+    rc = merge_device(ctx, dev->fs->p, dev->fq->p, dev->fo->p, dev->rs->p, dev->rq->p, dev->ro->p, n, f.off[(size_t)n], r.off[(size_t)n], std::max<int64_t>(dev->max_total, 2),
+                      maxdiffs, maxee, allow_stagger, want_text ? &oseq[0] : nullptr, want_text ? &oqual[0] : nullptr, olen.data(), reason.data(), nullptr, nullptr, &k);
+    if (rc == ITSX_OK) {                                 // as merge_core leaves *keep
+      dbuf_swap(k.fo, *dev->fo); dbuf_swap(k.ro, *dev->ro);
+      if (pair_records) { dbuf_swap(k.fs, *dev->fs); dbuf_swap(k.fq, *dev->fq); dbuf_swap(k.rs, *dev->rs); dbuf_swap(k.rq, *dev->rq); }
+    }
+  }
   if (rc != ITSX_OK) return rc;
   const auto tm2 = std::chrono::steady_clock::now();
   hipStream_t st = ctx->st;
@@ -4670,7 +4711,7 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
     // merge but carries a merged pair's identifier is sliced with that read's coordinates, and of equal labels the first wins
     // (trim_host.cpp: NameIndex).  h_merge_index is not that map.
     itsx_ctx::PairRecords &pr = ctx->prec;
-    if ((int64_t)f.titles.size() != n || (int64_t)r.titles.size() != n) SET_ERR(ctx, ITSX_E_FORMAT, "the title lines kept for the pairs do not match the pairs");
+    if (!dev && ((int64_t)f.titles.size() != n || (int64_t)r.titles.size() != n)) SET_ERR(ctx, ITSX_E_FORMAT, "the title lines kept for the pairs do not match the pairs");
     std::vector<int32_t> pread((size_t)n, -1);
     {
       std::vector<int64_t> rfirst((size_t)S + 1, 0);
@@ -4696,12 +4737,16 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
       HIPCHK(k.fs.alloc(64)); HIPCHK(k.fq.alloc(64)); HIPCHK(k.rs.alloc(64)); HIPCHK(k.rq.alloc(64)); HIPCHK(k.fo.alloc(1)); HIPCHK(k.ro.alloc(1));
       HIPCHK(hipMemsetAsync(k.fo.p, 0, 8, st)); HIPCHK(hipMemsetAsync(k.ro.p, 0, 8, st));
     }
-    HIPCHK(pr.t1.alloc(f.titles.blob.size() + 64)); HIPCHK(pr.t2.alloc(r.titles.blob.size() + 64));
+    if (dev && n > 0) { dbuf_swap(pr.t1, *dev->t1); dbuf_swap(pr.t2, *dev->t2); }      // the parser's title planes, where the gather left them
+    else {
+      const size_t nt1 = dev ? 0 : f.titles.blob.size(), nt2 = dev ? 0 : r.titles.blob.size();
+      HIPCHK(pr.t1.alloc(nt1 + 64)); HIPCHK(pr.t2.alloc(nt2 + 64));
+      if (nt1) HIPCHK(hipMemcpyAsync(pr.t1.p, f.titles.blob.data(), nt1, hipMemcpyHostToDevice, st));
+      if (nt2) HIPCHK(hipMemcpyAsync(pr.t2.p, r.titles.blob.data(), nt2, hipMemcpyHostToDevice, st));
+    }
     HIPCHK(pr.to1.alloc((size_t)n + 1)); HIPCHK(pr.to2.alloc((size_t)n + 1)); HIPCHK(pr.pair_read.alloc((size_t)n + 1));
-    if (!f.titles.blob.empty()) HIPCHK(hipMemcpyAsync(pr.t1.p, f.titles.blob.data(), f.titles.blob.size(), hipMemcpyHostToDevice, st));
-    if (!r.titles.blob.empty()) HIPCHK(hipMemcpyAsync(pr.t2.p, r.titles.blob.data(), r.titles.blob.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(pr.to1.p, f.titles.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(pr.to2.p, r.titles.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pr.to1.p, dev ? dev->to1->data() : f.titles.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pr.to2.p, dev ? dev->to2->data() : r.titles.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
     if (n > 0) HIPCHK(hipMemcpyAsync(pr.pair_read.p, pread.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     dbuf_swap(pr.s1, k.fs); dbuf_swap(pr.q1, k.fq); dbuf_swap(pr.s2, k.rs); dbuf_swap(pr.q2, k.rq); dbuf_swap(pr.o1, k.fo); dbuf_swap(pr.o2, k.ro);
@@ -4766,6 +4811,10 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
 static int merge_pairs_load_impl(itsx_ctx *ctx, const char *r1_path, const char *r2_path, const char *text1, int64_t nb1, const char *text2, int64_t nb2,
                                  int maxdiffs, double maxee, int allow_stagger, int64_t *n_pairs, int64_t *n_merged)
 {
+  if (device_parse_on(ctx)) {
+    const int drc = merge_pairs_load_device(ctx, &r1_path, &r2_path, nullptr, 1, text1, nb1, text2, nb2, maxdiffs, maxee, allow_stagger, n_pairs, n_merged, false);
+    if (drc != PARSE_FALLBACK) return drc;
+  }
   FastxPart f, r;
   std::string ferr, rerr2;
   int rc2 = ITSX_OK;
@@ -4806,6 +4855,10 @@ int itsx_merge_pairs_load_text(itsx_ctx *ctx, const char *text1, int64_t nbytes1
 static int merge_pairs_load_files_impl(itsx_ctx *ctx, const char *const *r1_paths, const char *const *r2_paths, const char *const *seq_out_paths,
                                        int32_t S, int maxdiffs, double maxee, int allow_stagger, int64_t *n_pairs_per_sample, int64_t *n_merged_per_sample)
 {
+  if (device_parse_on(ctx)) {
+    const int drc = merge_pairs_load_device(ctx, r1_paths, r2_paths, seq_out_paths, S, nullptr, 0, nullptr, 0, maxdiffs, maxee, allow_stagger, n_pairs_per_sample, n_merged_per_sample, true);
+    if (drc != PARSE_FALLBACK) return drc;
+  }
   const auto tm0 = std::chrono::steady_clock::now();
   std::vector<FastxPart> fs((size_t)S), rs((size_t)S);
   const bool pair_records = ctx->keep_pair_records;
@@ -5658,6 +5711,151 @@ static int load_parsed_device(itsx_ctx *ctx, const char *const *paths, int32_t n
   rr.seq_p = ctx->d_merged_text.p; rr.have = true;
   return ITSX_OK;
 }
+// ---- a PAIR of texts: the plane set once per side
+// a side's planes into the parser's slots (and, for the raw entry, the parser's offsets out of them) and back
+static void pair_side_swap(itsx_ctx *ctx, int side)
+{
+  itsx_ctx::PairSide &p = ctx->pp[side];
+  dbuf_swap(ctx->ps_seq, p.seq); dbuf_swap(ctx->ps_qual, p.qual); dbuf_swap(ctx->ps_titles, p.titles);
+}
+struct PairSideScope {      // the side's planes are the parser's for the scope's life
+  itsx_ctx *ctx; int side;
+  PairSideScope(itsx_ctx *c, int s) : ctx(c), side(s) { pair_side_swap(ctx, side); }
+  ~PairSideScope() { pair_side_swap(ctx, side); }
+};
+// the pass over both sides' finished planes (k_fastq.hip: k_fastq_pairs): flags and the longest pair come back
+static int pairs_pass_device(itsx_ctx *ctx, const int64_t *d_off1, const int64_t *d_off2, int64_t n, int64_t nb1, int64_t nb2, int32_t &flags, int64_t &max_total)
+{
+  flags = 0; max_total = 0;
+  if (n <= 0) return ITSX_OK;
+  hipStream_t st = ctx->st;
+  HIPCHK(ctx->pp_info.alloc(2));
+  FastqPairArgs a{};
+  a.seq[0] = ctx->pp[0].seq.p; a.qual[0] = ctx->pp[0].qual.p; a.total[0] = nb1; a.off[0] = d_off1;
+  a.seq[1] = ctx->pp[1].seq.p; a.qual[1] = ctx->pp[1].qual.p; a.total[1] = nb2; a.off[1] = d_off2;
+  a.n = n; a.info = ctx->pp_info.p;
+  {
+    StageTimer tm(st);
+    launch_fastq_pairs(a, st);
+    ctx->stats.ms_parse += tm.stop();
+  }
+  HIPCHK(hipGetLastError());
+  unsigned long long info[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(info, ctx->pp_info.p, sizeof(info), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  flags = (int32_t)info[0]; max_total = (int64_t)info[1];
+  return ITSX_OK;
+}
+// The paired merge loaders' device path.  All R1 texts of the call are parsed into one plane set and all R2 texts into the other, with
+// running bases as load_parsed_device's batch has them; a file the device inflate accepted is parsed where it lies, any other text goes
+// up once.  What comes back: the parser's two small reads per text, the offsets (8 bytes a record and plane, rebased per sample here and
+// sent up again as the merge kernel's), R1's title lines (the identifiers are cut from them) and the counts.  Bases and qualities never
+// do: k_fastq_pairs upper-cases and checks them where they lie, and merge_load_core runs the merge kernel on them and keeps them as the
+// pair records.  PARSE_FALLBACK: nothing of the context's read set, records or pair records has been touched.
+static int merge_pairs_load_device(itsx_ctx *ctx, const char *const *r1_paths, const char *const *r2_paths, const char *const *seq_out_paths, int32_t S,
+                                   const char *text1, int64_t nb1, const char *text2, int64_t nb2, int maxdiffs, double maxee, int allow_stagger,
+                                   int64_t *n_pairs_per_sample, int64_t *n_merged_per_sample, bool batch)
+{
+  const auto tm0 = std::chrono::steady_clock::now();
+  std::lock_guard<std::mutex> g(ctx->ps_mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  ctx->ps_n = -1; ctx->pp_n = -1; ctx->stats.ms_parse = 0;
+  FastxPart f, r;                                // of these only `off` is filled: the pairs' offsets over the whole call
+  std::vector<int64_t> toff[2] = {std::vector<int64_t>(1, 0), std::vector<int64_t>(1, 0)};
+  std::vector<NameList> names((size_t)S);        // R1's identifiers per sample: the title after its '@' up to the first blank or tab
+  std::vector<int64_t> counts[2] = {std::vector<int64_t>((size_t)S, 0), std::vector<int64_t>((size_t)S, 0)};
+  for (int side = 0; side < 2; side++) {
+    PairSideScope planes(ctx, side);
+    std::vector<int64_t> &off = side ? r.off : f.off;
+    int64_t gb = 0, gt = 0;
+    for (int32_t s = 0; s < S; s++) {
+      const char *path = text1 ? nullptr : (side ? r2_paths[s] : r1_paths[s]);
+      const uint8_t *dtext = nullptr; int64_t len = 0;
+      std::shared_ptr<const itsx_io::Text> tp;
+      bool kept = false;
+      if (path) {
+        std::string rerr;
+        if (device_inflate_on(ctx)) {
+          // the device inflate's text stays where it is: nothing of it comes back, nothing of it is cached
+          const itsx_io::InflateFirst first = [ctx](const itsx_io::Text &raw, itsx_io::Text &) {
+            std::lock_guard<std::mutex> gi(ctx->inf_mu);
+            if (hipSetDevice(ctx->device) != hipSuccess) return false;
+            return inflate_file(ctx, raw.data(), (int64_t)raw.size(), nullptr, nullptr) == ITSX_OK;
+          };
+          tp = itsx_io::read_text(path, rerr, true, &first, &kept);
+        } else tp = itsx_io::read_text(path, rerr, true);
+        if (!tp) return PARSE_FALLBACK;
+      }
+      if (kept) { dtext = ctx->inf_text.p; len = ctx->inf_len; }
+      else {
+        const char *h = path ? tp->data() : (side ? text2 : text1);
+        len = path ? (int64_t)tp->size() : (side ? nb2 : nb1);
+        bool fits = true;
+        { const int rc = parse_upload(ctx, h, len, fits); if (rc != ITSX_OK) return rc; }
+        if (!fits) return PARSE_FALLBACK;
+        dtext = ctx->ps_text.p;
+      }
+      ParsedText pt;
+      const int rc = parse_text_device(ctx, dtext, len, true, gb, gt, pt);
+      if (rc == ITSX_E_UNSUPPORTED) return PARSE_FALLBACK;
+      if (rc != ITSX_OK) return rc;
+      if (pt.n > 0) {
+        const size_t r0 = off.size() - 1;
+        off.resize(r0 + (size_t)pt.n + 1); toff[side].resize(r0 + (size_t)pt.n + 1);
+        HIPCHK(hipMemcpyAsync(off.data() + r0 + 1, ctx->ps_off.p + 1, (size_t)pt.n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(toff[side].data() + r0 + 1, ctx->ps_toff.p + 1, (size_t)pt.n * 8, hipMemcpyDeviceToHost, st));
+        std::vector<char> tl;
+        if (side == 0) { tl.resize((size_t)pt.nt); const int frc = fetch_staged(ctx, ctx->ps_titles.p + gt, pt.nt, tl.data()); if (frc != ITSX_OK) return frc; }
+        HIPCHK(hipStreamSynchronize(st));
+        if (side == 0) {
+          NameList &nm = names[(size_t)s];
+          nm.off.reserve((size_t)pt.n + 1); nm.blob.reserve((size_t)pt.nt);
+          for (size_t q = r0; q + 1 < off.size(); q++) {      // (the offsets are still this text's own; its first title starts at 0)
+            const char *b = tl.data() + (q > r0 ? toff[0][q] : 0) + 1, *e = tl.data() + toff[0][q + 1], *ne = b;
+            while (ne < e && *ne != ' ' && *ne != '\t') ne++;
+            nm.emplace_back(b, ne);
+          }
+        }
+        if (gb || gt) for (size_t q = r0 + 1; q < off.size(); q++) { off[q] += gb; toff[side][q] += gt; }
+      }
+      gb += pt.nb; gt += pt.nt;
+      counts[side][(size_t)s] = pt.n;
+    }
+    ctx->pp[side].nb = gb; ctx->pp[side].nt = gt;
+  }
+  std::vector<int64_t> pstart((size_t)S + 1, 0);
+  for (int32_t s = 0; s < S; s++) {
+    if (counts[0][(size_t)s] != counts[1][(size_t)s]) return PARSE_FALLBACK;      // the host path names the files and the counts
+    pstart[(size_t)s + 1] = pstart[(size_t)s] + counts[0][(size_t)s];
+  }
+  const int64_t n = pstart[(size_t)S];
+  if (n >= (1ll << 31) - 64) return PARSE_FALLBACK;
+  DBuf<int64_t> d_fo, d_ro;
+  int32_t flags = 0; int64_t max_total = 0;
+  if (n > 0) {
+    if (d_fo.alloc((size_t)n + 1) != hipSuccess || d_ro.alloc((size_t)n + 1) != hipSuccess) { (void)hipGetLastError(); return PARSE_FALLBACK; }
+    HIPCHK(hipMemcpyAsync(d_fo.p, f.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_ro.p, r.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    const int rc = pairs_pass_device(ctx, d_fo.p, d_ro.p, n, f.off[(size_t)n], r.off[(size_t)n], flags, max_total);
+    if (rc != ITSX_OK) return rc;
+  }
+  if ((flags & (itsx_fq::FQ_PAIR_QUAL1 | itsx_fq::FQ_PAIR_QUAL2)) || max_total > 12000) return PARSE_FALLBACK;      // the host path's errors, in its words
+  // ---- from here on the context's read set is replaced, as on the host path
+  const bool lower = (flags & (itsx_fq::FQ_PAIR_LOWER1 | itsx_fq::FQ_PAIR_LOWER2)) != 0;
+  const bool records = ctx->keep_records && !text1, pair_records = ctx->keep_pair_records && !text1 && !lower;
+  std::vector<const NameList *> ids((size_t)S);
+  for (int32_t s = 0; s < S; s++) { ids[(size_t)s] = &names[(size_t)s]; if (batch && n_pairs_per_sample) n_pairs_per_sample[s] = counts[0][(size_t)s]; }
+  itsx_ctx::PairSide &p1 = ctx->pp[0], &p2 = ctx->pp[1];
+  MergeDev dev{&p1.seq, &p1.qual, &p2.seq, &p2.qual, &p1.titles, &p2.titles, &d_fo, &d_ro, &toff[0], &toff[1], max_total};
+  std::vector<int64_t> merged((size_t)S, 0);
+  const int rc = merge_load_core(ctx, f, r, ids, pstart, seq_out_paths, maxdiffs, maxee, allow_stagger,
+                                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count(), merged.data(), records, pair_records, &dev);
+  if (rc != ITSX_OK) return rc;
+  if (batch) { if (n_merged_per_sample) for (int32_t s = 0; s < S; s++) n_merged_per_sample[s] = merged[(size_t)s]; }
+  else { if (n_pairs_per_sample) *n_pairs_per_sample = n; if (n_merged_per_sample) *n_merged_per_sample = merged[0]; }
+  return ITSX_OK;
+}
 extern "C" {
 int itsx_set_device_parse(itsx_ctx *ctx, int on)
 {
@@ -5704,6 +5902,80 @@ int itsx_parse_fetch(itsx_ctx *ctx, int32_t plane, int64_t lo, int64_t hi, void 
   }
   const uint8_t *src = plane == ITSX_PARSE_SEQ ? ctx->ps_seq.p : plane == ITSX_PARSE_QUAL ? ctx->ps_qual.p : ctx->ps_titles.p;
   return fetch_staged(ctx, src + lo, hi - lo, reinterpret_cast<char *>(out));
+}
+int itsx_parse_pairs_device(itsx_ctx *ctx, const char *text1, int64_t nbytes1, const char *text2, int64_t nbytes2, int64_t *n_pairs, int32_t *flags, int64_t *max_total)
+{
+  CTXCHK(ctx && nbytes1 >= 0 && nbytes2 >= 0 && (text1 || nbytes1 == 0) && (text2 || nbytes2 == 0) && n_pairs && flags && max_total);
+  std::lock_guard<std::mutex> g(ctx->ps_mu);
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->ps_n = -1; ctx->pp_n = -1; ctx->stats.ms_parse = 0;
+  int64_t n[2] = {0, 0};
+  for (int side = 0; side < 2; side++) {
+    const char *text = side ? text2 : text1; const int64_t nbytes = side ? nbytes2 : nbytes1;
+    bool fits = true;
+    { const int rc = parse_upload(ctx, text, nbytes, fits); if (rc != ITSX_OK) return rc; }
+    if (!fits) {
+      ctx->n_parse_declined++;
+      SET_ERR(ctx, ITSX_E_UNSUPPORTED, std::string("the device parse declined the text: ") + itsx_fq::fq_reason_name(itsx_fq::FQ_E_NOMEM) + ": the text's " + std::to_string(nbytes) + " bytes");
+    }
+    ParsedText pt;
+    {
+      PairSideScope planes(ctx, side);
+      const int rc = parse_text_device(ctx, ctx->ps_text.p, nbytes, true, 0, 0, pt);
+      if (rc != ITSX_OK) return rc;
+    }
+    itsx_ctx::PairSide &p = ctx->pp[side];
+    dbuf_swap(p.off, ctx->ps_off); dbuf_swap(p.toff, ctx->ps_toff);      // (the next text's parse makes its own)
+    p.nb = pt.nb; p.nt = pt.nt; n[side] = pt.n;
+  }
+  if (n[0] != n[1])
+    SET_ERR(ctx, ITSX_E_UNSUPPORTED, std::string("the device parse declined the pair: ") + itsx_fq::fq_reason_name(itsx_fq::FQ_E_PAIRS) + " (" + std::to_string(n[0]) + " and " + std::to_string(n[1]) + ")");
+  { const int rc = pairs_pass_device(ctx, ctx->pp[0].off.p, ctx->pp[1].off.p, n[0], ctx->pp[0].nb, ctx->pp[1].nb, *flags, *max_total); if (rc != ITSX_OK) return rc; }
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  HIPCHK(hipGetLastError());
+  ctx->pp_n = n[0];
+  *n_pairs = n[0];
+  return ITSX_OK;
+}
+int itsx_parse_pairs_fetch(itsx_ctx *ctx, int32_t side, int32_t plane, int64_t lo, int64_t hi, void *out)
+{
+  CTXCHK(ctx);
+  std::lock_guard<std::mutex> g(ctx->ps_mu);
+  if (ctx->pp_n < 0) SET_ERR(ctx, ITSX_E_ARG, "itsx_parse_pairs_fetch: no parse to fetch from (the last itsx_parse_pairs_device did not succeed, or there was none)");
+  if (side < 0 || side > 1) SET_ERR(ctx, ITSX_E_ARG, "itsx_parse_pairs_fetch: no such side");
+  if (plane < ITSX_PARSE_OFF || plane > ITSX_PARSE_TITLES) SET_ERR(ctx, ITSX_E_ARG, "itsx_parse_pairs_fetch: no such plane");
+  const itsx_ctx::PairSide &p = ctx->pp[side];
+  const bool offs = plane == ITSX_PARSE_OFF || plane == ITSX_PARSE_TOFF;
+  const int64_t size = offs ? ctx->pp_n + 1 : plane == ITSX_PARSE_TITLES ? p.nt : p.nb;
+  if (lo < 0 || hi < lo || hi > size || (!out && hi > lo)) SET_ERR(ctx, ITSX_E_ARG, "itsx_parse_pairs_fetch: the range is not inside the plane's " + std::to_string(size) + (offs ? " entries" : " bytes"));
+  if (hi == lo) return ITSX_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (offs) {
+    if (ctx->pp_n == 0) { *reinterpret_cast<int64_t *>(out) = 0; return ITSX_OK; }      // texts of no bytes: off = toff = {0}
+    const int64_t *src = plane == ITSX_PARSE_OFF ? p.off.p : p.toff.p;
+    return fetch_staged(ctx, reinterpret_cast<const uint8_t *>(src + lo), (hi - lo) * 8, reinterpret_cast<char *>(out));
+  }
+  const uint8_t *src = plane == ITSX_PARSE_SEQ ? p.seq.p : plane == ITSX_PARSE_QUAL ? p.qual.p : p.titles.p;
+  return fetch_staged(ctx, src + lo, hi - lo, reinterpret_cast<char *>(out));
+}
+int itsx_debug_parse_pairs_host(const char *text1, int64_t nbytes1, const char *text2, int64_t nbytes2, int64_t *off1, int64_t *toff1, char *seq1, char *qual1, char *titles1,
+                                int64_t *off2, int64_t *toff2, char *seq2, char *qual2, char *titles2, int64_t cap_records, int64_t cap_bases, int64_t cap_titles,
+                                int64_t *n_pairs, int64_t *sizes, int32_t *flags, int64_t *max_total, int32_t *reason, int32_t *bad_side, int64_t *bad_record)
+{
+  if (nbytes1 < 0 || nbytes2 < 0 || (!text1 && nbytes1 > 0) || (!text2 && nbytes2 > 0) || !off1 || !toff1 || !off2 || !toff2 || cap_records < 0 || cap_bases < 0 || cap_titles < 0 ||
+      ((!seq1 || !qual1 || !seq2 || !qual2) && cap_bases > 0) || ((!titles1 || !titles2) && cap_titles > 0) || !n_pairs || !sizes || !flags || !max_total || !reason || !bad_side || !bad_record)
+    return ITSX_E_ARG;
+  auto u = [](char *p) { return reinterpret_cast<uint8_t *>(p); };
+  const itsx_fq::FqSideBufs b1{off1, toff1, u(seq1), u(qual1), u(titles1)}, b2{off2, toff2, u(seq2), u(qual2), u(titles2)};
+  *reason = itsx_fq::fq_parse_pairs_host(reinterpret_cast<const uint8_t *>(text1), nbytes1, reinterpret_cast<const uint8_t *>(text2), nbytes2, b1, b2, cap_records, cap_bases, cap_titles,
+                                         n_pairs, sizes, flags, max_total, bad_side, bad_record);
+  return *reason == itsx_fq::FQ_OK ? ITSX_OK : *reason == itsx_fq::FQ_E_CAP ? ITSX_E_ARG : ITSX_E_UNSUPPORTED;
+}
+int itsx_debug_pair_pass_host(char *seq, const char *qual, int64_t nbytes, int32_t *flags)
+{
+  if (nbytes < 0 || ((!seq || !qual) && nbytes > 0) || !flags) return ITSX_E_ARG;
+  *flags = itsx_fq::fq_pair_side_host(reinterpret_cast<uint8_t *>(seq), reinterpret_cast<const uint8_t *>(qual), nbytes);
+  return ITSX_OK;
 }
 int itsx_debug_parse_host(const char *text, int64_t nbytes, int64_t *off, int64_t *toff, int64_t cap_records, char *seq, char *qual, int64_t cap_bases,
                           char *titles, int64_t cap_titles, int64_t *n_records, int64_t *n_bases, int64_t *n_title_bytes, int32_t *reason, int64_t *bad_record)

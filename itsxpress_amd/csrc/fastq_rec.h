@@ -32,6 +32,7 @@ enum : int32_t {
   FQ_E_QUAL = 4,         // a quality line and its sequence line differ in length
   FQ_E_NOMEM = 5,        // device memory for the index or the planes could not be had
   FQ_E_CAP = 6,          // (host routine only) the caller's buffers are too small
+  FQ_E_PAIRS = 7,        // (a pair of texts only) R1 and R2 hold different numbers of records
 };
 
 inline const char *fq_reason_name(int32_t why)
@@ -44,6 +45,7 @@ inline const char *fq_reason_name(int32_t why)
     case FQ_E_QUAL: return "quality and sequence differ in length";
     case FQ_E_NOMEM: return "no memory";
     case FQ_E_CAP: return "buffers too small";
+    case FQ_E_PAIRS: return "R1 and R2 hold different numbers of records";
   }
   return "unknown";
 }
@@ -112,6 +114,94 @@ inline int32_t fq_parse_host(const uint8_t *text, int64_t nbytes, int64_t *off, 
     nb += q.sl; nt += q.tl;
   }
   off[n] = nb; toff[n] = nt;
+  return FQ_OK;
+}
+
+// ---- the pass over a pair's planes (k_fastq.hip: k_fastq_pairs; the paired merge loaders of a context that opted in).  What the host
+// path does to R1 / R2 between its parser and the merge kernel, per 16 aligned bytes of a plane held as four little-endian dwords:
+//   bases      'a'..'z' -> 'A'..'Z' and nothing else (the host parser's toupper in the C locale); "changed" is reported,
+//   qualities  every byte must lie in 33..126 (merge_core's check).
+// Byte-parallel arithmetic on the low seven bits of each byte, so no carry crosses a byte: bit 7 of a byte of (h + 0x1f) says h >= 'a',
+// of (h + 0x05) says h > 'z', of (h + 0x5f) says h >= 33, of (h + 0x01) says h == 127; a byte above 127 is neither a letter nor a quality.
+enum : int32_t { FQ_PAIR_LOWER1 = 1, FQ_PAIR_LOWER2 = 2, FQ_PAIR_QUAL1 = 4, FQ_PAIR_QUAL2 = 8 };      // the flags of a pair of texts
+
+FQ_HD uint32_t fq_upper4(uint32_t x)
+{
+  const uint32_t h = x & 0x7f7f7f7fu;
+  const uint32_t lower = (h + 0x1f1f1f1fu) & ~(h + 0x05050505u) & ~x & 0x80808080u;
+  return x ^ (lower >> 2);
+}
+FQ_HD uint32_t fq_qual_bad4(uint32_t x)
+{
+  const uint32_t h = x & 0x7f7f7f7fu;
+  return (x | ~(h + 0x5f5f5f5fu) | (h + 0x01010101u)) & 0x80808080u;
+}
+// true: a base changed
+FQ_HD bool fq_upper16(uint32_t (&w)[4])
+{
+  uint32_t diff = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) { const uint32_t u = fq_upper4(w[k]); diff |= u ^ w[k]; w[k] = u; }
+  return diff != 0;
+}
+FQ_HD bool fq_qual_ok16(const uint32_t (&w)[4]) { return (fq_qual_bad4(w[0]) | fq_qual_bad4(w[1]) | fq_qual_bad4(w[2]) | fq_qual_bad4(w[3])) == 0; }
+// the same by bytes: the last, partial group of a plane
+FQ_HD uint8_t fq_upper1(uint8_t c) { return (c >= 'a' && c <= 'z') ? (uint8_t)(c - 32) : c; }
+FQ_HD bool fq_qual_ok1(uint8_t c) { return c >= 33 && c <= 126; }
+
+// one side on one host thread, group by group as the kernel's lanes go: bytes [0, total) of seq are upper-cased in place (stored only
+// where a byte changed), nothing else is touched.  Returns FQ_PAIR_LOWER1 | FQ_PAIR_QUAL1 as they apply.
+inline int32_t fq_pair_side_host(uint8_t *seq, const uint8_t *qual, int64_t total)
+{
+  int32_t flags = 0;
+  int64_t p = 0;
+  for (; p + 16 <= total; p += 16) {
+    uint32_t w[4];
+    memcpy(w, seq + p, 16);
+    if (fq_upper16(w)) { memcpy(seq + p, w, 16); flags |= FQ_PAIR_LOWER1; }
+    memcpy(w, qual + p, 16);
+    if (!fq_qual_ok16(w)) flags |= FQ_PAIR_QUAL1;
+  }
+  for (; p < total; p++) {
+    const uint8_t u = fq_upper1(seq[p]);
+    if (u != seq[p]) { seq[p] = u; flags |= FQ_PAIR_LOWER1; }
+    if (!fq_qual_ok1(qual[p])) flags |= FQ_PAIR_QUAL1;
+  }
+  return flags;
+}
+// the longest pair: max over i of (off1[i + 1] - off1[i]) + (off2[i + 1] - off2[i]); no pairs: 0
+inline int64_t fq_pair_max_total(const int64_t *off1, const int64_t *off2, int64_t n)
+{
+  int64_t m = 0;
+  for (int64_t i = 0; i < n; i++) { const int64_t t = (off1[i + 1] - off1[i]) + (off2[i + 1] - off2[i]); m = t > m ? t : m; }
+  return m;
+}
+
+// Two texts as a pair, on one host thread: each by fq_parse_host into its own buffers (caps per side), then the pass.  Returns FQ_OK, a
+// side's reason (*bad_side = 0 / 1, *bad_record as fq_parse_host gives it), FQ_E_PAIRS (*bad_side = -1), or FQ_E_CAP; sizes[4] = bases
+// and title bytes of R1, then of R2 (set on FQ_OK and FQ_E_CAP, like *n_pairs).  Nothing is written to a buffer unless FQ_OK is returned.
+struct FqSideBufs { int64_t *off, *toff; uint8_t *seq, *qual, *titles; };
+inline int32_t fq_parse_pairs_host(const uint8_t *text1, int64_t nbytes1, const uint8_t *text2, int64_t nbytes2, const FqSideBufs &b1, const FqSideBufs &b2,
+                                   int64_t cap_records, int64_t cap_bases, int64_t cap_titles, int64_t *n_pairs, int64_t *sizes, int32_t *flags, int64_t *max_total,
+                                   int32_t *bad_side, int64_t *bad_record)
+{
+  const uint8_t *text[2] = {text1, text2}; const int64_t nbytes[2] = {nbytes1, nbytes2}; const FqSideBufs *b[2] = {&b1, &b2};
+  int64_t n[2] = {0, 0};
+  *n_pairs = 0; sizes[0] = sizes[1] = sizes[2] = sizes[3] = 0; *flags = 0; *max_total = 0; *bad_side = -1; *bad_record = -1;
+  for (int s = 0; s < 2; s++) {                  // measured first (no room at all: nothing can be written)
+    const int32_t why = fq_parse_host(text[s], nbytes[s], nullptr, nullptr, -1, nullptr, nullptr, -1, nullptr, -1, &n[s], &sizes[2 * s], &sizes[2 * s + 1], bad_record);
+    if (why != FQ_E_CAP) { *bad_side = s; sizes[0] = sizes[1] = sizes[2] = sizes[3] = 0; return why; }
+  }
+  if (n[0] != n[1]) { sizes[0] = sizes[1] = sizes[2] = sizes[3] = 0; return FQ_E_PAIRS; }
+  *n_pairs = n[0];
+  if (cap_records < n[0] || cap_bases < sizes[0] || cap_bases < sizes[2] || cap_titles < sizes[1] || cap_titles < sizes[3]) return FQ_E_CAP;
+  for (int s = 0; s < 2; s++) {
+    int64_t nn, nb, nt, rec;
+    const int32_t why = fq_parse_host(text[s], nbytes[s], b[s]->off, b[s]->toff, cap_records, b[s]->seq, b[s]->qual, cap_bases, b[s]->titles, cap_titles, &nn, &nb, &nt, &rec);
+    if (why != FQ_OK) { *bad_side = s; *bad_record = rec; return why; }
+    *flags |= fq_pair_side_host(b[s]->seq, b[s]->qual, nb) << s;
+  }
+  *max_total = fq_pair_max_total(b1.off, b2.off, n[0]);
   return FQ_OK;
 }
 

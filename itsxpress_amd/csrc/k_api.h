@@ -286,6 +286,11 @@ void launch_fastq_plan(const FastqArgs &a, hipStream_t st);
 // line `which` (0 title, 1 bases, 3 qualities) of every record to dst[gbase + doff[r] ...): doff = off or toff of the plan, total = doff[n]
 // bytes; dst is 16-byte aligned and holds gbase + total bytes; the bytes of dst below gbase are left as they are
 void launch_fastq_gather(const uint8_t *text, const int64_t *nl, const int64_t *doff, int64_t n, int which, uint8_t *dst, int64_t gbase, int64_t total, hipStream_t st);
+// the pass over the finished planes of a pair of texts (side 0: R1, side 1: R2; planes 16-byte aligned, total[s] = off[s][n] bytes each):
+// bases 'a'..'z' -> upper case in place, info[0] = fastq_rec.h's FQ_PAIR_* flags (a base changed, a quality outside 33..126, per side),
+// info[1] = the longest pair, max over i < n of R1's plus R2's length (no pairs: 0).  info is zeroed first.
+struct FastqPairArgs { uint8_t *seq[2]; const uint8_t *qual[2]; int64_t total[2]; const int64_t *off[2]; int64_t n; unsigned long long *info; };
+void launch_fastq_pairs(const FastqPairArgs &a, hipStream_t st);
 
 // ---- k_util.hip
 // exclusive prefix sum of n int32 values (n < 2^31); tmp must hold scan_tmp_elems(n) int32

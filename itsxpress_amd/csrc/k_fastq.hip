@@ -12,6 +12,9 @@
 //           the tile's ends; where its 16 bytes come from one line they are five aligned dwords funnel-shifted into four -- the
 //           misalignment of source against destination falls on the loads -- and at the seams between records they are copied byte by
 //           byte.  Work follows output bytes: a 65 535-base read is spread over the lanes like anything else.
+// A pair of texts (the paired merge loaders, itsx_parse_pairs_device) takes one more pass, a kernel of its own over both sides' finished
+// planes (k_fastq_pairs): what the host path does between its parser and the merge kernel -- bases to upper case, qualities checked
+// against 33..126, the longest pair measured.
 #include <algorithm>
 #include "engine.h"
 #include "k_api.h"
@@ -211,6 +214,72 @@ void launch_fastq_gather(const uint8_t *text, const int64_t *nl, const int64_t *
   a.ntiles = (gbase + total - a.g0 + FG_TILE - 1) / FG_TILE;
   const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, 256 * 8);
   hipLaunchKernelGGL(k_fastq_gather, dim3(grid), dim3(FG_BLOCK), 0, st, a);
+}
+
+// ---- the pass over a pair's planes -----------------------------------------------------------------------------------------------
+// OUTPUT-stationary like the gather: a lane owns 16 aligned bytes of a plane, four dwords through fastq_rec.h's byte-parallel routines,
+// and stores them only where upper-casing changed one.  A plane starts at an allocation's first byte, so only its last group can be
+// partial: that one goes byte by byte, and nothing at or past `total` is read or written.  Then the pairs: fl + rl from the two offset
+// arrays, the block's maximum through one atomicMax.  The flags of a wave are folded with shuffles into one atomicOr at most.
+constexpr int FQP_BLOCK = 256;
+
+__global__ __launch_bounds__(FQP_BLOCK) void k_fastq_pairs(FastqPairArgs a)
+{
+  const int64_t t0 = (int64_t)blockIdx.x * FQP_BLOCK + threadIdx.x, stride = (int64_t)gridDim.x * FQP_BLOCK;
+  uint32_t flags = 0;
+#pragma unroll
+  for (int s = 0; s < 2; s++) {
+    uint8_t *seq = a.seq[s]; const uint8_t *qual = a.qual[s];
+    const int64_t total = a.total[s], groups = (total + 15) >> 4;
+    for (int64_t g = t0; g < groups; g += stride) {
+      const int64_t p = g << 4;
+      if (p + 16 <= total) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(seq + p), q = *reinterpret_cast<const uint4 *>(qual + p);
+        uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        const uint32_t qw[4] = {q.x, q.y, q.z, q.w};
+        if (fq_upper16(w)) { *reinterpret_cast<uint4 *>(seq + p) = make_uint4(w[0], w[1], w[2], w[3]); flags |= (uint32_t)FQ_PAIR_LOWER1 << s; }
+        if (!fq_qual_ok16(qw)) flags |= (uint32_t)FQ_PAIR_QUAL1 << s;
+      } else {
+        for (int64_t b = p; b < total; b++) {
+          const uint8_t c = seq[b], u = fq_upper1(c);
+          if (u != c) { seq[b] = u; flags |= (uint32_t)FQ_PAIR_LOWER1 << s; }
+          if (!fq_qual_ok1(qual[b])) flags |= (uint32_t)FQ_PAIR_QUAL1 << s;
+        }
+      }
+    }
+  }
+  int64_t longest = 0;
+  for (int64_t i = t0; i < a.n; i += stride) {
+    const int64_t t = (a.off[0][i + 1] - a.off[0][i]) + (a.off[1][i + 1] - a.off[1][i]);
+    longest = t > longest ? t : longest;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    flags |= (uint32_t)__shfl_xor((int)flags, d, 64);
+    const int64_t o = __shfl_xor(longest, d, 64);
+    longest = o > longest ? o : longest;
+  }
+  __shared__ int64_t part[FQP_BLOCK / 64];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) {
+    part[wid] = longest;
+    if (flags) atomicOr(a.info, (unsigned long long)flags);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < FQP_BLOCK / 64; w++) longest = part[w] > longest ? part[w] : longest;
+    if (longest > 0) atomicMax(a.info + 1, (unsigned long long)longest);
+  }
+}
+
+void launch_fastq_pairs(const FastqPairArgs &a, hipStream_t st)
+{
+  (void)hipMemsetAsync(a.info, 0, 2 * sizeof(unsigned long long), st);
+  const int64_t items = std::max(std::max((a.total[0] + 15) >> 4, (a.total[1] + 15) >> 4), a.n);
+  if (items <= 0) return;
+  const unsigned grid = (unsigned)std::min<int64_t>((items + FQP_BLOCK - 1) / FQP_BLOCK, 256 * 8);
+  hipLaunchKernelGGL(k_fastq_pairs, dim3(grid), dim3(FQP_BLOCK), 0, st, a);
 }
 
 }  // namespace itsx

@@ -81,7 +81,7 @@ static const Switch g_sw[] = {
   {"ITSX_DEVICE_INFLATE", SW_TUNING, "=1: the whole-file loaders of every context try a gzip file of independent members on the device first (same text; read at every load)"},
   {"ITSX_INFLATE_MEMBER_KB", SW_TUNING, "longest compressed member the device inflate takes (default 8192: twice the host writer's block); a file with a longer one is the host's"},
   {"ITSX_INFLATE_GRID", SW_TUNING, "most workgroups of the device inflate's launch (default: four per CU, what their LDS allows); fewer: each decodes more members in a row (same text)"},
-  {"ITSX_DEVICE_PARSE", SW_TUNING, "=1: the whole-file loaders of every context parse FASTQ text on the device (same reads; a text it declines is the host parser's; read at every load)"},
+  {"ITSX_DEVICE_PARSE", SW_TUNING, "=1: the whole-file loaders and the paired merge loaders of every context parse FASTQ text on the device (same reads; a text it declines is the host parser's; read at every load)"},
   {"ITSX_PARALLEL_INFLATE", SW_TUNING, "=0: single-stream inflate"},
   {"ITSX_PINFLATE_CHUNK_KB", SW_TUNING, "chunk of the block-parallel inflater"},
   {"ITSX_PARSE_MIN_MB", SW_TUNING, "smallest text parsed on several threads"},

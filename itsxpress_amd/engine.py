@@ -94,11 +94,15 @@ class Engine:
             self._chk(self.L.itsx_set_device_inflate(self.h, int(where == "device")))
         self._inflate = where
 
-    # Where the context's whole-file loaders (load_reads_file, load_reads_text, load_reads_files) parse FASTQ text: "host" (the default:
-    # the I/O threads, as ever) or "device" (csrc/k_fastq.hip: the text is parsed where the device inflate left it, or uploaded once;
-    # only offsets and title lines come back, and the bases stay on the device until rep.fa asks for them; a text the device declines
-    # -- FASTA, blank lines, a malformed record -- makes the call start over on the host).  The same reads either way.  A file the
-    # device both inflated and parsed never enters the host's text cache: a writer that wants its text later reads the file again.
+    # Where the context's whole-file loaders (load_reads_file, load_reads_text, load_reads_files) and its paired merge loaders
+    # (merge_pairs_load, merge_pairs_load_text, merge_pairs_load_files) parse FASTQ text: "host" (the default: the I/O threads, as ever)
+    # or "device" (csrc/k_fastq.hip: the text is parsed where the device inflate left it, or uploaded once; only offsets and title
+    # lines come back, and the bases stay on the device until rep.fa asks for them; a text the device declines -- FASTA, blank lines, a
+    # malformed record -- makes the call start over on the host).  The merge loaders parse R1 and R2 into a plane set each, upper-case
+    # and check them there, and the merge kernel and keep_pair_records take the planes where they lie; unequal record counts, a quality
+    # outside 33..126 and a pair above 12000 bases also start over on the host, whose errors they then are.  merge_pairs_files and the
+    # orient, shard and streamed loaders parse on the host.  The same reads either way.  A file the device both inflated and parsed
+    # never enters the host's text cache: a writer that wants its text later reads the file again.
     @property
     def parse(self):
         return getattr(self, "_parse", "host")
@@ -738,6 +742,31 @@ class Engine:
         off, toff = self.parse_fetch("off", 0, n + 1), self.parse_fetch("toff", 0, n + 1)
         return dict(n=n, off=off, toff=toff, seq=self.parse_fetch("seq", 0, int(off[-1])),
                     qual=self.parse_fetch("qual", 0, int(off[-1])) if keep_qual else None, titles=self.parse_fetch("titles", 0, int(toff[-1])))
+
+    # ---- a pair of texts through the device parse
+    def parse_pairs_fetch(self, side, plane, lo, hi):
+        """parse_fetch for one side (0: R1, 1: R2) of the last parse_pairs_device."""
+        k = self.PARSE_PLANES[plane]
+        n = max(int(hi) - int(lo), 0)
+        out = np.empty(max(n, 1), np.int64 if k < 2 else np.uint8)
+        self._chk(self.L.itsx_parse_pairs_fetch(self.h, int(side), k, int(lo), int(hi), out.ctypes.data))
+        return out[:n].copy() if k < 2 else out[:n].tobytes()
+
+    def parse_pairs_device(self, text1, text2):
+        """R1's and R2's FASTQ text taken apart on the device as the paired merge loaders do under parse = "device", nothing merged: a
+        dict of n, flags (bit 0 / 1: upper-casing changed a base of R1 / R2, bit 2 / 3: a quality of R1 / R2 outside 33..126),
+        max_total (the longest pair) and sides, two dicts of off, toff, seq (upper case), qual and titles.  EngineError with code -5
+        when the device declined a text or the two hold different numbers of records."""
+        text1, text2 = bytes(text1), bytes(text2)
+        n, flags, mx = C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        self._chk(self.L.itsx_parse_pairs_device(self.h, text1, len(text1), text2, len(text2), C.byref(n), C.byref(flags), C.byref(mx)))
+        n = int(n.value)
+        sides = []
+        for s in (0, 1):
+            off, toff = self.parse_pairs_fetch(s, "off", 0, n + 1), self.parse_pairs_fetch(s, "toff", 0, n + 1)
+            sides.append(dict(off=off, toff=toff, seq=self.parse_pairs_fetch(s, "seq", 0, int(off[-1])), qual=self.parse_pairs_fetch(s, "qual", 0, int(off[-1])),
+                              titles=self.parse_pairs_fetch(s, "titles", 0, int(toff[-1]))))
+        return dict(n=n, flags=int(flags.value), max_total=int(mx.value), sides=sides)
 
     # ---- writers
     def write_uc(self, path):

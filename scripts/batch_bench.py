@@ -25,7 +25,14 @@ dereplicated and searched, and its `write_paired_trimmed` -- the host loop: ever
 `itsx_write_trimmed_paired` -- runs `repeats` times with the text cache as the merge left it and `repeats` times with it emptied first;
 then the same for a `SampleBatch(keep_records="pairs")`, whose `write_paired_trimmed` is one `itsx_write_trimmed_paired_samples` from the
 pair records on the device.  Medians, the plan's and the copy's device times, and a check that every sample's two files are the same bytes.
-Usage: python scripts/batch_bench.py --trim-paired [n_samples] [pairs_per_sample] [repeats]"""
+Usage: python scripts/batch_bench.py --trim-paired [n_samples] [pairs_per_sample] [repeats]
+
+--pairs-flow: the flow `SampleBatch(keep_records="pairs")` exists for, from the compressed input files to the compressed output files on
+one warm context -- `merge_reads` + `deduplicate` + `_search` + `write_trimmed` + `write_paired_trimmed` (gzipped) -- once per arm of
+`--inflate host,device` x `--parse host,device` (SampleBatch.inflate / .parse; default: host alone), the arms alternated within every
+repeat, the first repeat the warm-up.  The inputs are gzip files of the device deflate's members (`--plain-inputs`: plain text).
+Per arm the stage times of every repeat, the parse and inflate counters, and a check that every arm wrote the same bytes.
+Usage: python scripts/batch_bench.py --pairs-flow [n_samples] [pairs_per_sample] [repeats] [--inflate LIST] [--parse LIST] [--plain-inputs]"""
 import gzip
 import hashlib
 import json
@@ -48,7 +55,17 @@ PAIRED = "--paired" in sys.argv
 ORIENT = "--orient" in sys.argv
 TRIM = "--trim" in sys.argv
 TRIM_PAIRED = "--trim-paired" in sys.argv
-argv = [a for a in sys.argv[1:] if a not in ("--paired", "--orient", "--trim", "--trim-paired")]
+PAIRS_FLOW = "--pairs-flow" in sys.argv
+PLAIN_INPUTS = "--plain-inputs" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--paired", "--orient", "--trim", "--trim-paired", "--pairs-flow", "--plain-inputs")]
+WHERE = {}
+for opt in ("--inflate", "--parse"):           # where the batch's loaders inflate and parse: host, device or a comma-separated list (arms)
+    if opt in argv:
+        k = argv.index(opt)
+        WHERE[opt[2:]] = argv[k + 1].split(",")
+        del argv[k:k + 2]
+if any(w not in ("host", "device") for l in WHERE.values() for w in l) or (WHERE and not PAIRS_FLOW):
+    sys.exit("--inflate / --parse take host, device or a comma-separated list of them, and go with --pairs-flow")
 S = int(argv[0]) if len(argv) > 0 else 96
 n = int(argv[1]) if len(argv) > 1 else 10000
 thmm = gzip.open(ROOT + "/tests/golden/T.hmm.gz", "rt").read()
@@ -402,6 +419,84 @@ def trim_paired_main():
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def pairs_flow_main():
+    from itsxpress_amd import SeqSamplePairedNotInterleaved
+    from itsxpress_amd.batch import SampleBatch
+    from itsxpress_amd.trim import cache_clear
+    os.environ["ITSXPRESS_ARRAYS"] = "0"
+    repeats = int(argv[2]) if len(argv) > 2 else 4
+    arms = [(i, p) for i in WHERE.get("inflate", ["host"]) for p in WHERE.get("parse", ["host"])]
+    tmp = tempfile.mkdtemp(prefix="itsx_batch_bench_")
+    try:
+        eng = Engine(0)
+        files = [write_paired_sample(tmp, s, n) for s in range(S)]
+        if not PLAIN_INPUTS:
+            for fs in files:
+                for k, p in enumerate(fs):
+                    with open(p, "rb") as f:
+                        text = f.read()
+                    with open(p + ".gz", "wb") as f:
+                        f.write(eng.deflate_device(text, [0, len(text)])[0])
+                    os.remove(p)
+                    fs[k] = p + ".gz"
+        hmm = os.path.join(tmp, "its2.hmm")
+        with open(hmm, "w") as f:
+            f.write(its2_profiles(thmm))
+        counters = ("n_parse_device", "n_parse_declined", "n_inflate_device", "n_inflate_declined")
+
+        def flow(fs, tag, arm):
+            d = os.path.join(tmp, tag)
+            os.makedirs(d, exist_ok=True)
+            cache_clear()                      # every run reads and inflates its inputs itself
+            st0 = eng.stats()
+            t, t0 = {}, time.perf_counter()
+            objs = [SeqSamplePairedNotInterleaved(r1, d, r2) for r1, r2 in fs]
+            b = SampleBatch(objs, engine=eng, keep_records="pairs")
+            b.inflate, b.parse = arm
+            b.merge_reads(threads=1, stagger=False)
+            t["merge"] = time.perf_counter() - t0
+            moved = {k: int(eng.stats()[k] - st0[k]) for k in counters}
+            t0 = time.perf_counter()
+            b.deduplicate(threads=1)
+            b._search(hmmfile=hmm, threads=1)
+            t["derep+search"] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            om = [os.path.join(d, "m_%04d.fq.gz" % k) for k in range(len(fs))]
+            o1 = [os.path.join(d, "t_%04d_R1.fq.gz" % k) for k in range(len(fs))]
+            o2 = [os.path.join(d, "t_%04d_R2.fq.gz" % k) for k in range(len(fs))]
+            b.write_trimmed(om, "ITS2", gzipped=True)
+            ret = b.write_paired_trimmed(o1, o2, "ITS2", gzipped=True)
+            t["write"] = time.perf_counter() - t0
+            st = eng.stats()
+            digest = hashlib.sha256(b"".join(gzip.decompress(open(p, "rb").read()) for p in om + o1 + o2)).hexdigest()
+            shutil.rmtree(d, ignore_errors=True)
+            return dict({"s_" + k: round(v, 3) for k, v in t.items()}, s_total=round(sum(t.values()), 3), ms_parse=round(float(st["ms_parse"]), 2),
+                        ms_trim_copy=round(float(st["ms_trim_copy"]), 2), **moved), digest, int(sum(ret)), int(b.counts.sum())
+        for arm in arms:                       # warm-up on two samples: first-touch costs outside the timed runs
+            flow(files[:2], "warm_%s_%s" % arm, arm)
+        out = [dict(inflate=i, parse=p, runs=[]) for i, p in arms]
+        digests = set()
+        for r in range(repeats):
+            for k, arm in enumerate(arms):
+                res, digest, written, merged = flow(files, "run_%d_%d" % (r, k), arm)
+                out[k]["runs"].append(res)
+                digests.add((digest, written, merged))
+                print("[batch_bench] repeat %d, inflate %s, parse %s: %.2f s (merge %.2f s, derep+search %.2f s, write %.2f s)" % (r, arm[0], arm[1], res["s_total"], res["s_merge"], res["s_derep+search"], res["s_write"]), file=sys.stderr, flush=True)
+        for a in out:
+            timed = a["runs"][1:] or a["runs"]
+            a["merge_median_s"] = round(float(np.median([x["s_merge"] for x in timed])), 3)
+            a["total_median_s"] = round(float(np.median([x["s_total"] for x in timed])), 3)
+        print(json.dumps({"pairs_flow": True, "samples": S, "pairs_per_sample": n, "repeats": repeats, "inputs": "plain" if PLAIN_INPUTS else "device-deflated gzip",
+                          "merged_reads": merged, "pairs_written": written, "arms": out, "identical_outputs": len(digests) == 1}))
+        return 0 if len(digests) == 1 else 1
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+if PAIRS_FLOW:
+    if len(argv) < 1:
+        S, n = 384, 2000
+    sys.exit(pairs_flow_main())
 if TRIM_PAIRED:
     if len(argv) < 1:
         S, n = 384, 2000

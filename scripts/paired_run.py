@@ -29,21 +29,34 @@ def main():
     ap.add_argument("--deflate", default="host", help="--stream: where the streamed writers' gzip members are made, host | device (StreamEngine.deflate); "
                                                       "a comma-separated list runs the streamed leg once per entry over the same files (arms of a comparison)")
     ap.add_argument("--check", action="store_true", help="--stream: the two outputs (inflated) must equal the staged run's byte for byte")
+    ap.add_argument("--inflate", default=None, help="where the staged run's merge loader inflates R1 / R2, host | device (Engine.inflate); a comma-separated "
+                                                     "list, like --parse, makes every inflate x parse combination an arm of a comparison over the same files")
+    ap.add_argument("--parse", default=None, help="where the merge loader parses R1 / R2, host | device (Engine.parse; with ITSXPRESS_ARRAYS=1 the staged run "
+                                                   "merges through itsx_merge_pairs_load).  --stream: the streamed leg runs once per entry, 'device' with ITSX_DEVICE_PARSE=1")
+    ap.add_argument("--runs", type=int, default=1, help="--inflate / --parse: staged runs per arm, the arms alternated within every round; the first round is the warm-up")
+    ap.add_argument("--in-writer", default="host", help="what deflates the two input files: host (this package's host writer) | device (the device deflate's "
+                                                         "65 535-byte members: the files on which the device inflate is the faster party)")
     args = ap.parse_args()
     arms = args.deflate.split(",")
     if any(a not in ("host", "device") for a in arms):
         ap.error("--deflate takes host, device or a comma-separated list of them")
-    print(json.dumps(run(args.pairs, args.array_path, args.stream, args.check, arms)))
+    lists = [(v or "host").split(",") for v in (args.inflate, args.parse)]
+    if any(a not in ("host", "device") for l in lists for a in l) or args.in_writer not in ("host", "device") or args.runs < 1:
+        ap.error("--inflate, --parse and --in-writer take host or device (the first two also a comma-separated list), --runs at least 1")
+    load_arms = [(i, p) for i in lists[0] for p in lists[1]] if (args.inflate or args.parse) else None
+    print(json.dumps(run(args.pairs, args.array_path, args.stream, args.check, arms, load_arms=load_arms, runs=args.runs, in_writer=args.in_writer)))
 
 
-def stream_leg(paths, hmm, tmp, deflate="host"):
+def stream_leg(paths, hmm, tmp, deflate="host", parse="host"):
     """the reference's call sequence (main.py:513-519, 534-554, 556-624) through the mirror with the streaming engine: R1 / R2 inflated side
     by side, merged chunk by chunk on the device, scored, the two outputs deflated while later chunks are scored"""
     import importlib
     S = importlib.import_module("itsxpress_amd.SeqSample")
     from itsxpress_amd import trim
-    keep = {k: os.environ.get(k) for k in ("ITSXPRESS_ARRAYS", "ITSXPRESS_STREAM", "ITSXPRESS_GPUS")}
+    keep = {k: os.environ.get(k) for k in ("ITSXPRESS_ARRAYS", "ITSXPRESS_STREAM", "ITSXPRESS_GPUS", "ITSX_DEVICE_PARSE")}
     os.environ.update({"ITSXPRESS_ARRAYS": "1", "ITSXPRESS_STREAM": "1", "ITSXPRESS_GPUS": "1"})
+    if parse == "device":                # every chunk's context merges its slices through itsx_merge_pairs_load_text: the switch reaches them all
+        os.environ["ITSX_DEVICE_PARSE"] = "1"
     trim.cache_clear()
     o1, o2 = os.path.join(tmp, "s1.fastq.gz"), os.path.join(tmp, "s2.fastq.gz")
     sobj = None
@@ -62,7 +75,7 @@ def stream_leg(paths, hmm, tmp, deflate="host"):
         total = time.perf_counter() - t0
         eng = sobj._engine
         outp = getattr(eng, "_out", None)
-        return {"deflate": deflate, "ms_deflate": round(getattr(outp, "ms_deflate", 0.0), 1),
+        return {"deflate": deflate, "parse": parse, "ms_deflate": round(getattr(outp, "ms_deflate", 0.0), 1),
                 "units_device": getattr(outp, "units_device", 0), "units_host_sliced": getattr(outp, "units_host", 0),
                 "s_total": round(total, 3), "s_merge+derep+search (streamed)": round(t_pipe, 3), "s_finalize+write tail": round(total - t_pipe, 3),
                 "chunks": int(eng.world), "pairs": int(getattr(eng, "n_pairs", 0)), "merged": int(eng.n_reads),
@@ -78,8 +91,11 @@ def stream_leg(paths, hmm, tmp, deflate="host"):
                 os.environ[k] = v
 
 
-def run(pairs, array_path=True, stream=False, check=False, arms=("host",)):
-    """the run as a function (bench.py --paired-pairs calls it for its `paired_file_to_file` key): the stage times as a dict"""
+def run(pairs, array_path=True, stream=False, check=False, arms=("host",), load_arms=None, runs=1, in_writer="host"):
+    """the run as a function (bench.py --paired-pairs calls it for its `paired_file_to_file` key): the stage times as a dict.
+    load_arms: None (the engine's settings are left alone) or [(inflate, parse)]: the staged run is made `runs` times per arm, the arms
+    alternated within every round, and `staged_arms` lists every run's stage times and counters; the top-level keys are the last run of
+    the first arm.  With --stream the streamed leg runs once per deflate arm and per parse setting among load_arms."""
     args = argparse.Namespace(pairs=int(pairs), array_path=bool(array_path))
     import synth
     from bench import its2_profiles
@@ -135,7 +151,16 @@ def run(pairs, array_path=True, stream=False, check=False, arms=("host",)):
                 for i in range(n):
                     f.write(b"@M0:1:000:1:%d:%d %s:N:0:1\n" % (1000 + i // 1000, i % 1000, tag[1:].encode()) + sq[i].tobytes() + b"\n+\n" + ql[i].tobytes() + b"\n")
             gz = plain + ".gz"
-            write_trimmed_fastq(plain, gz, np.zeros(n, np.int32), np.full(n, 1 << 30, np.int32), gzipped=True)
+            if in_writer == "device":
+                e0 = Engine(0)
+                with open(plain, "rb") as f:
+                    text = f.read()
+                with open(gz, "wb") as f:
+                    f.write(e0.deflate_device(text, [0, len(text)])[0])
+                e0.close()
+                del text
+            else:
+                write_trimmed_fastq(plain, gz, np.zeros(n, np.int32), np.full(n, 1 << 30, np.int32), gzipped=True)
             os.remove(plain)
             paths.append(gz)
             note(tag + " written")
@@ -148,41 +173,65 @@ def run(pairs, array_path=True, stream=False, check=False, arms=("host",)):
         eng.derep()
         eng.search()
         eng.finalize()
-        s = SeqSamplePairedNotInterleaved(paths[0], os.path.join(tmp, "work"), paths[1])
-        s._engine = eng
-        t = {}
-        note("staged run starts")
-        t0 = time.perf_counter()
-        s._merge_reads(threads=1, stagger=False)
-        t["merge"] = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        if args.array_path:
-            if getattr(s, "_reads_loaded_from", None) != s.seq_file:      # (ITSXPRESS_ARRAYS=1: the merge left its reads in the engine)
-                eng.load_reads_file(s.seq_file)
-            nu = eng.derep()
-            t["derep"] = time.perf_counter() - t0
+        from itsxpress_amd.trim import cache_clear
+
+        made = []
+
+        def staged(arm):
+            made.append(1)
+            if arm is not None:
+                eng.inflate, eng.parse = arm
+                cache_clear()                  # every arm reads and inflates the two files itself
+            st0 = eng.stats()
+            s = SeqSamplePairedNotInterleaved(paths[0], os.path.join(tmp, "work%d" % len(made)), paths[1])
+            s._engine = eng
+            t = {}
+            note("staged run starts")
             t0 = time.perf_counter()
-            eng.set_rows_mode("lazy")              # what SeqSample._search selects in arrays mode (coordinates only, no domtbl.txt)
-            eng.search()
-            eng.finalize()
-        else:
-            s.deduplicate(threads=1)
-            nu = eng.n_unique
-            t["derep"] = time.perf_counter() - t0
+            s._merge_reads(threads=1, stagger=False)
+            t["merge"] = time.perf_counter() - t0
             t0 = time.perf_counter()
-            s._search(hmmfile=hmm, threads=1)
-        t["search"] = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        start, stop, tl, ind = s.trim_coordinates("ITS2")
-        names = eng.read_names_raw()
-        t["coords+names"] = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        o1, o2 = os.path.join(tmp, "o1.fastq.gz"), os.path.join(tmp, "o2.fastq.gz")
-        nw = write_trimmed_paired(paths[0], paths[1], o1, o2, names, start, stop, tl, gzipped=True)
-        t["write"] = time.perf_counter() - t0
-        total = sum(t.values())
-        kept = int(((start >= 0) & (stop >= 0) & (start < stop)).sum())
-        assert nw == kept, (nw, kept)
+            if args.array_path:
+                if getattr(s, "_reads_loaded_from", None) != s.seq_file:      # (ITSXPRESS_ARRAYS=1: the merge left its reads in the engine)
+                    eng.load_reads_file(s.seq_file)
+                nu = eng.derep()
+                t["derep"] = time.perf_counter() - t0
+                t0 = time.perf_counter()
+                eng.set_rows_mode("lazy")              # what SeqSample._search selects in arrays mode (coordinates only, no domtbl.txt)
+                eng.search()
+                eng.finalize()
+            else:
+                s.deduplicate(threads=1)
+                nu = eng.n_unique
+                t["derep"] = time.perf_counter() - t0
+                t0 = time.perf_counter()
+                s._search(hmmfile=hmm, threads=1)
+            t["search"] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            start, stop, tl, ind = s.trim_coordinates("ITS2")
+            names = eng.read_names_raw()
+            t["coords+names"] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            o1, o2 = os.path.join(tmp, "o1.fastq.gz"), os.path.join(tmp, "o2.fastq.gz")
+            nw = write_trimmed_paired(paths[0], paths[1], o1, o2, names, start, stop, tl, gzipped=True)
+            t["write"] = time.perf_counter() - t0
+            total = sum(t.values())
+            kept = int(((start >= 0) & (stop >= 0) & (start < stop)).sum())
+            assert nw == kept, (nw, kept)
+            st1 = eng.stats()
+            moved = {k: int(st1[k] - st0[k]) for k in ("n_parse_device", "n_parse_declined", "n_inflate_device", "n_inflate_declined")}
+            return t, total, nu, nw, names, start, stop, tl, o1, o2, dict(moved, ms_parse=round(float(st1["ms_parse"]), 2), ms_merge=round(float(st1["ms_merge"]), 2))
+        staged_arms, res0 = None, None
+        if load_arms:
+            staged_arms = [dict(inflate=i, parse=p, runs=[]) for i, p in load_arms]
+            for r in range(int(runs)):
+                for k, arm in enumerate(load_arms):
+                    res = staged(arm)
+                    res0 = res if k == 0 else res0
+                    staged_arms[k]["runs"].append(dict({"s_" + key: round(v, 3) for key, v in res[0].items()}, s_total=round(res[1], 3), **res[10]))
+                    note("staged run %d, inflate %s, parse %s: %.2f s (merge %.2f s)" % (r, arm[0], arm[1], res[1], res[0]["merge"]))
+            eng.inflate, eng.parse = load_arms[0]
+        t, total, nu, nw, names, start, stop, tl, o1, o2, _ = res0 if res0 is not None else staged(None)
         streamed = None
         note("staged run done: %.2f s" % total)
         if stream:
@@ -190,13 +239,16 @@ def run(pairs, array_path=True, stream=False, check=False, arms=("host",)):
             # (a leg that does not end is reported by every thread's stack after two minutes)
             import faulthandler
             legs = []
-            for arm in arms:
-                faulthandler.dump_traceback_later(120, exit=True)
-                streamed, (s1, s2) = stream_leg(paths, hmm, tmp, arm)
-                faulthandler.cancel_dump_traceback_later()
-                note("streamed run (%s deflate) done: %.2f s" % (arm, streamed["s_total"]))
-                streamed["pairs_per_s_file_to_file"] = round(n / streamed["s_total"])
-                legs.append(streamed)
+            parses = sorted({p for _, p in load_arms}, key=("host", "device").index) if load_arms else ["host"]
+            for r in range(int(runs)):
+                for arm in arms:
+                    for parse in parses:
+                        faulthandler.dump_traceback_later(120, exit=True)
+                        streamed, (s1, s2) = stream_leg(paths, hmm, tmp, arm, parse)
+                        faulthandler.cancel_dump_traceback_later()
+                        note("streamed run %d (%s deflate, %s parse) done: %.2f s" % (r, arm, parse, streamed["s_total"]))
+                        streamed["pairs_per_s_file_to_file"] = round(n / streamed["s_total"])
+                        legs.append(streamed)
             streamed = legs[-1]
             if len(legs) > 1:
                 streamed = dict(streamed, legs=legs)
@@ -209,7 +261,7 @@ def run(pairs, array_path=True, stream=False, check=False, arms=("host",)):
                             if not x:
                                 break
                 streamed["outputs_equal_staged"] = True
-        return ({"streamed": streamed, "pairs": n, "merged": len(names[1]) - 1, "unique": int(nu), "pairs_written": int(nw), "array_path": bool(args.array_path),
+        return ({"streamed": streamed, **({"staged_arms": staged_arms, "in_writer": in_writer} if staged_arms else {}), "pairs": n, "merged": len(names[1]) - 1, "unique": int(nu), "pairs_written": int(nw), "array_path": bool(args.array_path),
                           "input_gz_MB": round(sum(os.path.getsize(p) for p in paths) / 1e6, 1),
                           "output_gz_MB": round((os.path.getsize(o1) + os.path.getsize(o2)) / 1e6, 1),
                           "gzip_level": int(os.environ.get("ITSX_GZIP_LEVEL", 6)),
