@@ -284,6 +284,40 @@ int itsx_load_reads_files(itsx_ctx *ctx, const char *const *paths, int32_t n_pat
 int itsx_set_samples(itsx_ctx *ctx, const int32_t *sample_of_read, int32_t n_samples);
 int itsx_num_samples(const itsx_ctx *ctx);
 int itsx_select_sample(itsx_ctx *ctx, int32_t sample);
+/* ---- sample sharing (opt-in; off by default, and off changes nothing).  The plugin's loop runs one hmmsearch per manifest row
+ * (itsxpress/q2_itsxpress.py:273-333), so a sequence that is a representative in 300 samples of one amplicon is scored 300 times --
+ * and a batch that keeps every sample's own representatives does the same.  hmmsearch scores a target from its residues alone (it
+ * reseeds its generator per target, -T is a score threshold); the sample enters only where a reported target is counted into domZ and
+ * where exp(lnP) * domZ is held against domE.  With the mode on, a search of S > 1 samples groups the uniques of all samples into
+ * SCORE CLASSES -- the uniques whose representatives are the same string in the same orientation (csrc/k_derep.hip: keyed by XXH64 of
+ * the packed forward words, the exception list and the length, verified word by word; a reverse complement is another target and
+ * another class) --, sends one HOLDER per class (its member with the smallest unique index) through the HMM stages, copies the
+ * holder's rows to every other member with `rep` rewritten, and counts each member's reported targets into its own sample's domZ.
+ * itsx_search_finalize and everything behind it (coordinates, domtbl.txt per sample) run unchanged on those rows: every member gets
+ * the rows, dom_reported under its own sample's domZ, coordinates and domtbl.txt lines of a search without the mode, bit for bit
+ * (the row table is served in --domtblout order either way).  uc.txt / rep.fa are untouched.  The pair traces
+ * (itsx_get_pairtraces) are the unshared search's too: every member gets its holder's traces with `rep` rewritten.  itsx_stats
+ * describes the work done: the pairs, cells, rows and times of the holders.
+ * Does not apply (accepted, and itsx_sample_sharing_info reports zero classes): one sample; the compact and lazy rows modes, which keep
+ * their domZ bounds, top-up round and verdicts per (sample, profile); a context whose active uniques the caller chose
+ * (itsx_set_active_uniques, and with it the itsx_unique_keys-driven sharded runs).  ITSX_SHARE_SAMPLES=1 does the same for every
+ * context. */
+int itsx_set_sample_sharing(itsx_ctx *ctx, int on);
+/* What the last itsx_search shared, in place of one hmmsearch per manifest row (itsxpress/q2_itsxpress.py:273-333): the score
+ * classes it built, the uniques that were not scored because their class's holder was (n_unique - n_classes), and the rows copied
+ * to them.  All zero when the mode was off or does not apply (the cases above).  Where it applies and the samples have nothing in
+ * common, the classes are built all the same: n_classes == n_unique, nothing shared, nothing copied, and the search itself runs as
+ * without the mode.  Each pointer may be NULL.  ITSX_E_ARG before a search. */
+int itsx_sample_sharing_info(const itsx_ctx *ctx, int64_t *n_classes, int64_t *n_uniques_shared, int64_t *n_rows_expanded);
+/* the mode's own two steps in that search, milliseconds: building the classes, and copying rows and counting (what the saved
+ * hmmsearch work of q2_itsxpress.py:273-333 is paid with; scripts/batch_bench.py reports both).  Each is the span between two HIP
+ * events on the engine's stream around the whole step, so it holds the step's kernels AND the host synchronisations and small
+ * device-to-host copies between them (the collision count and the number of classes; per row segment the number of copies). */
+int itsx_sample_sharing_times(const itsx_ctx *ctx, float *ms_classes, float *ms_expand);
+/* test hook: class_of[n = n_unique] as the last sharing search left it on the device.  Classes are numbered by their holders in
+ * rising unique index; uniques of different manifest rows (q2_itsxpress.py:273-333) share a number exactly when their
+ * representatives are one string in one orientation.  ITSX_E_ARG when that search built no classes. */
+int itsx_debug_sample_classes(itsx_ctx *ctx, int32_t *class_of, int64_t n);
 
 /* ---- f4: SeqSample.orient_reads (itsxpress/SeqSample.py:48-91) = vsearch --orient IN --db REF --fastqout OUT
  * (12-mer presence counts on both strands, 4x rule; restated in oracle/orc_cluster.c, parity unpinned).

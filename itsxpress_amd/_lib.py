@@ -103,7 +103,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_parse_device", "itsx_parse_fetch", "itsx_debug_parse_host", "itsx_set_device_parse",
            "itsx_parse_pairs_device", "itsx_parse_pairs_fetch", "itsx_debug_parse_pairs_host", "itsx_debug_pair_pass_host",
            "itsx_debug_set_domains", "itsx_debug_get_rows",
-           "itsx_debug_scan", "itsx_debug_select", "itsx_debug_region_keys", "itsx_debug_lazy_pairs"]
+           "itsx_debug_scan", "itsx_debug_select", "itsx_debug_region_keys", "itsx_debug_lazy_pairs",
+           "itsx_set_sample_sharing", "itsx_sample_sharing_info", "itsx_sample_sharing_times", "itsx_debug_sample_classes"]
 
 
 def lib():
@@ -265,6 +266,10 @@ def lib():
         "itsx_set_samples": (i32, [vp, vp, i32]),
         "itsx_num_samples": (i32, [vp]),
         "itsx_select_sample": (i32, [vp, i32]),
+        "itsx_set_sample_sharing": (i32, [vp, i32]),
+        "itsx_sample_sharing_info": (i32, [vp, vp, vp, vp]),
+        "itsx_sample_sharing_times": (i32, [vp, vp, vp]),
+        "itsx_debug_sample_classes": (i32, [vp, vp, i64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -313,6 +313,17 @@ class SampleBatch:
     def deflate(self, where: str):
         self.engine.deflate = where
 
+    # Whether _search scores each distinct representative once for all the samples it occurs in (score classes): the engine's own
+    # setting (Engine.share_samples, off by default), under the batch's name.  Every sample's domtbl.txt and coordinates are those of a
+    # batch without it.  A setting like deflate / inflate / parse, not a constructor keyword: the constructor's signature stays
+    @property
+    def share_samples(self) -> bool:
+        return self.engine.share_samples
+
+    @share_samples.setter
+    def share_samples(self, on: bool):
+        self.engine.share_samples = on
+
     # Where the engine's whole-file loaders inflate gzip input: the engine's own setting (Engine.inflate), under the batch's name
     @property
     def inflate(self) -> str:

@@ -369,6 +369,18 @@ struct itsx_ctx {
   const int32_t *dev_sample() const { return S > 1 ? d_sample.p : nullptr; }
   const int32_t *dev_usample() const { return S > 1 ? d_usample.p : nullptr; }
   int32_t usample(int64_t u) const { return S > 1 ? h_usample[(size_t)u] : 0; }
+  // sample sharing (itsx_set_sample_sharing; k_derep.hip: k_class_*, k_expand_*): a full-rows search of S > 1 samples scores one holder
+  // per score class (the uniques of all samples whose representatives are one string in one orientation) and copies its rows to the
+  // other members.  sc: the last search's figures (all zero when the mode did not apply); sc_*: the classes on the device, rebuilt
+  // by every search that shares (class_of [U], holder [C], the members as a CSR list: off [C + 1], members [U] in rising index)
+  bool share_samples = false;
+  bool active_narrowed = false;          // the CALLER chose the active uniques (itsx_set_active_uniques): the mode leaves them alone
+  struct SampleSharing { int64_t n_classes = 0, n_shared = 0, n_expanded = 0; float ms_classes = 0, ms_expand = 0; } sc;
+  // the list the last search walked when it was the holders' (PairRec::useq indexes it: append_traces), and whether the members'
+  // pair traces have been made from their holders' yet (fetch_traces)
+  bool searched_holders = false, trace_members_done = false; std::vector<int32_t> h_sorted_searched;
+  DBuf<int32_t> sc_class_of, sc_holder, sc_off, sc_members, sc_members_in, sc_holder_of, sc_is_holder, sc_rank, sc_scan, sc_cnt, sc_pos;
+  DBuf<unsigned long long> sc_keys, sc_keys_in; DBuf<uint8_t> sc_sort;
   double slab_gb = 0.0;                  // HBM budget for per-batch DP slabs
 
   // ---- derep
@@ -1429,7 +1441,7 @@ static int build_unique_lists(itsx_ctx *ctx)
     HIPCHK(hipMemcpyAsync(&U, seed_rank.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
   }
-  ctx->U = U; ctx->U_active = U;
+  ctx->U = U; ctx->U_active = U; ctx->active_narrowed = false;
   HIPCHK(ctx->d_seed_read.alloc((size_t)U + 1)); HIPCHK(ctx->d_abund.alloc((size_t)U + 1)); HIPCHK(ctx->d_sorted_uniq.alloc((size_t)U + 1));
   HIPCHK(ctx->d_ulen.alloc((size_t)U + 1));
   HIPCHK(hipMemsetAsync(ctx->d_abund.p, 0, ((size_t)U + 1) * sizeof(int32_t), ctx->st));
@@ -1912,19 +1924,28 @@ int itsx_unique_keys(itsx_ctx *ctx, uint64_t seed, uint64_t *fwd, uint64_t *rc)
   return ITSX_OK;
 }
 
+// the length-ordered list the HMM stages walk: `keep` (length-ordered already), or every unique again (keep == nullptr)
+static int set_walked_uniques(itsx_ctx *ctx, const std::vector<int32_t> *keep)
+{
+  const std::vector<int32_t> &lst = keep ? *keep : ctx->h_sorted_uniq;
+  ctx->U_active = (int32_t)lst.size();
+  ctx->h_sorted_active = lst;
+  if (!lst.empty()) {
+    HIPCHK(hipMemcpyAsync(ctx->d_sorted_uniq.p, lst.data(), lst.size() * 4, hipMemcpyHostToDevice, ctx->st));
+    launch_fill_ulen(ctx->U_active, ctx->d_sorted_uniq.p, ctx->d_seed_read.p, ctx->rd.len, ctx->d_ulen.p, ctx->st);
+    HIPCHK(hipStreamSynchronize(ctx->st));
+  }
+  return ITSX_OK;
+}
+
 int itsx_set_active_uniques(itsx_ctx *ctx, const uint8_t *active)
 {
   CTXCHK(ctx && ctx->have_derep && (active || ctx->U == 0));
   HIPCHK(hipSetDevice(ctx->device));
   std::vector<int32_t> keep; keep.reserve((size_t)ctx->U);
   for (int32_t s = 0; s < ctx->U; s++) { const int32_t u = ctx->h_sorted_uniq[(size_t)s]; if (active[u]) keep.push_back(u); }   // stays length-sorted
-  ctx->U_active = (int32_t)keep.size();
-  ctx->h_sorted_active = keep;           // the traces and the searched-target count follow the active list
-  if (!keep.empty()) {
-    HIPCHK(hipMemcpyAsync(ctx->d_sorted_uniq.p, keep.data(), keep.size() * 4, hipMemcpyHostToDevice, ctx->st));
-    launch_fill_ulen(ctx->U_active, ctx->d_sorted_uniq.p, ctx->d_seed_read.p, ctx->rd.len, ctx->d_ulen.p, ctx->st);
-    HIPCHK(hipStreamSynchronize(ctx->st));
-  }
+  { const int rc = set_walked_uniques(ctx, &keep); if (rc != ITSX_OK) return rc; }      // the traces and the searched-target count follow the active list
+  ctx->active_narrowed = true;           // (sample sharing leaves a caller's choice alone)
   ctx->have_search = ctx->have_final = false;
   return ITSX_OK;
 }
@@ -2227,7 +2248,22 @@ static int compact_segment(itsx_ctx *ctx, const itsx_domain *d_rows, int64_t NR,
   return ITSX_OK;
 }
 
-int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
+// rows mode of the search that is about to run: what the caller selected (itsx_set_rows_mode), else the environment
+// (ITSX_ROWS=full|compact|lazy; ITSX_COMPACT_ROWS=1)
+static int search_rows_mode(const itsx_ctx *ctx)
+{
+  int mode = ctx->rows_mode;
+  if (mode < 0) {
+    mode = ITSX_ROWS_FULL;
+    if (sw_get("ITSX_COMPACT_ROWS") && atoi(sw_get("ITSX_COMPACT_ROWS")) != 0) mode = ITSX_ROWS_COMPACT;
+    if (const char *e = sw_get("ITSX_ROWS")) mode = !strcmp(e, "lazy") ? ITSX_ROWS_LAZY : !strcmp(e, "compact") ? ITSX_ROWS_COMPACT : ITSX_ROWS_FULL;
+  }
+  if (mode == ITSX_ROWS_LAZY && sw_get("ITSX_KEEP_TRACE")) mode = ITSX_ROWS_COMPACT;      // pair traces describe the full pipeline
+  return mode;
+}
+
+// the search over the context's active uniques (itsx_search below: all of them, the caller's choice, or the holders of the score classes)
+static int search_active(itsx_ctx *ctx, double T, double F1, double F2, double F3)
 {
   CTXCHK(ctx);
   if (!ctx->have_derep) SET_ERR(ctx, ITSX_E_ARG, "itsx_search called before itsx_derep / itsx_cluster");
@@ -2245,14 +2281,7 @@ int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
   S.ms_msv = S.ms_filters = S.ms_domains = S.ms_msv_kernel = S.ms_fwd_kernel = S.ms_bwd_kernel = S.ms_env_kernel = S.ms_bias_kernel = S.ms_decode_kernel = 0; S.n_batches = 0; S.ms_ensemble = 0; S.n_mr_clustered = S.n_mr_distinct = S.n_mr_failed = S.n_mr_envelopes = 0; S.n_slab_shrinks = 0; S.n_mr_overflow = 0; S.ms_vit_kernel = 0; for (int k = 0; k < 8; k++) S.n_mr_fail_kind[k] = 0; S.n_rows_resident = 0; S.msv_cells = 0; S.msv_launches = 0; S.fwd_rows = 0; S.env_rows = 0; S.n_env_unique = 0;
   ctx->npairs_padded = 0; ctx->dom_n.clear(); ctx->trace_u0 = 0; ctx->n_chunks = 0;
   ctx->have_search = true; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->topup.list_live = false; ctx->injected = false;
-  // rows mode: what the caller selected (itsx_set_rows_mode), else the environment (ITSX_ROWS=full|compact|lazy; ITSX_COMPACT_ROWS=1)
-  int mode = ctx->rows_mode;
-  if (mode < 0) {
-    mode = ITSX_ROWS_FULL;
-    if (sw_get("ITSX_COMPACT_ROWS") && atoi(sw_get("ITSX_COMPACT_ROWS")) != 0) mode = ITSX_ROWS_COMPACT;
-    if (const char *e = sw_get("ITSX_ROWS")) mode = !strcmp(e, "lazy") ? ITSX_ROWS_LAZY : !strcmp(e, "compact") ? ITSX_ROWS_COMPACT : ITSX_ROWS_FULL;
-  }
-  if (mode == ITSX_ROWS_LAZY && sw_get("ITSX_KEEP_TRACE")) mode = ITSX_ROWS_COMPACT;      // pair traces describe the full pipeline
+  const int mode = search_rows_mode(ctx);
   ctx->compact_rows = mode != ITSX_ROWS_FULL;
   ctx->lazy = mode == ITSX_ROWS_LAZY;
   ctx->lazy_pending = 0; ctx->domz_exchanged = false; ctx->sF1 = F1; ctx->sF3 = F3;
@@ -2279,11 +2308,12 @@ int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
       for (int64_t u = (int64_t)Ua * t / Th, hi = (int64_t)Ua * (t + 1) / Th; u < hi; u++) {
         const int32_t L = ctx->h_len[ctx->h_seed_read[(size_t)u]];
         pr[(size_t)L] = 1;
-        if (u < Uact) c += L;
+        if (Uact == Ua) c += L;
       }
       csum[(size_t)t] = c;
     });
     for (int t = 0; t < Th; t++) { cells_active += csum[(size_t)t]; for (int L = 0; L < Lcap; L++) present[(size_t)L] |= pres[(size_t)t][(size_t)L]; }
+    if (Uact != Ua) for (int32_t u : ctx->h_sorted_active) cells_active += ctx->h_len[ctx->h_seed_read[(size_t)u]];      // a narrowed list: its own residues
   }
   for (int L = 0; L < Lcap; L++) {
     LenTables &t = lt[L]; memset(&t, 0, sizeof(t));
@@ -2392,6 +2422,165 @@ int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
     ctx->have_search = false;
     SET_ERR(ctx, ITSX_E_UNSUPPORTED, std::to_string(S.n_mr_failed) + " multidomain region(s) with a Forward matrix that cannot be sampled (hmmsearch's stochastic traceback throws on them)");
   }
+  return ITSX_OK;
+}
+
+// ---- sample sharing (itsx_set_sample_sharing): one holder per score class goes through the HMM stages
+static bool sample_sharing_wanted(const itsx_ctx *ctx)
+{
+  if (ctx->share_samples) return true;
+  const char *e = sw_get("ITSX_SHARE_SAMPLES");
+  return e && atoi(e) == 1;
+}
+// the score classes of the current dereplication (k_derep.hip: k_class_*), on the device; holders [C] on the host
+static int build_sample_classes(itsx_ctx *ctx, std::vector<int32_t> &holders)
+{
+  hipStream_t st = ctx->st;
+  const int32_t U = ctx->U;
+  StageTimer tm(st);
+  uint64_t tsize = 1024; while (tsize < (uint64_t)U * 2 + 16) tsize <<= 1;
+  DBuf<unsigned long long> &keys = ctx->w_keys; DBuf<int32_t> &vals = ctx->w_vals; DBuf<uint32_t> &slot_of = ctx->w_slot_of; DBuf<unsigned int> &ncoll = ctx->w_ncoll;
+  HIPCHK(keys.alloc(tsize)); HIPCHK(vals.alloc(tsize)); HIPCHK(slot_of.alloc((size_t)U + 1)); HIPCHK(ncoll.alloc(1));
+  HIPCHK(ctx->sc_holder_of.alloc((size_t)U + 1)); HIPCHK(ctx->sc_is_holder.alloc((size_t)U + 2)); HIPCHK(ctx->sc_rank.alloc((size_t)U + 2));
+  HIPCHK(ctx->sc_scan.alloc((size_t)scan_tmp_elems((int64_t)U + 1)));
+  HIPCHK(ctx->sc_class_of.alloc((size_t)U + 1)); HIPCHK(ctx->sc_members.alloc((size_t)U + 1)); HIPCHK(ctx->sc_members_in.alloc((size_t)U + 1));
+  HIPCHK(ctx->sc_keys.alloc((size_t)U + 1)); HIPCHK(ctx->sc_keys_in.alloc((size_t)U + 1));
+  unsigned int hcoll = 0;
+  uint64_t seed = 0x5343ull;
+  for (int attempt = 0; attempt < 4; attempt++) {
+    HIPCHK(hipMemsetAsync(keys.p, 0, tsize * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(vals.p, 0x7f, tsize * sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(ncoll.p, 0, sizeof(unsigned int), st));
+    launch_class_insert(ctx->rd, ctx->d_seed_read.p, U, seed, keys.p, vals.p, tsize - 1, slot_of.p, st);
+    launch_class_resolve(ctx->rd, ctx->d_seed_read.p, U, vals.p, slot_of.p, ctx->sc_holder_of.p, ctx->sc_is_holder.p, ncoll.p, st);
+    HIPCHK(hipMemcpyAsync(&hcoll, ncoll.p, sizeof(hcoll), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (hcoll == 0) break;
+    seed = seed * 6364136223846793005ULL + 1442695040888963407ULL;
+  }
+  if (hcoll != 0) SET_ERR(ctx, ITSX_E_COLLISION, "score classes: 64-bit key collisions survived 4 reseeds");
+  int32_t C = 0;
+  launch_exclusive_scan(ctx->sc_is_holder.p, ctx->sc_rank.p, (int64_t)U + 1, ctx->sc_scan.p, st);      // element U = the number of classes
+  HIPCHK(hipMemcpyAsync(&C, ctx->sc_rank.p + U, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (C <= 0 || C > U) SET_ERR(ctx, ITSX_E_DEVICE, "score classes: bookkeeping mismatch (" + std::to_string(C) + " classes of " + std::to_string(U) + " uniques)");
+  HIPCHK(ctx->sc_holder.alloc((size_t)C + 1)); HIPCHK(ctx->sc_off.alloc((size_t)C + 2));
+  launch_class_number(U, ctx->sc_holder_of.p, ctx->sc_rank.p, ctx->sc_class_of.p, ctx->sc_holder.p, ctx->sc_keys_in.p, ctx->sc_members_in.p, st);
+  const size_t sort_bytes = order_sort_bytes(U);
+  HIPCHK(ctx->sc_sort.alloc(sort_bytes));
+  if (order_sort(ctx->sc_sort.p, sort_bytes, ctx->sc_keys_in.p, ctx->sc_keys.p, ctx->sc_members_in.p, ctx->sc_members.p, U, st) != 0)
+    SET_ERR(ctx, ITSX_E_DEVICE, "score classes: the member sort failed");
+  launch_class_offsets(ctx->sc_keys.p, U, C, ctx->sc_off.p, st);
+  holders.resize((size_t)C);
+  HIPCHK(hipMemcpyAsync(holders.data(), ctx->sc_holder.p, (size_t)C * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  ctx->sc.n_classes = C; ctx->sc.n_shared = (int64_t)U - C;
+  ctx->sc.ms_classes = tm.stop();
+  return ITSX_OK;
+}
+// every non-holder member gets its holder's rows (k_expand_*), one more segment per segment of the search, and its reported targets
+// are counted into its own sample's domZ; then the host's counters follow the device's
+static int expand_shared_rows(itsx_ctx *ctx)
+{
+  hipStream_t st = ctx->st;
+  StageTimer tm(st);
+  const size_t nseg = ctx->dom_n.size();
+  int64_t expanded = 0;
+  for (size_t c = 0; c < nseg; c++) {
+    const int64_t NR = ctx->dom_n[c];
+    if (NR <= 0) continue;
+    HIPCHK(ctx->sc_cnt.alloc((size_t)NR + 1)); HIPCHK(ctx->sc_pos.alloc((size_t)NR + 1)); HIPCHK(ctx->sc_scan.alloc((size_t)scan_tmp_elems(NR + 1)));
+    DBuf<int64_t> &d_c = ctx->w_counters;
+    HIPCHK(d_c.alloc(8));
+    HIPCHK(hipMemsetAsync(d_c.p, 0, sizeof(int64_t), st));
+    launch_expand_count(ctx->dom_bufs[c]->p, NR, ctx->sc_class_of.p, ctx->sc_off.p, ctx->sc_cnt.p, (unsigned long long *)d_c.p, st);
+    int64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_c.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (total <= 0) continue;
+    if (total >= 2147483000ll)                // (the 32-bit scan below; rows of 80 bytes: such a table would not be resident either)
+      SET_ERR(ctx, ITSX_E_UNSUPPORTED, "sample sharing: " + std::to_string(total) + " rows to copy from one chunk of the search, more than 2^31 (lower ITSX_CHUNK_UNIQUES or search without sharing)");
+    launch_exclusive_scan(ctx->sc_cnt.p, ctx->sc_pos.p, NR + 1, ctx->sc_scan.p, st);
+    const size_t di = ctx->dom_n.size();
+    ctx->dom_n.push_back(0);
+    while (ctx->dom_bufs.size() <= di) ctx->dom_bufs.emplace_back(new DBuf<itsx_domain>());
+    HIPCHK(ctx->dom_bufs[di]->alloc((size_t)total));
+    launch_expand_rows(ctx->dom_bufs[c]->p, NR, ctx->sc_pos.p, total, ctx->sc_class_of.p, ctx->sc_off.p, ctx->sc_members.p, ctx->dev_usample(), ctx->P,
+                       ctx->dom_bufs[di]->p, ctx->d_domz32.p, st);
+    ctx->dom_n[di] = total;
+    expanded += total;
+  }
+  std::vector<int32_t> dz32((size_t)ctx->P * ctx->S, 0);
+  HIPCHK(hipMemcpyAsync(dz32.data(), ctx->d_domz32.p, dz32.size() * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  ctx->domz_loc.assign(dz32.begin(), dz32.end());
+  ctx->domz = ctx->domz_loc;
+  ctx->stats.n_rows_resident += expanded;
+  ctx->sc.n_expanded = expanded;
+  ctx->sc.ms_expand = tm.stop();
+  return ITSX_OK;
+}
+
+int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
+{
+  CTXCHK(ctx);
+  ctx->sc = itsx_ctx::SampleSharing{};
+  ctx->searched_holders = false; ctx->trace_members_done = false;
+  // The mode applies to a full-rows search of S > 1 samples whose active set is the engine's own (the lazy and compact stages keep
+  // their domZ bounds, their top-up round and their verdicts per (sample, profile): there the setting has no effect)
+  if (!sample_sharing_wanted(ctx) || !ctx->have_derep || ctx->P <= 0 || ctx->S <= 1 || ctx->U <= 0 || ctx->active_narrowed ||
+      search_rows_mode(ctx) != ITSX_ROWS_FULL)
+    return search_active(ctx, T, F1, F2, F3);
+  HIPCHK(hipSetDevice(ctx->device));
+  std::vector<int32_t> holders, keep;
+  { const int rc = build_sample_classes(ctx, holders); if (rc != ITSX_OK) { ctx->sc = itsx_ctx::SampleSharing{}; return rc; } }
+  const int32_t U = ctx->U, C = (int32_t)holders.size();
+  if (C == U) return search_active(ctx, T, F1, F2, F3);              // nothing in common: every unique is its own holder
+  {
+    std::vector<char> is_holder((size_t)U, 0);
+    for (int32_t h : holders) is_holder[(size_t)h] = 1;
+    keep.reserve((size_t)C);
+    for (int32_t s = 0; s < U; s++) { const int32_t u = ctx->h_sorted_uniq[(size_t)s]; if (is_holder[(size_t)u]) keep.push_back(u); }      // stays length-sorted
+  }
+  { const int rc = set_walked_uniques(ctx, &keep); if (rc != ITSX_OK) return rc; }
+  ctx->h_sorted_searched.swap(keep); ctx->searched_holders = true;      // (kept past the restore below: the pair traces are fetched later)
+  int rc = search_active(ctx, T, F1, F2, F3);
+  { const int rc2 = set_walked_uniques(ctx, nullptr); if (rc == ITSX_OK) rc = rc2; }      // (every exit leaves the context walking all its uniques again)
+  if (rc == ITSX_OK) rc = expand_shared_rows(ctx);
+  if (rc != ITSX_OK) { ctx->have_search = false; ctx->sc = itsx_ctx::SampleSharing{}; }
+  return rc;
+}
+
+int itsx_set_sample_sharing(itsx_ctx *ctx, int on)
+{
+  CTXCHK(ctx);
+  ctx->share_samples = on != 0;
+  return ITSX_OK;
+}
+int itsx_sample_sharing_info(const itsx_ctx *ctx, int64_t *n_classes, int64_t *n_uniques_shared, int64_t *n_rows_expanded)
+{
+  CTXCHK(ctx && ctx->have_search);
+  if (n_classes) *n_classes = ctx->sc.n_classes;
+  if (n_uniques_shared) *n_uniques_shared = ctx->sc.n_shared;
+  if (n_rows_expanded) *n_rows_expanded = ctx->sc.n_expanded;
+  return ITSX_OK;
+}
+int itsx_sample_sharing_times(const itsx_ctx *ctx, float *ms_classes, float *ms_expand)
+{
+  CTXCHK(ctx && ctx->have_search);
+  if (ms_classes) *ms_classes = ctx->sc.ms_classes;
+  if (ms_expand) *ms_expand = ctx->sc.ms_expand;
+  return ITSX_OK;
+}
+int itsx_debug_sample_classes(itsx_ctx *ctx, int32_t *class_of, int64_t n)
+{
+  CTXCHK(ctx && ctx->have_search && (class_of || n == 0));
+  if (ctx->sc.n_classes <= 0) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_sample_classes: the last search built no score classes (itsx_sample_sharing_info reports 0)");
+  if (n != (int64_t)ctx->U) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_sample_classes: n is not the number of uniques");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (n) { HIPCHK(hipMemcpyAsync(class_of, ctx->sc_class_of.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st)); HIPCHK(hipStreamSynchronize(ctx->st)); }
   return ITSX_OK;
 }
 
@@ -3659,7 +3848,7 @@ int itsx_debug_set_domains(itsx_ctx *ctx, const itsx_domain *rows, int64_t n_row
   hipStream_t st = ctx->st;
   const size_t m = (size_t)ctx->P * ctx->S;
   ctx->switches_at_search = sw_report();
-  ctx->h_dom.clear(); ctx->h_trace.clear(); ctx->trace_sorted = false;
+  ctx->searched_holders = false; ctx->h_dom.clear(); ctx->h_trace.clear(); ctx->trace_sorted = false;
   ctx->domz.assign(m, 0); ctx->domz_ub.assign(m, 0); ctx->domz_loc.assign(m, 0); ctx->domz_ub_loc.assign(m, 0);
   ctx->npairs_padded = 0; ctx->dom_n.clear(); ctx->n_chunks = n_segs;
   ctx->have_search = false; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->topup.list_live = false; ctx->injected = true;
@@ -4081,12 +4270,15 @@ static int append_traces(itsx_ctx *ctx)
   HIPCHK(hipMemcpy(po.data(), ctx->d_pout.p, (size_t)NP * sizeof(PairOut), hipMemcpyDeviceToHost));
   if (ctx->have_vit) { vo.resize((size_t)NP); HIPCHK(hipMemcpy(vo.data(), ctx->d_vit.p, (size_t)NP * sizeof(VitOut), hipMemcpyDeviceToHost)); }
   // PairRec::useq is a position in the list the search walked: with prefix sharing the processing order (k_share.hip), else by length
+  // (a sample-sharing search walked the holders only, and the context walks all its uniques again by the time a one-chunk search's
+  // traces are fetched: the list and the length are the SEARCHED ones)
+  const std::vector<int32_t> &searched = ctx->searched_holders ? ctx->h_sorted_searched : ctx->h_sorted_active;
   std::vector<int32_t> order;
   if (ctx->share_on) {
-    order.resize((size_t)ctx->U_active);
-    HIPCHK(hipMemcpy(order.data(), ctx->sh_order.p, order.size() * 4, hipMemcpyDeviceToHost));
+    order.resize(searched.size());
+    if (!order.empty()) HIPCHK(hipMemcpy(order.data(), ctx->sh_order.p, order.size() * 4, hipMemcpyDeviceToHost));
   }
-  const int32_t *walked = ctx->share_on ? order.data() : ctx->h_sorted_active.data();
+  const int32_t *walked = ctx->share_on ? order.data() : searched.data();
   for (int64_t i = 0; i < NP; i++) {
     if (pr[i].prof < 0 || pr[i].xj < 0) continue;          // (padding; a pair that ran only for a chain below it)
     itsx_pairtrace t{};
@@ -4107,6 +4299,22 @@ static int fetch_traces(const itsx_ctx *cctx)
     if (ctx->n_chunks > 1) SET_ERR(ctx, ITSX_E_ARG, "pair traces of a multi-chunk search are kept only when ITSX_KEEP_TRACE=1");
     const int rc = append_traces(ctx);
     if (rc != ITSX_OK) return rc;
+  }
+  if (ctx->searched_holders && !ctx->trace_members_done) {
+    // sample sharing: the pairs of a holder are the pairs of every member of its class (same residues, same filters, same scores):
+    // each member gets its holder's traces with `rep` rewritten, so the table is the one a search without the mode leaves
+    const size_t C = (size_t)ctx->sc.n_classes, U = (size_t)ctx->U;
+    std::vector<int32_t> cls(U), off(C + 1), mem(U);
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpy(cls.data(), ctx->sc_class_of.p, U * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(off.data(), ctx->sc_off.p, (C + 1) * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(mem.data(), ctx->sc_members.p, U * 4, hipMemcpyDeviceToHost));
+    const size_t n0 = ctx->h_trace.size();
+    for (size_t i = 0; i < n0; i++) {
+      const size_t c = (size_t)cls[(size_t)ctx->h_trace[i].rep];
+      for (int32_t k = off[c] + 1; k < off[c + 1]; k++) { itsx_pairtrace t = ctx->h_trace[i]; t.rep = mem[(size_t)k]; ctx->h_trace.push_back(t); }
+    }
+    ctx->trace_members_done = true; ctx->trace_sorted = false;
   }
   if (!ctx->trace_sorted) {
     std::sort(ctx->h_trace.begin(), ctx->h_trace.end(), [](const itsx_pairtrace &a, const itsx_pairtrace &b) {

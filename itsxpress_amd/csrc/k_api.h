@@ -35,6 +35,21 @@ void launch_region_resolve(const ReadsDev &rd, const RegionRec *regions, int64_t
 void launch_region_upos(int64_t nr, const RegionRec *regions, const PairRec *pairs, const int32_t *is_uniq, const int32_t *urank,
                         const int64_t *rseg, const int64_t *useg, int32_t *upos, RegionRec *ulist, hipStream_t st);
 void launch_region_upos_follow(int64_t nr, const int32_t *rep_region, const int32_t *is_uniq, int32_t *upos, hipStream_t st);
+// score classes of a sample batch (itsx_set_sample_sharing): the uniques whose representatives are one string in one orientation.
+// keys / vals: an open-addressing table of mask + 1 >= 2 U slots (keys 0, vals 0x7f7f7f7f); holder_of, slot_of: [U]; is_holder: [U + 1]
+// (its exclusive scan is `rank`); class_of, members, keys: [U]; holder: [C]; off: [C + 1] over the (class, unique) keys once sorted
+void launch_class_insert(const ReadsDev &rd, const int32_t *seed_read, int32_t U, uint64_t seed, unsigned long long *keys, int32_t *vals, uint64_t mask,
+                         uint32_t *slot_of, hipStream_t st);
+void launch_class_resolve(const ReadsDev &rd, const int32_t *seed_read, int32_t U, const int32_t *vals, const uint32_t *slot_of, int32_t *holder_of,
+                          int32_t *is_holder, unsigned int *n_collisions, hipStream_t st);
+void launch_class_number(int32_t U, const int32_t *holder_of, const int32_t *rank, int32_t *class_of, int32_t *holder, unsigned long long *keys,
+                         int32_t *members, hipStream_t st);
+void launch_class_offsets(const unsigned long long *sorted_keys, int32_t U, int32_t C, int32_t *off, hipStream_t st);
+// the holders' rows copied to the other members of their classes: cnt / pos: [n + 1] (pos = exclusive scan of cnt, pos[n] = total);
+// *total (zeroed by the caller) += the same sum in 64 bits
+void launch_expand_count(const itsx_domain *dom, int64_t n, const int32_t *class_of, const int32_t *off, int32_t *cnt, unsigned long long *total, hipStream_t st);
+void launch_expand_rows(const itsx_domain *dom, int64_t n, const int32_t *pos, int64_t total, const int32_t *class_of, const int32_t *off,
+                        const int32_t *members, const int32_t *usample, int P, itsx_domain *out, int32_t *domz, hipStream_t st);
 
 // ---- k_cluster.hip (row a2: greedy centroid clustering, speculative windows)
 struct ClusterArgs {

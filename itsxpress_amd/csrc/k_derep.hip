@@ -512,4 +512,155 @@ void launch_len_scatter(int32_t U, const int32_t *seed_read, const int32_t *len,
     hipLaunchKernelGGL(k_len_scatter, dim3(grid_for(U)), dim3(256), 0, st, U, seed_read, len, cursor, lcap, sorted_uniq);
 }
 
+// ---- score classes of a sample batch (itsx_set_sample_sharing) ------------------------------------------
+// The QIIME 2 plugin runs one hmmsearch per manifest row (itsxpress/q2_itsxpress.py:273-333); hmmsearch scores a target from its
+// residues alone, so the representatives of a batch that are the SAME STRING IN THE SAME ORIENTATION -- one per sample at most, since
+// a sample's own dereplication has merged its copies -- get the same rows.  A class = those uniques; its holder = the member with the
+// smallest unique index, the one the HMM stages score.  Key: XXH64 of the representative's forward key words (packed words, exception
+// list, length -- FwdKey, as the dereplication hashes them; never the orientation-free minimum, a reverse complement is another
+// target).  Grouping: the open-addressing table of the dereplication with k_region_keys' economy -- the lanes of a wave that hold
+// one key send their lowest lane (the smallest unique), and that lane reads the slot before it issues an atomic -- and a word-by-word
+// verification (same_forward: words, exceptions and length), so that neither a 64-bit collision nor an N packed as A merges targets.
+__global__ void __launch_bounds__(256) k_class_insert(ReadsDev rd, const int32_t *__restrict__ seed_read, int32_t U, uint64_t seed,
+                                                      unsigned long long *__restrict__ keys, int32_t *__restrict__ vals, uint64_t mask,
+                                                      uint32_t *__restrict__ slot_of)
+{
+  const int lane = threadIdx.x & 63;
+  // (whole waves walk the loop together: the block and the stride are multiples of 64)
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u - lane < U; u += (int64_t)gridDim.x * blockDim.x) {
+    uint64_t key = 0;                                           // 0: no unique here
+    if (u < U) {
+      const int64_t r = seed_read[u];
+      const int64_t wo = rd.woff[r], eo = rd.excoff[r];
+      const int nw = (int)(rd.woff[r + 1] - wo), nexc = (int)(rd.excoff[r + 1] - eo);
+      FwdKey fk{rd.words + wo, rd.exc + eo, nw, nexc, rd.len[r]};
+      key = xxh64_words(fk, nw + nexc + 1, seed);
+      if (key == 0) key = 1;
+    }
+    unsigned long long todo = __ballot(key != 0);
+    int leader = lane;
+    while (todo) {
+      const int l0 = __builtin_ctzll(todo);
+      const uint64_t k0 = ((uint64_t)(uint32_t)__shfl((int)(key >> 32), l0, 64) << 32) | (uint64_t)(uint32_t)__shfl((int)key, l0, 64);
+      const unsigned long long same = __ballot(key == k0) & todo;
+      if (key == k0) leader = l0;
+      todo &= ~same;
+    }
+    uint32_t myslot = 0;
+    if (key != 0 && leader == lane) {
+      uint64_t slot = (key * 0x9E3779B97F4A7C15ULL >> 20) & mask;
+      for (;;) {
+        unsigned long long cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == 0ull) { cur = atomicCAS(&keys[slot], 0ull, (unsigned long long)key); if (cur == 0ull) cur = key; }
+        if (cur == key) break;
+        slot = (slot + 1) & mask;
+      }
+      if (__hip_atomic_load(&vals[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (int32_t)u) atomicMin(&vals[slot], (int32_t)u);
+      myslot = (uint32_t)slot;
+    }
+    myslot = (uint32_t)__shfl((int)myslot, leader, 64);
+    if (key != 0) slot_of[u] = myslot;
+  }
+}
+// holder_of[u] = the smallest unique with u's key, once its representative is verified to be u's; is_holder[u] = (holder_of[u] == u).
+// Two different strings under one key: counted, and the host hashes again with another seed (a class is never merged on a hash alone
+// and never split by one either).
+__global__ void __launch_bounds__(256) k_class_resolve(ReadsDev rd, const int32_t *__restrict__ seed_read, int32_t U, const int32_t *__restrict__ vals,
+                                                       const uint32_t *__restrict__ slot_of, int32_t *__restrict__ holder_of, int32_t *__restrict__ is_holder,
+                                                       unsigned int *__restrict__ n_collisions)
+{
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u <= U; u += (int64_t)gridDim.x * blockDim.x) {
+    if (u == U) { is_holder[u] = 0; continue; }                 // (the scan's last element: its sum = the number of classes)
+    int32_t s = vals[slot_of[u]];
+    if (s != (int32_t)u && !same_forward(rd, seed_read[u], seed_read[s])) { atomicAdd(n_collisions, 1u); s = (int32_t)u; }
+    holder_of[u] = s; is_holder[u] = (s == (int32_t)u);
+  }
+}
+// classes numbered by their holders in rising unique index; the sort key of the member list: (class, unique)
+__global__ void __launch_bounds__(256) k_class_number(int32_t U, const int32_t *__restrict__ holder_of, const int32_t *__restrict__ rank,
+                                                      int32_t *__restrict__ class_of, int32_t *__restrict__ holder, unsigned long long *__restrict__ keys,
+                                                      int32_t *__restrict__ members)
+{
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < U; u += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t h = holder_of[u], c = rank[h];
+    class_of[u] = c;
+    if (h == (int32_t)u) holder[c] = (int32_t)u;
+    keys[u] = ((unsigned long long)(uint32_t)c << 32) | (unsigned long long)(uint32_t)u;
+    members[u] = (int32_t)u;
+  }
+}
+// off[c] = first position of the sorted (class, unique) keys that belongs to class c; off[C] = U
+__global__ void __launch_bounds__(256) k_class_offsets(const unsigned long long *__restrict__ sorted_keys, int32_t U, int32_t C, int32_t *__restrict__ off)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c > C) return;
+  const unsigned long long want = (unsigned long long)c << 32;
+  int32_t lo = 0, hi = U;
+  while (lo < hi) { const int32_t mid = lo + ((hi - lo) >> 1); if (sorted_keys[mid] < want) lo = mid + 1; else hi = mid; }
+  off[c] = lo;
+}
+// Row expansion.  The domain stage has left the holders' rows; every other member of a holder's class gets a copy with `rep` rewritten
+// to the member -- bit for bit the rows its own search would have left, since none of a row's other fields depends on the sample before
+// k_finalize.  cnt[i] = copies row i asks for (padding rows: none); after the scan, output row o finds its source row by bisection of
+// pos (one thread per output row, so a class of 384 members costs its rows no more than a class of two), and its member is the
+// (o - pos[i] + 1)-th of the class (the holder is the first: the smallest index).  hmmsearch's domZ counts a reported target once per
+// profile, and k_score counts exactly the pairs that leave a row with dom_idx == 0 and seq_reported set: the copy of that row adds the
+// member's own count to its own sample's counter (members of a class lie in different samples, so neighbouring lanes hit different
+// counters).  Consumers are order-free (k_finalize per row, k_positions by atomicMax of the rank key, the row table sorted on the host).
+__global__ void __launch_bounds__(256) k_expand_count(const itsx_domain *__restrict__ dom, int64_t n, const int32_t *__restrict__ class_of,
+                                                      const int32_t *__restrict__ off, int32_t *__restrict__ cnt, unsigned long long *__restrict__ total)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;          // (whole waves: no lane leaves before the reduction)
+  int32_t k = 0;
+  if (i < n && dom[i].dom_idx >= 0) { const int32_t c = class_of[dom[i].rep]; k = off[c + 1] - off[c] - 1; }
+  if (i <= n) cnt[i] = k;                                       // (cnt[n] = 0: the scan's last element is the total)
+  // the same total in 64 bits, one atomic per wave: the host refuses a segment whose copies would not fit the 32-bit scan
+  unsigned long long w = (unsigned long long)k;
+  for (int d = 32; d >= 1; d >>= 1) w += __shfl_down(w, d, 64);
+  if ((threadIdx.x & 63) == 0 && w) atomicAdd(total, w);
+}
+__global__ void __launch_bounds__(256) k_expand_rows(const itsx_domain *__restrict__ dom, int64_t n, const int32_t *__restrict__ pos, int64_t total,
+                                                     const int32_t *__restrict__ class_of, const int32_t *__restrict__ off, const int32_t *__restrict__ members,
+                                                     const int32_t *__restrict__ usample, int P, itsx_domain *__restrict__ out, int32_t *__restrict__ domz)
+{
+  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= total) return;
+  int64_t lo = 0, hi = n;                                       // the last row i with pos[i] <= o (rows without copies share their successor's pos)
+  while (hi - lo > 1) { const int64_t mid = lo + ((hi - lo) >> 1); if ((int64_t)pos[mid] <= o) lo = mid; else hi = mid; }
+  itsx_domain d = dom[lo];
+  const int32_t m = members[off[class_of[d.rep]] + 1 + (int32_t)(o - (int64_t)pos[lo])];
+  d.rep = m;
+  out[o] = d;
+  if (d.dom_idx == 0 && d.seq_reported) atomicAdd(&domz[(usample ? usample[m] * P : 0) + d.prof], 1);
+}
+
+void launch_class_insert(const ReadsDev &rd, const int32_t *seed_read, int32_t U, uint64_t seed, unsigned long long *keys, int32_t *vals, uint64_t mask,
+                         uint32_t *slot_of, hipStream_t st)
+{
+  if (U > 0) hipLaunchKernelGGL(k_class_insert, dim3(grid_for(U)), dim3(256), 0, st, rd, seed_read, U, seed, keys, vals, mask, slot_of);
+}
+void launch_class_resolve(const ReadsDev &rd, const int32_t *seed_read, int32_t U, const int32_t *vals, const uint32_t *slot_of, int32_t *holder_of,
+                          int32_t *is_holder, unsigned int *n_collisions, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_class_resolve, dim3(grid_for((int64_t)U + 1)), dim3(256), 0, st, rd, seed_read, U, vals, slot_of, holder_of, is_holder, n_collisions);
+}
+void launch_class_number(int32_t U, const int32_t *holder_of, const int32_t *rank, int32_t *class_of, int32_t *holder, unsigned long long *keys,
+                         int32_t *members, hipStream_t st)
+{
+  if (U > 0) hipLaunchKernelGGL(k_class_number, dim3(grid_for(U)), dim3(256), 0, st, U, holder_of, rank, class_of, holder, keys, members);
+}
+void launch_class_offsets(const unsigned long long *sorted_keys, int32_t U, int32_t C, int32_t *off, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_class_offsets, dim3((unsigned)(((int64_t)C + 1 + 255) / 256)), dim3(256), 0, st, sorted_keys, U, C, off);
+}
+void launch_expand_count(const itsx_domain *dom, int64_t n, const int32_t *class_of, const int32_t *off, int32_t *cnt, unsigned long long *total, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_expand_count, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, dom, n, class_of, off, cnt, total);
+}
+void launch_expand_rows(const itsx_domain *dom, int64_t n, const int32_t *pos, int64_t total, const int32_t *class_of, const int32_t *off,
+                        const int32_t *members, const int32_t *usample, int P, itsx_domain *out, int32_t *domz, hipStream_t st)
+{
+  if (total > 0) hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dom, n, pos, total, class_of, off, members, usample, P, out, domz);
+}
+
 }  // namespace itsx

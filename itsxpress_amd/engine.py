@@ -115,6 +115,40 @@ class Engine:
             self._chk(self.L.itsx_set_device_parse(self.h, int(where == "device")))
         self._parse = where
 
+    # Whether a search of a sample batch (S > 1, full rows mode) scores each distinct representative ONCE for all the samples it occurs
+    # in (itsx_set_sample_sharing): the uniques of all samples whose representatives are the same string in the same orientation form a
+    # score class, one holder per class goes through the HMM stages, and every member gets the holder's rows -- the rows, counters,
+    # coordinates and domtbl.txt of a search without it, bit for bit.  False (the default) or True; no effect on one sample, in the
+    # compact / lazy rows modes and after set_active_uniques (sample_sharing_info() then reports no classes).  Stays until set again.
+    @property
+    def share_samples(self):
+        return getattr(self, "_share_samples", False)
+
+    @share_samples.setter
+    def share_samples(self, on):
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError("Engine.share_samples is False or True, not %r" % (on,))
+        if getattr(self, "h", None):
+            self._chk(self.L.itsx_set_sample_sharing(self.h, int(bool(on))))
+        self._share_samples = bool(on)
+
+    def sample_sharing_info(self):
+        """What the last search() shared across samples: dict(n_classes, n_uniques_shared, n_rows_expanded, ms_classes, ms_expand) --
+        the score classes it built, the uniques it did not score because their class's holder was, the rows copied to them, and the
+        time of the two steps (event spans: their kernels and the host synchronisations between them).  All zero when share_samples was
+        off or does not apply; where it applies and nothing is common, n_classes == n_unique and nothing is shared or copied."""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.itsx_sample_sharing_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        x, y = C.c_float(0), C.c_float(0)
+        self._chk(self.L.itsx_sample_sharing_times(self.h, C.byref(x), C.byref(y)))
+        return dict(n_classes=int(a.value), n_uniques_shared=int(b.value), n_rows_expanded=int(c.value), ms_classes=float(x.value), ms_expand=float(y.value))
+
+    def debug_sample_classes(self):
+        """test hook: class_of[n_unique] of the last sharing search, from the device (classes numbered by their first member)"""
+        out = np.zeros(max(int(self.n_unique), 1), np.int32)
+        self._chk(self.L.itsx_debug_sample_classes(self.h, out.ctypes.data, int(self.n_unique)))
+        return out[:int(self.n_unique)]
+
     # Every call that changes the context's read set records the new count here, so the setter is where the read set's serial number
     # advances: a caller that left reads resident (SampleBatch.merge_reads) keeps the number and can tell later whether the
     # engine -- which may be shared -- still holds them

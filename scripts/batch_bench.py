@@ -32,7 +32,17 @@ one warm context -- `merge_reads` + `deduplicate` + `_search` + `write_trimmed` 
 `--inflate host,device` x `--parse host,device` (SampleBatch.inflate / .parse; default: host alone), the arms alternated within every
 repeat, the first repeat the warm-up.  The inputs are gzip files of the device deflate's members (`--plain-inputs`: plain text).
 Per arm the stage times of every repeat, the parse and inflate counters, and a check that every arm wrote the same bytes.
-Usage: python scripts/batch_bench.py --pairs-flow [n_samples] [pairs_per_sample] [repeats] [--inflate LIST] [--parse LIST] [--plain-inputs]"""
+Usage: python scripts/batch_bench.py --pairs-flow [n_samples] [pairs_per_sample] [repeats] [--inflate LIST] [--parse LIST] [--plain-inputs]
+
+--share-samples: sample sharing (Engine.share_samples: each distinct representative of a batch scored once for all the samples it occurs
+in) against the same batch without it, on one warm context in the full rows mode, the two arms alternated within every repeat, the first
+repeat the warm-up: derep + search + finalize + coordinates of S samples of n single-end reads handed over as arrays.  --overlap F (0..1,
+default 0.5) shapes the synthetic manifest: a share F of each sample's DISTINCT sequences is replaced by sequences drawn from a pool
+common to all samples (as large as one sample's distinct set, so a pool sequence turns up in about F of the samples); the rest are the
+sample's own.  The overlap is the generator's, not a real manifest's.  Per arm the wall times of every repeat, median and spread, the
+search's share of it; for the sharing arm the classes, the uniques not scored, the rows copied and the device time of both steps; and a
+check that both arms gave the same counters and coordinates.
+Usage: python scripts/batch_bench.py --share-samples [n_samples] [reads_per_sample] [repeats] [--overlap F]"""
 import gzip
 import hashlib
 import json
@@ -57,7 +67,15 @@ TRIM = "--trim" in sys.argv
 TRIM_PAIRED = "--trim-paired" in sys.argv
 PAIRS_FLOW = "--pairs-flow" in sys.argv
 PLAIN_INPUTS = "--plain-inputs" in sys.argv
-argv = [a for a in sys.argv[1:] if a not in ("--paired", "--orient", "--trim", "--trim-paired", "--pairs-flow", "--plain-inputs")]
+SHARE_SAMPLES = "--share-samples" in sys.argv
+argv = [a for a in sys.argv[1:] if a not in ("--paired", "--orient", "--trim", "--trim-paired", "--pairs-flow", "--plain-inputs", "--share-samples")]
+OVERLAP = 0.5
+if "--overlap" in argv:
+    k = argv.index("--overlap")
+    OVERLAP = float(argv[k + 1])
+    del argv[k:k + 2]
+    if not SHARE_SAMPLES or not 0.0 <= OVERLAP <= 1.0:
+        sys.exit("--overlap takes a share between 0 and 1 and goes with --share-samples")
 WHERE = {}
 for opt in ("--inflate", "--parse"):           # where the batch's loaders inflate and parse: host, device or a comma-separated list (arms)
     if opt in argv:
@@ -493,6 +511,87 @@ def pairs_flow_main():
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def overlap_manifest(n_samples, reads_per_sample, overlap):
+    """S samples of n reads (strings): every sample is its own draw of the generator (Zipf over its templates, substitutions, a few
+    reverse complements: duplicates inside the sample), then a share `overlap` of its distinct sequences is replaced, read for read, by
+    distinct sequences of a pool common to all samples (drawn without replacement, so the sample's distinct count stays)"""
+    def draw(seed):
+        blob, offs = synth.make_reads(thmm, reads_per_sample, config=2, seed=seed)
+        return synth.to_strings(blob, offs)
+    pool = list(dict.fromkeys(draw(synth.SEED + 99)))
+    out = []
+    for s in range(n_samples):
+        rng = np.random.default_rng(7000 + s)
+        reads = draw(synth.SEED + 100 + s)
+        distinct = list(dict.fromkeys(reads))
+        k = min(int(round(overlap * len(distinct))), len(pool))
+        swap = dict(zip((distinct[i] for i in rng.choice(len(distinct), k, replace=False)), (pool[j] for j in rng.choice(len(pool), k, replace=False))))
+        out.append([swap.get(r, r) for r in reads])
+    return out
+
+
+def share_samples_main():
+    repeats = int(argv[2]) if len(argv) > 2 else 4
+    samples = overlap_manifest(S, n, OVERLAP)
+    blob = "".join(r for x in samples for r in x).encode()
+    offs = np.concatenate([[0], np.cumsum([len(r) for x in samples for r in x])]).astype(np.int64)
+    smp = np.repeat(np.arange(S, dtype=np.int32), [len(x) for x in samples])
+    eng = Engine(0)
+    eng.load_profiles(text=its2_profiles(thmm))
+    eng.set_rows_mode("full")
+
+    def run(share):
+        eng.share_samples = share
+        t0 = time.perf_counter()
+        eng.set_reads_buffer(blob, offs)
+        eng.set_samples(smp, S)
+        nu = eng.derep()
+        t1 = time.perf_counter()
+        eng.search()
+        t2 = time.perf_counter()
+        domz = eng.get_domz().copy()
+        eng.finalize()
+        coords = [x.copy() for x in eng.trim_coords("3_", "4_")]
+        t3 = time.perf_counter()
+        info = eng.sample_sharing_info()
+        st = eng.stats()
+        return dict(s_total=round(t3 - t0, 4), s_search=round(t2 - t1, 4), s_finalize_coords=round(t3 - t2, 4), n_unique=int(nu), n_pairs=int(st["n_pairs"]),
+                    ms_msv=round(float(st["ms_msv"]), 2), ms_filters=round(float(st["ms_filters"]), 2), ms_domains=round(float(st["ms_domains"]), 2),
+                    **{k: (round(v, 3) if isinstance(v, float) else v) for k, v in info.items()}), (domz, coords)
+
+    arms = {False: [], True: []}
+    results = {}
+    try:
+        for r in range(repeats + 1):           # repeat 0 is the warm-up: buffers grow to their working size
+            for share in (False, True):
+                res, payload = run(share)
+                if r == 0:
+                    results[share] = payload
+                    continue
+                arms[share].append(res)
+                print("[batch_bench] repeat %d, share_samples %s: %.3f s (search %.3f s)" % (r, share, res["s_total"], res["s_search"]), file=sys.stderr, flush=True)
+    finally:
+        eng.share_samples = False
+    same = np.array_equal(results[False][0], results[True][0]) and all(np.array_equal(a, b) for a, b in zip(results[False][1], results[True][1]))
+    out = {"share_samples": True, "samples": S, "reads_per_sample": n, "overlap": OVERLAP, "repeats": repeats, "rows_mode": "full"}
+    for share, name in ((False, "off"), (True, "on")):
+        for key in ("s_total", "s_search"):
+            v = [x[key] for x in arms[share]]
+            out["%s_%s" % (name, key)] = v
+            out["%s_%s_median" % (name, key)] = round(float(np.median(v)), 4)
+            out["%s_%s_spread" % (name, key)] = round(max(v) - min(v), 4)
+        out["%s_last" % name] = arms[share][-1]
+    out["off_over_on_total"] = round(out["off_s_total_median"] / out["on_s_total_median"], 3)
+    out["off_over_on_search"] = round(out["off_s_search_median"] / out["on_s_search_median"], 3)
+    out["identical_counters_and_coordinates"] = bool(same)
+    print(json.dumps(out))
+    return 0 if same else 1
+
+
+if SHARE_SAMPLES:
+    if len(argv) < 1:
+        S, n = 384, 2000
+    sys.exit(share_samples_main())
 if PAIRS_FLOW:
     if len(argv) < 1:
         S, n = 384, 2000
