@@ -434,7 +434,7 @@ struct itsx_ctx {
   bool completing = false;               // itsx_lazy_complete: every pair of the profiles in plist goes through the domain pipeline
   std::vector<int32_t> h_plist; DBuf<int32_t> d_plist;
   int64_t s_Uc = 0; int s_Lcap = 0;       // the last search's chunk size and length cap (the completion walks the same chunks)
-  DBuf<float> l_fb; DBuf<uint32_t> l_b10; DBuf<uint8_t> l_done; DBuf<unsigned long long> l_smask; DBuf<int32_t> l_scnt, l_spos, l_scan, l_has; DBuf<unsigned long long> l_gtop, l_sure;
+  DBuf<float> l_fb; DBuf<uint32_t> l_b10, l_thr; DBuf<uint8_t> l_done; DBuf<unsigned long long> l_smask; DBuf<int32_t> l_scnt, l_spos, l_scan, l_has; DBuf<unsigned long long> l_gtop, l_sure;
   DBuf<PairRec> l_pairs; DBuf<int64_t> l_seg, l_zub; DBuf<int32_t> l_pflag; DBuf<uint8_t> l_uflag; bool partial_coords = false; bool kept_rows = false; std::vector<int32_t> lazy_pending_prof;
   std::vector<uint16_t> thr_memo; std::vector<char> thr_memo_have; double thr_memo_F1 = -1.0; int thr_memo_Ppad = 0;   // MSV thresholds by length, kept between searches
   DBuf<int32_t> w_coords4; DBuf<int64_t> w_keys128; DBuf<uint64_t> w_hf1, w_hr1;
@@ -3233,9 +3233,24 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
     const int NW = woff.back();
     HIPCHK(ctx->w_waves.alloc((size_t)std::max(NW, 1))); HIPCHK(ctx->w_counters.alloc(512));
     HIPCHK(hipMemsetAsync(ctx->w_counters.p, 0, 512 * sizeof(int64_t), st));
-    launch_share_waves(NW, nseg, P, ctx->sh_woff.p, ctx->sh_bnd.p, ctx->sh_segdepth.p, ctx->share_B, pl.pairs, two ? ctx->sh_endrow.p + u0 : nullptr, 0, ctx->w_waves.p,
-                       (unsigned long long *)ctx->w_counters.p, st);
-    std::vector<int64_t> lr((size_t)384, 0);
+    // the wave list from the segment bounds alone, the row counters by chain (k_share.hip).  Who reads a wave's last row from its descriptor
+    // -- the launch dump, and the check hooks' kernels on the one-sided schedule's own list -- gets the list that looks at every pair
+    // (its sums go to the spare counters: ITSX_SHARE_CHECK=1 runs it in any case and counts a sum that differs from the chains' as a mismatch)
+    const bool dump = sw_get("ITSX_PASSA_DUMP") != nullptr;
+    const bool share_check = sw_get("ITSX_SHARE_CHECK") && atoi(sw_get("ITSX_SHARE_CHECK")) != 0;
+    const bool want_check = sw_get("ITSX_LAZY_CHECK_BOUND") || share_check;
+    const bool need_rows = dump || (want_check && !two);
+    const int Wn = (P + 31) / 32;
+    launch_share_rows(Uc, Wn, ctx->sh_need.p, ctx->sh_ulen.p + u0, two ? ctx->sh_endrow.p + u0 : nullptr, ctx->sh_segflat.p, nseg, ctx->sh_segdepth.p, ctx->share_B, 0,
+                      (unsigned long long *)ctx->w_counters.p, st);
+    if (need_rows || share_check)
+      launch_share_waves(NW, nseg, P, ctx->sh_woff.p, ctx->sh_bnd.p, ctx->sh_segdepth.p, ctx->share_B, pl.pairs, two ? ctx->sh_endrow.p + u0 : nullptr, 0, ctx->w_waves.p,
+                         (unsigned long long *)ctx->w_counters.p + 256, st);
+    if (!need_rows) launch_share_wavelist(NW, nseg, P, ctx->sh_woff.p, ctx->sh_bnd.p, ctx->w_waves.p, st);
+    // the shared pass stores a pair's bound and its group's best beside its score (k_fwd_bound: ShareLaunch::b10): no pass over the list
+    // for them afterwards; the padding records' b10 = 0 is written here
+    launch_pad_b10(P, pl.d_seg_start, ctx->w_rcnt.p, ctx->l_b10.p, st);
+    std::vector<int64_t> lr((size_t)512, 0);
     FloatArgs a{};
     a.rd = ctx->rd; a.sorted_uniq = d_sorted; a.seed_read = ctx->d_seed_read.p; a.prof = ctx->d_prof.p; a.lt = ctx->d_lt.p;
     a.pairs = pl.pairs; a.waves = ctx->w_waves.p; a.F1 = F1; a.F3 = F3;
@@ -3274,9 +3289,8 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
         launch_need_res(ctx->sh_needb.p, Ubc, P, W, ctx->sh_resb.p, st);
         const int nchb = (Ubc + CHUNK - 1) / CHUNK;
         HIPCHK(ctx->sh_cntb.alloc((size_t)P * nchb)); HIPCHK(ctx->sh_totalb.alloc((size_t)P)); HIPCHK(ctx->sh_realb.alloc((size_t)P));
-        HIPCHK(hipMemsetAsync(ctx->sh_realb.p, 0, (size_t)P * 4, st));
-        launch_pair_count(ctx->sh_resb.p, P, Ubc, nchb, ctx->sh_cntb.p, ctx->sh_realb.p, st);
-        launch_chunk_scan(ctx->sh_cntb.p, P, nchb, ctx->sh_totalb.p, st);
+        launch_pair_count(ctx->sh_resb.p, P, Ubc, nchb, ctx->sh_cntb.p, st);
+        launch_chunk_scan(ctx->sh_cntb.p, P, nchb, ctx->sh_totalb.p, ctx->sh_realb.p, st);
         std::vector<int32_t> totalb((size_t)P);
         HIPCHK(hipMemcpyAsync(totalb.data(), ctx->sh_totalb.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -3287,8 +3301,7 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
         if (NPB > 0) {
           HIPCHK(upload(ctx->sh_bseg_start, bseg, st));
           HIPCHK(ctx->sh_bpairs.alloc((size_t)NPB));
-          HIPCHK(hipMemsetAsync(ctx->sh_bpairs.p, 0xFF, (size_t)NPB * sizeof(PairRec), st));
-          launch_pair_fill(ctx->sh_resb.p, P, Ubc, nchb, ctx->sh_cntb.p, ctx->sh_bseg_start.p, ctx->sh_bulen.p + cb0, ctx->sh_bpairs.p, st);
+          launch_pair_fill(ctx->sh_resb.p, P, Ubc, nchb, ctx->sh_cntb.p, ctx->sh_bseg_start.p, ctx->sh_totalb.p, ctx->sh_bulen.p + cb0, ctx->sh_bpairs.p, st);
           HIPCHK(upload(ctx->sh_bsegflat, bsegflat, st)); HIPCHK(upload(ctx->sh_bsegdepth, bsegdepth, st, 1));
           HIPCHK(ctx->sh_bbnd.alloc((size_t)(nbseg + 1) * P)); HIPCHK(ctx->sh_bwc.alloc((size_t)nbseg * P + 2)); HIPCHK(ctx->sh_bwoff.alloc((size_t)nbseg * P + 2));
           HIPCHK(ctx->sh_scan.alloc((size_t)scan_tmp_elems((int64_t)nbseg * P + 2)));
@@ -3299,16 +3312,18 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
           HIPCHK(hipStreamSynchronize(st));
           NWB = bwoff.back();
           HIPCHK(ctx->sh_bwaves.alloc((size_t)std::max(NWB, 1)));
-          launch_share_waves(NWB, nbseg, P, ctx->sh_bwoff.p, ctx->sh_bbnd.p, ctx->sh_bsegdepth.p, ctx->share_B, ctx->sh_bpairs.p, ctx->sh_bsteps.p + cb0, 1, ctx->sh_bwaves.p,
-                             (unsigned long long *)ctx->w_counters.p + 128, st);
+          launch_share_rows(Ubc, W, ctx->sh_needb.p, nullptr, ctx->sh_bsteps.p + cb0, nullptr, 0, nullptr, 0, 1, (unsigned long long *)ctx->w_counters.p + 128, st);
+          if (dump || share_check)
+            launch_share_waves(NWB, nbseg, P, ctx->sh_bwoff.p, ctx->sh_bbnd.p, ctx->sh_bsegdepth.p, ctx->share_B, ctx->sh_bpairs.p, ctx->sh_bsteps.p + cb0, 1, ctx->sh_bwaves.p,
+                               (unsigned long long *)ctx->w_counters.p + 384, st);
+          if (!dump) launch_share_wavelist(NWB, nbseg, P, ctx->sh_bwoff.p, ctx->sh_bbnd.p, ctx->sh_bwaves.p, st);
           ab.sorted_uniq = ctx->sh_border.p + cb0; ab.pairs = ctx->sh_bpairs.p; ab.waves = ctx->sh_bwaves.p;
         }
       }
     }
-    HIPCHK(hipMemcpyAsync(lr.data(), ctx->w_counters.p, 256 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(lr.data(), ctx->w_counters.p, 512 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     // diagnostic (scripts/passa_launches.py): every launch's waves and wave-rows, in launch order, to set against a kernel trace
     std::vector<WaveDesc> dumpf, dumpb;
-    const bool dump = sw_get("ITSX_PASSA_DUMP") != nullptr;
     if (dump) {
       dumpf.resize((size_t)std::max(NW, 1)); dumpb.resize((size_t)std::max(NWB, 1));
       HIPCHK(hipMemcpyAsync(dumpf.data(), ctx->w_waves.p, (size_t)NW * sizeof(WaveDesc), hipMemcpyDeviceToHost, st));
@@ -3366,6 +3381,7 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
           ShareLaunch sl{};
           sl.src = ctx->sh_src.p + u0; sl.mask = ctx->sh_mask.p + u0; sl.node0 = ctx->sh_node0.p + u0;
           sl.slots = fsl; sl.node_base = b.node0; sl.p0 = pa; sl.Pb = pb - pa; sl.depth = d; sl.logB = ctx->share_logB;
+          sl.b10 = ctx->l_b10.p; sl.done = ctx->l_done.p; sl.gtop = ctx->l_gtop.p; sl.cls = ctx->w_cls.p; sl.ncls = ncls;
           if (two) {
             sl.endrow = ctx->sh_endrow.p + u0; sl.jlev = ctx->sh_jlev.p + u0; sl.jsrc = ctx->sh_jsrc.p + u0; sl.gslots = gsl; sl.gnode_base = b.gnode0;
             if (!sw_get("ITSX_NO_CHAINREC")) { sl.chain = ctx->sh_chain.p + u0; sl.entab = ctx->d_entab.p; }
@@ -3380,9 +3396,15 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
     const float ms = tm.stop();
     tb.collect();
     S.ms_bound_kernel += ms; S.ms_filters += ms;
-    for (int q = 0; q < 64; q++) { S.bound_rows += lr[(size_t)2 * q]; S.bound_rows_full += lr[(size_t)2 * q + 1]; S.bwd_rows += lr[(size_t)128 + 2 * q]; }
+    int64_t by_pair[3] = {0, 0, 0}, by_chain[3] = {0, 0, 0};
+    for (int q = 0; q < 64; q++) {
+      by_chain[0] += lr[(size_t)2 * q]; by_chain[1] += lr[(size_t)2 * q + 1]; by_chain[2] += lr[(size_t)128 + 2 * q];
+      by_pair[0] += lr[(size_t)256 + 2 * q]; by_pair[1] += lr[(size_t)256 + 2 * q + 1]; by_pair[2] += lr[(size_t)384 + 2 * q];
+    }
+    S.bound_rows += by_chain[0]; S.bound_rows_full += by_chain[1]; S.bwd_rows += by_chain[2];
+    if (share_check)                                        // test hook: the three sums pair by pair (k_share_waves) against the chains' (k_share_rows)
+      for (int q = 0; q < 3; q++) S.share_mismatch += by_pair[q] != by_chain[q];
     // the check hooks below run every pair from row 1: their waves reach the pairs' last rows
-    const bool want_check = sw_get("ITSX_LAZY_CHECK_BOUND") || (sw_get("ITSX_SHARE_CHECK") && atoi(sw_get("ITSX_SHARE_CHECK")) != 0);
     if (two && want_check)
       launch_share_waves(NW, nseg, P, ctx->sh_woff.p, ctx->sh_bnd.p, ctx->sh_segdepth.p, ctx->share_B, pl.pairs, nullptr, 0, ctx->w_waves.p, (unsigned long long *)ctx->w_counters.p + 256, st);
     if (sw_get("ITSX_LAZY_CHECK_BOUND")) {       // test hook: the shared chains' scores against HMMER's own arithmetic from row 1
@@ -3481,7 +3503,9 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
   LazyArgs la{};
   la.pairs = pl.pairs; la.NP = NP; la.fb = ctx->l_fb.p; la.lt = ctx->d_lt.p; la.cls = ctx->w_cls.p; la.ncls = ncls; la.sorted_uniq = d_sorted;
   la.b10 = ctx->l_b10.p; la.gtop = ctx->l_gtop.p; la.bestc = ctx->w_bestc.p; la.done = ctx->l_done.p; la.smask = ctx->l_smask.p; la.scnt = ctx->l_scnt.p; la.ngroups = (int64_t)Uc * ncls;
-  launch_lazy_bound(la, st);
+  HIPCHK(ctx->l_thr.alloc((size_t)Uc * ncls + 1));
+  la.thr = ctx->l_thr.p; la.nthr = (int64_t)Uc * ncls; la.nbest = (int64_t)ctx->w_bestc.n;
+  if (!ctx->share_on) launch_lazy_bound(la, st);          // (the shared pass A has stored b10, done and gtop itself)
   float ms_sel = tm_sel.stop();
   for (int round = 0; round < 2; round++) {
     StageTimer tm_r(st);
@@ -3658,9 +3682,8 @@ static int search_chunk(itsx_ctx *ctx, int ci, int32_t u0, int32_t U, int Lcap, 
     launch_need_mark(d_res.p, U, P, W, ctx->sh_pass.p, ctx->sh_need.p, ctx->sh_counters.p + 9, st);
   }
   HIPCHK(ctx->sh_real.alloc((size_t)P));
-  HIPCHK(hipMemsetAsync(ctx->sh_real.p, 0, (size_t)P * 4, st));
-  launch_pair_count(d_res.p, P, U, nchunks, d_cnt.p, ctx->sh_real.p, st);
-  launch_chunk_scan(d_cnt.p, P, nchunks, d_total.p, st);
+  launch_pair_count(d_res.p, P, U, nchunks, d_cnt.p, st);
+  launch_chunk_scan(d_cnt.p, P, nchunks, d_total.p, ctx->sh_real.p, st);
   std::vector<int32_t> total((size_t)P), real((size_t)P);       // pairs on the list / pairs past the filter (the same without sharing)
   HIPCHK(hipMemcpyAsync(total.data(), d_total.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(real.data(), ctx->sh_real.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
@@ -3674,13 +3697,12 @@ static int search_chunk(itsx_ctx *ctx, int ci, int32_t u0, int32_t U, int Lcap, 
   DBuf<int64_t> &d_seg_start = ctx->w_seg_start;
   HIPCHK(upload(d_seg_start, seg_start, st));
   ctx->topup.list_live = false;
-  HIPCHK(ctx->d_pairs.alloc((size_t)NP));
-  HIPCHK(hipMemsetAsync(ctx->d_pairs.p, 0xFF, (size_t)NP * sizeof(PairRec), st));
+  HIPCHK(ctx->d_pairs.alloc((size_t)NP));                    // (k_pair_fill writes all of it, the segments' padding included)
   if (!lazy_now) {                                 // (the lazy stage keeps a PairOut only for the pairs it evaluates)
     HIPCHK(ctx->d_pout.alloc((size_t)NP));
     HIPCHK(hipMemsetAsync(ctx->d_pout.p, 0, (size_t)NP * sizeof(PairOut), st));
   }
-  launch_pair_fill(d_res.p, P, U, nchunks, d_cnt.p, d_seg_start.p, d_ulen, ctx->d_pairs.p, st);
+  launch_pair_fill(d_res.p, P, U, nchunks, d_cnt.p, d_seg_start.p, d_total.p, d_ulen, ctx->d_pairs.p, st);
   S.ms_msv += tm_list.stop();
   const int64_t zub_scale = sw_get("ITSX_LAZY_ZUB_SCALE") ? std::max<int64_t>(1, atoll(sw_get("ITSX_LAZY_ZUB_SCALE"))) : 1;   // test hook: looser bounds, more undecided rows
   if (!ctx->completing)
@@ -6704,7 +6726,7 @@ int itsx_debug_select(itsx_ctx *ctx, int mode, const int32_t *pairs, int64_t NP,
   }
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->st;
-  DBuf<PairRec> dp; DBuf<uint8_t> dd; DBuf<uint32_t> db, dcut; DBuf<int8_t> dcls; DBuf<unsigned long long> dg; DBuf<int32_t> dsu, dslot; DBuf<int64_t> dseg;
+  DBuf<PairRec> dp; DBuf<uint8_t> dd; DBuf<uint32_t> db, dcut, dthr; DBuf<int8_t> dcls; DBuf<unsigned long long> dg; DBuf<int32_t> dsu, dslot; DBuf<int64_t> dseg;
   HIPCHK(dp.alloc((size_t)NP)); HIPCHK(dd.alloc((size_t)NP)); HIPCHK(db.alloc((size_t)NP)); HIPCHK(dseg.alloc((size_t)P + 1));
   HIPCHK(hipMemcpyAsync(dp.p, pairs, (size_t)NP * sizeof(PairRec), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(dd.p, done, (size_t)NP, hipMemcpyHostToDevice, st));
@@ -6743,7 +6765,8 @@ int itsx_debug_select(itsx_ctx *ctx, int mode, const int32_t *pairs, int64_t NP,
   if (mode <= 1) {
     LazyArgs la{};
     la.pairs = dp.p; la.NP = NP; la.cls = dcls.p; la.ncls = ncls; la.sorted_uniq = dsu.p; la.b10 = db.p;
-    la.gtop = mode == 0 ? dg.p : nullptr; la.ngroups = mode == 0 ? n_group : 0; la.bestc = mode == 1 ? dg.p : nullptr; la.done = dd.p; la.smask = ctx->l_smask.p; la.scnt = ctx->l_scnt.p;
+    la.gtop = mode == 0 ? dg.p : nullptr; la.ngroups = mode == 0 ? n_group : 0; la.bestc = mode == 1 ? dg.p : nullptr; la.done = dd.p;
+    if (mode == 1) { HIPCHK(dthr.alloc((size_t)n_sorted * ncls + 1)); la.thr = dthr.p; la.nthr = (int64_t)n_sorted * ncls; la.nbest = n_group; } la.smask = ctx->l_smask.p; la.scnt = ctx->l_scnt.p;
     launch_lazy_mark(la, mode, st);
   } else launch_topup_mark(dp.p, NP, dd.p, db.p, dslot.p, dcut.p, ctx->l_smask.p, ctx->l_scnt.p, st);
   PairList sub; int64_t nsel = 0;

@@ -411,6 +411,10 @@ struct ShareLaunch {
   // chain of dependent loads (pair -> sorted position -> read -> offsets): a wave's start-up was 30 rows' worth of latency
   const struct ChainRec *chain;
   const float *entab;          // [P][NCODE][2 * BOUND_PAIRS] the folded emission odds by node (engine.hip: install_profiles)
+  // k_fwd_bound, b10 != nullptr: where a pair's score is stored, what k_lazy_bound makes of it is stored too -- b10[pair], done[pair] = 1 for
+  // a pair that ran for its row states only, and the atomicMax into gtop[useq * ncls + cls[prof]] (FloatArgs::lt gives the length's tables);
+  // launch_lazy_bound is then not needed.  The caller clears b10 at the list's padding records (launch_pad_b10)
+  uint32_t *b10; uint8_t *done; unsigned long long *gtop; const int8_t *cls; int32_t ncls;
   int32_t dbg;                 // diagnostic (ITSX_TEST_HOOKS=1 ITSX_PASSA_DBG=bits; results are garbage): 1 no rows, 2 no restore, 4 no join; k_bwd_bound: 8 no saves, 16 no restore, 32 no rows
 };
 struct alignas(16) ChainRec {
@@ -436,6 +440,11 @@ struct WaveDesc;
 void launch_share_waves(int32_t nw, int32_t nseg, int32_t P, const int32_t *woff, const int64_t *bnd, const int32_t *seg_depth, int32_t B, const PairRec *pairs,
                         const int32_t *endrow /*by useq; nullptr: the pair's L*/, int backward, WaveDesc *w,
                         unsigned long long *lane_rows /*[64][2], zeroed: rows computed, rows of the pairs (summed by the host)*/, hipStream_t st);
+// pass A's own list: one thread per wave and no look at the pairs (WaveDesc::rows = 0: k_fwd_bound<true, *> and k_bwd_bound find their wave's
+// last row themselves), and launch_share_waves' lane_rows summed by chain: need = the chains' profile bits [U][W], segk[nseg + 1]
+void launch_share_wavelist(int32_t nw, int32_t nseg, int32_t P, const int32_t *woff, const int64_t *bnd, WaveDesc *w, hipStream_t st);
+void launch_share_rows(int32_t U, int32_t W, const uint32_t *need, const int32_t *ulen, const int32_t *endrow /*nullptr: ulen*/, const int32_t *segk, int32_t nseg,
+                       const int32_t *seg_depth, int32_t B, int backward, unsigned long long *lane_rows, hipStream_t st);
 
 // ---- k_msv.hip
 struct MsvArgs {
@@ -465,10 +474,11 @@ void launch_msv(const MsvArgs &a, hipStream_t st, int lds_pad = 0);
 
 // survivor list: pairs grouped by profile, 64-aligned segments, ascending length inside a segment
 constexpr int CHUNK = 2048;
-void launch_pair_count(const uint16_t *res, int32_t P, int32_t U, int32_t nchunks, int32_t *cnt /*[P][nchunks]*/, int32_t *real /*[P], zeroed: pairs past the filter*/, hipStream_t st);
-void launch_chunk_scan(int32_t *cnt, int32_t P, int32_t nchunks, int32_t *total /*[P]*/, hipStream_t st);
+void launch_pair_count(const uint16_t *res, int32_t P, int32_t U, int32_t nchunks, int32_t *cnt /*[P][nchunks]: on the list | past the filter << 16*/, hipStream_t st);
+void launch_chunk_scan(int32_t *cnt, int32_t P, int32_t nchunks, int32_t *total /*[P]*/, int32_t *real /*[P]: pairs past the filter*/, hipStream_t st);
+// writes every record of the list, the padding at each segment's end (all 0xFF) included: the list needs no fill beforehand
 void launch_pair_fill(const uint16_t *res, int32_t P, int32_t U, int32_t nchunks, const int32_t *cnt,
-                      const int64_t *seg_start /*[P]*/, const int32_t *ulen /*[U] length by sorted position*/,
+                      const int64_t *seg_start /*[P + 1]*/, const int32_t *total /*[P]*/, const int32_t *ulen /*[U] length by sorted position*/,
                       PairRec *pairs, hipStream_t st);
 void launch_fill_ulen(int32_t U, const int32_t *sorted_uniq, const int32_t *seed_read, const int32_t *len, int32_t *ulen, hipStream_t st);
 
@@ -676,11 +686,15 @@ struct LazyArgs {
   unsigned long long *gtop;        // [chunk uniques x ncls] (b10 << 32 | ~pair) of the group's best-bound pair
   int64_t ngroups;                 // chunk uniques x ncls
   const unsigned long long *bestc; // [uniques x ncls] rank key of the best CERTAIN row so far (k_compact_best)
+  int64_t nbest;                   // entries of bestc
+  uint32_t *thr; int64_t nthr;     // round 1's scratch, [sorted positions x ncls]: the tenths of bestc's row by position (0: the group has none)
   uint8_t *done;                   // [NP] the pair went through the domain stage already
   unsigned long long *smask;       // [NP / 64] selected for this round: one bit per pair, one word per chunk of 64 pairs
   int32_t *scnt;                   // [NP / 64 + 1] set bits of each chunk (the last one 0)
 };
 void launch_lazy_bound(const LazyArgs &a, hipStream_t st);
+// b10 = 0 at the padding records behind each profile's segment (what launch_lazy_bound writes there; for a pass A that stores b10 itself)
+void launch_pad_b10(int32_t P, const int64_t *seg_start /*[P + 1]*/, const int32_t *total /*[P]*/, uint32_t *b10, hipStream_t st);
 void launch_lazy_mark(const LazyArgs &a, int round, hipStream_t st);
 // spos = the exclusive scan of scnt; profile segments (seg_old) start at multiples of 64
 void launch_lazy_scatter(const PairRec *pairs, int64_t NP, const unsigned long long *smask, const int32_t *spos, const int64_t *seg_old, const int64_t *seg_new,

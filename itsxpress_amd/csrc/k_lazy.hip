@@ -60,6 +60,32 @@ DEV BT ldbt(const float *tab, int j)
   return t;
 }
 DEV f2 pfma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
+// largest %.1f tenths (biased) a domain of a pair with pass-A score f can print (k_lazy_bound, and k_fwd_bound where it stores b10 itself)
+DEV uint32_t lazy_tenths(float f, const LenTables &lt)
+{
+  if (f != f || f == __builtin_inff()) return (1u << 24) - 1;               // no usable bound: always evaluated
+  if (f == -__builtin_inff()) return 1u;
+  const double bits = ((double)f - (double)lt.nullsc) / 0.69314718055994529 + (double)lt.lazy_c;
+  double t = __builtin_floor(bits * 10.0 + 0.5) + (double)LAZY_TENTHS_BIAS;      // round half UP: never below rint()
+  if (t < 1.0) t = 1.0;
+  if (t > (double)((1 << 24) - 1)) t = (double)((1 << 24) - 1);
+  return (uint32_t)t;
+}
+// what k_lazy_bound does for pair pi, with the score that was just stored (ShareLaunch::b10 != nullptr)
+DEV void lazy_bound_put(const ShareLaunch &sl, const LenTables *lt, int64_t pi, const PairRec &pr, float f)
+{
+  if (pr.xj < 0) { sl.b10[pi] = 0u; sl.done[pi] = 1; return; }      // ran for its row states only (k_share.hip): never selected
+  const uint32_t b = lazy_tenths(f, lt[pr.L]);
+  sl.b10[pi] = b;
+  atomicMax(&sl.gtop[(size_t)pr.useq * sl.ncls + sl.cls[pr.prof]], ((unsigned long long)b << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)pi));
+}
+// the largest v of the wave's 64 lanes, wave-uniform (a scalar register)
+DEV int wave_max(int v)
+{
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
+  return uni(v);
+}
 
 // SHARE (k_share.hip): the wave's pairs are chains that start at the same depth of their length's prefix tree -- the rows before
 // come from the state the parent chain saved for this profile (FWD_STATE_Q float4: M, I, D of the 46 nodes, xN xJ xC xB, the scale's
@@ -141,6 +167,9 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_fwd_bound(FloatArgs a, int 
         if (sl.endrow) { endrow = sl.endrow[k]; jlev = pr.xj >= 0 ? sl.jlev[k] : -1; jnode = (int64_t)sl.jsrc[k] - sl.gnode_base; }
       }
     }
+    // the wave runs to the last row of its longest chain: the maximum over its lanes (the shared schedule's descriptors carry no row
+    // count: k_share.hip, k_share_wavelist); a spare wave has no lane and no row
+    Lw = wave_max(active ? endrow : 0);
     if (sl.dbg & 1) Lw = row0;
     if (sl.dbg & 4) jlev = -1;
     if (sl.depth > 0 && !(sl.dbg & 2)) {
@@ -189,7 +218,9 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_fwd_bound(FloatArgs a, int 
           const float dot = (sa.x + sa.y) + (sb.x + sb.y);
           const double gscale = __builtin_bit_cast(double, (f2){t.z, t.w});
           const bool jbad = (dot != dot) || (dot <= 0.0f) || (dot == __builtin_inff());
-          fb[pi] = jbad ? __builtin_nanf("") : (float)(totscale + gscale + det_log((double)dot));
+          const float sc = jbad ? __builtin_nanf("") : (float)(totscale + gscale + det_log((double)dot));
+          fb[pi] = sc;
+          if (sl.b10) lazy_bound_put(sl, a.lt, pi, pr, sc);
         }
       }
     }
@@ -277,7 +308,11 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_fwd_bound(FloatArgs a, int 
     }
   }
   const bool bad = (xC != xC) || (xC == 0.0f) || (xC == __builtin_inff());
-  if (active && jlev < 0) fb[pi] = bad ? __builtin_nanf("") : (float)(totscale + det_log((double)(xC * pmove)));
+  if (active && jlev < 0) {
+    const float sc = bad ? __builtin_nanf("") : (float)(totscale + det_log((double)(xC * pmove)));
+    fb[pi] = sc;
+    if (sl.b10) lazy_bound_put(sl, a.lt, pi, pr, sc);
+  }
 }
 
 // =========================================================================================
@@ -329,7 +364,7 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_bwd_bound(FloatArgs a, int 
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
   Seq sq; sq.w = a.rd.words + cr.woff; sq.exc = a.rd.exc + cr.excoff; sq.nexc = cr.nexc; sq.L = cr.L;
-  const int nsteps = (sl.dbg & 32) ? 0 : wd.rows - 1;         // the wave's longest chain
+  const int nsteps = (sl.dbg & 32) ? 0 : wave_max(active ? cr.endrow : 0);         // the wave's longest chain (no lane: no step)
   f2 M[BP], I[BP], D[BP];
 #pragma unroll
   for (int j = 0; j < BP; j++) { M[j] = (f2){0.f, 0.f}; I[j] = (f2){0.f, 0.f}; D[j] = (f2){0.f, 0.f}; }
@@ -485,18 +520,7 @@ __global__ void __launch_bounds__(256) k_lazy_bound(LazyArgs a)
   const PairRec pr = a.pairs[i];
   if (pr.prof < 0) { a.b10[i] = 0u; return; }
   if (pr.xj < 0) { a.b10[i] = 0u; a.done[i] = 1; return; }      // ran for its row states only (k_share.hip): never selected
-  const float f = a.fb[i];
-  const LenTables lt = a.lt[pr.L];
-  uint32_t b;
-  if (f != f || f == __builtin_inff()) b = (1u << 24) - 1;                  // no usable bound: always evaluated
-  else if (f == -__builtin_inff()) b = 1u;
-  else {
-    const double bits = ((double)f - (double)lt.nullsc) / 0.69314718055994529 + (double)lt.lazy_c;
-    double t = __builtin_floor(bits * 10.0 + 0.5) + (double)LAZY_TENTHS_BIAS;      // round half UP: never below rint()
-    if (t < 1.0) t = 1.0;
-    if (t > (double)((1 << 24) - 1)) t = (double)((1 << 24) - 1);
-    b = (uint32_t)t;
-  }
+  const uint32_t b = lazy_tenths(a.fb[i], a.lt[pr.L]);
   a.b10[i] = b;
   const size_t g = (size_t)pr.useq * a.ncls + a.cls[pr.prof];
   atomicMax(&a.gtop[g], ((unsigned long long)b << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i));
@@ -537,21 +561,53 @@ __global__ void __launch_bounds__(256) k_select_count(const unsigned long long *
   if (c <= nch) scnt[c] = c < nch ? (int32_t)__popcll(smask[c]) : 0;
 }
 // round 1: everything not yet evaluated that could still beat (or tie with) the group's best certain row; all of a group that has none.
+// The group's row is asked for by 691 M pairs but there are only chunk uniques x ncls groups, and bestc lies by GLOBAL unique index: a
+// gather at random for every pair.  k_lazy_thr first lays the one number a pair compares with -- the row's tenths, 0 for a group that has
+// no certain row (every bound is >= 0: all of it selected) -- by sorted position, thr[useq * ncls + class]; useq ascends inside a profile
+// segment, so a wave of the marking kernel then reads consecutive words.
+__global__ void __launch_bounds__(256) k_lazy_thr(LazyArgs a)
+{
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= a.nthr) return;
+  const int64_t su = a.sorted_uniq[g / a.ncls], idx = su * a.ncls + g % a.ncls;
+  const unsigned long long bc = (su >= 0 && idx < a.nbest) ? a.bestc[idx] : 0ull;      // (a position no pair names may point anywhere)
+  a.thr[g] = (uint32_t)(bc >> 40);
+}
+// A wave of a marking kernel takes MARK_K consecutive chunks, a lane one pair of each: the MARK_K records, flags and bounds are
+// requested before the first of them is used, then the MARK_K loads that hang on them, level by level (one pair per thread went through
+// pair -> sorted_uniq -> bestc as one chain of latencies).  Chunk c is still the ballot of pairs [64 c, 64 c + 64), and chunk nch (no
+// pair: count 0) is still covered.
+constexpr int MARK_K = 4;
+static inline unsigned select_grid(int64_t NP) { const int64_t nw = (((NP + 63) >> 6) + 1 + MARK_K - 1) / MARK_K; return (unsigned)((nw + 3) / 4); }
 __global__ void __launch_bounds__(256) k_lazy_mark(LazyArgs a)
 {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
   const int64_t nch = (a.NP + 63) >> 6;
-  if ((i >> 6) > nch) return;                                   // (whole waves)
-  int f = 0;
-  if (i < a.NP) {
-    const PairRec pr = a.pairs[i];
-    if (pr.prof >= 0 && !a.done[i]) {
-      const unsigned long long bc = a.bestc[(size_t)a.sorted_uniq[pr.useq] * a.ncls + a.cls[pr.prof]];
-      f = bc == 0ull || a.b10[i] >= (uint32_t)(bc >> 40);
-      if (f) a.done[i] = 1;
-    }
+  const int64_t c0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * MARK_K;
+  if (c0 > nch) return;                                         // (whole waves)
+  PairRec pr[MARK_K]; uint8_t dn[MARK_K]; uint32_t b[MARK_K], t[MARK_K]; int cl[MARK_K]; bool live[MARK_K];
+#pragma unroll
+  for (int k = 0; k < MARK_K; k++) {
+    const int64_t i = (c0 + k) * 64 + lane;
+    pr[k].useq = 0; pr[k].prof = -1; pr[k].xj = -1; pr[k].L = 0; dn[k] = 1; b[k] = 0;
+    if (i < a.NP) { pr[k] = a.pairs[i]; dn[k] = a.done[i]; b[k] = a.b10[i]; }
   }
-  select_store(i, nch, f, a.smask, a.scnt);
+#pragma unroll
+  for (int k = 0; k < MARK_K; k++) {
+    live[k] = pr[k].prof >= 0 && !dn[k];
+    cl[k] = 0;
+    if (live[k]) cl[k] = a.cls[pr[k].prof];
+  }
+#pragma unroll
+  for (int k = 0; k < MARK_K; k++) { t[k] = 0u; if (live[k]) t[k] = a.thr[(size_t)pr[k].useq * a.ncls + cl[k]]; }
+#pragma unroll
+  for (int k = 0; k < MARK_K; k++) {
+    const int64_t c = c0 + k;
+    if (c > nch) break;                                         // (wave-uniform)
+    const int f = live[k] && b[k] >= t[k];
+    if (f) a.done[c * 64 + lane] = 1;
+    select_store(c * 64 + lane, nch, f, a.smask, a.scnt);
+  }
 }
 
 // selected pairs keep their profile segment and their order inside it (ascending length): out[seg_new[p] + rank inside p].
@@ -637,6 +693,15 @@ __global__ void __launch_bounds__(256) k_lazy_pending(const itsx_domain *__restr
   if (m && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(m)) atomicAdd(count, (unsigned long long)__builtin_popcountll(m));
 }
 
+__global__ void __launch_bounds__(64) k_pad_b10(const int64_t *__restrict__ seg_start, const int32_t *__restrict__ total, uint32_t *__restrict__ b10)
+{
+  const int64_t e = seg_start[blockIdx.x] + total[blockIdx.x] + threadIdx.x;      // (at most 63 records)
+  if (e < seg_start[blockIdx.x + 1]) b10[e] = 0u;
+}
+void launch_pad_b10(int32_t P, const int64_t *seg_start, const int32_t *total, uint32_t *b10, hipStream_t st)
+{
+  if (P > 0) hipLaunchKernelGGL(k_pad_b10, dim3((unsigned)P), dim3(64), 0, st, seg_start, total, b10);
+}
 void launch_lazy_bound(const LazyArgs &a, hipStream_t st)
 {
   if (a.NP > 0) hipLaunchKernelGGL(k_lazy_bound, dim3((unsigned)((a.NP + 255) / 256)), dim3(256), 0, st, a);
@@ -648,7 +713,10 @@ void launch_lazy_mark(const LazyArgs &a, int round, hipStream_t st)
     (void)hipMemsetAsync(a.smask, 0, (size_t)nch * sizeof(unsigned long long), st);
     if (a.ngroups > 0) hipLaunchKernelGGL(k_lazy_first, dim3((unsigned)((a.ngroups + 255) / 256)), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_select_count, dim3((unsigned)((nch + 1 + 255) / 256)), dim3(256), 0, st, a.smask, nch, a.scnt);
-  } else hipLaunchKernelGGL(k_lazy_mark, dim3((unsigned)((nch * 64 + 64 + 255) / 256)), dim3(256), 0, st, a);
+  } else {
+    if (a.nthr > 0) hipLaunchKernelGGL(k_lazy_thr, dim3((unsigned)((a.nthr + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_lazy_mark, dim3(select_grid(a.NP)), dim3(256), 0, st, a);
+  }
 }
 void launch_lazy_scatter(const PairRec *pairs, int64_t NP, const unsigned long long *smask, const int32_t *spos, const int64_t *seg_old, const int64_t *seg_new,
                          PairRec *out, hipStream_t st)
@@ -692,47 +760,72 @@ __global__ void __launch_bounds__(256) k_topup_keys(const PairRec *__restrict__ 
                                                     const int32_t *__restrict__ slot_of_prof, unsigned long long *__restrict__ smask, int32_t *__restrict__ scnt,
                                                     const int32_t *__restrict__ spos, unsigned long long *__restrict__ keys, int32_t *__restrict__ vals)
 {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
   const int64_t nch = (NP + 63) >> 6;
-  if ((i >> 6) > nch) return;
+  const int64_t c0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * MARK_K;
+  if (c0 > nch) return;
   if (!spos) {
-    int f = 0;
-    if (i < NP) {
-      const PairRec pr = pairs[i];
-      if (pr.prof >= 0 && pr.xj >= 0 && !done[i]) f = slot_of_prof[pr.prof] >= 0;
+    PairRec pr[MARK_K]; uint8_t dn[MARK_K];
+#pragma unroll
+    for (int k = 0; k < MARK_K; k++) {
+      const int64_t i = (c0 + k) * 64 + lane;
+      pr[k].useq = 0; pr[k].prof = -1; pr[k].xj = -1; pr[k].L = 0; dn[k] = 1;
+      if (i < NP) { pr[k] = pairs[i]; dn[k] = done[i]; }
     }
-    select_store(i, nch, f, smask, scnt);
+    int sl[MARK_K];
+#pragma unroll
+    for (int k = 0; k < MARK_K; k++) { sl[k] = -1; if (pr[k].prof >= 0 && pr[k].xj >= 0 && !dn[k]) sl[k] = slot_of_prof[pr[k].prof]; }
+#pragma unroll
+    for (int k = 0; k < MARK_K; k++) {
+      if (c0 + k > nch) break;
+      select_store((c0 + k) * 64 + lane, nch, sl[k] >= 0, smask, scnt);
+    }
     return;
   }
-  if ((i >> 6) >= nch) return;
-  const int lane = threadIdx.x & 63;
-  const unsigned long long m = smask[i >> 6];
-  if (!((m >> lane) & 1ull)) return;
-  const int32_t at = spos[i >> 6] + (int32_t)__popcll(m & ((1ull << lane) - 1ull));
-  const int sl = slot_of_prof[pairs[i].prof];
-  keys[at] = ((unsigned long long)sl << 32) | (unsigned long long)(0xFFFFFFFFu - b10[i]); vals[at] = (int32_t)i;
+  // (a chunk without a set bit costs its wave one 8-byte load)
+  unsigned long long m[MARK_K];
+#pragma unroll
+  for (int k = 0; k < MARK_K; k++) m[k] = c0 + k < nch ? smask[c0 + k] : 0ull;
+#pragma unroll
+  for (int k = 0; k < MARK_K; k++) {
+    if (!((m[k] >> lane) & 1ull)) continue;
+    const int64_t i = (c0 + k) * 64 + lane;                     // (< NP: a bit is set only for a pair)
+    const int32_t at = spos[c0 + k] + (int32_t)__popcll(m[k] & ((1ull << lane) - 1ull));
+    const int sl = slot_of_prof[pairs[i].prof];
+    keys[at] = ((unsigned long long)sl << 32) | (unsigned long long)(0xFFFFFFFFu - b10[i]); vals[at] = (int32_t)i;
+  }
 }
 __global__ void __launch_bounds__(256) k_topup_mark(const PairRec *__restrict__ pairs, int64_t NP, uint8_t *__restrict__ done, const uint32_t *__restrict__ b10,
                                                     const int32_t *__restrict__ slot_of_prof, const uint32_t *__restrict__ cutoff,
                                                     unsigned long long *__restrict__ smask, int32_t *__restrict__ scnt)
 {
   // cutoff[2 slot] > 0: the pairs whose bound is at least that (the best ones); cutoff[2 slot + 1] > 0: those whose bound is at most that
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
   const int64_t nch = (NP + 63) >> 6;
-  if ((i >> 6) > nch) return;
-  int f = 0;
-  if (i < NP) {
-    const PairRec pr = pairs[i];
-    if (pr.prof >= 0 && pr.xj >= 0 && !done[i]) {
-      const int sl = slot_of_prof[pr.prof];
-      if (sl >= 0) { const uint32_t hi = cutoff[2 * sl], lo = cutoff[2 * sl + 1], b = b10[i]; f = (hi > 0 && b >= hi) || (lo > 0 && b <= lo); }
-    }
-    if (f) done[i] = 1;
+  const int64_t c0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * MARK_K;
+  if (c0 > nch) return;
+  PairRec pr[MARK_K]; uint8_t dn[MARK_K]; uint32_t b[MARK_K];
+#pragma unroll
+  for (int k = 0; k < MARK_K; k++) {
+    const int64_t i = (c0 + k) * 64 + lane;
+    pr[k].useq = 0; pr[k].prof = -1; pr[k].xj = -1; pr[k].L = 0; dn[k] = 1; b[k] = 0;
+    if (i < NP) { pr[k] = pairs[i]; dn[k] = done[i]; b[k] = b10[i]; }
   }
-  select_store(i, nch, f, smask, scnt);
+  int sl[MARK_K];
+#pragma unroll
+  for (int k = 0; k < MARK_K; k++) { sl[k] = -1; if (pr[k].prof >= 0 && pr[k].xj >= 0 && !dn[k]) sl[k] = slot_of_prof[pr[k].prof]; }
+  uint32_t hi[MARK_K], lo[MARK_K];
+#pragma unroll
+  for (int k = 0; k < MARK_K; k++) { hi[k] = 0; lo[k] = 0; if (sl[k] >= 0) { hi[k] = cutoff[2 * sl[k]]; lo[k] = cutoff[2 * sl[k] + 1]; } }
+#pragma unroll
+  for (int k = 0; k < MARK_K; k++) {
+    if (c0 + k > nch) break;
+    const int f = (hi[k] > 0 && b[k] >= hi[k]) || (lo[k] > 0 && b[k] <= lo[k]);
+    if (f) done[(c0 + k) * 64 + lane] = 1;
+    select_store((c0 + k) * 64 + lane, nch, f, smask, scnt);
+  }
 }
 // (every marking launch covers chunk nch as well: its count, 0, makes the scan's last element the total)
-static inline unsigned select_grid(int64_t NP) { return (unsigned)((((NP + 63) >> 6) * 64 + 64 + 255) / 256); }
 void launch_topup_keys(const PairRec *pairs, int64_t NP, const uint8_t *done, const uint32_t *b10, const int32_t *slot_of_prof, unsigned long long *smask, int32_t *scnt,
                        const int32_t *spos, unsigned long long *keys, int32_t *vals, hipStream_t st)
 {

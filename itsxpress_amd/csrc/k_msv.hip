@@ -424,39 +424,42 @@ void launch_msv(const MsvArgs &a0, hipStream_t st, int lds_pad)
 // survivor list: (profile, sorted position) cells with the pass bit -> PairRec list grouped by
 // profile.  Three small passes: per-chunk counts, per-profile scan of chunk counts, fill.
 // a cell is on the list when it passed (bit 8) or when only a chain below it did (bit 9, k_share.hip: the pair runs in pass A for its
-// row states and is nobody's result: PairRec::xj = -1); real[p] counts the pairs that passed
-__global__ void __launch_bounds__(256) k_pair_count(const uint16_t *__restrict__ res, int32_t U, int32_t nchunks, int32_t *__restrict__ cnt, int32_t *__restrict__ real)
-{
-  __shared__ int32_t ws[4], wr[4];
-  const int p = blockIdx.y, c = blockIdx.x;
-  const int64_t base = (int64_t)p * U;
-  int32_t n = 0, nr = 0;
-  for (int i = threadIdx.x; i < CHUNK; i += 256) {
-    const int s = c * CHUNK + i;
-    if (s < U) { const int v = res[base + s]; n += (v & 0x300) != 0; nr += (v >> 8) & 1; }
-  }
-  for (int d = 32; d >= 1; d >>= 1) { n += __shfl_down(n, d, 64); nr += __shfl_down(nr, d, 64); }
-  if ((threadIdx.x & 63) == 0) { ws[threadIdx.x >> 6] = n; wr[threadIdx.x >> 6] = nr; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    cnt[(int64_t)p * nchunks + c] = ws[0] + ws[1] + ws[2] + ws[3];
-    const int32_t r = wr[0] + wr[1] + wr[2] + wr[3];
-    if (r) atomicAdd(&real[p], r);
-  }
-}
-// one block per profile: exclusive scan of its chunk counts (in place), total out
-__global__ void __launch_bounds__(256) k_chunk_scan(int32_t *__restrict__ cnt, int32_t nchunks, int32_t *__restrict__ total)
+// row states and is nobody's result: PairRec::xj = -1); real[p] counts the pairs that passed.  A chunk's two counts (at most CHUNK each)
+// travel in one word, cnt = on the list | passed << 16: the scan below sums the second into real[p], so that no chunk adds to its
+// profile's counter itself (3 000 chunks of a profile did, one after the other)
+static_assert(CHUNK == 2048 && CHUNK < (1 << 15), "k_pair_count packs two chunk counts into one word; k_pair_fill: four waves of eight steps");
+__global__ void __launch_bounds__(256) k_pair_count(const uint16_t *__restrict__ res, int32_t U, int32_t nchunks, int32_t *__restrict__ cnt)
 {
   __shared__ int32_t ws[4];
+  const int p = blockIdx.y, c = blockIdx.x;
+  const int64_t base = (int64_t)p * U;
+  int32_t v[CHUNK / 256];
+#pragma unroll
+  for (int i = 0; i < CHUNK / 256; i++) { const int s = c * CHUNK + i * 256 + (int)threadIdx.x; v[i] = s < U ? res[base + s] : 0; }
+  int32_t n = 0;
+#pragma unroll
+  for (int i = 0; i < CHUNK / 256; i++) n += ((v[i] & 0x300) != 0) + (((v[i] >> 8) & 1) << 16);
+  for (int d = 32; d >= 1; d >>= 1) n += __shfl_down(n, d, 64);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) cnt[(int64_t)p * nchunks + c] = ws[0] + ws[1] + ws[2] + ws[3];
+}
+// one block per profile: exclusive scan of its chunk counts (in place), total and real out
+__global__ void __launch_bounds__(256) k_chunk_scan(int32_t *__restrict__ cnt, int32_t nchunks, int32_t *__restrict__ total, int32_t *__restrict__ real)
+{
+  __shared__ int32_t ws[4], wr[4];
   __shared__ int32_t carry;
   int32_t *row = cnt + (int64_t)blockIdx.x * nchunks;
   if (threadIdx.x == 0) carry = 0;
   __syncthreads();
+  int32_t nr = 0;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   for (int b = 0; b < nchunks; b += 256) {
     const int i = b + threadIdx.x;
-    const int32_t v = i < nchunks ? row[i] : 0;
+    const int32_t both = i < nchunks ? row[i] : 0;
+    const int32_t v = both & 0xFFFF;
+    nr += both >> 16;
     int32_t inc = v;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     for (int d = 1; d < 64; d <<= 1) { const int32_t t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
     if (lane == 63) ws[wid] = inc;
     __syncthreads();
@@ -467,35 +470,48 @@ __global__ void __launch_bounds__(256) k_chunk_scan(int32_t *__restrict__ cnt, i
     if (threadIdx.x == 255) carry = off + inc;
     __syncthreads();
   }
-  if (threadIdx.x == 0) total[blockIdx.x] = carry;
+  for (int d = 32; d >= 1; d >>= 1) nr += __shfl_down(nr, d, 64);
+  if (lane == 0) wr[wid] = nr;
+  __syncthreads();
+  if (threadIdx.x == 0) { total[blockIdx.x] = carry; real[blockIdx.x] = wr[0] + wr[1] + wr[2] + wr[3]; }
 }
+// a wave takes CHUNK / 4 consecutive cells of its chunk, 64 at a time: a step's loads are lane-consecutive, its ballot ranks the cells
+// that are on the list, and their records leave as consecutive 16-byte stores.  The segment's padding up to the next multiple of 64
+// (prof < 0: all 0xFF) is written here too, by the profile's first block: nothing fills the list beforehand
 __global__ void __launch_bounds__(256) k_pair_fill(const uint16_t *__restrict__ res, int32_t U, int32_t nchunks, const int32_t *__restrict__ cnt,
-                                                   const int64_t *__restrict__ seg_start, const int32_t *__restrict__ ulen,
+                                                   const int64_t *__restrict__ seg_start, const int32_t *__restrict__ total, const int32_t *__restrict__ ulen,
                                                    PairRec *__restrict__ pairs)
 {
   __shared__ int32_t ws[4];
+  constexpr int STEPS = CHUNK / 256;
   const int p = blockIdx.y, c = blockIdx.x;
-  const int64_t base = (int64_t)p * U;
-  const int64_t out0 = seg_start[p] + cnt[(int64_t)p * nchunks + c];
-  // each thread owns 8 consecutive cells
-  const int s0 = c * CHUNK + threadIdx.x * 8;
-  uint16_t v[8]; int32_t n = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) { v[i] = (s0 + i < U) ? res[base + s0 + i] : 0; n += (v[i] & 0x300) != 0; }
-  int32_t inc = n;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  for (int d = 1; d < 64; d <<= 1) { const int32_t t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
-  if (lane == 63) ws[wid] = inc;
-  __syncthreads();
-  int32_t off = 0;
-  for (int w = 0; w < wid; w++) off += ws[w];
-  int64_t o = out0 + off + inc - n;
+  const int64_t base = (int64_t)p * U;
+  const int64_t seg0 = seg_start[p];
+  const int s0 = c * CHUNK + wid * (CHUNK / 4) + lane;
+  int32_t v[STEPS], len[STEPS];
 #pragma unroll
-  for (int i = 0; i < 8; i++)
+  for (int i = 0; i < STEPS; i++) { const int s = s0 + 64 * i; v[i] = s < U ? res[base + s] : 0; len[i] = s < U ? ulen[s] : 0; }
+  unsigned long long m[STEPS]; int32_t n = 0;
+#pragma unroll
+  for (int i = 0; i < STEPS; i++) { m[i] = __ballot((v[i] & 0x300) != 0); n += (int32_t)__popcll(m[i]); }
+  if (lane == 0) ws[wid] = n;
+  __syncthreads();
+  int64_t o = seg0 + cnt[(int64_t)p * nchunks + c];
+  for (int w = 0; w < wid; w++) o += ws[w];
+  const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (int i = 0; i < STEPS; i++) {
     if (v[i] & 0x300) {
-      PairRec pr; pr.useq = s0 + i; pr.prof = p; pr.xj = (v[i] & 0x100) ? (v[i] & 0xff) : -1; pr.L = ulen[s0 + i];
-      pairs[o++] = pr;
+      PairRec pr; pr.useq = s0 + 64 * i; pr.prof = p; pr.xj = (v[i] & 0x100) ? (v[i] & 0xff) : -1; pr.L = len[i];
+      pairs[o + __popcll(m[i] & below)] = pr;
     }
+    o += __popcll(m[i]);
+  }
+  if (c == 0 && wid == 0) {
+    const int64_t e = seg0 + total[p] + lane;                   // (at most 63 records)
+    if (e < seg_start[p + 1]) { PairRec pr; pr.useq = -1; pr.prof = -1; pr.xj = -1; pr.L = -1; pairs[e] = pr; }
+  }
 }
 __global__ void __launch_bounds__(256) k_fill_ulen(int32_t U, const int32_t *__restrict__ sorted_uniq, const int32_t *__restrict__ seed_read,
                                                    const int32_t *__restrict__ len, int32_t *__restrict__ ulen)
@@ -504,18 +520,18 @@ __global__ void __launch_bounds__(256) k_fill_ulen(int32_t U, const int32_t *__r
   if (s < U) ulen[s] = len[seed_read[sorted_uniq[s]]];
 }
 
-void launch_pair_count(const uint16_t *res, int32_t P, int32_t U, int32_t nchunks, int32_t *cnt, int32_t *real, hipStream_t st)
+void launch_pair_count(const uint16_t *res, int32_t P, int32_t U, int32_t nchunks, int32_t *cnt, hipStream_t st)
 {
-  hipLaunchKernelGGL(k_pair_count, dim3((unsigned)nchunks, (unsigned)P), dim3(256), 0, st, res, U, nchunks, cnt, real);
+  hipLaunchKernelGGL(k_pair_count, dim3((unsigned)nchunks, (unsigned)P), dim3(256), 0, st, res, U, nchunks, cnt);
 }
-void launch_chunk_scan(int32_t *cnt, int32_t P, int32_t nchunks, int32_t *total, hipStream_t st)
+void launch_chunk_scan(int32_t *cnt, int32_t P, int32_t nchunks, int32_t *total, int32_t *real, hipStream_t st)
 {
-  hipLaunchKernelGGL(k_chunk_scan, dim3((unsigned)P), dim3(256), 0, st, cnt, nchunks, total);
+  hipLaunchKernelGGL(k_chunk_scan, dim3((unsigned)P), dim3(256), 0, st, cnt, nchunks, total, real);
 }
-void launch_pair_fill(const uint16_t *res, int32_t P, int32_t U, int32_t nchunks, const int32_t *cnt, const int64_t *seg_start,
+void launch_pair_fill(const uint16_t *res, int32_t P, int32_t U, int32_t nchunks, const int32_t *cnt, const int64_t *seg_start, const int32_t *total,
                       const int32_t *ulen, PairRec *pairs, hipStream_t st)
 {
-  hipLaunchKernelGGL(k_pair_fill, dim3((unsigned)nchunks, (unsigned)P), dim3(256), 0, st, res, U, nchunks, cnt, seg_start, ulen, pairs);
+  hipLaunchKernelGGL(k_pair_fill, dim3((unsigned)nchunks, (unsigned)P), dim3(256), 0, st, res, U, nchunks, cnt, seg_start, total, ulen, pairs);
 }
 void launch_fill_ulen(int32_t U, const int32_t *sorted_uniq, const int32_t *seed_read, const int32_t *len, int32_t *ulen, hipStream_t st)
 {

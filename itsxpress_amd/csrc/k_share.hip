@@ -562,6 +562,62 @@ __global__ void __launch_bounds__(256) k_share_waves(int32_t nw, int32_t nseg, i
     if (f) atomicAdd(&lane_rows[2 * (blockIdx.x & 63) + 1], f);
   }
 }
+// the same list from woff / bnd alone, one thread per wave: prof, first, count.  rows = 0: k_fwd_bound<true, *> and k_bwd_bound take the
+// wave's last row from their lanes' chains themselves (k_lazy.hip); whoever needs it in the descriptor calls k_share_waves
+__global__ void __launch_bounds__(256) k_share_wavelist(int32_t nw, int32_t nseg, int32_t P, const int32_t *__restrict__ woff, const int64_t *__restrict__ bnd,
+                                                        WaveDesc *__restrict__ w)
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nw) return;
+  int lo = 0, hi = nseg * P;                                 // woff[lo] <= i < woff[hi]
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (woff[mid] <= i) lo = mid; else hi = mid; }
+  const int64_t first = bnd[lo] + (int64_t)(i - woff[lo]) * 64;
+  WaveDesc d;
+  d.prof = lo % P; d.first = first; d.count = (int32_t)min((int64_t)64, bnd[lo + P] - first); d.slab = 0; d.pad = 0; d.rows = 0;
+  w[i] = d;
+}
+// k_share_waves' three sums by chain, not by pair: chain k is on the list of every profile whose bit is set in need[k] (k_need_bits /
+// k_need_mark, k_join_need / k_need_res), n of them, and each of those pairs walks the same rows.  Forward: the rows from its segment's
+// depth to endrow[k] (nullptr: ulen[k]), and ulen[k] rows of the pair; backward: steps = endrow[k].  segk[t] = first position of
+// segment t (ascending, segk[nseg] = U)
+__global__ void __launch_bounds__(256) k_share_rows(int32_t U, int32_t W, const uint32_t *__restrict__ need, const int32_t *__restrict__ ulen, const int32_t *__restrict__ endrow,
+                                                    const int32_t *__restrict__ segk, int32_t nseg, const int32_t *__restrict__ seg_depth, int32_t B, int backward,
+                                                    unsigned long long *__restrict__ lane_rows)
+{
+  __shared__ unsigned long long sm[4][2];
+  const int k = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  unsigned long long mine = 0, full = 0;
+  if (k < U) {
+    unsigned long long n = 0;
+    for (int w = 0; w < W; w++) n += (unsigned long long)__popc(need[(size_t)k * W + w]);
+    if (n) {
+      if (backward) mine = n * (unsigned long long)endrow[k];
+      else if (k >= segk[0]) {
+        int lo = 0, hi = nseg;                               // segk[lo] <= k < segk[hi]: the last segment that starts at or before k
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (segk[mid] <= k) lo = mid; else hi = mid; }
+        const int L = ulen[k], rows = endrow ? endrow[k] : L;
+        mine = n * (unsigned long long)max(0, rows - seg_depth[lo] * B); full = n * (unsigned long long)L;
+      }
+    }
+  }
+  for (int o = 32; o >= 1; o >>= 1) { mine += __shfl_xor(mine, o, 64); full += __shfl_xor(full, o, 64); }
+  if (lane == 0) { sm[threadIdx.x >> 6][0] = mine; sm[threadIdx.x >> 6][1] = full; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long m = sm[0][0] + sm[1][0] + sm[2][0] + sm[3][0], f = sm[0][1] + sm[1][1] + sm[2][1] + sm[3][1];
+    if (m) atomicAdd(&lane_rows[2 * (blockIdx.x & 63)], m);
+    if (f) atomicAdd(&lane_rows[2 * (blockIdx.x & 63) + 1], f);
+  }
+}
+void launch_share_wavelist(int32_t nw, int32_t nseg, int32_t P, const int32_t *woff, const int64_t *bnd, WaveDesc *w, hipStream_t st)
+{
+  if (nw > 0) hipLaunchKernelGGL(k_share_wavelist, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, nw, nseg, P, woff, bnd, w);
+}
+void launch_share_rows(int32_t U, int32_t W, const uint32_t *need, const int32_t *ulen, const int32_t *endrow, const int32_t *segk, int32_t nseg, const int32_t *seg_depth,
+                       int32_t B, int backward, unsigned long long *lane_rows, hipStream_t st)
+{
+  if (U > 0) hipLaunchKernelGGL(k_share_rows, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, st, U, W, need, ulen, endrow, segk, nseg, seg_depth, B, backward, lane_rows);
+}
 void launch_share_bounds(const PairRec *pairs, const int64_t *seg_start, const int32_t *total, const int32_t *segk, int32_t nseg, int32_t P, int64_t *bnd, hipStream_t st)
 {
   hipLaunchKernelGGL(k_share_bounds, dim3(((nseg + 1) * P + 255) / 256), dim3(256), 0, st, pairs, seg_start, total, segk, nseg, P, bnd);
