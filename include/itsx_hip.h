@@ -66,6 +66,16 @@ typedef struct {
   int32_t dom_reported;   /* exp(lnP) * domZ <= domE, set by itsx_search_finalize */
 } itsx_domain;
 
+/* The optimal-accuracy alignment of one reported domain (itsx_align_domains).  Replaces the hmm from/to, ali from/to and acc
+ * columns (ll[15]..ll[18], ll[21]) of the --domtblout file of itsxpress/SeqSample.py:191-209, which are placeholders without it.
+ * acc = oasc / (1 + |jenv - ienv|), in double. */
+typedef struct {
+  int32_t hmm_from, hmm_to;   /* first and last match state of the alignment, 1-based */
+  int32_t ali_from, ali_to;   /* the target residues they emit, 1-based, inside [ienv, jenv] */
+  float   oasc;               /* expected number of correctly aligned residues (the optimal-accuracy score) */
+  int32_t aligned;            /* 1: the row was aligned; 0: it was not (not reported), everything else is zero */
+} itsx_alignment;             /* 24 bytes */
+
 /* per (representative, profile) filter trace for parity tests; only pairs past the MSV filter */
 typedef struct {
   int64_t rep; int32_t prof;
@@ -618,6 +628,19 @@ int itsx_set_domz(itsx_ctx *ctx, const int64_t *domZ /* same */);
 int itsx_search_finalize(itsx_ctx *ctx, double domE);
 int64_t itsx_num_domains(const itsx_ctx *ctx);
 int itsx_get_domains(const itsx_ctx *ctx, itsx_domain *rows /* [itsx_num_domains] */);
+/* ---- the hmm / ali / acc columns of the --domtblout file of itsxpress/SeqSample.py:191-209 (opt-in; a restatement of hmmsearch's
+ * optimal-accuracy stage, parity unpinned: DESIGN.md 2).
+ * itsx_align_domains: after itsx_search_finalize, aligns every resident row with dom_reported == 1 (unihit local mode over its
+ *   envelope, the length model at the target's length; the posteriors are the ones the row's null2 correction was summed from).
+ *   n_aligned = rows aligned (a pair a lazy search evaluated twice counts twice), ms_kernels = device time of the three sweeps;
+ *   either may be NULL.  ITSX_E_ARG before a finalize; where itsx_get_domains refuses, the same code; an envelope whose
+ *   posteriors are not finite is ITSX_E_UNSUPPORTED with the row named.  ITSX_ALIGN_SLAB_MB caps the slab of one batch of waves.
+ * itsx_get_alignments: out[k] belongs to row k of itsx_get_domains (aligned = 0, all zero, where that row is not reported).
+ *   ITSX_E_ARG when no alignments exist for the current finalize: a new read set, itsx_derep / itsx_cluster*, itsx_search,
+ *   itsx_search_finalize, itsx_lazy_complete, itsx_set_domz and itsx_debug_set_domains drop them.
+ * itsx_write_domtbl prints the real columns for every aligned row while alignments exist, and today's placeholders otherwise. */
+int itsx_align_domains(itsx_ctx *ctx, int64_t *n_aligned, float *ms_kernels);
+int itsx_get_alignments(const itsx_ctx *ctx, itsx_alignment *out /* [itsx_num_domains] */);
 int64_t itsx_num_pairtraces(const itsx_ctx *ctx);
 /* row_size = sizeof(itsx_pairtrace) as the CALLER was compiled: a library built from other sources is refused (ITSX_E_ARG) instead of
  * writing rows of another stride */
@@ -668,6 +691,12 @@ int itsx_write_derep_arrays(const char *uc_path, const char *rep_path, int64_t n
 int itsx_write_domtbl_arrays(const char *path, const itsx_domain *rows, int64_t n_rows, int64_t Z, const int64_t *domz, int32_t n_profiles,
                              const char *prof_names, const int64_t *prof_name_offsets, const int32_t *prof_M, const float *prof_tau,
                              const float *prof_lambda, const char *target_names, const int64_t *target_name_offsets);
+/* itsx_write_domtbl_arrays with the hmm / ali / acc columns of the --domtblout file of itsxpress/SeqSample.py:191-209 taken from
+ * ali[n_rows], parallel to rows, wherever ali[i].aligned == 1; ali == NULL: the file of itsx_write_domtbl_arrays, byte for byte */
+int itsx_write_domtbl_arrays_ali(const char *path, const itsx_domain *rows, int64_t n_rows, int64_t Z, const int64_t *domz, int32_t n_profiles,
+                                 const char *prof_names, const int64_t *prof_name_offsets, const int32_t *prof_M, const float *prof_tau,
+                                 const float *prof_lambda, const char *target_names, const int64_t *target_name_offsets,
+                                 const itsx_alignment *ali);
 const char *itsx_writers_last_error(void);
 int itsx_profile_params(const itsx_ctx *ctx, int i, int32_t *M, float *evparam6);
 int itsx_get_unique_seqs(itsx_ctx *ctx, char *bases, int64_t cap, int64_t *offsets);

@@ -71,6 +71,28 @@ def _winners_from_env():
     return os.environ.get("ITSXPRESS_DOMTBL", "").strip().lower() == "winners"
 
 
+def _domtbl_ali_from_env():
+    return os.environ.get("ITSXPRESS_DOMTBL_ALI", "").strip() not in ("", "0")
+
+
+def _domtbl_ali_wanted(sample, eng, fast) -> bool:
+    """ITSXPRESS_DOMTBL_ALI=1 (or `domtbl_ali` on the sample): domtbl.txt gets hmmsearch's hmm / ali coordinates and acc from the
+    engine's optimal-accuracy stage (Engine.align_domains).  One context writing the file only: the multi-GPU and streamed drivers
+    compose the file from gathered rows and keep today's columns, and arrays mode writes no file."""
+    v = getattr(sample, "domtbl_ali", None)
+    want = _domtbl_ali_from_env() if v is None else bool(v)
+    if not want:
+        return False
+    if fast:
+        logger.warning("ITSXPRESS_DOMTBL_ALI is ignored with ITSXPRESS_ARRAYS=1: no domtbl.txt is written")
+        return False
+    if not isinstance(eng, Engine):
+        logger.warning("ITSXPRESS_DOMTBL_ALI is ignored with ITSXPRESS_GPUS > 1 / ITSXPRESS_STREAM=1: domtbl.txt keeps the envelope "
+                       "coordinates in its hmm / ali columns and acc 0.00")
+        return False
+    return True
+
+
 class SeqSample:
     """Base class: dereplicate -> search, as the reference's SeqSample (SeqSample.py:18-225)."""
 
@@ -87,6 +109,7 @@ class SeqSample:
         self.gpus: Optional[int] = None          # None: ITSXPRESS_GPUS (default 1)
         self.fast: Optional[bool] = None         # None: ITSXPRESS_ARRAYS (default off)
         self.domtbl: Optional[str] = None        # None: ITSXPRESS_DOMTBL ("winners": files as ever, domtbl.txt = the rows that can win)
+        self.domtbl_ali: Optional[bool] = None   # None: ITSXPRESS_DOMTBL_ALI (domtbl.txt with hmmsearch's hmm / ali coordinates and acc)
 
     # -- engine plumbing -------------------------------------------------------------
     @property
@@ -237,10 +260,14 @@ class SeqSample:
             eng.set_rows_mode("lazy" if (fast or winners) else "full")
             eng.search(T=10.0, F1=1e-6, F2=1e-6, F3=1e-6)
             eng.finalize(domE=10.0)
+            ali = _domtbl_ali_wanted(self, eng, fast)
             if fast:
                 self.dom_file = EngineTable(self.dom_file, eng, "domtbl")
             else:
                 eng.set_kept_rows(winners)
+                if ali:
+                    r = eng.align_domains()
+                    logging.info("itsx_hip align: %d reported domains aligned (%.1f ms of kernels)", r["n_aligned"], r["ms_kernels"])
                 eng.write_domtbl(self.dom_file)
         except EngineError as e:
             logging.exception("Could not perform ITS identification with the HIP engine: %s", e)

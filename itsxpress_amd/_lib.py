@@ -32,6 +32,8 @@ DOMAIN_DTYPE = np.dtype([("rep", "<i8"), ("prof", "<i4"), ("tlen", "<i4"), ("ien
                          ("domcorrection", "<f4"), ("dombias", "<f4"), ("bitscore", "<f4"), ("lnP", "<f8"),
                          ("seq_score", "<f4"), ("seq_bias", "<f4"), ("seq_reported", "<i4"),
                          ("dom_reported", "<i4")], align=True)
+ALIGNMENT_DTYPE = np.dtype([("hmm_from", "<i4"), ("hmm_to", "<i4"), ("ali_from", "<i4"), ("ali_to", "<i4"), ("oasc", "<f4"),
+                            ("aligned", "<i4")], align=True)                        # itsx_alignment (itsx_get_alignments)
 LAZY_PAIR_DTYPE = np.dtype([("rep", "<i8"), ("prof", "<i4"), ("L", "<i4"), ("xj", "<i4"), ("fb", "<f4"), ("b10", "<u4"), ("done", "<i4"),
                             ("nullsc", "<f4"), ("lazy_c", "<f4")], align=True)      # itsx_lazy_pair (itsx_debug_lazy_pairs)
 TRACE_DTYPE = np.dtype([("rep", "<i8"), ("prof", "<i4"), ("msv_xj", "<i4"), ("pass_msv", "<i4"),
@@ -104,7 +106,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_parse_pairs_device", "itsx_parse_pairs_fetch", "itsx_debug_parse_pairs_host", "itsx_debug_pair_pass_host",
            "itsx_debug_set_domains", "itsx_debug_get_rows",
            "itsx_debug_scan", "itsx_debug_select", "itsx_debug_region_keys", "itsx_debug_lazy_pairs",
-           "itsx_set_sample_sharing", "itsx_sample_sharing_info", "itsx_sample_sharing_times", "itsx_debug_sample_classes"]
+           "itsx_set_sample_sharing", "itsx_sample_sharing_info", "itsx_sample_sharing_times", "itsx_debug_sample_classes",
+           "itsx_align_domains", "itsx_get_alignments", "itsx_write_domtbl_arrays_ali"]
 
 
 def lib():
@@ -194,6 +197,7 @@ def lib():
         "itsx_unique_keys128": (i32, [vp, C.c_uint64, C.c_uint64, i64, vp]),
         "itsx_write_derep_arrays": (i32, [cp, cp, i64, vp, vp, vp, vp, vp, vp, vp, i64]),
         "itsx_write_domtbl_arrays": (i32, [cp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "itsx_write_domtbl_arrays_ali": (i32, [cp, vp, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "itsx_writers_last_error": (cp, []),
         "itsx_profile_params": (i32, [vp, i32, vp, vp]),
         "itsx_get_unique_seqs": (i32, [vp, vp, i64, vp]),
@@ -225,6 +229,8 @@ def lib():
         "itsx_search_finalize": (i32, [vp, f64]),
         "itsx_num_domains": (i64, [vp]),
         "itsx_get_domains": (i32, [vp, vp]),
+        "itsx_align_domains": (i32, [vp, vp, vp]),
+        "itsx_get_alignments": (i32, [vp, vp]),
         "itsx_num_pairtraces": (i64, [vp]),
         "itsx_get_pairtraces": (i32, [vp, vp, i64]),
         "itsx_trim_coords": (i32, [vp, cp, cp, vp, vp, vp, vp]),

@@ -35,7 +35,7 @@ import numpy as np
 
 from .engine import Engine
 from ._lib import EngineError
-from .SeqSample import _REGION_PREFIX, _fast_from_env, _winners_from_env
+from .SeqSample import _REGION_PREFIX, _domtbl_ali_wanted, _fast_from_env, _winners_from_env
 from .definitions import maxmismatches
 
 
@@ -274,6 +274,8 @@ class SampleBatch:
                 eng.search(T=10.0, F1=1e-6, F2=1e-6, F3=1e-6)
                 eng.finalize(domE=10.0)
                 eng.set_kept_rows(winners)
+                if _domtbl_ali_wanted(self, eng, False):      # every sample's reported rows in one pass; the writer picks the sample's
+                    eng.align_domains()
                 for i, s in enumerate(self.samples):
                     s.dom_file = os.path.join(self._dir(i), "domtbl.txt")
                     eng.select_sample(i)

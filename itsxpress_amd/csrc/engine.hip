@@ -442,6 +442,13 @@ struct itsx_ctx {
   DBuf<LenTables> d_lt;
   std::vector<int64_t> domz;
   std::vector<itsx_domain> h_dom;        // valid rows, domtblout order
+  // itsx_align_domains: the alignments of the reported rows of the current finalize, ordered by (profile, representative, domain) for
+  // the lookup of itsx_get_alignments / itsx_write_domtbl; whatever changes the rows or their dom_reported drops them (drop_alignments)
+  struct AliRow { int32_t prof, dom_idx; int64_t rep; itsx_alignment a; };
+  bool have_ali = false; std::vector<AliRow> h_ali;
+  void drop_alignments() { have_ali = false; std::vector<AliRow>().swap(h_ali); }
+  bool alignments_live() const { return have_ali && have_search && have_final; }
+  DBuf<PairRec> w_al_pairs; DBuf<RegionRec> w_al_regions; DBuf<RegionOut> w_al_rout; DBuf<int32_t> w_al_rep; DBuf<WaveDesc> w_al_waves; DBuf<itsx_alignment> w_al_out;
   std::vector<itsx_pairtrace> h_trace;
 
   // ---- persistent work buffers (see DBuf)
@@ -2274,7 +2281,7 @@ static int search_active(itsx_ctx *ctx, double T, double F1, double F2, double F
   hipStream_t st = ctx->st;
   const int P = ctx->P, G = ctx->G, Ppad = G * 64, U = ctx->U_active;
   ctx->T = T;
-  ctx->h_dom.clear(); ctx->h_trace.clear(); ctx->trace_sorted = false;
+  ctx->h_dom.clear(); ctx->drop_alignments(); ctx->h_trace.clear(); ctx->trace_sorted = false;
   ctx->domz.assign((size_t)P * ctx->S, 0);
   itsx_stats &S = ctx->stats;
   S.n_pairs = (int64_t)U * P; S.n_past_msv = S.n_past_bias = S.n_past_fwd = S.n_regions = S.n_multidomain = S.n_domains = S.n_domain_overflow = 0;
@@ -3747,7 +3754,7 @@ int itsx_lazy_pending_profiles(const itsx_ctx *ctx, int32_t *flags)
   return ITSX_OK;
 }
 int itsx_set_partial_coords(itsx_ctx *ctx, int on) { CTXCHK(ctx); ctx->partial_coords = on != 0; return ITSX_OK; }
-int itsx_set_kept_rows(itsx_ctx *ctx, int on) { CTXCHK(ctx); if (ctx->kept_rows != (on != 0)) ctx->h_dom.clear(); ctx->kept_rows = on != 0; return ITSX_OK; }
+int itsx_set_kept_rows(itsx_ctx *ctx, int on) { CTXCHK(ctx); if (ctx->kept_rows != (on != 0)) { ctx->h_dom.clear(); ctx->drop_alignments(); } ctx->kept_rows = on != 0; return ITSX_OK; }
 // flags[n_unique]: 1 where an undecided row could still change the representative's coordinates (the rows itsx_lazy_pending counts)
 int itsx_lazy_pending_uniques(itsx_ctx *ctx, uint8_t *flags)
 {
@@ -3794,7 +3801,7 @@ int itsx_lazy_complete(itsx_ctx *ctx, const int32_t *flags)
       ctx->domz_loc[z] = ctx->domz_ub_loc[z] = dz32[z];
       if (!ctx->domz_exchanged) ctx->domz[z] = ctx->domz_ub[z] = dz32[z];
     }
-  ctx->have_final = false;
+  ctx->have_final = false; ctx->drop_alignments();
   ctx->stats.n_lazy_completed_profiles += (int64_t)ctx->h_plist.size();
   ctx->stats.n_rows_resident = 0;
   for (int64_t r : ctx->dom_n) ctx->stats.n_rows_resident += r;
@@ -3819,6 +3826,7 @@ int itsx_set_domz(itsx_ctx *ctx, const int64_t *domZ)
   for (size_t p = 0; p < ctx->domz.size(); p++) ctx->domz[p] = domZ[p];
   if (ctx->lazy) for (size_t p = 0; p < ctx->domz_ub.size(); p++) ctx->domz_ub[p] = domZ[ctx->domz.size() + p];
   ctx->domz_on_device = false; ctx->domz_exchanged = true;
+  ctx->drop_alignments();
   return ITSX_OK;
 }
 int64_t itsx_domz_count(const itsx_ctx *ctx) { return ctx ? (int64_t)ctx->domz.size() * (ctx->lazy ? 2 : 1) : -1; }
@@ -3870,7 +3878,7 @@ int itsx_debug_set_domains(itsx_ctx *ctx, const itsx_domain *rows, int64_t n_row
   hipStream_t st = ctx->st;
   const size_t m = (size_t)ctx->P * ctx->S;
   ctx->switches_at_search = sw_report();
-  ctx->searched_holders = false; ctx->h_dom.clear(); ctx->h_trace.clear(); ctx->trace_sorted = false;
+  ctx->searched_holders = false; ctx->h_dom.clear(); ctx->drop_alignments(); ctx->h_trace.clear(); ctx->trace_sorted = false;
   ctx->domz.assign(m, 0); ctx->domz_ub.assign(m, 0); ctx->domz_loc.assign(m, 0); ctx->domz_ub_loc.assign(m, 0);
   ctx->npairs_padded = 0; ctx->dom_n.clear(); ctx->n_chunks = n_segs;
   ctx->have_search = false; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->topup.list_live = false; ctx->injected = true;
@@ -4130,7 +4138,7 @@ int itsx_search_finalize(itsx_ctx *ctx, double domE)
   if (ctx->injected && ctx->lazy && !ctx->domz_exchanged)
     SET_ERR(ctx, ITSX_E_ARG, "itsx_search_finalize: a lazy row table that was handed in (itsx_debug_set_domains) has no counters of its own: give both bounds with itsx_set_domz first");
   StageTimer tm(ctx->st);
-  ctx->h_dom.clear();
+  ctx->h_dom.clear(); ctx->drop_alignments();
   auto check_compaction = [&](const std::vector<int64_t> &z) -> int {       // the rows were thinned out under two assumptions: check them against what finalize was given
     int64_t zmax = 0;
     for (int64_t v : z) zmax = std::max(zmax, v);
@@ -4279,6 +4287,153 @@ int itsx_get_domains(const itsx_ctx *ctx, itsx_domain *rows)
   const int rc = fetch_domains(ctx);
   if (rc != ITSX_OK) return rc;
   if (!ctx->h_dom.empty()) memcpy(rows, ctx->h_dom.data(), ctx->h_dom.size() * sizeof(itsx_domain));
+  return ITSX_OK;
+}
+
+// ---- the optimal-accuracy alignments of the reported rows (opt-in: nothing of the search is touched)
+// out[k] = the alignment of ctx->h_dom[k], looked up by (profile, representative, domain); all zero where there is none
+static void alignments_of_rows(const itsx_ctx *ctx, itsx_alignment *out)
+{
+  const auto &A = ctx->h_ali;
+  for (size_t k = 0; k < ctx->h_dom.size(); k++) {
+    const itsx_domain &d = ctx->h_dom[k];
+    itsx_alignment a{};
+    if (d.dom_reported == 1) {
+      size_t lo = 0, hi = A.size();
+      while (lo < hi) {
+        const size_t mid = (lo + hi) >> 1;
+        const itsx_ctx::AliRow &r = A[mid];
+        const bool less = r.prof != d.prof ? r.prof < d.prof : r.rep != d.rep ? r.rep < d.rep : r.dom_idx < d.dom_idx;
+        if (less) lo = mid + 1; else hi = mid;
+      }
+      if (lo < A.size() && A[lo].prof == d.prof && A[lo].rep == d.rep && A[lo].dom_idx == d.dom_idx) a = A[lo].a;
+    }
+    out[k] = a;
+  }
+}
+
+int itsx_align_domains(itsx_ctx *ctx, int64_t *n_aligned, float *ms_kernels)
+{
+  CTXCHK(ctx);
+  if (!ctx->have_search || !ctx->have_final) SET_ERR(ctx, ITSX_E_ARG, "itsx_align_domains is called after itsx_search_finalize");
+  { const int rc = fetch_domains(ctx); if (rc != ITSX_OK) return rc; }       // (refuses where the row table is refused)
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->drop_alignments();
+  hipStream_t st = ctx->st;
+  const int P = ctx->P;
+  // the work list: every resident row with dom_reported == 1, grouped by profile (the unrolled kernels' profiles first), ascending
+  // envelope length.  A row carries all the stage needs; it is checked against the read set before anything indexes with it.
+  std::vector<int32_t> rlen;
+  if ((int64_t)ctx->h_len.size() == ctx->N) rlen = ctx->h_len;
+  else { rlen.resize((size_t)ctx->N); if (ctx->N > 0) HIPCHK(hipMemcpy(rlen.data(), ctx->d_len.p, (size_t)ctx->N * 4, hipMemcpyDeviceToHost)); }
+  std::vector<itsx_ctx::AliRow> items;
+  std::vector<int32_t> iL, iLd;
+  {
+    std::vector<itsx_domain> seg;
+    for (size_t c = 0; c < ctx->dom_n.size(); c++) {
+      if (ctx->dom_n[c] <= 0) continue;
+      seg.resize((size_t)ctx->dom_n[c]);
+      HIPCHK(hipMemcpy(seg.data(), ctx->dom_bufs[c]->p, seg.size() * sizeof(itsx_domain), hipMemcpyDeviceToHost));
+      for (size_t r = 0; r < seg.size(); r++) {
+        const itsx_domain &d = seg[r];
+        if (d.dom_idx < 0 || d.dom_reported != 1) continue;
+        const bool ok = d.prof >= 0 && d.prof < P && d.rep >= 0 && d.rep < ctx->U && d.ienv >= 1 && d.jenv >= d.ienv && d.jenv <= d.tlen &&
+                        ctx->h_seed_read[(size_t)d.rep] >= 0 && ctx->h_seed_read[(size_t)d.rep] < ctx->N && d.tlen == rlen[(size_t)ctx->h_seed_read[(size_t)d.rep]];
+        if (!ok) SET_ERR(ctx, ITSX_E_ARG, "itsx_align_domains: row " + std::to_string(r) + " of segment " + std::to_string(c) + " does not name an envelope of a loaded read (profile " +
+                         std::to_string(d.prof) + ", representative " + std::to_string(d.rep) + ", envelope " + std::to_string(d.ienv) + ".." + std::to_string(d.jenv) + " of " + std::to_string(d.tlen) + ")");
+        itsx_ctx::AliRow it{}; it.prof = d.prof; it.dom_idx = d.dom_idx; it.rep = d.rep;
+        it.a.ali_from = d.ienv; it.a.ali_to = d.jenv; it.a.hmm_from = d.tlen;             // (carried to the device lists below)
+        items.push_back(it);
+      }
+    }
+  }
+  const int64_t NI = (int64_t)items.size();
+  float ms = 0.0f;
+  if (NI > 0) {
+    std::sort(items.begin(), items.end(), [&](const itsx_ctx::AliRow &x, const itsx_ctx::AliRow &y) {
+      const int gx = ctx->generic_q[(size_t)x.prof], gy = ctx->generic_q[(size_t)y.prof];
+      if (gx != gy) return gx < gy;
+      if (x.prof != y.prof) return x.prof < y.prof;
+      const int lx = x.a.ali_to - x.a.ali_from, ly = y.a.ali_to - y.a.ali_from;
+      if (lx != ly) return lx < ly;
+      if (x.rep != y.rep) return x.rep < y.rep;
+      return x.dom_idx < y.dom_idx;
+    });
+    std::vector<PairRec> pairs((size_t)NI); std::vector<RegionRec> regions((size_t)NI); std::vector<int32_t> reps((size_t)NI);
+    for (int64_t k = 0; k < NI; k++) {
+      const itsx_ctx::AliRow &it = items[(size_t)k];
+      pairs[(size_t)k] = PairRec{(int32_t)k, it.prof, 0, it.a.hmm_from};
+      regions[(size_t)k] = RegionRec{(int32_t)k, it.a.ali_from, it.a.ali_to, 0};
+      reps[(size_t)k] = (int32_t)it.rep;
+    }
+    std::vector<WaveDesc> waves; std::vector<char> wgen;
+    for (int64_t k = 0; k < NI;) {
+      int64_t e = k + 1;
+      while (e < NI && e - k < 64 && items[(size_t)e].prof == items[(size_t)k].prof) e++;
+      WaveDesc w{}; w.prof = items[(size_t)k].prof; w.first = k; w.count = (int32_t)(e - k);
+      w.rows = regions[(size_t)e - 1].jenv - regions[(size_t)e - 1].ienv + 2;              // the wave's longest envelope + 1
+      waves.push_back(w); wgen.push_back(ctx->generic_q[(size_t)w.prof]);
+      k = e;
+    }
+    const int NW = (int)waves.size();
+    HIPCHK(upload(ctx->w_al_pairs, pairs, st)); HIPCHK(upload(ctx->w_al_regions, regions, st)); HIPCHK(upload(ctx->w_al_rep, reps, st));
+    HIPCHK(ctx->w_al_rout.alloc((size_t)NI)); HIPCHK(ctx->w_al_out.alloc((size_t)NI)); HIPCHK(ctx->w_al_waves.alloc((size_t)NW));
+    HIPCHK(hipMemsetAsync(ctx->w_al_rout.p, 0, (size_t)NI * sizeof(RegionOut), st));
+    HIPCHK(hipMemsetAsync(ctx->w_al_out.p, 0, (size_t)NI * sizeof(itsx_alignment), st));
+    // the slab is sized from the envelopes of a batch of waves, under a budget: as many batches as it takes, one wave at the least
+    const int64_t row_floats = 104 * 64;
+    double mb = 4096.0;
+    if (const char *e = sw_get("ITSX_ALIGN_SLAB_MB")) { const double v = atof(e); if (v > 0.0) mb = v; }
+    const int64_t budget = std::max<int64_t>((int64_t)(mb * 1048576.0) / (row_floats * 4), 1);
+    DBuf<float> &d_eslab = ctx->w_eslab;
+    LazyTimers lt(st);
+    int w0 = 0;
+    while (w0 < NW) {
+      int w1 = w0; int64_t r = 0;
+      while (w1 < NW && wgen[(size_t)w1] == wgen[(size_t)w0] && (w1 == w0 || r + waves[(size_t)w1].rows <= budget)) { waves[(size_t)w1].slab = r; r += waves[(size_t)w1].rows; w1++; }
+      if ((int64_t)(d_eslab.cap / (size_t)row_floats) < r && d_eslab.alloc((size_t)(r * row_floats)) != hipSuccess) {
+        (void)hipGetLastError();
+        SET_ERR(ctx, ITSX_E_NOMEM, "itsx_align_domains: no device memory for a slab of " + std::to_string(r) + " rows (lower ITSX_ALIGN_SLAB_MB)");
+      }
+      HIPCHK(hipMemcpyAsync(ctx->w_al_waves.p + w0, waves.data() + w0, (size_t)(w1 - w0) * sizeof(WaveDesc), hipMemcpyHostToDevice, st));
+      EnvArgs a{};
+      a.rd = ctx->rd; a.sorted_uniq = ctx->w_al_rep.p; a.seed_read = ctx->d_seed_read.p; a.prof = ctx->d_prof.p; a.lt = ctx->d_lt.p;
+      a.pairs = ctx->w_al_pairs.p; a.regions = ctx->w_al_regions.p; a.rout = ctx->w_al_rout.p; a.waves = ctx->w_al_waves.p; a.slab = d_eslab.p;
+      { const size_t t = lt.begin(&ms); launch_align(a, ctx->w_al_out.p, w1 - w0, w0, wgen[(size_t)w0], st); lt.end(t); }
+      HIPCHK(hipStreamSynchronize(st));            // (the next batch's wave list and slab are the same buffers)
+      w0 = w1;
+    }
+    lt.collect();
+    std::vector<itsx_alignment> res((size_t)NI);
+    HIPCHK(hipMemcpy(res.data(), ctx->w_al_out.p, (size_t)NI * sizeof(itsx_alignment), hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < NI; k++) {
+      itsx_ctx::AliRow &it = items[(size_t)k];
+      const itsx_alignment &o = res[(size_t)k];
+      const bool sane = o.aligned == 1 && o.hmm_from >= 1 && o.hmm_from <= o.hmm_to && o.hmm_to <= ctx->profs[(size_t)it.prof].M &&
+                        o.ali_from >= it.a.ali_from && o.ali_from <= o.ali_to && o.ali_to <= it.a.ali_to && std::isfinite(o.oasc);
+      if (!sane) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "itsx_align_domains: the posteriors of an envelope are unusable: profile " + ctx->profs[(size_t)it.prof].name + ", representative " +
+                         std::to_string(it.rep) + ", domain " + std::to_string(it.dom_idx) + ", envelope " + std::to_string(it.a.ali_from) + ".." + std::to_string(it.a.ali_to));
+      it.a = o;
+    }
+    std::sort(items.begin(), items.end(), [](const itsx_ctx::AliRow &x, const itsx_ctx::AliRow &y) {
+      if (x.prof != y.prof) return x.prof < y.prof;
+      if (x.rep != y.rep) return x.rep < y.rep;
+      return x.dom_idx < y.dom_idx;
+    });
+  }
+  ctx->h_ali.swap(items);
+  ctx->have_ali = true;
+  if (n_aligned) *n_aligned = NI;
+  if (ms_kernels) *ms_kernels = ms;
+  return ITSX_OK;
+}
+
+int itsx_get_alignments(const itsx_ctx *ctx, itsx_alignment *out)
+{
+  CTXCHK(ctx && out);
+  if (!ctx->alignments_live()) SET_ERR(ctx, ITSX_E_ARG, "itsx_get_alignments: no alignments for the current finalize (itsx_align_domains comes after itsx_search_finalize)");
+  { const int rc = fetch_domains(ctx); if (rc != ITSX_OK) return rc; }
+  alignments_of_rows(ctx, out);
   return ITSX_OK;
 }
 
@@ -6499,6 +6654,8 @@ int itsx_write_domtbl(const itsx_ctx *ctx, const char *path)
   t.Z = Zs.data(); t.domz = ctx->domz.data();
   if (ctx->S > 1) { t.usample = ctx->h_usample.data(); t.sel = ctx->sel_sample; }
   t.seed_read = ctx->h_seed_read.data(); t.targets = read_labels(ctx);
+  std::vector<itsx_alignment> ali;
+  if (ctx->alignments_live()) { ali.resize(ctx->h_dom.size()); alignments_of_rows(ctx, ali.data()); t.ali = ali.data(); }
   std::string err;
   const int rc = itsx::write_domtbl(path, t, err);
   if (rc != ITSX_OK) SET_ERR(ctx, rc, err);

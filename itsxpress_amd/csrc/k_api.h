@@ -568,6 +568,9 @@ struct EnvArgs {
   float *slab;                  // per wave: [row][2 passes][96][64]
 };
 void launch_envelopes(const EnvArgs &a, int nwaves, int wave0, int generic_q, hipStream_t st);
+// itsx_align_domains: k_env_fwd and k_env_bwd as above, then the optimal-accuracy sweep; out[i] = the alignment of envelope regions[i]
+// (aligned = 1, or -1 where the envelope's posteriors are unusable)
+void launch_align(const EnvArgs &a, itsx_alignment *out, int nwaves, int wave0, int generic_q, hipStream_t st);
 
 // ---- k_ensemble.hip: multidomain regions (stochastic traceback clustering)
 constexpr int MRV = 52;            // float4 vectors per matrix row: {M D I B} of node 0 (zeros) .. 48 | (E N J B) | (E J C SCALE) | -

@@ -977,6 +977,201 @@ __global__ void __launch_bounds__(64, 2) k_env_post(EnvArgs a, int wave0)
 }
 
 // =========================================================================================
+// K3b: the optimal-accuracy alignment of one envelope per lane (itsx_align_domains; opt-in, after the search).  Replaces what
+// hmmsearch runs after the envelope's null2 (p7_OptimalAccuracy + p7_OATrace) for the hmm / ali / acc columns of the --domtblout
+// file of itsxpress/SeqSample.py:191-209.  k_env_fwd and k_env_bwd run first, unchanged; this is the third sweep: Forward again
+// as in k_env_post, every row's posteriors formed by k_env_post's own expression, and in the same step one row of
+//   A_M(i,k) = pM + max{A_B(i-1), A_M(i-1,k-1), A_I(i-1,k-1), A_D(i-1,k-1)}   A_I(i,k) = pI + max{A_M(i-1,k), A_I(i-1,k)}
+//   A_D(i,k) = max{A_M(i,k-1), A_D(i,k-1)}   A_E = max_k A_M   A_N += pN   A_B = A_N   A_C = max{A_C + pC, A_E}
+// over the transitions whose probability is not zero.  It is fwd_row in the (max, +) semiring with weights 0 / -inf, in the same
+// striped layout: the D->D chain is a maximum, so its four passes give the same bits as any other order.
+//   * the OA row (M, I, D: 3 x Q float4 per lane) lives in LDS, [q][lane] (conflict-free b128); 36 KB per wave, so 4 waves per CU
+//   * the choice made in every cell (2 bits M, 1 I, 1 D: 16 bits per node group) and at C / E go to the Backward slab row that was
+//     just consumed: vectors 0 and 1 of the row, words 0-5 = the groups' choices, word 6 = E's first best node | C's choice << 16
+//   * the traceback is one serial walk per lane over those words, at the end
+DEV V4 vmaxf(V4 x, V4 y)
+{
+  V4 r;
+  r.a = (f2){x.a.x > y.a.x ? x.a.x : y.a.x, x.a.y > y.a.y ? x.a.y : y.a.y};
+  r.b = (f2){x.b.x > y.b.x ? x.b.x : y.b.x, x.b.y > y.b.y ? x.b.y : y.b.y};
+  return r;
+}
+DEV V4 vrsh_ninf(V4 v) { V4 r; r.a = (f2){-__builtin_inff(), v.a.x}; r.b = (f2){v.a.y, v.b.x}; return r; }
+// (max, +) weight of a transition: 0 where it is allowed (its probability is not zero), -inf where it is not
+DEV float wgt1(float t) { return t > 0.0f ? 0.0f : -__builtin_inff(); }
+DEV V4 wgt(V4 t) { V4 r; r.a = (f2){wgt1(t.a.x), wgt1(t.a.y)}; r.b = (f2){wgt1(t.b.x), wgt1(t.b.y)}; return r; }
+DEV V4 f4v(f4 o) { V4 r; r.a = (f2){o.x, o.y}; r.b = (f2){o.z, o.w}; return r; }
+DEV f4 vf4(V4 v) { return (f4){v.a.x, v.a.y, v.b.x, v.b.y}; }
+// bit z of the result: x[z] > y[z]
+DEV uint32_t vgt4(V4 x, V4 y) { return (uint32_t)(x.a.x > y.a.x) | ((uint32_t)(x.a.y > y.a.y) << 1) | ((uint32_t)(x.b.x > y.b.x) << 2) | ((uint32_t)(x.b.y > y.b.y) << 3); }
+// the 4 bits of `m` spread to bit `b` of the four nibbles
+DEV uint32_t nib_spread(uint32_t m, int b) { return (((m & 1u)) | ((m & 2u) << 3) | ((m & 4u) << 6) | ((m & 8u) << 9)) << b; }
+
+template <int QT>
+__global__ void __launch_bounds__(64, 1) k_env_align(EnvArgs a, int wave0, itsx_alignment *__restrict__ out)
+{
+  __shared__ f4 oaM_s[QMAX * 64], oaI_s[QMAX * 64], oaD_s[QMAX * 64];
+  const WaveDesc wd = a.waves[wave0 + blockIdx.x];
+  const int lane = threadIdx.x;
+  const DevProfile *pp = a.prof + uni(wd.prof);
+  __shared__ __attribute__((aligned(16))) float rf_s[NCODE * QMAX * 4];
+  fill_lds_rf(rf_s, pp);
+  const float *tf = pp->tf;
+  const int Q = QT ? QT : uni(pp->Q);
+  const EnvLane e = env_lane(a, wd, lane);
+  const int Ld = e.Ld; const int64_t r0 = e.r0;
+  const float pmove = e.pmove, ploop = e.ploop;
+  const RegionOut ro = a.rout[e.ri];
+  const int own = ro.own;
+  const bool go = e.active && ro.ok == 0;
+  const float NINF = -__builtin_inff();
+  Row<QT> R;
+#pragma unroll
+  for (int q = 0; q < QMAX; q++) {
+    R.m[q] = vzero(); R.d[q] = vzero(); R.i[q] = vzero();
+    oaM_s[q * 64 + lane] = oaI_s[q * 64 + lane] = oaD_s[q * 64 + lane] = (f4){NINF, NINF, NINF, NINF};
+  }
+  float xE = 0.f, xN = 1.f, xJ = 0.f, xB = pmove, xC = 0.f;
+  float scaleproduct = (float)(1.0 / (double)ro.bN0);
+  float aN = 0.0f, aC = NINF;               // A_N(i-1) = A_B(i-1), A_C(i-1)
+  for (int r = 1; r <= e.Lw; r++) {
+    if (go && r <= Ld) {
+      const float fNp = xN, fCp = xC;
+      const int x = e.sq.code(e.off + r - 1);
+      fwd_row<QT>(R, Q, tf, rf_s + x * QMAX * 4, xN, xB, xJ, xC, xE, pmove, ploop, 0.0f, 1.0f);
+      float fS = 1.0f;
+      if (xE > 1.0e4f) {
+        xN = xN / xE; xC = xC / xE; xJ = xJ / xE; xB = xB / xE;
+        scale_row<QT>(R, Q, xE);
+        fS = xE;
+        xE = 1.0f;
+      }
+      const V4 totrv = vset(scaleproduct * fS);
+      const float *tfo = tf + opaque_zero();
+#define TFO(q, t) vldc(tfo + ((q) * 8 + (t)) * 4)
+      const V4 aBv = vset(aN);
+      // the previous row's last group, shifted one node up, is what group 0 comes from
+      const V4 mpv = vrsh_ninf(f4v(oaM_s[(Q - 1) * 64 + lane])), ipv = vrsh_ninf(f4v(oaI_s[(Q - 1) * 64 + lane])), dpv = vrsh_ninf(f4v(oaD_s[(Q - 1) * 64 + lane]));
+      V4 dcv = vset(NINF), eMax = vset(NINF);
+      uint32_t cw[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+      // groups descending, as in fwd_row: every new value overwrites an old one nobody needs any more
+#pragma unroll
+      for (int q = (QT ? QT : QMAX) - 1; q >= 0; q--) {
+        if (QT == 0 && q >= Q) continue;
+        const V4 bm = f4v(__builtin_nontemporal_load(eslab_at(a.slab, r0, r, q * 2, lane))), bi = f4v(__builtin_nontemporal_load(eslab_at(a.slab, r0, r, q * 2 + 1, lane)));
+        const V4 pm = vmul(vmul(R.m[q], bm), totrv);
+        const V4 pi = vmul(vmul(R.i[q], bi), totrv);
+        const V4 oldM = f4v(oaM_s[q * 64 + lane]), oldI = f4v(oaI_s[q * 64 + lane]);
+        const V4 iM = vadd(oldM, wgt(TFO(q, tMI))), iI = vadd(oldI, wgt(TFO(q, tII)));
+        const uint32_t ich = vgt4(iI, iM);                              // I: from M unless I is strictly better
+        const V4 newI = vadd(pi, vmaxf(iM, iI));
+        const V4 pM = q > 0 ? f4v(oaM_s[(q - 1) * 64 + lane]) : mpv, pI = q > 0 ? f4v(oaI_s[(q - 1) * 64 + lane]) : ipv, pD = q > 0 ? f4v(oaD_s[(q - 1) * 64 + lane]) : dpv;
+        const V4 cM = vadd(pM, wgt(TFO(q, tMM))), cI = vadd(pI, wgt(TFO(q, tIM))), cD = vadd(pD, wgt(TFO(q, tDM))), cB = vadd(aBv, wgt(TFO(q, tBM)));
+        // M: the first of M, I, D, B that reaches the maximum
+        V4 best = vmaxf(cM, cI);
+        const uint32_t gI = vgt4(cI, cM);
+        const uint32_t gD = vgt4(cD, best);
+        best = vmaxf(best, cD);
+        const uint32_t gB = vgt4(cB, best);
+        best = vmaxf(best, cB);
+        // choice = 3 where gB, else 2 where gD, else 1 where gI, else 0
+        const uint32_t lo = gB | (gI & ~gD), hi = gB | gD;
+        const V4 newM = vadd(pm, best);
+        oaM_s[q * 64 + lane] = vf4(newM); oaI_s[q * 64 + lane] = vf4(newI);
+        const V4 dpart = vadd(newM, wgt(TFO(q, tMD)));
+        if (q + 1 < Q) oaD_s[(q + 1) * 64 + lane] = vf4(dpart); else dcv = dpart;
+        eMax = vmaxf(eMax, newM);
+        cw[q >> 1] |= (nib_spread(lo, 0) | nib_spread(hi, 1) | nib_spread(ich, 2)) << ((q & 1) * 16);
+      }
+      // the D->D chain (fwd_row's four passes; a delete cell's M part sits in oaD_s, group 0's comes round from the last group)
+      {
+        V4 D[QMAX], dd[QMAX];
+        const V4 d0 = vrsh_ninf(dcv);
+        dcv = d0;
+#pragma unroll
+        for (int q = 0; q < (QT ? QT : QMAX); q++) {
+          if (QT == 0 && q >= Q) break;
+          dd[q] = wgt(TFO(q, tDD));
+          D[q] = q > 0 ? vmaxf(dcv, f4v(oaD_s[q * 64 + lane])) : dcv;
+          dcv = vadd(D[q], dd[q]);
+        }
+#pragma unroll
+        for (int j = 1; j < 4; j++) {
+          dcv = vrsh_ninf(dcv);
+#pragma unroll
+          for (int q = 0; q < (QT ? QT : QMAX); q++) {
+            if (QT == 0 && q >= Q) break;
+            D[q] = vmaxf(dcv, D[q]);
+            dcv = vadd(dcv, dd[q]);
+          }
+        }
+        const float aE = fmaxf(fmaxf(eMax.a.x, eMax.a.y), fmaxf(eMax.b.x, eMax.b.y));
+        int kE = 0xffff;
+#pragma unroll
+        for (int q = 0; q < (QT ? QT : QMAX); q++) {
+          if (QT == 0 && q >= Q) break;
+          const V4 mpart = q > 0 ? f4v(oaD_s[q * 64 + lane]) : d0;
+          cw[q >> 1] |= nib_spread(vgt4(D[q], mpart), 3) << ((q & 1) * 16);        // D: from M unless D is strictly better
+          oaD_s[q * 64 + lane] = vf4(D[q]);
+          const V4 m = f4v(oaM_s[q * 64 + lane]);
+          const int k0 = q + 1;
+          if (m.a.x == aE) kE = min(kE, k0);
+          if (m.a.y == aE) kE = min(kE, k0 + Q);
+          if (m.b.x == aE) kE = min(kE, k0 + 2 * Q);
+          if (m.b.y == aE) kE = min(kE, k0 + 3 * Q);
+        }
+        const f4 bsp = __builtin_nontemporal_load(eslab_at(a.slab, r0, r, 24, lane));
+        const float pN = fNp * bsp.x * ploop * scaleproduct;
+        const float pC = fCp * bsp.z * ploop * scaleproduct;
+        const float stay = aC + pC;                                    // C: stay unless entering from E is strictly better
+        const uint32_t cE = aE > stay;
+        aC = cE ? aE : stay;
+        aN += pN;
+        // (everything of this Backward row has been consumed: its first two vectors take the row's choices)
+        f4 *cp = eslab_at(a.slab, r0, r, 0, lane);
+        cp[0] = (f4){__uint_as_float(cw[0]), __uint_as_float(cw[1]), __uint_as_float(cw[2]), __uint_as_float(cw[3])};
+        cp[64] = (f4){__uint_as_float(cw[4]), __uint_as_float(cw[5]), __uint_as_float((uint32_t)kE | (cE << 16)), 0.0f};
+        if (own) scaleproduct *= fS / bsp.w;
+      }
+#undef TFO
+    }
+  }
+  if (e.active) {
+    itsx_alignment o;
+    o.hmm_from = o.hmm_to = o.ali_from = o.ali_to = 0; o.oasc = 0.0f; o.aligned = -1;       // -1: the posteriors are unusable
+    const bool fin = aC == aC && aC > NINF && aC < __builtin_inff() && scaleproduct != __builtin_inff();
+    if (go && fin) {
+      auto word = [&](int row, int w) { return __float_as_uint(((const float *)eslab_at(a.slab, r0, row, w >> 2, lane))[w & 3]); };
+      int i = Ld;
+      uint32_t w6 = 0u;
+      while (i >= 1) { w6 = word(i, 6); if (w6 >> 16 & 1u) break; i--; }
+      int k = (int)(w6 & 0xffffu);
+      bool okp = i >= 1 && k >= 1 && k <= 4 * Q;
+      const int i2 = i, k2 = k;
+      int i1 = i, k1 = k, st = 0;                    // 0 M, 1 I, 2 D
+      bool done = false;
+      // every step lowers i or k: at most Ld + 4 Q of them
+      for (int step = 0; okp && step < Ld + 4 * QMAX + 2; step++) {
+        const int q = (k - 1) % Q, z = (k - 1) / Q;
+        const uint32_t nib = (word(i, q >> 1) >> ((q & 1) * 16 + z * 4)) & 15u;
+        if (st == 0) {
+          i1 = i; k1 = k;
+          const int c = (int)(nib & 3u);
+          if (c == 3) { done = true; break; }
+          i--; k--; st = c;
+        } else if (st == 1) { i--; st = (nib >> 2 & 1u) ? 1 : 0; }
+        else { k--; st = (nib >> 3 & 1u) ? 2 : 0; }
+        if (i < 1 || k < 1) okp = false;
+      }
+      if (okp && done) {
+        o.hmm_from = k1; o.hmm_to = k2; o.ali_from = e.off + i1; o.ali_to = e.off + i2; o.oasc = aC; o.aligned = 1;
+      }
+    }
+    out[e.ri] = o;
+  }
+}
+
+// =========================================================================================
 // K4: per pair, chain its envelopes in order: null2 corrections, bit scores, reporting
 // count one "reported target" for profile `prof` per flagged lane, with one atomic per distinct profile per
 // wave: the work lists are grouped by profile, so per-lane atomics would all hit the same address
@@ -1311,6 +1506,19 @@ void launch_envelopes(const EnvArgs &a, int nwaves, int wave0, int generic_q, hi
     hipLaunchKernelGGL(k_env_fwd<QMAX>, dim3(nwaves), dim3(64), 0, st, a, wave0);
     hipLaunchKernelGGL(k_env_bwd<QMAX>, dim3(nwaves), dim3(64), 0, st, a, wave0);
     hipLaunchKernelGGL(k_env_post<QMAX>, dim3(nwaves), dim3(64), 0, st, a, wave0);
+  }
+}
+void launch_align(const EnvArgs &a, itsx_alignment *out, int nwaves, int wave0, int generic_q, hipStream_t st)
+{
+  if (nwaves <= 0) return;
+  if (generic_q) {
+    hipLaunchKernelGGL(k_env_fwd<0>, dim3(nwaves), dim3(64), 0, st, a, wave0);
+    hipLaunchKernelGGL(k_env_bwd<0>, dim3(nwaves), dim3(64), 0, st, a, wave0);
+    hipLaunchKernelGGL(k_env_align<0>, dim3(nwaves), dim3(64), 0, st, a, wave0, out);
+  } else {
+    hipLaunchKernelGGL(k_env_fwd<QMAX>, dim3(nwaves), dim3(64), 0, st, a, wave0);
+    hipLaunchKernelGGL(k_env_bwd<QMAX>, dim3(nwaves), dim3(64), 0, st, a, wave0);
+    hipLaunchKernelGGL(k_env_align<QMAX>, dim3(nwaves), dim3(64), 0, st, a, wave0, out);
   }
 }
 void launch_score(const ScoreArgs &a, hipStream_t st)

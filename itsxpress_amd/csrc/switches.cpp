@@ -58,6 +58,7 @@ static const Switch g_sw[] = {
   {"ITSX_LOAD_PRIORITY", SW_TUNING, "=0: loads do not use the high-priority stream"},
   {"ITSX_SLAB_GB", SW_TUNING, "DP slab budget, GB"},
   {"ITSX_SLAB_ADAPT", SW_TUNING, "=0: the slab budget does not adapt to the job"},
+  {"ITSX_ALIGN_SLAB_MB", SW_TUNING, "itsx_align_domains: slab budget of one batch of waves, MB (default 4096; a small value forces several batches: same alignments)"},
   {"ITSX_DEFER_FREE_GB", SW_TUNING, "device memory kept on the deferred-free list, GB"},
   {"ITSX_MR_LONG_FRAC", SW_TUNING, "ensemble stage: share of regions taken as 'long'"},
   {"ITSX_MR_LONG_LANES", SW_TUNING, "ensemble stage: lanes per long region"},

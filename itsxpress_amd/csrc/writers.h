@@ -54,6 +54,7 @@ struct DomTable {
   int32_t sel = -1;                     // the one sample to write (-1: all)
   const int32_t *seed_read = nullptr;   // target t is labelled targets(seed_read[t]); nullptr: targets(t)
   Labels targets;
+  const itsx_alignment *ali = nullptr;  // [n] parallel to rows, or nullptr: rows with aligned == 1 get their hmm / ali / acc columns from it
 };
 // the two header lines, then the reported domains of every (profile, target), renumbered "k of nrep"
 int write_domtbl(const char *path, const DomTable &t, std::string &err);

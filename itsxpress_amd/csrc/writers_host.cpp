@@ -7,6 +7,7 @@
 // its workers: ONE uc.txt / rep.fa / domtbl.txt, byte for byte the files one GPU writes.
 #include "writers.h"
 #include <algorithm>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -239,11 +240,17 @@ int write_domtbl(const char *path, const DomTable &t, std::string &err)
         k++;
         const double seqE = Z * det_exp(exp_logsurv((double)D[d].seq_score, (double)t.tau[p], (double)t.lambda[p]));
         const double P = det_exp(D[d].lnP);
-        // hmm/ali coordinates and acc need the optimal-accuracy alignment, which the engine does not compute:
-        // envelope coordinates are written in their place (the reference reads only env coords and the score).
+        // hmm/ali coordinates and acc come from the optimal-accuracy alignment where the caller has one for the row (itsx_align_domains);
+        // without it the envelope coordinates are written in their place (the reference reads only env coords and the score).
+        int hf = 1, ht = t.M[p], af = D[d].ienv, at = D[d].jenv; double acc = 0.0;
+        if (t.ali && t.ali[d].aligned == 1) {
+          const itsx_alignment &A = t.ali[d];
+          hf = A.hmm_from; ht = A.hmm_to; af = A.ali_from; at = A.ali_to;
+          acc = (double)A.oasc / (1.0 + std::fabs((double)(D[d].jenv - D[d].ienv)));
+        }
         appendf(out, "%-20s %-10s %5d %-20s %-10s %5d %9.2g %6.1f %5.1f %3d %3d %9.2g %9.2g %6.1f %5.1f %5d %5d %5d %5d %5d %5d %4.2f %s\n",
                 tname.c_str(), "-", D[d].tlen, pname[(size_t)p].c_str(), "-", t.M[p], seqE, D[d].seq_score, D[d].seq_bias,
-                k, nrep, P * dz, P * Z, D[d].bitscore, D[d].dombias / 0.69314718055994529, 1, t.M[p], D[d].ienv, D[d].jenv, D[d].ienv, D[d].jenv, 0.0, "-");
+                k, nrep, P * dz, P * Z, D[d].bitscore, D[d].dombias / 0.69314718055994529, hf, ht, af, at, D[d].ienv, D[d].jenv, acc, "-");
       }
       i = j;
     }
@@ -301,28 +308,50 @@ int itsx_write_derep_arrays(const char *uc_path, const char *rep_path, int64_t n
 // list, input order of the seeds), any order (sorted here: profile, target, domain -- the context writer's order); dom_reported
 // as itsx_search_finalize left it.  Z = targets searched (hmmsearch's Z: the global number of uniques), domz[n_profiles] = the
 // data set's reported targets per profile; per profile its NAME, length M and the Forward tail (tau, lambda) for the E-value columns.
-int itsx_write_domtbl_arrays(const char *path, const itsx_domain *rows, int64_t n_rows, int64_t Z, const int64_t *domz, int32_t n_profiles,
-                             const char *prof_names, const int64_t *prof_name_offsets, const int32_t *prof_M, const float *prof_tau,
-                             const float *prof_lambda, const char *target_names, const int64_t *target_name_offsets)
+int itsx_write_domtbl_arrays_ali(const char *path, const itsx_domain *rows, int64_t n_rows, int64_t Z, const int64_t *domz, int32_t n_profiles,
+                                 const char *prof_names, const int64_t *prof_name_offsets, const int32_t *prof_M, const float *prof_tau,
+                                 const float *prof_lambda, const char *target_names, const int64_t *target_name_offsets,
+                                 const itsx_alignment *ali)
 {
   if (!path || n_rows < 0 || (n_rows > 0 && !rows) || n_profiles < 0 || (n_profiles > 0 && (!domz || !prof_names || !prof_name_offsets || !prof_M || !prof_tau || !prof_lambda)))
     return fail(ITSX_E_ARG, "itsx_write_domtbl_arrays: missing arrays");
   std::vector<itsx_domain> D;
   D.reserve((size_t)n_rows);
-  for (int64_t i = 0; i < n_rows; i++) if (rows[i].dom_idx >= 0 && rows[i].prof >= 0 && rows[i].prof < n_profiles) D.push_back(rows[i]);
-  std::stable_sort(D.begin(), D.end(), [](const itsx_domain &a, const itsx_domain &b) {
+  std::vector<int64_t> src;                       // with alignments: the input row of every kept row, carried through the same sort
+  for (int64_t i = 0; i < n_rows; i++) if (rows[i].dom_idx >= 0 && rows[i].prof >= 0 && rows[i].prof < n_profiles) { D.push_back(rows[i]); if (ali) src.push_back(i); }
+  auto before = [](const itsx_domain &a, const itsx_domain &b) {
     if (a.prof != b.prof) return a.prof < b.prof;
     if (a.rep != b.rep) return a.rep < b.rep;
     return a.dom_idx < b.dom_idx;
-  });
+  };
+  std::vector<itsx_alignment> A;
+  if (!ali) std::stable_sort(D.begin(), D.end(), before);
+  else {
+    std::vector<size_t> ord(D.size());
+    for (size_t i = 0; i < ord.size(); i++) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t x, size_t y) { return before(D[x], D[y]); });
+    std::vector<itsx_domain> Ds(D.size());
+    A.resize(D.size());
+    for (size_t i = 0; i < ord.size(); i++) { Ds[i] = D[ord[i]]; A[i] = ali[src[ord[i]]]; }
+    D.swap(Ds);
+  }
   itsx::DomTable t;
   t.rows = D.data(); t.n = D.size(); t.P = n_profiles;
   t.prof_names = itsx::Labels{prof_names, prof_name_offsets}; t.M = prof_M; t.tau = prof_tau; t.lambda = prof_lambda;
   t.Z = &Z; t.domz = domz;
+  if (ali) t.ali = A.data();
   if (target_names && target_name_offsets) t.targets = itsx::Labels{target_names, target_name_offsets};
   std::string err;
   if (itsx::write_domtbl(path, t, err) != ITSX_OK) return fail(ITSX_E_IO, err);
   return ITSX_OK;
+}
+
+int itsx_write_domtbl_arrays(const char *path, const itsx_domain *rows, int64_t n_rows, int64_t Z, const int64_t *domz, int32_t n_profiles,
+                             const char *prof_names, const int64_t *prof_name_offsets, const int32_t *prof_M, const float *prof_tau,
+                             const float *prof_lambda, const char *target_names, const int64_t *target_name_offsets)
+{
+  return itsx_write_domtbl_arrays_ali(path, rows, n_rows, Z, domz, n_profiles, prof_names, prof_name_offsets, prof_M, prof_tau, prof_lambda,
+                                      target_names, target_name_offsets, nullptr);
 }
 
 }  // extern "C"

@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import DOMAIN_DTYPE, LAZY_PAIR_DTYPE, STATS_DTYPE_ALL, TRACE_DTYPE, EngineError
+from ._lib import ALIGNMENT_DTYPE, DOMAIN_DTYPE, LAZY_PAIR_DTYPE, STATS_DTYPE_ALL, TRACE_DTYPE, EngineError
 
 
 def _device_from_env():
@@ -634,6 +634,23 @@ class Engine:
         if n:
             self._chk(self.L.itsx_get_domains(self.h, out.ctypes.data))
         return out
+
+    def align_domains(self):
+        """The optimal-accuracy alignment of every reported domain row, after finalize(): what fills the hmm / ali / acc columns of
+        write_domtbl (placeholders without it).  Dropped by whatever changes the rows or their reporting.
+        Returns {"n_aligned": rows aligned, "ms_kernels": device time of the stage}."""
+        n, ms = C.c_int64(0), C.c_float(0.0)
+        self._chk(self.L.itsx_align_domains(self.h, C.byref(n), C.byref(ms)))
+        return {"n_aligned": int(n.value), "ms_kernels": float(ms.value)}
+
+    def alignments(self):
+        """ALIGNMENT_DTYPE rows parallel to domains(): aligned == 1 where the row is reported, all zero elsewhere"""
+        n = self.L.itsx_num_domains(self.h)
+        if n < 0:
+            raise EngineError(-1, self.L.itsx_last_error(self.h).decode())
+        out = np.zeros(max(n, 1), ALIGNMENT_DTYPE)
+        self._chk(self.L.itsx_get_alignments(self.h, out.ctypes.data))
+        return out[:n]
 
     def pairtraces(self):
         n = self.L.itsx_num_pairtraces(self.h)
