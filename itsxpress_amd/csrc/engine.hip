@@ -470,7 +470,7 @@ struct itsx_ctx {
   // and by processing position k = (batch, depth, s) (sh_dev); a batch is a range of s whose saved row states fit the slot budget
   struct ShareBatch { int32_t k0, k1; int64_t node0, nnodes; int32_t nsplit; int64_t gnode0, gnnodes; };   // nsplit > 1: the profiles in that many ranges, one after the other; g*: the batch's saved Backward states
   bool share_on = false; int share_B = 32, share_logB = 5, share_maxd = 0;
-  DBuf<unsigned long long> sh_tab, sh_mask_s, sh_mask, sh_counters; DBuf<uint8_t> sh_depth_s, sh_depth;
+  DBuf<unsigned long long> sh_tab, sh_mask_s, sh_mask, sh_counters, msv_xb; DBuf<uint8_t> sh_depth_s, sh_depth;
   DBuf<int32_t> sh_src, sh_parent_s, sh_parent, sh_nn_s, sh_nn, sh_node0_s, sh_node0, sh_order, sh_ulen, sh_uorder, sh_inv, sh_flag, sh_pos, sh_bstart, sh_cursor, sh_segk, sh_scan, sh_cuts;
   std::vector<ShareBatch> sh_batches; std::vector<int32_t> sh_segk_h;            // [batch][SHARE_SEGS]
   DBuf<uint4> sh_mgslots; size_t sh_mgslots_half = 0;        // the MSV filter's saved Backward states (two-sided sharing)
@@ -2199,11 +2199,26 @@ static int run_chunks(itsx_ctx *ctx, double T, double F1, double F3)
   int ci = 0;
   if (ctx->st2) HIPCHK(hipStreamSynchronize(ctx->st2));      // a search that failed half-way may have left an MSV launch behind
   ctx->msv_pre_u0 = -1;
+  msv_diag_begin();
+  // diagnostic (ITSX_TEST_HOOKS=1 ITSX_PASSA_DBG=64): how often a floored row of the shared MSV kernel takes the "xB rose" branch
+  const bool count_xb = sw_get("ITSX_PASSA_DBG") && (atoi(sw_get("ITSX_PASSA_DBG")) & 64);      // (a hook: nullptr unless ITSX_TEST_HOOKS=1)
+  if (count_xb) { HIPCHK(ctx->msv_xb.alloc(8)); HIPCHK(hipMemsetAsync(ctx->msv_xb.p, 0, 8 * sizeof(unsigned long long), ctx->st)); HIPCHK(hipStreamSynchronize(ctx->st)); }
+  else ctx->msv_xb.release();
   for (int64_t u0 = 0; u0 < U; u0 += Uc, ci++) {
     ctx->next_u0 = (u0 + Uc < U) ? u0 + Uc : -1;
     ctx->next_U = (int32_t)std::min<int64_t>(Uc, U - (u0 + Uc));
     const int rc = search_chunk(ctx, ci, (int32_t)u0, (int32_t)std::min<int64_t>(Uc, U - u0), ctx->s_Lcap, T, F1, F3);
     if (rc != ITSX_OK) return rc;
+  }
+  if (count_xb) {
+    unsigned long long n[5] = {0, 0, 0, 0, 0};
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(n, ctx->msv_xb.p, sizeof(n), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[itsx] msv floored wave-rows %llu, with the xB branch %llu (%.4f)\n", n[0], n[1], n[0] ? (double)n[1] / (double)n[0] : 0.0);
+    // (a wave counts once per launch: once per range when a batch takes its profiles in ranges)
+    int nsplit = 0;
+    for (const auto &b : ctx->sh_batches) nsplit = std::max(nsplit, (int)b.nsplit);
+    fprintf(stderr, "[itsx] msv shared waves: whole read %llu, window %llu, 16 words at a time %llu; profile ranges of a batch: at most %d\n", n[2], n[3], n[4], nsplit);
   }
   ctx->n_chunks = ci;
   return ITSX_OK;
@@ -3578,7 +3593,9 @@ static int search_chunk(itsx_ctx *ctx, int ci, int32_t u0, int32_t U, int Lcap, 
       (void)hipMemsetAsync(a.res, 0, (size_t)Ppad * (size_t)cU * sizeof(uint16_t), s);
     }
     const int np = a.plist ? a.nlist : P;
-    a.PB = (int)std::max<int64_t>(1, std::min<int64_t>(32, tiles * np / 4096));
+    // test hook ITSX_MSV_PB: the profiles a block takes its sequences through, whatever the job's size (a small job gets 1)
+    const int pb_forced = sw_get("ITSX_MSV_PB") ? std::max(1, std::min(32, atoi(sw_get("ITSX_MSV_PB")))) : 0;
+    a.PB = pb_forced ? pb_forced : (int)std::max<int64_t>(1, std::min<int64_t>(32, tiles * np / 4096));
     // (the completion filters a handful of profiles: its launches would be a hundred tiny ones per chunk -- it runs unshared, on the same
     // processing order)
     if (!sh || !shared || ctx->completing) { launch_msv(a, s, lds_pad); return; }
@@ -3626,6 +3643,7 @@ static int search_chunk(itsx_ctx *ctx, int ci, int32_t u0, int32_t U, int Lcap, 
             c.sl.slots = gslots; c.sl.node_base = b.gnode0; c.sl.p0 = pa; c.sl.Pb = pb - pa; c.sl.depth = d; c.sl.logB = ctx->share_logB;
             const int64_t t2 = ((int64_t)(k1 - k0) + 255) / 256;
             c.PB = (int)std::max<int64_t>(1, std::min<int64_t>(32, t2 * (pb - pa) / (alt != s ? 4096 : 16384)));
+            if (pb_forced) c.PB = pb_forced;
             launch_msv(c, bs, lds_pad);
           }
         for (int d = 0; d <= ctx->share_maxd; d++) {
@@ -3633,6 +3651,7 @@ static int search_chunk(itsx_ctx *ctx, int ci, int32_t u0, int32_t U, int Lcap, 
           if (k1 <= k0) continue;
           MsvArgs c = a;
           c.k0 = (int32_t)(k0 - cu0); c.k1 = (int32_t)(k1 - cu0); c.pfirst = pa; c.plast = pb; c.share = 1;
+          c.xb_cnt = ctx->msv_xb.p;                  // (nullptr unless the search counts xB branches: run_chunks)
           c.sl.src = ctx->sh_src.p + cu0; c.sl.mask = ctx->sh_mask.p + cu0; c.sl.node0 = ctx->sh_node0.p + cu0;
           c.sl.slots = slots; c.sl.node_base = b.node0; c.sl.p0 = pa; c.sl.Pb = pb - pa; c.sl.depth = d; c.sl.logB = ctx->share_logB;
           if (bi2) { c.sl.endrow = ctx->sh_endrow.p + cu0; c.sl.jlev = ctx->sh_jlev.p + cu0; c.sl.jsrc = ctx->sh_jsrc.p + cu0; c.sl.gslots = gslots; c.sl.gnode_base = b.gnode0; }
@@ -3641,6 +3660,7 @@ static int search_chunk(itsx_ctx *ctx, int ci, int32_t u0, int32_t U, int Lcap, 
           // beside it a block may be four times as long)
           const int64_t t2 = ((int64_t)(k1 - k0) + 255) / 256;
           c.PB = (int)std::max<int64_t>(1, std::min<int64_t>(32, t2 * (pb - pa) / (alt != s ? 4096 : 16384)));
+          if (pb_forced) c.PB = pb_forced;
           launch_msv(c, bs, lds_pad);
         }
       }

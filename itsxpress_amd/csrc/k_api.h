@@ -465,12 +465,15 @@ struct MsvArgs {
   int32_t nlist;
   int32_t k0, k1;               // sorted positions [k0, k1) of this launch (k1 = 0: all U)
   int32_t pfirst, plast;        // profiles (list positions with plist) [pfirst, plast) (plast = 0: all)
-  int32_t wtl;                  // packed words a lane keeps in LDS (set by launch_msv: the whole read, or 16 at a time)
+  int32_t wtl;                  // packed words a lane keeps in LDS (set by launch_msv: the whole read, or 16)
+  int32_t wwin;                 // set by launch_msv: a wave of shared chains whose rows span at most 16 words loads that window once
+  unsigned long long *xb_cnt;   // diagnostic (ITSX_TEST_HOOKS=1 ITSX_PASSA_DBG=64): [0] += floored wave-rows, [1] += those on which xB rose
   int32_t share;                // 1: prefix sharing, every sequence of [k0, k1) is a chain that starts at sl.depth; 2: the Backward chains of the
                                 // two-sided schedule (k_msv_bwd: [k0, k1) are backward positions, sl.depth blocks from the end)
   ShareLaunch sl;
 };
 void launch_msv(const MsvArgs &a, hipStream_t st, int lds_pad = 0);
+void msv_diag_begin();          // a search begins: ITSX_LAZY_HIST prints every launch shape's blocks per CU once more
 
 // survivor list: pairs grouped by profile, 64-aligned segments, ascending length inside a segment
 constexpr int CHUNK = 2048;

@@ -41,13 +41,18 @@
 //     the same double arithmetic hmmsearch uses.
 //   * results go to res[profile][sorted position]: consecutive lanes, consecutive halfwords.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
+#include <mutex>
 #include <type_traits>
+#include <utility>
+#include <vector>
 #include "engine.h"
 #include "k_api.h"
 
 namespace itsx {
 
+constexpr int MSV_WMODE_DEFAULT = 2;   // what ITSX_MSV_WHOLE means when it is not set (launch_msv)
 constexpr int MSV_WT = 16;      // packed words a lane stages in LDS at a time (256 rows)
 typedef short s2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ s2 as_s2(uint32_t u) { return __builtin_bit_cast(s2, u); }
@@ -60,14 +65,17 @@ __device__ __forceinline__ s2 real_off(bool floored, int xB) { return as_s2(floo
 // chain saved (23 packed registers, xJ, xB: MSV_STATE_Q uint4 per (node, profile)), and a chain saves its own state where a
 // later chain branches off.  Integer arithmetic on the same operands: the xJ bytes are those of the unshared kernel.
 // FLOOR: the floored row (above); false: the plain three-instruction row on every row (ITSX_MSV_FLOOR=0, A/B and cross-check)
-template <bool SHARE, bool FLOOR>
+// COUNT: the diagnostic launch (ITSX_TEST_HOOKS=1 ITSX_PASSA_DBG=64) that counts floored wave-rows and those on which xB rose
+template <bool SHARE, bool FLOOR, bool COUNT = false>
 __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
 {
   __shared__ __attribute__((aligned(16))) uint32_t tab[2][16 * MSV_TW];
-  // each lane's packed words in LDS (its own column: no barrier): the WHOLE read when the launch's longest fits 37 words (592 bases:
-  // 37 KB a block, four blocks a CU) -- loaded once for all the block's profiles --, else 16 words (256 rows) at a time
+  // each lane's packed words in LDS (its own column: no barrier), loaded ONCE for all the block's profiles where that can be:
+  //   a.wtl > 16: the WHOLE read (the launch's longest fits 37 words, 592 bases: 37 KB a block, four blocks a CU);
+  //   a.wwin (shared chains only): the wave's WINDOW -- its chains start at row0 and end by Lw, a third of the read on average --
+  //     when that is at most 16 words, indexed from the window's first word: 16 KB a block, six blocks a CU;
+  //   else 16 words (256 rows) at a time, again for every profile
   extern __shared__ uint32_t wst[];
-  const bool whole = a.wtl > MSV_WT;
   const int s = a.k0 + blockIdx.x * 256 + threadIdx.x;
   const bool valid = s < a.k1;
   int L = 0, nexc = 0, tjb = 0, Lt = 0;
@@ -84,10 +92,6 @@ __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
     Lt = L < a.Lcap ? L : a.Lcap - 1;
     tjb = a.tjb[Lt];
   }
-  if (whole) {
-    const int nw = (L + 15) >> 4;
-    for (int j = 0; j < a.wtl; j++) wst[j * 256 + threadIdx.x] = (j < nw) ? wp[j] : 0u;
-  }
   // two-sided sharing (round 6, k_share.hip: k_join_*): a chain whose suffix another representative of its length ends with too stops
   // after row `myend` = jlev * B and takes the rest of the maximum over paths from that representative's saved BACKWARD state
   // (k_msv_bwd below).  The filter is max-plus arithmetic on integers -- every cell is a maximum over paths of sums -- so
@@ -103,6 +107,18 @@ __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
   int Lw = valid ? myend : 0;                     // the wave runs to its longest chain (chains of one depth ascend by their last row)
   for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(Lw, d, 64); Lw = o > Lw ? o : Lw; }
   Lw = uni(Lw);
+  // wonce: the wave's words are loaded once, from word wbase on (both wave-uniform); words beyond the read are zeros
+  const bool whole = a.wtl > MSV_WT;
+  const bool wonce = whole || (SHARE && a.wwin && ((Lw - 1) >> 4) - (row0 >> 4) < MSV_WT);      // (the last word read is that of row Lw - 1)
+  const int wbase = whole ? 0 : (row0 >> 4);
+  if (wonce) {
+    const int nw = (L + 15) >> 4;
+    for (int j = 0; j < a.wtl; j++) wst[j * 256 + threadIdx.x] = (wbase + j < nw) ? wp[wbase + j] : 0u;
+  }
+  unsigned long long n_rows = 0, n_rose = 0;        // COUNT: this wave's floored rows, and those that took the xB branch
+  if constexpr (COUNT) {                            // ... and the waves with a chain by where their words come from: [2] whole read, [3] window, [4] 16 at a time
+    if ((threadIdx.x & 63) == 0 && a.xb_cnt && blockIdx.y == 0 && Lw > 0) atomicAdd(a.xb_cnt + (whole ? 2 : wonce ? 3 : 4), 1ull);
+  }
   const int Ppad = a.G * 64;
   const int p0 = a.pfirst + blockIdx.y * a.PB;
   const int np = a.plast;
@@ -141,15 +157,35 @@ __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
     const int lend = myend;
     int jxJ = -1;                                    // the joined result, if the chain joins
     int pos = row0;
-    // the rows from `pos` on, FAST: with the floored row (the registers hold c''), else with the plain one.  Two loops, not one loop with
-    // a flag: where both rows' registers meet again the compiler copies all 23 of them, every row.  The plain loop of a FLOOR kernel
-    // returns true at the top of the first row that the start-up rule lets the floored row take.
-    auto rows = [&](auto fast_c) -> bool {
+    // the lane's word of rows q .. q + 15 (q a multiple of 16 below Lw), from its LDS column
+    auto word = [&](int q) __attribute__((always_inline)) {
+      // 16 at a time (256 rows) where the words were not loaded once: one contiguous 64-byte piece of the read per load instead of a
+      // dword every 16 rows -- every one of those dwords cost a whole line once 49 k lanes' lines no longer fit the XCD's L2
+      // (75.6 GB fetched per 1 M reads in round 4 against 0.1-0.4 GB of packed reads; profiles/round5_pmc_hbm_traffic_1M.md)
+      if (!wonce && ((q & 255) == 0 || q == row0)) {
+        const int w0 = (q >> 8) << 4, nw = (L + 15) >> 4;
+#pragma unroll
+        for (int j = 0; j < MSV_WT; j++) wst[j * 256 + threadIdx.x] = (w0 + j < nw) ? wp[w0 + j] : 0u;
+      }
+      w = wst[(wonce ? (q >> 4) - wbase : ((q >> 4) & (MSV_WT - 1))) * 256 + threadIdx.x];
+    };
+    // the emission row of row q (a lane calls it for every row below its `lend`, in ascending order: the exception list is walked here)
+    auto erow = [&](int q) __attribute__((always_inline)) -> const uint4 * {
+      int code = (int)((w >> ((q & 15) * 2)) & 3u);
+      if (q == next_exc) {
+        code = (int)(ep[ei] & 15u);
+        ei++;
+        next_exc = ei < nexc ? (int)(ep[ei] >> 4) : 0x7fffffff;
+      }
+      return (const uint4 *)(tb + code * MSV_TW);
+    };
+    // one row.  0: go on, 1: the wave is done, 2 (the plain row of a FLOOR kernel): the start-up rule lets the floored row take this row
+    auto step = [&](auto fast_c) __attribute__((always_inline)) -> int {
     constexpr bool FAST = decltype(fast_c)::value;
-    for (; pos <= Lw; pos++) {
+    {
       if constexpr (FLOOR && !FAST) {
         // the start-up rule: no working lane of the wave is below bm0 - tec any more (monotone: it stays so)
-        if (__builtin_amdgcn_ballot_w64(pos < lend && xJ + tec < bm0) == 0ull) return true;
+        if (__builtin_amdgcn_ballot_w64(pos < lend && xJ + tec < bm0) == 0ull) return 2;
       }
       const int sh = (pos & 15) * 2;
       if (sh == 0) {
@@ -190,25 +226,11 @@ __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
             }
           }
         }
-        if (pos >= Lw) return false;
-        // the lane's packed words, 16 at a time (256 rows) through LDS: one contiguous 64-byte piece of the read per load instead of a
-        // dword every 16 rows -- every one of those dwords cost a whole line once 49 k lanes' lines no longer fit the XCD's L2
-        // (75.6 GB fetched per 1 M reads in round 4 against 0.1-0.4 GB of packed reads; profiles/round5_pmc_hbm_traffic_1M.md)
-        if (!whole && ((pos & 255) == 0 || pos == row0)) {
-          const int w0 = (pos >> 8) << 4, nw = (L + 15) >> 4;
-#pragma unroll
-          for (int j = 0; j < MSV_WT; j++) wst[j * 256 + threadIdx.x] = (w0 + j < nw) ? wp[w0 + j] : 0u;
-        }
-        w = wst[(whole ? (pos >> 4) : ((pos >> 4) & (MSV_WT - 1))) * 256 + threadIdx.x];
+        if (pos >= Lw) return 1;
+        word(pos);
       }
       if (pos < lend) {
-        int code = (int)((w >> sh) & 3u);
-        if (pos == next_exc) {
-          code = (int)(ep[ei] & 15u);
-          ei++;
-          next_exc = ei < nexc ? (int)(ep[ei] >> 4) : 0x7fffffff;
-        }
-        const uint4 *e4 = (const uint4 *)(tb + code * MSV_TW);
+        const uint4 *e4 = erow(pos);
         uint32_t e[MSV_TW];
 #pragma unroll
         for (int q = 0; q < MSV_TW / 4; q++) { const uint4 v = e4[q]; e[4 * q] = v.x; e[4 * q + 1] = v.y; e[4 * q + 2] = v.z; e[4 * q + 3] = v.w; }
@@ -229,7 +251,10 @@ __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
           int nb = xJ - tjbm; nb = nb > bm0 ? nb : bm0;
           const int delta = nb - xB;
           xB = nb;
-          if (__builtin_amdgcn_ballot_w64(delta > 0) != 0ull) {          // xB rose (inside a strong hit): the cells sink by as much
+          const bool rose = __builtin_amdgcn_ballot_w64(delta > 0) != 0ull;
+          // (the lanes at work in a row are nested, so the wave's longest lane counts the wave's rows)
+          if constexpr (COUNT) { n_rows++; n_rose += rose; }
+          if (rose) {                                                    // xB rose (inside a strong hit): the cells sink by as much
             const s2 dv = as_s2((uint32_t)((-delta) & 0xffff) * 0x10001u);
 #pragma unroll
             for (int i = 0; i < MSV_REGS; i++) dp[i] = as_u(__builtin_elementwise_add_sat(as_s2(dp[i]), dv));
@@ -255,9 +280,17 @@ __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
         }
       }
     }
-    return false;
+    return 0;
     };
-    if (rows(std::false_type())) {
+    // the rows from `pos` on, FAST: with the floored row (the registers hold c''), else with the plain one.  Two loops, not one loop with
+    // a flag: where both rows' registers meet again the compiler copies all 23 of them, every row.  The plain loop of a FLOOR kernel
+    // ends with step's 2 at the top of the first row that the start-up rule lets the floored row take.
+    auto rows = [&](auto fast_c) -> int {                // (step's 1 or 2)
+      for (; pos <= Lw; pos++)
+        if (const int r = step(fast_c)) return r;
+      return 1;
+    };
+    if (rows(std::false_type()) == 2) {
       // into the floored form, once: max with xB, subtract xB + 32768
       const s2 xBv = as_s2((uint32_t)xB * 0x10001u);
       const s2 dn = as_s2((uint32_t)((-(xB + 32768)) & 0xffff) * 0x10001u);
@@ -273,6 +306,13 @@ __global__ void __launch_bounds__(256, 6) k_msv(MsvArgs a)
       const int xj = ovf ? 255 : xJ;
       a.res[(size_t)p * a.U + s] = (uint16_t)(pass ? (0x100 | xj) : 0);
     }
+  }
+  if constexpr (COUNT) {
+    for (int d = 32; d >= 1; d >>= 1) {
+      const unsigned long long o = __shfl_xor(n_rows, d, 64), q = __shfl_xor(n_rose, d, 64);
+      n_rows = o > n_rows ? o : n_rows; n_rose = q > n_rose ? q : n_rose;
+    }
+    if ((threadIdx.x & 63) == 0 && a.xb_cnt) { atomicAdd(a.xb_cnt, n_rows); atomicAdd(a.xb_cnt + 1, n_rose); }
   }
 }
 
@@ -391,6 +431,27 @@ __global__ void __launch_bounds__(256, 6) k_msv_bwd(MsvArgs a)
   }
 }
 
+// ITSX_LAZY_HIST: the blocks a CU really holds of every launch shape (kernel, dynamic LDS) of a search, one stderr line per shape --
+// the occupancy the registers allow is not the one a launch gets (37 + 3 KB of LDS a block: four blocks, whatever the registers)
+static std::mutex g_occ_mu;
+static std::vector<std::pair<const void *, size_t>> g_occ_seen;
+void msv_diag_begin() { std::lock_guard<std::mutex> lk(g_occ_mu); g_occ_seen.clear(); }
+static void msv_occupancy_line(const void *fn, const char *name, size_t lds)
+{
+  std::lock_guard<std::mutex> lk(g_occ_mu);
+  for (const auto &o : g_occ_seen) if (o.first == fn && o.second == lds) return;
+  g_occ_seen.emplace_back(fn, lds);
+  int nb = -1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, lds) != hipSuccess) { (void)hipGetLastError(); nb = -1; }
+  fprintf(stderr, "[itsx] msv occupancy: %s dynamic LDS %zu B: %d blocks of 256 per CU (%d waves per SIMD)\n", name, lds, nb, nb);
+}
+template <typename K>
+static void msv_go(K kern, const char *name, const dim3 &grid, size_t lds, hipStream_t st, const MsvArgs &a)
+{
+  if (sw_get("ITSX_LAZY_HIST")) msv_occupancy_line((const void *)kern, name, lds);
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
+}
+
 // lds_pad: dynamic LDS the launch asks for and never touches -- a cap on the blocks a CU holds (160 KB per CU), for the launch that
 // runs beside another stream's kernels and must leave them their registers
 void launch_msv(const MsvArgs &a0, hipStream_t st, int lds_pad)
@@ -401,11 +462,19 @@ void launch_msv(const MsvArgs &a0, hipStream_t st, int lds_pad)
   const int np = a.plast - a.pfirst, nk = a.k1 - a.k0;
   if (nk <= 0 || np <= 0) return;
   const dim3 grid((unsigned)((nk + 255) / 256), (unsigned)((np + a.PB - 1) / a.PB));
-  // words a lane keeps in LDS: every word of the launch's longest read when that is at most 37 (four blocks of 37 + 3 KB fill a CU's
-  // 160 KB exactly), else 16 at a time; ITSX_MSV_WHOLE=0: always 16 (A/B)
-  static const bool allow_whole = !(sw_get("ITSX_MSV_WHOLE") && atoi(sw_get("ITSX_MSV_WHOLE")) == 0);
+  // words a lane keeps in LDS, ITSX_MSV_WHOLE (read at every launch; MSV_WMODE_DEFAULT when unset):
+  //   1: every word of the launch's longest read when that is at most 37 (four blocks of 37 + 3 KB fill a CU's 160 KB exactly: four
+  //      waves per SIMD whatever the registers allow), else 16 at a time;
+  //   2: shared chains keep their wave's window, 16 words (16 + 3 KB a block: six blocks a CU, the six waves per SIMD that 80 registers
+  //      are held to); the unshared kernel as under 1;
+  //   0: always 16 at a time
+  const char *wsw = sw_get("ITSX_MSV_WHOLE");
+  int wmode = wsw ? atoi(wsw) : MSV_WMODE_DEFAULT;
+  if (wmode < 0 || wmode > 2) wmode = MSV_WMODE_DEFAULT;
   const int need = (a.Lcap - 1 + 15) / 16;
-  a.wtl = (allow_whole && need > MSV_WT && need <= 37) ? need : MSV_WT;
+  const bool window = wmode == 2 && a.share == 1;
+  a.wtl = (wmode != 0 && !window && need > MSV_WT && need <= 37) ? need : MSV_WT;
+  a.wwin = window;
   // (a Backward chain walks a few blocks of its read through one to eight profiles: it takes its words from memory as it goes, a dword
   // every 16 rows -- the whole read in LDS first was 37 gathers per chain for ~6 words used, and 37 KB per block held a CU to 4 blocks)
   static const bool bwd_whole = sw_get("ITSX_MSV_BWD_WHOLE") && atoi(sw_get("ITSX_MSV_BWD_WHOLE")) != 0;
@@ -413,11 +482,12 @@ void launch_msv(const MsvArgs &a0, hipStream_t st, int lds_pad)
   const size_t lds = std::max<size_t>((size_t)lds_pad, (a.share == 2 && !bwd_whole) ? 0 : (size_t)a.wtl * 256 * sizeof(uint32_t));
   // ITSX_MSV_FLOOR=0: the plain three-instruction row on every row (A/B, and the cross-check of the floored row; read at every launch)
   const bool floored = !(sw_get("ITSX_MSV_FLOOR") && atoi(sw_get("ITSX_MSV_FLOOR")) == 0);
-  if (a.share == 2) hipLaunchKernelGGL(k_msv_bwd, grid, dim3(256), lds, st, a);
-  else if (a.share && floored) hipLaunchKernelGGL((k_msv<true, true>), grid, dim3(256), lds, st, a);
-  else if (a.share) hipLaunchKernelGGL((k_msv<true, false>), grid, dim3(256), lds, st, a);
-  else if (floored) hipLaunchKernelGGL((k_msv<false, true>), grid, dim3(256), lds, st, a);
-  else hipLaunchKernelGGL((k_msv<false, false>), grid, dim3(256), lds, st, a);
+  if (a.share == 2) msv_go(k_msv_bwd, "k_msv_bwd", grid, lds, st, a);
+  else if (a.share && floored && a.xb_cnt) msv_go(k_msv<true, true, true>, "k_msv<true, true> counting", grid, lds, st, a);
+  else if (a.share && floored) msv_go(k_msv<true, true>, "k_msv<true, true>", grid, lds, st, a);
+  else if (a.share) msv_go(k_msv<true, false>, "k_msv<true, false>", grid, lds, st, a);
+  else if (floored) msv_go(k_msv<false, true>, "k_msv<false, true>", grid, lds, st, a);
+  else msv_go(k_msv<false, false>, "k_msv<false, false>", grid, lds, st, a);
 }
 
 // ---------------------------------------------------------------------------------------

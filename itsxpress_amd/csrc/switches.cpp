@@ -15,7 +15,8 @@ static const Switch g_sw[] = {
   {"ITSX_LAZY_NO_COMPLETE", SW_HOOK, "skips itsx_lazy_complete inside itsx_search_finalize (leaves undecided rows undecided)"},
   {"ITSX_COMPACT_ZMAX", SW_HOOK, "largest domZ the compact / lazy modes call a row 'certain' for (default 1e9); a value below the data's domZ can drop a winner"},
   {"ITSX_COMPACT_DOME_MIN", SW_HOOK, "smallest --domE the compact / lazy modes call a row 'certain' for (default 1e-2)"},
-  {"ITSX_PASSA_DBG", SW_HOOK, "pass A diagnostic bits (no rows / no restore / no join): timings only, scores are garbage"},
+  {"ITSX_PASSA_DBG", SW_HOOK, "pass A diagnostic bits (no rows / no restore / no join): timings only, scores are garbage; 64: the shared MSV kernel counts its floored wave-rows, those with the xB branch and its waves by word layout (results unchanged; one stderr line per search)"},
+  {"ITSX_MSV_PB", SW_HOOK, "profiles one block of the MSV filter takes its sequences through (1 .. 32; default: by the job's size, 1 for a small job): same cells"},
   {"ITSX_TWRITER_HOST_SLICE", SW_HOOK, "=1: a streamed writer with a device (itsx_twriter_set_device) slices every unit on the host, as it does a unit its line index does not fit (same file bytes)"},
   // ---- MODEs
   {"ITSX_ROWS", SW_MODE, "rows mode when the caller did not call itsx_set_rows_mode: full | compact | lazy (coordinates identical in all three)"},
@@ -51,7 +52,7 @@ static const Switch g_sw[] = {
   {"ITSX_CHUNK_UNIQUES", SW_TUNING, "representatives per search chunk"},
   {"ITSX_MSV_OVERLAP", SW_TUNING, "=0: the next chunk's MSV filter does not run beside the domain stage"},
   {"ITSX_MSV_PAD", SW_TUNING, "dynamic LDS of the overlapped MSV launch (an occupancy cap)"},
-  {"ITSX_MSV_WHOLE", SW_TUNING, "=0: MSV stages 16 words at a time even when the whole read fits LDS"},
+  {"ITSX_MSV_WHOLE", SW_TUNING, "where the MSV filter keeps a lane's packed words: 2 (default) shared chains keep their wave's window of at most 16 words, loaded once per block; 1 the whole read when the launch's longest fits 37 words, as the unshared kernel always does; 0 16 words at a time everywhere (A/B arms: same cells; read at every launch)"},
   {"ITSX_MSV_FLOOR", SW_TUNING, "=0: the MSV filter's plain three-instruction row on every row instead of the floored two-instruction one (A/B arm: same cells; read at every launch)"},
   {"ITSX_BIAS_OVERLAP", SW_TUNING, "=0: the bias filter does not run on the second stream"},
   {"ITSX_ST2_PRIO", SW_TUNING, "priority of the second stream"},
