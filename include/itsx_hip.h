@@ -569,6 +569,25 @@ int itsx_get_cluster(const itsx_ctx *ctx, double *pct_id, int64_t *order, int64_
  * sample that itsx_search keeps domZ by; itsx_get_cluster's order is the samples' processing orders, sample after sample.
  * id == 1.0 is itsx_derep(ctx, strand_both, 32, ...) on the batch; with S == 1 this is itsx_cluster. */
 int itsx_cluster_samples(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique);
+/* ---- column 8 of the --uc file of itsxpress/SeqSample.py:147-162 (opt-in; the text form is the USEARCH / vsearch uc format's,
+ * parity unpinned as for the rest of a2: DESIGN.md 2).
+ * itsx_align_clusters: after itsx_cluster / itsx_cluster_multi / itsx_cluster_samples at id < 1, aligns every member with its
+ *   centroid once more and keeps the path (csrc/k_cigar.hip): global, the member on the strand itsx_get_derep reports, the cell
+ *   definition of the clustering; among the paths of the optimal (score, matches, -counted columns), walking back from the end:
+ *   the diagonal where it reproduces the cell, else the gap that consumes a centroid symbol, else the gap that consumes a member
+ *   symbol, and a gap extends in preference to closing.  n_aligned = members that have a text, ms_kernels = device time of the
+ *   sweeps and walks; either may be NULL.  ITSX_E_ARG before a clustering, and after itsx_derep or id == 1.0 (exact dereplication
+ *   has nothing to align: its file keeps '*', as vsearch's does).  ITSX_CIGAR_MB caps the direction bits of one batch of pairs; a
+ *   pair larger than it runs alone.
+ * itsx_get_cluster_cigars: read r's text is text[offs[r] .. offs[r + 1]): run-length encoded, M a column with a symbol of each read,
+ *   I a centroid symbol opposite a gap in the member, D a member symbol opposite a gap in the centroid, a run of one without its
+ *   count; the single character '=' for a member that equals its centroid symbol for symbol on its strand (never aligned); empty
+ *   for a centroid or a dropped read.  text == NULL fills offs only (offs[n_reads] = bytes needed).  ITSX_E_ARG when no alignments
+ *   exist for the current clustering: a new read set, itsx_derep and every itsx_cluster* drop them.
+ * itsx_write_uc prints column 8 of every H row from them while they exist (also under itsx_select_sample), and '*' otherwise;
+ *   100 * matches / counted columns of the printed path is itsx_get_cluster's pct_id, the same double. */
+int itsx_align_clusters(itsx_ctx *ctx, int64_t *n_aligned, float *ms_kernels);
+int itsx_get_cluster_cigars(const itsx_ctx *ctx, int64_t *offs /* [n_reads + 1] */, char *text);
 /* Dedup.parse's matchdict (itsxpress/SeqSample.py:542-562) as arrays over reads:
  * rep_of[i] = read index of the cluster seed (first occurrence), -1 if the read was dropped;
  * strand[i] = +1 / -1 (uc column 5); uniq_of[i] = index into the unique list, -1 if dropped. */

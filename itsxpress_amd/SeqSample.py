@@ -93,6 +93,27 @@ def _domtbl_ali_wanted(sample, eng, fast) -> bool:
     return True
 
 
+def _uc_cigar_from_env():
+    return os.environ.get("ITSXPRESS_UC_CIGAR", "").strip() not in ("", "0")
+
+
+def _uc_cigar_wanted(sample, eng, fast) -> bool:
+    """ITSXPRESS_UC_CIGAR=1 (or `uc_cigar` on the sample): at cluster_id < 1 the H rows of uc.txt get the member's alignment with
+    its centroid in column 8 (Engine.align_clusters) instead of '*'.  One context writing the file only: arrays mode writes no
+    file, and the multi-GPU and streamed drivers compose theirs from gathered arrays."""
+    v = getattr(sample, "uc_cigar", None)
+    want = _uc_cigar_from_env() if v is None else bool(v)
+    if not want:
+        return False
+    if fast:
+        logger.warning("ITSXPRESS_UC_CIGAR is ignored with ITSXPRESS_ARRAYS=1: no uc.txt is written")
+        return False
+    if not isinstance(eng, Engine):
+        logger.warning("ITSXPRESS_UC_CIGAR is ignored with ITSXPRESS_GPUS > 1 / ITSXPRESS_STREAM=1: column 8 of uc.txt stays '*'")
+        return False
+    return True
+
+
 class SeqSample:
     """Base class: dereplicate -> search, as the reference's SeqSample (SeqSample.py:18-225)."""
 
@@ -110,6 +131,7 @@ class SeqSample:
         self.fast: Optional[bool] = None         # None: ITSXPRESS_ARRAYS (default off)
         self.domtbl: Optional[str] = None        # None: ITSXPRESS_DOMTBL ("winners": files as ever, domtbl.txt = the rows that can win)
         self.domtbl_ali: Optional[bool] = None   # None: ITSXPRESS_DOMTBL_ALI (domtbl.txt with hmmsearch's hmm / ali coordinates and acc)
+        self.uc_cigar: Optional[bool] = None     # None: ITSXPRESS_UC_CIGAR (cluster_id < 1: uc.txt with the members' alignments in column 8)
 
     # -- engine plumbing -------------------------------------------------------------
     @property
@@ -220,6 +242,8 @@ class SeqSample:
             finally:
                 for h in helpers:
                     h.close()
+            if cid < 1.0 and _uc_cigar_wanted(self, self.engine, self._is_fast()):
+                self.engine.align_clusters()
             if self._is_fast():
                 self.uc_file = EngineTable(self.uc_file, self.engine, "uc")
             else:

@@ -107,7 +107,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_debug_set_domains", "itsx_debug_get_rows",
            "itsx_debug_scan", "itsx_debug_select", "itsx_debug_region_keys", "itsx_debug_lazy_pairs",
            "itsx_set_sample_sharing", "itsx_sample_sharing_info", "itsx_sample_sharing_times", "itsx_debug_sample_classes",
-           "itsx_align_domains", "itsx_get_alignments", "itsx_write_domtbl_arrays_ali"]
+           "itsx_align_domains", "itsx_get_alignments", "itsx_write_domtbl_arrays_ali",
+           "itsx_align_clusters", "itsx_get_cluster_cigars"]
 
 
 def lib():
@@ -206,6 +207,8 @@ def lib():
         "itsx_cluster_multi": (i32, [vp, vp, i32, f64, i32, vp]),
         "itsx_cluster_samples": (i32, [vp, f64, i32, vp]),
         "itsx_get_cluster": (i32, [vp, vp, vp, vp]),
+        "itsx_align_clusters": (i32, [vp, vp, vp]),
+        "itsx_get_cluster_cigars": (i32, [vp, vp, vp]),
         "itsx_merge_buffers": (i32, [vp, cp, cp, vp, cp, cp, vp, i64, i32, f64, i32, vp, vp, vp, vp, vp, vp]),
         "itsx_merge_pairs_files": (i32, [vp, cp, cp, cp, i32, f64, i32, vp, vp]),
         "itsx_merge_pairs_load": (i32, [vp, cp, cp, i32, f64, i32, vp, vp]),

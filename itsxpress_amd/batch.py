@@ -35,7 +35,7 @@ import numpy as np
 
 from .engine import Engine
 from ._lib import EngineError
-from .SeqSample import _REGION_PREFIX, _domtbl_ali_wanted, _fast_from_env, _winners_from_env
+from .SeqSample import _REGION_PREFIX, _domtbl_ali_wanted, _fast_from_env, _uc_cigar_wanted, _winners_from_env
 from .definitions import maxmismatches
 
 
@@ -242,6 +242,8 @@ class SampleBatch:
             eng = self.engine
             self._load_reads()
             n = eng.cluster_samples(float(cluster_id), strand_both=True)
+            if float(cluster_id) < 1.0 and _uc_cigar_wanted(self, eng, False):      # every sample's members in one pass; the writer picks the sample's
+                eng.align_clusters()
             for i, s in enumerate(self.samples):
                 d = self._dir(i)
                 s.uc_file = os.path.join(d, "uc.txt")

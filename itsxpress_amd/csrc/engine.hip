@@ -399,6 +399,11 @@ struct itsx_ctx {
   bool clustered = false;                // last grouping came from itsx_cluster at id < 1 (uc rows carry identities)
   std::vector<double> h_pct;             // per read: identity of its H row, -1 for centroids / dropped reads
   std::vector<int32_t> h_order;          // kept reads in processing (label) order
+  // itsx_align_clusters: the run-length alignment of every member with its centroid (uc column 8), read r's text at
+  // h_cg_text[h_cg_off[r], h_cg_off[r + 1]) (empty: a centroid or a dropped read); whatever changes the clustering drops them
+  bool have_cigar = false; std::vector<int64_t> h_cg_off; std::string h_cg_text;
+  void drop_cigars() { have_cigar = false; std::vector<int64_t>().swap(h_cg_off); std::string().swap(h_cg_text); }
+  bool cigars_live() const { return have_cigar && have_derep && clustered; }
 
   // ---- search
   bool have_search = false, have_final = false;
@@ -1056,7 +1061,7 @@ static int pack_and_upload(itsx_ctx *ctx, const char *view = nullptr, const uint
   }
   ctx->rd.words = ctx->d_words.p; ctx->rd.woff = ctx->d_woff.p; ctx->rd.len = ctx->d_len.p;
   ctx->rd.excoff = ctx->d_excoff.p; ctx->rd.exc = ctx->d_exc.p; ctx->rd.n = n;
-  ctx->have_derep = ctx->have_search = ctx->have_final = false;
+  ctx->have_derep = ctx->have_search = ctx->have_final = false; ctx->drop_cigars();
   ctx->stats.n_reads = n;
   ctx->order_cache_ok = false;
   ctx->S = 1; ctx->sel_sample = -1; ctx->h_sample.clear(); ctx->h_usample.clear();      // a new read set is one sample until told otherwise
@@ -1300,7 +1305,7 @@ int itsx_set_samples(itsx_ctx *ctx, const int32_t *sample_of_read, int32_t n_sam
 {
   CTXCHK(ctx);
   HIPCHK(hipSetDevice(ctx->device));
-  ctx->have_derep = ctx->have_search = ctx->have_final = false;
+  ctx->have_derep = ctx->have_search = ctx->have_final = false; ctx->drop_cigars();
   ctx->sel_sample = -1; ctx->h_usample.clear();
   ctx->order_cache_ok = false;
   if (!sample_of_read || n_samples <= 1) { ctx->S = 1; ctx->h_sample.clear(); return ITSX_OK; }
@@ -1498,6 +1503,7 @@ int itsx_derep(itsx_ctx *ctx, int strand_both, int minseqlength, int64_t *n_uniq
   CTXCHK(ctx);
   HIPCHK(hipSetDevice(ctx->device));
   LoadPriority load_priority(ctx);
+  ctx->drop_cigars();
   const int64_t n = ctx->N;
   StageTimer tm(ctx->st);
   DBuf<uint64_t> &hf = ctx->w_hf, &hr = ctx->w_hr; DBuf<unsigned long long> &keys = ctx->w_keys;
@@ -1580,6 +1586,7 @@ static void dust_host(const uint8_t *codes, int64_t L, std::vector<uint8_t> &mas
 static int cluster_run(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique, bool batched, ClusterShards *shards = nullptr)
 {
   HIPCHK(hipSetDevice(ctx->device));
+  ctx->drop_cigars();
   const int64_t n = ctx->N;
   const int minlen = 32;
   const int32_t S = batched ? ctx->S : 1;
@@ -1887,6 +1894,121 @@ int itsx_get_cluster(const itsx_ctx *ctx, double *pct_id, int64_t *order, int64_
   if (pct_id) for (int64_t r = 0; r < ctx->N; r++) pct_id[r] = ctx->h_pct[r];
   if (order) for (size_t i = 0; i < ctx->h_order.size(); i++) order[i] = ctx->h_order[i];
   if (n_order) *n_order = (int64_t)ctx->h_order.size();
+  return ITSX_OK;
+}
+
+// uc column 8 (k_cigar.hip): every member of the current clustering aligned with its centroid once more, this time with the path.
+// The pairs go in batches under a byte budget (ITSX_CIGAR_MB: the direction bits of a pair are about (Lq + 1)(Lt + 1) / 2 bytes);
+// a pair larger than the budget is a batch of its own, in an allocation of its own size.
+int itsx_align_clusters(itsx_ctx *ctx, int64_t *n_aligned, float *ms_kernels)
+{
+  CTXCHK(ctx);
+  if (!ctx->have_derep || !ctx->clustered) SET_ERR(ctx, ITSX_E_ARG, "itsx_align_clusters comes after a clustering at id < 1 (itsx_cluster, itsx_cluster_multi, itsx_cluster_samples); exact dereplication has nothing to align");
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->drop_cigars();
+  const int64_t n = ctx->N;
+  hipStream_t st = ctx->st;
+  std::vector<int32_t> hq, ht; std::vector<int8_t> hs;
+  int Lmax = 1;
+  for (int64_t r = 0; r < n; r++) {
+    const int32_t rep = ctx->h_rep_of[(size_t)r];
+    if (rep < 0 || rep == r) continue;
+    hq.push_back((int32_t)r); ht.push_back(rep); hs.push_back(ctx->h_strand[(size_t)r]);
+    Lmax = std::max(Lmax, std::max((int)ctx->h_len[(size_t)r], (int)ctx->h_len[(size_t)rep]));
+  }
+  const size_t M = hq.size();
+  float ms = 0.0f;
+  std::vector<std::string> text(M);
+  if (M > 0) {
+    // rows per lane as the clustering chooses them (cluster_run): the smallest variant that holds the longest read in one pass
+    int rows_per_lane = (Lmax + 1 <= 320) ? 5 : (Lmax + 1 <= 512) ? 8 : 10;
+    if (const char *e = sw_get("ITSX_CL_ROWS")) rows_per_lane = atoi(e) <= 5 ? 5 : atoi(e) <= 8 ? 8 : 10;
+    double budget_mb = 2048.0;
+    if (const char *e = sw_get("ITSX_CIGAR_MB")) budget_mb = std::max(0.0, atof(e));
+    const size_t budget = (size_t)(budget_mb * 1048576.0);
+    DBuf<int32_t> d_q, d_t, d_eq, d_tlen; DBuf<int8_t> d_s; DBuf<int64_t> d_doff, d_soff, d_toff;
+    DBuf<uint8_t> d_dir, d_text; DBuf<long long> d_scr, d_res; DBuf<double> d_pid;
+    HIPCHK(upload(d_q, hq, st)); HIPCHK(upload(d_t, ht, st)); HIPCHK(upload(d_s, hs, st));
+    HIPCHK(d_eq.alloc(M)); HIPCHK(d_res.alloc(M)); HIPCHK(d_pid.alloc(M));
+    CigarArgs a{};
+    a.rd = ctx->rd; a.q_read = d_q.p; a.t_read = d_t.p; a.strand = d_s.p; a.res = d_res.p; a.pid = d_pid.p;
+    std::vector<int32_t> eq(M);
+    launch_cg_equal(a, (int32_t)M, d_eq.p, st);
+    HIPCHK(hipMemcpyAsync(eq.data(), d_eq.p, M * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // the pairs that need the dynamic program, in member order, with their places in their batch
+    std::vector<int32_t> pq, pt, pm; std::vector<int8_t> ps; std::vector<int64_t> doff, soff;
+    struct Batch { size_t p0, np, dir_bytes, scr_elems; };
+    std::vector<Batch> batches;
+    for (size_t m = 0; m < M; m++) {
+      if (eq[m]) { text[m] = "="; continue; }
+      size_t db = 0, sb = 0;
+      cg_pair_bytes(ctx->h_len[(size_t)hq[m]], ctx->h_len[(size_t)ht[m]], rows_per_lane, &db, &sb);
+      db = (db + 255) & ~(size_t)255;
+      if (batches.empty() || (batches.back().np > 0 && batches.back().dir_bytes + batches.back().scr_elems * 8 + db + sb > budget)) batches.push_back(Batch{pq.size(), 0, 0, 0});
+      Batch &b = batches.back();
+      doff.push_back((int64_t)b.dir_bytes); soff.push_back((int64_t)b.scr_elems);
+      b.np++; b.dir_bytes += db; b.scr_elems += sb / 8;
+      pq.push_back(hq[m]); pt.push_back(ht[m]); ps.push_back(hs[m]); pm.push_back((int32_t)m);
+    }
+    const size_t NP = pq.size();
+    if (NP > 0) {
+      size_t max_dir = 0, max_scr = 0, max_np = 0;
+      for (const Batch &b : batches) { max_dir = std::max(max_dir, b.dir_bytes); max_scr = std::max(max_scr, b.scr_elems); max_np = std::max(max_np, b.np); }
+      HIPCHK(upload(d_q, pq, st)); HIPCHK(upload(d_t, pt, st)); HIPCHK(upload(d_s, ps, st)); HIPCHK(upload(d_doff, doff, st)); HIPCHK(upload(d_soff, soff, st));
+      if (d_dir.alloc(max_dir + 256, true) != hipSuccess || d_scr.alloc(max_scr + 2, true) != hipSuccess) {
+        (void)hipGetLastError();
+        SET_ERR(ctx, ITSX_E_NOMEM, "itsx_align_clusters: no device memory for " + std::to_string((max_dir + max_scr * 8) >> 20) + " MB of direction bits (lower ITSX_CIGAR_MB; a pair larger than the budget needs its own size)");
+      }
+      HIPCHK(d_tlen.alloc(max_np)); HIPCHK(d_toff.alloc(max_np + 1));
+      a.q_read = d_q.p; a.t_read = d_t.p; a.strand = d_s.p; a.dir_off = d_doff.p; a.scr_off = d_soff.p;
+      a.dir = d_dir.p; a.scratch = d_scr.p; a.tlen = d_tlen.p; a.toff = d_toff.p;
+      std::vector<int32_t> tlen; std::vector<int64_t> toff; std::vector<char> plane;
+      for (const Batch &b : batches) {
+        StageTimer t1(st);
+        launch_cg_forward(a, (int32_t)b.p0, (int32_t)b.np, rows_per_lane, Lmax, st);
+        launch_cg_traceback(a, (int32_t)b.p0, (int32_t)b.np, rows_per_lane, 0, st);
+        ms += t1.stop();
+        HIPCHK(hipGetLastError());
+        tlen.resize(b.np); toff.assign(b.np + 1, 0);
+        HIPCHK(hipMemcpy(tlen.data(), d_tlen.p, b.np * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < b.np; k++) {
+          if (tlen[k] <= 0) SET_ERR(ctx, ITSX_E_DEVICE, "itsx_align_clusters: the direction bits of read " + std::to_string(pq[b.p0 + k]) + " do not lead back to the first cell");
+          toff[k + 1] = toff[k] + tlen[k];
+        }
+        HIPCHK(d_text.alloc((size_t)toff[b.np] + 1));
+        a.text = reinterpret_cast<char *>(d_text.p);
+        HIPCHK(hipMemcpyAsync(d_toff.p, toff.data(), (b.np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        StageTimer t2(st);
+        launch_cg_traceback(a, (int32_t)b.p0, (int32_t)b.np, rows_per_lane, 1, st);
+        ms += t2.stop();
+        HIPCHK(hipGetLastError());
+        plane.resize((size_t)toff[b.np]);
+        HIPCHK(hipMemcpy(plane.data(), d_text.p, plane.size(), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < b.np; k++) text[(size_t)pm[b.p0 + k]].assign(plane.data() + toff[k], (size_t)tlen[k]);
+      }
+      // the sweep's last cell is the one the clustering accepted the member with: the same identity, bit for bit
+      std::vector<double> pid(NP);
+      HIPCHK(hipMemcpy(pid.data(), d_pid.p, NP * sizeof(double), hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < NP; k++)
+        if (memcmp(&pid[k], &ctx->h_pct[(size_t)pq[k]], sizeof(double)) != 0)
+          SET_ERR(ctx, ITSX_E_DEVICE, "itsx_align_clusters: read " + std::to_string(pq[k]) + " aligns at identity " + std::to_string(pid[k]) + ", the clustering accepted it at " + std::to_string(ctx->h_pct[(size_t)pq[k]]));
+    }
+  }
+  ctx->h_cg_off.assign((size_t)n + 1, 0);
+  { size_t m = 0, tot = 0; for (int64_t r = 0; r < n; r++) { ctx->h_cg_off[(size_t)r] = (int64_t)tot; if (m < M && hq[m] == r) tot += text[m++].size(); } ctx->h_cg_off[(size_t)n] = (int64_t)tot; ctx->h_cg_text.reserve(tot); }
+  for (size_t m = 0; m < M; m++) ctx->h_cg_text += text[m];
+  ctx->have_cigar = true;
+  if (n_aligned) *n_aligned = (int64_t)M;
+  if (ms_kernels) *ms_kernels = ms;
+  return ITSX_OK;
+}
+int itsx_get_cluster_cigars(const itsx_ctx *ctx, int64_t *offs, char *text)
+{
+  CTXCHK(ctx && offs);
+  if (!ctx->cigars_live()) SET_ERR(ctx, ITSX_E_ARG, "itsx_get_cluster_cigars: no alignments for the current clustering (itsx_align_clusters comes after itsx_cluster* at id < 1)");
+  memcpy(offs, ctx->h_cg_off.data(), ((size_t)ctx->N + 1) * sizeof(int64_t));
+  if (text && !ctx->h_cg_text.empty()) memcpy(text, ctx->h_cg_text.data(), ctx->h_cg_text.size());
   return ITSX_OK;
 }
 
@@ -4774,7 +4896,7 @@ int itsx_orient_apply(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t
     rr.h_titles.swap(r_names); rr.seq_p = rr.seq.p;
   }
   ctx->dev_bases = nullptr; ctx->d_merged_text.release();      // the text of the read set that was: this one's is on the host
-  ctx->have_derep = ctx->have_search = ctx->have_final = false;
+  ctx->have_derep = ctx->have_search = ctx->have_final = false; ctx->drop_cigars();
   ctx->order_cache_ok = false; ctx->sel_sample = -1; ctx->h_usample.clear();
   ctx->stats.n_reads = m;
   if (strand && n > 0) memcpy(strand, hs.data(), (size_t)n);
@@ -6620,6 +6742,7 @@ static itsx::Clusters clusters(const itsx_ctx *ctx)
   c.uniq_of = ctx->h_uniq_of.data(); c.seed_read = ctx->h_seed_read.data(); c.abund = ctx->h_abund.data();
   c.len = ctx->h_len.data(); c.strand = ctx->h_strand.data(); c.labels = read_labels(ctx);
   if (ctx->clustered) { c.order = ctx->h_order.data(); c.n_order = (int64_t)ctx->h_order.size(); c.pct = ctx->h_pct.data(); }
+  if (ctx->cigars_live()) { c.cigar_off = ctx->h_cg_off.data(); c.cigar_text = ctx->h_cg_text.data(); }
   if (ctx->S > 1) { c.sample = ctx->h_sample.data(); c.usample = ctx->h_usample.data(); c.sel = ctx->sel_sample; }   // writers restricted to one sample of a batch
   return c;
 }

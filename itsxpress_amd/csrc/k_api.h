@@ -131,6 +131,23 @@ void launch_cl_validate(const ClusterArgs &a, int rows_per_lane, hipStream_t st)
 void launch_cl_finalize(int32_t nk, const int32_t *order, const int32_t *res_col, const int8_t *res_strand, const double *res_id,
                         const int32_t *cent_read, int32_t *rep_of, int8_t *strand, double *pct, int32_t *is_seed, hipStream_t st);
 
+// ---- k_cigar.hip: the alignments of the accepted (member, centroid) pairs of a clustering (itsx_align_clusters)
+struct CigarArgs {
+  ReadsDev rd;
+  const int32_t *q_read, *t_read;   // [pairs] the member and its centroid
+  const int8_t *strand;             // [pairs] -1: the member is aligned as its reverse complement
+  const int64_t *dir_off;           // [pairs] the pair's direction bits: byte offset in dir (a multiple of 256, from the batch's start)
+  const int64_t *scr_off;           // [pairs] its border rows between passes: element offset in scratch (unused by a one-pass pair)
+  uint8_t *dir; long long *scratch;
+  long long *res; double *pid;      // [pairs] cell (Lq, Lt) as packed, and its identity
+  int32_t *tlen;                    // [batch] characters of the text, -1: the walk failed
+  const int64_t *toff; char *text;  // [batch + 1], the batch's text plane
+};
+void launch_cg_equal(const CigarArgs &a, int32_t n, int32_t *eq, hipStream_t st);
+void launch_cg_forward(const CigarArgs &a, int32_t p0, int32_t np, int rows_per_lane, int lmax, hipStream_t st);
+void launch_cg_traceback(const CigarArgs &a, int32_t p0, int32_t np, int rows_per_lane, int fill, hipStream_t st);
+void cg_pair_bytes(int Lq, int Lt, int rows_per_lane, size_t *dir_bytes, size_t *scr_bytes);
+
 // ---- f4: read orientation (k_cluster.hip)
 void launch_orient(const ReadsDev &rd, const uint32_t *dbbits /*4^12 bits*/, const uint32_t *dmask /*k_dust, or nullptr*/, int8_t *strand, int32_t *cfwd, int32_t *crev, hipStream_t st);
 void launch_dust(const ReadsDev &rd, uint32_t *dmask, hipStream_t st);

@@ -41,6 +41,7 @@
 #include <algorithm>
 #include "engine.h"
 #include "k_api.h"
+#include "k_cl_cell.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "this engine ships gfx950 code only (k_orient alone keeps 73 KB of LDS per workgroup: over the 64 KB of older targets)"
@@ -48,20 +49,6 @@
 
 namespace itsx {
 
-typedef long long i64;
-typedef unsigned long long u64;
-
-static constexpr int SH_S = 40, SH_M = 20;
-static constexpr i64 NEGV = -(1LL << 60);
-static constexpr i64 ONE_S = 1LL << SH_S, ONE_M = 1LL << SH_M;
-static constexpr i64 GOI = -22 * ONE_S - 1, GEI = -2 * ONE_S - 1, GOT = -3 * ONE_S, GET = -1 * ONE_S;
-// diagonal increments: match 2*ONE_S + ONE_M - 1, mismatch -4*ONE_S - 1, compatible ambiguity ONE_M - 1, incompatible -1 (built in align_pair)
-static constexpr u64 MASK4_LUT = 0xFD7EB96C3A508421ULL;      // IUPAC set of each digital code, 4 bits each
-
-__device__ __forceinline__ uint32_t mask4(uint32_t code) { return (uint32_t)(MASK4_LUT >> (4 * code)) & 15u; }
-__device__ __forceinline__ uint32_t revmask4(uint32_t m) { return ((m & 1u) << 3) | ((m & 2u) << 1) | ((m & 4u) >> 1) | ((m & 8u) >> 3); }
-__device__ __forceinline__ bool unamb4(uint32_t m) { return __popc(m) == 1; }
-__device__ __forceinline__ i64 max64(i64 a, i64 b) { return a > b ? a : b; }
 __device__ __forceinline__ uint32_t rc16(uint32_t k)
 {
   uint32_t x = ~k & 0xffffu;
@@ -656,13 +643,6 @@ __global__ void k_cl_take(ClusterArgs a, int round)
   if (m > 0) { const int w0 = atomicAdd(&a.work_n[0], m); for (int k = 0; k < m; k++) a.work[w0 + k] = qs * 32 + first + k; }
 }
 
-__device__ __forceinline__ i64 shfl_up64(i64 v)
-{
-  int lo = (int)(v & 0xffffffffLL), hi = (int)(v >> 32);
-  lo = __shfl_up(lo, 1); hi = __shfl_up(hi, 1);
-  return ((i64)hi << 32) | (i64)(uint32_t)lo;
-}
-
 // one wave = one (query strand, candidate centroid) alignment
 // (lane l owns S consecutive DP rows; returns true on the lane that holds cell (Lq, Lt), with its packed value)
 template <int S> __device__ __forceinline__ bool align_pair(const ClusterArgs &a, int qs, int col, int scr_slot, uint8_t *tmask, i64 &res)
@@ -766,15 +746,6 @@ template <int S> __device__ __forceinline__ bool align_pair(const ClusterArgs &a
   }
   return have;
 }
-__device__ __forceinline__ double identity_of(i64 res)
-{
-  const i64 score = (res + (1LL << (SH_S - 1))) >> SH_S;
-  const i64 low = res - score * ONE_S;
-  const i64 matches = (low + (1LL << (SH_M - 1))) >> SH_M;
-  const i64 cols = matches * ONE_M - low;
-  return cols > 0 ? 100.0 * (double)matches / (double)cols : 0.0;
-}
-
 // ------------------------------------------------------------------ a rejection certificate before the full alignment
 // 96 % of the alignments end in a rejection.  Most of them can be PROVEN rejections for a fraction of the work:
 //  (1) an accepted alignment A (identity = M / (M + E) >= X, M matching columns, E mismatching pairs + interior gap

@@ -28,6 +28,9 @@ struct Clusters {
   Labels labels;                        // of the reads
   // --cluster_size: the kept reads in processing order and the identity of their H rows; order == nullptr: exact dereplication
   const int32_t *order = nullptr; int64_t n_order = 0; const double *pct = nullptr;
+  // --cluster_size, optional: the alignment of every member with its centroid (column 8 of its H row), read r's at
+  // cigar_text[cigar_off[r], cigar_off[r + 1]); nullptr: the column is '*'
+  const int64_t *cigar_off = nullptr; const char *cigar_text = nullptr;
   // a batch of samples: the sample of every read / cluster (nullptr: one sample) and the one sample to write (-1: all)
   const int32_t *sample = nullptr, *usample = nullptr; int32_t sel = -1;
 };

@@ -101,6 +101,13 @@ void h_row(std::string &out, size_t c, int32_t len, double pct, int8_t strand, c
 {
   appendf(out, "H\t%zu\t%d\t%.1f\t%c\t0\t0\t*\t%s\t%s\n", c, len, pct, strand < 0 ? '-' : '+', label.c_str(), seed.c_str());
 }
+// the same row with the member's alignment in column 8 (an alignment of a long read is longer than appendf's line)
+void h_row_cigar(std::string &out, size_t c, int32_t len, double pct, int8_t strand, const char *cigar, size_t ncigar, const std::string &label, const std::string &seed)
+{
+  appendf(out, "H\t%zu\t%d\t%.1f\t%c\t0\t0\t", c, len, pct, strand < 0 ? '-' : '+');
+  out.append(cigar, ncigar);
+  out.push_back('\t'); out.append(label); out.push_back('\t'); out.append(seed); out.push_back('\n');
+}
 
 }  // namespace
 
@@ -158,6 +165,8 @@ int write_uc(const char *path, const Clusters &c, const std::vector<int32_t> &or
         if (c.sel >= 0 && c.sample[r] != c.sel) continue;
         const int32_t u = c.uniq_of[r], s = c.seed_read[u];
         if (s == r) s_row(out, (size_t)cno[(size_t)u], c.len[r], c.labels(r));
+        else if (c.cigar_off && c.cigar_off[r + 1] > c.cigar_off[r])
+          h_row_cigar(out, (size_t)cno[(size_t)u], c.len[r], c.pct[r], c.strand[r], c.cigar_text + c.cigar_off[r], (size_t)(c.cigar_off[r + 1] - c.cigar_off[r]), c.labels(r), c.labels(s));
         else h_row(out, (size_t)cno[(size_t)u], c.len[r], c.pct[r], c.strand[r], c.labels(r), c.labels(s));
       }
     }, err);

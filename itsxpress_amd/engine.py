@@ -489,6 +489,24 @@ class Engine:
         self._chk(self.L.itsx_get_cluster(self.h, pct.ctypes.data, order.ctypes.data, C.byref(n)))
         return pct, order[:n.value]
 
+    def align_clusters(self):
+        """After cluster(id < 1) / cluster_samples: the alignment of every member with its centroid (csrc/k_cigar.hip), what fills
+        column 8 of write_uc's H rows ('*' without it).  Dropped by whatever changes the clustering.
+        Returns {"n_aligned": members that have a text, "ms_kernels": device time of the stage}."""
+        n, ms = C.c_int64(0), C.c_float(0.0)
+        self._chk(self.L.itsx_align_clusters(self.h, C.byref(n), C.byref(ms)))
+        return {"n_aligned": int(n.value), "ms_kernels": float(ms.value)}
+
+    def get_cluster_cigars(self):
+        """list of str over the reads, after align_clusters(): a member's run-length alignment with its centroid (M / I / D, a run
+        of one without its count; '=' for a member that equals its centroid on its strand), '' for centroids and dropped reads"""
+        offs = np.zeros(self.n_reads + 1, np.int64)
+        self._chk(self.L.itsx_get_cluster_cigars(self.h, offs.ctypes.data, None))
+        text = C.create_string_buffer(max(1, int(offs[-1])))
+        self._chk(self.L.itsx_get_cluster_cigars(self.h, offs.ctypes.data, text))
+        raw = text.raw
+        return [raw[offs[r]:offs[r + 1]].decode("ascii") for r in range(self.n_reads)]
+
     def get_derep(self):
         rep_of = np.zeros(self.n_reads, np.int64)
         strand = np.zeros(self.n_reads, np.int8)

@@ -19,6 +19,7 @@ PY_SWITCHES = [
     ("ITSXPRESS_ARRAYS", "mode", "=1: arrays instead of uc.txt / rep.fa / domtbl.txt between the stages, lazy rows mode (same trimmed reads)"),
     ("ITSXPRESS_DOMTBL", "mode", "=winners: files as ever, the lazy search behind them; domtbl.txt holds per target and side the row ItsPosition.parse ends up with (same dictionary, same trimmed reads)"),
     ("ITSXPRESS_DOMTBL_ALI", "mode", "=1: domtbl.txt gets hmmsearch's hmm / ali coordinates and acc from the optimal-accuracy stage (itsx_align_domains) instead of placeholders; one context writing files only (ignored with a warning under ITSXPRESS_GPUS > 1, ITSXPRESS_STREAM=1, ITSXPRESS_ARRAYS=1)"),
+    ("ITSXPRESS_UC_CIGAR", "mode", "=1: at cluster_id < 1 the H rows of uc.txt get the member's alignment with its centroid in column 8 (itsx_align_clusters) instead of '*'; one context writing files only (ignored with a warning under ITSXPRESS_GPUS > 1 through MultiEngine, ITSXPRESS_STREAM=1, ITSXPRESS_ARRAYS=1)"),
     ("ITSXPRESS_STREAM", "mode", "=1 / 0: streamed file-order chunks on / off (default: by input size, ITSX_STREAM_AUTO_MB)"),
     ("ITSXPRESS_DB_DIR", "mode", "directory with additional ITSx_db HMM files (F.hmm)"),
     ("ITSXPRESS_XDIR", "tuning", "directory of the multi-GPU exchange files (default /dev/shm when it has room, else the temp directory)"),
