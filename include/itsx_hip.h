@@ -641,6 +641,12 @@ int itsx_lazy_pending_profiles(const itsx_ctx *ctx, int32_t *flags);
 int itsx_lazy_pending_uniques(itsx_ctx *ctx, uint8_t *flags);
 int itsx_set_partial_coords(itsx_ctx *ctx, int on);
 int itsx_lazy_complete(itsx_ctx *ctx, const int32_t *flags);
+/* The top-up round of itsx_search_finalize runs count-only (ITSX_TOPUP_COUNT_ONLY=0: as a third lazy round): it is there for the lower
+ * bounds on domZ, so a pair with a multidomain region is deferred -- unevaluated, on the upper bound's side -- instead of taking the
+ * ensemble stage, and no rows are kept.  counters[0] = pairs the last search's round deferred; counters[1] = 1 when rows of its profiles
+ * were still undecided and the deferred pairs went through the ordinary pipeline in a second sub-round, else 0.  (Counters of their own
+ * and not fields of itsx_stats: that structure's size and last fields are fixed by its readers.) */
+int itsx_topup_counters(const itsx_ctx *ctx, int64_t *counters /* [2] */);
 int64_t itsx_domz_count(const itsx_ctx *ctx);
 int itsx_get_domz(const itsx_ctx *ctx, int64_t *domZ /* [itsx_domz_count]: [n_samples][n_profiles] (x 2 after a lazy search) */);
 int itsx_set_domz(itsx_ctx *ctx, const int64_t *domZ /* same */);

@@ -108,7 +108,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_debug_scan", "itsx_debug_select", "itsx_debug_region_keys", "itsx_debug_lazy_pairs",
            "itsx_set_sample_sharing", "itsx_sample_sharing_info", "itsx_sample_sharing_times", "itsx_debug_sample_classes",
            "itsx_align_domains", "itsx_get_alignments", "itsx_write_domtbl_arrays_ali",
-           "itsx_align_clusters", "itsx_get_cluster_cigars"]
+           "itsx_align_clusters", "itsx_get_cluster_cigars",
+           "itsx_topup_counters"]
 
 
 def lib():
@@ -224,6 +225,7 @@ def lib():
         "itsx_search": (i32, [vp, f64, f64, f64, f64]),
         "itsx_set_rows_mode": (i32, [vp, i32]),
         "itsx_lazy_pending": (i64, [vp]),
+        "itsx_topup_counters": (i32, [vp, vp]),
         "itsx_lazy_pending_profiles": (i32, [vp, vp]),
         "itsx_lazy_complete": (i32, [vp, vp]),
         "itsx_domz_count": (i64, [vp]),

@@ -488,6 +488,12 @@ struct itsx_ctx {
   // the top-up round of itsx_search_finalize (round 6): the last search's pair list, while it is still in the buffers (one chunk, one sample)
   struct TopUp { bool valid = false, list_live = false /* d_pairs, l_fb, l_b10 and l_done still hold the list (itsx_debug_lazy_pairs) */; int64_t NP = 0; std::vector<int64_t> seg_start; std::vector<int32_t> total; int32_t u0 = 0, Uc = 0; } topup;
   DBuf<unsigned long long> l_zneed, l_zsplit, l_tcnt; DBuf<int32_t> l_slot, l_pslot; DBuf<uint32_t> l_cut;
+  // the count-only top-up round: each pair of its list's index in the search's list, the deferred pairs' bits and their number; the two
+  // counters of the last search (itsx_topup_counters)
+  DBuf<int32_t> l_src; DBuf<unsigned long long> l_dmask, l_defn, l_tcnt2;
+  int64_t n_topup_deferred = 0, n_topup_ensemble = 0, topup_deferred_live = 0 /* deferred by the last count-only round and not evaluated since */;
+  std::vector<int64_t> topup_defp;                                   // [P] deferred pairs per profile
+  std::vector<int32_t> topup_profs, topup_partial;                   // the profiles of the last top-up round; those of them that took their `need` pairs instead of all (ITSX_LAZY_TOPUP_ALL=2)
   std::vector<unsigned long long> h_zneed;
   bool prev_lazy = false; int prev_P = 0; int64_t prev_U = 0, prev_Uc = 0;      // the last search's chunking (itsx_search)
   std::vector<int32_t> h_merge_index;      // per pair of the last merge-and-load: its merged read, -1 = not merged
@@ -2432,7 +2438,7 @@ static int search_active(itsx_ctx *ctx, double T, double F1, double F2, double F
   ctx->domz_ub.assign((size_t)P * ctx->S, 0);
   if (ctx->compact_rows)                    // a full table of an earlier search (80 B x ~130 per representative) goes back to the device
     for (auto &b : ctx->dom_bufs) if (b && b->cap * sizeof(itsx_domain) > ((size_t)256 << 20)) b->release();
-  S.lazy = ctx->lazy; S.n_lazy_evaluated = S.n_lazy_round1 = S.n_lazy_pending = S.n_lazy_reruns = 0; S.n_lazy_completed = S.n_lazy_completed_profiles = S.n_lazy_pending_profiles = 0; S.ms_lazy_complete = 0; S.lazy_bound_maxdiff = 0; S.ms_bound_kernel = S.ms_lazy_select = 0; S.bound_rows = 0; S.n_bound_launches = 0; S.n_lazy_topup = 0; S.ms_lazy_topup = 0; S.ms_lazy_topup_stages = 0;
+  S.lazy = ctx->lazy; S.n_lazy_evaluated = S.n_lazy_round1 = S.n_lazy_pending = S.n_lazy_reruns = 0; S.n_lazy_completed = S.n_lazy_completed_profiles = S.n_lazy_pending_profiles = 0; S.ms_lazy_complete = 0; S.lazy_bound_maxdiff = 0; S.ms_bound_kernel = S.ms_lazy_select = 0; S.bound_rows = 0; S.n_bound_launches = 0; S.n_lazy_topup = 0; S.ms_lazy_topup = 0; S.ms_lazy_topup_stages = 0; ctx->n_topup_deferred = ctx->n_topup_ensemble = 0;
   if (ctx->compact_rows && U > 0) { const int rc = compact_setup(ctx); if (rc != ITSX_OK) return rc; }
   if (U == 0) return ITSX_OK;
 
@@ -2763,8 +2769,13 @@ static int build_waves(itsx_ctx *ctx, const PairList &pl, std::vector<WaveDesc> 
 }
 
 // every stage after the survivor list, for the pairs of `pl`: bias filter + Forward, Backward + decoding + regions, the ensemble
-// stage, envelope re-scoring, scores and domZ counts, domain rows (compacted when the context keeps only what can still win)
-static int domain_pipeline(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorted, double T, double F1, double F3, const std::function<int()> *next_msv)
+// stage, envelope re-scoring, scores and domZ counts, domain rows (compacted when the context keeps only what can still win).
+// count_only (the top-up round alone; pl is then select_compact's list with its source indices in l_src, l_dmask is zeroed and l_defn[0]
+// counts): the call is there for the domZ counters, not for rows.  A pair with a multidomain region is deferred (k_topup_defer: no
+// envelopes, no score, no count, unevaluated again) and the ensemble stage does not run; every other pair is scored and counted as
+// always, and no row is written, compacted or merged -- a pair that is unevaluated after round 2 ranks below its group's best certain
+// row (k_lazy_mark), so no row of it can win or tie ItsPosition's argmax.
+static int domain_pipeline(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorted, double T, double F1, double F3, const std::function<int()> *next_msv, bool count_only = false)
 {
   hipStream_t st = ctx->st;
   const int P = ctx->P;
@@ -2946,7 +2957,11 @@ static int domain_pipeline(itsx_ctx *ctx, const PairList &pl, const int32_t *d_s
   // ---- multidomain regions: resolved into envelopes by stochastic traceback clustering (k_ensemble.hip)
   int64_t NMR = 0;
   const bool ensemble = !(sw_get("ITSX_NO_ENSEMBLE") && atoi(sw_get("ITSX_NO_ENSEMBLE")) != 0);
-  if (ensemble) {
+  if (ensemble && count_only) {
+    HIPCHK(ctx->w_mrcnt.alloc((size_t)NP + 2));
+    launch_mr_count(pl.pout, d_raw.p, pv, NP, ctx->w_mrcnt.p, st);
+    launch_topup_defer(pl.pout, ctx->w_mrcnt.p, ctx->l_src.p, NP, ctx->l_done.p, ctx->l_dmask.p, ctx->l_defn.p, st);
+  } else if (ensemble) {
     DBuf<int32_t> &mrcnt = ctx->w_mrcnt, &mroff = ctx->w_mroff, &stmp = ctx->w_scan2;
     HIPCHK(mrcnt.alloc((size_t)NP + 2)); HIPCHK(mroff.alloc((size_t)NP + 2)); HIPCHK(stmp.alloc((size_t)scan_tmp_elems(NP + 2)));
     launch_mr_count(pl.pout, d_raw.p, pv, NP, mrcnt.p, st);
@@ -3157,11 +3172,13 @@ static int domain_pipeline(itsx_ctx *ctx, const PairList &pl, const int32_t *d_s
   std::vector<int32_t> rtotal((size_t)P);
   for (int p = 0; p < P; p++) { rtotal[p] = bound[p + 1] - bound[p]; rseg[p + 1] = rseg[p] + ((int64_t)rtotal[p] + 63) / 64 * 64; S.n_domains += rtotal[p]; }
   const int64_t NR = rseg[P];
-  ctx->dom_n[di] = NR;
+  ctx->dom_n[di] = count_only ? 0 : NR;                    // (count_only: this call leaves no segment of rows)
   HIPCHK(ctx->d_pair_region0.alloc((size_t)NP));
   HIPCHK(ctx->d_regions.alloc((size_t)std::max<int64_t>(NR, 1)));
-  HIPCHK(d_dom.alloc((size_t)std::max<int64_t>(NR, 1)));
-  HIPCHK(hipMemsetAsync(d_dom.p, 0xFF, (size_t)std::max<int64_t>(NR, 1) * sizeof(itsx_domain), st));
+  if (!count_only) {
+    HIPCHK(d_dom.alloc((size_t)std::max<int64_t>(NR, 1)));
+    HIPCHK(hipMemsetAsync(d_dom.p, 0xFF, (size_t)std::max<int64_t>(NR, 1) * sizeof(itsx_domain), st));
+  }
   if (NR > 0) {
     DBuf<int64_t> &d_rseg = ctx->w_rseg;
     HIPCHK(upload(d_rseg, rseg, st));
@@ -3250,11 +3267,11 @@ static int domain_pipeline(itsx_ctx *ctx, const PairList &pl, const int32_t *d_s
     ScoreArgs sa{};
     sa.rd = ctx->rd; sa.sorted_uniq = d_sorted; sa.seed_read = ctx->d_seed_read.p; sa.prof = ctx->d_prof.p; sa.lt = ctx->d_lt.p;
     sa.flogsum = ctx->d_flogsum.p; sa.pairs = pl.pairs; sa.pout = pl.pout; sa.regions = ctx->d_regions.p; sa.rout = ctx->d_rout.p;
-    sa.pair_region0 = ctx->d_pair_region0.p; sa.upos = ctx->d_upos.p; sa.dom = d_dom.p; sa.npairs = NP; sa.T = T;
+    sa.pair_region0 = ctx->d_pair_region0.p; sa.upos = ctx->d_upos.p; sa.dom = count_only ? nullptr : d_dom.p; sa.npairs = NP; sa.T = T;
     if (NMR > 0) { sa.mr = ctx->w_mr.p; sa.mr_u = ctx->w_mru.p; sa.mrout = ctx->w_mrout.p; sa.n2off = ctx->w_n2off.p; sa.n2sc = ctx->w_n2sc.p; sa.mr_off = ctx->w_mroff.p; }
     sa.domz = ctx->d_domz32.p; sa.usample = ctx->dev_usample(); sa.P = ctx->P;
     launch_score(sa, st);
-    if (ctx->compact_rows) {
+    if (ctx->compact_rows && !count_only) {
       // keep what can still win once domZ is known, in row order; the chunk's full rows are scratch
       { const int rc = compact_segment(ctx, d_dom.p, NR, di); if (rc != ITSX_OK) return rc; }
     }
@@ -3300,7 +3317,8 @@ __global__ void k_dbg_group_hist(const unsigned long long *__restrict__ cnt, int
 // The pairs that a marking kernel (k_lazy_mark, k_topup_mark) set a bit for, as a list of their own in l_pairs / d_pout: the chunk counts
 // are scanned, the profiles' totals read at their segments' first chunks, and the set bits scattered.  Each profile keeps its segment,
 // padded to 64 with 0xFF records, and its pairs their order.  nsel = pairs selected; sub.NP == 0: none (nothing was allocated).
-static int select_compact(itsx_ctx *ctx, const PairRec *pairs, int64_t NP, int P, const std::vector<int64_t> &seg_start, const int64_t *d_seg_start, PairList &sub, int64_t &nsel)
+// want_src: l_src[k] = the index in `pairs` of the new list's pair k (padding records: not written).
+static int select_compact(itsx_ctx *ctx, const PairRec *pairs, int64_t NP, int P, const std::vector<int64_t> &seg_start, const int64_t *d_seg_start, PairList &sub, int64_t &nsel, bool want_src = false)
 {
   hipStream_t st = ctx->st;
   const int64_t nch = (NP + 63) >> 6;
@@ -3322,7 +3340,8 @@ static int select_compact(itsx_ctx *ctx, const PairRec *pairs, int64_t NP, int P
   HIPCHK(hipMemsetAsync(ctx->l_pairs.p, 0xFF, (size_t)sub.NP * sizeof(PairRec), st));
   HIPCHK(hipMemsetAsync(ctx->d_pout.p, 0, (size_t)sub.NP * sizeof(PairOut), st));
   HIPCHK(upload(ctx->l_seg, sub.seg_start, st));
-  launch_lazy_scatter(pairs, NP, ctx->l_smask.p, ctx->l_spos.p, d_seg_start, ctx->l_seg.p, ctx->l_pairs.p, st);
+  if (want_src) HIPCHK(ctx->l_src.alloc((size_t)sub.NP));
+  launch_lazy_scatter(pairs, NP, ctx->l_smask.p, ctx->l_spos.p, d_seg_start, ctx->l_seg.p, ctx->l_pairs.p, st, want_src ? ctx->l_src.p : nullptr);
   sub.pairs = ctx->l_pairs.p; sub.pout = ctx->d_pout.p; sub.d_seg_start = ctx->l_seg.p;
   return ITSX_OK;
 }
@@ -3895,6 +3914,12 @@ int itsx_lazy_pending_profiles(const itsx_ctx *ctx, int32_t *flags)
   for (int p = 0; p < ctx->P; p++) flags[p] = (ctx->lazy && (size_t)p < ctx->lazy_pending_prof.size()) ? (ctx->lazy_pending_prof[(size_t)p] != 0) : 0;
   return ITSX_OK;
 }
+int itsx_topup_counters(const itsx_ctx *ctx, int64_t *counters)
+{
+  CTXCHK(ctx && counters);
+  counters[0] = ctx->n_topup_deferred; counters[1] = ctx->n_topup_ensemble;
+  return ITSX_OK;
+}
 int itsx_set_partial_coords(itsx_ctx *ctx, int on) { CTXCHK(ctx); ctx->partial_coords = on != 0; return ITSX_OK; }
 int itsx_set_kept_rows(itsx_ctx *ctx, int on) { CTXCHK(ctx); if (ctx->kept_rows != (on != 0)) { ctx->h_dom.clear(); ctx->drop_alignments(); } ctx->kept_rows = on != 0; return ITSX_OK; }
 // flags[n_unique]: 1 where an undecided row could still change the representative's coordinates (the rows itsx_lazy_pending counts)
@@ -4027,7 +4052,7 @@ int itsx_debug_set_domains(itsx_ctx *ctx, const itsx_domain *rows, int64_t n_row
   ctx->compact_rows = mode != ITSX_ROWS_FULL; ctx->lazy = mode == ITSX_ROWS_LAZY;
   ctx->lazy_pending = 0; ctx->domz_exchanged = false; ctx->lazy_pending_prof.clear();
   itsx_stats &S = ctx->stats;
-  S.lazy = ctx->lazy; S.n_domains = 0; S.n_lazy_pending = S.n_lazy_reruns = S.n_lazy_topup = S.n_lazy_completed = S.n_lazy_completed_profiles = S.n_lazy_pending_profiles = 0;
+  S.lazy = ctx->lazy; S.n_domains = 0; S.n_lazy_pending = S.n_lazy_reruns = S.n_lazy_topup = S.n_lazy_completed = S.n_lazy_completed_profiles = S.n_lazy_pending_profiles = 0; ctx->n_topup_deferred = ctx->n_topup_ensemble = 0;
   for (int64_t i = 0; i < n_rows; i++) S.n_domains += rows[i].dom_idx >= 0;
   HIPCHK(ctx->d_domz32.alloc(std::max<size_t>(m, 1)));
   HIPCHK(hipMemsetAsync(ctx->d_domz32.p, 0, std::max<size_t>(m, 1) * 4, st));
@@ -4129,19 +4154,58 @@ static int finalize_lazy(itsx_ctx *ctx, double domE)
   return ITSX_OK;
 }
 
+// The bounds after a sub-round of the top-up (its profiles: ctx->topup_profs): reported among the evaluated pairs below, those + the pairs
+// still not evaluated above (a pair the count-only round deferred is one of the latter until it is evaluated)
+static int topup_bounds(itsx_ctx *ctx, bool with_deferred)
+{
+  hipStream_t st = ctx->st;
+  const auto &tu = ctx->topup;
+  const std::vector<int32_t> &prof_of = ctx->topup_profs;
+  const int ns = (int)prof_of.size(), P = ctx->P;
+  std::vector<int32_t> dz32((size_t)P * ctx->S, 0);
+  HIPCHK(hipMemcpyAsync(dz32.data(), ctx->d_domz32.p, dz32.size() * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(upload(ctx->w_idx, tu.seg_start, st)); HIPCHK(upload(ctx->w_rcnt, tu.total, st)); HIPCHK(upload(ctx->l_pslot, prof_of, st));      // (the pipeline used the buffers)
+  HIPCHK(ctx->l_tcnt.alloc((size_t)std::max(ns, 1)));
+  HIPCHK(hipMemsetAsync(ctx->l_tcnt.p, 0, (size_t)std::max(ns, 1) * sizeof(unsigned long long), st));
+  launch_topup_count(ctx->l_done.p, ctx->w_idx.p, ctx->w_rcnt.p, ctx->l_pslot.p, ns, ctx->l_tcnt.p, st);
+  std::vector<unsigned long long> ndone((size_t)ns, 0), ndef((size_t)ns, 0);
+  if (ns > 0) HIPCHK(hipMemcpyAsync(ndone.data(), ctx->l_tcnt.p, (size_t)ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  if (with_deferred && ns > 0) {                          // the profiles' deferred pairs: what a second sub-round could still add to / take off their bounds
+    HIPCHK(ctx->l_tcnt2.alloc((size_t)ns));
+    HIPCHK(hipMemsetAsync(ctx->l_tcnt2.p, 0, (size_t)ns * sizeof(unsigned long long), st));
+    launch_topup_count_mask(ctx->l_dmask.p, ctx->w_idx.p, ctx->w_rcnt.p, ctx->l_pslot.p, ns, ctx->l_tcnt2.p, st);
+    HIPCHK(hipMemcpyAsync(ndef.data(), ctx->l_tcnt2.p, (size_t)ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  ctx->topup_defp.assign((size_t)P, 0);
+  for (int k = 0; k < ns; k++) ctx->topup_defp[(size_t)prof_of[(size_t)k]] = (int64_t)ndef[(size_t)k];
+  for (size_t z = 0; z < dz32.size(); z++) { ctx->domz_loc[z] = dz32[z]; ctx->domz[z] = dz32[z]; }
+  for (int k = 0; k < ns; k++) {
+    const int p = prof_of[(size_t)k];
+    const int64_t left = (int64_t)tu.total[(size_t)p] - (int64_t)ndone[(size_t)k];       // (helper pairs, xj < 0, are marked done by k_lazy_bound)
+    const int64_t hi = (int64_t)dz32[(size_t)p] + std::max<int64_t>(0, left);
+    if (hi < ctx->domz_ub[(size_t)p]) { ctx->domz_ub[(size_t)p] = hi; ctx->domz_ub_loc[(size_t)p] = hi; }
+    if (sw_get("ITSX_LAZY_HIST")) fprintf(stderr, "[itsx] top-up: profile %d now %d .. %lld\n", p, dz32[(size_t)p], (long long)ctx->domz_ub[(size_t)p]);
+  }
+  return ITSX_OK;
+}
+
 // The top-up round (round 6).  A row is undecided when domE / P-value lies between the bounds on its profile's domZ -- the reported
 // targets among the EVALUATED pairs below, the pairs past the MSV filter above.  On amplicon data nearly every pair past the filter is a
 // reported target, so the truth is almost always "domZ is far larger, the row is not reported", and proving it does not take the exact
 // count (itsx_lazy_complete: every pair of the profile through the whole pipeline, 13.7 M pairs for 4 rows at 10 M reads): it takes
 // enough MORE reported targets for the lower bound to pass domE / P-value.  So the profile's unevaluated pairs are ordered by their
-// bound (one radix sort), as many of the best as the rows need (+ 2 %) go through the domain pipeline like a third lazy round, and the
+// bound (one radix sort), as many of the best as the rows need (+ 2 %) go through the domain pipeline -- count-only, see below -- and the
 // thresholds are applied again; what is still undecided then (a row that IS reported, or one whose count lies in the top third of the
 // profile's pairs) is counted in full as before.  The upper bound is tightened on the way: reported among the evaluated + pairs not evaluated.  Exact for the same reason the bounds are: a lower bound that passes domE / P-value decides the row whatever the
 // exact count is.  Only for a search of one chunk and one sample whose lists are still in the buffers; everything else goes straight on.
-static int lazy_topup(itsx_ctx *ctx, double domE, bool *ran)
+// rest (only after a count-only call that took a nearly-needed profile's `need` pairs instead of all of them, ITSX_LAZY_TOPUP_ALL=2): the
+// remaining unevaluated pairs of those profiles whose rows are still undecided, count-only again.
+static int lazy_topup(itsx_ctx *ctx, double domE, bool *ran, bool rest = false)
 {
   (void)domE;
   *ran = false;
+  if (!rest) { ctx->topup_deferred_live = 0; ctx->topup_partial.clear(); }
   const auto &tu = ctx->topup;
   if (sw_get("ITSX_LAZY_HIST")) fprintf(stderr, "[itsx] top-up: valid %d chunks %d samples %d pairs %lld\n", (int)tu.valid, ctx->n_chunks, ctx->S, (long long)tu.NP);
   if (!tu.valid || ctx->n_chunks != 1 || ctx->S != 1 || tu.NP <= 0) return ITSX_OK;
@@ -4154,6 +4218,7 @@ static int lazy_topup(itsx_ctx *ctx, double domE, bool *ran)
   for (int p = 0; p < P; p++) {
     if (!ctx->lazy_pending_prof[(size_t)p]) continue;
     if (ctx->h_zneed[(size_t)2 * p] == 0 && ctx->h_zneed[(size_t)2 * p + 1] == ~0ull) continue;
+    if (rest && std::find(ctx->topup_partial.begin(), ctx->topup_partial.end(), p) == ctx->topup_partial.end()) continue;
     slot[(size_t)p] = (int32_t)prof_of.size(); prof_of.push_back(p);
   }
   const int ns = (int)prof_of.size();
@@ -4162,18 +4227,6 @@ static int lazy_topup(itsx_ctx *ctx, double domE, bool *ran)
   const int64_t NP = tu.NP;
   HIPCHK(upload(ctx->l_slot, slot, st)); HIPCHK(upload(ctx->l_pslot, prof_of, st));
   HIPCHK(upload(ctx->w_idx, tu.seg_start, st)); HIPCHK(upload(ctx->w_rcnt, tu.total, st));
-  // evaluated pairs per profile so far: the upper bound on its domZ is (reported among them) + (pairs not evaluated)
-  auto count_done = [&](std::vector<unsigned long long> &out) -> int {
-    HIPCHK(ctx->l_tcnt.alloc((size_t)ns));
-    HIPCHK(hipMemsetAsync(ctx->l_tcnt.p, 0, (size_t)ns * sizeof(unsigned long long), st));
-    launch_topup_count(ctx->l_done.p, ctx->w_idx.p, ctx->w_rcnt.p, ctx->l_pslot.p, ns, ctx->l_tcnt.p, st);
-    out.assign((size_t)ns, 0);
-    HIPCHK(hipMemcpyAsync(out.data(), ctx->l_tcnt.p, (size_t)ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return ITSX_OK;
-  };
-  std::vector<unsigned long long> ndone;
-  { const int rc = count_done(ndone); if (rc != ITSX_OK) return rc; }
   // the unevaluated pairs of those profiles, compact (a few per cent of the list), then ordered by (profile, bound descending)
   const int64_t nch = (NP + 63) >> 6;                           // (the chunk buffers are lazy_rounds' own: the same list)
   launch_topup_keys(ctx->d_pairs.p, NP, ctx->l_done.p, ctx->l_b10.p, ctx->l_slot.p, ctx->l_smask.p, ctx->l_scnt.p, nullptr, nullptr, nullptr, st);
@@ -4223,14 +4276,23 @@ static int lazy_topup(itsx_ctx *ctx, double domE, bool *ran)
     // pair evaluated once, the count exact), and what itsx_lazy_complete would do for it -- the filter again on the profile, every pair of
     // it through the pipeline again, the evaluated ones a second time, in an invocation of its own with its own ensemble batch -- is not
     // needed (10 M reads: top-up 89 + full count 165 ms -> one round of 2xx ms).  ITSX_LAZY_TOPUP_ALL=0: left to the full count as before.
+    // ITSX_LAZY_TOPUP_ALL=2 (count-only rounds; read at every call): a round that only counts is cheap enough to come twice, so a row
+    // that the lower bound settles takes its `need` best pairs like every other profile's, and the profile's remaining pairs follow in a
+    // count-only sub-round of their own only if the row is still undecided then (`rest`).
     static const bool topup_all = !(sw_get("ITSX_LAZY_TOPUP_ALL") && atoi(sw_get("ITSX_LAZY_TOPUP_ALL")) == 0);
+    const bool by_need = sw_get("ITSX_LAZY_TOPUP_ALL") && atoi(sw_get("ITSX_LAZY_TOPUP_ALL")) == 2 && !(sw_get("ITSX_TOPUP_COUNT_ONLY") && atoi(sw_get("ITSX_TOPUP_COUNT_ONLY")) == 0);
     const bool above = zh != ~0ull && hi > (int64_t)zh;      // a row that only the upper bound settles: its count lies in the top third of the profile's pairs
-    if ((above && !both) || from_top + from_bottom > have - have / 3) {
-      if (!topup_all) continue;
+    // (by need, such a row is asked from below as well: zh is the SMALLEST Z* past the split, so the lower bound reaching it settles that row at
+    // least; the rows with a larger one, if there are any, are what the rest sub-round is for)
+    if (by_need && !rest && above && from_bottom == 0 && (int64_t)zh > lo) { const int64_t need = (int64_t)zh - lo; from_top = std::max(from_top, need + need / 50 + 64); }
+    const bool partial = by_need && !rest && from_bottom == 0 && from_top > 0 && from_top < have;
+    if (rest || (!partial && ((above && !both) || from_top + from_bottom > have - have / 3))) {
+      if (!topup_all && !rest) continue;
       cut[(size_t)2 * k] = 1u; cut[(size_t)2 * k + 1] = 0u;      // (every bound is at least 1: k_lazy_bound)
       any = true;
       continue;
     }
+    if (partial && (above || from_top > have - have / 3)) ctx->topup_partial.push_back(p);
     unsigned long long v = 0;
     if (from_top > 0) {
       HIPCHK(hipMemcpy(&v, ctx->sh_keys2.p + a + from_top - 1, 8, hipMemcpyDeviceToHost));
@@ -4246,30 +4308,65 @@ static int lazy_topup(itsx_ctx *ctx, double domE, bool *ran)
   if (!any) return ITSX_OK;
   HIPCHK(upload(ctx->l_cut, cut, st));
   launch_topup_mark(ctx->d_pairs.p, NP, ctx->l_done.p, ctx->l_b10.p, ctx->l_slot.p, ctx->l_cut.p, ctx->l_smask.p, ctx->l_scnt.p, st);
+  // The round wants ONE number per profile -- how many of these pairs are reported targets -- and no row of theirs can win or tie (they are
+  // unevaluated after round 2: below their group's best certain row).  So the pipeline runs count-only (ITSX_TOPUP_COUNT_ONLY=0: as a third
+  // lazy round, rows and ensemble stage included): pairs with a multidomain region are deferred, the ensemble stage is not launched.
+  const bool count_only = !(sw_get("ITSX_TOPUP_COUNT_ONLY") && atoi(sw_get("ITSX_TOPUP_COUNT_ONLY")) == 0);      // (read at every call)
   PairList sub; int64_t nsel = 0;
-  { const int rc = select_compact(ctx, ctx->d_pairs.p, NP, P, tu.seg_start, ctx->w_seg_start.p, sub, nsel); if (rc != ITSX_OK) return rc; }
+  { const int rc = select_compact(ctx, ctx->d_pairs.p, NP, P, tu.seg_start, ctx->w_seg_start.p, sub, nsel, count_only); if (rc != ITSX_OK) return rc; }
   if (sub.NP == 0) return ITSX_OK;
+  if (count_only) {
+    HIPCHK(ctx->l_dmask.alloc((size_t)nch + 1)); HIPCHK(ctx->l_defn.alloc(2));
+    if (!rest) HIPCHK(hipMemsetAsync(ctx->l_dmask.p, 0, ((size_t)nch + 1) * sizeof(unsigned long long), st));      // (rest: the first call's bits stay)
+    HIPCHK(hipMemsetAsync(ctx->l_defn.p, 0, 2 * sizeof(unsigned long long), st));      // (counts the pairs whose bit is new)
+  }
   const int32_t *d_sorted = (ctx->share_on ? ctx->sh_order.p : ctx->d_sorted_uniq.p) + tu.u0;
   ctx->trace_u0 = tu.u0;
-  { StageTimer tp(st); const int rc = domain_pipeline(ctx, sub, d_sorted, ctx->T, ctx->sF1, ctx->sF3, nullptr); if (rc != ITSX_OK) return rc; S.ms_lazy_topup_stages += tp.stop(); }
-  // the bounds after the round: reported among the evaluated pairs below, those + the pairs still not evaluated above
-  std::vector<int32_t> dz32((size_t)P * ctx->S, 0);
-  HIPCHK(hipMemcpyAsync(dz32.data(), ctx->d_domz32.p, dz32.size() * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(upload(ctx->w_idx, tu.seg_start, st)); HIPCHK(upload(ctx->w_rcnt, tu.total, st));      // (the pipeline used the buffers)
-  { const int rc = count_done(ndone); if (rc != ITSX_OK) return rc; }
-  for (size_t z = 0; z < dz32.size(); z++) { ctx->domz_loc[z] = dz32[z]; ctx->domz[z] = dz32[z]; }
-  for (int k = 0; k < ns; k++) {
-    const int p = prof_of[(size_t)k];
-    const int64_t left = (int64_t)tu.total[(size_t)p] - (int64_t)ndone[(size_t)k];       // (helper pairs, xj < 0, are marked done by k_lazy_bound)
-    const int64_t hi = (int64_t)dz32[(size_t)p] + std::max<int64_t>(0, left);
-    if (hi < ctx->domz_ub[(size_t)p]) { ctx->domz_ub[(size_t)p] = hi; ctx->domz_ub_loc[(size_t)p] = hi; }
-    if (sw_get("ITSX_LAZY_HIST")) fprintf(stderr, "[itsx] top-up: profile %d now %d .. %lld\n", p, dz32[(size_t)p], (long long)ctx->domz_ub[(size_t)p]);
+  { StageTimer tp(st); const int rc = domain_pipeline(ctx, sub, d_sorted, ctx->T, ctx->sF1, ctx->sF3, nullptr, count_only); if (rc != ITSX_OK) return rc; S.ms_lazy_topup_stages += tp.stop(); }
+  unsigned long long ndef = 0;
+  if (count_only) HIPCHK(hipMemcpyAsync(&ndef, ctx->l_defn.p, sizeof(ndef), hipMemcpyDeviceToHost, st));      // (topup_bounds waits for the stream)
+  if (!rest) ctx->topup_profs = prof_of;                  // (rest: a subset of them)
+  { const int rc = topup_bounds(ctx, count_only); if (rc != ITSX_OK) return rc; }
+  // (a deferred pair counts when and if it is evaluated; a rest call selects the first call's deferred pairs of its profiles again -- they
+  // are unevaluated -- and defers them again: new bits are the ones it counts)
+  if (rest && count_only) {
+    unsigned long long again = 0;
+    HIPCHK(hipMemcpy(&again, ctx->l_defn.p + 1, sizeof(again), hipMemcpyDeviceToHost));
+    nsel -= (int64_t)again;
   }
+  nsel -= (int64_t)ndef;
+  if (rest) { ctx->n_topup_deferred += (int64_t)ndef; ctx->topup_deferred_live += (int64_t)ndef; }
+  else { ctx->n_topup_deferred = (int64_t)ndef; ctx->topup_deferred_live = (int64_t)ndef; }
   S.n_lazy_evaluated += nsel; S.n_lazy_topup += nsel;
   S.n_rows_resident = 0;
   for (int64_t r : ctx->dom_n) S.n_rows_resident += r;
   S.ms_lazy_topup += tm.stop();
   *ran = true;
+  return ITSX_OK;
+}
+
+// The top-up round's second sub-round: the pairs the count-only round deferred (their bits are in l_dmask), and only they, through the
+// ordinary pipeline -- ensemble stage, rows and all.  Taken when a row of the round's profiles is still undecided without them.
+static int lazy_topup_deferred(itsx_ctx *ctx)
+{
+  const auto &tu = ctx->topup;
+  hipStream_t st = ctx->st;
+  itsx_stats &S = ctx->stats;
+  StageTimer tm(st);
+  ctx->topup_deferred_live = 0;
+  launch_topup_deferred_select(ctx->l_dmask.p, tu.NP, ctx->l_smask.p, ctx->l_scnt.p, ctx->l_done.p, st);
+  PairList sub; int64_t nsel = 0;
+  { const int rc = select_compact(ctx, ctx->d_pairs.p, tu.NP, ctx->P, tu.seg_start, ctx->w_seg_start.p, sub, nsel); if (rc != ITSX_OK) return rc; }
+  if (sub.NP == 0) return ITSX_OK;
+  const int32_t *d_sorted = (ctx->share_on ? ctx->sh_order.p : ctx->d_sorted_uniq.p) + tu.u0;
+  ctx->trace_u0 = tu.u0;
+  { StageTimer tp(st); const int rc = domain_pipeline(ctx, sub, d_sorted, ctx->T, ctx->sF1, ctx->sF3, nullptr); if (rc != ITSX_OK) return rc; S.ms_lazy_topup_stages += tp.stop(); }
+  { const int rc = topup_bounds(ctx, false); if (rc != ITSX_OK) return rc; }
+  S.n_lazy_evaluated += nsel; S.n_lazy_topup += nsel;
+  ctx->n_topup_ensemble = 1;
+  S.n_rows_resident = 0;
+  for (int64_t r : ctx->dom_n) S.n_rows_resident += r;
+  S.ms_lazy_topup += tm.stop();
   return ITSX_OK;
 }
 
@@ -4304,6 +4401,36 @@ int itsx_search_finalize(itsx_ctx *ctx, double domE)
         if (ran) {
           { const int rc = finalize_lazy(ctx, domE); if (rc != ITSX_OK) return rc; }
           ctx->stats.n_lazy_pending = pend;
+          // the count-only round deferred pairs and a row of its profiles is still undecided: those pairs, through the ensemble stage
+          // (test hook ITSX_TOPUP_FORCE_SECOND: as if the first sub-round had not settled its rows)
+          // (ITSX_LAZY_TOPUP_ALL=2: first the remaining pairs of a profile that took only what its row needed and is still undecided)
+          bool more = false;
+          if (ctx->lazy_pending > 0) for (int32_t p : ctx->topup_partial) more = more || ctx->lazy_pending_prof[(size_t)p] != 0;
+          if (more) {
+            bool ran2 = false;
+            { const int rc = lazy_topup(ctx, domE, &ran2, true); if (rc != ITSX_OK) return rc; }
+            if (ran2) { const int rc = finalize_lazy(ctx, domE); if (rc != ITSX_OK) return rc; ctx->stats.n_lazy_pending = pend; }
+          }
+          bool second = sw_get("ITSX_TOPUP_FORCE_SECOND") && atoi(sw_get("ITSX_TOPUP_FORCE_SECOND")) != 0;
+          // (a profile's deferred pairs are worth their ensemble invocation when they could settle every row of it that is still undecided --
+          // all of them reported targets for the rows that wait for the lower bound, none of them for the rows that wait for the upper one;
+          // a profile they cannot settle is counted in full below, deferred pairs included, whatever this sub-round would have found)
+          if (ctx->lazy_pending > 0 && ctx->S == 1)
+            for (int32_t p : ctx->topup_profs) {
+              const int64_t nd = (size_t)p < ctx->topup_defp.size() ? ctx->topup_defp[(size_t)p] : 0;
+              if (!ctx->lazy_pending_prof[(size_t)p] || nd <= 0) continue;
+              const unsigned long long zl = ctx->h_zneed[(size_t)2 * p], zh = ctx->h_zneed[(size_t)2 * p + 1];
+              if (zl == 0 && zh == ~0ull) continue;
+              const int64_t lo = ctx->domz[(size_t)p], hi = std::max(ctx->domz_ub[(size_t)p], lo);
+              const bool below = zl == 0 || (int64_t)zl <= lo || (int64_t)zl - lo + 1 <= nd;
+              const bool above = zh == ~0ull || hi <= (int64_t)zh || hi - (int64_t)zh + 1 <= nd;
+              second = second || (below && above);
+            }
+          if (second && ctx->topup_deferred_live > 0) {
+            { const int rc = lazy_topup_deferred(ctx); if (rc != ITSX_OK) return rc; }
+            { const int rc = finalize_lazy(ctx, domE); if (rc != ITSX_OK) return rc; }
+            ctx->stats.n_lazy_pending = pend;
+          }
           if (ctx->lazy_pending == 0) {
             ctx->stats.ms_finalize = tm.stop();
             ctx->have_final = true;

@@ -671,7 +671,7 @@ struct ScoreArgs {
   const RegionOut *rout;
   const int64_t *pair_region0;  // [npairs] index of the pair's first compacted region
   const int32_t *upos;          // [nregions] index into rout (distinct envelopes) of each region's result
-  itsx_domain *dom;             // one per region
+  itsx_domain *dom;             // one per region (null: no rows are written, the pairs are only counted)
   int64_t npairs;
   double T;
   // clustered regions of the chunk (null when it has none): a pair's regions are mr[mr_off[pi] .. mr_off[pi + 1])
@@ -721,7 +721,7 @@ void launch_pad_b10(int32_t P, const int64_t *seg_start /*[P + 1]*/, const int32
 void launch_lazy_mark(const LazyArgs &a, int round, hipStream_t st);
 // spos = the exclusive scan of scnt; profile segments (seg_old) start at multiples of 64
 void launch_lazy_scatter(const PairRec *pairs, int64_t NP, const unsigned long long *smask, const int32_t *spos, const int64_t *seg_old, const int64_t *seg_new,
-                         PairRec *out, hipStream_t st);
+                         PairRec *out, hipStream_t st, int32_t *src = nullptr /* [new list] each pair's index in the old one */);
 // three-valued thresholds with bounds on hmmsearch's domZ: dom_reported = 1 reported for every domZ in [zlb, zub], 0 for none, 2 = depends
 void launch_finalize_lazy(itsx_domain *dom, int64_t n, const int64_t *zlb, const int64_t *zub, double domE, const int32_t *usample, int P, hipStream_t st);
 // best sure row per (representative, class) and "has a sure row" per representative; then the rows whose status matters
@@ -732,5 +732,10 @@ void launch_topup_count(const uint8_t *done, const int64_t *seg_start, const int
 void launch_topup_keys(const PairRec *pairs, int64_t NP, const uint8_t *done, const uint32_t *b10, const int32_t *slot_of_prof, unsigned long long *smask, int32_t *scnt, const int32_t *spos /*nullptr: marks only*/,
                        unsigned long long *keys, int32_t *vals, hipStream_t st);
 void launch_topup_mark(const PairRec *pairs, int64_t NP, uint8_t *done, const uint32_t *b10, const int32_t *slot_of_prof, const uint32_t *cutoff, unsigned long long *smask, int32_t *scnt, hipStream_t st);
+// the count-only top-up round: pairs of its list with a multidomain region (mrcnt > 0) leave the list (ndom = 0), are unevaluated again
+// (done[src] = 0), counted (n) and remembered (dmask, one bit per pair of the search's list); and those pairs as a selection of their own
+void launch_topup_defer(PairOut *pout, const int32_t *mrcnt, const int32_t *src, int64_t npairs, uint8_t *done, unsigned long long *dmask, unsigned long long *n, hipStream_t st);
+void launch_topup_count_mask(const unsigned long long *dmask, const int64_t *seg_start, const int32_t *total, const int32_t *prof_of_slot, int nslots, unsigned long long *cnt, hipStream_t st);
+void launch_topup_deferred_select(const unsigned long long *dmask, int64_t NP, unsigned long long *smask, int32_t *scnt, uint8_t *done, hipStream_t st);
 
 }  // namespace itsx

@@ -1198,6 +1198,7 @@ DEV void emit_domain(const ScoreArgs &a, int64_t slot, const PairRec &pr, const 
                      float domcorr, int dom_idx, int ndom, int poflags, float nullsc, float seq_score, float final_bias, int seq_rep,
                      int L, double lognn3, double log_omega)
 {
+  if (!a.dom) return;
   itsx_domain o;
   const int Ld = rg.jenv - rg.ienv + 1;
   float bits = (float)((double)ro.envsc + (double)(L - Ld) * lognn3);

@@ -615,7 +615,7 @@ __global__ void __launch_bounds__(256) k_lazy_mark(LazyArgs a)
 constexpr int SCATTER_CHUNKS = 16;
 __global__ void __launch_bounds__(256) k_lazy_scatter(const PairRec *__restrict__ pairs, int64_t NP, const unsigned long long *__restrict__ smask,
                                                       const int32_t *__restrict__ spos, const int64_t *__restrict__ seg_old,
-                                                      const int64_t *__restrict__ seg_new, PairRec *__restrict__ out)
+                                                      const int64_t *__restrict__ seg_new, PairRec *__restrict__ out, int32_t *__restrict__ src)
 {
   const int lane = threadIdx.x & 63;
   const int64_t nch = (NP + 63) >> 6;
@@ -629,6 +629,7 @@ __global__ void __launch_bounds__(256) k_lazy_scatter(const PairRec *__restrict_
     const PairRec pr = pairs[i];
     const int32_t rank = spos[c] + (int32_t)__popcll(m & ((1ull << lane) - 1ull)) - spos[seg_old[pr.prof] >> 6];
     out[seg_new[pr.prof] + (int64_t)rank] = pr;
+    if (src) src[seg_new[pr.prof] + (int64_t)rank] = (int32_t)i;     // (the count-only top-up round finds a pair's done flag again by it)
   }
 }
 
@@ -719,10 +720,10 @@ void launch_lazy_mark(const LazyArgs &a, int round, hipStream_t st)
   }
 }
 void launch_lazy_scatter(const PairRec *pairs, int64_t NP, const unsigned long long *smask, const int32_t *spos, const int64_t *seg_old, const int64_t *seg_new,
-                         PairRec *out, hipStream_t st)
+                         PairRec *out, hipStream_t st, int32_t *src)
 {
   const int64_t nch = (NP + 63) >> 6, per_block = 4 * SCATTER_CHUNKS;
-  if (NP > 0) hipLaunchKernelGGL(k_lazy_scatter, dim3((unsigned)((nch + per_block - 1) / per_block)), dim3(256), 0, st, pairs, NP, smask, spos, seg_old, seg_new, out);
+  if (NP > 0) hipLaunchKernelGGL(k_lazy_scatter, dim3((unsigned)((nch + per_block - 1) / per_block)), dim3(256), 0, st, pairs, NP, smask, spos, seg_old, seg_new, out, src);
 }
 void launch_finalize_lazy(itsx_domain *dom, int64_t n, const int64_t *zlb, const int64_t *zub, double domE, const int32_t *usample, int P, hipStream_t st)
 {
@@ -835,6 +836,56 @@ void launch_topup_mark(const PairRec *pairs, int64_t NP, uint8_t *done, const ui
                        unsigned long long *smask, int32_t *scnt, hipStream_t st)
 {
   hipLaunchKernelGGL(k_topup_mark, dim3(select_grid(NP)), dim3(256), 0, st, pairs, NP, done, b10, slot_of_prof, cutoff, smask, scnt);
+}
+
+// ---- the count-only top-up round.  A pair of the round's list that has a multidomain region (mrcnt > 0: k_mr_count) is DEFERRED: the
+// round wants a count, and that pair's verdict would take the ensemble stage.  It leaves the list's later stages (no envelope: ndom = 0,
+// so the region list, the envelope kernels and k_score pass it by), it is unevaluated again in the search's own list (done = 0 at src:
+// it stays on the upper bound's side), and its bit in dmask (zeroed by the caller) lets a second sub-round take exactly these pairs.
+__global__ void __launch_bounds__(256) k_topup_defer(PairOut *__restrict__ pout, const int32_t *__restrict__ mrcnt, const int32_t *__restrict__ src, int64_t npairs,
+                                                     uint8_t *__restrict__ done, unsigned long long *__restrict__ dmask, unsigned long long *__restrict__ n)
+{
+  const int64_t pi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pi >= npairs || mrcnt[pi] <= 0) return;
+  pout[pi].ndom = 0;
+  const int64_t i = src[pi];
+  done[i] = 0;
+  const unsigned long long bit = 1ull << (i & 63);
+  atomicAdd(&n[(atomicOr(&dmask[i >> 6], bit) & bit) ? 1 : 0], 1ull);      // n[0]: deferred for the first time, n[1]: again
+}
+// the deferred pairs as a selection of the search's list (smask / scnt as k_lazy_mark leaves them, chunk nch included), marked evaluated
+__global__ void __launch_bounds__(256) k_topup_deferred_select(const unsigned long long *__restrict__ dmask, int64_t nch, unsigned long long *__restrict__ smask,
+                                                               int32_t *__restrict__ scnt, uint8_t *__restrict__ done)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c > nch) return;
+  unsigned long long m = c < nch ? dmask[c] : 0ull;
+  smask[c] = m; scnt[c] = (int32_t)__popcll(m);
+  while (m) { const int b = __ffsll((long long)m) - 1; done[c * 64 + b] = 1; m &= m - 1; }
+}
+// the deferred pairs of the listed profiles: cnt[slot] (zeroed) = bits of dmask in the profile's segment (segments start at whole chunks)
+__global__ void __launch_bounds__(256) k_topup_count_mask(const unsigned long long *__restrict__ dmask, const int64_t *__restrict__ seg_start, const int32_t *__restrict__ total,
+                                                          const int32_t *__restrict__ prof_of_slot, unsigned long long *__restrict__ cnt)
+{
+  const int sl = blockIdx.y, p = prof_of_slot[sl];
+  const int64_t c0 = seg_start[p] >> 6, n = ((int64_t)total[p] + 63) >> 6;
+  unsigned long long c = 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) c += (unsigned long long)__popcll(dmask[c0 + i]);
+  for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(&cnt[sl], c);
+}
+void launch_topup_count_mask(const unsigned long long *dmask, const int64_t *seg_start, const int32_t *total, const int32_t *prof_of_slot, int nslots, unsigned long long *cnt, hipStream_t st)
+{
+  if (nslots > 0) hipLaunchKernelGGL(k_topup_count_mask, dim3(64, (unsigned)nslots), dim3(256), 0, st, dmask, seg_start, total, prof_of_slot, cnt);
+}
+void launch_topup_defer(PairOut *pout, const int32_t *mrcnt, const int32_t *src, int64_t npairs, uint8_t *done, unsigned long long *dmask, unsigned long long *n, hipStream_t st)
+{
+  if (npairs > 0) hipLaunchKernelGGL(k_topup_defer, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, pout, mrcnt, src, npairs, done, dmask, n);
+}
+void launch_topup_deferred_select(const unsigned long long *dmask, int64_t NP, unsigned long long *smask, int32_t *scnt, uint8_t *done, hipStream_t st)
+{
+  const int64_t nch = (NP + 63) >> 6;
+  hipLaunchKernelGGL(k_topup_deferred_select, dim3((unsigned)((nch + 1 + 255) / 256)), dim3(256), 0, st, dmask, nch, smask, scnt, done);
 }
 
 }  // namespace itsx

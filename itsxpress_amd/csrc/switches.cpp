@@ -18,6 +18,7 @@ static const Switch g_sw[] = {
   {"ITSX_PASSA_DBG", SW_HOOK, "pass A diagnostic bits (no rows / no restore / no join): timings only, scores are garbage; 64: the shared MSV kernel counts its floored wave-rows, those with the xB branch and its waves by word layout (results unchanged; one stderr line per search)"},
   {"ITSX_MSV_PB", SW_HOOK, "profiles one block of the MSV filter takes its sequences through (1 .. 32; default: by the job's size, 1 for a small job): same cells"},
   {"ITSX_TWRITER_HOST_SLICE", SW_HOOK, "=1: a streamed writer with a device (itsx_twriter_set_device) slices every unit on the host, as it does a unit its line index does not fit (same file bytes)"},
+  {"ITSX_TOPUP_FORCE_SECOND", SW_HOOK, "=1: the top-up round's second sub-round (the deferred pairs through the ensemble stage) runs as if the count-only sub-round had left rows undecided (same rows)"},
   // ---- MODEs
   {"ITSX_ROWS", SW_MODE, "rows mode when the caller did not call itsx_set_rows_mode: full | compact | lazy (coordinates identical in all three)"},
   {"ITSX_COMPACT_ROWS", SW_MODE, "=1: rows mode compact (older spelling of ITSX_ROWS=compact)"},
@@ -64,7 +65,8 @@ static const Switch g_sw[] = {
   {"ITSX_MR_LONG_FRAC", SW_TUNING, "ensemble stage: share of regions taken as 'long'"},
   {"ITSX_MR_LONG_LANES", SW_TUNING, "ensemble stage: lanes per long region"},
   {"ITSX_MSV_BWD_WHOLE", SW_TUNING, "=1: the MSV filter's Backward chains copy their whole read to LDS first (A/B arm: same cells)"},
-  {"ITSX_LAZY_TOPUP_ALL", SW_TUNING, "=0: a profile whose undecided rows need most of its pairs is left to the full count (itsx_lazy_complete) instead of taking all its unevaluated pairs in the top-up round (same rows)"},
+  {"ITSX_LAZY_TOPUP_ALL", SW_TUNING, "=0: a profile whose undecided rows need most of its pairs is left to the full count (itsx_lazy_complete) instead of taking all its unevaluated pairs in the top-up round; =2 (with the count-only round): such a profile takes what its row needs like any other, and its remaining pairs follow in a count-only sub-round of their own only if the row is still undecided (same coordinates; read at every call)"},
+  {"ITSX_TOPUP_COUNT_ONLY", SW_TUNING, "=0: the top-up round sends its pairs through the whole domain pipeline like a third lazy round (rows kept, an ensemble invocation of its own) instead of counting reported targets only and deferring the pairs with a multidomain region (A/B arm and cross-check: same coordinates)"},
   {"ITSX_MR_WAVES", SW_TUNING, "ensemble stage: waves a batch is spread over (lanes per wave = regions / this, 2 .. 64); 0 = waves of 64 lanes"},
   {"ITSX_MR_ONE_MAX", SW_TUNING, "ensemble stage: a batch of at most this many regions (default 2048) is walked one region per wave with the matrix in LDS; 0 = never"},
   {"ITSX_CIGAR_MB", SW_TUNING, "itsx_align_clusters: byte budget of one batch of pairs (direction bits and border rows), MB (default 2048; a small value forces several batches, and a pair larger than it runs alone: same alignments)"},

@@ -850,7 +850,12 @@ class Engine:
     def stats(self):
         s = np.zeros(1, STATS_DTYPE_ALL)
         self._chk(self.L.itsx_get_stats(self.h, s.ctypes.data, STATS_DTYPE_ALL.itemsize))
-        return {k: (s[0][k].item() if s[0][k].ndim == 0 else s[0][k].tolist()) for k in STATS_DTYPE_ALL.names}
+        out = {k: (s[0][k].item() if s[0][k].ndim == 0 else s[0][k].tolist()) for k in STATS_DTYPE_ALL.names}
+        # the count-only top-up round's counters (itsx_topup_counters: itsx_stats itself keeps its size)
+        t = np.zeros(2, np.int64)
+        self._chk(self.L.itsx_topup_counters(self.h, t.ctypes.data))
+        out["n_topup_deferred"], out["n_topup_ensemble"] = int(t[0]), int(t[1])
+        return out
 
     def release_scratch(self):
         """hand the context's DP slab (tens of GB) to the next context of this process on the device: a streamed file's chunk after
