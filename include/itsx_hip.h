@@ -309,7 +309,8 @@ int itsx_select_sample(itsx_ctx *ctx, int32_t sample);
  * (itsx_get_pairtraces) are the unshared search's too: every member gets its holder's traces with `rep` rewritten.  itsx_stats
  * describes the work done: the pairs, cells, rows and times of the holders.
  * Does not apply (accepted, and itsx_sample_sharing_info reports zero classes): one sample; the compact and lazy rows modes, which keep
- * their domZ bounds, top-up round and verdicts per (sample, profile); a context whose active uniques the caller chose
+ * their domZ bounds, top-up round and verdicts per (sample, profile) and have a setting of their own
+ * (itsx_set_sample_sharing_lazy, below); a context whose active uniques the caller chose
  * (itsx_set_active_uniques, and with it the itsx_unique_keys-driven sharded runs).  ITSX_SHARE_SAMPLES=1 does the same for every
  * context. */
 int itsx_set_sample_sharing(itsx_ctx *ctx, int on);
@@ -319,6 +320,29 @@ int itsx_set_sample_sharing(itsx_ctx *ctx, int on);
  * common, the classes are built all the same: n_classes == n_unique, nothing shared, nothing copied, and the search itself runs as
  * without the mode.  Each pointer may be NULL.  ITSX_E_ARG before a search. */
 int itsx_sample_sharing_info(const itsx_ctx *ctx, int64_t *n_classes, int64_t *n_uniques_shared, int64_t *n_rows_expanded);
+/* ---- sample sharing in the lazy and compact rows modes (opt-in; a setting of its own: itsx_set_sample_sharing keeps governing the
+ * full rows mode alone, and this one has no effect there).  The plugin's loop (itsxpress/q2_itsxpress.py:273-333) is where both of
+ * the batch's large savings count -- evaluating only the pairs that can still win, and scoring a shared sequence once -- and with this
+ * setting a lazy or compact search of S > 1 samples takes both: the score classes are built as above, the MSV filter, pass A, the
+ * lazy rounds and the domain pipeline walk the holders only, and
+ *   - every evaluated pair that is a reported target adds one to the domZ counter of EVERY member's sample (csrc/k_derep.hip:
+ *     k_member_*, over the chunk's scratch rows before compaction drops them: exact, since the members of a class lie in different
+ *     samples and their residues, hence their scores, are the holder's);
+ *   - the upper counter of a lazy search adds the HOLDERS past the MSV filter to every sample.  It stays an upper bound: a sample
+ *     holds at most one member of a class, so the classes past the filter are at least any one sample's uniques past it;
+ *   - the rows the search KEPT are copied to the other members with `rep` rewritten before any finalize (n_rows_expanded counts
+ *     them), so finalize, the coordinates, the writers and itsx_align_domains see a member's rows under its own sample's counters.
+ * itsx_lazy_complete (and itsx_search_finalize through it) walks the holders again, counts members the same way and copies the rows
+ * of the segments it adds; afterwards lower == upper == the exact count for every (sample, completed profile).  The compact re-search
+ * that finalize keeps as a safety net is a sharing search itself.  Coordinates, uc.txt, rep.fa and the kept rows' domtbl.txt are
+ * those of a search without the setting; the lazy counters are valid bounds on hmmsearch's domZ either way, though not necessarily
+ * the same bounds (which pairs the lazy rounds evaluate may depend on the last bits of pass A's scores, and those on the prefix
+ * tree of the uniques searched); the compact mode's counters are exact and equal.  itsx_stats describes the holders' work, as in
+ * the full mode; the pair traces of a compact search are mapped to the members as there, and itsx_debug_lazy_pairs serves one
+ * sample only, so it never follows such a search.  Applies when: the setting is on (or ITSX_SHARE_SAMPLES_LAZY=1), S > 1, the
+ * rows mode of the search is compact or lazy, and the caller has not narrowed the active uniques.  Not changed: counters exchanged
+ * between ranks (itsx_set_domz / itsx_domz_device) at S > 1 -- a combination nothing uses -- behave as before. */
+int itsx_set_sample_sharing_lazy(itsx_ctx *ctx, int on);
 /* the mode's own two steps in that search, milliseconds: building the classes, and copying rows and counting (what the saved
  * hmmsearch work of q2_itsxpress.py:273-333 is paid with; scripts/batch_bench.py reports both).  Each is the span between two HIP
  * events on the engine's stream around the whole step, so it holds the step's kernels AND the host synchronisations and small

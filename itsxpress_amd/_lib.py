@@ -106,7 +106,7 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_parse_pairs_device", "itsx_parse_pairs_fetch", "itsx_debug_parse_pairs_host", "itsx_debug_pair_pass_host",
            "itsx_debug_set_domains", "itsx_debug_get_rows",
            "itsx_debug_scan", "itsx_debug_select", "itsx_debug_region_keys", "itsx_debug_lazy_pairs",
-           "itsx_set_sample_sharing", "itsx_sample_sharing_info", "itsx_sample_sharing_times", "itsx_debug_sample_classes",
+           "itsx_set_sample_sharing", "itsx_set_sample_sharing_lazy", "itsx_sample_sharing_info", "itsx_sample_sharing_times", "itsx_debug_sample_classes",
            "itsx_align_domains", "itsx_get_alignments", "itsx_write_domtbl_arrays_ali",
            "itsx_align_clusters", "itsx_get_cluster_cigars",
            "itsx_topup_counters"]
@@ -278,6 +278,7 @@ def lib():
         "itsx_num_samples": (i32, [vp]),
         "itsx_select_sample": (i32, [vp, i32]),
         "itsx_set_sample_sharing": (i32, [vp, i32]),
+        "itsx_set_sample_sharing_lazy": (i32, [vp, i32]),
         "itsx_sample_sharing_info": (i32, [vp, vp, vp, vp]),
         "itsx_sample_sharing_times": (i32, [vp, vp, vp]),
         "itsx_debug_sample_classes": (i32, [vp, vp, i64]),

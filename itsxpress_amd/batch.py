@@ -328,6 +328,16 @@ class SampleBatch:
     def share_samples(self, on: bool):
         self.engine.share_samples = on
 
+    # The same for the lazy / compact searches (ITSXPRESS_DOMTBL=winners, set_rows_mode): the engine's own setting
+    # (Engine.share_samples_lazy, off by default), under the batch's name.  A property, not a constructor keyword
+    @property
+    def share_samples_lazy(self) -> bool:
+        return self.engine.share_samples_lazy
+
+    @share_samples_lazy.setter
+    def share_samples_lazy(self, on: bool):
+        self.engine.share_samples_lazy = on
+
     # Where the engine's whole-file loaders inflate gzip input: the engine's own setting (Engine.inflate), under the batch's name
     @property
     def inflate(self) -> str:

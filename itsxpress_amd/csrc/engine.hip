@@ -374,6 +374,11 @@ struct itsx_ctx {
   // other members.  sc: the last search's figures (all zero when the mode did not apply); sc_*: the classes on the device, rebuilt
   // by every search that shares (class_of [U], holder [C], the members as a CSR list: off [C + 1], members [U] in rising index)
   bool share_samples = false;
+  // the same for the compact and lazy rows modes (itsx_set_sample_sharing_lazy): the chunk loops walk the holders, the members'
+  // reported targets are counted from each chunk's scratch rows before compaction (sc_count_members, set while the holders are
+  // walked: domain_pipeline), the kept rows are copied afterwards.  shared_lazy: the last search was such a one, so itsx_lazy_complete
+  // walks h_sorted_searched again and expands the segments past sc_segs_done
+  bool share_samples_lazy = false, sc_count_members = false, shared_lazy = false; size_t sc_segs_done = 0;
   bool active_narrowed = false;          // the CALLER chose the active uniques (itsx_set_active_uniques): the mode leaves them alone
   struct SampleSharing { int64_t n_classes = 0, n_shared = 0, n_expanded = 0; float ms_classes = 0, ms_expand = 0; } sc;
   // the list the last search walked when it was the holders' (PairRec::useq indexes it: append_traces), and whether the members'
@@ -1459,7 +1464,7 @@ static int build_unique_lists(itsx_ctx *ctx)
     HIPCHK(hipMemcpyAsync(&U, seed_rank.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
   }
-  ctx->U = U; ctx->U_active = U; ctx->active_narrowed = false;
+  ctx->U = U; ctx->U_active = U; ctx->active_narrowed = false; ctx->shared_lazy = false;
   HIPCHK(ctx->d_seed_read.alloc((size_t)U + 1)); HIPCHK(ctx->d_abund.alloc((size_t)U + 1)); HIPCHK(ctx->d_sorted_uniq.alloc((size_t)U + 1));
   HIPCHK(ctx->d_ulen.alloc((size_t)U + 1));
   HIPCHK(hipMemsetAsync(ctx->d_abund.p, 0, ((size_t)U + 1) * sizeof(int32_t), ctx->st));
@@ -2582,6 +2587,12 @@ static bool sample_sharing_wanted(const itsx_ctx *ctx)
   const char *e = sw_get("ITSX_SHARE_SAMPLES");
   return e && atoi(e) == 1;
 }
+static bool sample_sharing_lazy_wanted(const itsx_ctx *ctx)
+{
+  if (ctx->share_samples_lazy) return true;
+  const char *e = sw_get("ITSX_SHARE_SAMPLES_LAZY");
+  return e && atoi(e) == 1;
+}
 // the score classes of the current dereplication (k_derep.hip: k_class_*), on the device; holders [C] on the host
 static int build_sample_classes(itsx_ctx *ctx, std::vector<int32_t> &holders)
 {
@@ -2630,14 +2641,17 @@ static int build_sample_classes(itsx_ctx *ctx, std::vector<int32_t> &holders)
   return ITSX_OK;
 }
 // every non-holder member gets its holder's rows (k_expand_*), one more segment per segment of the search, and its reported targets
-// are counted into its own sample's domZ; then the host's counters follow the device's
-static int expand_shared_rows(itsx_ctx *ctx)
+// are counted into its own sample's domZ; then the host's counters follow the device's.
+// count == false (a lazy / compact sharing search: the segments hold the KEPT rows, and the members were counted chunk by chunk from
+// the scratch rows, count_member_targets): the rows of the segments from seg0 on are copied, nothing is counted, and the figures add
+// to those of the search (itsx_lazy_complete comes here for the segments it added).
+static int expand_shared_rows(itsx_ctx *ctx, size_t seg0 = 0, bool count = true)
 {
   hipStream_t st = ctx->st;
   StageTimer tm(st);
   const size_t nseg = ctx->dom_n.size();
   int64_t expanded = 0;
-  for (size_t c = 0; c < nseg; c++) {
+  for (size_t c = seg0; c < nseg; c++) {
     const int64_t NR = ctx->dom_n[c];
     if (NR <= 0) continue;
     HIPCHK(ctx->sc_cnt.alloc((size_t)NR + 1)); HIPCHK(ctx->sc_pos.alloc((size_t)NR + 1)); HIPCHK(ctx->sc_scan.alloc((size_t)scan_tmp_elems(NR + 1)));
@@ -2657,19 +2671,52 @@ static int expand_shared_rows(itsx_ctx *ctx)
     while (ctx->dom_bufs.size() <= di) ctx->dom_bufs.emplace_back(new DBuf<itsx_domain>());
     HIPCHK(ctx->dom_bufs[di]->alloc((size_t)total));
     launch_expand_rows(ctx->dom_bufs[c]->p, NR, ctx->sc_pos.p, total, ctx->sc_class_of.p, ctx->sc_off.p, ctx->sc_members.p, ctx->dev_usample(), ctx->P,
-                       ctx->dom_bufs[di]->p, ctx->d_domz32.p, st);
+                       ctx->dom_bufs[di]->p, count ? ctx->d_domz32.p : nullptr, st);
     ctx->dom_n[di] = total;
     expanded += total;
   }
-  std::vector<int32_t> dz32((size_t)ctx->P * ctx->S, 0);
-  HIPCHK(hipMemcpyAsync(dz32.data(), ctx->d_domz32.p, dz32.size() * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipGetLastError());
-  ctx->domz_loc.assign(dz32.begin(), dz32.end());
-  ctx->domz = ctx->domz_loc;
+  if (count) {
+    std::vector<int32_t> dz32((size_t)ctx->P * ctx->S, 0);
+    HIPCHK(hipMemcpyAsync(dz32.data(), ctx->d_domz32.p, dz32.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    ctx->domz_loc.assign(dz32.begin(), dz32.end());
+    ctx->domz = ctx->domz_loc;
+    ctx->sc.n_expanded = 0; ctx->sc.ms_expand = 0;
+  } else {
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+  }
+  ctx->sc_segs_done = ctx->dom_n.size();
   ctx->stats.n_rows_resident += expanded;
-  ctx->sc.n_expanded = expanded;
-  ctx->sc.ms_expand = tm.stop();
+  ctx->sc.n_expanded += expanded;
+  ctx->sc.ms_expand += tm.stop();
+  return ITSX_OK;
+}
+// A lazy / compact sharing search, after k_score and before the compaction of the chunk's NR scratch rows at d_rows: every row that
+// k_score counted for its holder's sample (dom_idx == 0, seq_reported) adds one to the counter of every other member's sample
+// (k_derep.hip: k_member_*).  Exact: the members of a class lie in different samples, and a member's own search would have scored the
+// same residues.
+static int count_member_targets(itsx_ctx *ctx, const itsx_domain *d_rows, int64_t NR)
+{
+  if (NR <= 0) return ITSX_OK;
+  hipStream_t st = ctx->st;
+  StageTimer tm(st);
+  HIPCHK(ctx->sc_cnt.alloc((size_t)NR + 1)); HIPCHK(ctx->sc_pos.alloc((size_t)NR + 1)); HIPCHK(ctx->sc_scan.alloc((size_t)scan_tmp_elems(NR + 1)));
+  DBuf<int64_t> &d_c = ctx->w_counters;
+  HIPCHK(d_c.alloc(8));
+  HIPCHK(hipMemsetAsync(d_c.p, 0, sizeof(int64_t), st));
+  launch_member_count(d_rows, NR, ctx->sc_class_of.p, ctx->sc_off.p, ctx->sc_cnt.p, (unsigned long long *)d_c.p, st);
+  int64_t total = 0;
+  HIPCHK(hipMemcpyAsync(&total, d_c.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (total >= 2147483000ll)                  // (the 32-bit scan below)
+    SET_ERR(ctx, ITSX_E_UNSUPPORTED, "sample sharing: " + std::to_string(total) + " member counts from one chunk of the search, more than 2^31 (lower ITSX_CHUNK_UNIQUES or search without sharing)");
+  if (total > 0) {
+    launch_exclusive_scan(ctx->sc_cnt.p, ctx->sc_pos.p, NR + 1, ctx->sc_scan.p, st);
+    launch_member_add(d_rows, NR, ctx->sc_pos.p, total, ctx->sc_class_of.p, ctx->sc_off.p, ctx->sc_members.p, ctx->dev_usample(), ctx->P, ctx->d_domz32.p, st);
+  }
+  ctx->sc.ms_expand += tm.stop();
   return ITSX_OK;
 }
 
@@ -2678,10 +2725,17 @@ int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
   CTXCHK(ctx);
   ctx->sc = itsx_ctx::SampleSharing{};
   ctx->searched_holders = false; ctx->trace_members_done = false;
-  // The mode applies to a full-rows search of S > 1 samples whose active set is the engine's own (the lazy and compact stages keep
-  // their domZ bounds, their top-up round and their verdicts per (sample, profile): there the setting has no effect)
-  if (!sample_sharing_wanted(ctx) || !ctx->have_derep || ctx->P <= 0 || ctx->S <= 1 || ctx->U <= 0 || ctx->active_narrowed ||
-      search_rows_mode(ctx) != ITSX_ROWS_FULL)
+  ctx->sc_count_members = false; ctx->shared_lazy = false; ctx->sc_segs_done = 0;
+  // The mode applies to a search of S > 1 samples whose active set is the engine's own.  Each rows mode has its setting: the full mode
+  // itsx_set_sample_sharing (the rows are copied and counted from afterwards), the lazy and compact modes -- they keep their domZ
+  // bounds and their verdicts per (sample, profile), and their segments hold only the rows that can still win --
+  // itsx_set_sample_sharing_lazy.  That is bookkeeping, not an obstacle: rounds 1 and 2 of lazy_rounds do not depend on the sample
+  // (the bound comes from pass A's score, round 2's threshold is the group's best certain row, reported for every domZ <= 1e9); the
+  // lower counter gets one count per member of an evaluated, reported pair's class (count_member_targets); the upper counter adds the
+  // holders past the filter to every sample (search_chunk); the top-up round runs at S == 1 only; and a kept row depends on the sample
+  // through `rep` alone until k_finalize_lazy.
+  const bool full = search_rows_mode(ctx) == ITSX_ROWS_FULL;
+  if (!(full ? sample_sharing_wanted(ctx) : sample_sharing_lazy_wanted(ctx)) || !ctx->have_derep || ctx->P <= 0 || ctx->S <= 1 || ctx->U <= 0 || ctx->active_narrowed)
     return search_active(ctx, T, F1, F2, F3);
   HIPCHK(hipSetDevice(ctx->device));
   std::vector<int32_t> holders, keep;
@@ -2696,10 +2750,13 @@ int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
   }
   { const int rc = set_walked_uniques(ctx, &keep); if (rc != ITSX_OK) return rc; }
   ctx->h_sorted_searched.swap(keep); ctx->searched_holders = true;      // (kept past the restore below: the pair traces are fetched later)
+  ctx->sc_count_members = !full;
   int rc = search_active(ctx, T, F1, F2, F3);
+  ctx->sc_count_members = false;
   { const int rc2 = set_walked_uniques(ctx, nullptr); if (rc == ITSX_OK) rc = rc2; }      // (every exit leaves the context walking all its uniques again)
-  if (rc == ITSX_OK) rc = expand_shared_rows(ctx);
+  if (rc == ITSX_OK) rc = expand_shared_rows(ctx, 0, full);
   if (rc != ITSX_OK) { ctx->have_search = false; ctx->sc = itsx_ctx::SampleSharing{}; }
+  else ctx->shared_lazy = !full;
   return rc;
 }
 
@@ -2707,6 +2764,12 @@ int itsx_set_sample_sharing(itsx_ctx *ctx, int on)
 {
   CTXCHK(ctx);
   ctx->share_samples = on != 0;
+  return ITSX_OK;
+}
+int itsx_set_sample_sharing_lazy(itsx_ctx *ctx, int on)
+{
+  CTXCHK(ctx);
+  ctx->share_samples_lazy = on != 0;
   return ITSX_OK;
 }
 int itsx_sample_sharing_info(const itsx_ctx *ctx, int64_t *n_classes, int64_t *n_uniques_shared, int64_t *n_rows_expanded)
@@ -3271,6 +3334,7 @@ static int domain_pipeline(itsx_ctx *ctx, const PairList &pl, const int32_t *d_s
     if (NMR > 0) { sa.mr = ctx->w_mr.p; sa.mr_u = ctx->w_mru.p; sa.mrout = ctx->w_mrout.p; sa.n2off = ctx->w_n2off.p; sa.n2sc = ctx->w_n2sc.p; sa.mr_off = ctx->w_mroff.p; }
     sa.domz = ctx->d_domz32.p; sa.usample = ctx->dev_usample(); sa.P = ctx->P;
     launch_score(sa, st);
+    if (ctx->sc_count_members && !count_only) { const int rc = count_member_targets(ctx, d_dom.p, NR); if (rc != ITSX_OK) return rc; }
     if (ctx->compact_rows && !count_only) {
       // keep what can still win once domZ is known, in row order; the chunk's full rows are scratch
       { const int rc = compact_segment(ctx, d_dom.p, NR, di); if (rc != ITSX_OK) return rc; }
@@ -3874,7 +3938,11 @@ static int search_chunk(itsx_ctx *ctx, int ci, int32_t u0, int32_t U, int Lcap, 
   S.ms_msv += tm_list.stop();
   const int64_t zub_scale = sw_get("ITSX_LAZY_ZUB_SCALE") ? std::max<int64_t>(1, atoll(sw_get("ITSX_LAZY_ZUB_SCALE"))) : 1;   // test hook: looser bounds, more undecided rows
   if (!ctx->completing)
-    for (int p = 0; p < P; p++)                   // an upper bound of hmmsearch's domZ: every reported target is a pair past the MSV filter
+    // an upper bound of hmmsearch's domZ: every reported target is a pair past the MSV filter.  Sample-blind: every sample gets the
+    // chunk's count.  In a sharing search (itsx_set_sample_sharing_lazy) real[p] counts the HOLDERS past the filter, and stays a bound
+    // for every sample: a sample holds at most one member of a class, so the classes past the filter for p are at least any one
+    // sample's uniques past it
+    for (int p = 0; p < P; p++)
       for (int32_t sm = 0; sm < ctx->S; sm++) ctx->domz_ub_loc[(size_t)sm * P + p] += (int64_t)real[p] * zub_scale;
   PairList pl;
   pl.pairs = ctx->d_pairs.p; pl.pout = lazy_now ? nullptr : ctx->d_pout.p; pl.NP = NP; pl.seg_start = seg_start; pl.total = total; pl.d_seg_start = d_seg_start.p;
@@ -3956,9 +4024,22 @@ int itsx_lazy_complete(itsx_ctx *ctx, const int32_t *flags)
   HIPCHK(hipStreamSynchronize(st));
   for (int32_t sm = 0; sm < ctx->S; sm++) for (int p : ctx->h_plist) dz32[(size_t)sm * P + p] = 0;
   HIPCHK(hipMemcpyAsync(ctx->d_domz32.p, dz32.data(), dz32.size() * 4, hipMemcpyHostToDevice, st));
+  // after a sharing search (itsx_set_sample_sharing_lazy) the holders are walked again -- the prefix tree, the chunks and the classes
+  // are that search's --, the members are counted as there, and the kept rows of the segments added here are copied to the members
+  const bool shared = ctx->shared_lazy;
+  if (shared) {
+    const int rcw = set_walked_uniques(ctx, &ctx->h_sorted_searched);
+    if (rcw != ITSX_OK) { (void)set_walked_uniques(ctx, nullptr); ctx->have_search = false; return rcw; }
+    ctx->sc_count_members = true;
+  }
   ctx->completing = true;
-  const int rc = run_chunks(ctx, ctx->T, ctx->sF1, ctx->sF3);
+  int rc = run_chunks(ctx, ctx->T, ctx->sF1, ctx->sF3);
   ctx->completing = false;
+  if (shared) {
+    ctx->sc_count_members = false;
+    { const int rc2 = set_walked_uniques(ctx, nullptr); if (rc == ITSX_OK) rc = rc2; }      // (every exit leaves the context walking all its uniques again)
+    if (rc == ITSX_OK) rc = expand_shared_rows(ctx, ctx->sc_segs_done, false);
+  }
   if (rc != ITSX_OK) { ctx->have_search = false; return rc; }
   HIPCHK(hipMemcpyAsync(dz32.data(), ctx->d_domz32.p, dz32.size() * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -4045,7 +4126,7 @@ int itsx_debug_set_domains(itsx_ctx *ctx, const itsx_domain *rows, int64_t n_row
   hipStream_t st = ctx->st;
   const size_t m = (size_t)ctx->P * ctx->S;
   ctx->switches_at_search = sw_report();
-  ctx->searched_holders = false; ctx->h_dom.clear(); ctx->drop_alignments(); ctx->h_trace.clear(); ctx->trace_sorted = false;
+  ctx->searched_holders = false; ctx->shared_lazy = false; ctx->h_dom.clear(); ctx->drop_alignments(); ctx->h_trace.clear(); ctx->trace_sorted = false;
   ctx->domz.assign(m, 0); ctx->domz_ub.assign(m, 0); ctx->domz_loc.assign(m, 0); ctx->domz_ub_loc.assign(m, 0);
   ctx->npairs_padded = 0; ctx->dom_n.clear(); ctx->n_chunks = n_segs;
   ctx->have_search = false; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->topup.list_live = false; ctx->injected = true;

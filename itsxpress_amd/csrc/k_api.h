@@ -49,7 +49,12 @@ void launch_class_offsets(const unsigned long long *sorted_keys, int32_t U, int3
 // *total (zeroed by the caller) += the same sum in 64 bits
 void launch_expand_count(const itsx_domain *dom, int64_t n, const int32_t *class_of, const int32_t *off, int32_t *cnt, unsigned long long *total, hipStream_t st);
 void launch_expand_rows(const itsx_domain *dom, int64_t n, const int32_t *pos, int64_t total, const int32_t *class_of, const int32_t *off,
-                        const int32_t *members, const int32_t *usample, int P, itsx_domain *out, int32_t *domz, hipStream_t st);
+                        const int32_t *members, const int32_t *usample, int P, itsx_domain *out, int32_t *domz, hipStream_t st);      // domz == nullptr: copy only
+// a lazy / compact sharing search's member counting over a chunk's scratch rows (before compaction): cnt / pos / *total as above, but
+// only for the rows k_score counted (dom_idx == 0, seq_reported); domz[usample[member] * P + prof] += 1 per (such row, other member)
+void launch_member_count(const itsx_domain *dom, int64_t n, const int32_t *class_of, const int32_t *off, int32_t *cnt, unsigned long long *total, hipStream_t st);
+void launch_member_add(const itsx_domain *dom, int64_t n, const int32_t *pos, int64_t total, const int32_t *class_of, const int32_t *off,
+                       const int32_t *members, const int32_t *usample, int P, int32_t *domz, hipStream_t st);
 
 // ---- k_cluster.hip (row a2: greedy centroid clustering, speculative windows)
 struct ClusterArgs {

@@ -631,7 +631,52 @@ __global__ void __launch_bounds__(256) k_expand_rows(const itsx_domain *__restri
   const int32_t m = members[off[class_of[d.rep]] + 1 + (int32_t)(o - (int64_t)pos[lo])];
   d.rep = m;
   out[o] = d;
-  if (d.dom_idx == 0 && d.seq_reported) atomicAdd(&domz[(usample ? usample[m] * P : 0) + d.prof], 1);
+  if (domz && d.dom_idx == 0 && d.seq_reported) atomicAdd(&domz[(usample ? usample[m] * P : 0) + d.prof], 1);      // (nullptr: counted already, below)
+}
+// Member counting of a lazy / compact sharing search (itsx_set_sample_sharing_lazy).  There the rows that reach k_expand_rows are the
+// KEPT ones -- compaction has dropped most dom_idx == 0 rows --, so the members' reported targets are counted from the chunk's scratch
+// rows, straight after k_score and before k_compact_*: k_score counts exactly the pairs that leave a row with dom_idx == 0 and
+// seq_reported set, and that pair stands for every member of the holder's class.  Same shape as the expansion: cnt[i] = members of
+// row i's class beside the holder when the row is such a row (else 0), a scan, and one thread per (counted row, member) that finds
+// its row by bisection -- a class of 384 members is 383 threads, not one lane's loop of 383.  The members of one class lie in
+// different samples, but two rows of a wave can meet in one (sample, profile): one atomic per distinct counter per wave, as
+// count_reported (k_float.hip) does.
+__global__ void __launch_bounds__(256) k_member_count(const itsx_domain *__restrict__ dom, int64_t n, const int32_t *__restrict__ class_of,
+                                                      const int32_t *__restrict__ off, int32_t *__restrict__ cnt, unsigned long long *__restrict__ total)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;          // (whole waves: no lane leaves before the reduction)
+  int32_t k = 0;
+  if (i < n) {
+    const itsx_domain &d = dom[i];
+    if (d.dom_idx == 0 && d.seq_reported) { const int32_t c = class_of[d.rep]; k = off[c + 1] - off[c] - 1; }
+  }
+  if (i <= n) cnt[i] = k;
+  unsigned long long w = (unsigned long long)k;
+  for (int s = 32; s >= 1; s >>= 1) w += __shfl_down(w, s, 64);
+  if ((threadIdx.x & 63) == 0 && w) atomicAdd(total, w);
+}
+__global__ void __launch_bounds__(256) k_member_add(const itsx_domain *__restrict__ dom, int64_t n, const int32_t *__restrict__ pos, int64_t total,
+                                                    const int32_t *__restrict__ class_of, const int32_t *__restrict__ off, const int32_t *__restrict__ members,
+                                                    const int32_t *__restrict__ usample, int P, int32_t *__restrict__ domz)
+{
+  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;          // (whole waves: every lane takes part in the ballots)
+  const bool live = o < total;
+  int32_t z = -1;                                                // this lane's counter
+  if (live) {
+    int64_t lo = 0, hi = n;                                      // the last row i with pos[i] <= o, as in k_expand_rows
+    while (hi - lo > 1) { const int64_t mid = lo + ((hi - lo) >> 1); if ((int64_t)pos[mid] <= o) lo = mid; else hi = mid; }
+    const int32_t rep = dom[lo].rep, prof = dom[lo].prof;
+    const int32_t m = members[off[class_of[rep]] + 1 + (int32_t)(o - (int64_t)pos[lo])];
+    z = (usample ? usample[m] * P : 0) + prof;
+  }
+  unsigned long long todo = __ballot(live);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int32_t z0 = __shfl(z, leader, 64);
+    const unsigned long long same = __ballot(live && z == z0) & todo;
+    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&domz[z0], __popcll(same));
+    todo &= ~same;
+  }
 }
 
 void launch_class_insert(const ReadsDev &rd, const int32_t *seed_read, int32_t U, uint64_t seed, unsigned long long *keys, int32_t *vals, uint64_t mask,
@@ -661,6 +706,15 @@ void launch_expand_rows(const itsx_domain *dom, int64_t n, const int32_t *pos, i
                         const int32_t *members, const int32_t *usample, int P, itsx_domain *out, int32_t *domz, hipStream_t st)
 {
   if (total > 0) hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dom, n, pos, total, class_of, off, members, usample, P, out, domz);
+}
+void launch_member_count(const itsx_domain *dom, int64_t n, const int32_t *class_of, const int32_t *off, int32_t *cnt, unsigned long long *total, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_member_count, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, dom, n, class_of, off, cnt, total);
+}
+void launch_member_add(const itsx_domain *dom, int64_t n, const int32_t *pos, int64_t total, const int32_t *class_of, const int32_t *off,
+                       const int32_t *members, const int32_t *usample, int P, int32_t *domz, hipStream_t st)
+{
+  if (total > 0) hipLaunchKernelGGL(k_member_add, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dom, n, pos, total, class_of, off, members, usample, P, domz);
 }
 
 }  // namespace itsx

@@ -27,6 +27,7 @@ static const Switch g_sw[] = {
   {"ITSX_GZIP_LEVEL", SW_MODE, "deflate level of the trimmed-FASTQ writers (default 6; output bytes differ, records do not)"},
   {"ITSX_DEVICE_DEFLATE", SW_MODE, "=1: the batch writers deflate gzip output on the device, and so do the outputs a StreamEngine plans (output bytes differ, records do not)"},
   {"ITSX_SHARE_SAMPLES", SW_MODE, "=1: every context shares the HMM stages across the samples of a batch, as after itsx_set_sample_sharing(ctx, 1) (full rows mode, S > 1; same rows, counters, coordinates and files)"},
+  {"ITSX_SHARE_SAMPLES_LAZY", SW_MODE, "=1: every context shares the HMM stages across the samples of a batch in the compact and lazy rows modes, as after itsx_set_sample_sharing_lazy(ctx, 1) (S > 1; same coordinates and files, valid domZ bounds)"},
   // ---- DIAGnostics
   {"ITSX_TEST_HOOKS", SW_DIAG, "=1: honour the HOOK switches above"},
   {"ITSX_SHARE_CHECK", SW_DIAG, "runs the unshared kernels beside the shared ones and counts differences (itsx_stats.share_mismatch, join_maxdiff)"},

@@ -119,7 +119,7 @@ class Engine:
     # in (itsx_set_sample_sharing): the uniques of all samples whose representatives are the same string in the same orientation form a
     # score class, one holder per class goes through the HMM stages, and every member gets the holder's rows -- the rows, counters,
     # coordinates and domtbl.txt of a search without it, bit for bit.  False (the default) or True; no effect on one sample, in the
-    # compact / lazy rows modes and after set_active_uniques (sample_sharing_info() then reports no classes).  Stays until set again.
+    # compact / lazy rows modes (share_samples_lazy, below, is theirs) and after set_active_uniques (sample_sharing_info() then reports no classes).  Stays until set again.
     @property
     def share_samples(self):
         return getattr(self, "_share_samples", False)
@@ -131,6 +131,25 @@ class Engine:
         if getattr(self, "h", None):
             self._chk(self.L.itsx_set_sample_sharing(self.h, int(bool(on))))
         self._share_samples = bool(on)
+
+    # The same for the compact and lazy rows modes (itsx_set_sample_sharing_lazy), a setting of its own: share_samples governs the full
+    # rows mode alone, this one the searches behind set_rows_mode("lazy") / ("compact") and ITSXPRESS_DOMTBL=winners.  One holder per
+    # score class goes through the MSV filter, pass A, the lazy rounds and the domain pipeline; every evaluated, reported pair counts
+    # for each member's sample, the holders past the filter bound every sample's domZ from above, and the kept rows are copied to the
+    # members before finalize().  Coordinates, uc.txt / rep.fa and the kept rows' domtbl.txt are those of a search without it; the lazy
+    # counters are valid bounds (exact after a completion), the compact ones exact.  False (the default) or True; no effect on one
+    # sample, in the full rows mode and after set_active_uniques.  Stays until set again.
+    @property
+    def share_samples_lazy(self):
+        return getattr(self, "_share_samples_lazy", False)
+
+    @share_samples_lazy.setter
+    def share_samples_lazy(self, on):
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError("Engine.share_samples_lazy is False or True, not %r" % (on,))
+        if getattr(self, "h", None):
+            self._chk(self.L.itsx_set_sample_sharing_lazy(self.h, int(bool(on))))
+        self._share_samples_lazy = bool(on)
 
     def sample_sharing_info(self):
         """What the last search() shared across samples: dict(n_classes, n_uniques_shared, n_rows_expanded, ms_classes, ms_expand) --

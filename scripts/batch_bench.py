@@ -35,14 +35,16 @@ Per arm the stage times of every repeat, the parse and inflate counters, and a c
 Usage: python scripts/batch_bench.py --pairs-flow [n_samples] [pairs_per_sample] [repeats] [--inflate LIST] [--parse LIST] [--plain-inputs]
 
 --share-samples: sample sharing (Engine.share_samples: each distinct representative of a batch scored once for all the samples it occurs
-in) against the same batch without it, on one warm context in the full rows mode, the two arms alternated within every repeat, the first
+in) against the same batch without it, on one warm context in the full rows mode (--rows lazy / compact: in that rows mode, with
+Engine.share_samples_lazy as the setting; a lazy search's counters are bounds, so its identity check covers the coordinates only), the
+two arms alternated within every repeat, the first
 repeat the warm-up: derep + search + finalize + coordinates of S samples of n single-end reads handed over as arrays.  --overlap F (0..1,
 default 0.5) shapes the synthetic manifest: a share F of each sample's DISTINCT sequences is replaced by sequences drawn from a pool
 common to all samples (as large as one sample's distinct set, so a pool sequence turns up in about F of the samples); the rest are the
 sample's own.  The overlap is the generator's, not a real manifest's.  Per arm the wall times of every repeat, median and spread, the
 search's share of it; for the sharing arm the classes, the uniques not scored, the rows copied and the device time of both steps; and a
 check that both arms gave the same counters and coordinates.
-Usage: python scripts/batch_bench.py --share-samples [n_samples] [reads_per_sample] [repeats] [--overlap F]"""
+Usage: python scripts/batch_bench.py --share-samples [n_samples] [reads_per_sample] [repeats] [--overlap F] [--rows full|lazy|compact]"""
 import gzip
 import hashlib
 import json
@@ -69,6 +71,13 @@ PAIRS_FLOW = "--pairs-flow" in sys.argv
 PLAIN_INPUTS = "--plain-inputs" in sys.argv
 SHARE_SAMPLES = "--share-samples" in sys.argv
 argv = [a for a in sys.argv[1:] if a not in ("--paired", "--orient", "--trim", "--trim-paired", "--pairs-flow", "--plain-inputs", "--share-samples")]
+ROWS = "full"
+if "--rows" in argv:
+    k = argv.index("--rows")
+    ROWS = argv[k + 1]
+    del argv[k:k + 2]
+    if not SHARE_SAMPLES or ROWS not in ("full", "lazy", "compact"):
+        sys.exit("--rows takes full, lazy or compact and goes with --share-samples")
 OVERLAP = 0.5
 if "--overlap" in argv:
     k = argv.index("--overlap")
@@ -538,10 +547,11 @@ def share_samples_main():
     smp = np.repeat(np.arange(S, dtype=np.int32), [len(x) for x in samples])
     eng = Engine(0)
     eng.load_profiles(text=its2_profiles(thmm))
-    eng.set_rows_mode("full")
+    eng.set_rows_mode(ROWS)
+    setting = "share_samples" if ROWS == "full" else "share_samples_lazy"      # each rows mode has its own setting
 
     def run(share):
-        eng.share_samples = share
+        setattr(eng, setting, share)
         t0 = time.perf_counter()
         eng.set_reads_buffer(blob, offs)
         eng.set_samples(smp, S)
@@ -569,11 +579,14 @@ def share_samples_main():
                     results[share] = payload
                     continue
                 arms[share].append(res)
-                print("[batch_bench] repeat %d, share_samples %s: %.3f s (search %.3f s)" % (r, share, res["s_total"], res["s_search"]), file=sys.stderr, flush=True)
+                print("[batch_bench] repeat %d, %s %s: %.3f s (search %.3f s)" % (r, setting, share, res["s_total"], res["s_search"]), file=sys.stderr, flush=True)
     finally:
-        eng.share_samples = False
-    same = np.array_equal(results[False][0], results[True][0]) and all(np.array_equal(a, b) for a, b in zip(results[False][1], results[True][1]))
-    out = {"share_samples": True, "samples": S, "reads_per_sample": n, "overlap": OVERLAP, "repeats": repeats, "rows_mode": "full"}
+        setattr(eng, setting, False)
+        eng.set_rows_mode(None)
+    # (a lazy search's counters are bounds, and which pairs it evaluates may depend on the last bits of pass A's scores, hence on the
+    # prefix tree of the uniques searched: both arms' bounds are valid, not necessarily equal -- the identity check is the coordinates')
+    same = (ROWS == "lazy" or np.array_equal(results[False][0], results[True][0])) and all(np.array_equal(a, b) for a, b in zip(results[False][1], results[True][1]))
+    out = {"share_samples": True, "samples": S, "reads_per_sample": n, "overlap": OVERLAP, "repeats": repeats, "rows_mode": ROWS, "setting": setting}
     for share, name in ((False, "off"), (True, "on")):
         for key in ("s_total", "s_search"):
             v = [x[key] for x in arms[share]]
@@ -583,7 +596,7 @@ def share_samples_main():
         out["%s_last" % name] = arms[share][-1]
     out["off_over_on_total"] = round(out["off_s_total_median"] / out["on_s_total_median"], 3)
     out["off_over_on_search"] = round(out["off_s_search_median"] / out["on_s_search_median"], 3)
-    out["identical_counters_and_coordinates"] = bool(same)
+    out["identical_counters_and_coordinates" if ROWS != "lazy" else "identical_coordinates"] = bool(same)
     print(json.dumps(out))
     return 0 if same else 1
 
