@@ -372,6 +372,22 @@ int itsx_write_oriented_fastq(const char *seq_path, const char *out_path, const 
  * On any error (ITSX_E_ARG before itsx_orient_load_db, ITSX_E_NOMEM, ITSX_E_DEVICE) the context KEEPS the read set it had, with whatever
  * results it held: the new read set is built beside it and swapped in only when it is complete. */
 int itsx_orient_apply(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t *count_rev, int64_t *n_kept_per_sample);
+/* Orientation by the profiles (opt-in; no reference tool does this step: ITSx's own both-strand search is the model).  For a text t,
+ * n_fwd(t) = the loaded profiles whose MSV filter passes on t at threshold F1 -- exactly the filter of itsx_search (pass_msv of
+ * itsx_pairtrace; the bias filter plays no part) -- and n_rev(t) = n_fwd(reverse complement of t).  strand = +1 if n_fwd > n_rev, -1 if
+ * n_rev > n_fwd, 0 otherwise (nothing passes on either strand, or a tie).  Exact integer arithmetic throughout.
+ * The call dereplicates the read set itself (strand both, minseqlength 1, per sample) and scans the distinct texts only; a read that
+ * is the reverse complement of its cluster's seed gets the seed's strand negated and its counts swapped; a read the dereplication
+ * drops (empty) gets 0 / 0 / 0.  strand / count_fwd / count_rev: [reads], each may be NULL.  *ms_kernels (may be NULL): the device
+ * time of the scans and of this step's own kernels.  Reads of any length the engine loads (up to 65535 bases).
+ * itsx_orient_profiles_apply also reverse-complements the reads of strand -1 where they are, as itsx_orient_apply does (packed words,
+ * exception lists, the host text with its case kept, and with itsx_keep_records the records) -- but a read of strand 0 is KEPT AS IT
+ * IS: the number of reads, their order and their samples do not change.
+ * Afterwards (either call) the context holds no dereplication, clustering or search results.  ITSX_E_ARG before profiles are loaded
+ * and before a read set is loaded.  On any error the context keeps the read set it had: the new one is built beside it and swapped
+ * in only when it is complete.  The scan obeys ITSX_CHUNK_UNIQUES and the device memory that is free. */
+int itsx_orient_profiles(itsx_ctx *ctx, double F1, int8_t *strand, int32_t *count_fwd, int32_t *count_rev, float *ms_kernels);
+int itsx_orient_profiles_apply(itsx_ctx *ctx, double F1, int8_t *strand, int32_t *count_fwd, int32_t *count_rev, float *ms_kernels);
 
 /* ---- f2: SeqSample._merge_reads (itsxpress/SeqSample.py:266-365) = vsearch --fastq_mergepairs R1 --reverse R2
  * --fastqout seq.fq --fastq_maxdiffs 40 --fastq_maxee 2 --fastq_qmax 93 [--fastq_allowmergestagger]; restated in

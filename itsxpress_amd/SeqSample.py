@@ -93,6 +93,22 @@ def _domtbl_ali_wanted(sample, eng, fast) -> bool:
     return True
 
 
+def _orient_hmmfile(sample):
+    """The profile file orient_reads orients by, or None for the k-mer orientation: with ITSXPRESS_ORIENT=profiles the sample's
+    `orient_hmmfile` attribute."""
+    if os.environ.get("ITSXPRESS_ORIENT", "").strip().lower() == "profiles":
+        return getattr(sample, "orient_hmmfile", None)
+    return None
+
+
+def _keep_undecided(strand):
+    """the strands the host writer gets from an orientation by profiles: 0 (undecided) as +1, so that the read is written as it is"""
+    import numpy as np
+    s = np.array(strand, np.int8)
+    s[s == 0] = 1
+    return s
+
+
 def _uc_cigar_from_env():
     return os.environ.get("ITSXPRESS_UC_CIGAR", "").strip() not in ("", "0")
 
@@ -132,6 +148,8 @@ class SeqSample:
         self.domtbl: Optional[str] = None        # None: ITSXPRESS_DOMTBL ("winners": files as ever, domtbl.txt = the rows that can win)
         self.domtbl_ali: Optional[bool] = None   # None: ITSXPRESS_DOMTBL_ALI (domtbl.txt with hmmsearch's hmm / ali coordinates and acc)
         self.uc_cigar: Optional[bool] = None     # None: ITSXPRESS_UC_CIGAR (cluster_id < 1: uc.txt with the members' alignments in column 8)
+        self.orient_hmmfile: Optional[str] = None   # with ITSXPRESS_ORIENT=profiles: the profile file orient_reads orients by
+        self.orient_strand = None                # after an orientation by profiles: the reads' strands (+1 / -1 / 0 undecided)
 
     # -- engine plumbing -------------------------------------------------------------
     @property
@@ -155,18 +173,39 @@ class SeqSample:
             self._reads_loaded_from = self.seq_file
 
     # -- f4 --------------------------------------------------------------------------
+    def orient_reads_by_profiles(self, hmmfile: str, threads: Union[int, str] = 1) -> None:
+        """`orient_reads` by the profiles of `hmmfile` (the file `_search` will get) instead of the universal database: a read's
+        strand is the one on which more profiles pass the search's MSV filter (Engine.orient_profiles).  A read the profiles
+        cannot judge is written as it is, so oriented.fq holds every read; the strands (+1 / -1 / 0) are left in `orient_strand`.
+        `orient_reads` comes here by itself with ITSXPRESS_ORIENT=profiles and the sample's `orient_hmmfile` set."""
+        self._orient(threads, hmmfile)
+
     def orient_reads(self, threads: Union[int, str] = 1) -> None:
         """Replaces `vsearch --orient FASTQ --db universal_orient_ref_clean.fasta.gz --fastqout oriented.fq`
         (SeqSample.py:48-91): 12-mer counts on both strands on the GPU, then the oriented FASTQ; the sample's
-        fastq / seq_file / r1 point at it afterwards, as in the reference."""
+        fastq / seq_file / r1 point at it afterwards, as in the reference.
+        With ITSXPRESS_ORIENT=profiles and the sample's `orient_hmmfile` set: `orient_reads_by_profiles` of that file instead."""
+        self._orient(threads, _orient_hmmfile(self))
+
+    def _orient(self, threads, hmm) -> None:
         try:
             from .definitions import ROOT_DIR
             from .trim import write_oriented_fastq
             orient_ref = os.path.join(ROOT_DIR, "universal_orient_ref_clean.fasta.gz")
             oriented_fastq = os.path.join(self.tempdir, "oriented.fq")
             os.makedirs(self.tempdir, exist_ok=True)
-            self.engine.orient_load_db(orient_ref)
-            strand, _, _ = self.engine.orient_file(self.fastq)
+            if hmm is not None:
+                eng = self.engine
+                if not isinstance(eng, Engine):
+                    eng.orient_profiles()                   # (not streamed, not sharded: EngineError -5 naming the mode)
+                eng.load_profiles(hmm)
+                eng.load_reads_file(self.fastq)
+                strand, _, _ = eng.orient_profiles()
+                self.orient_strand = strand
+                strand = _keep_undecided(strand)
+            else:
+                self.engine.orient_load_db(orient_ref)
+                strand, _, _ = self.engine.orient_file(self.fastq)
             write_oriented_fastq(self.fastq, oriented_fastq, strand)
             self.fastq = oriented_fastq
             self.seq_file = oriented_fastq

@@ -109,7 +109,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_set_sample_sharing", "itsx_set_sample_sharing_lazy", "itsx_sample_sharing_info", "itsx_sample_sharing_times", "itsx_debug_sample_classes",
            "itsx_align_domains", "itsx_get_alignments", "itsx_write_domtbl_arrays_ali",
            "itsx_align_clusters", "itsx_get_cluster_cigars",
-           "itsx_topup_counters"]
+           "itsx_topup_counters",
+           "itsx_orient_profiles", "itsx_orient_profiles_apply"]
 
 
 def lib():
@@ -217,6 +218,8 @@ def lib():
         "itsx_orient_load_db": (i32, [vp, cp, vp]),
         "itsx_orient": (i32, [vp, vp, vp, vp]),
         "itsx_orient_apply": (i32, [vp, vp, vp, vp, vp]),
+        "itsx_orient_profiles": (i32, [vp, f64, vp, vp, vp, vp]),
+        "itsx_orient_profiles_apply": (i32, [vp, f64, vp, vp, vp, vp]),
         "itsx_write_oriented_fastq": (i32, [cp, cp, vp, i64, vp]),
         "itsx_unique_keys": (i32, [vp, C.c_uint64, vp, vp]),
         "itsx_set_active_uniques": (i32, [vp, vp]),

@@ -35,7 +35,7 @@ import numpy as np
 
 from .engine import Engine
 from ._lib import EngineError
-from .SeqSample import _REGION_PREFIX, _domtbl_ali_wanted, _fast_from_env, _uc_cigar_wanted, _winners_from_env
+from .SeqSample import _REGION_PREFIX, _domtbl_ali_wanted, _fast_from_env, _keep_undecided, _orient_hmmfile, _uc_cigar_wanted, _winners_from_env
 from .definitions import maxmismatches
 
 
@@ -116,6 +116,13 @@ class SampleBatch:
         self._records_read_set = self._resident_read_set if self.keep_records else None
 
     # -- f4 for all samples ------------------------------------------------------------------
+    def orient_reads_by_profiles(self, hmmfile: str, threads: Union[int, str] = 1, write_seq_files: Optional[bool] = None) -> None:
+        """`orient_reads` by the profiles of `hmmfile` (the file `_search` will get) instead of the universal database, every sample
+        in one engine call (`orient_profiles_apply`).  A read the profiles cannot judge stays as it is, so no sample loses a read;
+        every sample's strands (+1 / -1 / 0) are left in its `orient_strand`.  `orient_reads` comes here by itself with
+        ITSXPRESS_ORIENT=profiles and every sample's `orient_hmmfile` set to one file."""
+        self._orient(write_seq_files, hmmfile)
+
     def orient_reads(self, threads: Union[int, str] = 1, write_seq_files: Optional[bool] = None) -> None:
         """`orient_reads` of every sample (SeqSample.py:48-91; the plugin calls it per manifest row with trim_ccs, q2_itsxpress.py:284-285)
         in one engine call: every sample's `fastq` loaded as one read set, the orientation database loaded once, one `orient_apply`,
@@ -125,7 +132,14 @@ class SampleBatch:
         is to write it in both modes: a single-end sample's trimmed output is cut from it -- except in a batch with keep_records, which
         cuts it from the records on the device and so defaults to not writing the file).  `threads` is taken for the sake of
         SeqSample's signature and ignored, as in `merge_reads`: the engine sizes its own I/O pool, and the files are written by
-        min(16, samples) writers at a time."""
+        min(16, samples) writers at a time.
+        With ITSXPRESS_ORIENT=profiles and every sample's `orient_hmmfile` set to one file: `orient_reads_by_profiles` of that file."""
+        hmms = {_orient_hmmfile(s) for s in self.samples}
+        if len(hmms) > 1:
+            raise ValueError("a batch is oriented by one profile file: every sample's orient_hmmfile must name the same one")
+        self._orient(write_seq_files, hmms.pop())
+
+    def _orient(self, write_seq_files, hmm) -> None:
         try:
             from concurrent.futures import ThreadPoolExecutor
             from .definitions import ROOT_DIR
@@ -139,12 +153,21 @@ class SampleBatch:
             outs = [os.path.join(self._dir(i), "oriented.fq") for i in range(len(self.samples))]
             self._resident = None
             eng.keep_records(self.keep_records)
+            if hmm is not None and not isinstance(eng, Engine):
+                eng.orient_profiles_apply()                 # (not streamed, not sharded: EngineError -5 naming the mode)
             before = np.asarray(eng.load_reads_files(inputs), np.int64)
-            eng.orient_load_db(os.path.join(ROOT_DIR, "universal_orient_ref_clean.fasta.gz"))
-            strand, _, _, kept = eng.orient_apply()
+            first = np.concatenate([[0], np.cumsum(before)]).astype(np.int64)
+            if hmm is not None:
+                eng.load_profiles(hmm)
+                strand, _, _ = eng.orient_profiles_apply()
+                for i, s in enumerate(self.samples):
+                    s.orient_strand = strand[first[i]:first[i + 1]].copy()
+                strand, kept = _keep_undecided(strand), before
+            else:
+                eng.orient_load_db(os.path.join(ROOT_DIR, "universal_orient_ref_clean.fasta.gz"))
+                strand, _, _, kept = eng.orient_apply()
             if write:
                 # the host writer, per sample, on the sample's own file and its slice of the strands (ctypes releases the GIL)
-                first = np.concatenate([[0], np.cumsum(before)]).astype(np.int64)
                 def one(i):
                     return write_oriented_fastq(inputs[i], outs[i], strand[first[i]:first[i + 1]])
                 with ThreadPoolExecutor(max_workers=max(1, min(16, len(outs)))) as pool:

@@ -2417,42 +2417,19 @@ static int search_rows_mode(const itsx_ctx *ctx)
   return mode;
 }
 
-// the search over the context's active uniques (itsx_search below: all of them, the caller's choice, or the holders of the score classes)
-static int search_active(itsx_ctx *ctx, double T, double F1, double F2, double F3)
+// What the MSV filter needs of the host before it runs over the context's active uniques (search_active, orient_profiles): the
+// per-length constants (d_lt), the null-length table (w_tjb) and the pass thresholds at F1 (w_thr: a row per length that occurs),
+// uploaded and waited for.  *cells_active: the residues of the active representatives.
+static int filter_tables(itsx_ctx *ctx, double F1, int64_t *cells_active_out)
 {
-  CTXCHK(ctx);
-  if (!ctx->have_derep) SET_ERR(ctx, ITSX_E_ARG, "itsx_search called before itsx_derep / itsx_cluster");
-  if (ctx->P <= 0) SET_ERR(ctx, ITSX_E_ARG, "no profiles loaded");
-  ctx->F2 = F2; ctx->have_vit = F2 < F1;              // hmmsearch enters the Viterbi filter only for P > F2: never when F1 <= F2
-  ctx->switches_at_search = sw_report();              // what the environment asked of this search (itsx_switches)
-  HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->st;
-  const int P = ctx->P, G = ctx->G, Ppad = G * 64, U = ctx->U_active;
-  ctx->T = T;
-  ctx->h_dom.clear(); ctx->drop_alignments(); ctx->h_trace.clear(); ctx->trace_sorted = false;
-  ctx->domz.assign((size_t)P * ctx->S, 0);
-  itsx_stats &S = ctx->stats;
-  S.n_pairs = (int64_t)U * P; S.n_past_msv = S.n_past_bias = S.n_past_fwd = S.n_regions = S.n_multidomain = S.n_domains = S.n_domain_overflow = 0;
-  S.ms_msv = S.ms_filters = S.ms_domains = S.ms_msv_kernel = S.ms_fwd_kernel = S.ms_bwd_kernel = S.ms_env_kernel = S.ms_bias_kernel = S.ms_decode_kernel = 0; S.n_batches = 0; S.ms_ensemble = 0; S.n_mr_clustered = S.n_mr_distinct = S.n_mr_failed = S.n_mr_envelopes = 0; S.n_slab_shrinks = 0; S.n_mr_overflow = 0; S.ms_vit_kernel = 0; for (int k = 0; k < 8; k++) S.n_mr_fail_kind[k] = 0; S.n_rows_resident = 0; S.msv_cells = 0; S.msv_launches = 0; S.fwd_rows = 0; S.env_rows = 0; S.n_env_unique = 0;
-  ctx->npairs_padded = 0; ctx->dom_n.clear(); ctx->trace_u0 = 0; ctx->n_chunks = 0;
-  ctx->have_search = true; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->topup.list_live = false; ctx->injected = false;
-  const int mode = search_rows_mode(ctx);
-  ctx->compact_rows = mode != ITSX_ROWS_FULL;
-  ctx->lazy = mode == ITSX_ROWS_LAZY;
-  ctx->lazy_pending = 0; ctx->domz_exchanged = false; ctx->sF1 = F1; ctx->sF3 = F3;
-  ctx->domz_ub.assign((size_t)P * ctx->S, 0);
-  if (ctx->compact_rows)                    // a full table of an earlier search (80 B x ~130 per representative) goes back to the device
-    for (auto &b : ctx->dom_bufs) if (b && b->cap * sizeof(itsx_domain) > ((size_t)256 << 20)) b->release();
-  S.lazy = ctx->lazy; S.n_lazy_evaluated = S.n_lazy_round1 = S.n_lazy_pending = S.n_lazy_reruns = 0; S.n_lazy_completed = S.n_lazy_completed_profiles = S.n_lazy_pending_profiles = 0; S.ms_lazy_complete = 0; S.lazy_bound_maxdiff = 0; S.ms_bound_kernel = S.ms_lazy_select = 0; S.bound_rows = 0; S.n_bound_launches = 0; S.n_lazy_topup = 0; S.ms_lazy_topup = 0; S.ms_lazy_topup_stages = 0; ctx->n_topup_deferred = ctx->n_topup_ensemble = 0;
-  if (ctx->compact_rows && U > 0) { const int rc = compact_setup(ctx); if (rc != ITSX_OK) return rc; }
-  if (U == 0) return ITSX_OK;
-
+  const int P = ctx->P, Ppad = ctx->G * 64;
   // ---- per-length constants (host libm, as hmmsearch computes them per target)
   const int Lcap = ctx->Lmax + 1;
   std::vector<LenTables> lt((size_t)Lcap);
   std::vector<int32_t> tjb((size_t)Lcap, 0);
   std::vector<char> present((size_t)Lcap, 0);
-  int64_t cells_active = 0;                                 // residues of the active representatives (the filter's cell count, below)
+  int64_t cells_active = 0;                                 // residues of the active representatives (the filter's cell count)
   {   // two gathers per representative from arrays the size of the read set: a few threads (10 M reads: 25 ms on one, the GPU idle)
     const int32_t Ua = ctx->U, Uact = ctx->U_active;
     const int Th = Ua >= (1 << 19) ? std::max(1, std::min(8, itsx_io::io_threads())) : 1;
@@ -2521,6 +2498,43 @@ static int search_active(itsx_ctx *ctx, double T, double F1, double F2, double F
   HIPCHK(upload(ctx->d_lt, lt, st)); HIPCHK(upload(d_thr, thr, st)); HIPCHK(upload(d_tjb, tjb, st));
 
   HIPCHK(hipStreamSynchronize(st));
+  if (cells_active_out) *cells_active_out = cells_active;
+  return ITSX_OK;
+}
+
+// the search over the context's active uniques (itsx_search below: all of them, the caller's choice, or the holders of the score classes)
+static int search_active(itsx_ctx *ctx, double T, double F1, double F2, double F3)
+{
+  CTXCHK(ctx);
+  if (!ctx->have_derep) SET_ERR(ctx, ITSX_E_ARG, "itsx_search called before itsx_derep / itsx_cluster");
+  if (ctx->P <= 0) SET_ERR(ctx, ITSX_E_ARG, "no profiles loaded");
+  ctx->F2 = F2; ctx->have_vit = F2 < F1;              // hmmsearch enters the Viterbi filter only for P > F2: never when F1 <= F2
+  ctx->switches_at_search = sw_report();              // what the environment asked of this search (itsx_switches)
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  const int P = ctx->P, G = ctx->G, Ppad = G * 64, U = ctx->U_active;
+  ctx->T = T;
+  ctx->h_dom.clear(); ctx->drop_alignments(); ctx->h_trace.clear(); ctx->trace_sorted = false;
+  ctx->domz.assign((size_t)P * ctx->S, 0);
+  itsx_stats &S = ctx->stats;
+  S.n_pairs = (int64_t)U * P; S.n_past_msv = S.n_past_bias = S.n_past_fwd = S.n_regions = S.n_multidomain = S.n_domains = S.n_domain_overflow = 0;
+  S.ms_msv = S.ms_filters = S.ms_domains = S.ms_msv_kernel = S.ms_fwd_kernel = S.ms_bwd_kernel = S.ms_env_kernel = S.ms_bias_kernel = S.ms_decode_kernel = 0; S.n_batches = 0; S.ms_ensemble = 0; S.n_mr_clustered = S.n_mr_distinct = S.n_mr_failed = S.n_mr_envelopes = 0; S.n_slab_shrinks = 0; S.n_mr_overflow = 0; S.ms_vit_kernel = 0; for (int k = 0; k < 8; k++) S.n_mr_fail_kind[k] = 0; S.n_rows_resident = 0; S.msv_cells = 0; S.msv_launches = 0; S.fwd_rows = 0; S.env_rows = 0; S.n_env_unique = 0;
+  ctx->npairs_padded = 0; ctx->dom_n.clear(); ctx->trace_u0 = 0; ctx->n_chunks = 0;
+  ctx->have_search = true; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->topup.list_live = false; ctx->injected = false;
+  const int mode = search_rows_mode(ctx);
+  ctx->compact_rows = mode != ITSX_ROWS_FULL;
+  ctx->lazy = mode == ITSX_ROWS_LAZY;
+  ctx->lazy_pending = 0; ctx->domz_exchanged = false; ctx->sF1 = F1; ctx->sF3 = F3;
+  ctx->domz_ub.assign((size_t)P * ctx->S, 0);
+  if (ctx->compact_rows)                    // a full table of an earlier search (80 B x ~130 per representative) goes back to the device
+    for (auto &b : ctx->dom_bufs) if (b && b->cap * sizeof(itsx_domain) > ((size_t)256 << 20)) b->release();
+  S.lazy = ctx->lazy; S.n_lazy_evaluated = S.n_lazy_round1 = S.n_lazy_pending = S.n_lazy_reruns = 0; S.n_lazy_completed = S.n_lazy_completed_profiles = S.n_lazy_pending_profiles = 0; S.ms_lazy_complete = 0; S.lazy_bound_maxdiff = 0; S.ms_bound_kernel = S.ms_lazy_select = 0; S.bound_rows = 0; S.n_bound_launches = 0; S.n_lazy_topup = 0; S.ms_lazy_topup = 0; S.ms_lazy_topup_stages = 0; ctx->n_topup_deferred = ctx->n_topup_ensemble = 0;
+  if (ctx->compact_rows && U > 0) { const int rc = compact_setup(ctx); if (rc != ITSX_OK) return rc; }
+  if (U == 0) return ITSX_OK;
+
+  const int Lcap = ctx->Lmax + 1;
+  int64_t cells_active = 0;                                 // residues of the active representatives (the filter's cell count, below)
+  { const int rc = filter_tables(ctx, F1, &cells_active); if (rc != ITSX_OK) return rc; }
   HIPCHK(ctx->d_domz32.alloc((size_t)P * ctx->S));
   HIPCHK(hipMemsetAsync(ctx->d_domz32.p, 0, (size_t)P * ctx->S * 4, st));
   {
@@ -3768,6 +3782,29 @@ static int lazy_rounds(itsx_ctx *ctx, const PairList &pl, const int32_t *d_sorte
   return ITSX_OK;
 }
 
+// The MSV filter's arguments for the cU sequences seed_read[sorted[0 .. cU)] of `rd`, every profile, unshared, with the tables
+// filter_tables left on the device (search_chunk's msv_for, orient_profiles).
+// blocks of 256 sequences x PB profiles: a few thousand blocks at least, and up to 32 profiles per block so that a
+// large job re-reads its sequences' packed words (from L2) 32 times less often than it has profiles
+// test hook ITSX_MSV_PB: the profiles a block takes its sequences through, whatever the job's size (a small job gets 1)
+static int msv_pb_forced() { return sw_get("ITSX_MSV_PB") ? std::max(1, std::min(32, atoi(sw_get("ITSX_MSV_PB")))) : 0; }
+static int msv_pb(int64_t cU, int np)
+{
+  const int64_t tiles = (cU + 255) / 256;
+  const int pb_forced = msv_pb_forced();
+  return pb_forced ? pb_forced : (int)std::max<int64_t>(1, std::min<int64_t>(32, tiles * np / 4096));
+}
+static MsvArgs msv_args(const itsx_ctx *ctx, const ReadsDev &rd, const int32_t *sorted, const int32_t *seed_read, int32_t cU, int Lcap, uint16_t *res)
+{
+  MsvArgs a{};
+  a.rd = rd; a.sorted_uniq = sorted; a.seed_read = seed_read; a.U = cU; a.G = ctx->G;
+  a.etab = ctx->d_etab.p; a.pbias = ctx->d_pbias.p; a.ptec = ctx->d_ptec.p; a.ptbm = ctx->d_ptbm.p;
+  a.thr = ctx->w_thr.p; a.tjb = ctx->w_tjb.p; a.Lcap = Lcap; a.res = res;
+  a.P = ctx->P;
+  a.PB = msv_pb(cU, ctx->P);
+  return a;
+}
+
 // one chunk [u0, u0+U) of the length-sorted unique list through every stage up to per-sequence reporting
 static int search_chunk(itsx_ctx *ctx, int ci, int32_t u0, int32_t U, int Lcap, double T, double F1, double F3)
 {
@@ -3779,28 +3816,19 @@ static int search_chunk(itsx_ctx *ctx, int ci, int32_t u0, int32_t U, int Lcap, 
   const bool sh = ctx->share_on;
   const int32_t *d_sorted = (sh ? ctx->sh_order.p : ctx->d_sorted_uniq.p) + u0;
   const int32_t *d_ulen = (sh ? ctx->sh_ulen.p : ctx->d_ulen.p) + u0;
-  DBuf<uint16_t> &d_thr = ctx->w_thr; DBuf<int32_t> &d_tjb = ctx->w_tjb;
   ctx->trace_u0 = u0;
   // ---- MSV for every (unique, profile)
   DBuf<uint16_t> &d_res = ctx->w_res;
   HIPCHK(d_res.alloc((size_t)Ppad * std::max<int64_t>(U, ctx->next_u0 >= 0 ? ctx->next_U : 0)));
   auto msv_for = [&](int64_t cu0, int32_t cU, hipStream_t s, int lds_pad = 0, uint16_t *res_out = nullptr, bool shared = true) {
-    MsvArgs a{};
-    a.rd = ctx->rd; a.sorted_uniq = (sh ? ctx->sh_order.p : ctx->d_sorted_uniq.p) + cu0; a.seed_read = ctx->d_seed_read.p; a.U = cU; a.G = G;
-    a.etab = ctx->d_etab.p; a.pbias = ctx->d_pbias.p; a.ptec = ctx->d_ptec.p; a.ptbm = ctx->d_ptbm.p;
-    a.thr = d_thr.p; a.tjb = d_tjb.p; a.Lcap = Lcap; a.res = res_out ? res_out : d_res.p;
-    a.P = P;
-    // blocks of 256 sequences x PB profiles: a few thousand blocks at least, and up to 32 profiles per block so that a
-    // large job re-reads its sequences' packed words (from L2) 32 times less often than it has profiles
-    const int64_t tiles = ((int64_t)cU + 255) / 256;
+    MsvArgs a = msv_args(ctx, ctx->rd, (sh ? ctx->sh_order.p : ctx->d_sorted_uniq.p) + cu0, ctx->d_seed_read.p, cU, Lcap, res_out ? res_out : d_res.p);
     if (ctx->completing) {           // only the listed profiles are filtered; every other row of res must read "not passed"
       a.plist = ctx->d_plist.p; a.nlist = (int32_t)ctx->h_plist.size();
       (void)hipMemsetAsync(a.res, 0, (size_t)Ppad * (size_t)cU * sizeof(uint16_t), s);
     }
     const int np = a.plist ? a.nlist : P;
-    // test hook ITSX_MSV_PB: the profiles a block takes its sequences through, whatever the job's size (a small job gets 1)
-    const int pb_forced = sw_get("ITSX_MSV_PB") ? std::max(1, std::min(32, atoi(sw_get("ITSX_MSV_PB")))) : 0;
-    a.PB = pb_forced ? pb_forced : (int)std::max<int64_t>(1, std::min<int64_t>(32, tiles * np / 4096));
+    const int pb_forced = msv_pb_forced();
+    a.PB = msv_pb(cU, np);
     // (the completion filters a handful of profiles: its launches would be a hundred tiny ones per chunk -- it runs unshared, on the same
     // processing order)
     if (!sh || !shared || ctx->completing) { launch_msv(a, s, lds_pad); return; }
@@ -4978,18 +5006,28 @@ static int host_bases(const itsx_ctx *cctx);
 // exceptions are and where they go) and a scatter into fresh buffers (k_orient.hip); the host needs the strand vector alone and compacts
 // its labels, offsets and text -- the reverse reads' text reverse-complemented with the table the oriented FASTQ writer uses -- while
 // those kernels run.  Everything is built beside the read set and swapped in at the end: whatever fails, the context keeps what it had.
+static int orient_apply_strands(itsx_ctx *ctx, const std::vector<int8_t> &hs, DBuf<int8_t> &d_s, int64_t *n_kept_per_sample);
 int itsx_orient_apply(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t *count_rev, int64_t *n_kept_per_sample)
 {
   CTXCHK(ctx);
   if (!ctx->have_orient_db) SET_ERR(ctx, ITSX_E_ARG, "itsx_orient_apply called before itsx_orient_load_db");
   HIPCHK(hipSetDevice(ctx->device));
   const int64_t n = ctx->N;
-  const int32_t S = ctx->S;
   if (!ctx->bases_view) { const int rc = host_bases(ctx); if (rc != ITSX_OK) return rc; }      // reads handed over in device memory: their text comes back first
-  hipStream_t st = ctx->st;
   std::vector<int8_t> hs((size_t)n + 1, 0);
   DBuf<int8_t> d_s;
   if (n > 0) { const int rc = orient_device(ctx, hs.data(), count_fwd, count_rev, d_s); if (rc != ITSX_OK) return rc; }
+  { const int rc = orient_apply_strands(ctx, hs, d_s, n_kept_per_sample); if (rc != ITSX_OK) return rc; }
+  if (strand && n > 0) memcpy(strand, hs.data(), (size_t)n);
+  return ITSX_OK;
+}
+// ... given the strands (hs on the host, d_s on the device: +1 kept, -1 kept reverse-complemented, 0 dropped; the host's text present):
+// itsx_orient_apply's, and itsx_orient_profiles_apply's, which drops nothing
+static int orient_apply_strands(itsx_ctx *ctx, const std::vector<int8_t> &hs, DBuf<int8_t> &d_s, int64_t *n_kept_per_sample)
+{
+  const int64_t n = ctx->N;
+  const int32_t S = ctx->S;
+  hipStream_t st = ctx->st;
   // ---- what the host knows from the strands: the kept reads, their offsets, their words
   int64_t m = 0;
   for (int64_t r = 0; r < n; r++) m += hs[(size_t)r] != 0;
@@ -5107,9 +5145,111 @@ int itsx_orient_apply(itsx_ctx *ctx, int8_t *strand, int32_t *count_fwd, int32_t
   ctx->have_derep = ctx->have_search = ctx->have_final = false; ctx->drop_cigars();
   ctx->order_cache_ok = false; ctx->sel_sample = -1; ctx->h_usample.clear();
   ctx->stats.n_reads = m;
-  if (strand && n > 0) memcpy(strand, hs.data(), (size_t)n);
   if (n_kept_per_sample) for (int32_t s = 0; s < S; s++) n_kept_per_sample[s] = scnt[(size_t)s];
   return ITSX_OK;
+}
+
+// ------------------------------------------------------------------------------ f4: orientation by the profiles (k_orient_prof.hip)
+// n_fwd / n_rev of a text: the profiles whose MSV filter passes at F1 on it / on its reverse complement -- the search's own filter
+// (filter_tables' thresholds, launch_msv unshared, a res cell != 0).  Strand +1 / -1 by the larger count, 0 when they are equal.
+// The read set is dereplicated here (strand both, minseqlength 1, per sample) and only the uniques' seeds are scanned, chunk by chunk
+// of the length-sorted list: the chunk's reverse complements are written into a scratch read set by the apply kernels of k_orient.hip
+// (source list = the chunk's seeds, every strand -1) and go through the filter with the same threshold rows -- a text and its reverse
+// complement have one length.  The reads take their seed's verdict, negated and swapped where they are its reverse complement.
+// apply: the reads of strand -1 are reverse-complemented where they are (orient_apply_strands with 0 as +1: nothing is dropped).
+// Whatever happens the context holds no dereplication afterwards, and on an error the read set it had.
+static int orient_profiles(itsx_ctx *ctx, double F1, int8_t *strand, int32_t *count_fwd, int32_t *count_rev, float *ms_kernels, bool apply)
+{
+  CTXCHK(ctx);
+  const char *who = apply ? "itsx_orient_profiles_apply" : "itsx_orient_profiles";
+  if (ms_kernels) *ms_kernels = 0;
+  if (ctx->P <= 0) SET_ERR(ctx, ITSX_E_ARG, std::string(who) + " called before the profiles are loaded");
+  if (!ctx->rd.woff) SET_ERR(ctx, ITSX_E_ARG, std::string(who) + " called before a read set is loaded");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (apply && !ctx->bases_view) { const int rc = host_bases(ctx); if (rc != ITSX_OK) return rc; }
+  struct Forget {                                            // the dereplication is this call's own
+    itsx_ctx *c;
+    ~Forget() { c->have_derep = c->have_search = c->have_final = false; c->clustered = false; c->drop_cigars(); c->order_cache_ok = false; c->h_usample.clear(); }
+  } forget{ctx};
+  { const int rc = itsx_derep(ctx, 1, 1, nullptr); if (rc != ITSX_OK) return rc; }
+  hipStream_t st = ctx->st;
+  const int64_t n = ctx->N;
+  const int32_t U = ctx->U;
+  const int P = ctx->P, Ppad = ctx->G * 64, Lcap = ctx->Lmax + 1;
+  float ms = 0;
+  DBuf<int32_t> ucf, ucr; DBuf<int8_t> ustr;
+  HIPCHK(ucf.alloc((size_t)U + 1)); HIPCHK(ucr.alloc((size_t)U + 1)); HIPCHK(ustr.alloc((size_t)U + 1));
+  if (U > 0) {
+    { const int rc = filter_tables(ctx, F1, nullptr); if (rc != ITSX_OK) return rc; }
+    // a chunk holds two result tables, its reverse complements and their lists: a quarter of what is free
+    const size_t per_unique = (size_t)Ppad * 4 + (size_t)((ctx->Lmax + 15) / 16) * 4 + 64;
+    int64_t Uc = ((1ll << 31) - 4096) / std::max(Ppad, 1);
+    { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess) Uc = std::min<int64_t>(Uc, (int64_t)(fr / 4 / per_unique)); }
+    if (const char *e = sw_get("ITSX_CHUNK_UNIQUES")) Uc = atoll(e);
+    Uc = std::max<int64_t>(1, std::min<int64_t>(Uc, U));
+    std::vector<int64_t> hexc((size_t)n + 1, 0);             // (the exceptions' offsets live on the device only)
+    HIPCHK(hipMemcpyAsync(hexc.data(), ctx->d_excoff.p, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
+    DBuf<int8_t> d_neg; DBuf<int32_t> d_iota, s_src, s_len; DBuf<int64_t> s_woff, s_excoff; DBuf<uint32_t> s_words, s_exc; DBuf<uint16_t> res_f, res_r;
+    HIPCHK(d_neg.alloc((size_t)n + 1)); HIPCHK(hipMemsetAsync(d_neg.p, 0xff, (size_t)n + 1, st));
+    HIPCHK(d_iota.alloc((size_t)Uc)); launch_op_iota(d_iota.p, (int32_t)Uc, st);
+    HIPCHK(res_f.alloc((size_t)Ppad * (size_t)Uc)); HIPCHK(res_r.alloc((size_t)Ppad * (size_t)Uc));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<int32_t> src, len; std::vector<int64_t> woff, excoff;
+    for (int64_t u0 = 0; u0 < U; u0 += Uc) {
+      const int32_t cU = (int32_t)std::min<int64_t>(Uc, U - u0);
+      src.assign((size_t)cU, 0); len.assign((size_t)cU, 0); woff.assign((size_t)cU + 1, 0); excoff.assign((size_t)cU + 1, 0);
+      for (int32_t j = 0; j < cU; j++) {
+        const size_t r = (size_t)ctx->h_seed_read[(size_t)ctx->h_sorted_uniq[(size_t)(u0 + j)]];
+        src[(size_t)j] = (int32_t)r; len[(size_t)j] = ctx->h_len[r];
+        woff[(size_t)j + 1] = woff[(size_t)j] + (ctx->h_woff[r + 1] - ctx->h_woff[r]);
+        excoff[(size_t)j + 1] = excoff[(size_t)j] + (hexc[r + 1] - hexc[r]);
+      }
+      HIPCHK(s_words.alloc((size_t)woff[(size_t)cU] + 1)); HIPCHK(s_exc.alloc((size_t)excoff[(size_t)cU] + 1));
+      HIPCHK(upload(s_src, src, st)); HIPCHK(upload(s_len, len, st)); HIPCHK(upload(s_woff, woff, st)); HIPCHK(upload(s_excoff, excoff, st));
+      StageTimer tm(st);
+      OrientApplyArgs a{};
+      a.rd = ctx->rd; a.strand = d_neg.p; a.src = s_src.p; a.woff = s_woff.p; a.excoff = s_excoff.p; a.len = s_len.p; a.words = s_words.p; a.exc = s_exc.p;
+      launch_orient_apply_scatter(a, cU, st);
+      ReadsDev srd{};
+      srd.words = s_words.p; srd.woff = s_woff.p; srd.len = s_len.p; srd.excoff = s_excoff.p; srd.exc = s_exc.p; srd.n = cU;
+      launch_msv(msv_args(ctx, ctx->rd, ctx->d_sorted_uniq.p + u0, ctx->d_seed_read.p, cU, Lcap, res_f.p), st);
+      launch_msv(msv_args(ctx, srd, d_iota.p, d_iota.p, cU, Lcap, res_r.p), st);
+      launch_op_verdict(res_f.p, res_r.p, cU, P, ctx->d_sorted_uniq.p + u0, ucf.p, ucr.p, ustr.p, st);
+      ms += tm.stop();                                        // (waited for: the host's lists may change for the next chunk)
+      HIPCHK(hipGetLastError());
+    }
+  }
+  std::vector<int8_t> hs((size_t)n + 1, 0);
+  DBuf<int8_t> d_s, d_keep; DBuf<int32_t> d_f, d_r;
+  HIPCHK(d_s.alloc((size_t)n + 1)); HIPCHK(d_f.alloc((size_t)n + 1)); HIPCHK(d_r.alloc((size_t)n + 1));
+  if (apply) HIPCHK(d_keep.alloc((size_t)n + 1));
+  if (n > 0) {
+    StageTimer tm(st);
+    launch_op_compose(n, ctx->d_uniq_of.p, ctx->d_strand.p, ucf.p, ucr.p, ustr.p, d_s.p, d_f.p, d_r.p, apply ? d_keep.p : nullptr, st);
+    ms += tm.stop();
+    HIPCHK(hipMemcpyAsync(hs.data(), d_s.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    if (count_fwd) HIPCHK(hipMemcpyAsync(count_fwd, d_f.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (count_rev) HIPCHK(hipMemcpyAsync(count_rev, d_r.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+  }
+  if (apply) {
+    std::vector<int8_t> hk((size_t)n + 1, 1);
+    for (int64_t r = 0; r < n; r++) if (hs[(size_t)r] < 0) hk[(size_t)r] = -1;
+    const int rc = orient_apply_strands(ctx, hk, d_keep, nullptr);
+    if (rc != ITSX_OK) return rc;
+  }
+  if (strand && n > 0) memcpy(strand, hs.data(), (size_t)n);
+  if (ms_kernels) *ms_kernels = ms;
+  return ITSX_OK;
+}
+int itsx_orient_profiles(itsx_ctx *ctx, double F1, int8_t *strand, int32_t *count_fwd, int32_t *count_rev, float *ms_kernels)
+{
+  return orient_profiles(ctx, F1, strand, count_fwd, count_rev, ms_kernels, false);
+}
+int itsx_orient_profiles_apply(itsx_ctx *ctx, double F1, int8_t *strand, int32_t *count_fwd, int32_t *count_rev, float *ms_kernels)
+{
+  return orient_profiles(ctx, F1, strand, count_fwd, count_rev, ms_kernels, true);
 }
 
 // ------------------------------------------------------------------------------ f2: paired-end merge (k_merge.hip)

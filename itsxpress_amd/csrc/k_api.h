@@ -178,6 +178,14 @@ int64_t orient_apply_blocks(int64_t n);
 int orient_apply_tile();
 void launch_orient_apply_plan(const OrientApplyArgs &a, hipStream_t st);
 void launch_orient_apply_scatter(const OrientApplyArgs &a, int64_t m, hipStream_t st);
+// k_orient_prof.hip: orientation by the profiles (itsx_orient_profiles).  res_f / res_r: the MSV filter's [G*64][cU] results on a chunk of
+// the sorted unique list and on its reverse complements; sorted: the chunk's unique indices; ucf / ucr / ustrand by unique index.
+void launch_op_iota(int32_t *v, int32_t n, hipStream_t st);
+void launch_op_verdict(const uint16_t *res_f, const uint16_t *res_r, int32_t cU, int32_t P, const int32_t *sorted, int32_t *ucf, int32_t *ucr,
+                       int8_t *ustrand, hipStream_t st);
+// per read: strand / counts from its unique's (negated / swapped where rstrand < 0; 0 / 0 / 0 where uniq_of < 0); keep (may be null): 0 as +1
+void launch_op_compose(int64_t n, const int32_t *uniq_of, const int8_t *rstrand, const int32_t *ucf, const int32_t *ucr, const int8_t *ustrand,
+                       int8_t *strand, int32_t *cf, int32_t *cr, int8_t *keep, hipStream_t st);
 
 // ---- k_merge.hip (paired-end merge)
 struct MergeArgs {

@@ -378,6 +378,31 @@ class Engine:
         self.n_reads, self.n_unique = int(kept.sum()), 0
         return strand[:n], cf[:n], cr[:n], kept
 
+    def _orient_profiles(self, fn, F1):
+        n = self.n_reads
+        strand = np.zeros(max(1, n), np.int8)
+        cf = np.zeros(max(1, n), np.int32)
+        cr = np.zeros(max(1, n), np.int32)
+        ms = C.c_float(0)
+        self._chk(fn(self.h, float(F1), strand.ctypes.data, cf.ctypes.data, cr.ctypes.data, C.byref(ms)))
+        self.last_orient_ms = float(ms.value)
+        self.n_unique = 0
+        return strand[:n], cf[:n], cr[:n]
+
+    def orient_profiles(self, F1=1e-6):
+        """Orientation by the loaded profiles (itsx_orient_profiles): per read strand int8 (+1 if more profiles pass the MSV filter at
+        F1 on the read than on its reverse complement, -1 if fewer, 0 if equally many -- none, or a tie), count_fwd, count_rev.  The
+        call dereplicates the reads itself and leaves no dereplication behind; last_orient_ms is the device time of its kernels."""
+        return self._orient_profiles(self.L.itsx_orient_profiles, F1)
+
+    def orient_profiles_apply(self, F1=1e-6):
+        """orient_profiles(), and the reads of strand -1 reverse-complemented where they are (packed words, exceptions, the host text,
+        with keep_records the records).  Unlike orient_apply() a read of strand 0 is kept as it is: the number of reads, their order
+        and their samples do not change.  Returns (strand, count_fwd, count_rev) of the reads before the call."""
+        out = self._orient_profiles(self.L.itsx_orient_profiles_apply, F1)
+        self.read_set += 1
+        return out
+
     def orient_file(self, fastq):
         """load a FASTQ file and orient its reads (what SeqSample.orient_reads needs in one call)"""
         self.load_reads_file(fastq)

@@ -1058,6 +1058,14 @@ class MultiEngine(ShardedOps):
         res = self._each("orient_piece", [(pieces[r], self._orient_db) for r in range(self.world)])
         return tuple(np.concatenate([r[k] for r in res]) for k in range(3))
 
+    def orient_profiles(self, F1=1e-6):
+        raise EngineError(-5, "orientation by the profiles (orient_profiles) does not shard over GPUs: run it with ITSXPRESS_GPUS=1 "
+                              "(DESIGN.md section 9)")
+
+    def orient_profiles_apply(self, F1=1e-6):
+        raise EngineError(-5, "orientation by the profiles (orient_profiles_apply) does not shard over GPUs: run it with ITSXPRESS_GPUS=1 "
+                              "(DESIGN.md section 9)")
+
     def _merge(self, r1, r2, out, maxdiffs, maxee, allow_stagger):
         for p in (r1, r2):
             if not os.path.exists(p):

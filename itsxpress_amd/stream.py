@@ -987,5 +987,13 @@ class StreamEngine(ShardedOps):
         self._plain_eng = None
         return res
 
+    def orient_profiles(self, F1=1e-6):
+        raise EngineError(-5, "orientation by the profiles (orient_profiles) is not streamed: run it without ITSXPRESS_STREAM "
+                              "(DESIGN.md section 9)")
+
+    def orient_profiles_apply(self, F1=1e-6):
+        raise EngineError(-5, "orientation by the profiles (orient_profiles_apply) is not streamed: run it without ITSXPRESS_STREAM "
+                              "(DESIGN.md section 9)")
+
     def merge_pairs_files(self, r1, r2, out, maxdiffs=40, maxee=2.0, allow_stagger=False):
         return self._plain().merge_pairs_files(r1, r2, out, maxdiffs=maxdiffs, maxee=maxee, allow_stagger=allow_stagger)
