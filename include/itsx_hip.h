@@ -811,7 +811,7 @@ int itsx_write_trimmed_fastq(const char *seq_path, const char *out_path, int com
  * Errors: negative code, text from itsx_trim_last_error(). */
 int itsx_twriter_open(const char *out_path, int compression, int trim_ccs, itsx_twriter **w);
 /* mode 1 (a paired run's mates, itsxpress/SeqSample.py:587-670): (start, stop) are Python slice bounds as they come -- start may be
- * negative, stop == INT32_MAX = open end, stop == INT32_MIN = the record is not written */
+ * negative, stop == INT32_MAX = open end, stop == INT32_MIN = the record is not written (ITSX_E_ARG on a writer that has strands) */
 int itsx_twriter_set_mode(itsx_twriter *w, int32_t mode);
 /* The writer's gzip output made on the device (opt-in): a unit that is ready has its raw text and coordinates uploaded, its lines
  * indexed, its records planned, copied and deflated by the context (csrc/k_trim.hip, csrc/k_deflate.hip: members of at most
@@ -832,6 +832,19 @@ int itsx_twriter_text(itsx_twriter *w, const char *text, int64_t avail, int32_t 
 int itsx_twriter_coords(itsx_twriter *w, int64_t first_record, int64_t n, const int32_t *start, const int32_t *stop, const uint8_t *decided);
 int itsx_twriter_update(itsx_twriter *w, const int64_t *records, int64_t m, const int32_t *start, const int32_t *stop);
 int itsx_twriter_close(itsx_twriter *w, int64_t *n_written, int64_t *total_len);
+/* Strands for the writer (a streamed run that orients its reads chunk by chunk): rows of records first_record .. first_record + n - 1,
+ * in record order without gaps, BEFORE the coordinates of the same records (rows for records whose coordinates are in: ITSX_E_ARG).
+ * A record of strand -1 is written from its reverse complement -- bases reversed and complemented byte by byte with the table
+ * itsx_write_oriented_fastq uses (case and IUPAC symbols kept), qualities reversed -- and start / stop are the Python slice of THAT
+ * record, trim_ccs stitching around it as ever: the bytes are those of the writer run over oriented.fq.  Strand +1 and 0 are written as
+ * they are, and a writer that never gets this call writes what it always wrote.  Mode 0 only (ITSX_E_ARG on a mode-1 writer).  On the
+ * device path the unit's strands are uploaded beside its coordinates and the copy kernel reads a flipped record's lines backwards
+ * (csrc/k_trim.hip); units the host slices honour the strands there.
+ * itsx_write_trimmed_fastq_strands: the object fed once (strand == NULL: itsx_write_trimmed_fastq). */
+int itsx_twriter_strands(itsx_twriter *w, int64_t first_record, int64_t n, const int8_t *strand);
+int itsx_write_trimmed_fastq_strands(const char *seq_path, const char *out_path, int compression, int trim_ccs,
+                                     const int32_t *start, const int32_t *stop, const int8_t *strand, int64_t n_records,
+                                     int64_t *n_written, int64_t *total_len);
 
 int itsx_write_trimmed_paired(const char *r1_path, const char *r2_path, const char *out1_path, const char *out2_path,
                               int compression, int trim_ccs, const char *names, const int64_t *name_offsets, int64_t n_names,

@@ -150,6 +150,7 @@ class SeqSample:
         self.uc_cigar: Optional[bool] = None     # None: ITSXPRESS_UC_CIGAR (cluster_id < 1: uc.txt with the members' alignments in column 8)
         self.orient_hmmfile: Optional[str] = None   # with ITSXPRESS_ORIENT=profiles: the profile file orient_reads orients by
         self.orient_strand = None                # after an orientation by profiles: the reads' strands (+1 / -1 / 0 undecided)
+        self._orient_planned: Optional[str] = None  # the profile file a streamed run in arrays mode orients by, chunk by chunk (plan_orient)
 
     # -- engine plumbing -------------------------------------------------------------
     @property
@@ -195,12 +196,25 @@ class SeqSample:
             oriented_fastq = os.path.join(self.tempdir, "oriented.fq")
             os.makedirs(self.tempdir, exist_ok=True)
             if hmm is not None:
-                eng = self.engine
+                eng = plain = self.engine
                 if not isinstance(eng, Engine):
-                    eng.orient_profiles()                   # (not streamed, not sharded: EngineError -5 naming the mode)
-                eng.load_profiles(hmm)
-                eng.load_reads_file(self.fastq)
-                strand, _, _ = eng.orient_profiles()
+                    if not hasattr(eng, "plan_orient"):
+                        eng.orient_profiles()               # (not sharded: EngineError -5 naming the mode)
+                    if self._is_fast():
+                        # a streamed run in arrays mode: every chunk orients its own reads after it has loaded them and the writer
+                        # slices a reverse read from its reverse complement -- no oriented.fq, the sample's files stay the input
+                        eng.plan_orient()
+                        self.orient_hmmfile = self._orient_planned = hmm
+                        return
+                    plain = eng._plain()                    # file mode: the whole file on the stream engine's plain context, as the k-mer rule
+                try:
+                    plain.load_profiles(hmm)
+                    plain.load_reads_file(self.fastq)
+                    strand, _, _ = plain.orient_profiles()
+                finally:
+                    if plain is not eng:                    # (it has done its work: it leaves the device before the streaming run starts)
+                        plain.close()
+                        eng._plain_eng = None
                 self.orient_strand = strand
                 strand = _keep_undecided(strand)
             else:
@@ -266,6 +280,9 @@ class SeqSample:
                 self._reads_loaded_from = None
                 self._load_reads()
                 helpers = [Engine(d) for d in devs[1:]]
+            elif cid < 1.0 and getattr(self, "_orient_planned", None) is not None:
+                raise EngineError(-5, "cluster_id < 1 runs on one plain engine, and this sample's orientation by the profiles was planned "
+                                      "inside the streamed run: orient it without ITSXPRESS_STREAM")
             elif cid < 1.0 and (world > 1 or getattr(self.engine, "deferred", False)):
                 # greedy clustering is sequential by definition (a query sees every centroid before it): one GPU runs it, in one piece
                 logging.warning("cluster_id < 1 does not shard over GPUs or chunks: this sample runs on one GPU (ITSXPRESS_GPUS / ITSXPRESS_STREAM ignored)")
@@ -301,6 +318,11 @@ class SeqSample:
         try:
             self.dom_file = os.path.join(self.tempdir, "domtbl.txt")
             eng = self.engine
+            planned = getattr(self, "_orient_planned", None)
+            if planned is not None and os.path.abspath(str(hmmfile)) != os.path.abspath(str(planned)):
+                # (a chunk orients with the profiles it searches with)
+                raise EngineError(-5, "_search: the streamed run's orientation was planned with the profiles of %s, the search is given %s: "
+                                      "one profile file serves both" % (planned, hmmfile))
             if not getattr(eng, "deferred", False) and eng.n_unique == 0 and self.rep_file and os.path.exists(self.rep_file) and eng.n_reads == 0:
                 # _search called on a rep.fa produced elsewhere (the reference's tests do this)
                 eng.load_reads_file(self.rep_file)
@@ -323,6 +345,8 @@ class SeqSample:
             eng.set_rows_mode("lazy" if (fast or winners) else "full")
             eng.search(T=10.0, F1=1e-6, F2=1e-6, F3=1e-6)
             eng.finalize(domE=10.0)
+            if planned is not None:
+                self.orient_strand = eng.orient_strands()[0]
             ali = _domtbl_ali_wanted(self, eng, fast)
             if fast:
                 self.dom_file = EngineTable(self.dom_file, eng, "domtbl")
@@ -595,12 +619,15 @@ class Dedup:
                 return
             # arrays mode: per-read coordinates straight from the engine, in the order of seq_file's records (the engine read them from it)
             start, stop, _, _ = self._engine.trim_coords(itspos.leftprefix, itspos.rightprefix)
+            # a streamed run that oriented its reads chunk by chunk (plan_orient) has coordinates of the ORIENTED reads and no oriented.fq:
+            # the writer slices seq_file's reverse reads from their reverse complements
+            strand = self._engine.orient_strands()[0] if getattr(self._engine, "_orient_plan", None) is not None else None
             if not os.path.exists(self.seq_file) and getattr(self._engine, "_last_merge", None) is not None:
                 # a paired sample whose merged reads never left the engine (_merge_reads in arrays mode writes no seq.fq) and whose caller
                 # wants the MERGED reads trimmed (main.py:596-624: --fastq2 without --outfile2): the merged records are written now
                 logging.info("itsx_hip: writing the merged reads to %s for the single merged output", self.seq_file)
                 self._engine.write_merged_fastq(self.seq_file)
-            write_trimmed_fastq(self.seq_file, outfile, start, stop, gzipped=gzipped, trim_ccs=trim_ccs, zstd_file=zstd_file)
+            write_trimmed_fastq(self.seq_file, outfile, start, stop, gzipped=gzipped, trim_ccs=trim_ccs, zstd_file=zstd_file, strand=strand)
             return
         names = read_names(self.seq_file)           # the native writer's own record parser: names and records cannot disagree
         start, stop, _ = coords_from_dicts(names, self.matchdict, itspos)

@@ -110,7 +110,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_align_domains", "itsx_get_alignments", "itsx_write_domtbl_arrays_ali",
            "itsx_align_clusters", "itsx_get_cluster_cigars",
            "itsx_topup_counters",
-           "itsx_orient_profiles", "itsx_orient_profiles_apply"]
+           "itsx_orient_profiles", "itsx_orient_profiles_apply",
+           "itsx_twriter_strands", "itsx_write_trimmed_fastq_strands"]
 
 
 def lib():
@@ -169,6 +170,7 @@ def lib():
         "itsx_twriter_text": (i32, [vp, vp, i64, i32]),
         "itsx_twriter_coords": (i32, [vp, i64, i64, vp, vp, vp]),
         "itsx_twriter_update": (i32, [vp, vp, i64, vp, vp]),
+        "itsx_twriter_strands": (i32, [vp, i64, i64, vp]),
         "itsx_twriter_close": (i32, [vp, vp, vp]),
         "itsx_lazy_pending_uniques": (i32, [vp, vp]),
         "itsx_set_partial_coords": (i32, [vp, i32]),
@@ -267,6 +269,7 @@ def lib():
         "itsx_shard_last_error": (C.c_char_p, []),
         "itsx_owner_verdicts": (i32, [vp, vp, i64, vp]),
         "itsx_write_trimmed_fastq": (i32, [cp, cp, i32, i32, vp, vp, i64, vp, vp]),
+        "itsx_write_trimmed_fastq_strands": (i32, [cp, cp, i32, i32, vp, vp, vp, i64, vp, vp]),
         "itsx_write_trimmed_paired": (i32, [cp, cp, cp, cp, i32, i32, vp, vp, i64, vp, vp, vp, vp]),
         "itsx_trim_last_error": (cp, []),
         "itsx_io_read": (i32, [cp, vp, vp]),

@@ -535,6 +535,7 @@ struct itsx_ctx {
   // a streamed writer's device path (twdev_*, for itsx_twriter_set_device): a unit's raw text, its line index and the plan's scratch
   // (records, output text and deflate scratch are the batch writers' buffers above); tw_mu serialises the writers that share the context
   DBuf<uint8_t> tw_raw; DBuf<int32_t> tw_ls, tw_le; DBuf<int64_t> tw_lblk, tw_qsrc, tw_info;
+  DBuf<int8_t> tw_strand; DBuf<uint8_t> tw_comp; bool tw_comp_set = false;      // a unit's strands (itsx_twriter_strands) and iupac.h's complement table
   std::mutex tw_mu; bool tw_failed = false; float tw_ms_deflate = 0;
   // the device inflate (inflate_file): the uploaded file, the candidate scan's tiles and list, the members and their statuses, and the
   // text of the last successful call (inf_len bytes; -1: none).  inf_mu serialises the loader threads that share the context.
@@ -6881,6 +6882,7 @@ static int tw_alloc_unit(itsx_ctx *ctx, int64_t nbytes, int64_t count)
   HIPCHK(ctx->w_tstart.alloc((size_t)count + 1)); HIPCHK(ctx->w_tstop.alloc((size_t)count + 1));
   HIPCHK(ctx->w_trec.alloc((size_t)count + 1)); HIPCHK(ctx->tw_qsrc.alloc((size_t)count + 1));
   HIPCHK(ctx->w_tblk.alloc((size_t)trim_plan_blocks(count) * 3 + 3));
+  HIPCHK(ctx->tw_strand.alloc((size_t)count + 1)); HIPCHK(ctx->tw_comp.alloc(256));
   return ITSX_OK;
 }
 // one text in w_tout -> its gzip members
@@ -6906,10 +6908,20 @@ static int tw_unit(itsx_ctx *ctx, const itsx::TwUnit &u, bool &fits, std::string
   { const int rc = put_staged(ctx, u.text, nbytes, ctx->tw_raw.p); if (rc != ITSX_OK) return rc; }
   { const int rc = put_staged(ctx, reinterpret_cast<const char *>(u.start), n * 4, reinterpret_cast<uint8_t *>(ctx->w_tstart.p)); if (rc != ITSX_OK) return rc; }
   { const int rc = put_staged(ctx, reinterpret_cast<const char *>(u.stop), n * 4, reinterpret_cast<uint8_t *>(ctx->w_tstop.p)); if (rc != ITSX_OK) return rc; }
+  const bool flips = u.strand != nullptr && u.mode == 0;
+  if (flips) {
+    { const int rc = put_staged(ctx, reinterpret_cast<const char *>(u.strand), n, reinterpret_cast<uint8_t *>(ctx->tw_strand.p)); if (rc != ITSX_OK) return rc; }
+    if (!ctx->tw_comp_set) {
+      const int rc = put_staged(ctx, itsx::iupac_complement(), 256, ctx->tw_comp.p);
+      if (rc != ITSX_OK) return rc;
+      ctx->tw_comp_set = true;
+    }
+  }
   step = "the unit's line index and plan";
   TrimUnitArgs ua{};
   ua.text = ctx->tw_raw.p; ua.nbytes = nbytes; ua.count = n; ua.ls = ctx->tw_ls.p; ua.le = ctx->tw_le.p;
   ua.start = ctx->w_tstart.p; ua.stop = ctx->w_tstop.p; ua.mode = u.mode; ua.ccs = u.ccs ? 1 : 0;
+  ua.strand = flips ? ctx->tw_strand.p : nullptr;
   ua.lblk = ctx->tw_lblk.p; ua.blk = ctx->w_tblk.p; ua.rec = ctx->w_trec.p; ua.qsrc = ctx->tw_qsrc.p; ua.info = ctx->tw_info.p;
   launch_trim_unit(ua, st);
   HIPCHK(hipGetLastError());
@@ -6928,6 +6940,7 @@ static int tw_unit(itsx_ctx *ctx, const itsx::TwUnit &u, bool &fits, std::string
   TrimCopyArgs ca{};
   ca.rec = ctx->w_trec.p; ca.n = n; ca.seq = ca.qual = ca.titles = ctx->tw_raw.p; ca.qsrc = ctx->tw_qsrc.p;
   ca.total = total; ca.ccs = ua.ccs; ca.out = ctx->w_tout.p;
+  ca.comp = flips ? ctx->tw_comp.p : nullptr;
   launch_trim_copy(ca, st);
   HIPCHK(hipGetLastError());
   step = "deflating the unit's output";

@@ -241,6 +241,7 @@ struct TrimCopyArgs {
   int64_t total, ntiles; int32_t ccs;           // bytes of the text (ntiles: set by the launcher)
   uint32_t *out;                                // trim_copy_bytes(total) bytes
   const int64_t *qsrc = nullptr;                // [n] record r's first kept quality where it does not sit at rec[r].src of `qual` (a unit of raw text)
+  const uint8_t *comp = nullptr;                // with qsrc: the 256-byte complement table (iupac.h) of a unit with flipped records, marked by qsrc[r] < 0
 };
 int64_t trim_copy_bytes(int64_t total);
 void launch_trim_copy(TrimCopyArgs a, hipStream_t st);
@@ -267,6 +268,7 @@ struct TrimUnitArgs {
   int64_t count;                                // records the host counted
   int32_t *ls, *le;                             // [4 count + 1] line k is text[ls[k], le[k]) (its newline and a '\r' before it left out)
   const int32_t *start, *stop;                  // [count]
+  const int8_t *strand;                         // [count] or null: -1 = the record is written from its reverse complement (mode 0)
   int32_t mode, ccs;                            // itsx_twriter_set_mode's mode
   int64_t *lblk;                                // [trim_index_blocks(nbytes) + 1] scratch
   int64_t *blk;                                 // [3 x trim_plan_blocks(count) + 3] scratch

@@ -16,7 +16,9 @@
 //          shape, and the copy kernel as it is, once per side.
 //   unit   a unit of RAW FASTQ text (the streamed writers' device path, itsx_twriter_set_device): the line index from its newline bytes
 //          (popcount per thread, two scans), trusted where the unit has 4 lines per record; the plan of itsx_twriter::work's two modes;
-//          and the copy kernel with all three planes = that text and a quality source of its own per record (k_trim_copy<true>).
+//          and the copy kernel with all three planes = that text and a quality source of its own per record (k_trim_copy<true, .>).
+//          A unit that has a record of strand -1 (itsx_twriter_strands) takes k_trim_copy<true, true>, which reads such a record's
+//          lines backwards and complements its bases; every other unit, and every batch, takes the kernel without that branch.
 //   orient the records of the reads itsx_orient_apply keeps: reverse reads with IUPAC-complemented reversed bases and reversed qualities.
 #include <algorithm>
 #include "engine.h"
@@ -228,8 +230,9 @@ __device__ __forceinline__ uint32_t trim_load4(const uint8_t *p)
   const uint64_t both = ((uint64_t)w[1] << 32) | w[0];
   return (uint32_t)(both >> (8 * (unsigned)(reinterpret_cast<uintptr_t>(p) & 3)));
 }
-// byte p of record q's text (qs: its first kept quality in a.qual)
-__device__ __forceinline__ uint32_t trim_byte(const TrimCopyArgs &a, const TrimRec &q, int64_t qs, int64_t p)
+// byte p of record q's text (qs: its first kept quality in a.qual).  fl (FLIP only): the record is flipped -- q.src / qs are where its
+// slice's FIRST base / quality sits, the slice runs backwards from there, and a base goes through the complement table
+template <bool FLIP> __device__ __forceinline__ uint32_t trim_byte(const TrimCopyArgs &a, const TrimRec &q, int64_t qs, int64_t p, bool fl, const uint8_t *comp)
 {
   const int64_t pre = a.ccs ? 17 : 0;
   if (p < q.tl) return a.titles[q.toff + p];
@@ -239,6 +242,7 @@ __device__ __forceinline__ uint32_t trim_byte(const TrimCopyArgs &a, const TrimR
   if (p < q.slen + 2 * pre) {
     if (p < pre) return (uint8_t)TRIM_CCS_FWD[p];
     p -= pre;
+    if (FLIP && fl && p < q.slen) return comp[a.seq[q.src - p]];
     return p < q.slen ? a.seq[q.src + p] : (uint8_t)TRIM_CCS_REV[p - q.slen];
   }
   p -= q.slen + 2 * pre;
@@ -246,15 +250,25 @@ __device__ __forceinline__ uint32_t trim_byte(const TrimCopyArgs &a, const TrimR
   p -= 3;
   if (p < q.slen + 2 * pre) {
     p -= pre;
+    if (FLIP && fl && p >= 0 && p < q.slen) return a.qual[qs - p];
     return (p >= 0 && p < q.slen) ? a.qual[qs + p] : '~';
   }
   return '\n';
 }
 
 // QS: a record's qualities start at a.qsrc[r] (a unit of raw text, where all three planes are that text), not at rec[r].src
-template <bool QS> __global__ __launch_bounds__(TC_BLOCK) void k_trim_copy(TrimCopyArgs a)
+// FLIP (a unit with strands, QS only): a.qsrc[r] < 0 marks a record written from its reverse complement; ~a.qsrc[r] and rec[r].src are
+// then the source bytes of its slice's first quality and base, and output byte p comes from source byte (first - p).  A dword wholly
+// inside such a line is the two aligned loads that hold source bytes s - 3 .. s, byte-reversed, and for bases four look-ups in the
+// complement table (256 bytes of LDS = 64 dwords, one per bank: lanes that meet in a dword read the same dword, which is a broadcast).
+// The lanes' source addresses run DOWN by one dword per lane where they ran up: the wave still reads one contiguous stretch.
+// A base line never starts at byte 0 of a unit (its title precedes it), so s - 3 is inside the text.
+template <bool QS, bool FLIP> __global__ __launch_bounds__(TC_BLOCK) void k_trim_copy(TrimCopyArgs a)
 {
+  static_assert(QS || !FLIP, "only a unit of raw text has flipped records");
   const int64_t pre = a.ccs ? 17 : 0;
+  __shared__ uint8_t comp[FLIP ? 256 : 4];
+  if (FLIP) { comp[threadIdx.x] = a.comp[threadIdx.x]; __syncthreads(); }
   for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
     const int64_t t0 = tile * TC_TILE, t1 = t0 + TC_TILE < a.total ? t0 + TC_TILE : a.total;
     const int64_t rlo = trim_find(a.rec, 0, a.n, t0), rhi = trim_find(a.rec, rlo, a.n, t1 - 1);      // the same in every lane
@@ -267,20 +281,36 @@ template <bool QS> __global__ __launch_bounds__(TC_BLOCK) void k_trim_copy(TrimC
       int64_t next = a.rec[r + 1].out;
       const int64_t p = o - q.out;
       const uint8_t *src = nullptr;
+      int64_t qs = 0; bool fl = false;           // (FLIP only)
+      int rev = 0;                               // 1: a flipped record's qualities, 2: its bases
+      if (FLIP) { qs = a.qsrc[r]; fl = qs < 0; if (fl) qs = ~qs; }
       if (o + 4 <= next) {                       // the dword lies in one record: in one of its three sources?
         const int64_t ps = p - q.tl - 1 - pre, pq = ps - q.slen - 2 * pre - 3;
         if (p + 4 <= q.tl) src = a.titles + q.toff + p;
-        else if (ps >= 0 && ps + 4 <= q.slen) src = a.seq + q.src + ps;
-        else if (pq >= 0 && pq + 4 <= q.slen) src = a.qual + (QS ? a.qsrc[r] : q.src) + pq;
+        else if (ps >= 0 && ps + 4 <= q.slen) {
+          if (FLIP && fl) { src = a.seq + q.src - ps - 3; rev = 2; }
+          else src = a.seq + q.src + ps;
+        } else if (pq >= 0 && pq + 4 <= q.slen) {
+          if (FLIP && fl) { src = a.qual + qs - pq - 3; rev = 1; }
+          else src = a.qual + (FLIP ? qs : QS ? a.qsrc[r] : q.src) + pq;
+        }
       }
       uint32_t v = 0;
-      if (src) v = trim_load4(src);
-      else {
+      if (src) {
+        v = trim_load4(src);
+        if (FLIP && rev) {
+          v = __builtin_bswap32(v);
+          if (rev == 2) v = (uint32_t)comp[v & 255] | ((uint32_t)comp[(v >> 8) & 255] << 8) | ((uint32_t)comp[(v >> 16) & 255] << 16) | ((uint32_t)comp[v >> 24] << 24);
+        }
+      } else {
         for (int b = 0; b < 4; b++) {
           const int64_t ob = o + b;
           if (ob >= a.total) break;              // the text's last dword: the bytes past its end stay 0 (the buffer is padded to whole tiles)
-          while (ob >= next) { r++; q = a.rec[r]; next = a.rec[r + 1].out; }
-          v |= trim_byte(a, q, QS ? a.qsrc[r] : q.src, ob - q.out) << (8 * b);
+          while (ob >= next) {
+            r++; q = a.rec[r]; next = a.rec[r + 1].out;
+            if (FLIP) { qs = a.qsrc[r]; fl = qs < 0; if (fl) qs = ~qs; }
+          }
+          v |= trim_byte<FLIP>(a, q, FLIP ? qs : QS ? a.qsrc[r] : q.src, ob - q.out, fl, comp) << (8 * b);
         }
       }
       a.out[o >> 2] = v;
@@ -295,8 +325,9 @@ void launch_trim_copy(TrimCopyArgs a, hipStream_t st)
   if (a.total <= 0) return;
   a.ntiles = (a.total + TC_TILE - 1) / TC_TILE;
   const unsigned grid = (unsigned)std::min<int64_t>(a.ntiles, 256 * 8);
-  if (a.qsrc) hipLaunchKernelGGL(k_trim_copy<true>, dim3(grid), dim3(TC_BLOCK), 0, st, a);
-  else hipLaunchKernelGGL(k_trim_copy<false>, dim3(grid), dim3(TC_BLOCK), 0, st, a);
+  if (a.qsrc && a.comp) hipLaunchKernelGGL((k_trim_copy<true, true>), dim3(grid), dim3(TC_BLOCK), 0, st, a);
+  else if (a.qsrc) hipLaunchKernelGGL((k_trim_copy<true, false>), dim3(grid), dim3(TC_BLOCK), 0, st, a);
+  else hipLaunchKernelGGL((k_trim_copy<false, false>), dim3(grid), dim3(TC_BLOCK), 0, st, a);
 }
 
 // ---- a unit of raw FASTQ text (itsx_twriter_set_device) -------------------------------------------------------------------------
@@ -348,7 +379,9 @@ __global__ __launch_bounds__(LI_BLOCK) void k_trim_index_sums(TrimUnitArgs a, in
 
 // record r of the unit = lines 4 r .. 4 r + 3: whether it is written and its slice, as itsx_twriter::work decides both (mode 0: written
 // iff start >= 0 && stop >= 0 && start < stop; mode 1: iff stop != INT32_MIN, INT32_MAX an open end), and whether it is a record at all
-struct TrimUnitOne { int32_t t0, s0, q0, tl, lo, sl; bool w, bad; };
+// flip (a.strand, mode 0): the record's strand is -1 -- its slice is that of the reversed read, so its first base and quality are source
+// byte L - 1 - lo of their lines and the copy walks down from there (fs: that offset instead of lo); the output's length is the same
+struct TrimUnitOne { int32_t t0, s0, q0, tl, lo, sl, fs; bool w, bad, flip; };
 __device__ __forceinline__ TrimUnitOne trim_unit_one(const TrimUnitArgs &a, int64_t r)
 {
   TrimUnitOne u;
@@ -361,6 +394,8 @@ __device__ __forceinline__ TrimUnitOne trim_unit_one(const TrimUnitArgs &a, int6
   if (a.mode == 1) { u.w = e != (int64_t)INT32_MIN; trim_py_slice(L, s, e, e == (int64_t)INT32_MAX, u.lo, u.sl); }
   else { u.w = s >= 0 && e >= 0 && s < e; trim_py_slice(L, s, e, false, u.lo, u.sl); }
   if (u.bad) { u.w = false; u.lo = u.sl = 0; }
+  u.flip = a.strand && a.mode == 0 && !u.bad && a.strand[r] < 0;
+  u.fs = u.flip ? L - 1 - u.lo : u.lo;
   return u;
 }
 
@@ -374,7 +409,7 @@ template <bool SCATTER> __global__ __launch_bounds__(TR_BLOCK) void k_trim_unit_
 #pragma unroll
   for (int i = 0; i < TR_ITEMS; i++) {
     const int64_t r = base + i;
-    u[i].w = false; u[i].bad = false;
+    u[i].w = false; u[i].bad = false; u[i].flip = false;
     if (r < a.count) u[i] = trim_unit_one(a, r);
     if (u[i].w) { v[0] += (int64_t)u[i].tl + 5 + 2 * ((int64_t)u[i].sl + extra); v[1]++; v[2] += (int64_t)u[i].sl + extra; }
     if (!SCATTER && u[i].bad) a.info[1] = 1;
@@ -391,8 +426,8 @@ template <bool SCATTER> __global__ __launch_bounds__(TR_BLOCK) void k_trim_unit_
     const int64_t r = base + i;
     if (r >= a.count) break;
     TrimRec q;
-    q.out = o; q.src = (int64_t)u[i].s0 + u[i].lo; q.toff = u[i].t0; q.tl = u[i].tl; q.slen = u[i].sl;
-    a.rec[r] = q; a.qsrc[r] = (int64_t)u[i].q0 + u[i].lo;
+    q.out = o; q.src = (int64_t)u[i].s0 + u[i].fs; q.toff = u[i].t0; q.tl = u[i].tl; q.slen = u[i].sl;
+    a.rec[r] = q; a.qsrc[r] = u[i].flip ? ~((int64_t)u[i].q0 + u[i].fs) : (int64_t)u[i].q0 + u[i].fs;
     if (u[i].w) o += (int64_t)u[i].tl + 5 + 2 * ((int64_t)u[i].sl + extra);
   }
 }

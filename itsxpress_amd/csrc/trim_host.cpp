@@ -125,6 +125,15 @@ void emit(Writer &w, const View &title, const char *seq, const char *qual, int64
   if (total) *total += (hi - lo) + (ccs ? 34 : 0);
 }
 
+// a reverse read as vsearch --orient --fastqout writes it: IUPAC-complemented reversed bases (iupac.h), reversed qualities
+void revcomp_record(const Rec &rec, std::string &t, std::string &q)
+{
+  const char *comp = itsx::iupac_complement();
+  const size_t L = rec.seq.size();
+  t.resize(L); q.resize(L);
+  for (size_t k = 0; k < L; k++) { t[k] = comp[(unsigned char)rec.seq.p[L - 1 - k]]; q[k] = rec.qual.p[L - 1 - k]; }
+}
+
 }  // namespace
 
 extern "C" {
@@ -134,6 +143,15 @@ const char *itsx_trim_last_error(void) { return g_trim_error.c_str(); }
 int itsx_write_trimmed_fastq(const char *seq_path, const char *out_path, int compression, int trim_ccs,
                              const int32_t *start, const int32_t *stop, int64_t n_records,
                              int64_t *n_written, int64_t *total_len)
+{
+  return itsx_write_trimmed_fastq_strands(seq_path, out_path, compression, trim_ccs, start, stop, nullptr, n_records, n_written, total_len);
+}
+
+// the same with a strand per record: a record of strand -1 is sliced from its reverse complement, as itsx_write_oriented_fastq
+// would have written it (strand == NULL: every record as it is)
+int itsx_write_trimmed_fastq_strands(const char *seq_path, const char *out_path, int compression, int trim_ccs,
+                                     const int32_t *start, const int32_t *stop, const int8_t *strand, int64_t n_records,
+                                     int64_t *n_written, int64_t *total_len)
 {
   if (!seq_path || !out_path || !start || !stop) { g_trim_error = "null argument"; return ITSX_E_ARG; }
   if (compression < 0 || compression > 2) { g_trim_error = "compression must be 0 (plain), 1 (gzip) or 2 (zstd)"; return ITSX_E_ARG; }
@@ -150,6 +168,7 @@ int itsx_write_trimmed_fastq(const char *seq_path, const char *out_path, int com
     int rc = itsx_twriter_open(out_path, compression, trim_ccs, &tw);
     if (rc != ITSX_OK) return rc;
     rc = itsx_twriter_text(tw, in.s, (int64_t)size, 1);
+    if (rc == ITSX_OK && strand) rc = itsx_twriter_strands(tw, 0, n_records, strand);
     if (rc == ITSX_OK) rc = itsx_twriter_coords(tw, 0, n_records, start, stop, nullptr);
     int64_t nw = 0, tot = 0;
     const int crc = itsx_twriter_close(tw, &nw, &tot);
@@ -169,13 +188,17 @@ int itsx_write_trimmed_fastq(const char *seq_path, const char *out_path, int com
   }
   if (!out.open(out_path, compression)) return ITSX_E_IO;        // (the single-threaded way through: one I/O thread, or a text below ITSX_WRITE_MIN_MB)
   Rec rec; int64_t i = 0, nw = 0, tot = 0; int rc;
+  std::string ft, fq;
   while ((rc = in.next(rec)) == 1) {
     if (i >= n_records) { g_trim_error = "more records in the file than coordinates"; return ITSX_E_ARG; }
     const int64_t a = start[i], b = stop[i];
+    const bool flip = strand && strand[i] < 0;
     i++;
     if (a < 0 || b < 0 || !(a < b)) continue;
     int64_t lo, hi; py_slice((int64_t)rec.seq.size(), a, b, false, lo, hi);
-    emit(out, rec.title, rec.seq.p, rec.qual.p, lo, hi, trim_ccs != 0, &tot);
+    const char *sq = rec.seq.p, *ql = rec.qual.p;
+    if (flip) { revcomp_record(rec, ft, fq); sq = ft.data(); ql = fq.data(); }
+    emit(out, rec.title, sq, ql, lo, hi, trim_ccs != 0, &tot);
     nw++;
   }
   if (rc < 0) { g_trim_error = "malformed FASTQ record " + std::to_string(i); return ITSX_E_FORMAT; }
@@ -234,6 +257,7 @@ struct itsx_twriter {
   size_t counted_prefix = 0;               // units [0, counted_prefix) know their `first`
   int64_t records_cut = 0;                 // records in those units
   StableVec<int32_t> start, stop; StableVec<uint8_t> decided;
+  StableVec<int8_t> strand;                // itsx_twriter_strands: empty (no record is flipped), or a row for every record that has coordinates
   size_t next_write = 0; bool flushing = false;
   bool wrote_any = false, failed = false, malformed = false, closing = false;
   std::string err;
@@ -295,7 +319,7 @@ struct itsx_twriter {
   }
   void work();
   void work_device();
-  int slice(size_t lo, size_t hi, int64_t first, std::string &out, int64_t &n_out, int64_t &t_out) const;
+  int slice(size_t lo, size_t hi, int64_t first, bool strands, std::string &out, int64_t &n_out, int64_t &t_out) const;
   // writes every finished unit that is next in order (called without the lock)
   void flush_ready()
   {
@@ -348,8 +372,9 @@ struct itsx_twriter {
   }
 };
 
-// the records of text [lo, hi) (the first is record `first`) sliced into `out`; 0, or -1 at a malformed record
-int itsx_twriter::slice(size_t lo, size_t hi, int64_t first, std::string &out, int64_t &n_out, int64_t &t_out) const
+// the records of text [lo, hi) (the first is record `first`) sliced into `out`; 0, or -1 at a malformed record.  strands: the writer
+// has strand rows (read with `mu` held when the job was taken), and a record of strand -1 goes through a scratch pair of strings
+int itsx_twriter::slice(size_t lo, size_t hi, int64_t first, bool strands, std::string &out, int64_t &n_out, int64_t &t_out) const
 {
   Records r; r.s = base + lo; r.end = base + hi;
   Rec rec; int rc;
@@ -358,8 +383,10 @@ int itsx_twriter::slice(size_t lo, size_t hi, int64_t first, std::string &out, i
   static const char *fwd = "GACAGGTACAAGAAGGA", *rev = "TTAACCCAGTCTCCAGT";
   int64_t i = first;
   n_out = t_out = 0;
+  std::string ft, fq;
   while ((rc = r.next(rec)) == 1) {
     const int64_t a = start[(size_t)i], b = stop[(size_t)i];      // (rows of decided records are not written to any more)
+    const bool flip = strands && strand[(size_t)i] < 0;
     i++;
     int64_t l, h;
     if (mode == 1) {
@@ -369,13 +396,15 @@ int itsx_twriter::slice(size_t lo, size_t hi, int64_t first, std::string &out, i
       if (a < 0 || b < 0 || !(a < b)) continue;
       py_slice((int64_t)rec.seq.size(), a, b, false, l, h);
     }
+    const char *sq = rec.seq.p, *ql = rec.qual.p;
+    if (flip) { revcomp_record(rec, ft, fq); sq = ft.data(); ql = fq.data(); }
     out.append(rec.title.p, rec.title.n); out += '\n';
     if (ccs) out += fwd;
-    out.append(rec.seq.p + l, (size_t)(h - l));
+    out.append(sq + l, (size_t)(h - l));
     if (ccs) out += rev;
     out += "\n+\n";
     if (ccs) out.append(17, '~');
-    out.append(rec.qual.p + l, (size_t)(h - l));
+    out.append(ql + l, (size_t)(h - l));
     if (ccs) out.append(17, '~');
     out += '\n';
     n_out++; t_out += (h - l) + (ccs ? 34 : 0);
@@ -391,8 +420,9 @@ void itsx_twriter::work_device()
 {
   std::string out, comp, e;
   std::vector<int32_t> a, b;
+  std::vector<int8_t> sd;
   for (;;) {
-    size_t k, lo, hi; int64_t first, count; bool skip, host;
+    size_t k, lo, hi; int64_t first, count; bool skip, host, strands;
     {
       std::unique_lock<std::mutex> lk(mu);
       cv_work.wait(lk, [&] { return quit || !djobs.empty(); });
@@ -401,6 +431,7 @@ void itsx_twriter::work_device()
       busy++;
       lo = units[k].lo; hi = units[k].hi; first = units[k].first; count = units[k].count;
       skip = dev_failed; host = dev_host_slice || malformed || hi - lo >= ((size_t)1 << 31);
+      strands = strand.size() > 0;
     }
     int64_t n_out = 0, t_out = 0;
     int rc = ITSX_OK; bool bad = false;
@@ -410,11 +441,14 @@ void itsx_twriter::work_device()
       if (!host) {
         a.resize((size_t)count); b.resize((size_t)count);
         for (int64_t i = 0; i < count; i++) { a[(size_t)i] = start[(size_t)(first + i)]; b[(size_t)i] = stop[(size_t)(first + i)]; }
-        itsx::TwUnit u{base + lo, hi - lo, a.data(), b.data(), count, mode, ccs ? 1 : 0};
+        // (the unit's strands go up only where one of them is -1: a unit without a flipped record takes the copy kernel as it always was)
+        bool any = false;
+        if (strands) { sd.resize((size_t)count); for (int64_t i = 0; i < count; i++) { sd[(size_t)i] = strand[(size_t)(first + i)]; any = any || sd[(size_t)i] < 0; } }
+        itsx::TwUnit u{base + lo, hi - lo, a.data(), b.data(), count, mode, ccs ? 1 : 0, any ? sd.data() : nullptr};
         rc = itsx::twdev_unit(dev, u, fits, comp, n_out, t_out, e);
       }
       if (rc == ITSX_OK && !fits) {
-        bad = slice(lo, hi, first, out, n_out, t_out) < 0;
+        bad = slice(lo, hi, first, strands, out, n_out, t_out) < 0;
         if (!bad && !out.empty()) rc = itsx::twdev_text(dev, out.data(), out.size(), comp, e);
       }
     }
@@ -438,7 +472,7 @@ void itsx_twriter::work()
   std::string out;
   for (;;) {
     std::pair<int, size_t> j;
-    size_t lo, hi; int64_t first = 0;
+    size_t lo, hi; int64_t first = 0; bool strands;
     {
       std::unique_lock<std::mutex> lk(mu);
       cv_work.wait(lk, [&] { return quit || !jobs.empty(); });
@@ -446,6 +480,7 @@ void itsx_twriter::work()
       j = jobs.front(); jobs.pop_front();
       busy++;
       lo = units[j.second].lo; hi = units[j.second].hi; first = units[j.second].first;
+      strands = strand.size() > 0;
     }
     Records r; r.s = base + lo; r.end = base + hi;
     Rec rec; int rc;
@@ -461,7 +496,7 @@ void itsx_twriter::work()
       continue;
     }
     int64_t n_out = 0, t_out = 0;
-    rc = slice(lo, hi, first, out, n_out, t_out);
+    rc = slice(lo, hi, first, strands, out, n_out, t_out);
     std::string comp;
     bool ok = rc == 0;
     if (ok && !out.empty()) ok = pc.run(out, comp);
@@ -502,6 +537,7 @@ int itsx_twriter_set_mode(itsx_twriter *w, int32_t mode)
 {
   if (!w || mode < 0 || mode > 1) { g_trim_error = "itsx_twriter_set_mode: mode must be 0 or 1"; return ITSX_E_ARG; }
   std::lock_guard<std::mutex> lk(w->mu);
+  if (mode == 1 && w->strand.size() > 0) { g_trim_error = "itsx_twriter_set_mode: the writer has strands, and a paired run's mates are not oriented"; return ITSX_E_ARG; }
   w->mode = mode;
   return ITSX_OK;
 }
@@ -527,7 +563,8 @@ int itsx_twriter_text(itsx_twriter *w, const char *base, int64_t avail, int32_t 
   if (!w || avail < 0 || (!base && avail > 0)) { g_trim_error = "itsx_twriter_text: bad argument"; return ITSX_E_ARG; }
   std::lock_guard<std::mutex> lk(w->mu);
   if (w->text_done || (w->base && base != w->base) || (size_t)avail < w->avail) { g_trim_error = "itsx_twriter_text: the text grows at one address, front to back"; return ITSX_E_ARG; }
-  w->base = base; w->avail = (size_t)avail; w->text_done = last != 0;
+  if (w->base != base) w->base = base;      // (written once: the pool's threads read it without the lock)
+  w->avail = (size_t)avail; w->text_done = last != 0;
   w->cut_units();
   return ITSX_OK;
 }
@@ -540,7 +577,25 @@ int itsx_twriter_coords(itsx_twriter *w, int64_t first_record, int64_t n, const 
   w->start.append(start, (size_t)n, 0);
   w->stop.append(stop, (size_t)n, 0);
   w->decided.append(decided, (size_t)n, 1);
+  if (w->strand.size() > 0 && w->strand.size() < w->start.size()) w->strand.append(nullptr, w->start.size() - w->strand.size(), 0);      // (no row: as it is)
   w->advance();
+  return ITSX_OK;
+}
+
+// The strands of records first_record .. first_record + n - 1 (record order, no gaps; before the same records' coordinates): a record
+// of strand -1 is written from its reverse complement -- bases reversed and complemented byte by byte with iupac.h's table, qualities
+// reversed, which is the record itsx_write_oriented_fastq writes -- and start / stop are the Python slice of THAT record.  +1 and 0 are
+// written as they are, and so is every record of a writer that never gets this call.  Mode 0 (single-end) only.
+int itsx_twriter_strands(itsx_twriter *w, int64_t first_record, int64_t n, const int8_t *strand)
+{
+  if (!w || n < 0 || (n > 0 && !strand)) { g_trim_error = "itsx_twriter_strands: bad argument"; return ITSX_E_ARG; }
+  std::lock_guard<std::mutex> lk(w->mu);
+  if (w->mode != 0) { g_trim_error = "itsx_twriter_strands: a paired run's mates (mode 1) are not oriented"; return ITSX_E_ARG; }
+  if (first_record < (int64_t)w->start.size()) { g_trim_error = "itsx_twriter_strands: strands arrive before the coordinates of the same records"; return ITSX_E_ARG; }
+  if (first_record != (int64_t)std::max(w->strand.size(), w->start.size())) { g_trim_error = "itsx_twriter_strands: strands arrive in record order, without gaps"; return ITSX_E_ARG; }
+  if (n == 0) return ITSX_OK;
+  if (w->strand.size() < w->start.size()) w->strand.append(nullptr, w->start.size() - w->strand.size(), 0);
+  w->strand.append(strand, (size_t)n, 0);
   return ITSX_OK;
 }
 
@@ -839,8 +894,7 @@ int itsx_write_oriented_fastq(const char *seq_path, const char *out_path, const 
   Records in; Writer out;
   if (!in.open(seq_path)) return ITSX_E_IO;
   if (!out.open(out_path, itsx_io::PLAIN, true)) return ITSX_E_IO;      // oriented.fq is read back by the loader and the trimmer
-  const char *comp = itsx::iupac_complement();      // (iupac.h: itsx_orient_apply orients the host text with the same table)
-  Rec rec; int64_t i = 0, nw = 0; int rc;
+  Rec rec; int64_t i = 0, nw = 0; int rc;                          // (iupac.h: itsx_orient_apply orients the host text with the same table)
   std::string t, q;
   while ((rc = in.next(rec)) == 1) {
     if (i >= n_records) { g_trim_error = "more records in the file than orientations"; return ITSX_E_ARG; }
@@ -848,8 +902,7 @@ int itsx_write_oriented_fastq(const char *seq_path, const char *out_path, const 
     if (s == 0) continue;
     const size_t L = rec.seq.size();
     if (s < 0) {
-      t.resize(L); q.resize(L);
-      for (size_t k = 0; k < L; k++) { t[k] = comp[(unsigned char)rec.seq.p[L - 1 - k]]; q[k] = rec.qual.p[L - 1 - k]; }
+      revcomp_record(rec, t, q);
       emit(out, rec.title, t.data(), q.data(), 0, (int64_t)L, false, nullptr);
     } else emit(out, rec.title, rec.seq.p, rec.qual.p, 0, (int64_t)L, false, nullptr);
     nw++;

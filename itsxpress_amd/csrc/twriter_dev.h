@@ -18,6 +18,7 @@ struct TwUnit {
   const char *text; size_t nbytes;              // the unit's raw text (whole records)
   const int32_t *start, *stop; int64_t count;   // its records' coordinates; count as the host counted them
   int mode, ccs;
+  const int8_t *strand = nullptr;               // [count], or null where no record of the unit is flipped (itsx_twriter_strands; mode 0)
 };
 // index, plan, copy and deflate of one unit.  fits = false (and nothing else set): the unit's lines are not 4 per record, or a record is
 // malformed -- the caller slices it on the host and hands the text to twdev_text.  comp: the unit's gzip members (empty: no record

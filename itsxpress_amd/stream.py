@@ -192,6 +192,12 @@ class _Output:
         else:
             g = np.zeros(n, np.int64)
             start = np.full(n, -1, np.int32); stop = np.full(n, -1, np.int32); dec = np.ones(n, np.uint8)
+        if "orient" in st:
+            # plan_orient: the chunk's reads were oriented where they were loaded -- the writer slices a read of strand -1 from its
+            # reverse complement (strands before the same records' coordinates: itsx_twriter_strands)
+            sd = np.ascontiguousarray(st["orient"][0], np.int8)
+            assert sd.shape[0] == n
+            self._chk(self.L.itsx_twriter_strands(self.w, int(st["base"]), n, sd.ctypes.data))
         self._chk(self.L.itsx_twriter_text(self.w, C.c_void_p(self.base_ptr), int(st["text_end"]), 1 if st["last"] else 0))
         self._chk(self.L.itsx_twriter_coords(self.w, int(st["base"]), n, start.ctypes.data, stop.ctypes.data, dec.ctypes.data))
         idx = np.flatnonzero(dec == 0)
@@ -438,6 +444,7 @@ class StreamEngine(ShardedOps):
         self._stream2 = None
         self._last_merge = None
         self.n_pairs = 0
+        self._orient_plan = None      # plan_orient(): every chunk orients its reads by the profiles before it dereplicates them
 
     # Where the planned outputs' gzip bytes are made (plan_output, plan_output_paired with gzipped=True): "host" (the default: the
     # writer's pool deflates, byte for byte what it always wrote) or "device" (one small Engine of the writers' own indexes, slices and
@@ -523,6 +530,32 @@ class StreamEngine(ShardedOps):
                       "ccs": False, "domE": float(domE),
                       "deflate": self._plan_deflate(gzipped, zstd_file, "plan_output_paired"), "device": self.device}
 
+    def plan_orient(self, F1=1e-6):
+        """Say BEFORE search() that the reads are to be oriented by the loaded profiles (Engine.orient_profiles_apply): a read's strand
+        is a function of its text, the profiles and F1 alone, so every chunk orients its own reads right after it has loaded them and
+        everything downstream -- dereplication, search, coordinates, the planned output -- is what a streamed run over oriented.fq
+        computes.  No oriented.fq is written: the writer gets the strands and slices a reverse read from its reverse complement.
+        orient_strands() has the strands once the pipeline has run.  Single-end input only."""
+        if getattr(self, "_path2", None) is not None:
+            raise EngineError(-5, "plan_orient: orientation by the profiles is not streamed for a paired sample (merge_pairs_load)")
+        self._orient_plan = float(F1)
+        if self._loaded:                                  # chunks loaded without the plan: the pipeline runs again
+            self.close()
+            self._loaded = self._searched = self._final = False
+            self._derep = None
+
+    def orient_strands(self):
+        """(strand, count_fwd, count_rev) of every read of the file, in record order, as the chunks' orient_profiles_apply returned
+        them (plan_orient); the pipeline must have run"""
+        if self._orient_plan is None:
+            raise EngineError(-1, "orient_strands: no orientation was planned (plan_orient)")
+        if not self._loaded:
+            raise EngineError(-1, "orient_strands: the pipeline has not run yet (search())")
+        parts = [st["orient"] for _, st in self._engs]
+        if not parts:
+            return np.zeros(0, np.int8), np.zeros(0, np.int32), np.zeros(0, np.int32)
+        return tuple(np.concatenate([p[j] for p in parts]) for j in range(3))
+
     def output_planned_paired(self, outfile1, outfile2, left, right, gzipped=False, zstd_file=False):
         p = self._plan
         return (self._out is not None and p is not None and p.get("out2") == outfile2 and p["out"] == outfile1 and p["left"] == left
@@ -562,6 +595,9 @@ class StreamEngine(ShardedOps):
         for p in (r1, r2):
             if not os.path.exists(p):
                 raise FileNotFoundError(p)
+        if self._orient_plan is not None:
+            raise EngineError(-5, "merge_pairs_load: an orientation by the profiles is planned (plan_orient), and that is not streamed "
+                                  "for a paired sample")
         self.close()
         self._path, self._path2 = r1, r2
         self._merge = dict(maxdiffs=int(maxdiffs), maxee=float(maxee), allow_stagger=bool(allow_stagger))
@@ -671,6 +707,14 @@ class StreamEngine(ShardedOps):
             t1 = time.perf_counter()
             if ptr2 is None:
                 eng.load_reads_text(ptr, nb)
+                if self._orient_plan is not None:
+                    if self._profiles is None:
+                        raise EngineError(-1, "plan_orient: the reads are oriented by the profiles, and no profiles are loaded "
+                                              "(load_profiles before the pipeline runs)")
+                    # (the context builds the flipped host text beside the stream's, which the writer reads and which stays as it is)
+                    st["orient"] = eng.orient_profiles_apply(self._orient_plan) if eng.n_reads else \
+                        (np.zeros(0, np.int8), np.zeros(0, np.int32), np.zeros(0, np.int32))
+                    st["orient_ms"] = float(getattr(eng, "last_orient_ms", 0.0)) if eng.n_reads else 0.0
             else:
                 npairs, _, st["merged_index"] = eng.merge_pairs_load_text(ptr, nb, ptr2, nb2, **self._merge)
                 st["pairs"] = int(npairs)
@@ -988,12 +1032,12 @@ class StreamEngine(ShardedOps):
         return res
 
     def orient_profiles(self, F1=1e-6):
-        raise EngineError(-5, "orientation by the profiles (orient_profiles) is not streamed: run it without ITSXPRESS_STREAM "
-                              "(DESIGN.md section 9)")
+        raise EngineError(-5, "orientation by the profiles (orient_profiles) is a whole-file call and is not streamed: plan_orient() "
+                              "before search() orients a streamed run chunk by chunk (DESIGN.md section 9)")
 
     def orient_profiles_apply(self, F1=1e-6):
-        raise EngineError(-5, "orientation by the profiles (orient_profiles_apply) is not streamed: run it without ITSXPRESS_STREAM "
-                              "(DESIGN.md section 9)")
+        raise EngineError(-5, "orientation by the profiles (orient_profiles_apply) is a whole-file call and is not streamed: plan_orient() "
+                              "before search() orients a streamed run chunk by chunk (DESIGN.md section 9)")
 
     def merge_pairs_files(self, r1, r2, out, maxdiffs=40, maxee=2.0, allow_stagger=False):
         return self._plain().merge_pairs_files(r1, r2, out, maxdiffs=maxdiffs, maxee=maxee, allow_stagger=allow_stagger)

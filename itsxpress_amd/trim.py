@@ -61,14 +61,25 @@ def read_text(path):
         L.itsx_io_free(buf)
 
 
-def write_trimmed_fastq(seq_file, outfile, start, stop, gzipped=False, trim_ccs=False, zstd_file=False):
+def write_trimmed_fastq(seq_file, outfile, start, stop, gzipped=False, trim_ccs=False, zstd_file=False, strand=None):
     """record i of seq_file -> record[start[i]:stop[i]] when both >= 0 and start < stop.
+    strand (one int8 per record, or None): a record of strand -1 is sliced from its reverse complement, as oriented.fq holds it
+    (IUPAC complement, qualities reversed); +1 and 0 are sliced as they are.
     Output plain, gzip (gzipped) or zstd (zstd_file).  Returns (records written, summed trimmed length)."""
     if not os.path.exists(seq_file):
         raise FileNotFoundError(seq_file)
     L = _lib.lib()
     start, stop = _i32(start), _i32(stop)
     n, tot = C.c_int64(0), C.c_int64(0)
+    if strand is not None:
+        st = np.ascontiguousarray(strand, np.int8)
+        if len(st) != len(start):
+            raise EngineError(-1, "write_trimmed_fastq: %d strands for %d records" % (len(st), len(start)))
+        rc = L.itsx_write_trimmed_fastq_strands(os.fsencode(seq_file), os.fsencode(outfile), _compression(gzipped, zstd_file), int(trim_ccs),
+                                                start.ctypes.data, stop.ctypes.data, st.ctypes.data, len(start), C.byref(n), C.byref(tot))
+        if rc != 0:
+            raise EngineError(rc, L.itsx_trim_last_error().decode())
+        return n.value, tot.value
     rc = L.itsx_write_trimmed_fastq(os.fsencode(seq_file), os.fsencode(outfile), _compression(gzipped, zstd_file), int(trim_ccs),
                                     start.ctypes.data, stop.ctypes.data, len(start), C.byref(n), C.byref(tot))
     if rc != 0:

@@ -3,7 +3,10 @@
 -- what a user of `itsxpress --fastq x.fq.gz --single_end --region ITS2 --outfile y.fq.gz` waits for, stage by stage
 (load = inflate + parse + upload + device packing; write = slice + block-parallel deflate; the input's text is shared
 between the two through the reader's cache, ITSX_TEXT_CACHE_GB=0 turns that off).
-Prints one JSON line.  usage: file_run.py [--reads 1000000] [--out-kind gz|zst|plain] [--stream [--check]]"""
+--flip F reverse-complements that share of the generated reads (qualities reversed); --stream --orient profiles orients them inside
+the streamed run (StreamEngine.plan_orient), --stream --orient staged as a user had to before: a plain engine writes oriented.fq,
+the streamed run reads that.
+Prints one JSON line.  usage: file_run.py [--reads 1000000] [--out-kind gz|zst|plain] [--stream [--check]] [--flip 0.33 --orient profiles]"""
 import argparse
 import gzip
 import json
@@ -34,6 +37,10 @@ def main():
     ap.add_argument("--parse", default="host", choices=["host", "device"], help="where the whole-file load parses the FASTQ text (Engine.parse); not with --stream")
     ap.add_argument("--loads", type=int, default=1, help="whole-file load: this many timed loads, the text cache cleared before each (the stages' total counts the last)")
     ap.add_argument("--in-writer", default="host", choices=["host", "device"], help="who writes the generated in.fastq.gz: the host writer (members of 4 MiB of text) or the device deflate (of 65 535 bytes)")
+    ap.add_argument("--flip", type=float, default=0.0, help="this share of the generated reads is reverse-complemented, qualities reversed")
+    ap.add_argument("--orient", default="none", choices=["none", "profiles", "staged"],
+                    help="--stream: orientation by the profiles -- profiles: inside the streamed run, chunk by chunk (plan_orient); staged: a plain engine "
+                         "orients the whole file and writes oriented.fq first, the streamed run reads that")
     ap.add_argument("--check", action="store_true", help="--stream: compare the coordinates with one context on the whole file")
     ap.add_argument("--input-dir", default="", help="keep the generated in.fastq.gz here and use it again when it is there (several arms over one file)")
     args = ap.parse_args()
@@ -41,6 +48,10 @@ def main():
         ap.error("--inflate device is the whole-file loaders' mode: the streamed loaders inflate on the host (not with --stream)")
     if args.parse == "device" and args.stream:
         ap.error("--parse device is the whole-file loaders' mode: the streamed loaders parse on the host (not with --stream)")
+    if args.orient != "none" and not args.stream:
+        ap.error("--orient is the streamed run's: with --stream")
+    if not 0.0 <= args.flip <= 1.0:
+        ap.error("--flip is a share of the reads: 0 .. 1")
     import synth
     from bench import its2_profiles
     from itsxpress_amd import Engine, _lib
@@ -57,7 +68,17 @@ def main():
     try:
         plain = os.path.join(tmp, "in.fastq")
         bases = np.frombuffer(blob, np.uint8)
-        kept = os.path.join(args.input_dir, "in_%s_%d%s.fastq.gz" % (args.shape, n, "_dev" if args.in_writer == "device" else "")) if args.input_dir else ""
+        flipped = np.random.default_rng(11).random(n) < args.flip          # (the same reads whether the file is generated or found)
+        comp = np.arange(256, dtype=np.uint8)
+        comp[np.frombuffer(b"ACGTacgt", np.uint8)] = np.frombuffer(b"TGCAtgca", np.uint8)
+
+        def read_in(i):
+            """read i as the input file holds it"""
+            s = bases[offs[i]:offs[i + 1]]
+            return comp[s[::-1]] if flipped[i] else s
+
+        tag = ("_flip%g" % args.flip if args.flip > 0 else "") + ("_dev" if args.in_writer == "device" else "")
+        kept = os.path.join(args.input_dir, "in_%s_%d%s.fastq.gz" % (args.shape, n, tag)) if args.input_dir else ""
         if kept and os.path.exists(kept) and os.path.exists(kept + ".size"):
             fq = kept
             in_bytes, in_gz = int(open(kept + ".size").read()), os.path.getsize(fq)
@@ -66,7 +87,10 @@ def main():
                 qtab = [(np.clip(38 - (np.arange(600) // 25) - rng.integers(0, 6, 600), 2, 40) + 33).astype(np.uint8).tobytes() for _ in range(64)]
                 for i in range(n):
                     s = bases[offs[i]:offs[i + 1]]
-                    f.write(b"@read%d 1:N:0:1\n" % i + s.tobytes() + b"\n+\n" + qtab[i & 63][:len(s)] + b"\n")
+                    q = qtab[i & 63][:len(s)]
+                    if flipped[i]:
+                        s, q = comp[s[::-1]], q[::-1]
+                    f.write(b"@read%d 1:N:0:1\n" % i + s.tobytes() + b"\n+\n" + q + b"\n")
             fq = kept or os.path.join(tmp, "in.fastq.gz")
             if kept:
                 os.makedirs(args.input_dir, exist_ok=True)
@@ -97,15 +121,35 @@ def main():
         if args.stream:
             # file-order chunks: chunk k is dereplicated and scored while chunk k + 1 is inflated and parsed (itsxpress_amd/stream.py)
             from itsxpress_amd.stream import StreamEngine
+            strand = None
+            if args.orient == "staged":
+                # what a streamed run needed before plan_orient: the whole file oriented on a plain engine, oriented.fq written in full
+                # size, and the streamed run inflating, parsing and loading that
+                from itsxpress_amd.trim import write_oriented_fastq
+                cache_clear()
+                t0 = time.perf_counter()
+                eng.load_reads_file(fq)
+                strand, _, _ = eng.orient_profiles()
+                extra["orient_ms"] = round(eng.last_orient_ms, 1)
+                oriented = os.path.join(tmp, "oriented.fq")
+                write_oriented_fastq(fq, oriented, np.where(strand == 0, 1, strand).astype(np.int8))
+                t["orient (plain engine, oriented.fq written)"] = time.perf_counter() - t0
+                extra["oriented_fq_MB"] = round(os.path.getsize(oriented) / 1e6, 1)
+                fq_run = oriented
+            else:
+                fq_run = fq
             eng.close()
+            cache_clear()
             t0 = time.perf_counter()
             se = StreamEngine(0, chunk_mb=args.chunk_mb or None)
+            if args.orient == "profiles":
+                se.plan_orient()
             se.set_rows_mode(args.rows)
             out = os.path.join(tmp, "trimmed.fastq" + {"gz": ".gz", "zst": ".zst", "plain": ""}[args.out_kind])
             if args.stream_write:
                 se.deflate = args.deflate
                 se.plan_output(out, "3_", "4_", gzipped=args.out_kind == "gz", zstd_file=args.out_kind == "zst")
-            se.load_reads_file(fq)
+            se.load_reads_file(fq_run)
             se.derep()
             se.load_profiles(text=its2_profiles(thmm))
             se.search()
@@ -128,13 +172,25 @@ def main():
                 extra["deflate"] = se._out.plan["deflate"]
                 extra["ms_deflate"] = round(se._out.ms_deflate, 1)          # (device: the deflate kernel's time over all units)
                 extra["units_device"], extra["units_host_sliced"] = se._out.units_device, se._out.units_host      # (which path was timed)
-            extra = {**extra, "stream_chunks": se.world, "stream_timeline_s(chunk, text ready, loaded, searched)": se.timeline,
+            if args.orient == "profiles":
+                strand = se.orient_strands()[0]
+                extra["orient_ms"] = round(sum(st.get("orient_ms", 0.0) for _, st in se._engs), 1)      # (the chunks' kernels, summed)
+            if strand is not None:
+                extra["strands(-1, 0, +1)"] = [int((strand == v).sum()) for v in (-1, 0, 1)]
+                extra["strand_is_the_flip"] = round(float(((strand == -1) == flipped)[strand != 0].mean()), 4) if (strand != 0).any() else None
+            # every chunk dereplicates (and, oriented, scans) its own distinct texts: the chunks' counts against the file's
+            extra["chunk_uniques"] = [int(e.n_unique) for e, _ in se._engs]
+            extra = {**extra, "orient": args.orient, "flip": args.flip, "stream_chunks": se.world, "stream_timeline_s(chunk, text ready, loaded, searched)": se.timeline,
                      "chunk_load_s": [st.get("load_s") for _, st in se._engs], "finalize_s": getattr(se, "finalize_s", None)}
             if args.check:                              # the same file through one context: identical coordinates
                 e1 = Engine(0)
                 e1.set_rows_mode(args.rows)
                 e1.load_profiles(text=its2_profiles(thmm))
-                e1.load_reads_file(fq); e1.derep(); e1.search(); e1.finalize()
+                e1.load_reads_file(fq_run)
+                if args.orient == "profiles":           # (the whole file oriented in one piece: the strands and coordinates the chunks must give)
+                    extra["strands_equal_one_context"] = bool(np.array_equal(e1.orient_profiles_apply()[0], strand))
+                    assert extra["strands_equal_one_context"]
+                e1.derep(); e1.search(); e1.finalize()
                 ref = e1.trim_coords("3_", "4_")
                 extra["coordinates_equal_one_context"] = bool(all(np.array_equal(a, b) for a, b in zip((start, stop, tlen, ind), ref)))
                 assert extra["coordinates_equal_one_context"]
@@ -166,7 +222,8 @@ def main():
             extra["representatives_that_waited_for_the_exact_thresholds"] = extra_w["late_uniques"]
             if args.check:                              # the one-go writer on the same coordinates: the same bytes
                 ref_out = out + ".ref"
-                assert write_trimmed_fastq(fq, ref_out, start, stop, gzipped=args.out_kind == "gz", zstd_file=args.out_kind == "zst") == (nw, tot)
+                assert write_trimmed_fastq(fq, ref_out, start, stop, gzipped=args.out_kind == "gz", zstd_file=args.out_kind == "zst",
+                                           strand=strand) == (nw, tot)
                 if args.deflate == "device":                # (other bytes, the same records)
                     extra["output_text_equal_one_go_writer"] = read_text(ref_out) == read_text(out)
                     assert extra["output_text_equal_one_go_writer"]
@@ -175,7 +232,8 @@ def main():
                     assert extra["output_bytes_equal_one_go_writer"]
         else:
             t0 = time.perf_counter()
-            nw, tot = write_trimmed_fastq(fq, out, start, stop, gzipped=args.out_kind == "gz", zstd_file=args.out_kind == "zst")
+            nw, tot = write_trimmed_fastq(fq, out, start, stop, gzipped=args.out_kind == "gz", zstd_file=args.out_kind == "zst",
+                                          strand=strand if args.stream else None)
             t["write"] = time.perf_counter() - t0
         total = sum(t.values())
         # the output holds exactly the kept reads, sliced: check a sample against the coordinates
@@ -189,7 +247,10 @@ def main():
         for k in (() if big else (0, nw // 2, nw - 1)):
             i = int(kept[k])
             assert lines[4 * k] == b"@read%d 1:N:0:1" % i
-            assert lines[4 * k + 1] == bases[offs[i]:offs[i + 1]].tobytes()[start[i]:stop[i]]
+            s = read_in(i)
+            if args.stream and strand is not None and strand[i] < 0:       # (an oriented run slices the read's reverse complement)
+                s = comp[s[::-1]]
+            assert lines[4 * k + 1] == s.tobytes()[start[i]:stop[i]]
         # the output's text: per written record its title line, "\n", bases, "\n+\n", qualities, "\n" = title + 5 + 2 x (bases kept), summed
         # (the titles are the b"@read%d 1:N:0:1" written above: the fixed part plus the digits of the read's number)
         digits = np.searchsorted(10 ** np.arange(1, 12), kept, side="right") + 1

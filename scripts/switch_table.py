@@ -20,7 +20,7 @@ PY_SWITCHES = [
     ("ITSXPRESS_DOMTBL", "mode", "=winners: files as ever, the lazy search behind them; domtbl.txt holds per target and side the row ItsPosition.parse ends up with (same dictionary, same trimmed reads)"),
     ("ITSXPRESS_DOMTBL_ALI", "mode", "=1: domtbl.txt gets hmmsearch's hmm / ali coordinates and acc from the optimal-accuracy stage (itsx_align_domains) instead of placeholders; one context writing files only (ignored with a warning under ITSXPRESS_GPUS > 1, ITSXPRESS_STREAM=1, ITSXPRESS_ARRAYS=1)"),
     ("ITSXPRESS_UC_CIGAR", "mode", "=1: at cluster_id < 1 the H rows of uc.txt get the member's alignment with its centroid in column 8 (itsx_align_clusters) instead of '*'; one context writing files only (ignored with a warning under ITSXPRESS_GPUS > 1 through MultiEngine, ITSXPRESS_STREAM=1, ITSXPRESS_ARRAYS=1)"),
-    ("ITSXPRESS_ORIENT", "mode", "=profiles: orient_reads orients by the profiles of the sample's orient_hmmfile (itsx_orient_profiles: the MSV filter on both strands, undecided reads kept) instead of the k-mer counts against the universal database; one context only (EngineError -5 under ITSXPRESS_GPUS > 1 and ITSXPRESS_STREAM=1)"),
+    ("ITSXPRESS_ORIENT", "mode", "=profiles: orient_reads orients by the profiles of the sample's orient_hmmfile (itsx_orient_profiles: the MSV filter on both strands, undecided reads kept) instead of the k-mer counts against the universal database; ITSXPRESS_STREAM=1 with ITSXPRESS_ARRAYS=1 orients chunk by chunk inside the streamed run (StreamEngine.plan_orient, no oriented.fq); EngineError -5 under ITSXPRESS_GPUS > 1"),
     ("ITSXPRESS_STREAM", "mode", "=1 / 0: streamed file-order chunks on / off (default: by input size, ITSX_STREAM_AUTO_MB)"),
     ("ITSXPRESS_DB_DIR", "mode", "directory with additional ITSx_db HMM files (F.hmm)"),
     ("ITSXPRESS_XDIR", "tuning", "directory of the multi-GPU exchange files (default /dev/shm when it has room, else the temp directory)"),

@@ -17,6 +17,7 @@
 #include <vector>
 #include <zlib.h>
 #include "twriter_dev.h"
+#include "iupac.h"
 
 static int g_fail = 0;
 #define CHECK(c, ...) do { if (!(c)) { g_fail++; fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } } while (0)
@@ -85,13 +86,20 @@ int twdev_unit(itsx_ctx *ctx, const TwUnit &u, bool &fits, std::string &comp, in
     if (u.mode == 1) { w = e != INT32_MIN; py_slice(L, s, e, e == INT32_MAX, lo, sl); }
     else { w = s >= 0 && e >= 0 && s < e; py_slice(L, s, e, false, lo, sl); }
     if (!w) continue;
+    // a record of strand -1 (itsx_twriter_strands): output byte p of the slice is source byte L - 1 - (lo + p), a base complemented
+    const bool flip = u.strand && u.mode == 0 && u.strand[r] < 0;
+    std::string fs, fq;
+    if (flip) {
+      const char *comp = iupac_complement();
+      for (int64_t p = 0; p < sl; p++) { fs += comp[(unsigned char)t[s0 + L - 1 - (lo + p)]]; fq += t[q0 + L - 1 - (lo + p)]; }
+    }
     out.append(t + t0, (size_t)tl); out += '\n';
     if (u.ccs) out += fwd;
-    out.append(t + s0 + lo, (size_t)sl);
+    if (flip) out += fs; else out.append(t + s0 + lo, (size_t)sl);
     if (u.ccs) out += rev;
     out += "\n+\n";
     if (u.ccs) out.append(17, '~');
-    out.append(t + q0 + lo, (size_t)sl);
+    if (flip) out += fq; else out.append(t + q0 + lo, (size_t)sl);
     if (u.ccs) out.append(17, '~');
     out += '\n';
     nw++; tot += sl + (u.ccs ? 34 : 0);
@@ -187,7 +195,7 @@ static void coords(std::mt19937 &rng, const Input &in, int mode, std::vector<int
 
 // the writer fed in pieces (rhythm < 0: all at once), with late records; returns the close code
 static int feed(const std::string &path, const Input &in, const std::vector<int32_t> &a, const std::vector<int32_t> &b, int kind, int ccs, int mode,
-                int rhythm, itsx_ctx *ctx, int64_t *nw, int64_t *tot)
+                int rhythm, itsx_ctx *ctx, int64_t *nw, int64_t *tot, const std::vector<int8_t> *sd = nullptr)
 {
   itsx_twriter *w = nullptr;
   if (itsx_twriter_open(path.c_str(), kind, ccs, &w) != ITSX_OK) return -100;
@@ -195,6 +203,7 @@ static int feed(const std::string &path, const Input &in, const std::vector<int3
   if (ctx) CHECK(itsx_twriter_set_device(w, ctx) == ITSX_OK, "set_device: %s", itsx_trim_last_error());
   const int64_t n = (int64_t)in.len.size();
   if (rhythm < 0) {
+    if (sd) CHECK(itsx_twriter_strands(w, 0, n, sd->data()) == ITSX_OK, "strands: %s", itsx_trim_last_error());
     CHECK(itsx_twriter_text(w, in.text.data(), (int64_t)in.text.size(), 1) == ITSX_OK, "text");
     CHECK(itsx_twriter_coords(w, 0, n, a.data(), b.data(), nullptr) == ITSX_OK, "coords");
   } else {
@@ -206,6 +215,7 @@ static int feed(const std::string &path, const Input &in, const std::vector<int3
     for (int piece = 0; lo < n; piece++) {
       const int64_t hi = std::min<int64_t>(n, lo + 1 + (int64_t)(rng() % (unsigned)(n / 3)));
       const int64_t upto = hi == n ? (int64_t)in.text.size() : (int64_t)in.ends[(size_t)hi - 1];
+      if (sd) CHECK(itsx_twriter_strands(w, lo, hi - lo, sd->data() + lo) == ITSX_OK, "strands: %s", itsx_trim_last_error());
       for (int step = 0; step < 2; step++) {
         if ((step + piece + rhythm) % 2 == 0) CHECK(itsx_twriter_text(w, in.text.data(), upto, hi == n) == ITSX_OK, "text: %s", itsx_trim_last_error());
         else CHECK(itsx_twriter_coords(w, lo, hi - lo, wrong.data() + lo, b.data() + lo, dec.data() + lo) == ITSX_OK, "coords: %s", itsx_trim_last_error());
@@ -244,6 +254,28 @@ int main()
           CHECK(slurp(out, true) == want, "open_end %d mode %d ccs %d rhythm %d: the output differs from the host model", open_end, mode, ccs, rhythm);
         }
       }
+    // strands (mode 0): the host writer's plain file with the strands is the model of the device thread's units; and that model differs
+    // from the file without strands, and equals it where every strand is +1 or 0
+    for (int ccs = 0; ccs < 2; ccs++) {
+      std::vector<int32_t> a, b;
+      coords(rng, in, 0, a, b);
+      std::vector<int8_t> sd(in.len.size()), none(in.len.size());
+      for (size_t i = 0; i < sd.size(); i++) { sd[i] = (int8_t)((int)(rng() % 3) - 1); none[i] = (int8_t)(rng() & 1); }
+      int64_t mw = 0, mt = 0, pw = 0, pt = 0;
+      CHECK(feed(model, in, a, b, 0, ccs, 0, -1, nullptr, &pw, &pt) == ITSX_OK, "model without strands: %s", itsx_trim_last_error());
+      const std::string plain = slurp(model, false);
+      CHECK(feed(model, in, a, b, 0, ccs, 0, 2, nullptr, &mw, &mt, &none) == ITSX_OK, "model, no strand -1: %s", itsx_trim_last_error());
+      CHECK(slurp(model, false) == plain, "strands of +1 and 0 change the file");
+      CHECK(feed(model, in, a, b, 0, ccs, 0, -1, nullptr, &mw, &mt, &sd) == ITSX_OK, "model with strands: %s", itsx_trim_last_error());
+      const std::string want = slurp(model, false);
+      CHECK(mw == pw && mt == pt && want.size() == plain.size() && want != plain, "strands change the bytes, not the counts");
+      for (int rhythm = -1; rhythm < 3; rhythm++) {
+        int64_t nw = 0, tot = 0;
+        CHECK(feed(out, in, a, b, 1, ccs, 0, rhythm, &ctx, &nw, &tot, &sd) == ITSX_OK, "device writer with strands: %s", itsx_trim_last_error());
+        CHECK(nw == mw && tot == mt, "counts %lld %lld, model %lld %lld", (long long)nw, (long long)tot, (long long)mw, (long long)mt);
+        CHECK(slurp(out, true) == want, "open_end %d ccs %d rhythm %d with strands: the output differs from the host model", open_end, ccs, rhythm);
+      }
+    }
     // malformed text: reported as the host writer reports it
     Input bad = in;
     bad.text += "@broken\nACGT\n+\nII\n"; bad.ends.push_back(bad.text.size()); bad.len.push_back(4);
@@ -264,6 +296,16 @@ int main()
     CHECK(itsx_twriter_text(w, nullptr, 0, 1) == ITSX_E_ARG, "the text does not move");
     (void)itsx_twriter_close(w, nullptr, nullptr);
     CHECK(itsx_twriter_open(out.c_str(), 3, 0, &w) == ITSX_E_ARG, "compression 3 is refused at open");
+    const int8_t one[2] = {-1, 1}; const int32_t z[2] = {0, 0}, e[2] = {2, 2};
+    CHECK(itsx_twriter_open(model.c_str(), 0, 0, &w) == ITSX_OK, "open");
+    CHECK(itsx_twriter_coords(w, 0, 1, z, e, nullptr) == ITSX_OK && itsx_twriter_strands(w, 0, 2, one) == ITSX_E_ARG, "strands after coordinates");
+    CHECK(itsx_twriter_strands(w, 2, 1, one) == ITSX_E_ARG && itsx_twriter_strands(w, 1, 1, one) == ITSX_OK, "strands in record order");
+    CHECK(itsx_twriter_set_mode(w, 1) == ITSX_E_ARG, "a writer with strands takes no mode 1");
+    CHECK(itsx_twriter_coords(w, 1, 1, z, e, nullptr) == ITSX_OK && itsx_twriter_text(w, "@a\nAC\n+\nIJ\n@b\nAC\n+\nIJ\n", 22, 1) == ITSX_OK, "text");
+    CHECK(itsx_twriter_close(w, nullptr, nullptr) == ITSX_OK && slurp(model, false) == "@a\nAC\n+\nIJ\n@b\nGT\n+\nJI\n", "a late first row");
+    CHECK(itsx_twriter_open(model.c_str(), 0, 0, &w) == ITSX_OK && itsx_twriter_set_mode(w, 1) == ITSX_OK, "open");
+    CHECK(itsx_twriter_strands(w, 0, 2, one) == ITSX_E_ARG, "a mode-1 writer takes no strands");
+    CHECK(itsx_twriter_text(w, nullptr, 0, 1) == ITSX_OK && itsx_twriter_close(w, nullptr, nullptr) == ITSX_OK, "close");
   }
   remove(model.c_str()); remove(out.c_str());
   printf("%s: %ld units, %ld through the index, %ld host-sliced texts\n", g_fail ? "FAILED" : "ok", ctx.units, ctx.fitted, ctx.texts);
