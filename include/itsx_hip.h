@@ -430,6 +430,30 @@ int itsx_merge_pairs_load_files(itsx_ctx *ctx, const char *const *r1_paths, cons
                                 int32_t n_samples, int maxdiffs, double maxee, int allow_stagger,
                                 int64_t *n_pairs_per_sample, int64_t *n_merged_per_sample);
 int itsx_merge_tables(double *q2p, double *match, double *mism, uint8_t *qsame, uint8_t *qdiff);
+/* ---- joining the pairs that do not overlap (opt-in per context; off by default, and off runs the merge kernel built without it).
+ * ITS1 / ITS2 span about 100 to over 600 bases, so a 2x250 or 2x300 run cannot merge the long ones, and a pair the merge rejects is
+ * gone from seq.fq, the read set and both trimmed outputs.  While on, a pair rejected with reason 1 (no shared 5-mers), 3 (score < 16)
+ * or 5 (overlap < 10) is JOINED instead: its read is R1 (upper case), "NNNNNNNN", then the reverse complement of R2 as the merge reads
+ * it (upper case; a symbol outside ACGTU complements to N, U to A); its qualities are R1's, "IIIIIIII", then R2's reversed -- vsearch
+ * --fastq_join's padding as its manual gives it (PARITY UNPINNED, like the merge's: no vsearch build was at hand; the join is not part
+ * of the reference, which drops these pairs).  Reasons 2, 4, 6, 7 and 8 are not joined; a joined read gets no expected-error filter
+ * (--fastq_join has none); reason[i] keeps its code; merged pairs are bit for bit what they are with the setting off.
+ * Honoured by itsx_merge_pairs_files (seq.fq holds merged and joined records in pair order), itsx_merge_pairs_load, _load_text and
+ * _load_files, on the host and the device parse path: the read set holds merged and joined reads in pair order, labels and
+ * itsx_merge_pair_index cover both kinds, itsx_keep_records / itsx_keep_pair_records work unchanged.  *n_merged keeps counting merged
+ * pairs only.  A joined read is a read like any other: with tlen = L1 + 8 + L2, start inside R1 and stop inside the R2 part, the paired
+ * writers' slices R1[start:stop] and R2[tlen - stop : tlen - start] are R1[start:] and R2[tlen - stop:], each mate cut at its own anchor.
+ * itsx_merge_buffers ignores the setting.  Left out: --join_padgap / --join_padgapq, an expected-error or length filter for joined reads.
+ * itsx_merge_join_info: per pair of the context's last merge call (after a merge-and-load: the pairs itsx_merge_pair_index speaks of;
+ * after itsx_merge_pairs_files: that call's pairs) joined[i] = 1 where its read is a joined one, *n_joined their number; either may be
+ * NULL; all 0 with the setting off.
+ * itsx_merge_buffers_join: itsx_merge_buffers with the join always on.  Output planes hold foff[n] + roff[n] + 8 n bytes, pair i's read
+ * is at foff[i] + roff[i] + 8 i, out_len[i] = fl + 8 + rl and joined[i] = 1 for a joined pair. */
+int itsx_set_merge_join(itsx_ctx *ctx, int on);
+int itsx_merge_join_info(const itsx_ctx *ctx, int8_t *joined, int64_t n_pairs, int64_t *n_joined);
+int itsx_merge_buffers_join(itsx_ctx *ctx, const char *fseq, const char *fqual, const int64_t *foff, const char *rseq, const char *rqual,
+                            const int64_t *roff, int64_t n, int maxdiffs, double maxee, int allow_stagger,
+                            char *out_seq, char *out_qual, int32_t *out_len, int32_t *reason, double *score, int32_t *shift, int8_t *joined);
 
 /* ---- a read set that keeps its records (opt-in; off by default, and off costs nothing).  While on, every read set made by
  * itsx_load_reads_files (FASTQ only: a FASTA file is ITSX_E_FORMAT, naming it), itsx_merge_pairs_load_files / itsx_merge_pairs_load and

@@ -415,13 +415,19 @@ class SeqSamplePairedNotInterleaved(SeqSample):
     def _merge_reads(self, threads: Union[int, str], stagger: bool = False) -> None:
         """Replaces `vsearch --fastq_mergepairs R1 --reverse R2 --fastqout seq.fq --fastq_maxdiffs 40 --fastq_maxee 2
         --fastq_qmax 93 [--fastq_allowmergestagger]` (SeqSample.py:266-365; constants definitions.py:79-82) with the
-        engine's merge kernel; writes tempdir/seq.fq and points seq_file at it, as the reference does."""
+        engine's merge kernel; writes tempdir/seq.fq and points seq_file at it, as the reference does.
+        ITSXPRESS_JOIN_UNMERGED=1 or `sobj.join_unmerged = True` (not the reference's: it drops such pairs): a pair whose mates do not
+        overlap is kept as R1 + NNNNNNNN + revcomp(R2) (Engine.merge_join), so that the paired output (--outfile2) holds each mate cut
+        at its own anchor.  The single merged output (--fastq2 without --outfile2) then contains joined reads with the N gap."""
         try:
             if self.r1 is None or self.fastq2 is None:
                 raise ValueError("Both r1 and fastq2 paths must be defined to merge reads.")
             os.makedirs(self.tempdir, exist_ok=True)
             seq_file = os.path.join(self.tempdir, "seq.fq")
             eng = self.engine
+            join = bool(getattr(self, "join_unmerged", False)) or os.environ.get("ITSXPRESS_JOIN_UNMERGED", "") == "1"
+            if join:
+                eng.merge_join = True                        # (a streaming or multi-GPU engine hands it to every context it creates)
             if self._is_fast() and not hasattr(eng, "merge_pairs_load") and hasattr(eng, "_plain"):
                 # arrays mode on a streaming engine: the merged reads live in ONE context (nothing of a merged sample is inflated
                 # while it is scored: the merge needs both files whole) -- that context is the sample's engine from here on
@@ -437,7 +443,7 @@ class SeqSamplePairedNotInterleaved(SeqSample):
                 n, m = eng.merge_pairs_files(self.r1, self.fastq2, seq_file, maxdiffs=maxmismatches, maxee=2.0,
                                              allow_stagger=bool(stagger))
             if n >= 0:
-                logging.info("%d pairs, %d merged", n, m)
+                logging.info("%d pairs, %d merged, %d joined", n, m, int(getattr(eng, "n_joined", 0)))
             else:
                 logging.info("itsx_hip: the pairs are merged chunk by chunk while the files are inflated (streamed)")
             self.seq_file = seq_file

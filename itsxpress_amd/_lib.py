@@ -111,7 +111,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_align_clusters", "itsx_get_cluster_cigars",
            "itsx_topup_counters",
            "itsx_orient_profiles", "itsx_orient_profiles_apply",
-           "itsx_twriter_strands", "itsx_write_trimmed_fastq_strands"]
+           "itsx_twriter_strands", "itsx_write_trimmed_fastq_strands",
+           "itsx_set_merge_join", "itsx_merge_join_info", "itsx_merge_buffers_join"]
 
 
 def lib():
@@ -214,6 +215,9 @@ def lib():
         "itsx_align_clusters": (i32, [vp, vp, vp]),
         "itsx_get_cluster_cigars": (i32, [vp, vp, vp]),
         "itsx_merge_buffers": (i32, [vp, cp, cp, vp, cp, cp, vp, i64, i32, f64, i32, vp, vp, vp, vp, vp, vp]),
+        "itsx_merge_buffers_join": (i32, [vp, cp, cp, vp, cp, cp, vp, i64, i32, f64, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "itsx_set_merge_join": (i32, [vp, i32]),
+        "itsx_merge_join_info": (i32, [vp, vp, i64, vp]),
         "itsx_merge_pairs_files": (i32, [vp, cp, cp, cp, i32, f64, i32, vp, vp]),
         "itsx_merge_pairs_load": (i32, [vp, cp, cp, i32, f64, i32, vp, vp]),
         "itsx_merge_tables": (i32, [vp, vp, vp, vp, vp]),

@@ -63,6 +63,7 @@ class SampleBatch:
         self.counts: Optional[np.ndarray] = None       # reads per sample
         self.first: Optional[np.ndarray] = None        # index of each sample's first read in the batch
         self.n_pairs: Optional[np.ndarray] = None      # after merge_reads: read pairs per sample
+        self.n_joined: Optional[np.ndarray] = None     # after merge_reads: of them joined, not merged, per sample (merge_join; else zeros)
         self._resident = None                          # the seq_files whose reads merge_reads / orient_reads left resident in the engine,
         self._resident_read_set = None                 # and the engine's read-set number at that moment (the engine may be shared)
         self._seq_written = False                      # whether they wrote those files
@@ -216,10 +217,18 @@ class SampleBatch:
             for s, f in zip(self.samples, seq_files):
                 s.seq_file = f
             self.n_pairs = np.asarray(n, np.int64)
+            self.n_joined = np.zeros(len(self.samples), np.int64)      # merge_join: the joined pairs per sample, reads of the batch like the merged
+            if self.merge_join:
+                joined = eng.merge_join_info()[0].astype(np.int64)
+                ends = np.cumsum(self.n_pairs)
+                csum = np.concatenate(([0], np.cumsum(joined)))
+                self.n_joined = csum[ends] - csum[ends - self.n_pairs]
+            m = np.asarray(m, np.int64) + self.n_joined
             self._set_counts(m)
             self._left_resident(seq_files, write, "merge_reads")
             self._pair_records_read_set = self._resident_read_set if self.keep_pair_records else None
-            logging.info("itsx_hip batch merge: %d samples, %d pairs, %d merged", len(self.samples), int(self.n_pairs.sum()), int(self.counts.sum()))
+            logging.info("itsx_hip batch merge: %d samples, %d pairs, %d merged, %d joined", len(self.samples), int(self.n_pairs.sum()),
+                         int(self.counts.sum() - self.n_joined.sum()), int(self.n_joined.sum()))
         except EngineError as e:
             logging.exception("Could not perform read merging with the HIP engine: %s", e)
             raise e
@@ -379,6 +388,16 @@ class SampleBatch:
     @parse.setter
     def parse(self, where: str):
         self.engine.parse = where
+
+    # Whether merge_reads keeps the pairs whose mates do not overlap as joined reads: the engine's own setting (Engine.merge_join),
+    # under the batch's name.  `counts` then holds merged and joined reads, `n_joined` the joined ones per sample.
+    @property
+    def merge_join(self) -> bool:
+        return bool(getattr(self.engine, "merge_join", False))
+
+    @merge_join.setter
+    def merge_join(self, on: bool):
+        self.engine.merge_join = on
 
     def _device_deflate_falls_back(self, who, gzipped, zstd_file):
         if self.deflate == "device":

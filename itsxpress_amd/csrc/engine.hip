@@ -502,6 +502,9 @@ struct itsx_ctx {
   std::vector<unsigned long long> h_zneed;
   bool prev_lazy = false; int prev_P = 0; int64_t prev_U = 0, prev_Uc = 0;      // the last search's chunking (itsx_search)
   std::vector<int32_t> h_merge_index;      // per pair of the last merge-and-load: its merged read, -1 = not merged
+  bool merge_join = false;                 // itsx_set_merge_join: pairs rejected for want of an overlap (reason 1, 3, 5) are joined and kept
+  std::vector<int8_t> h_merge_join;        // per pair of the last merge call (itsx_merge_pairs_files included): 1 = its read is a joined one (all 0 with the setting off)
+  int64_t pack_exc_hint = 0;               // non-ACGT symbols the next pack_and_upload is known to meet (a joined read's eight N); taken once
   // ---- the records of the read set (itsx_keep_records; consumer: itsx_write_trimmed_samples): what a FASTQ record needs beyond the
   // packed words -- ASCII bases as in the input, qualities, whole title lines -- one owned copy, dropped with the read set
   bool keep_records = false;
@@ -1026,7 +1029,8 @@ static int pack_and_upload(itsx_ctx *ctx, const char *view = nullptr, const uint
   HIPCHK(hipMemcpyAsync(d_lut.p, g_code, 256, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(d_excnt.p, 0, ((size_t)n + 2) * 4, st));
   // the exception list is sized by a guess; a read set with more non-ACGT symbols than that repeats the exception pass
-  int64_t ecap = std::max<int64_t>((int64_t)ctx->d_exc.cap, nb / 256 + 4096);
+  int64_t ecap = std::max<int64_t>((int64_t)ctx->d_exc.cap, nb / 256 + 4096 + ctx->pack_exc_hint);
+  ctx->pack_exc_hint = 0;
   if (const char *e = sw_get("ITSX_PACK_ECAP")) ecap = std::max<int64_t>(1, atoll(e));
   HIPCHK(ctx->d_exc.alloc((size_t)ecap));
   int copy_threads = std::max(1, std::min(8, itsx_io::io_threads()));
@@ -1414,6 +1418,13 @@ int itsx_keep_pair_records(itsx_ctx *ctx, int on)
 {
   CTXCHK(ctx);
   ctx->keep_pair_records = on != 0;
+  return ITSX_OK;
+}
+
+int itsx_set_merge_join(itsx_ctx *ctx, int on)
+{
+  CTXCHK(ctx);
+  ctx->merge_join = on != 0;
   return ITSX_OK;
 }
 
@@ -5303,14 +5314,19 @@ struct MergeKeep {
 // The device step of a merge: bases, qualities and offsets of both sides lie in device memory (fb / rb bytes a side, max_total = the
 // longest pair, at least 2); the kernel runs and the results are copied back.  keep (may be null): the merged bases stay in device
 // memory (pair i's at foff[i] + roff[i]) with the pairs' lengths and reasons, taken over by *keep (the inputs stay the caller's); the
-// bases are copied back only if out_seq is given -- the merge-and-load calls pack them where they are
+// bases are copied back only if out_seq is given -- the merge-and-load calls pack them where they are.  join: the kernel that joins
+// runs (k_merge.hip: JOIN); the output planes are fb + rb + 8 n bytes, pair i's slot starts at foff[i] + roff[i] + 8 i, and joined
+// (may be null) takes the pairs' marks.
 static int merge_device(itsx_ctx *ctx, const uint8_t *d_fs, const uint8_t *d_fq, const int64_t *d_fo, const uint8_t *d_rs, const uint8_t *d_rq, const int64_t *d_ro,
                         int64_t n, int64_t fb, int64_t rb, int64_t max_total, int maxdiffs, double maxee, int allow_stagger,
-                        char *out_seq, char *out_qual, int32_t *out_len, int32_t *reason, double *score, int32_t *shift, MergeKeep *keep)
+                        char *out_seq, char *out_qual, int32_t *out_len, int32_t *reason, double *score, int32_t *shift, MergeKeep *keep,
+                        bool join = false, int8_t *joined = nullptr)
 {
   const MergeTables &t = merge_tables();
-  DBuf<uint8_t> d_os, d_oq, d_qs, d_qd; DBuf<int32_t> d_len, d_reason, d_shift; DBuf<double> d_q2p, d_m, d_x, d_score;
-  HIPCHK(d_os.alloc((size_t)(fb + rb) + 1)); HIPCHK(d_oq.alloc((size_t)(fb + rb) + 1));
+  DBuf<uint8_t> d_os, d_oq, d_qs, d_qd; DBuf<int32_t> d_len, d_reason, d_shift; DBuf<double> d_q2p, d_m, d_x, d_score; DBuf<int8_t> d_joined;
+  const int64_t ob = fb + rb + (join ? 8 * n : 0);       // the bytes of an output plane
+  HIPCHK(d_os.alloc((size_t)ob + 1)); HIPCHK(d_oq.alloc((size_t)ob + 1));
+  if (join) HIPCHK(d_joined.alloc((size_t)n));
   HIPCHK(d_len.alloc((size_t)n)); HIPCHK(d_reason.alloc((size_t)n)); HIPCHK(d_shift.alloc((size_t)n)); HIPCHK(d_score.alloc((size_t)n));
   HIPCHK(upload(d_q2p, t.q2p, ctx->st)); HIPCHK(upload(d_m, t.match, ctx->st)); HIPCHK(upload(d_x, t.mism, ctx->st));
   HIPCHK(upload(d_qs, t.qsame, ctx->st)); HIPCHK(upload(d_qd, t.qdiff, ctx->st));
@@ -5319,12 +5335,14 @@ static int merge_device(itsx_ctx *ctx, const uint8_t *d_fs, const uint8_t *d_fq,
   a.maxdiffs = maxdiffs; a.allow_stagger = allow_stagger ? 1 : 0; a.maxee = maxee;
   a.q2p = d_q2p.p; a.match = d_m.p; a.mism = d_x.p; a.qsame = d_qs.p; a.qdiff = d_qd.p;
   a.out_seq = d_os.p; a.out_qual = d_oq.p; a.out_len = d_len.p; a.reason = d_reason.p; a.shift = d_shift.p; a.score = d_score.p;
+  a.join = join ? 1 : 0; a.joined = d_joined.p;
   StageTimer tm(ctx->st);
   launch_merge(a, ctx->st);
   ctx->stats.ms_merge = tm.stop();
   HIPCHK(hipGetLastError());
-  if (out_seq) HIPCHK(hipMemcpyAsync(out_seq, d_os.p, (size_t)(fb + rb), hipMemcpyDeviceToHost, ctx->st));
-  if (out_qual) HIPCHK(hipMemcpyAsync(out_qual, d_oq.p, (size_t)(fb + rb), hipMemcpyDeviceToHost, ctx->st));
+  if (out_seq) HIPCHK(hipMemcpyAsync(out_seq, d_os.p, (size_t)ob, hipMemcpyDeviceToHost, ctx->st));
+  if (out_qual) HIPCHK(hipMemcpyAsync(out_qual, d_oq.p, (size_t)ob, hipMemcpyDeviceToHost, ctx->st));
+  if (join && joined) HIPCHK(hipMemcpyAsync(joined, d_joined.p, (size_t)n, hipMemcpyDeviceToHost, ctx->st));
   HIPCHK(hipMemcpyAsync(out_len, d_len.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st)); HIPCHK(hipMemcpyAsync(reason, d_reason.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
   if (score) HIPCHK(hipMemcpyAsync(score, d_score.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->st));
   if (shift) HIPCHK(hipMemcpyAsync(shift, d_shift.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->st));
@@ -5336,7 +5354,8 @@ static int merge_device(itsx_ctx *ctx, const uint8_t *d_fs, const uint8_t *d_fq,
 // them.  keep (may be null) also takes over the pairs' offsets and, where the pair records are kept, the uploaded planes.
 static int merge_core(itsx_ctx *ctx, const char *fseq, const char *fqual, const int64_t *foff, const char *rseq, const char *rqual,
                       const int64_t *roff, int64_t n, int maxdiffs, double maxee, int allow_stagger,
-                      char *out_seq, char *out_qual, int32_t *out_len, int32_t *reason, double *score, int32_t *shift, MergeKeep *keep)
+                      char *out_seq, char *out_qual, int32_t *out_len, int32_t *reason, double *score, int32_t *shift, MergeKeep *keep,
+                      bool join = false, int8_t *joined = nullptr)
 {
   CTXCHK(ctx && foff && roff && n >= 0 && out_len && reason && (n == 0 || (fseq && fqual && rseq && rqual && (keep || (out_seq && out_qual)))));
   HIPCHK(hipSetDevice(ctx->device));
@@ -5371,7 +5390,7 @@ static int merge_core(itsx_ctx *ctx, const char *fseq, const char *fqual, const 
   HIPCHK(hipMemcpyAsync(d_rs.p, rseq, (size_t)rb, hipMemcpyHostToDevice, ctx->st)); HIPCHK(hipMemcpyAsync(d_rq.p, rqual, (size_t)rb, hipMemcpyHostToDevice, ctx->st));
   HIPCHK(hipMemcpyAsync(d_fo.p, foff, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->st)); HIPCHK(hipMemcpyAsync(d_ro.p, roff, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->st));
   const int rc = merge_device(ctx, d_fs.p, d_fq.p, d_fo.p, d_rs.p, d_rq.p, d_ro.p, n, fb, rb, max_total, maxdiffs, maxee, allow_stagger,
-                              out_seq, out_qual, out_len, reason, score, shift, keep);
+                              out_seq, out_qual, out_len, reason, score, shift, keep, join, joined);
   if (rc != ITSX_OK) return rc;
   if (keep) { dbuf_swap(keep->fo, d_fo); dbuf_swap(keep->ro, d_ro); }
   if (keep && keep->want_pairs) { dbuf_swap(keep->fs, d_fs); dbuf_swap(keep->fq, d_fq); dbuf_swap(keep->rs, d_rs); dbuf_swap(keep->rq, d_rq); }
@@ -5383,6 +5402,16 @@ int itsx_merge_buffers(itsx_ctx *ctx, const char *fseq, const char *fqual, const
 {
   CTXCHK(ctx && (n == 0 || (out_seq && out_qual)));
   return merge_core(ctx, fseq, fqual, foff, rseq, rqual, roff, n, maxdiffs, maxee, allow_stagger, out_seq, out_qual, out_len, reason, score, shift, nullptr);
+}
+
+// the same with the join always on (the context's setting is not consulted): output planes of foff[n] + roff[n] + 8 n bytes, pair i's
+// slot at foff[i] + roff[i] + 8 i, joined[i] = 1 where the read there is R1 + NNNNNNNN + revcomp(R2)
+int itsx_merge_buffers_join(itsx_ctx *ctx, const char *fseq, const char *fqual, const int64_t *foff, const char *rseq, const char *rqual,
+                            const int64_t *roff, int64_t n, int maxdiffs, double maxee, int allow_stagger,
+                            char *out_seq, char *out_qual, int32_t *out_len, int32_t *reason, double *score, int32_t *shift, int8_t *joined)
+{
+  CTXCHK(ctx && (n == 0 || (out_seq && out_qual && joined)));
+  return merge_core(ctx, fseq, fqual, foff, rseq, rqual, roff, n, maxdiffs, maxee, allow_stagger, out_seq, out_qual, out_len, reason, score, shift, nullptr, true, joined);
 }
 
 // FASTQ in, FASTQ out: R1/R2 (plain or gzip) -> merged reads, labels = forward read's identifier up to the first blank
@@ -5412,11 +5441,14 @@ int itsx_merge_pairs_files(itsx_ctx *ctx, const char *r1_path, const char *r2_pa
   if (rc2 != ITSX_OK) { ctx->set_error(rerr2); return rc2; }
   if (f.ids.size() != r.ids.size()) SET_ERR(ctx, ITSX_E_FORMAT, "R1 and R2 hold different numbers of records");
   const int64_t n = (int64_t)f.ids.size();
-  std::string oseq((size_t)(f.seq.size() + r.seq.size()) + 1, '\0'), oqual = oseq;
+  const bool join = ctx->merge_join;                     // (itsx_set_merge_join: joined records go to seq.fq in pair order, 8 bytes more per slot)
+  std::string oseq((size_t)(f.seq.size() + r.seq.size()) + (join ? (size_t)n * 8 : 0) + 1, '\0'), oqual = oseq;
   std::vector<int32_t> olen((size_t)n + 1), reason((size_t)n + 1);
-  rc = itsx_merge_buffers(ctx, f.seq.data(), f.qual.data(), f.off.data(), r.seq.data(), r.qual.data(), r.off.data(), n, maxdiffs, maxee, allow_stagger,
-                          &oseq[0], &oqual[0], olen.data(), reason.data(), nullptr, nullptr);
+  rc = merge_core(ctx, f.seq.data(), f.qual.data(), f.off.data(), r.seq.data(), r.qual.data(), r.off.data(), n, maxdiffs, maxee, allow_stagger,
+                  &oseq[0], &oqual[0], olen.data(), reason.data(), nullptr, nullptr, nullptr, join, nullptr);
   if (rc != ITSX_OK) return rc;
+  ctx->h_merge_join.assign((size_t)n, 0);                // itsx_merge_join_info: the marks of this call's pairs
+  if (join) for (int64_t i = 0; i < n; i++) ctx->h_merge_join[(size_t)i] = olen[i] > 0 && reason[i] != 0;
   const auto tm2 = std::chrono::steady_clock::now();
   // seq.fq is read back by the loader and by the paired trimmer: written through the block writer, which also leaves
   // its text in the reader's cache
@@ -5425,13 +5457,13 @@ int itsx_merge_pairs_files(itsx_ctx *ctx, const char *r1_path, const char *r2_pa
   if (!bw.open(out_path, itsx_io::PLAIN, werr, true)) SET_ERR(ctx, ITSX_E_IO, werr);
   int64_t merged = 0;
   for (int64_t i = 0; i < n; i++) {
-    if (reason[i] != 0) continue;
-    const size_t o = (size_t)(f.off[i] + r.off[i]);
+    if (join ? olen[i] <= 0 : reason[i] != 0) continue;
+    const size_t o = (size_t)(f.off[i] + r.off[i]) + (join ? (size_t)i * 8 : 0);
     buf += '@'; buf.append(f.ids.ptr((size_t)i), f.ids.len((size_t)i)); buf += '\n';
     buf.append(oseq.data() + o, (size_t)olen[i]); buf += "\n+\n";
     buf.append(oqual.data() + o, (size_t)olen[i]); buf += '\n';
     if (buf.size() >= (1u << 20)) { bw.put(buf); buf.clear(); }
-    merged++;
+    if (reason[i] == 0) merged++;                        // (joined records are not counted here: itsx_merge_join_info has them)
   }
   bw.put(buf);
   if (!bw.close(werr)) SET_ERR(ctx, ITSX_E_IO, werr);
@@ -5489,15 +5521,19 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
   if (seq_out_paths) for (int32_t s = 0; s < S; s++) want_text = want_text || seq_out_paths[s] != nullptr;
   std::vector<int32_t> olen((size_t)n + 1), reason((size_t)n + 1);
   std::string oseq, oqual;
-  if (want_text) { oseq.assign((dev ? (size_t)(f.off[(size_t)n] + r.off[(size_t)n]) : (size_t)(f.seq.size() + r.seq.size())) + 1, '\0'); oqual = oseq; }
+  // itsx_set_merge_join: the reads are the merged AND the joined pairs (out_len > 0), and a pair's slot lies 8 bytes further per pair before it
+  const bool join = ctx->merge_join;
+  const auto kept = [&](int64_t p) { return join ? olen[(size_t)p] > 0 : reason[(size_t)p] == 0; };
+  const auto slot = [&](int64_t p) { return (size_t)(f.off[(size_t)p] + r.off[(size_t)p]) + (join ? (size_t)p * 8 : 0); };
+  if (want_text) { oseq.assign((dev ? (size_t)(f.off[(size_t)n] + r.off[(size_t)n]) : (size_t)(f.seq.size() + r.seq.size())) + (join ? (size_t)n * 8 : 0) + 1, '\0'); oqual = oseq; }
   MergeKeep k;
   k.want_oq = records; k.want_pairs = pair_records;
   int rc = ITSX_OK;
   if (!dev) rc = merge_core(ctx, f.seq.data(), f.qual.data(), f.off.data(), r.seq.data(), r.qual.data(), r.off.data(), n, maxdiffs, maxee, allow_stagger,
-                            want_text ? &oseq[0] : nullptr, want_text ? &oqual[0] : nullptr, olen.data(), reason.data(), nullptr, nullptr, &k);
+                            want_text ? &oseq[0] : nullptr, want_text ? &oqual[0] : nullptr, olen.data(), reason.data(), nullptr, nullptr, &k, join, nullptr);
   else if (n > 0) {
     rc = merge_device(ctx, dev->fs->p, dev->fq->p, dev->fo->p, dev->rs->p, dev->rq->p, dev->ro->p, n, f.off[(size_t)n], r.off[(size_t)n], std::max<int64_t>(dev->max_total, 2),
-                      maxdiffs, maxee, allow_stagger, want_text ? &oseq[0] : nullptr, want_text ? &oqual[0] : nullptr, olen.data(), reason.data(), nullptr, nullptr, &k);
+                      maxdiffs, maxee, allow_stagger, want_text ? &oseq[0] : nullptr, want_text ? &oqual[0] : nullptr, olen.data(), reason.data(), nullptr, nullptr, &k, join, nullptr);
     if (rc == ITSX_OK) {                                 // as merge_core leaves *keep
       dbuf_swap(k.fo, *dev->fo); dbuf_swap(k.ro, *dev->ro);
       if (pair_records) { dbuf_swap(k.fs, *dev->fs); dbuf_swap(k.fq, *dev->fq); dbuf_swap(k.rs, *dev->rs); dbuf_swap(k.rq, *dev->rq); }
@@ -5513,7 +5549,7 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
     const int64_t nb = merge_compact_blocks(n);
     HIPCHK(d_src.alloc((size_t)n + 1)); HIPCHK(d_dst.alloc((size_t)n + 1)); HIPCHK(d_pidx.alloc((size_t)n)); HIPCHK(d_blk.alloc((size_t)nb * 2)); HIPCHK(d_tot.alloc(2));
     MergeCompactArgs a{};
-    a.reason = k.reason.p; a.out_len = k.len.p; a.foff = k.fo.p; a.roff = k.ro.p; a.n = n; a.n_samples = S;
+    a.reason = k.reason.p; a.out_len = k.len.p; a.foff = k.fo.p; a.roff = k.ro.p; a.n = n; a.n_samples = S; a.join = join ? 1 : 0;
     a.blk_cnt = d_blk.p; a.blk_len = d_blk.p + nb; a.pair_index = d_pidx.p; a.srcoff = d_src.p; a.dstoff = d_dst.p;
     if (S > 1) {
       HIPCHK(upload(d_pstart, pstart, st)); HIPCHK(d_scnt.alloc((size_t)S)); HIPCHK(ctx->d_sample.alloc((size_t)n + 1));
@@ -5531,6 +5567,11 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
   if (S == 1) scnt[0] = m;
   ctx->h_off.assign((size_t)m + 1, 0);
   ctx->h_merge_index.assign((size_t)n, -1);              // per pair: its merged read (itsx_merge_pair_index)
+  ctx->h_merge_join.assign((size_t)n, 0);                // per pair: its read is a joined one (itsx_merge_join_info)
+  std::vector<int64_t> sjoin((size_t)S, 0);              // joined reads per sample
+  if (join) for (int32_t s = 0; s < S; s++)
+    for (int64_t p = pstart[(size_t)s]; p < pstart[(size_t)s + 1]; p++)
+      if (olen[(size_t)p] > 0 && reason[(size_t)p] != 0) { ctx->h_merge_join[(size_t)p] = 1; sjoin[(size_t)s]++; }
   HIPCHK(d_cmp.alloc((size_t)tot[1] + 64));
   if (m > 0) {
     hipLaunchKernelGGL(k_gather_reads, dim3((unsigned)std::min<int64_t>((m + 3) / 4, 65535)), dim3(256), 0, st, k.os.p, d_src.p, d_dst.p, m, d_cmp.p);
@@ -5548,7 +5589,7 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
     const NameList &nl = *ids[(size_t)s];
     const int64_t p0 = pstart[(size_t)s], cnt = pstart[(size_t)s + 1] - p0;
     for (int64_t i = 0; i < cnt; i++)
-      if (reason[(size_t)(p0 + i)] == 0) ctx->h_names.emplace_back(nl.ptr((size_t)i), nl.ptr((size_t)i) + nl.len((size_t)i));
+      if (kept(p0 + i)) ctx->h_names.emplace_back(nl.ptr((size_t)i), nl.ptr((size_t)i) + nl.len((size_t)i));
   }
   if (m > 0) HIPCHK(hipMemcpyAsync(ctx->h_off.data(), d_dst.p, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, st));
   if (n > 0) HIPCHK(hipMemcpyAsync(ctx->h_merge_index.data(), d_pidx.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
@@ -5561,6 +5602,9 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
   // rep.fa and the seeds' sequences fetch the text from dev_bases later (host_bases): the context owns it from here on
   ctx->d_merged_text.release();
   dbuf_swap(ctx->d_merged_text, d_cmp);
+  // every joined read brings eight N: the exception list is sized for them at once (its guess is one symbol in 256 bases, and a read set
+  // past it packs its exceptions twice)
+  for (int32_t s = 0; s < S; s++) ctx->pack_exc_hint += 8 * sjoin[(size_t)s];
   rc = pack_and_upload(ctx, nullptr, m > 0 ? ctx->d_merged_text.p : &none);
   if (rc != ITSX_OK) return rc;
   if (records) {                                         // bases = the gathered text, titles = '@' + label (what itsx_merge_pairs_files writes)
@@ -5601,7 +5645,7 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
           named.clear(); named.reserve((size_t)scnt[(size_t)s] * 2);
           int64_t j = rfirst[(size_t)s];
           for (int64_t i = 0; i < cnt; i++)
-            if (reason[(size_t)(p0 + i)] == 0) named.emplace(std::string_view(nl.ptr((size_t)i), nl.len((size_t)i)), (int32_t)j++);      // (emplace keeps the first)
+            if (kept(p0 + i)) named.emplace(std::string_view(nl.ptr((size_t)i), nl.len((size_t)i)), (int32_t)j++);      // (emplace keeps the first)
           for (int64_t i = 0; i < cnt; i++) {
             const auto it = named.find(std::string_view(nl.ptr((size_t)i), nl.len((size_t)i)));
             if (it != named.end()) pread[(size_t)(p0 + i)] = it->second;
@@ -5655,8 +5699,8 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
         std::string werr, buf;
         if (!bw.open(seq_out_paths[s], itsx_io::PLAIN, werr, true)) { werrs[(size_t)t] = werr; continue; }
         for (int64_t p = pstart[(size_t)s], i = 0; p < pstart[(size_t)s + 1]; p++, i++) {
-          if (reason[(size_t)p] != 0) continue;
-          const size_t o = (size_t)(f.off[(size_t)p] + r.off[(size_t)p]);
+          if (!kept(p)) continue;
+          const size_t o = slot(p);
           buf += '@'; buf.append(nl.ptr((size_t)i), nl.len((size_t)i)); buf += '\n';
           buf.append(oseq.data() + o, (size_t)olen[(size_t)p]); buf += "\n+\n";
           buf.append(oqual.data() + o, (size_t)olen[(size_t)p]); buf += '\n';
@@ -5673,7 +5717,7 @@ static int merge_load_core(itsx_ctx *ctx, const FastxPart &f, const FastxPart &r
     fprintf(stderr, "[itsx] merge + load (%d sample%s): read+inflate+parse %.0f ms, upload+kernel %.0f ms, compact+gather+pack %.0f ms, write %.0f ms\n",
             (int)S, S == 1 ? "" : "s", parse_ms, ms(tm1, tm2), ms(tm2, tm3), ms(tm3, std::chrono::steady_clock::now()));
   }
-  if (n_merged_per_sample) for (int32_t s = 0; s < S; s++) n_merged_per_sample[s] = scnt[(size_t)s];
+  if (n_merged_per_sample) for (int32_t s = 0; s < S; s++) n_merged_per_sample[s] = scnt[(size_t)s] - sjoin[(size_t)s];      // merged pairs only
   return ITSX_OK;
 }
 
@@ -5812,7 +5856,7 @@ int itsx_merge_pairs_load_files(itsx_ctx *ctx, const char *const *r1_paths, cons
     const std::string why = ctx->err;
     const int64_t zero = 0;
     (void)itsx_set_reads(ctx, nullptr, &zero, 0, nullptr, nullptr);
-    ctx->h_merge_index.clear();
+    ctx->h_merge_index.clear(); ctx->h_merge_join.clear();
     ctx->set_error(why);
   }
   return rc;
@@ -5824,6 +5868,17 @@ int itsx_merge_pair_index(const itsx_ctx *ctx, int32_t *index, int64_t n_pairs)
   CTXCHK(ctx && index);
   if ((size_t)n_pairs != ctx->h_merge_index.size()) SET_ERR(ctx, ITSX_E_ARG, "itsx_merge_pair_index: the last merge held " + std::to_string(ctx->h_merge_index.size()) + " pairs");
   memcpy(index, ctx->h_merge_index.data(), (size_t)n_pairs * sizeof(int32_t));
+  return ITSX_OK;
+}
+
+// per pair of the context's last merge call (a merge-and-load: the pairs itsx_merge_pair_index speaks of; itsx_merge_pairs_files: that
+// call's pairs): 1 = the pair was joined (itsx_set_merge_join), and how many were
+int itsx_merge_join_info(const itsx_ctx *ctx, int8_t *joined, int64_t n_pairs, int64_t *n_joined)
+{
+  CTXCHK(ctx);
+  if ((size_t)n_pairs != ctx->h_merge_join.size()) SET_ERR(ctx, ITSX_E_ARG, "itsx_merge_join_info: the last merge held " + std::to_string(ctx->h_merge_join.size()) + " pairs");
+  if (joined && n_pairs > 0) memcpy(joined, ctx->h_merge_join.data(), (size_t)n_pairs);
+  if (n_joined) { int64_t c = 0; for (const int8_t j : ctx->h_merge_join) c += j; *n_joined = c; }
   return ITSX_OK;
 }
 

@@ -198,6 +198,9 @@ struct MergeArgs {
   const uint8_t *qsame, *qdiff;                 // [128*128]
   uint8_t *out_seq, *out_qual;                  // merged read of pair i at foff[i] + roff[i]
   int32_t *out_len, *reason, *shift; double *score;
+  // join (itsx_set_merge_join; off: the kernel instantiated without it): a pair rejected with reason 1, 3 or 5 leaves R1, eight N and
+  // revcomp(R2) as its read, out_len = fl + 8 + rl, and every pair's slot starts at foff[i] + roff[i] + 8 i
+  int32_t join; int8_t *joined;                 // [n] 1 = joined (join only)
 };
 void launch_merge(const MergeArgs &a, hipStream_t st);
 // the merged pairs of a merge kernel's output, compacted: read j = the j-th pair with reason 0, in pair order
@@ -212,6 +215,7 @@ struct MergeCompactArgs {
   int64_t *srcoff, *dstoff;                     // [n+1]: read j's bases in the merge output / in the gap-free text (dstoff[reads] = its size)
   int32_t *sample;                              // [n]: read j's sample (n_samples > 1 only)
   int64_t *sample_count;                        // [n_samples], zeroed by the caller: merged reads per sample (n_samples > 1 only)
+  int32_t join;                                 // the kernel ran with join: a read is a pair with out_len > 0, at foff[i] + roff[i] + 8 i
 };
 int64_t merge_compact_blocks(int64_t n);
 // total[0] = merged reads, total[1] = the bytes of their text (device memory)

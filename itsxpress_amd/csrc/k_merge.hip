@@ -34,17 +34,23 @@ __device__ __forceinline__ uint8_t comp_base(uint8_t c)
 // INDEXED: the shared 5-mers of every diagonal come from a 5-mer -> positions index of the forward read (LDS: 1024 chain
 // heads + one link per position), O(fl + rl + matches) instead of one compare per (diagonal, position); needs 13 B of LDS
 // per base, so pairs longer than 4096 bases in total take the plain variant.
-template <bool INDEXED> __global__ __launch_bounds__(64) void k_merge(MergeArgs a)
+// JOIN (itsx_set_merge_join): a pair whose mates do not overlap -- reason 1, 3 or 5 -- is kept as R1 + "NNNNNNNN" + revcomp(R2) with
+// qualities Q1 + "IIIIIIII" + reversed Q2, vsearch --fastq_join's padding as its manual gives it (PARITY UNPINNED, as the merge: no
+// vsearch build was at hand).  Both mates are in LDS when the verdict falls, so the join is five copies by all lanes; no LDS is added.
+// The joined read is 8 bytes longer than its mates, so with JOIN pair i's slot starts at foff[i] + roff[i] + 8 i.  No expected-error
+// filter (--fastq_join has none); reason[i] keeps its code, joined[i] marks the read.
+constexpr int JOIN_PAD = 8;
+template <bool INDEXED, bool JOIN> __global__ __launch_bounds__(64) void k_merge(MergeArgs a)
 {
   extern __shared__ uint8_t lds[];
   const int lane = threadIdx.x;
   for (int64_t pr = blockIdx.x; pr < a.n; pr += gridDim.x) {
     const int64_t fo = a.foff[pr], ro = a.roff[pr];
     const int fl = (int)(a.foff[pr + 1] - fo), rl = (int)(a.roff[pr + 1] - ro);
-    const int64_t oo = fo + ro;                              // merged reads are at most fl + rl long
+    const int64_t oo = fo + ro + (JOIN ? (int64_t)JOIN_PAD * pr : 0);      // merged reads are at most fl + rl long, joined ones fl + 8 + rl
     __syncthreads();
     if (fl < 1 || rl < 1 || fl + rl > a.max_total) {
-      if (lane == 0) { a.out_len[pr] = 0; a.reason[pr] = 8; a.score[pr] = 0.0; a.shift[pr] = 0; }
+      if (lane == 0) { a.out_len[pr] = 0; a.reason[pr] = 8; a.score[pr] = 0.0; a.shift[pr] = 0; if (JOIN) a.joined[pr] = 0; }
       continue;
     }
     uint8_t *fs = lds, *fq = fs + fl, *rs = fq + fl, *rq = rs + rl, *mq = rq + rl;       // mq: merged qualities (fl + rl)
@@ -136,6 +142,15 @@ template <bool INDEXED> __global__ __launch_bounds__(64) void k_merge(MergeArgs 
         a.out_seq[oo + n] = s; a.out_qual[oo + n] = q; mq[n] = q;
       }
     }
+    bool join = false;
+    if (JOIN && (reason == 1 || reason == 3 || reason == 5)) {       // (the verdict is the same in every lane)
+      join = true;
+      mlen = fl + JOIN_PAD + rl;
+      uint8_t *os = a.out_seq + oo, *oq = a.out_qual + oo;
+      for (int p = lane; p < fl; p += 64) { os[p] = fs[p]; oq[p] = fq[p]; }
+      if (lane < JOIN_PAD) { os[fl + lane] = 'N'; oq[fl + lane] = 'I'; }
+      for (int j = lane; j < rl; j += 64) { os[fl + JOIN_PAD + j] = rs[j]; oq[fl + JOIN_PAD + j] = rq[j]; }
+    }
     __syncthreads();
     if (lane == 0) {
       if (reason == 0) {
@@ -144,6 +159,7 @@ template <bool INDEXED> __global__ __launch_bounds__(64) void k_merge(MergeArgs 
         if (ee > a.maxee) { reason = 7; mlen = 0; }
       }
       a.out_len[pr] = mlen; a.reason[pr] = reason; a.score[pr] = best_idx == 0x7fffffff ? 0.0 : best; a.shift[pr] = shift;
+      if (JOIN) a.joined[pr] = join ? 1 : 0;
     }
   }
 }
@@ -154,10 +170,12 @@ void launch_merge(const MergeArgs &a, hipStream_t st)
   const int grid = (int)std::min<int64_t>(a.n, 65536);
   if (a.max_total <= 4096) {
     const size_t lds = (size_t)a.max_total * 13 + 4096 + 64;  // + chain heads, links and diagonal counters (4 B each)
-    hipLaunchKernelGGL(k_merge<true>, dim3(grid), dim3(64), lds, st, a);
+    if (a.join) hipLaunchKernelGGL((k_merge<true, true>), dim3(grid), dim3(64), lds, st, a);
+    else hipLaunchKernelGGL((k_merge<true, false>), dim3(grid), dim3(64), lds, st, a);
   } else {
     const size_t lds = (size_t)a.max_total * 5 + 16;          // bases, qualities, merged qualities (1 B each x 3) + 5-mer codes (2 B)
-    hipLaunchKernelGGL(k_merge<false>, dim3(grid), dim3(64), lds, st, a);
+    if (a.join) hipLaunchKernelGGL((k_merge<false, true>), dim3(grid), dim3(64), lds, st, a);
+    else hipLaunchKernelGGL((k_merge<false, false>), dim3(grid), dim3(64), lds, st, a);
   }
 }
 
@@ -166,7 +184,8 @@ void launch_merge(const MergeArgs &a, hipStream_t st)
 // reads gap-free, in pair order, and -- for a batch of samples -- to know each read's sample.  A two-level exclusive scan over the
 // pairs of (merged ? 1 : 0, merged ? out_len : 0): every block of MC_TILE pairs sums its tile (k_merge_compact<false>), one block scans
 // the tiles' sums (k_merge_compact_sums), and every block scans its tile again and scatters (k_merge_compact<true>).  Counts and byte
-// offsets are 64-bit throughout: a batch's text can pass 2^31 bytes.
+// offsets are 64-bit throughout: a batch's text can pass 2^31 bytes.  After a merge that joins (MergeCompactArgs::join) a read is a
+// pair with out_len > 0 -- merged or joined -- and pair i's read sits 8 i bytes further on.
 constexpr int MC_BLOCK = 256;
 constexpr int MC_ITEMS = 8;
 constexpr int MC_TILE = MC_BLOCK * MC_ITEMS;   // pairs per block; thread t owns MC_ITEMS consecutive pairs
@@ -188,7 +207,7 @@ template <bool SCATTER> __global__ __launch_bounds__(MC_BLOCK) void k_merge_comp
 #pragma unroll
   for (int i = 0; i < MC_ITEMS; i++) {
     const int64_t p = base + i;
-    const bool ok = p < a.n && a.reason[p] == 0;
+    const bool ok = p < a.n && (a.join ? a.out_len[p] > 0 : a.reason[p] == 0);      // join: merged and joined pairs alike
     len[i] = ok ? a.out_len[p] : -1;
     if (ok) { c++; l += len[i]; }
   }
@@ -206,7 +225,7 @@ template <bool SCATTER> __global__ __launch_bounds__(MC_BLOCK) void k_merge_comp
     if (p >= a.n) break;
     if (len[i] < 0) { a.pair_index[p] = -1; continue; }
     a.pair_index[p] = (int32_t)j;
-    a.srcoff[j] = a.foff[p] + a.roff[p];
+    a.srcoff[j] = a.foff[p] + a.roff[p] + (a.join ? (int64_t)JOIN_PAD * p : 0);
     a.dstoff[j] = d;
     if (a.n_samples > 1) {
       if (s < 0 || p >= a.pair_start[s + 1]) {

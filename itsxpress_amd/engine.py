@@ -63,6 +63,7 @@ class Engine:
         self.n_profiles = 0
         self.n_samples = 1
         self.rows_mode = -1
+        self.n_joined = 0            # the joined pairs of the last merge call (merge_join; 0 with it off)
 
     # Where the batch writers (write_trimmed_samples, write_trimmed_paired_samples) make the bytes of gzip output: "host" (the
     # default: the text comes back and the host's deflate writes it, byte for byte what it always wrote) or "device" (the gzip
@@ -150,6 +151,45 @@ class Engine:
         if getattr(self, "h", None):
             self._chk(self.L.itsx_set_sample_sharing_lazy(self.h, int(bool(on))))
         self._share_samples_lazy = bool(on)
+
+    # Whether the merge entry points keep a pair whose mates do not overlap (itsx_set_merge_join).  ITS1 / ITS2 run from about 100 to
+    # over 600 bases, so a 2x250 or 2x300 run cannot merge the long ones, and a pair the merge rejects is gone from seq.fq, the read
+    # set and both trimmed outputs.  While on, a pair rejected with reason 1, 3 or 5 (no shared 5-mers, score < 16, overlap < 10) is
+    # joined: R1 + "NNNNNNNN" + revcomp(R2), qualities Q1 + "IIIIIIII" + reversed Q2 (vsearch --fastq_join's padding; parity unpinned,
+    # like the merge's), with no expected-error filter.  merge_pairs_files, merge_pairs_load, merge_pairs_load_text and
+    # merge_pairs_load_files honour it; the counts they return stay those of the MERGED pairs, n_reads and merge_pair_index cover both
+    # kinds, merge_join_info() tells them apart.  The paired trimmed output is what the mode is for: each mate is cut at its own anchor.
+    # A single merged output then holds joined reads with the N gap inside.  False (the default) or True; stays until set again.
+    @property
+    def merge_join(self):
+        return getattr(self, "_merge_join", False)
+
+    @merge_join.setter
+    def merge_join(self, on):
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError("Engine.merge_join is False or True, not %r" % (on,))
+        if getattr(self, "h", None):
+            self._chk(self.L.itsx_set_merge_join(self.h, int(bool(on))))
+        self._merge_join = bool(on)
+
+    def merge_join_info(self):
+        """After a merge (merge_pairs_load / _load_text / _load_files: the pairs merge_pair_index speaks of; merge_pairs_files: that
+        call's pairs): (joined int8[n_pairs], n_joined) -- 1 where the pair's read is a joined one.  All 0 with merge_join off."""
+        n = int(getattr(self, "_n_pairs_join", getattr(self, "_n_pairs", 0)))
+        j = np.zeros(max(1, n), np.int8)
+        c = C.c_int64(0)
+        self._chk(self.L.itsx_merge_join_info(self.h, j.ctypes.data, n, C.byref(c)))
+        return j[:n], int(c.value)
+
+    def _n_joined(self, n_pairs):
+        """the joined pairs of the merge call just made (0 without a call to the engine when merge_join is off)"""
+        self._n_pairs_join = int(n_pairs)
+        self.n_joined = 0
+        if self.merge_join:
+            c = C.c_int64(0)
+            self._chk(self.L.itsx_merge_join_info(self.h, None, int(n_pairs), C.byref(c)))
+            self.n_joined = int(c.value)
+        return self.n_joined
 
     def sample_sharing_info(self):
         """What the last search() shared across samples: dict(n_classes, n_uniques_shared, n_rows_expanded, ms_classes, ms_expand) --
@@ -409,29 +449,41 @@ class Engine:
         return self.orient()
 
     # ---- f2: paired-end merge
-    def merge_pairs(self, fwd, fqual, rev, rqual, maxdiffs=40, maxee=2.0, allow_stagger=False):
+    def merge_pairs(self, fwd, fqual, rev, rqual, maxdiffs=40, maxee=2.0, allow_stagger=False, join=False):
         """Lists of equal length (str): forward reads / qualities, reverse reads / qualities as they are in the file.
-        Returns (reason int32[n], merged list[(seq, qual) or None], score float64[n], shift int32[n])."""
+        Returns (reason int32[n], merged list[(seq, qual) or None], score float64[n], shift int32[n]).
+        join=True (itsx_merge_buffers_join; the merge_join setting is not consulted): a pair rejected with reason 1, 3 or 5 is joined,
+        its (bases, quals) stand in the list, and a fifth array joined int8[n] marks it."""
         n = len(fwd)
         enc = lambda xs: ("".join(xs)).encode()
         fo = np.zeros(n + 1, np.int64); np.cumsum([len(x) for x in fwd], out=fo[1:])
         ro = np.zeros(n + 1, np.int64); np.cumsum([len(x) for x in rev], out=ro[1:])
         fs, fq, rs, rq = enc(fwd), enc(fqual), enc(rev), enc(rqual)
         assert len(fs) == len(fq) and len(rs) == len(rq)
-        cap = int(fo[-1] + ro[-1]) + 1
+        pad = 8 if join else 0                               # a slot holds 8 bytes more than the mates
+        cap = int(fo[-1] + ro[-1]) + pad * n + 1
         oseq = C.create_string_buffer(cap)
         oqual = C.create_string_buffer(cap)
         olen = np.zeros(max(1, n), np.int32)
         reason = np.zeros(max(1, n), np.int32)
         score = np.zeros(max(1, n), np.float64)
         shift = np.zeros(max(1, n), np.int32)
-        self._chk(self.L.itsx_merge_buffers(self.h, fs, fq, fo.ctypes.data, rs, rq, ro.ctypes.data, n, int(maxdiffs), float(maxee),
-                                            int(allow_stagger), oseq, oqual, olen.ctypes.data, reason.ctypes.data,
-                                            score.ctypes.data, shift.ctypes.data))
+        joined = np.zeros(max(1, n), np.int8)
+        if join:
+            self._chk(self.L.itsx_merge_buffers_join(self.h, fs, fq, fo.ctypes.data, rs, rq, ro.ctypes.data, n, int(maxdiffs), float(maxee),
+                                                     int(allow_stagger), oseq, oqual, olen.ctypes.data, reason.ctypes.data,
+                                                     score.ctypes.data, shift.ctypes.data, joined.ctypes.data))
+        else:
+            self._chk(self.L.itsx_merge_buffers(self.h, fs, fq, fo.ctypes.data, rs, rq, ro.ctypes.data, n, int(maxdiffs), float(maxee),
+                                                int(allow_stagger), oseq, oqual, olen.ctypes.data, reason.ctypes.data,
+                                                score.ctypes.data, shift.ctypes.data))
         merged = []
+        sraw, qraw = oseq.raw, oqual.raw
         for i in range(n):
-            o = int(fo[i] + ro[i])
-            merged.append((oseq.raw[o:o + olen[i]].decode(), oqual.raw[o:o + olen[i]].decode()) if reason[i] == 0 else None)
+            o = int(fo[i] + ro[i]) + pad * i
+            merged.append((sraw[o:o + olen[i]].decode(), qraw[o:o + olen[i]].decode()) if (reason[i] == 0 or joined[i]) else None)
+        if join:
+            return reason[:n], merged, score[:n], shift[:n], joined[:n]
         return reason[:n], merged, score[:n], shift[:n]
 
     def merge_pairs_files(self, r1, r2, out, maxdiffs=40, maxee=2.0, allow_stagger=False):
@@ -442,6 +494,7 @@ class Engine:
         m = C.c_int64(0)
         self._chk(self.L.itsx_merge_pairs_files(self.h, os.fsencode(r1), os.fsencode(r2), os.fsencode(out), int(maxdiffs),
                                                 float(maxee), int(allow_stagger), C.byref(n), C.byref(m)))
+        self._n_joined_files = self._n_joined(n.value)       # (merge_join: the joined records the file holds beside the m merged ones)
         return n.value, m.value
 
     def merge_pairs_load(self, r1, r2, maxdiffs=40, maxee=2.0, allow_stagger=False):
@@ -453,9 +506,9 @@ class Engine:
         m = C.c_int64(0)
         self._chk(self.L.itsx_merge_pairs_load(self.h, os.fsencode(r1), os.fsencode(r2), int(maxdiffs), float(maxee), int(allow_stagger),
                                                C.byref(n), C.byref(m)))
-        self.n_reads, self.n_samples, self.n_unique = m.value, 1, 0
+        self.n_reads, self.n_samples, self.n_unique = m.value + self._n_joined(n.value), 1, 0      # (the reads: merged and joined)
         self._n_pairs = n.value
-        self._last_merge = dict(r1=r1, r2=r2, maxdiffs=int(maxdiffs), maxee=float(maxee), allow_stagger=bool(allow_stagger))
+        self._last_merge = dict(r1=r1, r2=r2, maxdiffs=int(maxdiffs), maxee=float(maxee), allow_stagger=bool(allow_stagger), join=self.merge_join)
         return n.value, m.value
 
     def merge_pairs_load_text(self, ptr1, nb1, ptr2, nb2, maxdiffs=40, maxee=2.0, allow_stagger=False):
@@ -465,7 +518,7 @@ class Engine:
         m = C.c_int64(0)
         self._chk(self.L.itsx_merge_pairs_load_text(self.h, C.c_void_p(ptr1), int(nb1), C.c_void_p(ptr2), int(nb2), int(maxdiffs), float(maxee),
                                                     int(allow_stagger), C.byref(n), C.byref(m)))
-        self.n_reads, self.n_samples, self.n_unique = m.value, 1, 0
+        self.n_reads, self.n_samples, self.n_unique = m.value + self._n_joined(n.value), 1, 0
         self._n_pairs = n.value
         idx = np.zeros(max(1, n.value), np.int32)
         self._chk(self.L.itsx_merge_pair_index(self.h, idx.ctypes.data, n.value))
@@ -496,7 +549,7 @@ class Engine:
         except EngineError:
             self.n_reads, self.n_samples, self.n_unique, self._n_pairs = 0, 1, 0, 0      # the context is left empty
             raise
-        self.n_reads, self.n_unique = int(m.sum()), 0
+        self.n_reads, self.n_unique = int(m.sum()) + self._n_joined(int(n.sum())), 0
         self.n_samples = max(1, self.L.itsx_num_samples(self.h))
         self._n_pairs = int(n.sum())
         return n, m
@@ -518,7 +571,9 @@ class Engine:
             raise EngineError(-1, "write_merged_fastq: this engine's reads do not come from merge_pairs_load")
         tmp = Engine(self.device)
         try:
+            tmp.merge_join = bool(lm.get("join", False))      # the same merge: joined records too, where the reads hold them
             n, m = tmp.merge_pairs_files(lm["r1"], lm["r2"], path, maxdiffs=lm["maxdiffs"], maxee=lm["maxee"], allow_stagger=lm["allow_stagger"])
+            m += tmp._n_joined_files
         finally:
             tmp.close()
         if m != self.n_reads:

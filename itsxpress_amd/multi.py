@@ -170,9 +170,12 @@ def _h_load_range(eng, st, path, off, nb):
     return n
 
 
-def _h_merge_piece(eng, st, p1, p2, out, maxdiffs, maxee, allow_stagger):
-    """merge this worker's pieces of R1 / R2: into the engine's read set (out None) or into a piece of seq.fq"""
+def _h_merge_piece(eng, st, p1, p2, out, maxdiffs, maxee, allow_stagger, join=False):
+    """merge this worker's pieces of R1 / R2: into the engine's read set (out None) or into a piece of seq.fq; join: the parent's
+    merge_join setting.  Returns (pairs, merged, joined)."""
     try:
+        if bool(join) != eng.merge_join:
+            eng.merge_join = bool(join)
         if out is None:
             n, m = eng.merge_pairs_load(p1, p2, maxdiffs=maxdiffs, maxee=maxee, allow_stagger=allow_stagger)
         else:
@@ -183,7 +186,7 @@ def _h_merge_piece(eng, st, p1, p2, out, maxdiffs, maxee, allow_stagger):
                 os.unlink(p)
             except OSError:
                 pass
-    return n, m
+    return n, m, int(getattr(eng, "n_joined", 0))
 
 
 def _h_set_base(eng, st, base):
@@ -1075,8 +1078,22 @@ class MultiEngine(ShardedOps):
         p2, _ = self._shard(r2, "r2", match=rec)           # R2 cut where R1 was: the same pairs on every worker
         self._timed("merge: inflate + cut", t0)
         outs = [None if out is None else "%s_merged.%d" % (self._xprefix, r) for r in range(self.world)]
-        res = self._each("merge_piece", [(p1[r], p2[r], outs[r], int(maxdiffs), float(maxee), bool(allow_stagger)) for r in range(self.world)])
-        return int(sum(x[0] for x in res)), [int(x[1]) for x in res], outs
+        res = self._each("merge_piece", [(p1[r], p2[r], outs[r], int(maxdiffs), float(maxee), bool(allow_stagger), self.merge_join) for r in range(self.world)])
+        self.n_joined = int(sum(x[2] for x in res))          # (merge_join: every worker's reads are its merged and its joined pairs)
+        self._merged_only = int(sum(x[1] for x in res))
+        return int(sum(x[0] for x in res)), [int(x[1]) + int(x[2]) for x in res], outs
+
+    # Whether the workers' merges keep the pairs whose mates do not overlap as joined reads (Engine.merge_join): handed to every worker
+    # with its piece.  The counts the merge calls return stay those of the merged pairs; n_reads and n_joined tell the rest.
+    @property
+    def merge_join(self):
+        return getattr(self, "_merge_join", False)
+
+    @merge_join.setter
+    def merge_join(self, on):
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError("MultiEngine.merge_join is False or True, not %r" % (on,))
+        self._merge_join = bool(on)
 
     def merge_pairs_load(self, r1, r2, maxdiffs=40, maxee=2.0, allow_stagger=False):
         """merge R1 / R2 on every worker's piece; the merged reads are the workers' read sets (nothing written): (pairs, merged)"""
@@ -1087,8 +1104,8 @@ class MultiEngine(ShardedOps):
         self._bases, self._nloc = [int(b) for b in base[:-1]], ms
         self._derep = None
         self._final = False
-        self._last_merge = dict(r1=r1, r2=r2, maxdiffs=int(maxdiffs), maxee=float(maxee), allow_stagger=bool(allow_stagger))
-        return n, self.n_reads
+        self._last_merge = dict(r1=r1, r2=r2, maxdiffs=int(maxdiffs), maxee=float(maxee), allow_stagger=bool(allow_stagger), join=self.merge_join)
+        return n, self._merged_only
 
     def merge_pairs_files(self, r1, r2, out, maxdiffs=40, maxee=2.0, allow_stagger=False):
         """the merged reads as ONE file (seq.fq): every worker merges its piece, the pieces are joined in order"""
@@ -1102,14 +1119,19 @@ class MultiEngine(ShardedOps):
                             break
                         f.write(b)
                 os.unlink(p)
-        return n, int(sum(ms))
+        return n, self._merged_only
 
     def write_merged_fastq(self, path):
         lm = self._last_merge
         if lm is None:
             raise EngineError(-1, "write_merged_fastq: this engine's reads do not come from merge_pairs_load")
         # (the same merge once more, into files this time: itsx_merge_pairs_files leaves a context's read set and results alone)
-        n, m = self.merge_pairs_files(lm["r1"], lm["r2"], path, maxdiffs=lm["maxdiffs"], maxee=lm["maxee"], allow_stagger=lm["allow_stagger"])
+        keep, self.merge_join = self.merge_join, bool(lm.get("join", False))      # the same merge: joined records too, where the reads hold them
+        try:
+            n, m = self.merge_pairs_files(lm["r1"], lm["r2"], path, maxdiffs=lm["maxdiffs"], maxee=lm["maxee"], allow_stagger=lm["allow_stagger"])
+            m += self.n_joined
+        finally:
+            self.merge_join = keep
         if m != self.n_reads:
             raise EngineError(-1, "write_merged_fastq: %d merged records written, the engines hold %d" % (m, self.n_reads))
         return m

@@ -601,7 +601,7 @@ class StreamEngine(ShardedOps):
         self.close()
         self._path, self._path2 = r1, r2
         self._merge = dict(maxdiffs=int(maxdiffs), maxee=float(maxee), allow_stagger=bool(allow_stagger))
-        self._last_merge = dict(r1=r1, r2=r2, **self._merge)
+        self._last_merge = dict(r1=r1, r2=r2, join=self.merge_join, **self._merge)
         self._loaded = self._searched = self._final = False
         self._derep = None
         return -1, -1
@@ -611,7 +611,11 @@ class StreamEngine(ShardedOps):
         lm = self._last_merge
         if lm is None:
             raise EngineError(-1, "write_merged_fastq: no paired sample was loaded")
-        res = self._plain().merge_pairs_files(lm["r1"], lm["r2"], path, maxdiffs=lm["maxdiffs"], maxee=lm["maxee"], allow_stagger=lm["allow_stagger"])
+        keep, self.merge_join = self.merge_join, bool(lm.get("join", False))      # the same merge: joined records too, where the reads hold them
+        try:
+            res = self._plain().merge_pairs_files(lm["r1"], lm["r2"], path, maxdiffs=lm["maxdiffs"], maxee=lm["maxee"], allow_stagger=lm["allow_stagger"])
+        finally:
+            self.merge_join = keep
         self._plain_eng.close()
         self._plain_eng = None
         return res
@@ -697,6 +701,8 @@ class StreamEngine(ShardedOps):
         import time
         t0 = time.perf_counter()
         eng = Engine(self.device)
+        if self.merge_join:
+            eng.merge_join = True
         tc = time.perf_counter()
         st = {"rank": k, "world": 0, "base": int(base)}
         try:
@@ -718,6 +724,7 @@ class StreamEngine(ShardedOps):
             else:
                 npairs, _, st["merged_index"] = eng.merge_pairs_load_text(ptr, nb, ptr2, nb2, **self._merge)
                 st["pairs"] = int(npairs)
+                st["joined"] = int(getattr(eng, "n_joined", 0))
             st["load_s"] = {"context": round(tc - t0, 3), "profiles": round(t1 - tc, 3), "parse+upload": round(time.perf_counter() - t1, 3),
                             "MB": round((nb + nb2) / 1e6, 1), "reads": eng.n_reads}
         except BaseException:
@@ -923,6 +930,7 @@ class StreamEngine(ShardedOps):
         self._nloc = [eng.n_reads for eng, _ in self._engs]
         self._n_reads = int(sum(self._nloc))
         self.n_pairs = int(sum(st.get("pairs", 0) for _, st in self._engs))
+        self.n_joined = int(sum(st.get("joined", 0) for _, st in self._engs))
         self._index_uniques()
         self._loaded = True
         if with_search:
@@ -1018,7 +1026,21 @@ class StreamEngine(ShardedOps):
     def _plain(self):
         if getattr(self, "_plain_eng", None) is None:
             self._plain_eng = Engine(self.device)
+        if self._plain_eng.merge_join != self.merge_join:
+            self._plain_eng.merge_join = self.merge_join
         return self._plain_eng
+
+    # Whether the merges keep the pairs whose mates do not overlap as joined reads (Engine.merge_join): handed to every context this
+    # engine creates -- the chunks' and the plain one.  n_joined counts them after the pipeline.
+    @property
+    def merge_join(self):
+        return getattr(self, "_merge_join", False)
+
+    @merge_join.setter
+    def merge_join(self, on):
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError("StreamEngine.merge_join is False or True, not %r" % (on,))
+        self._merge_join = bool(on)
 
     def orient_load_db(self, fasta_path):
         return self._plain().orient_load_db(fasta_path)

@@ -21,6 +21,7 @@ PY_SWITCHES = [
     ("ITSXPRESS_DOMTBL_ALI", "mode", "=1: domtbl.txt gets hmmsearch's hmm / ali coordinates and acc from the optimal-accuracy stage (itsx_align_domains) instead of placeholders; one context writing files only (ignored with a warning under ITSXPRESS_GPUS > 1, ITSXPRESS_STREAM=1, ITSXPRESS_ARRAYS=1)"),
     ("ITSXPRESS_UC_CIGAR", "mode", "=1: at cluster_id < 1 the H rows of uc.txt get the member's alignment with its centroid in column 8 (itsx_align_clusters) instead of '*'; one context writing files only (ignored with a warning under ITSXPRESS_GPUS > 1 through MultiEngine, ITSXPRESS_STREAM=1, ITSXPRESS_ARRAYS=1)"),
     ("ITSXPRESS_ORIENT", "mode", "=profiles: orient_reads orients by the profiles of the sample's orient_hmmfile (itsx_orient_profiles: the MSV filter on both strands, undecided reads kept) instead of the k-mer counts against the universal database; ITSXPRESS_STREAM=1 with ITSXPRESS_ARRAYS=1 orients chunk by chunk inside the streamed run (StreamEngine.plan_orient, no oriented.fq); EngineError -5 under ITSXPRESS_GPUS > 1"),
+    ("ITSXPRESS_JOIN_UNMERGED", "mode", "=1: _merge_reads keeps a pair the merge rejects for want of an overlap (reason 1, 3, 5) as R1 + NNNNNNNN + revcomp(R2) (itsx_set_merge_join; also sobj.join_unmerged = True): more reads in seq.fq and both trimmed outputs, the merged pairs unchanged; the single merged output then holds reads with the N gap"),
     ("ITSXPRESS_STREAM", "mode", "=1 / 0: streamed file-order chunks on / off (default: by input size, ITSX_STREAM_AUTO_MB)"),
     ("ITSXPRESS_DB_DIR", "mode", "directory with additional ITSx_db HMM files (F.hmm)"),
     ("ITSXPRESS_XDIR", "tuning", "directory of the multi-GPU exchange files (default /dev/shm when it has room, else the temp directory)"),
