@@ -761,7 +761,7 @@ static int install_profiles(itsx_ctx *ctx, std::vector<HostProfile> &pv, int *n_
     }
     HIPCHK(upload(ctx->d_vtab, vt, ctx->st));
   }
-  {   // the bound kernel's transitions by pair of nodes (k_lazy.hip: k_fwd_bound): record j = pair j's early half, pair j - 1's late half
+  {   // the bound kernel's transitions by pair of nodes (k_lazy.hip: k_fwd_bound), one 16-float record per step of its row loop
     // FOLD (k_lazy.hip): with H_k = 1 + t(D_k -> D_k+1) H_k+1 (what one unit of D_k adds to the row's E through itself and the deletes
     // after it), g_k = 1 + t(M_k -> D_k+1) H_k+1, s_1 = 1, s_k+1 = t(M_k -> D_k+1) / g_k, a_k = s_k t(D_k -> D_k+1) / s_k+1 the kernel
     // keeps M~_k = M_k g_k and D^_k = D_k / s_k:  D^_k+1 = D^_k a_k + M~_k,  E = sum of M~_k;  M -> M / I transitions divided by g_k, the D -> M
@@ -805,18 +805,20 @@ static int install_profiles(itsx_ctx *ctx, std::vector<HostProfile> &pv, int *n_
       auto gk = [&](int k) { return fold && k >= 1 && k <= KK ? G[(size_t)i][(size_t)k] : 1.0; };
       auto sk = [&](int k) { return fold && k >= 1 && k <= KK + 1 ? SC[(size_t)i][(size_t)k] : 1.0; };
       auto rk = [&](int k) { return fold && k >= 1 && k <= KK ? RI[(size_t)i][(size_t)k] : 1.0; };
+      // record j = what step j of the row loop reads: the chain of pair j (bm dd dd, md) and what pair j - 1's new cells leave for the next
+      // row (mm im dm ii, mi)
       for (int j = 0; j <= BOUND_PAIRS; j++) {
         float *o = bt.data() + (size_t)i * BOUND_TAB + (size_t)j * 16;
-        if (j < BOUND_PAIRS) {
-          const int k1 = 2 * j + 1, k2 = 2 * j + 2;
+        if (j > 0) {
+          const int k1 = 2 * (j - 1) + 1, k2 = 2 * (j - 1) + 2;
           o[0] = (float)(tn(k1 + 1, 1) / gk(k1)); o[1] = (float)(tn(k2 + 1, 1) / gk(k2));      // M_k -> M_k+1 (tf stores it at the target node)
           o[2] = (float)(tn(k1 + 1, 2) * rk(k1)); o[3] = (float)(tn(k2 + 1, 2) * rk(k2));      // I_k -> M_k+1
           o[4] = (float)(tn(k1 + 1, 3) * sk(k1)); o[5] = (float)(tn(k2 + 1, 3) * sk(k2));      // D_k -> M_k+1
           o[6] = tn(k1, 6); o[7] = tn(k2, 6);                                                    // I_k -> I_k
           o[12] = (float)(tn(k1, 5) / gk(k1)); o[13] = (float)(tn(k2, 5) / gk(k2));            // M_k -> I_k (FOLD: not read)
         }
-        if (j > 0) {
-          const int k1 = 2 * (j - 1) + 1, k2 = 2 * (j - 1) + 2;
+        if (j < BOUND_PAIRS) {
+          const int k1 = 2 * j + 1, k2 = 2 * j + 2;
           o[8] = tn(k1, 0); o[9] = tn(k2, 0);              // B -> M_k
           if (fold) { o[10] = k1 > 1 ? (float)AA[(size_t)i][(size_t)k1 - 1] : 0.0f; o[11] = (float)AA[(size_t)i][(size_t)k1]; }
           else { o[10] = tn(k1 - 1, 7); o[11] = tn(k1, 7); }   // D_k1-1 -> D_k1 (0 before node 1), D_k1 -> D_k2
@@ -832,20 +834,17 @@ static int install_profiles(itsx_ctx *ctx, std::vector<HostProfile> &pv, int *n_
     std::vector<float> rt((size_t)std::max(P, 1) * BOUND_RTAB, 0.0f);
     for (int i = 0; i < P && fold; i++) {
       const float *b = bt.data() + (size_t)i * BOUND_TAB;
-      // record j = what the kernel's step j reads: mm im dm bm of pair j (the late half of pair j: k_lazy.hip) and ii, dd of pair j - 1
-      // (the early half of the pair after it in walking order); the last pair's ii, dd stand behind the records
+      // record j = what the kernel's step j reads: bm of pair j (its w goes into the row's B) and mm im dm ii dd of pair j - 1 (whose cells'
+      // adjoints are formed from the carried W and G in the same step: k_lazy.hip); record BOUND_PAIRS holds the last pair's alone
       for (int j = 0; j <= BOUND_PAIRS; j++) {
         float *o = rt.data() + (size_t)i * BOUND_RTAB + (size_t)j * 12;
-        if (j < BOUND_PAIRS) {
-          for (int q = 0; q < 6; q++) o[q] = b[(size_t)j * 16 + q];                        // mm im dm of the pair's nodes
-          o[6] = b[(size_t)(j + 1) * 16 + 8]; o[7] = b[(size_t)(j + 1) * 16 + 9];          // B -> M_k1, B -> M_k2
-        }
+        if (j < BOUND_PAIRS) { o[6] = b[(size_t)j * 16 + 8]; o[7] = b[(size_t)j * 16 + 9]; }      // B -> M_k1, B -> M_k2
         if (j >= 1) {
           const int jj = j - 1;
-          float *q = j < BOUND_PAIRS ? o + 8 : o;
-          q[0] = b[(size_t)jj * 16 + 6]; q[1] = b[(size_t)jj * 16 + 7];                    // I_k -> I_k of pair j - 1
-          q[2] = b[(size_t)(jj + 1) * 16 + 11];                                            // D_k1 -> D_k2
-          q[3] = (jj + 2 <= BOUND_PAIRS) ? b[(size_t)(jj + 2) * 16 + 10] : 0.0f;           // D_k2 -> D_k2+1 (none after the last node)
+          for (int q = 0; q < 6; q++) o[q] = b[(size_t)(jj + 1) * 16 + q];                         // mm im dm of the pair's nodes
+          o[8] = b[(size_t)(jj + 1) * 16 + 6]; o[9] = b[(size_t)(jj + 1) * 16 + 7];                // I_k -> I_k
+          o[10] = b[(size_t)jj * 16 + 11];                                                         // D_k1 -> D_k2
+          o[11] = (jj + 1 < BOUND_PAIRS) ? b[(size_t)(jj + 1) * 16 + 10] : 0.0f;                   // D_k2 -> D_k2+1 (none after the last node)
         }
       }
     }
@@ -2229,7 +2228,11 @@ static int build_share(itsx_ctx *ctx)
   // their own -- round 5's first streamed run spent 5 s in hipMalloc for slots its 1.3 M-read chunks filled to a tenth)
   // (a quarter and a twentieth: the groups a batch is made of do not fill four exact quarters, and a fifth batch with the 2 % that are left
   // over is thirty launches of a few thousand waves -- 39 ms of pass A and 20 ms of the filter at 10 M reads for 15 ms' worth of rows)
-  if (!sw_get("ITSX_SHARE_GB")) gb = std::min(gb, std::max(1.0, (double)((int64_t)NN + NG) * state_b * (double)P / (double)(1ull << 30) / 3.8));
+  // (ITSX_SHARE_DIV: the divisor, for A/B -- 2.8 gives three batches where 3.8 gives four; the cap above holds either way.  A divisor
+  // that is asked for is obeyed in a small search too, which otherwise gets 1 GB and one batch)
+  double share_div = 3.8, share_floor = 1.0;
+  if (const char *e = sw_get("ITSX_SHARE_DIV")) { share_div = std::min(16.0, std::max(1.0, atof(e))); share_floor = 0.0001; }
+  if (!sw_get("ITSX_SHARE_GB")) gb = std::min(gb, std::max(share_floor, (double)((int64_t)NN + NG) * state_b * (double)P / (double)(1ull << 30) / share_div));
   // (in steps of half a GB: a budget that follows the free memory byte by byte made every search of a warm context ask for a slab a few
   // KB larger than the one it held -- 20 GB freed and allocated again per search)
   if (gb > 1.0) gb = floor(gb * 2.0) / 2.0;

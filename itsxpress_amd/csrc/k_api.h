@@ -434,6 +434,7 @@ void launch_need_res(const uint32_t *need_b, int32_t Ub, int32_t P, int32_t W, u
 struct ShareLaunch {
   const int32_t *src; const unsigned long long *mask; const int32_t *node0;
   void *slots;                 // saved row states: [(node - node_base) * Pb + profile - p0][MSV_STATE_Q uint4 | FWD_STATE_Q float4]
+                               // (a Forward state: 23 x (S pair, I+ pair), then xN xJ xC xB, then the scale's double: 400 bytes)
   int64_t node_base; int32_t p0, Pb;
   int32_t depth, logB;
   float rescale;               // k_fwd_bound: a row's cells are scaled back when its E passes this
@@ -464,7 +465,9 @@ static_assert(sizeof(ChainRec) == 64, "k_fwd_bound / k_bwd_bound read a chain's 
 void launch_chain_recs(int32_t n, const ReadsDev &rd, const int32_t *order /*global unique by position*/, const int32_t *seed_read, const int32_t *src, const int32_t *node0,
                        const unsigned long long *mask, const int32_t *endrow, const int32_t *jlev, const int32_t *jsrc, ChainRec *out, hipStream_t st);
 constexpr int MSV_STATE_Q = 8;             // 23 packed registers + xJ, xB, 0 (was xEmax), padded to one 128-byte line
-constexpr int FWD_STATE_Q = 36;            // M, I, D of 46 nodes + xN xJ xC xB + the scale's logarithm (double)
+// pass A's row state (k_lazy.hip): float4 j < 23 = S and I+ of pair j's two nodes (k_bwd_bound: their adjoints W and G), float4 23 = xN xJ xC xB,
+// float4 24 = the scale's logarithm (double) and two floats of padding
+constexpr int FWD_STATE_Q = 25;
 // lazy searches only: a chain whose own pair failed the MSV filter still has to run for a profile when a chain below it needs its state
 void launch_need_bits(const uint16_t *res, int32_t U, int32_t P, int32_t W, uint32_t *pass, uint32_t *need, hipStream_t st);
 void launch_need_up(int d, const uint8_t *depth, const int32_t *parent, int32_t U, int32_t W, uint32_t *need, hipStream_t st);

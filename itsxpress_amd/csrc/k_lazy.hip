@@ -35,10 +35,13 @@ namespace itsx {
 // (whose four D->D passes per row exist only because of the striping), fused multiply-adds, rescaling at 1e20 instead of 1e4.
 // The result differs from HMMER's float by rounding only (relative ~1e-5, far inside LenTables::lazy_c's margin) and is used
 // for nothing but the selection; the pairs that matter get HMMER's own arithmetic in the domain pipeline.
-//   * lane = pair, wave = 64 pairs of one profile (the work list's grouping), state M, I, D of 46 nodes in 69 register pairs,
-//     pair j = nodes (2j + 1, 2j + 2): every operation on M and I is a packed one over two adjacent nodes;
-//   * a node's contribution to the NEXT node's match cell, S[k] = M[k] t(M_k->M_k+1) + I[k] t(I_k->M_k+1) + D[k] t(D_k->M_k+1), is
-//     formed on the aligned pairs and shifted by one node with a single register move per pair (the transitions are stored by
+//   * lane = pair, wave = 64 pairs of one profile (the work list's grouping), pair j = nodes (2j + 1, 2j + 2): every operation on
+//     the cells is a packed one over two adjacent nodes;
+//   * the row state is TWO cell arrays, 46 register pairs: row i + 1 reads row i's cells only through S[k] = M[k] t(M_k->M_k+1) +
+//     I[k] t(I_k->M_k+1) + D[k] t(D_k->M_k+1), a node's contribution to the NEXT node's match cell, and through I+[k], its own insert
+//     cell (I[k] t(I_k->I_k) + M[k] t(M_k->I_k)).  Both are formed in row i itself, when M'[k] and D'[k] are born; M and D live for one
+//     step of the row loop.  166 registers instead of 212 with M, I, D carried: three waves per SIMD instead of two (ITSX_BOUND_WAVES);
+//   * S is formed on the aligned pairs and shifted by one node with a single register move per pair (the transitions are stored by
 //     their source node for that: BoundTab);
 //   * the D->D chain is 2 scalar FMAs per pair, sequential, as the recurrence is;
 //   * the profile's transitions are wave-uniform: 64 B per pair of nodes through scalar loads, double-buffered by hand (as in
@@ -46,8 +49,8 @@ namespace itsx {
 // ~13 packed instructions per pair of nodes, ~320 per row against the striped kernel's 533.
 constexpr int BP = BOUND_PAIRS;                     // 23 pairs of nodes: models of up to 46 nodes (engine.h: MMAX)
 typedef const f4 __attribute__((address_space(4))) *cf4q;
-// record j of a profile's table (engine.hip: install_profiles), 16 floats: what pair j needs EARLY -- its transitions out of the
-// nodes (mm im dm: into the next node's match cell; mi ii) -- and what pair j - 1 needs LATE (bm md dd dd): one record per step
+// record j of a profile's table (engine.hip: install_profiles), 16 floats, what step j of the row loop reads: the chain of pair j
+// (bm md dd dd) and the transitions out of pair j - 1's nodes (mm im dm: into the next node's match cell; mi ii), one record per step
 struct BT { f2 mm, im, dm, mi, ii, bm, md; float dd1, dd2; };
 DEV BT ldbt(const float *tab, int j)
 {
@@ -88,7 +91,7 @@ DEV int wave_max(int v)
 }
 
 // SHARE (k_share.hip): the wave's pairs are chains that start at the same depth of their length's prefix tree -- the rows before
-// come from the state the parent chain saved for this profile (FWD_STATE_Q float4: M, I, D of the 46 nodes, xN xJ xC xB, the scale's
+// come from the state the parent chain saved for this profile (FWD_STATE_Q float4: S and I+ of the 46 nodes, xN xJ xC xB, the scale's
 // logarithm), and a chain saves its own state after row d * B where a later chain branches off.  The same operations on the same
 // operands in the same order as the chain's unshared run: the scores are bitwise equal (tests/test_gpu_share.py).
 // A block is FWD_WPB consecutive waves of the work list -- the same profile but at a run's end -- so that the waves a CU holds at one time
@@ -97,6 +100,16 @@ DEV int wave_max(int v)
 #define ITSX_FWD_WPB 1
 #endif
 constexpr int FWD_WPB = ITSX_FWD_WPB;
+// Waves per SIMD both pass-A kernels are compiled for.  The row state is two cell arrays (92 registers), so the kernels fit the 168
+// registers that three resident waves leave each of them, without scratch; -DITSX_BOUND_WAVES=2 builds the two-wave arm (256 registers)
+// from the same source for an A/B.
+#ifndef ITSX_BOUND_WAVES
+#define ITSX_BOUND_WAVES 3
+#endif
+// (the attribute and not __launch_bounds__' second argument, which is a minimum only: the kernels need no more than 168 registers, and
+// three waves would be resident whatever the minimum says.  With the maximum given too the compiler reports enough registers to hold
+// the occupancy at exactly this many waves)
+#define BOUND_OCC __attribute__((amdgpu_waves_per_eu(ITSX_BOUND_WAVES, ITSX_BOUND_WAVES)))
 // FOLD (engine.hip: install_profiles builds the table for it; every profile whose interior M->D transitions are all > 0, i.e. every
 // profile hmmbuild writes): the delete cells are kept DIVIDED by s_k = t(M_k-1 -> D_k) / g_k-1 and the match cells MULTIPLIED by
 // g_k = 1 + the share of M_k that the deletes after it carry into E -- constants of the profile, folded into its transitions and
@@ -104,8 +117,12 @@ constexpr int FWD_WPB = ITSX_FWD_WPB;
 // multiply-add (D^_k+1 = D^_k a_k + M~_k: no product M_k t(M_k -> D_k+1) first), and the row's E is the sum of the match cells alone
 // (no second accumulation of the deletes).  The insert cells are kept divided by r_k = t(M_k -> I_k) / g_k in the same way: I^_k' = I^_k t(I_k -> I_k)
 // + M~_k, one multiply-add instead of a product and a multiply-add.  8 packed + 2 plain instructions per pair of nodes instead of 11 + 2.
+// A row in the carried state (S, I+), x the row's residue:
+//     M~'_k = (xB bm_k + S_k-1) e_k(x),   D^'_k+1 = D^'_k a_k + M~'_k,   E = sum M~'_k
+//     S'_k = M~'_k mm_k + I+_k im_k + D^'_k dm_k,   I+'_k = I+_k ii_k + M~'_k
+// FOLD = false: S' = M' mm + I+ im + D' dm, I+' = M' mi + I+ ii, D'_k+1 = D'_k dd_k + M'_k md_k, and E adds the deletes.
 template <bool SHARE, bool FOLD>
-__global__ void __launch_bounds__(64 * FWD_WPB, 2) k_fwd_bound(FloatArgs a, int wave0, int nwaves, const float *__restrict__ btab, float *__restrict__ fb, ShareLaunch sl)
+__global__ void __launch_bounds__(64 * FWD_WPB) BOUND_OCC k_fwd_bound(FloatArgs a, int wave0, int nwaves, const float *__restrict__ btab, float *__restrict__ fb, ShareLaunch sl)
 {
   const int wv = threadIdx.x >> 6, widx = blockIdx.x * FWD_WPB + wv;
   WaveDesc wd = a.waves[wave0 + min(widx, nwaves - 1)];
@@ -144,9 +161,9 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_fwd_bound(FloatArgs a, int 
   if (recs) { sq.w = a.rd.words + cr.woff; sq.exc = a.rd.exc + cr.excoff; sq.nexc = cr.nexc; sq.L = cr.L; }
   else sq = open_seq(a.rd, a.seed_read[a.sorted_uniq[pr.useq]]);
   int Lw = wd.rows - 1;
-  f2 M[BP], I[BP], D[BP];
+  f2 S[BP], Ip[BP];
 #pragma unroll
-  for (int j = 0; j < BP; j++) { M[j] = (f2){0.f, 0.f}; I[j] = (f2){0.f, 0.f}; D[j] = (f2){0.f, 0.f}; }
+  for (int j = 0; j < BP; j++) { S[j] = (f2){0.f, 0.f}; Ip[j] = (f2){0.f, 0.f}; }
   const float pmove = (2.0f + 1.0f) / ((float)L + 2.0f + 1.0f);
   const float ploop = 1.0f - pmove;
   float xE = 0.f, xN = 1.f, xJ = 0.f, xB = pmove, xC = 0.f;
@@ -176,12 +193,10 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_fwd_bound(FloatArgs a, int 
       const int64_t node = (int64_t)(recs ? cr.src : sl.src[k]) - sl.node_base;
       const f4 *src = (const f4 *)sl.slots + (node * sl.Pb + (prof - sl.p0)) * FWD_STATE_Q;
 #pragma unroll
-      for (int j = 0; j < BP; j++) { const f4 v = src[j]; M[j] = (f2){v.x, v.y}; I[j] = (f2){v.z, v.w}; }
-#pragma unroll
-      for (int j = 0; j < BP / 2; j++) { const f4 v = src[BP + j]; D[2 * j] = (f2){v.x, v.y}; D[2 * j + 1] = (f2){v.z, v.w}; }
-      const f4 u = src[BP + BP / 2], t = src[BP + BP / 2 + 1];
-      D[BP - 1] = (f2){u.x, u.y}; xN = u.z; xJ = u.w; xC = t.x; xB = t.y;
-      totscale = __builtin_bit_cast(double, (f2){t.z, t.w});
+      for (int j = 0; j < BP; j++) { const f4 v = src[j]; S[j] = (f2){v.x, v.y}; Ip[j] = (f2){v.z, v.w}; }
+      const f4 u = src[BP], t = src[BP + 1];
+      xN = u.x; xJ = u.y; xC = u.z; xB = u.w;
+      totscale = __builtin_bit_cast(double, (f2){t.x, t.y});
     }
   }
   SeqStream ss; ss.open(sq, row0, +1);
@@ -195,28 +210,24 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_fwd_bound(FloatArgs a, int 
           const int64_t node = snode + __popcll(smask & ((1ull << d) - 1ull));
           f4 *dst = (f4 *)sl.slots + (node * sl.Pb + (prof - sl.p0)) * FWD_STATE_Q;
 #pragma unroll
-          for (int j = 0; j < BP; j++) dst[j] = (f4){M[j].x, M[j].y, I[j].x, I[j].y};
-#pragma unroll
-          for (int j = 0; j < BP / 2; j++) dst[BP + j] = (f4){D[2 * j].x, D[2 * j].y, D[2 * j + 1].x, D[2 * j + 1].y};
+          for (int j = 0; j < BP; j++) dst[j] = (f4){S[j].x, S[j].y, Ip[j].x, Ip[j].y};
           const f2 ts = __builtin_bit_cast(f2, totscale);
-          dst[BP + BP / 2] = (f4){D[BP - 1].x, D[BP - 1].y, xN, xJ};
-          dst[BP + BP / 2 + 1] = (f4){xC, xB, ts.x, ts.y};
+          dst[BP] = (f4){xN, xJ, xC, xB};
+          dst[BP + 1] = (f4){ts.x, ts.y, 0.f, 0.f};
         }
         if (d == jlev) {
-          // the join: every path crosses the cut after row d * B in exactly one of M_k, I_k, D_k, N, J, C, B -- the score is the inner
-          // product of the Forward state with the suffix's Backward state (same layout, dual units: k_bwd_bound), plus both scales
+          // the join: every path crosses the cut after row d * B in exactly one of S_k (a cell of row d B on its way to the next row's
+          // match cell M_k+1), I+_k (the next row's insert cell), N, J, C, B -- the score is the inner product of the Forward state with
+          // the suffix's Backward state (same layout, dual units: k_bwd_bound), plus both scales
           const f4 *g = (const f4 *)sl.gslots + (jnode * sl.Pb + (prof - sl.p0)) * FWD_STATE_Q;
           f2 sa = (f2){0.f, 0.f}, sb = (f2){0.f, 0.f};
 #pragma unroll
-          for (int j = 0; j < BP; j++) { const f4 v = g[j]; sa = pfma(M[j], (f2){v.x, v.y}, sa); sb = pfma(I[j], (f2){v.z, v.w}, sb); }
-#pragma unroll
-          for (int j = 0; j < BP / 2; j++) { const f4 v = g[BP + j]; sa = pfma(D[2 * j], (f2){v.x, v.y}, sa); sb = pfma(D[2 * j + 1], (f2){v.z, v.w}, sb); }
-          const f4 u = g[BP + BP / 2], t = g[BP + BP / 2 + 1];
-          sa = pfma(D[BP - 1], (f2){u.x, u.y}, sa);
-          sb = pfma((f2){xN, xJ}, (f2){u.z, u.w}, sb);
-          sa = pfma((f2){xC, xB}, (f2){t.x, t.y}, sa);
+          for (int j = 0; j < BP; j++) { const f4 v = g[j]; sa = pfma(S[j], (f2){v.x, v.y}, sa); sb = pfma(Ip[j], (f2){v.z, v.w}, sb); }
+          const f4 u = g[BP], t = g[BP + 1];
+          sb = pfma((f2){xN, xJ}, (f2){u.x, u.y}, sb);
+          sa = pfma((f2){xC, xB}, (f2){u.z, u.w}, sa);
           const float dot = (sa.x + sa.y) + (sb.x + sb.y);
-          const double gscale = __builtin_bit_cast(double, (f2){t.z, t.w});
+          const double gscale = __builtin_bit_cast(double, (f2){t.x, t.y});
           const bool jbad = (dot != dot) || (dot <= 0.0f) || (dot == __builtin_inff());
           const float sc = jbad ? __builtin_nanf("") : (float)(totscale + gscale + det_log((double)dot));
           fb[pi] = sc;
@@ -232,63 +243,47 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_fwd_bound(FloatArgs a, int 
       const float *tb = tab + opaque_zero();
       const f2 xBv = (f2){xB, xB};
       f2 acc = (f2){0.f, 0.f};
-      float sprev = 0.0f;                       // S of the node before the pair (S[0] = 0)
-      // pair 0's early half: S = what its nodes send to the next node's match cell (from the OLD row), and its new insert cells
       BT cur = ldbt(tb, 0);
       f2 ecur = *(const f2 *)(ex);
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      f2 Scur = pfma(M[0], cur.mm, pfma(I[0], cur.im, D[0] * cur.dm));
-      if constexpr (FOLD) I[0] = pfma(I[0], cur.ii, M[0]); else I[0] = pfma(M[0], cur.mi, I[0] * cur.ii);
       float dprev = 0.0f, mdprev = 0.0f;         // D'[2j] and M'[2j] t(M->D) (FOLD: M'[2j] itself) of the node before the pair (none before node 1)
-      f2 Sprev = (f2){0.f, 0.f};                 // S of the pair before (its second node feeds this pair's first; S[0] = 0)
-      f2 dlast = (f2){0.f, 0.f};                 // the pair before's new delete cells, not yet in the row's sum
-      cur = ldbt(tb, 1);
-      // One step = the late half of pair j (8 instructions, a chain: sh -> w -> mn -> md -> dn.y) and the early half of pair j + 1 (5,
-      // independent of it).  At two waves per SIMD an instruction that reads the result of the one before it costs a wait state that the
-      // other wave only half fills (profiles/round5_valu_issue.md: an s_nop holds the SIMD 0.9 ns at this occupancy; the compiler's own
-      // order had 4 per step, 11 % of the row).  The order is therefore fixed by hand -- every statement fenced -- so that no instruction
-      // follows its producer directly: the early half's instructions sit between the links of the chain, and the new delete cells go
-      // into the row's sum one step later.
+      float sprev = 0.0f;                        // the OLD row's S of the node before the pair (S[0] = 0)
+      f2 mnp = (f2){0.f, 0.f}, dnp = mnp;        // the new match and delete cells of the pair before: they live for one step
+      // One step = the chain of pair j (sh -> w -> mn -> dn.y: the new row's match and delete cells) and, between its links, what pair
+      // j - 1's new cells leave for the next row (S' and I+': 5 instructions, independent of the chain).  An instruction that reads the
+      // result of the one before it costs a wait state that the other waves only partly fill (profiles/round5_valu_issue.md), so the
+      // order is fixed by hand -- every statement fenced -- and no instruction follows its producer directly.  The old S of pair j - 1
+      // goes into sh before the new one is written.
 #define SB __builtin_amdgcn_sched_barrier(0)
 #pragma unroll
-      for (int j = 0; j < BP; j++) {
-        __builtin_amdgcn_s_waitcnt(0xC07F);     // lgkmcnt(0): record j + 1 and pair j's emissions, requested one step ago
-        const bool more = j + 1 < BP;
-        BT nxt = cur; f2 enxt = ecur;
-        if (more) { nxt = ldbt(tb, j + 2); enxt = *(const f2 *)(ex + 2 * (j + 1)); }
+      for (int j = 0; j <= BP; j++) {
+        __builtin_amdgcn_s_waitcnt(0xC07F);     // lgkmcnt(0): record j and pair j's emissions, requested one step ago
+        const bool chain = j < BP, fin = j > 0;
+        const BT c = cur; const f2 e = ecur;
+        if (chain) { cur = ldbt(tb, j + 1); if (j + 1 < BP) ecur = *(const f2 *)(ex + 2 * (j + 1)); }
         SB;
-        const f2 sh = (f2){Sprev.y, Scur.x}; SB;
-        f2 t = (f2){0.f, 0.f}, u = t, Sn = Scur;
-        if (more) { t = D[j + 1] * cur.dm; SB; }
-        // both new delete cells of the pair are born in this step (its old ones went into Scur one step ago): dd1 = D_2j -> D_2j+1 (0
-        // for j = 0), dd2 = D_2j+1 -> D_2j+2
+        f2 sh = (f2){0.f, 0.f}, t = sh, u = sh, w = sh, mn = sh, md = sh, dn = sh;
+        if (chain) { sh = (f2){sprev, S[j].x}; sprev = S[j].y; SB; }
+        if (fin) { t = Ip[j - 1] * c.im; SB; if constexpr (!FOLD) { u = Ip[j - 1] * c.ii; SB; } }
+        // both new delete cells of the pair are born in this step: dd1 = D_2j -> D_2j+1 (0 for j = 0), dd2 = D_2j+1 -> D_2j+2
         // (as inline assembly: left to itself the compiler accumulates into the dying product's register -- v_fmac -- and then
         // moves the result into the pair, twice per pair of nodes and row)
-        f2 dn;
-        asm("v_fma_f32 %0, %1, %2, %3" : "=v"(dn.x) : "v"(dprev), "s"(cur.dd1), "v"(mdprev)); SB;
-        const f2 w = pfma(xBv, cur.bm, sh); SB;
-        if (more) { t = pfma(I[j + 1], cur.im, t); SB; if constexpr (!FOLD) { u = I[j + 1] * cur.ii; SB; } }
-        const f2 mn = w * ecur; SB;
-        if (more) { Sn = pfma(M[j + 1], cur.mm, t); SB; }
+        if (chain) { asm("v_fma_f32 %0, %1, %2, %3" : "=v"(dn.x) : "v"(dprev), "s"(c.dd1), "v"(mdprev)); SB; }
+        if (chain) { w = pfma(xBv, c.bm, sh); SB; }
+        if (fin) { t = pfma(dnp, c.dm, t); SB; }
+        if (chain) { mn = w * e; SB; }
+        if (fin) { S[j - 1] = pfma(mnp, c.mm, t); SB; }
         if constexpr (FOLD) {
-          acc = acc + mn; SB;
-          if (more) { I[j + 1] = pfma(I[j + 1], cur.ii, M[j + 1]); SB; }      // (the insert cells divided by t(M_k -> I_k) / g_k)
-          asm("v_fma_f32 %0, %1, %2, %3" : "=v"(dn.y) : "v"(dn.x), "s"(cur.dd2), "v"(mn.x)); SB;
-          mdprev = mn.y;
+          if (chain) { acc = acc + mn; SB; }
+          if (fin) { Ip[j - 1] = pfma(Ip[j - 1], c.ii, mnp); SB; }             // (the insert cells divided by t(M_k -> I_k) / g_k)
+          if (chain) { asm("v_fma_f32 %0, %1, %2, %3" : "=v"(dn.y) : "v"(dn.x), "s"(c.dd2), "v"(mn.x)); SB; mdprev = mn.y; }
         } else {
-          const f2 md = mn * cur.md; SB;
-          acc = acc + mn; SB;
-          if (more) { I[j + 1] = pfma(M[j + 1], cur.mi, u); SB; }
-          acc = acc + dlast; SB;
-          asm("v_fma_f32 %0, %1, %2, %3" : "=v"(dn.y) : "v"(dn.x), "s"(cur.dd2), "v"(md.x)); SB;
-          mdprev = md.y; dlast = dn;
+          if (chain) { md = mn * c.md; SB; acc = acc + mn; SB; }
+          if (fin) { Ip[j - 1] = pfma(mnp, c.mi, u); SB; acc = acc + dnp; SB; }
+          if (chain) { asm("v_fma_f32 %0, %1, %2, %3" : "=v"(dn.y) : "v"(dn.x), "s"(c.dd2), "v"(md.x)); SB; mdprev = md.y; }
         }
-        M[j] = mn; D[j] = dn;
-        dprev = dn.y;
-        Sprev = Scur; Scur = Sn; cur = nxt; ecur = enxt;
+        mnp = mn; dnp = dn; dprev = dn.y;
       }
 #undef SB
-      if constexpr (!FOLD) acc = acc + dlast;
       xE = acc.x + acc.y;
       xN = xN * ploop;
       xC = __builtin_fmaf(xC, ploop, xE * 0.5f);
@@ -301,7 +296,7 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_fwd_bound(FloatArgs a, int 
         xN *= r; xC *= r; xJ *= r; xB *= r;
         const f2 rv = (f2){r, r};
 #pragma unroll
-        for (int j = 0; j < BP; j++) { M[j] = M[j] * rv; I[j] = I[j] * rv; D[j] = D[j] * rv; }
+        for (int j = 0; j < BP; j++) { S[j] = S[j] * rv; Ip[j] = Ip[j] * rv; }
         totscale += det_log((double)xE);
         xE = 1.0f;
       }
@@ -317,12 +312,16 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_fwd_bound(FloatArgs a, int 
 
 // =========================================================================================
 // Round 6, two-sided sharing: the BACKWARD half of pass A's sum over paths.  One Forward row is a linear map of the row state
-// (M~, I^, D^ of 46 nodes, N, J, C, B: k_fwd_bound's folded units); the score is a linear functional of the last row's state (C times
+// (S, I+ of 46 nodes, N, J, C, B: k_fwd_bound's folded units); the score is a linear functional of the last row's state (C times
 // the move out).  Pulled back through the rows L, L - 1, ..., j B + 1 -- the TRANSPOSED maps, applied in that order -- it becomes a
 // vector gamma_j with   score = < Forward state after row j B, gamma_j >   for EVERY prefix, and gamma_j depends on the profile, the
 // target's length and the residues after row j B only: the uniques of one length that end alike share it.  This kernel walks a
 // Backward chain (lane = chain x profile, wave = 64 chains of one (batch, blocks-from-the-end) segment) and saves gamma at the block
-// boundaries where somebody joins (k_share.hip: k_join_*), in k_fwd_bound's state layout, so that the join is 72 packed multiply-adds.
+// boundaries where somebody joins (k_share.hip: k_join_*), in k_fwd_bound's state layout, so that the join is 48 packed multiply-adds.
+// What it carries is the dual of Forward's (S, I+): W_k = w_k+1 of the last row pulled back, the adjoint of S_k, and G_k, the adjoint of
+// I+_k -- the gI that row was entered with; the adjoints of the row's own cells are formed from them on the fly:
+//     gM_k = mm_k W_k + G_k,   gD_k = dm_k W_k,   G_k <- im_k W_k + ii_k G_k,   W_k <- w_k+1
+//     score = sum_k S_k W_k + sum_k I+_k G_k + N gN + J gJ + C gC + B gB        (plus both scale logarithms)
 // The transposed row, with a' = adjoint of the new row's cell and x the row's residue:
 //     nJ = gJ + move gB,  nN = gN + move gB,  aE = (nJ + gC) / 2
 //     aD_k = gD_k + dd_k aD_k+1,   aM_k = gM_k + aE + aD_k+1,   w_k = e_k(x) aM_k                  (k = 46 .. 1, aD_47 = w_47 = 0)
@@ -330,8 +329,8 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_fwd_bound(FloatArgs a, int 
 //     gN <- loop nN,  gJ <- loop nJ,  gC <- loop gC
 // (the same table entries as the Forward kernel's, by pair of nodes: engine.hip builds rtab).  The cells are kept below ~1e6 by a sum test
 // every 16 rows (block boundaries are multiples of 16), the scale's logarithm travels with the state like Forward's.
-// record j of the table (engine.hip: install_profiles): mm im dm bm of pair j, then ii and dd (aa) of pair j - 1 -- what ONE step of the
-// row loop below reads: the late half of pair j and the early half of pair j - 1
+// record j of the table (engine.hip: install_profiles): bm of pair j; mm im dm, ii and dd (aa) of pair j - 1 -- what ONE step of the
+// row loop below reads: the late half of pair j and the early half of pair j - 1 (record BP: the last pair's early half alone)
 struct RT { f2 mm, im, dm, bm, ii, aa; };
 DEV RT ldrt(const float *tab, int j)
 {
@@ -340,7 +339,7 @@ DEV RT ldrt(const float *tab, int j)
   t.mm = (f2){a.x, a.y}; t.im = (f2){a.z, a.w}; t.dm = (f2){b.x, b.y}; t.bm = (f2){b.z, b.w}; t.ii = (f2){c.x, c.y}; t.aa = (f2){c.z, c.w};
   return t;
 }
-__global__ void __launch_bounds__(64 * FWD_WPB, 2) k_bwd_bound(FloatArgs a, int wave0, int nwaves, const float *__restrict__ btab, const float *__restrict__ rtab, ShareLaunch sl)
+__global__ void __launch_bounds__(64 * FWD_WPB) BOUND_OCC k_bwd_bound(FloatArgs a, int wave0, int nwaves, const float *__restrict__ btab, const float *__restrict__ rtab, ShareLaunch sl)
 {
   const int wv = threadIdx.x >> 6, widx = blockIdx.x * FWD_WPB + wv;
   WaveDesc wd = a.waves[wave0 + min(widx, nwaves - 1)];
@@ -365,12 +364,12 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_bwd_bound(FloatArgs a, int 
   }
   Seq sq; sq.w = a.rd.words + cr.woff; sq.exc = a.rd.exc + cr.excoff; sq.nexc = cr.nexc; sq.L = cr.L;
   const int nsteps = (sl.dbg & 32) ? 0 : wave_max(active ? cr.endrow : 0);         // the wave's longest chain (no lane: no step)
-  f2 M[BP], I[BP], D[BP];
+  f2 W[BP], G[BP];
 #pragma unroll
-  for (int j = 0; j < BP; j++) { M[j] = (f2){0.f, 0.f}; I[j] = (f2){0.f, 0.f}; D[j] = (f2){0.f, 0.f}; }
+  for (int j = 0; j < BP; j++) { W[j] = (f2){0.f, 0.f}; G[j] = (f2){0.f, 0.f}; }
   const float pmove = (2.0f + 1.0f) / ((float)L + 2.0f + 1.0f);
   const float ploop = 1.0f - pmove;
-  float xN = 0.f, xJ = 0.f, xB = 0.f, xC = pmove;             // gamma after the last row: the score is C times the move out
+  float xN = 0.f, xJ = 0.f, xB = 0.f, xC = pmove;            // gamma after the last row: the score is C times the move out
   double totscale = 0.0;
   const int kb = pr.useq;
   const int rd = sl.depth;                                    // blocks from the end the launch's chains start at (wave-uniform)
@@ -381,14 +380,12 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_bwd_bound(FloatArgs a, int 
     const int64_t node = (int64_t)cr.src - sl.node_base;
     const f4 *src = (const f4 *)sl.slots + (node * sl.Pb + (prof - sl.p0)) * FWD_STATE_Q;
 #pragma unroll
-    for (int j = 0; j < BP; j++) { const f4 v = src[j]; M[j] = (f2){v.x, v.y}; I[j] = (f2){v.z, v.w}; }
-#pragma unroll
-    for (int j = 0; j < BP / 2; j++) { const f4 v = src[BP + j]; D[2 * j] = (f2){v.x, v.y}; D[2 * j + 1] = (f2){v.z, v.w}; }
-    const f4 u = src[BP + BP / 2], t = src[BP + BP / 2 + 1];
-    D[BP - 1] = (f2){u.x, u.y}; xN = u.z; xJ = u.w; xC = t.x; xB = t.y;
-    totscale = __builtin_bit_cast(double, (f2){t.z, t.w});
+    for (int j = 0; j < BP; j++) { const f4 v = src[j]; W[j] = (f2){v.x, v.y}; G[j] = (f2){v.z, v.w}; }
+    const f4 u = src[BP], t = src[BP + 1];
+    xN = u.x; xJ = u.y; xC = u.z; xB = u.w;
+    totscale = __builtin_bit_cast(double, (f2){t.x, t.y});
   }
-  const int A = (L + (1 << sl.logB) - 1) >> sl.logB;
+  const int A =(L + (1 << sl.logB) - 1) >> sl.logB;
   const int top = (A - rd) << sl.logB;                        // the row the chain's state stands after (virtual when rd = 0 and L is no multiple of B)
   const int first = top < L ? top : L;
   SeqStream ss; ss.open(sq, first > 0 ? first - 1 : 0, -1);
@@ -401,12 +398,10 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_bwd_bound(FloatArgs a, int 
         const int64_t node = snode + __popcll(smask & ((1ull << rdl) - 1ull));
         f4 *dst = (f4 *)sl.slots + (node * sl.Pb + (prof - sl.p0)) * FWD_STATE_Q;
 #pragma unroll
-        for (int j = 0; j < BP; j++) dst[j] = (f4){M[j].x, M[j].y, I[j].x, I[j].y};
-#pragma unroll
-        for (int j = 0; j < BP / 2; j++) dst[BP + j] = (f4){D[2 * j].x, D[2 * j].y, D[2 * j + 1].x, D[2 * j + 1].y};
+        for (int j = 0; j < BP; j++) dst[j] = (f4){W[j].x, W[j].y, G[j].x, G[j].y};
         const f2 ts = __builtin_bit_cast(f2, totscale);
-        dst[BP + BP / 2] = (f4){D[BP - 1].x, D[BP - 1].y, xN, xJ};
-        dst[BP + BP / 2 + 1] = (f4){xC, xB, ts.x, ts.y};
+        dst[BP] = (f4){xN, xJ, xC, xB};
+        dst[BP + 1] = (f4){ts.x, ts.y, 0.f, 0.f};
       }
     }
     if (step >= nsteps) break;
@@ -422,45 +417,37 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_bwd_bound(FloatArgs a, int 
       const f2 aEv = (f2){aE, aE};
       float aDn = 0.0f, wn = 0.0f;                            // aD and w of the node after the pair
       f2 accB = (f2){0.f, 0.f};
-      // One step = the LATE half of pair j (w = e aM, its share of B, the new M I D of the pair: a chain w -> wsh -> cells) and the EARLY half
-      // of pair j - 1 (its aD chain -- two dependent multiply-adds --, aM, ii I), statement by statement in a fixed order so that no
+      // One step = the LATE half of pair j (w = e aM, its share of B, the pair's new W) and the EARLY half of pair j - 1 (gD, gM and the new
+      // G from its W and G, its aD chain -- two dependent multiply-adds --, aM), statement by statement in a fixed order so that no
       // instruction reads the result of the one before it (at two waves per SIMD that costs a wait state the other wave only half fills:
       // the compiler's own order ran at 0.87 ns per wave-row against the Forward step's 0.56); the step's table record (engine.hip: what
       // both halves read, 12 floats) and emission odds are requested one step ahead, as in the Forward step.
 #define SB __builtin_amdgcn_sched_barrier(0)
-      const f4 tl = *(cf4q)(uintptr_t)(tb + BP * 12);         // ii, dd of the last pair
-      RT cur = ldrt(tb, BP - 1);
-      f2 ecur = *(const f2 *)(ex + 2 * (BP - 1));
-      // the early half of the last pair (no node after it: aDn = 0)
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      float aD2 = __builtin_fmaf(tl.w, aDn, D[BP - 1].y);
-      f2 pre = M[BP - 1] + aEv;
-      float aD1 = __builtin_fmaf(tl.z, aD2, D[BP - 1].x);
-      f2 iig = (f2){tl.x, tl.y} * I[BP - 1];
-      f2 aM = pre + (f2){aD2, aDn};
-      aDn = aD1;
+      RT cur = ldrt(tb, BP);                                  // mm im dm ii dd of the last pair
+      f2 ecur = (f2){0.f, 0.f};
+      f2 aM = (f2){0.f, 0.f};
 #pragma unroll
-      for (int j = BP - 1; j >= 0; j--) {
+      for (int j = BP; j >= 0; j--) {
         __builtin_amdgcn_s_waitcnt(0xC07F);                   // lgkmcnt(0): step j's record and pair j's emissions, requested one step ago
         const RT t = cur;
         const f2 e = ecur;
-        const bool more = j > 0;
+        const bool late = j < BP, more = j > 0;
         if (more) { cur = ldrt(tb, j - 1); ecur = *(const f2 *)(ex + 2 * (j - 1)); }
         SB;
-        const f2 w = aM * e; SB;
-        float aD2n = 0.f, aD1n = 0.f; f2 pren = (f2){0.f, 0.f}, iign = pren, aMn = pren;
-        if (more) { aD2n = __builtin_fmaf(t.aa.y, aDn, D[j - 1].y); SB; }
-        accB = pfma(t.bm, w, accB); SB;
-        if (more) { pren = M[j - 1] + aEv; SB; }
-        const f2 wsh = (f2){w.y, wn}; SB;                     // w of the node after each of the pair's two
-        if (more) { aD1n = __builtin_fmaf(t.aa.x, aD2n, D[j - 1].x); SB; }
-        const f2 gi = I[j];
-        M[j] = pfma(t.mm, wsh, gi); SB;
-        if (more) { iign = t.ii * I[j - 1]; SB; }
-        I[j] = pfma(t.im, wsh, iig); SB;
-        if (more) { aMn = pren + (f2){aD2n, aDn}; SB; }
-        D[j] = t.dm * wsh; SB;
-        wn = w.x; aDn = aD1n; aM = aMn; iig = iign;
+        f2 w = (f2){0.f, 0.f}, gD = w, pren = w, gMp = w, iig = w, aMn = w;
+        float aD2n = 0.f, aD1n = 0.f;
+        if (late) { w = aM * e; SB; }
+        if (more) { gD = t.dm * W[j - 1]; SB; }               // the adjoints of the row's cells, from (W, G): gD = dm W, gM = mm W + G
+        if (late) { accB = pfma(t.bm, w, accB); SB; }
+        if (more) { pren = G[j - 1] + aEv; SB; }
+        if (more) { aD2n = __builtin_fmaf(t.aa.y, aDn, gD.y); SB; }
+        if (late) { W[j] = (f2){w.y, wn}; SB; }               // w of the node after each of the pair's two (the old W[j] was read one step ago)
+        if (more) { gMp = pfma(t.mm, W[j - 1], pren); SB; }   // gM + aE
+        if (more) { aD1n = __builtin_fmaf(t.aa.x, aD2n, gD.x); SB; }
+        if (more) { iig = t.ii * G[j - 1]; SB; }
+        if (more) { aMn = gMp + (f2){aD2n, aDn}; SB; }
+        if (more) { G[j - 1] = pfma(t.im, W[j - 1], iig); SB; }
+        wn = w.x; aDn = aD1n; aM = aMn;
       }
 #undef SB
       xB = accB.x + accB.y;
@@ -469,13 +456,13 @@ __global__ void __launch_bounds__(64 * FWD_WPB, 2) k_bwd_bound(FloatArgs a, int 
     if ((step & 15) == 15) {
       f2 sm = (f2){0.f, 0.f};
 #pragma unroll
-      for (int j = 0; j < BP; j++) sm = sm + ((M[j] + I[j]) + D[j]);
+      for (int j = 0; j < BP; j++) sm = sm + (W[j] + G[j]);
       const float tot = (sm.x + sm.y) + ((xN + xJ) + (xC + xB));
       if (tot > 1e6f || (tot < 1e-6f && tot > 0.0f)) {
         const float r = 1.0f / tot;
         const f2 rv = (f2){r, r};
 #pragma unroll
-        for (int j = 0; j < BP; j++) { M[j] = M[j] * rv; I[j] = I[j] * rv; D[j] = D[j] * rv; }
+        for (int j = 0; j < BP; j++) { W[j] = W[j] * rv; G[j] = G[j] * rv; }
         xN *= r; xJ *= r; xC *= r; xB *= r;
         totscale += det_log((double)tot);
       }
@@ -492,8 +479,10 @@ void launch_bwd_bound_share(const FloatArgs &a, const float *btab, const float *
 // 1e20 by default (ITSX_BOUND_RESCALE_EXP: another power of ten, for A/B; at most 28 -- the folded cells must stay inside float)
 static float bound_rescale()
 {
-  static const float v = [] { const char *e = sw_get("ITSX_BOUND_RESCALE_EXP"); const double x = e ? atof(e) : 20.0; return (float)pow(10.0, x < 4.0 ? 4.0 : x > 28.0 ? 28.0 : x); }();
-  return v;
+  // (read at every launch: a process can run an A/B of it)
+  const char *e = sw_get("ITSX_BOUND_RESCALE_EXP");
+  const double x = e ? atof(e) : 20.0;
+  return (float)pow(10.0, x < 4.0 ? 4.0 : x > 28.0 ? 28.0 : x);
 }
 void launch_fwd_bound_seq(const FloatArgs &a, const float *btab, bool fold, float *fb, int nwaves, int wave0, hipStream_t st)
 {

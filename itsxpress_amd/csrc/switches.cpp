@@ -43,6 +43,7 @@ static const Switch g_sw[] = {
   {"ITSX_MSV_TWO", SW_TUNING, "=0: the MSV filter keeps the one-sided (prefix-only) schedule when pass A shares two-sidedly"},
   {"ITSX_SHARE_B", SW_TUNING, "rows per block of the prefix / suffix trees (default 32)"},
   {"ITSX_SHARE_GB", SW_TUNING, "budget of the saved row states, GB"},
+  {"ITSX_SHARE_DIV", SW_TUNING, "the saved row states' budget is all of a search's states divided by this (default 3.8: four batches; 2.8: three)"},
   {"ITSX_SHARE_MIN", SW_TUNING, "smallest shared-row fraction for which the shared schedule is used (default 0.10)"},
   {"ITSX_SHARE_FWD_STREAMS", SW_TUNING, "1 | 2 streams for pass A's batches"},
   {"ITSX_SHARE_MSV_STREAMS", SW_TUNING, "1 | 2 streams for the MSV filter's batches"},
