@@ -478,6 +478,53 @@ int itsx_keep_records(itsx_ctx *ctx, int on);
 int itsx_write_trimmed_samples(itsx_ctx *ctx, const char *const *out_paths, int32_t n_samples, int compression, int trim_ccs,
                                const char *left_prefix, const char *right_prefix, const int32_t *start, const int32_t *stop,
                                int64_t *n_written_per_sample, int64_t *total_len_per_sample);
+/* ---- the feature table of the trimmed regions (a new call after the search; nothing else changes).  What a user of amplicon data
+ * does next with the trimmed FASTQ files of all samples: `vsearch --derep_fulllength --sizeout --relabel_sha1` behind QIIME 2's
+ * dereplicate-sequences -- a table of distinct trimmed sequences by samples plus one FASTA of representatives, the input of the
+ * OTU-clustering workflows.  The reference stops at the trimmed FASTQ: these calls have no reference call site.
+ * itsx_trimmed_table builds the table from what the context holds (packed reads, coordinates, samples; csrc/k_ftable.hip):
+ *   counted: read i contributes iff the trimmed-FASTQ writer would write it and its slice is not empty: start[i] >= 0, stop[i] >= 0,
+ *     start[i] < stop[i] and min(stop[i], len[i]) - start[i] >= min_len (min_len >= 1; the usual value is 1).
+ *   bases: the read's own bases [start, min(stop, len)) as the packed read set holds them: upper case, U is T, IUPAC symbols kept
+ *     (N and A differ).  No trim_ccs stitching.
+ *   feature: two counted reads are one feature iff those sequences are equal symbol for symbol (forward strand only: trimmed regions
+ *     are oriented; a sequence that is a prefix of another is another feature).  count[f][s] = counted reads of sample s with
+ *     feature f (one column without itsx_set_samples).
+ *   order: descending total count, ties by the smaller index of the feature's first read in read-set order; that read is the feature's
+ *     representative.  This rule is the project's own (vsearch's order among equal sizes is not pinned against it).
+ *   coordinates: either left_prefix / right_prefix (the finalized search's per-read coordinates, taken where they lie on the device, as
+ *     itsx_trim_coords_device gives them) or start / stop [n_reads] from the caller -- exactly one of the two.
+ *   *n_features, *n_entries (non-zero cells of the table), *n_counted (reads counted), *ms_kernels (device time of the call, by
+ *     events; itsx_stats does not grow for it): each may be NULL.
+ *   The table stays in the context until the next itsx_trimmed_table or the next call that makes a read set.
+ *   ITSX_E_ARG: both, neither or half a coordinate source, prefixes before itsx_search_finalize, min_len < 1, no reads loaded.
+ *   Limits: one context (one GPU), a whole-file read set (not a streamed chunk), forward strand only, no trim_ccs stitching. */
+int itsx_trimmed_table(itsx_ctx *ctx, const char *left_prefix, const char *right_prefix, const int32_t *start, const int32_t *stop,
+                       int32_t min_len, int64_t *n_features, int64_t *n_entries, int64_t *n_counted, float *ms_kernels);
+/* the table of the last itsx_trimmed_table, features in table order: feat_len / feat_total / feat_first_read [n_features]; the cells as
+ * CSR rows: feature f's entries are [row_off[f], row_off[f + 1]) of entry_sample / entry_count [n_entries], samples ascending;
+ * row_off [n_features + 1].  Any pointer may be NULL.  ITSX_E_ARG: no table (none made, or a new read set dropped it). */
+int itsx_trimmed_table_get(itsx_ctx *ctx, int32_t *feat_len, int32_t *feat_total, int32_t *feat_first_read, int64_t *row_off,
+                           int32_t *entry_sample, int32_t *entry_count);
+/* feature_of_read [n_reads]: every read's feature (its row of the table), -1 for a read that is not counted */
+int itsx_trimmed_table_reads(itsx_ctx *ctx, int32_t *feature_of_read);
+/* the features' sequences, feature f's at bases[offsets[f], offsets[f + 1]) (no terminators); offsets [n_features + 1].  bases == NULL
+ * fills offsets only (offsets[n_features] = the bytes bases needs); offsets may be NULL. */
+int itsx_trimmed_table_seqs(itsx_ctx *ctx, char *bases, int64_t *offsets);
+/* The two files of a feature table, from the arrays above (host only, no context, like itsx_write_trimmed_fastq; no reference call
+ * site).  fasta_path: per feature `>label;size=total` and the sequence on one line (vsearch --sizeout's header).  tsv_path: a first
+ * line `#feature`, a TAB and the TAB-joined sample names, then per feature, in table order, its label and its n_samples counts.
+ * Either path may be NULL.
+ * labels / label_offsets: feature f's label at labels[label_offsets[f], label_offsets[f + 1]); NULL: the id of the feature's first read --
+ *   read_names[read_name_offsets[r], ...) up to the first blank or TAB -- or r%09d of that read's index where read_names is NULL.
+ * sample_names / sample_name_offsets: likewise; NULL: s%d.
+ * ITSX_E_ARG: missing arrays, an entry's sample outside [0, n_samples).  ITSX_E_IO: a file could not be written whole (it is removed,
+ * never left short; a FASTA already written stays); itsx_writers_last_error() has the text. */
+int itsx_write_feature_files(const char *fasta_path, const char *tsv_path, int64_t n_features, int32_t n_samples, const int32_t *feat_total,
+                             const int32_t *feat_first_read, const int64_t *row_off, const int32_t *entry_sample, const int32_t *entry_count,
+                             const char *bases, const int64_t *offsets, const char *labels, const int64_t *label_offsets,
+                             const char *read_names, const int64_t *read_name_offsets, const char *sample_names,
+                             const int64_t *sample_name_offsets);
 /* ---- a merged read set that keeps its ORIGINAL pairs (opt-in; off by default; independent of itsx_keep_records).  While on,
  * itsx_merge_pairs_load and itsx_merge_pairs_load_files also keep, in device memory beside the merged read set, every pair's R1 and
  * R2 record: the bases and qualities as the merge kernel read them (its own upload, taken over instead of freed), both whole title lines ('@' and any comment included, no CR), and per pair the merged read whose

@@ -112,7 +112,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_topup_counters",
            "itsx_orient_profiles", "itsx_orient_profiles_apply",
            "itsx_twriter_strands", "itsx_write_trimmed_fastq_strands",
-           "itsx_set_merge_join", "itsx_merge_join_info", "itsx_merge_buffers_join"]
+           "itsx_set_merge_join", "itsx_merge_join_info", "itsx_merge_buffers_join",
+           "itsx_trimmed_table", "itsx_trimmed_table_get", "itsx_trimmed_table_reads", "itsx_trimmed_table_seqs", "itsx_write_feature_files"]
 
 
 def lib():
@@ -178,6 +179,11 @@ def lib():
         "itsx_set_kept_rows": (i32, [vp, i32]),
         "itsx_keep_records": (i32, [vp, i32]),
         "itsx_write_trimmed_samples": (i32, [vp, vp, i32, i32, i32, cp, cp, vp, vp, vp, vp]),
+        "itsx_trimmed_table": (i32, [vp, cp, cp, vp, vp, i32, vp, vp, vp, vp]),
+        "itsx_trimmed_table_get": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+        "itsx_trimmed_table_reads": (i32, [vp, vp]),
+        "itsx_trimmed_table_seqs": (i32, [vp, vp, vp]),
+        "itsx_write_feature_files": (i32, [cp, cp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "itsx_keep_pair_records": (i32, [vp, i32]),
         "itsx_write_trimmed_paired_samples": (i32, [vp, vp, vp, i32, i32, i32, cp, cp, vp, vp, vp, vp]),
         "itsx_deflate_block_bytes": (i64, []),

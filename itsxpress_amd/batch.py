@@ -408,6 +408,54 @@ class SampleBatch:
     def _sample_range(self, i: int):
         return int(self.first[i]), int(self.first[i] + self.counts[i])
 
+    # -- the feature table of the trimmed regions ------------------------------------------------
+    def feature_table(self, region: str, min_len: int = 1, ids: str = "sha1"):
+        """The batch's trimmed `region` dereplicated over all samples (Engine.trimmed_table with the region's profile prefixes): the
+        table `vsearch --derep_fulllength --sizeout --relabel_sha1` makes of the files write_trimmed writes, without writing them.
+        Returns the engine's FeatureTable with `labels` added: ids="sha1" names a feature by the SHA-1 of its sequence, ids="first" by
+        the id of its first read.  Needs the finalized search (_search); one GPU, whole-file read sets, forward strand, no trim_ccs
+        stitching."""
+        if ids not in ("sha1", "first"):
+            raise ValueError('ids is "sha1" or "first"')
+        t = self.engine.trimmed_table(region_prefixes=_REGION_PREFIX[region], min_len=min_len)
+        if ids == "sha1":
+            import hashlib
+            t.labels = [hashlib.sha1(s.encode()).hexdigest() for s in t.sequences]
+        else:
+            blob, offs = self.engine.read_names_raw()
+            t.labels = [blob[int(offs[r]):int(offs[r + 1])].decode().split(None, 1)[0] if offs[r + 1] > offs[r] else "r%09d" % r
+                        for r in t.first_read]
+        return t
+
+    def write_feature_table(self, fasta: Optional[str], tsv: Optional[str], region: str, min_len: int = 1, ids: str = "sha1",
+                            sample_names: Optional[Sequence[str]] = None):
+        """feature_table(region) written as two files (either may be None): `fasta` holds `>label;size=total` and the sequence per
+        feature, `tsv` a `#feature` header line with the sample names and one line of counts per feature, both in table order.
+        sample_names default to the basename of each sample's input file.  Returns the table."""
+        from . import _lib
+        import ctypes as C
+        t = self.feature_table(region, min_len=min_len, ids=ids)
+        if sample_names is None:
+            sample_names = [os.path.basename(getattr(s, "fastq", None) or getattr(s, "r1", None) or s.seq_file) for s in self.samples]
+        sample_names = [str(x) for x in sample_names]
+        if len(sample_names) != t.n_samples:
+            raise ValueError("write_feature_table: %d sample names for %d sample(s)" % (len(sample_names), t.n_samples))
+
+        def blob_of(names):
+            enc = [x.encode() for x in names]
+            return b"".join(enc), np.concatenate([[0], np.cumsum([len(x) for x in enc])]).astype(np.int64)
+        lab, lab_off = blob_of(t.labels)
+        sn, sn_off = blob_of(sample_names)
+        pad = lambda x: x.ctypes.data if x.size else None
+        L = _lib.lib()
+        rc = L.itsx_write_feature_files(None if fasta is None else os.fsencode(fasta), None if tsv is None else os.fsencode(tsv),
+                                        t.n_features, t.n_samples, pad(t.totals), pad(t.first_read), t.row_off.ctypes.data,
+                                        pad(t.entry_sample), pad(t.entry_count), C.c_char_p(t.bases), t.seq_off.ctypes.data,
+                                        C.c_char_p(lab), lab_off.ctypes.data, None, None, C.c_char_p(sn), sn_off.ctypes.data)
+        if rc != 0:
+            raise EngineError(rc, L.itsx_writers_last_error().decode())
+        return t
+
     def write_paired_trimmed(self, outfiles1: Sequence[str], outfiles2: Sequence[str], region: str, gzipped: bool = False,
                              zstd_file: bool = False, trim_ccs: bool = False) -> List[int]:
         """`Dedup.create_paired_trimmed_seqs` of every sample from the batch's arrays: the ORIGINAL r1 / fastq2 records of sample i,

@@ -534,6 +534,15 @@ struct itsx_ctx {
   } prec;
   DBuf<TrimRec> w_trec2; DBuf<int32_t> w_ttlen;          // itsx_write_trimmed_paired_samples (beside the buffers below)
   DBuf<TrimRec> w_trec; DBuf<int64_t> w_tcnt, w_ttot, w_tblk, w_tfirst, w_tbounds; DBuf<int32_t> w_tstart, w_tstop; DBuf<uint32_t> w_tout;   // itsx_write_trimmed_samples
+  // ---- the feature table of the trimmed regions (itsx_trimmed_table; k_ftable.hip): the last call's table in its order, kept until the next
+  // call or the next read set (the sequences were cut from this read set's words); the rest is that call's scratch
+  struct FeatureTable {
+    bool have = false; int64_t n = 0, nc = 0; int32_t F = 0, E = 0; int64_t text_bytes = 0;
+    DBuf<int32_t> feat_len, feat_total, feat_first, row_off, entry_sample, entry_count, feature_of_read; DBuf<uint32_t> text; std::vector<int64_t> h_seq_off;
+    DBuf<int32_t> start, stop, vals, feature_read, ehead, epos, fhead, fpos, ent_start, ent_sample, ent_feat, f_ent0, f_pos0, f_first, hold_f, ovals, ovals2,
+        rank_of, nent, scan;
+    DBuf<unsigned long long> keys, counters, pair_keys, pair_sorted, okeys, okeys2; DBuf<uint64_t> hash; DBuf<uint32_t> slot_of; DBuf<int64_t> seq_off; DBuf<uint8_t> sort_tmp;
+  } ft;
   DBuf<DeflateBlock> w_dblk; DBuf<uint32_t> w_dtok, w_dtext; DBuf<uint8_t> w_dslots, w_dpacked; DBuf<int32_t> w_dsizes; DBuf<int64_t> w_ddst;   // deflate_ranges
   // a streamed writer's device path (twdev_*, for itsx_twriter_set_device): a unit's raw text, its line index and the plan's scratch
   // (records, output text and deflate scratch are the batch writers' buffers above); tw_mu serialises the writers that share the context
@@ -971,6 +980,7 @@ static int pack_and_upload(itsx_ctx *ctx, const char *view = nullptr, const uint
 {
   init_codes();
   ctx->rec.drop(); ctx->prec.drop();                     // a new read set: whoever keeps records installs them after this
+  ctx->ft.have = false;
   const auto tp0 = std::chrono::steady_clock::now();
   const int64_t n = ctx->N;
   ctx->dev_bases = dev_raw;
@@ -5151,6 +5161,7 @@ static int orient_apply_strands(itsx_ctx *ctx, const std::vector<int8_t> &hs, DB
   if (S > 1) ctx->h_sample.swap(smp);
   ctx->h_bases.swap(text); ctx->bases_view = ctx->h_bases.data();
   ctx->prec.drop();                                      // the pairs' map named the reads that were
+  ctx->ft.have = false;
   if (records) {
     itsx_ctx::Records &rr = ctx->rec;
     dbuf_swap(rr.seq, r_seq); dbuf_swap(rr.qual, r_qual); dbuf_swap(rr.titles, r_titles); dbuf_swap(rr.off, r_off); dbuf_swap(rr.toff, r_toff);
@@ -6180,6 +6191,152 @@ int itsx_write_trimmed_samples(itsx_ctx *ctx, const char *const *out_paths, int3
     if (total_len_per_sample) total_len_per_sample[s] = bt[s + 1] - bt[s];
   }
   return ITSX_OK;
+}
+// ------------------------------------------------------------------------------ the feature table of the trimmed regions (k_ftable.hip)
+// Distinct trimmed sequences by samples, from the packed reads, the coordinates and the samples the context holds: what a user makes of
+// the trimmed FASTQ files with `vsearch --derep_fulllength --sizeout`.  The table stays in the context (ctx->ft) for the getters below.
+int itsx_trimmed_table(itsx_ctx *ctx, const char *left_prefix, const char *right_prefix, const int32_t *start, const int32_t *stop, int32_t min_len,
+                       int64_t *n_features, int64_t *n_entries, int64_t *n_counted, float *ms_kernels)
+{
+  CTXCHK(ctx);
+  const bool by_prefix = left_prefix || right_prefix, by_arrays = start || stop;
+  if (by_prefix == by_arrays || (by_prefix && !(left_prefix && right_prefix)) || (by_arrays && !(start && stop)))
+    SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table: give either left_prefix and right_prefix or start and stop");
+  if (min_len < 1) SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table: min_len must be at least 1, not " + std::to_string(min_len));
+  if (!ctx->rd.woff || ctx->N <= 0) SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table called before a read set is loaded");
+  if (by_prefix && !ctx->have_final) SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table: prefixes given before itsx_search_finalize");
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  itsx_ctx::FeatureTable &t = ctx->ft;
+  t.have = false;
+  const int64_t n = ctx->N;
+  HIPCHK(t.start.alloc((size_t)n)); HIPCHK(t.stop.alloc((size_t)n));
+  const int32_t *src_start = nullptr, *src_stop = nullptr; int32_t stride = 1;
+  if (by_prefix) {
+    int32_t *rows = nullptr; int64_t nrows = 0;
+    const int rc = coords_device(ctx, left_prefix, right_prefix, true, &rows, &nrows);
+    if (rc != ITSX_OK) return rc;
+    src_start = rows; src_stop = rows + 1; stride = 4;
+  }
+  StageTimer tm(st);
+  if (by_prefix) launch_ft_coords(src_start, src_stop, stride, n, t.start.p, t.stop.p, st);
+  else { HIPCHK(hipMemcpyAsync(t.start.p, start, (size_t)n * 4, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(t.stop.p, stop, (size_t)n * 4, hipMemcpyHostToDevice, st)); }
+  // ---- 1 + 2: the table (a power of two, at least 2 n slots: never more than half full), and the exact verification
+  uint64_t tsize = 1024; while (tsize < 2 * (uint64_t)n) tsize <<= 1;
+  HIPCHK(t.keys.alloc((size_t)tsize)); HIPCHK(t.vals.alloc((size_t)tsize)); HIPCHK(t.hash.alloc((size_t)n)); HIPCHK(t.slot_of.alloc((size_t)n));
+  HIPCHK(t.feature_read.alloc((size_t)n)); HIPCHK(t.counters.alloc(2)); HIPCHK(t.feature_of_read.alloc((size_t)n));
+  HIPCHK(hipMemsetAsync(t.keys.p, 0, (size_t)tsize * 8, st)); HIPCHK(hipMemsetAsync(t.vals.p, 0x7f, (size_t)tsize * 4, st));
+  HIPCHK(hipMemsetAsync(t.counters.p, 0, 16, st));
+  FtArgs a{};
+  a.rd = ctx->rd; a.start = t.start.p; a.stop = t.stop.p; a.min_len = min_len; a.sample = ctx->dev_sample();
+  a.keys = t.keys.p; a.vals = t.vals.p; a.mask = tsize - 1; a.hash = t.hash.p; a.slot_of = t.slot_of.p; a.feature_read = t.feature_read.p; a.counters = t.counters.p;
+  unsigned long long hc[2] = {0, 0};
+  for (int round = 0;; round++) {                       // one round, unless two different sequences share a 64-bit hash
+    launch_ft_insert(a, round, st);
+    launch_ft_resolve(a, round, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hc, t.counters.p, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (hc[1] == 0) break;
+    if (round >= 64) SET_ERR(ctx, ITSX_E_COLLISION, "itsx_trimmed_table: sequences still share a hash after 64 rounds of probing");
+    HIPCHK(hipMemsetAsync(t.counters.p + 1, 0, 8, st));
+  }
+  const int64_t nc = (int64_t)hc[0];
+  // ---- 3: (holder, sample) pairs, sorted; their runs; the features' order
+  int sbits = 0; while (((int64_t)1 << sbits) < (int64_t)ctx->S) sbits++;
+  int nbits = 1; while (((int64_t)1 << nbits) <= n) nbits++;
+  const size_t sort_bytes = ft_sort_bytes(n);
+  HIPCHK(t.sort_tmp.alloc(sort_bytes)); HIPCHK(t.pair_keys.alloc((size_t)n)); HIPCHK(t.pair_sorted.alloc((size_t)n));
+  HIPCHK(t.ehead.alloc((size_t)nc + 1)); HIPCHK(t.epos.alloc((size_t)nc + 1)); HIPCHK(t.fhead.alloc((size_t)nc + 1)); HIPCHK(t.fpos.alloc((size_t)nc + 1));
+  HIPCHK(t.scan.alloc((size_t)scan_tmp_elems(n + 1)));
+  a.pair_keys = t.pair_keys.p; a.pair_sorted = t.pair_sorted.p; a.sbits = sbits; a.nc = nc;
+  a.ehead = t.ehead.p; a.epos = t.epos.p; a.fhead = t.fhead.p; a.fpos = t.fpos.p;
+  launch_ft_pairs(a, st);
+  if (ft_sort_keys(t.sort_tmp.p, sort_bytes, t.pair_keys.p, t.pair_sorted.p, n, sbits + nbits, st) != 0) SET_ERR(ctx, ITSX_E_DEVICE, "itsx_trimmed_table: the pair sort failed");
+  launch_ft_heads(a, st);
+  launch_exclusive_scan(t.ehead.p, t.epos.p, nc + 1, t.scan.p, st);
+  launch_exclusive_scan(t.fhead.p, t.fpos.p, nc + 1, t.scan.p, st);
+  HIPCHK(hipGetLastError());
+  int32_t EF[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(&EF[0], t.epos.p + nc, 4, hipMemcpyDeviceToHost, st)); HIPCHK(hipMemcpyAsync(&EF[1], t.fpos.p + nc, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const int32_t E = EF[0], F = EF[1];
+  HIPCHK(t.ent_start.alloc((size_t)E + 1)); HIPCHK(t.ent_sample.alloc((size_t)E + 1)); HIPCHK(t.ent_feat.alloc((size_t)E + 1));
+  HIPCHK(t.f_ent0.alloc((size_t)F + 1)); HIPCHK(t.f_pos0.alloc((size_t)F + 1)); HIPCHK(t.f_first.alloc((size_t)F + 1)); HIPCHK(t.hold_f.alloc((size_t)n));
+  HIPCHK(t.okeys.alloc((size_t)F + 1)); HIPCHK(t.okeys2.alloc((size_t)F + 1)); HIPCHK(t.ovals.alloc((size_t)F + 1)); HIPCHK(t.ovals2.alloc((size_t)F + 1));
+  HIPCHK(t.rank_of.alloc((size_t)F + 1)); HIPCHK(t.feat_len.alloc((size_t)F + 1)); HIPCHK(t.feat_total.alloc((size_t)F + 1)); HIPCHK(t.feat_first.alloc((size_t)F + 1));
+  HIPCHK(t.nent.alloc((size_t)F + 1)); HIPCHK(t.row_off.alloc((size_t)F + 1)); HIPCHK(t.entry_sample.alloc((size_t)E + 1)); HIPCHK(t.entry_count.alloc((size_t)E + 1));
+  a.ent_start = t.ent_start.p; a.ent_sample = t.ent_sample.p; a.ent_feat = t.ent_feat.p; a.f_ent0 = t.f_ent0.p; a.f_pos0 = t.f_pos0.p; a.f_first = t.f_first.p;
+  a.hold_f = t.hold_f.p; a.E = E; a.F = F; a.okeys = t.okeys.p; a.okeys_sorted = t.okeys2.p; a.ovals = t.ovals.p; a.ovals_sorted = t.ovals2.p;
+  a.rank_of = t.rank_of.p; a.feat_len = t.feat_len.p; a.feat_total = t.feat_total.p; a.feat_first = t.feat_first.p; a.nent = t.nent.p; a.row_off = t.row_off.p;
+  a.entry_sample = t.entry_sample.p; a.entry_count = t.entry_count.p; a.feature_of_read = t.feature_of_read.p;
+  launch_ft_runs(a, st);
+  launch_ft_order_keys(a, st);
+  if (ft_sort_pairs(t.sort_tmp.p, sort_bytes, t.okeys.p, t.okeys2.p, t.ovals.p, t.ovals2.p, F, st) != 0) SET_ERR(ctx, ITSX_E_DEVICE, "itsx_trimmed_table: the feature sort failed");
+  launch_ft_ranked(a, st);
+  launch_exclusive_scan(t.nent.p, t.row_off.p, (int64_t)F + 1, t.scan.p, st);
+  launch_ft_entries(a, st);
+  HIPCHK(hipGetLastError());
+  // ---- 4: the representatives' sequences (their offsets are a 64-bit running sum of F lengths: made here, on the host)
+  std::vector<int32_t> flen((size_t)F);
+  if (F > 0) HIPCHK(hipMemcpyAsync(flen.data(), t.feat_len.p, (size_t)F * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  t.h_seq_off.assign((size_t)F + 1, 0);
+  for (int32_t g = 0; g < F; g++) t.h_seq_off[(size_t)g + 1] = t.h_seq_off[(size_t)g] + flen[(size_t)g];
+  t.text_bytes = t.h_seq_off[(size_t)F];
+  HIPCHK(upload(t.seq_off, t.h_seq_off, st));
+  HIPCHK(t.text.alloc((size_t)((t.text_bytes + 15) / 16) * 4 + 4));
+  a.seq_off = t.seq_off.p; a.text = t.text.p; a.text_bytes = t.text_bytes;
+  launch_ft_text(a, st);
+  HIPCHK(hipGetLastError());
+  const float ms = tm.stop();
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  t.have = true; t.n = n; t.nc = nc; t.F = F; t.E = E;
+  if (n_features) *n_features = F;
+  if (n_entries) *n_entries = E;
+  if (n_counted) *n_counted = nc;
+  if (ms_kernels) *ms_kernels = ms;
+  return ITSX_OK;
+}
+int itsx_trimmed_table_get(itsx_ctx *ctx, int32_t *feat_len, int32_t *feat_total, int32_t *feat_first_read, int64_t *row_off, int32_t *entry_sample, int32_t *entry_count)
+{
+  CTXCHK(ctx);
+  itsx_ctx::FeatureTable &t = ctx->ft;
+  if (!t.have) SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table_get: no table (call itsx_trimmed_table; a new read set drops it)");
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  const size_t F = (size_t)t.F, E = (size_t)t.E;
+  std::vector<int32_t> ro(F + 1, 0);
+  if (F && feat_len) HIPCHK(hipMemcpyAsync(feat_len, t.feat_len.p, F * 4, hipMemcpyDeviceToHost, st));
+  if (F && feat_total) HIPCHK(hipMemcpyAsync(feat_total, t.feat_total.p, F * 4, hipMemcpyDeviceToHost, st));
+  if (F && feat_first_read) HIPCHK(hipMemcpyAsync(feat_first_read, t.feat_first.p, F * 4, hipMemcpyDeviceToHost, st));
+  if (F && row_off) HIPCHK(hipMemcpyAsync(ro.data(), t.row_off.p, (F + 1) * 4, hipMemcpyDeviceToHost, st));
+  if (E && entry_sample) HIPCHK(hipMemcpyAsync(entry_sample, t.entry_sample.p, E * 4, hipMemcpyDeviceToHost, st));
+  if (E && entry_count) HIPCHK(hipMemcpyAsync(entry_count, t.entry_count.p, E * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (row_off) for (size_t g = 0; g <= F; g++) row_off[g] = ro[g];
+  return ITSX_OK;
+}
+int itsx_trimmed_table_reads(itsx_ctx *ctx, int32_t *feature_of_read)
+{
+  CTXCHK(ctx && feature_of_read);
+  itsx_ctx::FeatureTable &t = ctx->ft;
+  if (!t.have) SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table_reads: no table (call itsx_trimmed_table; a new read set drops it)");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipMemcpyAsync(feature_of_read, t.feature_of_read.p, (size_t)t.n * 4, hipMemcpyDeviceToHost, ctx->st));
+  HIPCHK(hipStreamSynchronize(ctx->st));
+  return ITSX_OK;
+}
+int itsx_trimmed_table_seqs(itsx_ctx *ctx, char *bases, int64_t *offsets)
+{
+  CTXCHK(ctx);
+  itsx_ctx::FeatureTable &t = ctx->ft;
+  if (!t.have) SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table_seqs: no table (call itsx_trimmed_table; a new read set drops it)");
+  if (offsets) memcpy(offsets, t.h_seq_off.data(), t.h_seq_off.size() * sizeof(int64_t));
+  if (!bases) return ITSX_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  return fetch_staged(ctx, reinterpret_cast<const uint8_t *>(t.text.p), t.text_bytes, bases);
 }
 // f1 for a batch of PAIRED samples: Dedup.create_paired_trimmed_seqs (SeqSample.py:564-790) of every sample in one call, from the pair
 // records the context keeps (itsx_keep_pair_records).  One plan for both sides; then per side the copy kernel with that side's planes and

@@ -284,6 +284,43 @@ void launch_trim_unit(const TrimUnitArgs &a, hipStream_t st);
 void launch_trim_orient(const uint8_t *seq, const uint8_t *qual, const int64_t *off, const int32_t *from, const int8_t *strand, const uint8_t *comp,
                         const int64_t *noff, int64_t m, uint8_t *nseq, uint8_t *nqual, hipStream_t st);
 
+// ---- k_ftable.hip (the feature table of a batch's trimmed regions: itsx_trimmed_table)
+// Read r is counted iff start[r] >= 0, stop[r] >= 0, start[r] < stop[r] and min(stop[r], len[r]) - start[r] >= min_len; its key is the
+// slice's 2-bit words re-packed from bit 2 * start[r], the exceptions inside the slice rebased to it, and the slice's length.
+constexpr int32_t FT_PENDING = -2;          // feature_read: the slot's holder is another sequence under the same hash; the next round probes on
+constexpr uint32_t FT_NONE = 0xFFFFFFFFu;   // slot_of: the read is not counted
+struct FtArgs {
+  ReadsDev rd;
+  const int32_t *start, *stop;              // [n] compact copies of the caller's or the search's coordinates
+  int32_t min_len;
+  const int32_t *sample;                    // [n], or nullptr: one sample
+  // the table: mask + 1 >= 2 n slots (keys 0, vals 0x7f7f7f7f); hash, slot_of, feature_read: [n]
+  unsigned long long *keys; int32_t *vals; uint64_t mask; uint64_t *hash; uint32_t *slot_of; int32_t *feature_read;
+  unsigned long long *counters;             // [0] counted reads, [1] reads left pending by the last resolve (zeroed by the caller)
+  // counting: pair keys (holder << sbits | sample; n << sbits for a read that is not counted), sorted; nc = counted reads
+  unsigned long long *pair_keys; const unsigned long long *pair_sorted; int sbits; int64_t nc;
+  int32_t *ehead, *epos, *fhead, *fpos;     // [nc + 1] run heads of the sorted pairs (entries / features) and their exclusive scans
+  // runs in holder order: entries [E + 1], features [F + 1] (the last element closes the last run), hold_f [n]
+  int32_t *ent_start, *ent_sample, *ent_feat, *f_ent0, *f_pos0, *f_first, *hold_f; int32_t E, F;
+  unsigned long long *okeys; const unsigned long long *okeys_sorted; int32_t *ovals; const int32_t *ovals_sorted;   // (~total << 32 | first_read, f)
+  // the table in its order: [F] / [F + 1] / [E], and every read's feature [n]
+  int32_t *rank_of, *feat_len, *feat_total, *feat_first, *nent, *row_off, *entry_sample, *entry_count, *feature_of_read;
+  const int64_t *seq_off; uint32_t *text; int64_t text_bytes;   // [F + 1]; the sequences, padded to whole 16-byte chunks
+};
+void launch_ft_coords(const int32_t *start, const int32_t *stop, int32_t stride, int64_t n, int32_t *ostart, int32_t *ostop, hipStream_t st);
+void launch_ft_insert(const FtArgs &a, int round, hipStream_t st);
+void launch_ft_resolve(const FtArgs &a, int round, hipStream_t st);
+void launch_ft_pairs(const FtArgs &a, hipStream_t st);
+void launch_ft_heads(const FtArgs &a, hipStream_t st);
+void launch_ft_runs(const FtArgs &a, hipStream_t st);
+void launch_ft_order_keys(const FtArgs &a, hipStream_t st);
+void launch_ft_ranked(const FtArgs &a, hipStream_t st);
+void launch_ft_entries(const FtArgs &a, hipStream_t st);
+void launch_ft_text(const FtArgs &a, hipStream_t st);
+size_t ft_sort_bytes(int64_t n);            // scratch for either sort below
+int ft_sort_keys(void *tmp, size_t bytes, const unsigned long long *kin, unsigned long long *kout, int64_t n, int end_bit, hipStream_t st);
+int ft_sort_pairs(void *tmp, size_t bytes, const unsigned long long *kin, unsigned long long *kout, const int32_t *vin, int32_t *vout, int64_t n, hipStream_t st);
+
 // ---- k_deflate.hip (the batch writers' gzip output made on the device: one gzip member per block of text)
 constexpr int DEFLATE_BLOCK_BYTES = 65535;      // text of one member at most: what ONE stored block holds, so a member never costs more than len + 5 + 18
 constexpr int DEFLATE_SLOT_BYTES = 65600;       // where a member is built: its stored form (text + 5 + 18) after 2 bytes of lead, whole dwords

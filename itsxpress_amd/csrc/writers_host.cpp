@@ -363,4 +363,61 @@ int itsx_write_domtbl_arrays(const char *path, const itsx_domain *rows, int64_t 
                                       target_names, target_name_offsets, nullptr);
 }
 
+// The two files of a feature table (itsx_trimmed_table's arrays): blocks of features through write_blocks, like every other file here.
+int itsx_write_feature_files(const char *fasta_path, const char *tsv_path, int64_t n_features, int32_t n_samples, const int32_t *feat_total,
+                             const int32_t *feat_first_read, const int64_t *row_off, const int32_t *entry_sample, const int32_t *entry_count,
+                             const char *bases, const int64_t *offsets, const char *labels, const int64_t *label_offsets,
+                             const char *read_names, const int64_t *read_name_offsets, const char *sample_names,
+                             const int64_t *sample_name_offsets)
+{
+  const int64_t F = n_features;
+  if (F < 0 || n_samples < 0 || (F > 0 && (!feat_total || !feat_first_read))) return fail(ITSX_E_ARG, "itsx_write_feature_files: missing arrays");
+  if (fasta_path && F > 0 && (!bases || !offsets)) return fail(ITSX_E_ARG, "itsx_write_feature_files: the FASTA needs the features' sequences");
+  if (tsv_path && F > 0 && (!row_off || (row_off[F] > 0 && (!entry_sample || !entry_count)))) return fail(ITSX_E_ARG, "itsx_write_feature_files: the table needs its entries");
+  if (tsv_path && F > 0)
+    for (int64_t e = 0; e < row_off[F]; e++)
+      if (entry_sample[e] < 0 || entry_sample[e] >= n_samples) return fail(ITSX_E_ARG, "itsx_write_feature_files: entry " + std::to_string(e) + " names sample " + std::to_string(entry_sample[e]) + " of " + std::to_string(n_samples));
+  const itsx::Labels given{labels, label_offsets}, reads{read_names, read_name_offsets};
+  auto label = [&](int64_t f) -> std::string {
+    if (labels && label_offsets) return given(f);
+    std::string id = reads(feat_first_read[f]);             // (without names: r%09d of the read's index)
+    const size_t cut = id.find_first_of(" \t");
+    if (cut != std::string::npos) id.resize(cut);
+    return id;
+  };
+  constexpr int64_t BLOCK = 4096;                           // features per block
+  const size_t nb = (size_t)((F + BLOCK - 1) / BLOCK);
+  std::string err;
+  if (fasta_path) {
+    const int rc = itsx::write_blocks(fasta_path, nb, [&](size_t b, std::string &out) {
+      for (int64_t f = (int64_t)b * BLOCK, hi = std::min(F, f + BLOCK); f < hi; f++) {
+        out.push_back('>'); out.append(label(f)); itsx::appendf(out, ";size=%d\n", feat_total[f]);
+        out.append(bases + offsets[f], (size_t)(offsets[f + 1] - offsets[f])); out.push_back('\n');
+      }
+    }, err);
+    if (rc != ITSX_OK) { (void)remove(fasta_path); return fail(ITSX_E_IO, err); }
+  }
+  if (tsv_path) {
+    const itsx::Labels snames{sample_names, sample_name_offsets};
+    const int rc = itsx::write_blocks(tsv_path, nb + 1, [&](size_t b, std::string &out) {
+      if (b == 0) {
+        out.append("#feature");
+        for (int32_t s = 0; s < n_samples; s++) { out.push_back('\t'); if (sample_names && sample_name_offsets) out.append(snames(s)); else itsx::appendf(out, "s%d", s); }
+        out.push_back('\n');
+        return;
+      }
+      std::vector<int32_t> row((size_t)n_samples);
+      for (int64_t f = (int64_t)(b - 1) * BLOCK, hi = std::min(F, f + BLOCK); f < hi; f++) {
+        std::fill(row.begin(), row.end(), 0);
+        for (int64_t e = row_off[f]; e < row_off[f + 1]; e++) row[(size_t)entry_sample[e]] += entry_count[e];
+        out.append(label(f));
+        for (int32_t s = 0; s < n_samples; s++) itsx::appendf(out, "\t%d", row[(size_t)s]);
+        out.push_back('\n');
+      }
+    }, err);
+    if (rc != ITSX_OK) { (void)remove(tsv_path); return fail(ITSX_E_IO, err); }
+  }
+  return ITSX_OK;
+}
+
 }  // extern "C"

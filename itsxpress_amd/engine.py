@@ -47,6 +47,35 @@ def _batch_compression(gzipped, zstd_file, deflate, who):
     return _compression(gzipped, zstd_file)
 
 
+class FeatureTable:
+    """What Engine.trimmed_table returns: the distinct trimmed sequences of a read set by its samples, in table order.
+    sequences (list[str], made on first use from bases / seq_off), lengths, totals, first_read: per feature; the cells as CSR rows --
+    feature f's are [row_off[f], row_off[f + 1]) of entry_sample / entry_count, samples ascending; feature_of_read: per read, -1 = not
+    counted; n_counted; ms_kernels: the device time of the call."""
+    n_samples = 1
+    n_counted = 0
+    ms_kernels = 0.0
+    _seqs = None
+
+    @property
+    def n_features(self):
+        return int(self.totals.shape[0])
+
+    @property
+    def sequences(self):
+        if self._seqs is None:
+            text = self.bases.decode("ascii")
+            self._seqs = [text[int(self.seq_off[f]):int(self.seq_off[f + 1])] for f in range(self.n_features)]
+        return self._seqs
+
+    def dense(self):
+        """the table as an [n_features, n_samples] int64 array"""
+        out = np.zeros((self.n_features, self.n_samples), np.int64)
+        rows = np.repeat(np.arange(self.n_features), np.diff(self.row_off))
+        out[rows, self.entry_sample] = self.entry_count
+        return out
+
+
 class Engine:
     def __init__(self, device=None):
         self.L = _lib.lib()
@@ -822,6 +851,51 @@ class Engine:
                                                     None if keep[0] is None else keep[0].ctypes.data,
                                                     None if keep[1] is None else keep[1].ctypes.data, nw.ctypes.data, tot.ctypes.data))
         return [(int(nw[s]), int(tot[s])) for s in range(S)]
+
+    # ---- the feature table of the trimmed regions (distinct trimmed sequences by samples)
+    def trimmed_table(self, region_prefixes=None, start=None, stop=None, min_len=1):
+        """The trimmed regions of the read set dereplicated over all its samples (itsx_trimmed_table): a FeatureTable.
+        Read i is counted iff the trimmed-FASTQ writer would write it and min(stop, len) - start >= min_len; two counted reads are one
+        feature iff their slices are equal symbol for symbol (upper case, U is T, IUPAC symbols kept; forward strand; no trim_ccs
+        stitching).  Features are ordered by descending total, ties by the smaller index of the first read, which is the representative.
+        Coordinates: region_prefixes = (left, right) of the finalized search, or start / stop arrays over the reads -- exactly one of
+        the two.  One GPU, a whole-file read set."""
+        left = right = None
+        if region_prefixes is not None:
+            left, right = (x.encode() for x in region_prefixes)
+        keep = []
+        for a in (start, stop):
+            if a is None:
+                keep.append(None)
+                continue
+            a = np.ascontiguousarray(a, np.int32)
+            if a.shape[0] != self.n_reads:
+                raise ValueError("trimmed_table: start / stop hold one entry per read")
+            keep.append(a if a.size else np.zeros(1, np.int32))
+        nf, ne, nc, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_float(0)
+        self._chk(self.L.itsx_trimmed_table(self.h, left, right, None if keep[0] is None else keep[0].ctypes.data,
+                                            None if keep[1] is None else keep[1].ctypes.data, int(min_len),
+                                            C.byref(nf), C.byref(ne), C.byref(nc), C.byref(ms)))
+        F, E = int(nf.value), int(ne.value)
+        t = FeatureTable()
+        t.n_samples = int(self.L.itsx_num_samples(self.h))
+        t.n_counted = int(nc.value)
+        t.ms_kernels = float(ms.value)
+        t.lengths, t.totals, t.first_read = (np.zeros(F, np.int32) for _ in range(3))
+        t.row_off = np.zeros(F + 1, np.int64)
+        t.entry_sample, t.entry_count = np.zeros(E, np.int32), np.zeros(E, np.int32)
+        pad = lambda x: x.ctypes.data if x.size else None
+        self._chk(self.L.itsx_trimmed_table_get(self.h, pad(t.lengths), pad(t.totals), pad(t.first_read), t.row_off.ctypes.data,
+                                                pad(t.entry_sample), pad(t.entry_count)))
+        t.feature_of_read = np.zeros(max(self.n_reads, 1), np.int32)
+        self._chk(self.L.itsx_trimmed_table_reads(self.h, t.feature_of_read.ctypes.data))
+        t.feature_of_read = t.feature_of_read[:self.n_reads]
+        t.seq_off = np.zeros(F + 1, np.int64)
+        self._chk(self.L.itsx_trimmed_table_seqs(self.h, None, t.seq_off.ctypes.data))
+        buf = C.create_string_buffer(int(t.seq_off[-1]) + 1)
+        self._chk(self.L.itsx_trimmed_table_seqs(self.h, buf, None))
+        t.bases = buf.raw[:int(t.seq_off[-1])]
+        return t
 
     # ---- f1 for a batch of paired samples: trimmed R1 / R2 FASTQ from the pair records the context keeps
     def keep_pair_records(self, on=True):

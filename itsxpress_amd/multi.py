@@ -1069,6 +1069,10 @@ class MultiEngine(ShardedOps):
         raise EngineError(-5, "orientation by the profiles (orient_profiles_apply) does not shard over GPUs: run it with ITSXPRESS_GPUS=1 "
                               "(DESIGN.md section 9)")
 
+    def trimmed_table(self, region_prefixes=None, start=None, stop=None, min_len=1):
+        raise EngineError(-5, "the feature table of the trimmed regions (trimmed_table) does not shard over GPUs: run it with ITSXPRESS_GPUS=1 "
+                              "(DESIGN.md section 8)")
+
     def _merge(self, r1, r2, out, maxdiffs, maxee, allow_stagger):
         for p in (r1, r2):
             if not os.path.exists(p):

@@ -1061,5 +1061,9 @@ class StreamEngine(ShardedOps):
         raise EngineError(-5, "orientation by the profiles (orient_profiles_apply) is a whole-file call and is not streamed: plan_orient() "
                               "before search() orients a streamed run chunk by chunk (DESIGN.md section 9)")
 
+    def trimmed_table(self, region_prefixes=None, start=None, stop=None, min_len=1):
+        raise EngineError(-5, "the feature table of the trimmed regions (trimmed_table) counts a whole-file read set and is not streamed: "
+                              "run it without ITSXPRESS_STREAM (DESIGN.md section 8)")
+
     def merge_pairs_files(self, r1, r2, out, maxdiffs=40, maxee=2.0, allow_stagger=False):
         return self._plain().merge_pairs_files(r1, r2, out, maxdiffs=maxdiffs, maxee=maxee, allow_stagger=allow_stagger)
