@@ -388,8 +388,31 @@ struct itsx_ctx {
   DBuf<unsigned long long> sc_keys, sc_keys_in; DBuf<uint8_t> sc_sort;
   double slab_gb = 0.0;                  // HBM budget for per-batch DP slabs
 
+  // ---- what the context holds: one ladder, every level standing on the ones below it.  ST_GROUPED: a dereplication or a clustering is
+  // in place; ST_SEARCHED: the rows of a search (or of itsx_debug_set_domains); ST_FINAL: itsx_search_finalize has decided them.
+  // The stage rises through StageTxn::commit (below the struct) and falls through fall_to alone.
+  enum Stage { ST_NONE, ST_READS, ST_GROUPED, ST_SEARCHED, ST_FINAL };
+  Stage stage{ST_NONE};
+  bool grouped() const { return stage >= ST_GROUPED; }
+  bool searched() const { return stage >= ST_SEARCHED; }
+  bool finalized() const { return stage >= ST_FINAL; }
+  // Down to s at most, and whatever is attached to a level above s goes -- also when the stage is there already: a rebuild that failed
+  // half way may have attached something.  What stays: the buffers themselves; thr_memo (it belongs to the profiles: install_profiles);
+  // prev_* (search_active reads the last search's chunking at its next call); have_orient_db (the database is not the read set's);
+  // the samples of the reads (h_sample, S: a new read set makes itself one sample, orient_apply_strands compacts them)
+  void fall_to(Stage s)
+  {
+    if (s < ST_FINAL) { drop_alignments(); h_dom.clear(); }
+    if (s < ST_SEARCHED) {
+      h_trace.clear(); trace_sorted = trace_members_done = searched_holders = shared_lazy = false; sc = SampleSharing{};
+      topup.valid = topup.list_live = false; injected = domz_on_device = domz_exchanged = false; lazy_pending = 0; lazy_pending_prof.clear();
+    }
+    if (s < ST_GROUPED) { clustered = false; drop_cigars(); order_cache_ok = false; h_usample.clear(); active_narrowed = false; }
+    if (s < ST_READS) { rec.drop(); prec.drop(); ft.have = false; }
+    if (stage > s) stage = s;
+  }
+
   // ---- derep
-  bool have_derep = false;
   std::vector<int32_t> order_cache; bool order_cache_ok = false;      // cluster_order() of the current dereplication (uc.txt and rep.fa both ask)
   int derep_strand_both = 1;             // how the last itsx_derep / itsx_cluster matched (the cross-shard keys follow it)
   int32_t U = 0;
@@ -408,10 +431,9 @@ struct itsx_ctx {
   // h_cg_text[h_cg_off[r], h_cg_off[r + 1]) (empty: a centroid or a dropped read); whatever changes the clustering drops them
   bool have_cigar = false; std::vector<int64_t> h_cg_off; std::string h_cg_text;
   void drop_cigars() { have_cigar = false; std::vector<int64_t>().swap(h_cg_off); std::string().swap(h_cg_text); }
-  bool cigars_live() const { return have_cigar && have_derep && clustered; }
+  bool cigars_live() const { return have_cigar && grouped() && clustered; }
 
   // ---- search
-  bool have_search = false, have_final = false;
   bool injected = false;                 // the row table came from itsx_debug_set_domains, not from a search: nothing can be evaluated again
   double T = 10.0;
   int64_t npairs_padded = 0;
@@ -457,7 +479,7 @@ struct itsx_ctx {
   struct AliRow { int32_t prof, dom_idx; int64_t rep; itsx_alignment a; };
   bool have_ali = false; std::vector<AliRow> h_ali;
   void drop_alignments() { have_ali = false; std::vector<AliRow>().swap(h_ali); }
-  bool alignments_live() const { return have_ali && have_search && have_final; }
+  bool alignments_live() const { return have_ali && finalized(); }
   DBuf<PairRec> w_al_pairs; DBuf<RegionRec> w_al_regions; DBuf<RegionOut> w_al_rout; DBuf<int32_t> w_al_rep; DBuf<WaveDesc> w_al_waves; DBuf<itsx_alignment> w_al_out;
   std::vector<itsx_pairtrace> h_trace;
 
@@ -574,6 +596,17 @@ struct itsx_ctx {
   DBuf<PairRec> sh_bpairs; DBuf<WaveDesc> sh_bwaves;
 };
 
+// An entry point that rebuilds a level of the ladder: the context falls below that level at once and rises to it through commit(), the last
+// statement of the success path.  Every early return leaves it below (at `failed`, where that is lower than where the work starts: itsx_lazy_complete).
+struct StageTxn {
+  itsx_ctx *c; itsx_ctx::Stage failed; bool done = false;
+  StageTxn(itsx_ctx *ctx, itsx_ctx::Stage below, itsx_ctx::Stage failed_) : c(ctx), failed(failed_) { c->fall_to(below); }
+  StageTxn(itsx_ctx *ctx, itsx_ctx::Stage below) : StageTxn(ctx, below, below) {}
+  StageTxn(const StageTxn &) = delete;
+  void commit(itsx_ctx::Stage s) { c->stage = s; done = true; }
+  ~StageTxn() { if (!done) c->fall_to(failed); }
+};
+
 #define CTXCHK(c)                                   \
   if (!(c)) return ITSX_E_ARG;
 #define SET_ERR(ctx, code, msg) do { (ctx)->set_error(msg); return (code); } while (0)
@@ -651,7 +684,6 @@ itsx_ctx *itsx_create(int device_id, int flags)
   itsx_ctx *ctx = new itsx_ctx();
   ctx->device = device_id;
   ctx->w_slab.pool_device = device_id;
-  { std::lock_guard<std::mutex> g(g_pool_mu); g_live_contexts++; }
   if (hipStreamCreate(&ctx->st) != hipSuccess) { g_create_error = "hipStreamCreate failed"; delete ctx; return nullptr; }
   if (!(sw_get("ITSX_LOAD_PRIORITY") && atoi(sw_get("ITSX_LOAD_PRIORITY")) == 0)) {
     int least = 0, greatest = 0;
@@ -666,6 +698,7 @@ itsx_ctx *itsx_create(int device_id, int flags)
   build_logtab(lt.data());
   if (upload(ctx->d_logtab, lt, ctx->st) != hipSuccess) { g_create_error = "device allocation failed"; delete ctx; return nullptr; }
   (void)hipStreamSynchronize(ctx->st);
+  { std::lock_guard<std::mutex> g(g_pool_mu); g_live_contexts++; }      // (only a context that itsx_destroy will see is counted)
   return ctx;
 }
 
@@ -708,6 +741,7 @@ static int install_profiles(itsx_ctx *ctx, std::vector<HostProfile> &pv, int *n_
     if (p.base_b + p.bias_b >= 255) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "model '" + p.name + "': MSV bias too large");
   }
   ctx->thr_memo.clear(); ctx->thr_memo_have.clear(); ctx->thr_memo_F1 = -1.0;      // (the MSV thresholds kept between searches belong to the old profiles)
+  ctx->fall_to(itsx_ctx::ST_GROUPED);                    // ... and so do a search's rows, from here on whether the new ones arrive or not
   HIPCHK(hipSetDevice(ctx->device));
   LoadPriority load_priority(ctx);
   ctx->profs = std::move(pv);
@@ -879,7 +913,6 @@ static int install_profiles(itsx_ctx *ctx, std::vector<HostProfile> &pv, int *n_
   HIPCHK(upload(ctx->d_ptbm, pm, ctx->st));
   HIPCHK(hipStreamSynchronize(ctx->st));
   ctx->stats.n_profiles = P;
-  ctx->have_search = ctx->have_final = false;
   if (n_profiles) *n_profiles = P;
   return ITSX_OK;
 }
@@ -979,8 +1012,7 @@ static int stage_reserve(itsx_ctx *ctx, int64_t bytes)
 static int pack_and_upload(itsx_ctx *ctx, const char *view = nullptr, const uint8_t *dev_raw = nullptr)
 {
   init_codes();
-  ctx->rec.drop(); ctx->prec.drop();                     // a new read set: whoever keeps records installs them after this
-  ctx->ft.have = false;
+  StageTxn txn(ctx, itsx_ctx::ST_NONE);                  // a new read set (whoever keeps records installs them after this), or none
   const auto tp0 = std::chrono::steady_clock::now();
   const int64_t n = ctx->N;
   ctx->dev_bases = dev_raw;
@@ -1086,11 +1118,10 @@ static int pack_and_upload(itsx_ctx *ctx, const char *view = nullptr, const uint
   }
   ctx->rd.words = ctx->d_words.p; ctx->rd.woff = ctx->d_woff.p; ctx->rd.len = ctx->d_len.p;
   ctx->rd.excoff = ctx->d_excoff.p; ctx->rd.exc = ctx->d_exc.p; ctx->rd.n = n;
-  ctx->have_derep = ctx->have_search = ctx->have_final = false; ctx->drop_cigars();
   ctx->stats.n_reads = n;
-  ctx->order_cache_ok = false;
-  ctx->S = 1; ctx->sel_sample = -1; ctx->h_sample.clear(); ctx->h_usample.clear();      // a new read set is one sample until told otherwise
+  ctx->S = 1; ctx->sel_sample = -1; ctx->h_sample.clear();      // a new read set is one sample until told otherwise
   ctx->stats.ms_pack = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count();
+  txn.commit(itsx_ctx::ST_READS);
   return ITSX_OK;
 }
 
@@ -1330,10 +1361,9 @@ int itsx_set_samples(itsx_ctx *ctx, const int32_t *sample_of_read, int32_t n_sam
 {
   CTXCHK(ctx);
   HIPCHK(hipSetDevice(ctx->device));
-  ctx->have_derep = ctx->have_search = ctx->have_final = false; ctx->drop_cigars();
-  ctx->sel_sample = -1; ctx->h_usample.clear();
-  ctx->order_cache_ok = false;
-  if (!sample_of_read || n_samples <= 1) { ctx->S = 1; ctx->h_sample.clear(); return ITSX_OK; }
+  StageTxn txn(ctx, itsx_ctx::ST_READS);                 // the reads stay, what was grouped by the old samples goes
+  ctx->sel_sample = -1;
+  if (!sample_of_read || n_samples <= 1) { ctx->S = 1; ctx->h_sample.clear(); txn.commit(itsx_ctx::ST_READS); return ITSX_OK; }
   if ((int64_t)n_samples * std::max(ctx->P, 1) > (1ll << 28)) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "too many samples x profiles for one batch");
   for (int64_t r = 0; r < ctx->N; r++)
     if (sample_of_read[r] < 0 || sample_of_read[r] >= n_samples) SET_ERR(ctx, ITSX_E_ARG, "sample index of read " + std::to_string(r) + " is out of range");
@@ -1341,6 +1371,7 @@ int itsx_set_samples(itsx_ctx *ctx, const int32_t *sample_of_read, int32_t n_sam
   ctx->S = n_samples;
   HIPCHK(upload(ctx->d_sample, ctx->h_sample, ctx->st));
   HIPCHK(hipStreamSynchronize(ctx->st));
+  txn.commit(itsx_ctx::ST_READS);
   return ITSX_OK;
 }
 int itsx_num_samples(const itsx_ctx *ctx) { return ctx ? ctx->S : ITSX_E_ARG; }
@@ -1363,7 +1394,7 @@ int itsx_debug_read_samples(itsx_ctx *ctx, int32_t *device_ids, int32_t *host_id
 // test hook: the length-ordered unique list as it lies on the device (d_sorted_uniq, its first U_active entries)
 int itsx_debug_sorted_uniques(itsx_ctx *ctx, int32_t *out)
 {
-  CTXCHK(ctx && ctx->have_derep && (out || ctx->U_active == 0));
+  CTXCHK(ctx && ctx->grouped() && (out || ctx->U_active == 0));
   const size_t m = (size_t)ctx->U_active;
   if (ctx->d_sorted_uniq.n < m) SET_ERR(ctx, ITSX_E_ARG, "the length-ordered list does not cover the active uniques");
   HIPCHK(hipSetDevice(ctx->device));
@@ -1485,7 +1516,7 @@ static int build_unique_lists(itsx_ctx *ctx)
     HIPCHK(hipMemcpyAsync(&U, seed_rank.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
   }
-  ctx->U = U; ctx->U_active = U; ctx->active_narrowed = false; ctx->shared_lazy = false;
+  ctx->U = U; ctx->U_active = U;
   HIPCHK(ctx->d_seed_read.alloc((size_t)U + 1)); HIPCHK(ctx->d_abund.alloc((size_t)U + 1)); HIPCHK(ctx->d_sorted_uniq.alloc((size_t)U + 1));
   HIPCHK(ctx->d_ulen.alloc((size_t)U + 1));
   HIPCHK(hipMemsetAsync(ctx->d_abund.p, 0, ((size_t)U + 1) * sizeof(int32_t), ctx->st));
@@ -1535,7 +1566,7 @@ int itsx_derep(itsx_ctx *ctx, int strand_both, int minseqlength, int64_t *n_uniq
   CTXCHK(ctx);
   HIPCHK(hipSetDevice(ctx->device));
   LoadPriority load_priority(ctx);
-  ctx->drop_cigars();
+  StageTxn txn(ctx, itsx_ctx::ST_READS);
   const int64_t n = ctx->N;
   StageTimer tm(ctx->st);
   DBuf<uint64_t> &hf = ctx->w_hf, &hr = ctx->w_hr; DBuf<unsigned long long> &keys = ctx->w_keys;
@@ -1574,10 +1605,9 @@ int itsx_derep(itsx_ctx *ctx, int strand_both, int minseqlength, int64_t *n_uniq
   int64_t dropped = 0;
   for (int64_t r = 0; r < n; r++) dropped += ctx->h_rep_of[r] < 0;
   ctx->stats.n_unique = U; ctx->stats.n_dropped_short = dropped;
-  ctx->have_derep = true; ctx->have_search = ctx->have_final = false; ctx->clustered = false;
-  ctx->order_cache_ok = false;
   ctx->derep_strand_both = strand_both != 0;
   if (n_unique) *n_unique = U;
+  txn.commit(itsx_ctx::ST_GROUPED);
   return ITSX_OK;
 }
 
@@ -1618,7 +1648,7 @@ static void dust_host(const uint8_t *codes, int64_t L, std::vector<uint8_t> &mas
 static int cluster_run(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique, bool batched, ClusterShards *shards = nullptr)
 {
   HIPCHK(hipSetDevice(ctx->device));
-  ctx->drop_cigars();
+  StageTxn txn(ctx, itsx_ctx::ST_READS);
   const int64_t n = ctx->N;
   const int minlen = 32;
   const int32_t S = batched ? ctx->S : 1;
@@ -1878,10 +1908,10 @@ static int cluster_run(itsx_ctx *ctx, double id, int strand_both, int64_t *n_uni
   ctx->h_order = ord;
   ctx->stats.n_unique = ctx->U; ctx->stats.n_dropped_short = n - nk;
   ctx->stats.cl_windows = windows; ctx->stats.cl_cuts = cuts; ctx->stats.cl_alignments = (int64_t)naln; ctx->stats.cl_certified = (int64_t)nskip;
-  ctx->have_derep = true; ctx->have_search = ctx->have_final = false; ctx->clustered = true;
-  ctx->order_cache_ok = false;
   if (ctx->U != ncent) SET_ERR(ctx, ITSX_E_DEVICE, "clustering bookkeeping mismatch (centroids " + std::to_string(ncent) + " vs uniques " + std::to_string(ctx->U) + ")");
   if (n_unique) *n_unique = ctx->U;
+  ctx->clustered = true;
+  txn.commit(itsx_ctx::ST_GROUPED);
   return ITSX_OK;
 }
 int itsx_cluster(itsx_ctx *ctx, double id, int strand_both, int64_t *n_unique)
@@ -1922,7 +1952,7 @@ int itsx_cluster_samples(itsx_ctx *ctx, double id, int strand_both, int64_t *n_u
 
 int itsx_get_cluster(const itsx_ctx *ctx, double *pct_id, int64_t *order, int64_t *n_order)
 {
-  CTXCHK(ctx && ctx->have_derep && ctx->clustered);
+  CTXCHK(ctx && ctx->grouped() && ctx->clustered);
   if (pct_id) for (int64_t r = 0; r < ctx->N; r++) pct_id[r] = ctx->h_pct[r];
   if (order) for (size_t i = 0; i < ctx->h_order.size(); i++) order[i] = ctx->h_order[i];
   if (n_order) *n_order = (int64_t)ctx->h_order.size();
@@ -1935,7 +1965,7 @@ int itsx_get_cluster(const itsx_ctx *ctx, double *pct_id, int64_t *order, int64_
 int itsx_align_clusters(itsx_ctx *ctx, int64_t *n_aligned, float *ms_kernels)
 {
   CTXCHK(ctx);
-  if (!ctx->have_derep || !ctx->clustered) SET_ERR(ctx, ITSX_E_ARG, "itsx_align_clusters comes after a clustering at id < 1 (itsx_cluster, itsx_cluster_multi, itsx_cluster_samples); exact dereplication has nothing to align");
+  if (!ctx->grouped() || !ctx->clustered) SET_ERR(ctx, ITSX_E_ARG, "itsx_align_clusters comes after a clustering at id < 1 (itsx_cluster, itsx_cluster_multi, itsx_cluster_samples); exact dereplication has nothing to align");
   HIPCHK(hipSetDevice(ctx->device));
   ctx->drop_cigars();
   const int64_t n = ctx->N;
@@ -2046,7 +2076,7 @@ int itsx_get_cluster_cigars(const itsx_ctx *ctx, int64_t *offs, char *text)
 
 int itsx_get_derep(const itsx_ctx *ctx, int64_t *rep_of, int8_t *strand, int64_t *uniq_of)
 {
-  CTXCHK(ctx && ctx->have_derep);
+  CTXCHK(ctx && ctx->grouped());
   for (int64_t r = 0; r < ctx->N; r++) {
     if (rep_of) rep_of[r] = ctx->h_rep_of[r];
     if (strand) strand[r] = ctx->h_strand[r];
@@ -2056,7 +2086,7 @@ int itsx_get_derep(const itsx_ctx *ctx, int64_t *rep_of, int8_t *strand, int64_t
 }
 int itsx_get_uniques(const itsx_ctx *ctx, int64_t *seed_read, int64_t *abundance)
 {
-  CTXCHK(ctx && ctx->have_derep);
+  CTXCHK(ctx && ctx->grouped());
   for (int32_t u = 0; u < ctx->U; u++) { if (seed_read) seed_read[u] = ctx->h_seed_read[u]; if (abundance) abundance[u] = ctx->h_abund[u]; }
   return ITSX_OK;
 }
@@ -2065,7 +2095,7 @@ int itsx_get_uniques(const itsx_ctx *ctx, int64_t *seed_read, int64_t *abundance
 // ---- multi-GPU exact dereplication (SURVEY 8e option 2): keys out, active set in
 int itsx_unique_keys(itsx_ctx *ctx, uint64_t seed, uint64_t *fwd, uint64_t *rc)
 {
-  CTXCHK(ctx && ctx->have_derep && fwd && rc);
+  CTXCHK(ctx && ctx->grouped() && fwd && rc);
   if (ctx->S > 1) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "cross-rank dereplication of a sample batch is not supported: shard whole samples across ranks");
   HIPCHK(hipSetDevice(ctx->device));
   const int64_t n = ctx->N;
@@ -2101,13 +2131,14 @@ static int set_walked_uniques(itsx_ctx *ctx, const std::vector<int32_t> *keep)
 
 int itsx_set_active_uniques(itsx_ctx *ctx, const uint8_t *active)
 {
-  CTXCHK(ctx && ctx->have_derep && (active || ctx->U == 0));
+  CTXCHK(ctx && ctx->grouped() && (active || ctx->U == 0));
   HIPCHK(hipSetDevice(ctx->device));
+  StageTxn txn(ctx, itsx_ctx::ST_GROUPED);               // a search of other uniques is not this choice's
   std::vector<int32_t> keep; keep.reserve((size_t)ctx->U);
   for (int32_t s = 0; s < ctx->U; s++) { const int32_t u = ctx->h_sorted_uniq[(size_t)s]; if (active[u]) keep.push_back(u); }   // stays length-sorted
   { const int rc = set_walked_uniques(ctx, &keep); if (rc != ITSX_OK) return rc; }      // the traces and the searched-target count follow the active list
   ctx->active_narrowed = true;           // (sample sharing leaves a caller's choice alone)
-  ctx->have_search = ctx->have_final = false;
+  txn.commit(itsx_ctx::ST_GROUPED);
   return ITSX_OK;
 }
 
@@ -2531,7 +2562,7 @@ static int filter_tables(itsx_ctx *ctx, double F1, int64_t *cells_active_out)
 static int search_active(itsx_ctx *ctx, double T, double F1, double F2, double F3)
 {
   CTXCHK(ctx);
-  if (!ctx->have_derep) SET_ERR(ctx, ITSX_E_ARG, "itsx_search called before itsx_derep / itsx_cluster");
+  if (!ctx->grouped()) SET_ERR(ctx, ITSX_E_ARG, "itsx_search called before itsx_derep / itsx_cluster");
   if (ctx->P <= 0) SET_ERR(ctx, ITSX_E_ARG, "no profiles loaded");
   ctx->F2 = F2; ctx->have_vit = F2 < F1;              // hmmsearch enters the Viterbi filter only for P > F2: never when F1 <= F2
   ctx->switches_at_search = sw_report();              // what the environment asked of this search (itsx_switches)
@@ -2539,17 +2570,15 @@ static int search_active(itsx_ctx *ctx, double T, double F1, double F2, double F
   hipStream_t st = ctx->st;
   const int P = ctx->P, G = ctx->G, Ppad = G * 64, U = ctx->U_active;
   ctx->T = T;
-  ctx->h_dom.clear(); ctx->drop_alignments(); ctx->h_trace.clear(); ctx->trace_sorted = false;
   ctx->domz.assign((size_t)P * ctx->S, 0);
   itsx_stats &S = ctx->stats;
   S.n_pairs = (int64_t)U * P; S.n_past_msv = S.n_past_bias = S.n_past_fwd = S.n_regions = S.n_multidomain = S.n_domains = S.n_domain_overflow = 0;
   S.ms_msv = S.ms_filters = S.ms_domains = S.ms_msv_kernel = S.ms_fwd_kernel = S.ms_bwd_kernel = S.ms_env_kernel = S.ms_bias_kernel = S.ms_decode_kernel = 0; S.n_batches = 0; S.ms_ensemble = 0; S.n_mr_clustered = S.n_mr_distinct = S.n_mr_failed = S.n_mr_envelopes = 0; S.n_slab_shrinks = 0; S.n_mr_overflow = 0; S.ms_vit_kernel = 0; for (int k = 0; k < 8; k++) S.n_mr_fail_kind[k] = 0; S.n_rows_resident = 0; S.msv_cells = 0; S.msv_launches = 0; S.fwd_rows = 0; S.env_rows = 0; S.n_env_unique = 0;
   ctx->npairs_padded = 0; ctx->dom_n.clear(); ctx->trace_u0 = 0; ctx->n_chunks = 0;
-  ctx->have_search = true; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->topup.list_live = false; ctx->injected = false;
   const int mode = search_rows_mode(ctx);
   ctx->compact_rows = mode != ITSX_ROWS_FULL;
   ctx->lazy = mode == ITSX_ROWS_LAZY;
-  ctx->lazy_pending = 0; ctx->domz_exchanged = false; ctx->sF1 = F1; ctx->sF3 = F3;
+  ctx->sF1 = F1; ctx->sF3 = F3;
   ctx->domz_ub.assign((size_t)P * ctx->S, 0);
   if (ctx->compact_rows)                    // a full table of an earlier search (80 B x ~130 per representative) goes back to the device
     for (auto &b : ctx->dom_bufs) if (b && b->cap * sizeof(itsx_domain) > ((size_t)256 << 20)) b->release();
@@ -2612,10 +2641,8 @@ static int search_active(itsx_ctx *ctx, double T, double F1, double F2, double F
   // Nothing is capped: a pair's regions beyond its slots go to an overflow list, an ensemble beyond the fast kernel's bookkeeping to the
   // overflow path (k_ensemble.hip).  What remains is what makes hmmsearch itself throw: a region whose Forward matrix cannot be sampled
   // (p7_StochasticTrace's "probabilities were not normalised"): reported, not papered over.
-  if (S.n_mr_failed > 0) {
-    ctx->have_search = false;
+  if (S.n_mr_failed > 0)
     SET_ERR(ctx, ITSX_E_UNSUPPORTED, std::to_string(S.n_mr_failed) + " multidomain region(s) with a Forward matrix that cannot be sampled (hmmsearch's stochastic traceback throws on them)");
-  }
   return ITSX_OK;
 }
 
@@ -2759,12 +2786,10 @@ static int count_member_targets(itsx_ctx *ctx, const itsx_domain *d_rows, int64_
   return ITSX_OK;
 }
 
-int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
+// the search in the mode that applies: of all active uniques, or of the holders of the score classes and the rows' expansion to the members
+static int search_in_mode(itsx_ctx *ctx, double T, double F1, double F2, double F3)
 {
-  CTXCHK(ctx);
-  ctx->sc = itsx_ctx::SampleSharing{};
-  ctx->searched_holders = false; ctx->trace_members_done = false;
-  ctx->sc_count_members = false; ctx->shared_lazy = false; ctx->sc_segs_done = 0;
+  ctx->sc_count_members = false; ctx->sc_segs_done = 0;
   // The mode applies to a search of S > 1 samples whose active set is the engine's own.  Each rows mode has its setting: the full mode
   // itsx_set_sample_sharing (the rows are copied and counted from afterwards), the lazy and compact modes -- they keep their domZ
   // bounds and their verdicts per (sample, profile), and their segments hold only the rows that can still win --
@@ -2774,11 +2799,11 @@ int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
   // holders past the filter to every sample (search_chunk); the top-up round runs at S == 1 only; and a kept row depends on the sample
   // through `rep` alone until k_finalize_lazy.
   const bool full = search_rows_mode(ctx) == ITSX_ROWS_FULL;
-  if (!(full ? sample_sharing_wanted(ctx) : sample_sharing_lazy_wanted(ctx)) || !ctx->have_derep || ctx->P <= 0 || ctx->S <= 1 || ctx->U <= 0 || ctx->active_narrowed)
+  if (!(full ? sample_sharing_wanted(ctx) : sample_sharing_lazy_wanted(ctx)) || !ctx->grouped() || ctx->P <= 0 || ctx->S <= 1 || ctx->U <= 0 || ctx->active_narrowed)
     return search_active(ctx, T, F1, F2, F3);
   HIPCHK(hipSetDevice(ctx->device));
   std::vector<int32_t> holders, keep;
-  { const int rc = build_sample_classes(ctx, holders); if (rc != ITSX_OK) { ctx->sc = itsx_ctx::SampleSharing{}; return rc; } }
+  { const int rc = build_sample_classes(ctx, holders); if (rc != ITSX_OK) return rc; }
   const int32_t U = ctx->U, C = (int32_t)holders.size();
   if (C == U) return search_active(ctx, T, F1, F2, F3);              // nothing in common: every unique is its own holder
   {
@@ -2794,8 +2819,16 @@ int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
   ctx->sc_count_members = false;
   { const int rc2 = set_walked_uniques(ctx, nullptr); if (rc == ITSX_OK) rc = rc2; }      // (every exit leaves the context walking all its uniques again)
   if (rc == ITSX_OK) rc = expand_shared_rows(ctx, 0, full);
-  if (rc != ITSX_OK) { ctx->have_search = false; ctx->sc = itsx_ctx::SampleSharing{}; }
-  else ctx->shared_lazy = !full;
+  if (rc == ITSX_OK) ctx->shared_lazy = !full;
+  return rc;
+}
+
+int itsx_search(itsx_ctx *ctx, double T, double F1, double F2, double F3)
+{
+  CTXCHK(ctx);
+  StageTxn txn(ctx, itsx_ctx::ST_GROUPED);               // the last search's rows, traces, counters' exchange, sharing figures and top-up list go
+  const int rc = search_in_mode(ctx, T, F1, F2, F3);
+  if (rc == ITSX_OK) txn.commit(itsx_ctx::ST_SEARCHED);
   return rc;
 }
 
@@ -2813,7 +2846,7 @@ int itsx_set_sample_sharing_lazy(itsx_ctx *ctx, int on)
 }
 int itsx_sample_sharing_info(const itsx_ctx *ctx, int64_t *n_classes, int64_t *n_uniques_shared, int64_t *n_rows_expanded)
 {
-  CTXCHK(ctx && ctx->have_search);
+  CTXCHK(ctx && ctx->searched());
   if (n_classes) *n_classes = ctx->sc.n_classes;
   if (n_uniques_shared) *n_uniques_shared = ctx->sc.n_shared;
   if (n_rows_expanded) *n_rows_expanded = ctx->sc.n_expanded;
@@ -2821,14 +2854,14 @@ int itsx_sample_sharing_info(const itsx_ctx *ctx, int64_t *n_classes, int64_t *n
 }
 int itsx_sample_sharing_times(const itsx_ctx *ctx, float *ms_classes, float *ms_expand)
 {
-  CTXCHK(ctx && ctx->have_search);
+  CTXCHK(ctx && ctx->searched());
   if (ms_classes) *ms_classes = ctx->sc.ms_classes;
   if (ms_expand) *ms_expand = ctx->sc.ms_expand;
   return ITSX_OK;
 }
 int itsx_debug_sample_classes(itsx_ctx *ctx, int32_t *class_of, int64_t n)
 {
-  CTXCHK(ctx && ctx->have_search && (class_of || n == 0));
+  CTXCHK(ctx && ctx->searched() && (class_of || n == 0));
   if (ctx->sc.n_classes <= 0) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_sample_classes: the last search built no score classes (itsx_sample_sharing_info reports 0)");
   if (n != (int64_t)ctx->U) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_sample_classes: n is not the number of uniques");
   HIPCHK(hipSetDevice(ctx->device));
@@ -4031,7 +4064,7 @@ int itsx_set_rows_mode(itsx_ctx *ctx, int mode)
 int64_t itsx_lazy_pending(const itsx_ctx *ctx) { return ctx ? ctx->lazy_pending : -1; }
 int itsx_lazy_pending_profiles(const itsx_ctx *ctx, int32_t *flags)
 {
-  CTXCHK(ctx && flags && ctx->have_search);
+  CTXCHK(ctx && flags && ctx->searched());
   for (int p = 0; p < ctx->P; p++) flags[p] = (ctx->lazy && (size_t)p < ctx->lazy_pending_prof.size()) ? (ctx->lazy_pending_prof[(size_t)p] != 0) : 0;
   return ITSX_OK;
 }
@@ -4046,9 +4079,9 @@ int itsx_set_kept_rows(itsx_ctx *ctx, int on) { CTXCHK(ctx); if (ctx->kept_rows 
 // flags[n_unique]: 1 where an undecided row could still change the representative's coordinates (the rows itsx_lazy_pending counts)
 int itsx_lazy_pending_uniques(itsx_ctx *ctx, uint8_t *flags)
 {
-  CTXCHK(ctx && flags && ctx->have_search);
+  CTXCHK(ctx && flags && ctx->searched());
   if (ctx->U <= 0) return ITSX_OK;
-  if (!ctx->lazy || !ctx->have_final || ctx->l_uflag.n < (size_t)ctx->U) { memset(flags, 0, (size_t)ctx->U); return ITSX_OK; }
+  if (!ctx->lazy || !ctx->finalized() || ctx->l_uflag.n < (size_t)ctx->U) { memset(flags, 0, (size_t)ctx->U); return ITSX_OK; }
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipMemcpyAsync(flags, ctx->l_uflag.p, (size_t)ctx->U, hipMemcpyDeviceToHost, ctx->st));
   HIPCHK(hipStreamSynchronize(ctx->st));
@@ -4060,7 +4093,7 @@ int itsx_lazy_pending_uniques(itsx_ctx *ctx, uint8_t *flags)
 // profiles are equal; a multi-rank driver exchanges the counters again before it finalizes.
 int itsx_lazy_complete(itsx_ctx *ctx, const int32_t *flags)
 {
-  CTXCHK(ctx && flags && ctx->have_search);
+  CTXCHK(ctx && flags && ctx->searched());
   if (!ctx->lazy) SET_ERR(ctx, ITSX_E_ARG, "itsx_lazy_complete: the last search was not a lazy one");
   if (ctx->injected) SET_ERR(ctx, ITSX_E_ARG, "itsx_lazy_complete: the row table was handed in (itsx_debug_set_domains): there are no pairs to evaluate");
   HIPCHK(hipSetDevice(ctx->device));
@@ -4069,6 +4102,8 @@ int itsx_lazy_complete(itsx_ctx *ctx, const int32_t *flags)
   ctx->h_plist.clear();
   for (int p = 0; p < P; p++) if (flags[p]) ctx->h_plist.push_back(p);
   if (ctx->h_plist.empty() || ctx->U_active == 0) return ITSX_OK;
+  // the rows are added to, so they are to be finalized again; a completion that fails half way leaves no search to finalize
+  StageTxn txn(ctx, itsx_ctx::ST_SEARCHED, itsx_ctx::ST_GROUPED);
   StageTimer tm(st);
   HIPCHK(upload(ctx->d_plist, ctx->h_plist, st));
   // the flagged profiles are counted afresh (k_score adds one per reported target)
@@ -4082,7 +4117,7 @@ int itsx_lazy_complete(itsx_ctx *ctx, const int32_t *flags)
   const bool shared = ctx->shared_lazy;
   if (shared) {
     const int rcw = set_walked_uniques(ctx, &ctx->h_sorted_searched);
-    if (rcw != ITSX_OK) { (void)set_walked_uniques(ctx, nullptr); ctx->have_search = false; return rcw; }
+    if (rcw != ITSX_OK) { (void)set_walked_uniques(ctx, nullptr); return rcw; }
     ctx->sc_count_members = true;
   }
   ctx->completing = true;
@@ -4093,7 +4128,7 @@ int itsx_lazy_complete(itsx_ctx *ctx, const int32_t *flags)
     { const int rc2 = set_walked_uniques(ctx, nullptr); if (rc == ITSX_OK) rc = rc2; }      // (every exit leaves the context walking all its uniques again)
     if (rc == ITSX_OK) rc = expand_shared_rows(ctx, ctx->sc_segs_done, false);
   }
-  if (rc != ITSX_OK) { ctx->have_search = false; return rc; }
+  if (rc != ITSX_OK) return rc;
   HIPCHK(hipMemcpyAsync(dz32.data(), ctx->d_domz32.p, dz32.size() * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   for (int32_t sm = 0; sm < ctx->S; sm++)
@@ -4102,11 +4137,11 @@ int itsx_lazy_complete(itsx_ctx *ctx, const int32_t *flags)
       ctx->domz_loc[z] = ctx->domz_ub_loc[z] = dz32[z];
       if (!ctx->domz_exchanged) ctx->domz[z] = ctx->domz_ub[z] = dz32[z];
     }
-  ctx->have_final = false; ctx->drop_alignments();
   ctx->stats.n_lazy_completed_profiles += (int64_t)ctx->h_plist.size();
   ctx->stats.n_rows_resident = 0;
   for (int64_t r : ctx->dom_n) ctx->stats.n_rows_resident += r;
   ctx->stats.ms_lazy_complete += tm.stop();
+  txn.commit(itsx_ctx::ST_SEARCHED);
   return ITSX_OK;
 }
 
@@ -4115,7 +4150,7 @@ int itsx_lazy_complete(itsx_ctx *ctx, const int32_t *flags)
 // not lazy; after a lazy search they move both halves (2 x S x P values), like itsx_domz_device.
 int itsx_get_domz(const itsx_ctx *ctx, int64_t *domZ)
 {
-  CTXCHK(ctx && domZ && ctx->have_search);
+  CTXCHK(ctx && domZ && ctx->searched());
   // this context's OWN counters (what a multi-rank driver sums), whatever itsx_set_domz / an in-place reduction put in their place
   for (size_t p = 0; p < ctx->domz_loc.size(); p++) domZ[p] = ctx->domz_loc[p];
   if (ctx->lazy) for (size_t p = 0; p < ctx->domz_ub_loc.size(); p++) domZ[ctx->domz_loc.size() + p] = ctx->domz_ub_loc[p];
@@ -4123,7 +4158,7 @@ int itsx_get_domz(const itsx_ctx *ctx, int64_t *domZ)
 }
 int itsx_set_domz(itsx_ctx *ctx, const int64_t *domZ)
 {
-  CTXCHK(ctx && domZ && ctx->have_search);
+  CTXCHK(ctx && domZ && ctx->searched());
   for (size_t p = 0; p < ctx->domz.size(); p++) ctx->domz[p] = domZ[p];
   if (ctx->lazy) for (size_t p = 0; p < ctx->domz_ub.size(); p++) ctx->domz_ub[p] = domZ[ctx->domz.size() + p];
   ctx->domz_on_device = false; ctx->domz_exchanged = true;
@@ -4136,7 +4171,7 @@ int64_t itsx_domz_count(const itsx_ctx *ctx) { return ctx ? (int64_t)ctx->domz.s
 // through host arrays.  Pointers stay valid until the next call that recomputes the same quantity.
 int itsx_domz_device(itsx_ctx *ctx, int64_t **d_domz, int64_t *n)
 {
-  CTXCHK(ctx && d_domz && ctx->have_search);
+  CTXCHK(ctx && d_domz && ctx->searched());
   HIPCHK(hipSetDevice(ctx->device));
   const size_t m = ctx->domz.size(), mm = m * (ctx->lazy ? 2 : 1);
   HIPCHK(ctx->d_domz64.alloc(std::max<size_t>(mm, 1)));
@@ -4159,7 +4194,7 @@ int itsx_domz_device(itsx_ctx *ctx, int64_t **d_domz, int64_t *n)
 int itsx_debug_set_domains(itsx_ctx *ctx, const itsx_domain *rows, int64_t n_rows, const int64_t *seg_rows, int32_t n_segs, int mode)
 {
   CTXCHK(ctx);
-  if (!ctx->have_derep) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_set_domains called before itsx_derep / itsx_cluster");
+  if (!ctx->grouped()) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_set_domains called before itsx_derep / itsx_cluster");
   if (ctx->P <= 0) SET_ERR(ctx, ITSX_E_ARG, "no profiles loaded");
   if (mode < ITSX_ROWS_FULL || mode > ITSX_ROWS_LAZY) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_set_domains: mode must be 0 (full), 1 (compact) or 2 (lazy)");
   if (n_rows < 0 || n_segs < 0 || (n_rows > 0 && !rows) || (n_segs > 0 && !seg_rows)) SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_set_domains: missing arrays");
@@ -4178,13 +4213,12 @@ int itsx_debug_set_domains(itsx_ctx *ctx, const itsx_domain *rows, int64_t n_row
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->st;
   const size_t m = (size_t)ctx->P * ctx->S;
+  StageTxn txn(ctx, itsx_ctx::ST_GROUPED);
   ctx->switches_at_search = sw_report();
-  ctx->searched_holders = false; ctx->shared_lazy = false; ctx->h_dom.clear(); ctx->drop_alignments(); ctx->h_trace.clear(); ctx->trace_sorted = false;
+  ctx->injected = true;
   ctx->domz.assign(m, 0); ctx->domz_ub.assign(m, 0); ctx->domz_loc.assign(m, 0); ctx->domz_ub_loc.assign(m, 0);
   ctx->npairs_padded = 0; ctx->dom_n.clear(); ctx->n_chunks = n_segs;
-  ctx->have_search = false; ctx->have_final = false; ctx->domz_on_device = false; ctx->topup.valid = false; ctx->topup.list_live = false; ctx->injected = true;
   ctx->compact_rows = mode != ITSX_ROWS_FULL; ctx->lazy = mode == ITSX_ROWS_LAZY;
-  ctx->lazy_pending = 0; ctx->domz_exchanged = false; ctx->lazy_pending_prof.clear();
   itsx_stats &S = ctx->stats;
   S.lazy = ctx->lazy; S.n_domains = 0; S.n_lazy_pending = S.n_lazy_reruns = S.n_lazy_topup = S.n_lazy_completed = S.n_lazy_completed_profiles = S.n_lazy_pending_profiles = 0; ctx->n_topup_deferred = ctx->n_topup_ensemble = 0;
   for (int64_t i = 0; i < n_rows; i++) S.n_domains += rows[i].dom_idx >= 0;
@@ -4211,7 +4245,7 @@ int itsx_debug_set_domains(itsx_ctx *ctx, const itsx_domain *rows, int64_t n_row
   HIPCHK(hipGetLastError());
   S.n_rows_resident = 0;
   for (int64_t r : ctx->dom_n) S.n_rows_resident += r;
-  ctx->have_search = true;
+  txn.commit(itsx_ctx::ST_SEARCHED);
   return ITSX_OK;
 }
 
@@ -4219,7 +4253,7 @@ int itsx_debug_set_domains(itsx_ctx *ctx, const itsx_domain *rows, int64_t n_row
 // last finalize left it -- 2 = undecided after a lazy one): the count; the rows too when cap holds them all.  Negative on error.
 int64_t itsx_debug_get_rows(itsx_ctx *ctx, itsx_domain *rows, int64_t cap)
 {
-  if (!ctx || !ctx->have_search) return ITSX_E_ARG;
+  if (!ctx || !ctx->searched()) return ITSX_E_ARG;
   int64_t n = 0;
   for (int64_t r : ctx->dom_n) n += std::max<int64_t>(r, 0);
   if (!rows || cap < n) return n;
@@ -4506,12 +4540,12 @@ static int lazy_topup_deferred(itsx_ctx *ctx)
 
 int itsx_search_finalize(itsx_ctx *ctx, double domE)
 {
-  CTXCHK(ctx && ctx->have_search);
+  CTXCHK(ctx && ctx->searched());
   HIPCHK(hipSetDevice(ctx->device));
   if (ctx->injected && ctx->lazy && !ctx->domz_exchanged)
     SET_ERR(ctx, ITSX_E_ARG, "itsx_search_finalize: a lazy row table that was handed in (itsx_debug_set_domains) has no counters of its own: give both bounds with itsx_set_domz first");
+  StageTxn txn(ctx, itsx_ctx::ST_SEARCHED);              // the last finalize's verdicts, row table and alignments go
   StageTimer tm(ctx->st);
-  ctx->h_dom.clear(); ctx->drop_alignments();
   auto check_compaction = [&](const std::vector<int64_t> &z) -> int {       // the rows were thinned out under two assumptions: check them against what finalize was given
     int64_t zmax = 0;
     for (int64_t v : z) zmax = std::max(zmax, v);
@@ -4567,7 +4601,7 @@ int itsx_search_finalize(itsx_ctx *ctx, double domE)
           }
           if (ctx->lazy_pending == 0) {
             ctx->stats.ms_finalize = tm.stop();
-            ctx->have_final = true;
+            txn.commit(itsx_ctx::ST_FINAL);
             return ITSX_OK;
           }
         }
@@ -4581,19 +4615,20 @@ int itsx_search_finalize(itsx_ctx *ctx, double domE)
       }
       if (ctx->lazy_pending == 0) {
         ctx->stats.ms_finalize = tm.stop();
-        ctx->have_final = true;
+        txn.commit(itsx_ctx::ST_FINAL);
         return ITSX_OK;
       }
       // (cannot happen after a completion -- every row of a counted profile is decided --; kept as the safety net: everything in full)
       const int keep = ctx->rows_mode;
+      int64_t pend_profiles = 0; for (int32_t f : ctx->lazy_pending_prof) pend_profiles += f != 0;      // (the search forgets them)
       ctx->rows_mode = ITSX_ROWS_COMPACT;
       const int rc = itsx_search(ctx, ctx->T, ctx->sF1, ctx->F2, ctx->sF3);
       ctx->rows_mode = keep;
       if (rc != ITSX_OK) return rc;
-      ctx->stats.n_lazy_reruns = 1; ctx->stats.n_lazy_pending = pend; ctx->stats.n_lazy_pending_profiles = 0; for (int32_t f : ctx->lazy_pending_prof) ctx->stats.n_lazy_pending_profiles += f != 0;
+      ctx->stats.n_lazy_reruns = 1; ctx->stats.n_lazy_pending = pend; ctx->stats.n_lazy_pending_profiles = pend_profiles;
     } else {
       ctx->stats.ms_finalize = tm.stop();
-      ctx->have_final = true;
+      txn.commit(itsx_ctx::ST_FINAL);
       return ITSX_OK;
     }
   }
@@ -4608,7 +4643,7 @@ int itsx_search_finalize(itsx_ctx *ctx, double domE)
     if (ctx->compact_rows) { const int rc = check_compaction(ctx->domz); if (rc != ITSX_OK) return rc; }
   }
   ctx->stats.ms_finalize = tm.stop();
-  ctx->have_final = true;
+  txn.commit(itsx_ctx::ST_FINAL);
   return ITSX_OK;
 }
 
@@ -4616,7 +4651,7 @@ static int fetch_domains(const itsx_ctx *cctx)
 {
   itsx_ctx *ctx = const_cast<itsx_ctx *>(cctx);
   if (ctx->compact_rows && !ctx->kept_rows) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "the domain rows of this search were compacted (ITSX_COMPACT_ROWS=1): only coordinates are available, not the row table / domtbl.txt (itsx_set_kept_rows(ctx, 1) serves the rows that were kept)");
-  if (ctx->compact_rows && !ctx->have_final) SET_ERR(ctx, ITSX_E_ARG, "the kept rows of a compact / lazy search are served after itsx_search_finalize");
+  if (ctx->compact_rows && !ctx->finalized()) SET_ERR(ctx, ITSX_E_ARG, "the kept rows of a compact / lazy search are served after itsx_search_finalize");
   if (ctx->lazy && ctx->lazy_pending > 0) SET_ERR(ctx, ITSX_E_ARG, "the kept rows of a lazy search are served once no row is undecided (itsx_lazy_pending)");
   if (!ctx->h_dom.empty()) return ITSX_OK;
   // domtblout order: profile, then target, then domain.  The device rows are grouped by profile already (not contiguously
@@ -4680,13 +4715,13 @@ static int fetch_domains(const itsx_ctx *cctx)
 
 int64_t itsx_num_domains(const itsx_ctx *ctx)
 {
-  if (!ctx || !ctx->have_search) return -1;
+  if (!ctx || !ctx->searched()) return -1;
   if (fetch_domains(ctx) != ITSX_OK) return -1;
   return (int64_t)ctx->h_dom.size();
 }
 int itsx_get_domains(const itsx_ctx *ctx, itsx_domain *rows)
 {
-  CTXCHK(ctx && rows && ctx->have_search);
+  CTXCHK(ctx && rows && ctx->searched());
   const int rc = fetch_domains(ctx);
   if (rc != ITSX_OK) return rc;
   if (!ctx->h_dom.empty()) memcpy(rows, ctx->h_dom.data(), ctx->h_dom.size() * sizeof(itsx_domain));
@@ -4718,7 +4753,7 @@ static void alignments_of_rows(const itsx_ctx *ctx, itsx_alignment *out)
 int itsx_align_domains(itsx_ctx *ctx, int64_t *n_aligned, float *ms_kernels)
 {
   CTXCHK(ctx);
-  if (!ctx->have_search || !ctx->have_final) SET_ERR(ctx, ITSX_E_ARG, "itsx_align_domains is called after itsx_search_finalize");
+  if (!ctx->finalized()) SET_ERR(ctx, ITSX_E_ARG, "itsx_align_domains is called after itsx_search_finalize");
   { const int rc = fetch_domains(ctx); if (rc != ITSX_OK) return rc; }       // (refuses where the row table is refused)
   HIPCHK(hipSetDevice(ctx->device));
   ctx->drop_alignments();
@@ -4907,14 +4942,14 @@ static int fetch_traces(const itsx_ctx *cctx)
 }
 int64_t itsx_num_pairtraces(const itsx_ctx *ctx)
 {
-  if (!ctx || !ctx->have_search) return -1;
+  if (!ctx || !ctx->searched()) return -1;
   if (fetch_traces(ctx) != ITSX_OK) return -1;
   return (int64_t)ctx->h_trace.size();
 }
 int itsx_get_pairtraces(const itsx_ctx *ctx, itsx_pairtrace *rows, int64_t row_size)
 {
   if (ctx && row_size != (int64_t)sizeof(itsx_pairtrace)) SET_ERR(ctx, ITSX_E_ARG, "itsx_get_pairtraces: the caller's rows have " + std::to_string(row_size) + " bytes, this library's " + std::to_string(sizeof(itsx_pairtrace)));
-  CTXCHK(ctx && rows && ctx->have_search);
+  CTXCHK(ctx && rows && ctx->searched());
   const int rc = fetch_traces(ctx);
   if (rc != ITSX_OK) return rc;
   if (!ctx->h_trace.empty()) memcpy(rows, ctx->h_trace.data(), ctx->h_trace.size() * sizeof(itsx_pairtrace));
@@ -5168,8 +5203,8 @@ static int orient_apply_strands(itsx_ctx *ctx, const std::vector<int8_t> &hs, DB
     rr.h_titles.swap(r_names); rr.seq_p = rr.seq.p;
   }
   ctx->dev_bases = nullptr; ctx->d_merged_text.release();      // the text of the read set that was: this one's is on the host
-  ctx->have_derep = ctx->have_search = ctx->have_final = false; ctx->drop_cigars();
-  ctx->order_cache_ok = false; ctx->sel_sample = -1; ctx->h_usample.clear();
+  ctx->fall_to(itsx_ctx::ST_READS);      // (no StageTxn: the read set is replaced after the last step that can fail, and a failure keeps what stood on the old one)
+  ctx->sel_sample = -1;
   ctx->stats.n_reads = m;
   if (n_kept_per_sample) for (int32_t s = 0; s < S; s++) n_kept_per_sample[s] = scnt[(size_t)s];
   return ITSX_OK;
@@ -5193,10 +5228,7 @@ static int orient_profiles(itsx_ctx *ctx, double F1, int8_t *strand, int32_t *co
   if (!ctx->rd.woff) SET_ERR(ctx, ITSX_E_ARG, std::string(who) + " called before a read set is loaded");
   HIPCHK(hipSetDevice(ctx->device));
   if (apply && !ctx->bases_view) { const int rc = host_bases(ctx); if (rc != ITSX_OK) return rc; }
-  struct Forget {                                            // the dereplication is this call's own
-    itsx_ctx *c;
-    ~Forget() { c->have_derep = c->have_search = c->have_final = false; c->clustered = false; c->drop_cigars(); c->order_cache_ok = false; c->h_usample.clear(); }
-  } forget{ctx};
+  StageTxn own(ctx, itsx_ctx::ST_READS);                     // never committed: the dereplication is this call's own, and goes with it
   { const int rc = itsx_derep(ctx, 1, 1, nullptr); if (rc != ITSX_OK) return rc; }
   hipStream_t st = ctx->st;
   const int64_t n = ctx->N;
@@ -5902,7 +5934,7 @@ static int coords_common(itsx_ctx *ctx, const char *lp, const char *rp, bool per
   CTXCHK(ctx && lp && rp);
   const bool to_host = start && stop && tlen && ind;        // all four, or none (the results stay on the device)
   if (!to_host && (start || stop || tlen || ind)) return ITSX_E_ARG;
-  if (!ctx->have_final) SET_ERR(ctx, ITSX_E_ARG, "coordinates requested before itsx_search_finalize");
+  if (!ctx->finalized()) SET_ERR(ctx, ITSX_E_ARG, "coordinates requested before itsx_search_finalize");
   if (ctx->lazy && ctx->lazy_pending > 0 && !ctx->partial_coords)
     SET_ERR(ctx, ITSX_E_ARG, std::to_string(ctx->lazy_pending) + " domain row(s) of the lazy search depend on the exact domZ and could change a result: "
             "search again with itsx_set_rows_mode(ctx, 1) (itsx_lazy_pending reports this after itsx_search_finalize)");
@@ -6132,6 +6164,35 @@ static int trim_text_to_files(itsx_ctx *ctx, int64_t total, const int64_t *bo, c
   for (const std::string &e : werrs) if (!e.empty()) SET_ERR(ctx, ITSX_E_IO, e);
   return ITSX_OK;
 }
+// Where a trimming call takes its coordinates from: the finalized search by two profile prefixes, or the caller's arrays over the reads
+// (tlen among them where the caller has one: with_tlen) -- exactly one of the two, checked in the caller's name.  As device pointers: the
+// rows of coords_device (stride 4), or the arrays in w_tstart / w_tstop / w_ttlen (stride 1; upload = false: the caller places them itself)
+struct CoordSource { const int32_t *start = nullptr, *stop = nullptr, *tlen = nullptr; int32_t stride = 1; bool by_prefix = false; };
+static int coord_source(itsx_ctx *ctx, const std::string &who, const char *lp, const char *rp, const int32_t *start, const int32_t *stop, const int32_t *tlen,
+                        bool with_tlen, bool upload, CoordSource &out)
+{
+  const bool by_prefix = lp || rp, by_arrays = start || stop || tlen;
+  if (by_prefix == by_arrays || (by_prefix && !(lp && rp)) || (by_arrays && !(start && stop && (tlen || !with_tlen))))
+    SET_ERR(ctx, ITSX_E_ARG, who + ": give either left_prefix and right_prefix or " + (with_tlen ? "start, stop and tlen" : "start and stop"));
+  if (by_prefix && !ctx->finalized()) SET_ERR(ctx, ITSX_E_ARG, who + ": prefixes given before itsx_search_finalize");
+  HIPCHK(hipSetDevice(ctx->device));
+  out.by_prefix = by_prefix;
+  if (by_prefix) {
+    int32_t *rows = nullptr; int64_t nrows = 0;
+    const int rc = coords_device(ctx, lp, rp, true, &rows, &nrows);
+    if (rc != ITSX_OK) return rc;
+    out.start = rows; out.stop = rows + 1; out.tlen = rows + 2; out.stride = 4;
+  } else if (upload) {
+    const size_t n = (size_t)ctx->N;
+    const int32_t *src[3] = {start, stop, tlen}; DBuf<int32_t> *dst[3] = {&ctx->w_tstart, &ctx->w_tstop, &ctx->w_ttlen}; const int32_t **res[3] = {&out.start, &out.stop, &out.tlen};
+    for (int k = 0; k < (with_tlen ? 3 : 2); k++) {
+      HIPCHK(dst[k]->alloc(n + 1));
+      if (n > 0) HIPCHK(hipMemcpyAsync(dst[k]->p, src[k], n * 4, hipMemcpyHostToDevice, ctx->st));
+      *res[k] = dst[k]->p;
+    }
+  }
+  return ITSX_OK;
+}
 // ------------------------------------------------------------------------------ f1 for a batch (k_trim.hip)
 // The trimmed FASTQ of every sample from the records the context keeps: one plan (lengths, 64-bit scan) and one copy kernel make the
 // text of the whole batch in device memory; it comes back through the pinned staging buffers in pieces, and each sample's byte range
@@ -6145,25 +6206,13 @@ int itsx_write_trimmed_samples(itsx_ctx *ctx, const char *const *out_paths, int3
   if (n_samples != ctx->S) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_samples: " + std::to_string(n_samples) + " output paths for " + std::to_string(ctx->S) + " sample(s)");
   if (compression < 0 || compression > 3) SET_ERR(ctx, ITSX_E_ARG, "compression must be 0 (plain), 1 (gzip), 2 (zstd) or 3 (gzip, deflated on the device)");
   if (compression == 1 && device_deflate_switch()) compression = 3;
-  const bool by_prefix = left_prefix || right_prefix, by_arrays = start || stop;
-  if (by_prefix == by_arrays || (by_prefix && !(left_prefix && right_prefix)) || (by_arrays && !(start && stop)))
-    SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_samples: give either left_prefix and right_prefix or start and stop");
-  if (by_prefix && !ctx->have_final) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_samples: prefixes given before itsx_search_finalize");
+  CoordSource cs;
+  { const int rc = coord_source(ctx, "itsx_write_trimmed_samples", left_prefix, right_prefix, start, stop, nullptr, false, true, cs); if (rc != ITSX_OK) return rc; }
   if (compression != 3) { itsx_io::PieceCompressor probe(compression); if (!probe.ok()) SET_ERR(ctx, ITSX_E_IO, "zstd output requested but libzstd.so.1 could not be loaded"); }
-  HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->st;
   const int64_t n = ctx->N; const int32_t S = ctx->S;
   TrimPlanArgs pa{};
-  if (by_prefix) {
-    int32_t *rows = nullptr; int64_t nrows = 0;
-    const int rc = coords_device(ctx, left_prefix, right_prefix, true, &rows, &nrows);
-    if (rc != ITSX_OK) return rc;
-    pa.start = rows; pa.stop = rows + 1; pa.stride = 4;
-  } else {
-    HIPCHK(ctx->w_tstart.alloc((size_t)n + 1)); HIPCHK(ctx->w_tstop.alloc((size_t)n + 1));
-    if (n > 0) { HIPCHK(hipMemcpyAsync(ctx->w_tstart.p, start, (size_t)n * 4, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(ctx->w_tstop.p, stop, (size_t)n * 4, hipMemcpyHostToDevice, st)); }
-    pa.start = ctx->w_tstart.p; pa.stop = ctx->w_tstop.p; pa.stride = 1;
-  }
+  pa.start = cs.start; pa.stop = cs.stop; pa.stride = cs.stride;
   // samples are contiguous in the read set: sample s is reads [first[s], first[s + 1])
   std::vector<int64_t> first((size_t)S + 1, 0), bounds((size_t)(S + 1) * 3, 0);
   if (S > 1) { for (int64_t r = 0; r < n; r++) first[(size_t)ctx->h_sample[(size_t)r] + 1]++; for (int32_t s = 0; s < S; s++) first[(size_t)s + 1] += first[(size_t)s]; }
@@ -6199,27 +6248,17 @@ int itsx_trimmed_table(itsx_ctx *ctx, const char *left_prefix, const char *right
                        int64_t *n_features, int64_t *n_entries, int64_t *n_counted, float *ms_kernels)
 {
   CTXCHK(ctx);
-  const bool by_prefix = left_prefix || right_prefix, by_arrays = start || stop;
-  if (by_prefix == by_arrays || (by_prefix && !(left_prefix && right_prefix)) || (by_arrays && !(start && stop)))
-    SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table: give either left_prefix and right_prefix or start and stop");
   if (min_len < 1) SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table: min_len must be at least 1, not " + std::to_string(min_len));
   if (!ctx->rd.woff || ctx->N <= 0) SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table called before a read set is loaded");
-  if (by_prefix && !ctx->have_final) SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table: prefixes given before itsx_search_finalize");
-  HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->st;
   itsx_ctx::FeatureTable &t = ctx->ft;
   t.have = false;
+  CoordSource cs;                                          // (the arrays go straight into the table's own buffers, below)
+  { const int rc = coord_source(ctx, "itsx_trimmed_table", left_prefix, right_prefix, start, stop, nullptr, false, false, cs); if (rc != ITSX_OK) return rc; }
   const int64_t n = ctx->N;
   HIPCHK(t.start.alloc((size_t)n)); HIPCHK(t.stop.alloc((size_t)n));
-  const int32_t *src_start = nullptr, *src_stop = nullptr; int32_t stride = 1;
-  if (by_prefix) {
-    int32_t *rows = nullptr; int64_t nrows = 0;
-    const int rc = coords_device(ctx, left_prefix, right_prefix, true, &rows, &nrows);
-    if (rc != ITSX_OK) return rc;
-    src_start = rows; src_stop = rows + 1; stride = 4;
-  }
   StageTimer tm(st);
-  if (by_prefix) launch_ft_coords(src_start, src_stop, stride, n, t.start.p, t.stop.p, st);
+  if (cs.by_prefix) launch_ft_coords(cs.start, cs.stop, cs.stride, n, t.start.p, t.stop.p, st);
   else { HIPCHK(hipMemcpyAsync(t.start.p, start, (size_t)n * 4, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(t.stop.p, stop, (size_t)n * 4, hipMemcpyHostToDevice, st)); }
   // ---- 1 + 2: the table (a power of two, at least 2 n slots: never more than half full), and the exact verification
   uint64_t tsize = 1024; while (tsize < 2 * (uint64_t)n) tsize <<= 1;
@@ -6355,28 +6394,13 @@ int itsx_write_trimmed_paired_samples(itsx_ctx *ctx, const char *const *out1_pat
     if ((out1_paths[s] == nullptr) != (out2_paths[s] == nullptr)) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_paired_samples: sample " + std::to_string(s) + " has one output path of its two");
   if (compression < 0 || compression > 3) SET_ERR(ctx, ITSX_E_ARG, "compression must be 0 (plain), 1 (gzip), 2 (zstd) or 3 (gzip, deflated on the device)");
   if (compression == 1 && device_deflate_switch()) compression = 3;
-  const bool by_prefix = left_prefix || right_prefix, by_arrays = start || stop || tlen;
-  if (by_prefix == by_arrays || (by_prefix && !(left_prefix && right_prefix)) || (by_arrays && !(start && stop && tlen)))
-    SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_paired_samples: give either left_prefix and right_prefix or start, stop and tlen");
-  if (by_prefix && !ctx->have_final) SET_ERR(ctx, ITSX_E_ARG, "itsx_write_trimmed_paired_samples: prefixes given before itsx_search_finalize");
+  CoordSource cs;
+  { const int rc = coord_source(ctx, "itsx_write_trimmed_paired_samples", left_prefix, right_prefix, start, stop, tlen, true, true, cs); if (rc != ITSX_OK) return rc; }
   if (compression != 3) { itsx_io::PieceCompressor probe(compression); if (!probe.ok()) SET_ERR(ctx, ITSX_E_IO, "zstd output requested but libzstd.so.1 could not be loaded"); }
-  HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->st;
   const int64_t nr = ctx->N, n = pr.n; const int32_t S = ctx->S;
   TrimPairPlanArgs pa{};
-  if (by_prefix) {
-    int32_t *rows = nullptr; int64_t nrows = 0;
-    const int rc = coords_device(ctx, left_prefix, right_prefix, true, &rows, &nrows);
-    if (rc != ITSX_OK) return rc;
-    pa.start = rows; pa.stop = rows + 1; pa.tlen = rows + 2; pa.stride = 4;
-  } else {
-    HIPCHK(ctx->w_tstart.alloc((size_t)nr + 1)); HIPCHK(ctx->w_tstop.alloc((size_t)nr + 1)); HIPCHK(ctx->w_ttlen.alloc((size_t)nr + 1));
-    if (nr > 0) {
-      HIPCHK(hipMemcpyAsync(ctx->w_tstart.p, start, (size_t)nr * 4, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(ctx->w_tstop.p, stop, (size_t)nr * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(ctx->w_ttlen.p, tlen, (size_t)nr * 4, hipMemcpyHostToDevice, st));
-    }
-    pa.start = ctx->w_tstart.p; pa.stop = ctx->w_tstop.p; pa.tlen = ctx->w_ttlen.p; pa.stride = 1;
-  }
+  pa.start = cs.start; pa.stop = cs.stop; pa.tlen = cs.tlen; pa.stride = cs.stride;
   std::vector<int64_t> bounds((size_t)(S + 1) * 3, 0);
   HIPCHK(upload(ctx->w_tfirst, pr.pstart, st));          // sample s is pairs [pstart[s], pstart[s + 1])
   HIPCHK(ctx->w_trec.alloc((size_t)n + 1)); HIPCHK(ctx->w_trec2.alloc((size_t)n + 1)); HIPCHK(ctx->w_tcnt.alloc((size_t)n + 1));
@@ -7223,7 +7247,7 @@ int itsx_debug_huffman_lengths(const uint32_t *freq, int32_t n, int32_t maxbits,
 }
 int itsx_derep_device(itsx_ctx *ctx, const int32_t **d_rep_of, const int32_t **d_uniq_of, const int8_t **d_strand, const int32_t **d_seed_read)
 {
-  CTXCHK(ctx && ctx->have_derep);
+  CTXCHK(ctx && ctx->grouped());
   if (d_rep_of) *d_rep_of = ctx->d_rep_of.p;
   if (d_uniq_of) *d_uniq_of = ctx->d_uniq_of.p;
   if (d_strand) *d_strand = ctx->d_strand.p;
@@ -7232,7 +7256,7 @@ int itsx_derep_device(itsx_ctx *ctx, const int32_t **d_rep_of, const int32_t **d
 }
 int itsx_unique_keys128_device(itsx_ctx *ctx, uint64_t seed_a, uint64_t seed_b, int64_t gidx_base, int64_t **d_tuples, int64_t *n_unique)
 {
-  CTXCHK(ctx && ctx->have_derep && d_tuples);
+  CTXCHK(ctx && ctx->grouped() && d_tuples);
   if (ctx->S > 1) SET_ERR(ctx, ITSX_E_UNSUPPORTED, "cross-rank dereplication of a sample batch is not supported: shard whole samples across ranks");
   HIPCHK(hipSetDevice(ctx->device));
   LoadPriority load_priority(ctx);
@@ -7290,7 +7314,7 @@ static int host_bases(const itsx_ctx *cctx)
 // bases == NULL fills the offsets only
 int itsx_get_unique_seqs(itsx_ctx *ctx, char *bases, int64_t cap, int64_t *offsets)
 {
-  CTXCHK(ctx && offsets && ctx->have_derep);
+  CTXCHK(ctx && offsets && ctx->grouped());
   { const int rc = host_bases(ctx); if (rc != ITSX_OK) return rc; }
   int64_t o = 0;
   for (int32_t u = 0; u < ctx->U; u++) {
@@ -7332,7 +7356,7 @@ static const std::vector<int32_t> &cluster_order(const itsx_ctx *cctx, const its
 
 int itsx_write_uc(const itsx_ctx *ctx, const char *path)
 {
-  CTXCHK(ctx && path && ctx->have_derep);
+  CTXCHK(ctx && path && ctx->grouped());
   const itsx::Clusters c = clusters(ctx);
   std::string err;
   const int rc = itsx::write_uc(path, c, cluster_order(ctx, c), err);
@@ -7342,7 +7366,7 @@ int itsx_write_uc(const itsx_ctx *ctx, const char *path)
 
 int itsx_write_rep_fasta(const itsx_ctx *ctx, const char *path)
 {
-  CTXCHK(ctx && path && ctx->have_derep);
+  CTXCHK(ctx && path && ctx->grouped());
   { const int rc = host_bases(ctx); if (rc != ITSX_OK) return rc; }
   const itsx::Clusters c = clusters(ctx);
   std::string err;
@@ -7353,7 +7377,7 @@ int itsx_write_rep_fasta(const itsx_ctx *ctx, const char *path)
 
 int itsx_write_domtbl(const itsx_ctx *ctx, const char *path)
 {
-  CTXCHK(ctx && path && ctx->have_final);
+  CTXCHK(ctx && path && ctx->finalized());
   { const int rc = fetch_domains(ctx); if (rc != ITSX_OK) return rc; }
   std::vector<int64_t> Zs((size_t)ctx->S, 0);          // hmmsearch's Z: targets searched, per sample
   // (a context narrowed by itsx_set_active_uniques searched only its active targets: the E-value columns of a sharded run are
@@ -7663,7 +7687,7 @@ int64_t itsx_debug_lazy_pairs(itsx_ctx *ctx, itsx_lazy_pair *out, int64_t cap, i
   if (tenths_bias) *tenths_bias = LAZY_TENTHS_BIAS;
   const auto &tu = ctx->topup;
   // the buffers lazy_rounds left (what the top-up round reads): only a lazy search of one chunk still has its whole list in them
-  if (!ctx->have_search || !ctx->lazy || ctx->injected || !tu.list_live || ctx->n_chunks != 1 || ctx->S != 1 || tu.NP <= 0)
+  if (!ctx->searched() || !ctx->lazy || ctx->injected || !tu.list_live || ctx->n_chunks != 1 || ctx->S != 1 || tu.NP <= 0)
     SET_ERR(ctx, ITSX_E_ARG, "itsx_debug_lazy_pairs: the pair list of a lazy search of one chunk and one sample is not in the buffers");
   const int64_t NP = tu.NP;
   if (!out || cap < NP) return NP;
