@@ -506,6 +506,8 @@ int itsx_trimmed_table(itsx_ctx *ctx, const char *left_prefix, const char *right
  * row_off [n_features + 1].  Any pointer may be NULL.  ITSX_E_ARG: no table (none made, or a new read set dropped it). */
 int itsx_trimmed_table_get(itsx_ctx *ctx, int32_t *feat_len, int32_t *feat_total, int32_t *feat_first_read, int64_t *row_off,
                            int32_t *entry_sample, int32_t *entry_count);
+/* the sizes of the table the context holds now (what the getters' arrays must hold); each may be NULL.  ITSX_E_ARG: no table */
+int itsx_trimmed_table_size(itsx_ctx *ctx, int64_t *n_features, int64_t *n_entries, int64_t *n_counted);
 /* feature_of_read [n_reads]: every read's feature (its row of the table), -1 for a read that is not counted */
 int itsx_trimmed_table_reads(itsx_ctx *ctx, int32_t *feature_of_read);
 /* the features' sequences, feature f's at bases[offsets[f], offsets[f + 1]) (no terminators); offsets [n_features + 1].  bases == NULL
@@ -525,6 +527,46 @@ int itsx_write_feature_files(const char *fasta_path, const char *tsv_path, int64
                              const char *bases, const int64_t *offsets, const char *labels, const int64_t *label_offsets,
                              const char *read_names, const int64_t *read_name_offsets, const char *sample_names,
                              const int64_t *sample_name_offsets);
+/* ---- the feature table denoised into ZOTUs (a new call after itsx_trimmed_table; nothing else changes).  What a user does with a
+ * table of distinct sequences: `usearch -unoise3` / `vsearch --cluster_unoise` fold every low-abundance sequence into the abundant one
+ * it is an error copy of; the survivors are the ZOTUs (ASVs).  The reference stops at the trimmed FASTQ: no reference call site.
+ * The rule (the project's own statement, after Edgar's UNOISE2 paper; it does not restate vsearch's k-mer candidate ranking or
+ * maxrejects, and parity with usearch / vsearch is not pinned):
+ *   inputs: the feature table of the last itsx_trimmed_table -- features 0 .. F-1 in table order, totals a_f, sequences s_f;
+ *     max_skew[0 .. D-1], D = n_diffs in 0 .. 31, every value a double in (0, 1), non-increasing: max_skew[d-1] is UNOISE's
+ *     beta(d) = 1 / 2^(alpha*d + 1), tabulated by the caller (device and model never evaluate pow); minsize >= 1.
+ *   Features are processed in table order; the centroid set starts empty.  For feature q:
+ *     d(q, t) is the Levenshtein distance, unit costs, global, of the two sequences as the table holds them: upper case, IUPAC
+ *       symbols compared literally, so N != A.
+ *     Centroid t takes q iff 1 <= d(q, t) <= D and (double)a_q <= max_skew[d-1] * (double)a_t (one IEEE multiply and one compare,
+ *       no FMA).
+ *     If some centroid takes q, q joins the one with the smallest d, ties going to the smallest feature index t:
+ *       zotu_of_feature[q] is that centroid's ZOTU, dist_of_feature[q] = d.
+ *     Else if a_q >= minsize, q becomes a centroid: the next ZOTU, dist 0.
+ *     Else q is unassigned: zotu_of_feature[q] = -1, dist -1; its reads leave the denoised table and are counted in n_dropped_reads.
+ *   ZOTUs are numbered in the order their centroids appear, which is table order.  A ZOTU's row is the sample-wise sum of its members'
+ *   rows, CSR with samples ascending; zotu_total is the sum of the members' totals and need not descend.
+ *   n_diffs == 0 is valid: nothing is taken, every feature with a_q >= minsize is a ZOTU.
+ *   *n_zotus, *n_entries (non-zero cells of the denoised table), *n_dropped_reads, *n_pairs ((feature, centroid) pairs that reached the
+ *   distance kernel), *ms_kernels (device time of the call, by events; itsx_stats does not grow for it): each may be NULL.
+ *   The result stays in the context until the next itsx_denoise_table, the next itsx_trimmed_table or the next call that makes a read set.
+ *   ITSX_E_ARG: no table, n_diffs outside 0 .. 31, a skew outside (0, 1) or above the one before it, minsize < 1.
+ *   Limits: one context (one GPU), whole-file read sets, no chimera step (uchime3_denovo is another step), unassigned reads are dropped,
+ *   not mapped back at 97 %.  Cost: three launches per level of the schedule, at most 1 + ln(largest total) / ln(1 / max_skew[0]) levels and
+ *   never more than n_features: a max_skew[0] close to 1 is answered correctly, but slowly. */
+int itsx_denoise_table(itsx_ctx *ctx, const double *max_skew, int32_t n_diffs, int32_t minsize, int64_t *n_zotus, int64_t *n_entries,
+                       int64_t *n_dropped_reads, int64_t *n_pairs, float *ms_kernels);
+/* the denoised table of the last itsx_denoise_table: zotu_feature (the centroid's feature) / zotu_total [n_zotus]; ZOTU z's cells are
+ * [row_off[z], row_off[z + 1]) of entry_sample / entry_count [n_entries], samples ascending; row_off [n_zotus + 1].  Any pointer may be
+ * NULL.  ITSX_E_ARG: no denoised table. */
+int itsx_denoise_table_get(itsx_ctx *ctx, int32_t *zotu_feature, int32_t *zotu_total, int64_t *row_off, int32_t *entry_sample,
+                           int32_t *entry_count);
+/* zotu_of_feature / dist_of_feature [n_features]; either may be NULL */
+int itsx_denoise_table_features(itsx_ctx *ctx, int32_t *zotu_of_feature, int32_t *dist_of_feature);
+/* how the last call went (for profiles): the levels of its schedule, the (feature, centroid) pairs left out before any distance work
+ * by the skew (dmax == 0) and by the length difference (> dmax), and the target symbols the distance kernel stepped over all its pairs
+ * (a pair stops at the column where its score passes its cut-off); each may be NULL */
+int itsx_denoise_table_info(itsx_ctx *ctx, int64_t *n_levels, int64_t *n_skipped_skew, int64_t *n_skipped_length, int64_t *n_columns);
 /* ---- a merged read set that keeps its ORIGINAL pairs (opt-in; off by default; independent of itsx_keep_records).  While on,
  * itsx_merge_pairs_load and itsx_merge_pairs_load_files also keep, in device memory beside the merged read set, every pair's R1 and
  * R2 record: the bases and qualities as the merge kernel read them (its own upload, taken over instead of freed), both whole title lines ('@' and any comment included, no CR), and per pair the merged read whose

@@ -113,7 +113,8 @@ EXPORTS = ["itsx_abi_version", "itsx_last_error", "itsx_create", "itsx_destroy",
            "itsx_orient_profiles", "itsx_orient_profiles_apply",
            "itsx_twriter_strands", "itsx_write_trimmed_fastq_strands",
            "itsx_set_merge_join", "itsx_merge_join_info", "itsx_merge_buffers_join",
-           "itsx_trimmed_table", "itsx_trimmed_table_get", "itsx_trimmed_table_reads", "itsx_trimmed_table_seqs", "itsx_write_feature_files"]
+           "itsx_trimmed_table", "itsx_trimmed_table_get", "itsx_trimmed_table_reads", "itsx_trimmed_table_seqs", "itsx_write_feature_files",
+           "itsx_denoise_table", "itsx_denoise_table_get", "itsx_denoise_table_features", "itsx_denoise_table_info", "itsx_trimmed_table_size"]
 
 
 def lib():
@@ -183,6 +184,11 @@ def lib():
         "itsx_trimmed_table_get": (i32, [vp, vp, vp, vp, vp, vp, vp]),
         "itsx_trimmed_table_reads": (i32, [vp, vp]),
         "itsx_trimmed_table_seqs": (i32, [vp, vp, vp]),
+        "itsx_trimmed_table_size": (i32, [vp, vp, vp, vp]),
+        "itsx_denoise_table": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+        "itsx_denoise_table_get": (i32, [vp, vp, vp, vp, vp, vp]),
+        "itsx_denoise_table_features": (i32, [vp, vp, vp]),
+        "itsx_denoise_table_info": (i32, [vp, vp, vp, vp, vp]),
         "itsx_write_feature_files": (i32, [cp, cp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "itsx_keep_pair_records": (i32, [vp, i32]),
         "itsx_write_trimmed_paired_samples": (i32, [vp, vp, vp, i32, i32, i32, cp, cp, vp, vp, vp, vp]),

@@ -39,6 +39,34 @@ from .SeqSample import _REGION_PREFIX, _domtbl_ali_wanted, _fast_from_env, _keep
 from .definitions import maxmismatches
 
 
+def write_denoised_files(fasta, tsv, n_samples, totals, zotu_feature, row_off, entry_sample, entry_count, sequences, labels, sample_names):
+    """The two files of a denoised table from its arrays, through the host formatter itsx_write_feature_files (no device): the ZOTUs'
+    bases and offsets are compacted here, `size=` is the ZOTU's total.  Either path may be None."""
+    from . import _lib
+    import ctypes as C
+    sample_names = [str(x) for x in sample_names]
+    if len(sample_names) != n_samples:
+        raise ValueError("write_denoised_table: %d sample names for %d sample(s)" % (len(sample_names), n_samples))
+
+    def blob_of(names):
+        enc = [x.encode() for x in names]
+        return b"".join(enc), np.concatenate([[0], np.cumsum([len(x) for x in enc])]).astype(np.int64)
+    bases, seq_off = blob_of(sequences)
+    lab, lab_off = blob_of(labels)
+    sn, sn_off = blob_of(sample_names)
+    arr = lambda x, dt: np.ascontiguousarray(x, dt)
+    totals, zotu_feature, row_off = arr(totals, np.int32), arr(zotu_feature, np.int32), arr(row_off, np.int64)
+    entry_sample, entry_count = arr(entry_sample, np.int32), arr(entry_count, np.int32)
+    pad = lambda x: x.ctypes.data if x.size else None
+    L = _lib.lib()
+    rc = L.itsx_write_feature_files(None if fasta is None else os.fsencode(fasta), None if tsv is None else os.fsencode(tsv),
+                                    int(totals.shape[0]), int(n_samples), pad(totals), pad(zotu_feature), row_off.ctypes.data,
+                                    pad(entry_sample), pad(entry_count), C.c_char_p(bases), seq_off.ctypes.data,
+                                    C.c_char_p(lab), lab_off.ctypes.data, None, None, C.c_char_p(sn), sn_off.ctypes.data)
+    if rc != 0:
+        raise EngineError(rc, L.itsx_writers_last_error().decode())
+
+
 class SampleBatch:
     """Runs `deduplicate()` and `_search()` of many SeqSample objects as one engine pass.
 
@@ -454,6 +482,30 @@ class SampleBatch:
                                         C.c_char_p(lab), lab_off.ctypes.data, None, None, C.c_char_p(sn), sn_off.ctypes.data)
         if rc != 0:
             raise EngineError(rc, L.itsx_writers_last_error().decode())
+        return t
+
+    # -- the feature table denoised into ZOTUs ---------------------------------------------------
+    def denoise_features(self, region: str, alpha: float = 2.0, minsize: int = 8, min_len: int = 1, ids: str = "sha1"):
+        """feature_table(region) denoised by the UNOISE rule (Engine.denoise_table): what `usearch -unoise3` / `vsearch --cluster_unoise`
+        make of the dereplicated trimmed regions, as the project states the rule (parity with either is not pinned; no chimera step;
+        unassigned reads are dropped, not mapped back).  Returns the engine's DenoisedTable with `sequences` and `labels` of the
+        centroids added (ids as in feature_table) and `features`, the table it was made of."""
+        ft = self.feature_table(region, min_len=min_len, ids=ids)
+        t = self.engine.denoise_table(alpha=alpha, minsize=minsize)
+        t.features = ft
+        t.sequences = [ft.sequences[int(f)] for f in t.zotu_feature]
+        t.labels = [ft.labels[int(f)] for f in t.zotu_feature]
+        return t
+
+    def write_denoised_table(self, fasta: Optional[str], tsv: Optional[str], region: str, alpha: float = 2.0, minsize: int = 8,
+                             min_len: int = 1, ids: str = "sha1", sample_names: Optional[Sequence[str]] = None):
+        """denoise_features(region) written as the two files write_feature_table writes, one record per ZOTU: `>label;size=total` with
+        the ZOTU's total and the centroid's sequence, and the TSV of the ZOTUs' counts.  Returns the table."""
+        t = self.denoise_features(region, alpha=alpha, minsize=minsize, min_len=min_len, ids=ids)
+        if sample_names is None:
+            sample_names = [os.path.basename(getattr(s, "fastq", None) or getattr(s, "r1", None) or s.seq_file) for s in self.samples]
+        write_denoised_files(fasta, tsv, t.n_samples, t.totals, t.zotu_feature, t.row_off, t.entry_sample, t.entry_count, t.sequences, t.labels,
+                             sample_names)
         return t
 
     def write_paired_trimmed(self, outfiles1: Sequence[str], outfiles2: Sequence[str], region: str, gzipped: bool = False,

@@ -408,7 +408,7 @@ struct itsx_ctx {
       topup.valid = topup.list_live = false; injected = domz_on_device = domz_exchanged = false; lazy_pending = 0; lazy_pending_prof.clear();
     }
     if (s < ST_GROUPED) { clustered = false; drop_cigars(); order_cache_ok = false; h_usample.clear(); active_narrowed = false; }
-    if (s < ST_READS) { rec.drop(); prec.drop(); ft.have = false; }
+    if (s < ST_READS) { rec.drop(); prec.drop(); ft.have = false; dn.have = false; }
     if (stage > s) stage = s;
   }
 
@@ -559,12 +559,20 @@ struct itsx_ctx {
   // ---- the feature table of the trimmed regions (itsx_trimmed_table; k_ftable.hip): the last call's table in its order, kept until the next
   // call or the next read set (the sequences were cut from this read set's words); the rest is that call's scratch
   struct FeatureTable {
-    bool have = false; int64_t n = 0, nc = 0; int32_t F = 0, E = 0; int64_t text_bytes = 0;
+    bool have = false; int64_t n = 0, nc = 0; int32_t F = 0, E = 0, S = 1; int64_t text_bytes = 0;   // (S: the samples its cells were counted over)
     DBuf<int32_t> feat_len, feat_total, feat_first, row_off, entry_sample, entry_count, feature_of_read; DBuf<uint32_t> text; std::vector<int64_t> h_seq_off;
     DBuf<int32_t> start, stop, vals, feature_read, ehead, epos, fhead, fpos, ent_start, ent_sample, ent_feat, f_ent0, f_pos0, f_first, hold_f, ovals, ovals2,
         rank_of, nent, scan;
     DBuf<unsigned long long> keys, counters, pair_keys, pair_sorted, okeys, okeys2; DBuf<uint64_t> hash; DBuf<uint32_t> slot_of; DBuf<int64_t> seq_off; DBuf<uint8_t> sort_tmp;
   } ft;
+  // ---- the table above denoised into ZOTUs (itsx_denoise_table; k_denoise.hip): the last call's result, beside the table it was made of --
+  // whatever drops ft drops it, and so does the next itsx_trimmed_table or itsx_denoise_table; the rest is that call's scratch
+  struct Denoised {
+    bool have = false; int32_t F = 0, Z = 0, E = 0; int64_t dropped = 0, pairs = 0, skip_skew = 0, skip_len = 0, columns = 0; int32_t levels = 0;
+    DBuf<int32_t> cent, zotu_of, dist_of, z_row_off, z_total, z_entry_sample, z_entry_count;
+    DBuf<int32_t> lv, nlev, ncent, flag, pos, vals, vals2, head, hpos, csum, run_start, scan; DBuf<double> skew;
+    DBuf<unsigned long long> keys, keys2, counters; DBuf<uint8_t> sort_tmp;
+  } dn;
   DBuf<DeflateBlock> w_dblk; DBuf<uint32_t> w_dtok, w_dtext; DBuf<uint8_t> w_dslots, w_dpacked; DBuf<int32_t> w_dsizes; DBuf<int64_t> w_ddst;   // deflate_ranges
   // a streamed writer's device path (twdev_*, for itsx_twriter_set_device): a unit's raw text, its line index and the plan's scratch
   // (records, output text and deflate scratch are the batch writers' buffers above); tw_mu serialises the writers that share the context
@@ -5196,7 +5204,7 @@ static int orient_apply_strands(itsx_ctx *ctx, const std::vector<int8_t> &hs, DB
   if (S > 1) ctx->h_sample.swap(smp);
   ctx->h_bases.swap(text); ctx->bases_view = ctx->h_bases.data();
   ctx->prec.drop();                                      // the pairs' map named the reads that were
-  ctx->ft.have = false;
+  ctx->ft.have = false; ctx->dn.have = false;
   if (records) {
     itsx_ctx::Records &rr = ctx->rec;
     dbuf_swap(rr.seq, r_seq); dbuf_swap(rr.qual, r_qual); dbuf_swap(rr.titles, r_titles); dbuf_swap(rr.off, r_off); dbuf_swap(rr.toff, r_toff);
@@ -6252,7 +6260,7 @@ int itsx_trimmed_table(itsx_ctx *ctx, const char *left_prefix, const char *right
   if (!ctx->rd.woff || ctx->N <= 0) SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table called before a read set is loaded");
   hipStream_t st = ctx->st;
   itsx_ctx::FeatureTable &t = ctx->ft;
-  t.have = false;
+  t.have = false; ctx->dn.have = false;
   CoordSource cs;                                          // (the arrays go straight into the table's own buffers, below)
   { const int rc = coord_source(ctx, "itsx_trimmed_table", left_prefix, right_prefix, start, stop, nullptr, false, false, cs); if (rc != ITSX_OK) return rc; }
   const int64_t n = ctx->N;
@@ -6331,7 +6339,7 @@ int itsx_trimmed_table(itsx_ctx *ctx, const char *left_prefix, const char *right
   const float ms = tm.stop();
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipGetLastError());
-  t.have = true; t.n = n; t.nc = nc; t.F = F; t.E = E;
+  t.have = true; t.n = n; t.nc = nc; t.F = F; t.E = E; t.S = ctx->S;
   if (n_features) *n_features = F;
   if (n_entries) *n_entries = E;
   if (n_counted) *n_counted = nc;
@@ -6357,6 +6365,16 @@ int itsx_trimmed_table_get(itsx_ctx *ctx, int32_t *feat_len, int32_t *feat_total
   if (row_off) for (size_t g = 0; g <= F; g++) row_off[g] = ro[g];
   return ITSX_OK;
 }
+int itsx_trimmed_table_size(itsx_ctx *ctx, int64_t *n_features, int64_t *n_entries, int64_t *n_counted)
+{
+  CTXCHK(ctx);
+  itsx_ctx::FeatureTable &t = ctx->ft;
+  if (!t.have) SET_ERR(ctx, ITSX_E_ARG, "itsx_trimmed_table_size: no table (call itsx_trimmed_table; a new read set drops it)");
+  if (n_features) *n_features = t.F;
+  if (n_entries) *n_entries = t.E;
+  if (n_counted) *n_counted = t.nc;
+  return ITSX_OK;
+}
 int itsx_trimmed_table_reads(itsx_ctx *ctx, int32_t *feature_of_read)
 {
   CTXCHK(ctx && feature_of_read);
@@ -6376,6 +6394,136 @@ int itsx_trimmed_table_seqs(itsx_ctx *ctx, char *bases, int64_t *offsets)
   if (!bases) return ITSX_OK;
   HIPCHK(hipSetDevice(ctx->device));
   return fetch_staged(ctx, reinterpret_cast<const uint8_t *>(t.text.p), t.text_bytes, bases);
+}
+// ------------------------------------------------------------------------------ the feature table denoised into ZOTUs (k_denoise.hip)
+// The UNOISE rule (include/itsx_hip.h) on the table the last itsx_trimmed_table left in ctx->ft, level by level: per level the distance
+// kernel, a scan of the new centroids and their append -- no host round trip between the levels -- then the collapse of the cells.
+int itsx_denoise_table(itsx_ctx *ctx, const double *max_skew, int32_t n_diffs, int32_t minsize, int64_t *n_zotus, int64_t *n_entries,
+                       int64_t *n_dropped_reads, int64_t *n_pairs, float *ms_kernels)
+{
+  CTXCHK(ctx);
+  itsx_ctx::FeatureTable &t = ctx->ft;
+  itsx_ctx::Denoised &d = ctx->dn;
+  d.have = false;
+  if (!t.have) SET_ERR(ctx, ITSX_E_ARG, "itsx_denoise_table: no table (call itsx_trimmed_table; a new read set drops it)");
+  if (n_diffs < 0 || n_diffs > DN_MAX_DIFFS) SET_ERR(ctx, ITSX_E_ARG, "itsx_denoise_table: n_diffs must be 0 .. 31, not " + std::to_string(n_diffs));
+  if (n_diffs > 0 && !max_skew) SET_ERR(ctx, ITSX_E_ARG, "itsx_denoise_table: n_diffs > 0 without max_skew");
+  if (minsize < 1) SET_ERR(ctx, ITSX_E_ARG, "itsx_denoise_table: minsize must be at least 1, not " + std::to_string(minsize));
+  std::vector<double> skew(32, 0.0);
+  for (int32_t i = 0; i < n_diffs; i++) {
+    if (!(max_skew[i] > 0.0 && max_skew[i] < 1.0)) SET_ERR(ctx, ITSX_E_ARG, "itsx_denoise_table: max_skew[" + std::to_string(i) + "] is not inside (0, 1)");
+    if (i > 0 && max_skew[i] > max_skew[i - 1]) SET_ERR(ctx, ITSX_E_ARG, "itsx_denoise_table: max_skew[" + std::to_string(i) + "] is above the entry before it");
+    skew[(size_t)i] = max_skew[i];
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  const int32_t F = t.F, E = t.E;
+  int sbits = 0; while (((int64_t)1 << sbits) < (int64_t)t.S) sbits++;
+  HIPCHK(upload(d.skew, skew, st));
+  HIPCHK(d.lv.alloc((size_t)F + 1)); HIPCHK(d.nlev.alloc(1)); HIPCHK(d.ncent.alloc((size_t)F + 2)); HIPCHK(d.cent.alloc((size_t)F + 1));
+  HIPCHK(d.zotu_of.alloc((size_t)F + 1)); HIPCHK(d.dist_of.alloc((size_t)F + 1)); HIPCHK(d.flag.alloc((size_t)F + 1)); HIPCHK(d.pos.alloc((size_t)F + 1));
+  HIPCHK(d.counters.alloc(DN_COUNTERS)); HIPCHK(d.scan.alloc((size_t)scan_tmp_elems(std::max<int64_t>(F, E) + 1)));
+  HIPCHK(d.keys.alloc((size_t)E + 1)); HIPCHK(d.keys2.alloc((size_t)E + 1)); HIPCHK(d.vals.alloc((size_t)E + 1)); HIPCHK(d.vals2.alloc((size_t)E + 1));
+  HIPCHK(d.head.alloc((size_t)E + 1)); HIPCHK(d.hpos.alloc((size_t)E + 1)); HIPCHK(d.csum.alloc((size_t)E + 1)); HIPCHK(d.run_start.alloc((size_t)E + 1));
+  HIPCHK(d.z_row_off.alloc((size_t)F + 1)); HIPCHK(d.z_total.alloc((size_t)F + 1)); HIPCHK(d.z_entry_sample.alloc((size_t)E + 1)); HIPCHK(d.z_entry_count.alloc((size_t)E + 1));
+  const size_t sort_bytes = ft_sort_bytes(std::max<int64_t>(E, 1));
+  HIPCHK(d.sort_tmp.alloc(sort_bytes));
+  StageTimer tm(st);
+  HIPCHK(hipMemsetAsync(d.counters.p, 0, DN_COUNTERS * 8, st));
+  DnArgs a{};
+  a.F = F; a.feat_total = t.feat_total.p; a.feat_len = t.feat_len.p; a.seq_off = t.seq_off.p; a.text = t.text.p;
+  a.row_off = t.row_off.p; a.entry_sample = t.entry_sample.p; a.entry_count = t.entry_count.p; a.E = E; a.sbits = sbits;
+  a.max_skew = d.skew.p; a.D = n_diffs; a.minsize = minsize;
+  a.lv = d.lv.p; a.nlev = d.nlev.p; a.cent = d.cent.p; a.ncent = d.ncent.p; a.zotu_of = d.zotu_of.p; a.dist_of = d.dist_of.p;
+  a.flag = d.flag.p; a.pos = d.pos.p; a.counters = d.counters.p;
+  a.keys = d.keys.p; a.keys_sorted = d.keys2.p; a.vals = d.vals.p; a.vals_sorted = d.vals2.p; a.head = d.head.p; a.hpos = d.hpos.p; a.csum = d.csum.p; a.run_start = d.run_start.p;
+  a.z_row_off = d.z_row_off.p; a.z_total = d.z_total.p; a.z_entry_sample = d.z_entry_sample.p; a.z_entry_count = d.z_entry_count.p;
+  // ---- the levels (their number is at most F; with UNOISE's skews about one per factor 8 of abundance)
+  launch_dn_levels(a, st);
+  HIPCHK(hipGetLastError());
+  int32_t nlev = 0;
+  HIPCHK(hipMemcpyAsync(&nlev, d.nlev.p, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::vector<int32_t> lv((size_t)nlev + 1, 0);
+  HIPCHK(hipMemcpyAsync(lv.data(), d.lv.p, ((size_t)nlev + 1) * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int32_t l = 0; l < nlev; l++) {
+    const int32_t f0 = lv[(size_t)l], f1 = lv[(size_t)l + 1];
+    launch_dn_distance(a, l, f0, f1, st);
+    launch_exclusive_scan(d.flag.p, d.pos.p, (int64_t)(f1 - f0) + 1, d.scan.p, st);
+    launch_dn_append(a, l, f0, f1, st);
+  }
+  HIPCHK(hipGetLastError());
+  int32_t Z = 0;
+  HIPCHK(hipMemcpyAsync(&Z, d.ncent.p + nlev, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // ---- the collapse: a ZOTU's row is the sample-wise sum of its members' rows
+  a.Z = Z;
+  launch_dn_keys(a, st);
+  if (ft_sort_pairs(d.sort_tmp.p, sort_bytes, d.keys.p, d.keys2.p, d.vals.p, d.vals2.p, E, st) != 0) SET_ERR(ctx, ITSX_E_DEVICE, "itsx_denoise_table: the cell sort failed");
+  launch_dn_heads(a, st);
+  launch_exclusive_scan(d.head.p, d.hpos.p, (int64_t)E + 1, d.scan.p, st);
+  launch_exclusive_scan(d.vals2.p, d.csum.p, (int64_t)E + 1, d.scan.p, st);
+  launch_dn_runs(a, st);
+  launch_dn_rows(a, st);
+  HIPCHK(hipGetLastError());
+  int32_t Ez = 0; unsigned long long hc[DN_COUNTERS] = {0, 0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(&Ez, d.hpos.p + E, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(hc, d.counters.p, DN_COUNTERS * 8, hipMemcpyDeviceToHost, st));
+  const float ms = tm.stop();
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  d.F = F; d.Z = Z; d.E = Ez; d.levels = nlev;
+  d.pairs = (int64_t)hc[DN_C_PAIRS]; d.skip_skew = (int64_t)hc[DN_C_SKIP_SKEW]; d.skip_len = (int64_t)hc[DN_C_SKIP_LEN]; d.dropped = (int64_t)hc[DN_C_DROPPED]; d.columns = (int64_t)hc[DN_C_COLUMNS];
+  d.have = true;
+  if (n_zotus) *n_zotus = Z;
+  if (n_entries) *n_entries = Ez;
+  if (n_dropped_reads) *n_dropped_reads = d.dropped;
+  if (n_pairs) *n_pairs = d.pairs;
+  if (ms_kernels) *ms_kernels = ms;
+  return ITSX_OK;
+}
+int itsx_denoise_table_get(itsx_ctx *ctx, int32_t *zotu_feature, int32_t *zotu_total, int64_t *row_off, int32_t *entry_sample, int32_t *entry_count)
+{
+  CTXCHK(ctx);
+  itsx_ctx::Denoised &d = ctx->dn;
+  if (!d.have) SET_ERR(ctx, ITSX_E_ARG, "itsx_denoise_table_get: no denoised table (call itsx_denoise_table; a new table or read set drops it)");
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  const size_t Z = (size_t)d.Z, E = (size_t)d.E;
+  std::vector<int32_t> ro(Z + 1, 0);
+  if (Z && zotu_feature) HIPCHK(hipMemcpyAsync(zotu_feature, d.cent.p, Z * 4, hipMemcpyDeviceToHost, st));
+  if (Z && zotu_total) HIPCHK(hipMemcpyAsync(zotu_total, d.z_total.p, Z * 4, hipMemcpyDeviceToHost, st));
+  if (Z && row_off) HIPCHK(hipMemcpyAsync(ro.data(), d.z_row_off.p, (Z + 1) * 4, hipMemcpyDeviceToHost, st));
+  if (E && entry_sample) HIPCHK(hipMemcpyAsync(entry_sample, d.z_entry_sample.p, E * 4, hipMemcpyDeviceToHost, st));
+  if (E && entry_count) HIPCHK(hipMemcpyAsync(entry_count, d.z_entry_count.p, E * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (row_off) for (size_t z = 0; z <= Z; z++) row_off[z] = ro[z];
+  return ITSX_OK;
+}
+int itsx_denoise_table_features(itsx_ctx *ctx, int32_t *zotu_of_feature, int32_t *dist_of_feature)
+{
+  CTXCHK(ctx);
+  itsx_ctx::Denoised &d = ctx->dn;
+  if (!d.have) SET_ERR(ctx, ITSX_E_ARG, "itsx_denoise_table_features: no denoised table (call itsx_denoise_table; a new table or read set drops it)");
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->st;
+  const size_t F = (size_t)d.F;
+  if (F && zotu_of_feature) HIPCHK(hipMemcpyAsync(zotu_of_feature, d.zotu_of.p, F * 4, hipMemcpyDeviceToHost, st));
+  if (F && dist_of_feature) HIPCHK(hipMemcpyAsync(dist_of_feature, d.dist_of.p, F * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return ITSX_OK;
+}
+int itsx_denoise_table_info(itsx_ctx *ctx, int64_t *n_levels, int64_t *n_skipped_skew, int64_t *n_skipped_length, int64_t *n_columns)
+{
+  CTXCHK(ctx);
+  itsx_ctx::Denoised &d = ctx->dn;
+  if (!d.have) SET_ERR(ctx, ITSX_E_ARG, "itsx_denoise_table_info: no denoised table (call itsx_denoise_table; a new table or read set drops it)");
+  if (n_levels) *n_levels = d.levels;
+  if (n_skipped_skew) *n_skipped_skew = d.skip_skew;
+  if (n_skipped_length) *n_skipped_length = d.skip_len;
+  if (n_columns) *n_columns = d.columns;
+  return ITSX_OK;
 }
 // f1 for a batch of PAIRED samples: Dedup.create_paired_trimmed_seqs (SeqSample.py:564-790) of every sample in one call, from the pair
 // records the context keeps (itsx_keep_pair_records).  One plan for both sides; then per side the copy kernel with that side's planes and

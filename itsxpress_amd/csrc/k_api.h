@@ -321,6 +321,36 @@ size_t ft_sort_bytes(int64_t n);            // scratch for either sort below
 int ft_sort_keys(void *tmp, size_t bytes, const unsigned long long *kin, unsigned long long *kout, int64_t n, int end_bit, hipStream_t st);
 int ft_sort_pairs(void *tmp, size_t bytes, const unsigned long long *kin, unsigned long long *kout, const int32_t *vin, int32_t *vout, int64_t n, hipStream_t st);
 
+// ---- k_denoise.hip (the feature table denoised into ZOTUs by the UNOISE rule: itsx_denoise_table)
+// Features are processed level by level (a level: the features whose total is above max_skew[0] times its first feature's; none of
+// them can take another).  Per level: the distance kernel decides every feature against the centroids of the earlier levels, a scan
+// numbers the new centroids, the append puts them behind the others.  Then the collapse sums the members' cells per ZOTU.
+constexpr int DN_MAX_DIFFS = 31;           // the skew table's entries at most: the band 2 * 31 + 1 fits one 64-bit word
+constexpr int DN_NONE = -1;                 // zotu_of / dist_of: neither taken nor a centroid
+enum { DN_C_PAIRS = 0, DN_C_SKIP_SKEW = 1, DN_C_SKIP_LEN = 2, DN_C_DROPPED = 3, DN_C_COLUMNS = 4, DN_COUNTERS = 5 };   // (columns: target symbols stepped)
+struct DnArgs {
+  // the feature table (k_ftable.hip), in its order
+  int32_t F; const int32_t *feat_total, *feat_len; const int64_t *seq_off; const uint32_t *text;
+  const int32_t *row_off, *entry_sample, *entry_count; int32_t E; int sbits;
+  const double *max_skew; int32_t D, minsize;  // [32] on the device (the entries past D: 0)
+  int32_t *lv, *nlev;                       // [F + 1] level starts (lv[*nlev] = F); the number of levels
+  int32_t *cent, *ncent;                    // [F] the centroids in table order; [levels + 1] how many stand before each level
+  int32_t *zotu_of, *dist_of;               // [F]
+  int32_t *flag, *pos;                      // [level size + 1] the level's new centroids and their exclusive scan
+  unsigned long long *counters;             // [DN_COUNTERS]
+  // the collapse: (zotu << sbits | sample, count) per cell of an assigned feature (~0 otherwise), sorted; run heads and their scan
+  unsigned long long *keys; const unsigned long long *keys_sorted; int32_t *vals, *vals_sorted, *head, *hpos;   // [E + 1]
+  int32_t *csum, *run_start;                // [E + 1] exclusive scan of the sorted counts; the first cell of every run
+  int32_t Z; int32_t *z_row_off, *z_total, *z_entry_sample, *z_entry_count;   // [Z + 1], [Z], [E]
+};
+void launch_dn_levels(const DnArgs &a, hipStream_t st);
+void launch_dn_distance(const DnArgs &a, int32_t level, int32_t f0, int32_t f1, hipStream_t st);
+void launch_dn_append(const DnArgs &a, int32_t level, int32_t f0, int32_t f1, hipStream_t st);
+void launch_dn_keys(const DnArgs &a, hipStream_t st);
+void launch_dn_heads(const DnArgs &a, hipStream_t st);
+void launch_dn_runs(const DnArgs &a, hipStream_t st);
+void launch_dn_rows(const DnArgs &a, hipStream_t st);
+
 // ---- k_deflate.hip (the batch writers' gzip output made on the device: one gzip member per block of text)
 constexpr int DEFLATE_BLOCK_BYTES = 65535;      // text of one member at most: what ONE stored block holds, so a member never costs more than len + 5 + 18
 constexpr int DEFLATE_SLOT_BYTES = 65600;       // where a member is built: its stored form (text + 5 + 18) after 2 bytes of lead, whole dwords

@@ -76,6 +76,49 @@ class FeatureTable:
         return out
 
 
+class DenoisedTable:
+    """What Engine.denoise_table returns: the feature table denoised into ZOTUs by the UNOISE rule, ZOTUs in the order of their
+    centroids (table order).  zotu_feature (the centroid's feature), totals: per ZOTU; the cells as CSR rows -- ZOTU z's are
+    [row_off[z], row_off[z + 1]) of entry_sample / entry_count, samples ascending; zotu_of_feature (-1: unassigned) and dist_of_feature
+    (0: a centroid, -1: unassigned): per feature; n_dropped_reads: the unassigned features' reads; n_pairs: the (feature, centroid) pairs
+    that reached the distance kernel; n_levels, n_skipped_skew, n_skipped_length: the schedule's levels and the pairs left out before
+    any distance work; n_columns: the target symbols the kernel stepped; max_skew: the skew table used; ms_kernels: the device time of the call."""
+    n_samples = 1
+    n_dropped_reads = 0
+    n_pairs = 0
+    ms_kernels = 0.0
+
+    @property
+    def n_zotus(self):
+        return int(self.totals.shape[0])
+
+    def dense(self):
+        """the denoised table as an [n_zotus, n_samples] int64 array"""
+        out = np.zeros((self.n_zotus, self.n_samples), np.int64)
+        rows = np.repeat(np.arange(self.n_zotus), np.diff(self.row_off))
+        out[rows, self.entry_sample] = self.entry_count
+        return out
+
+
+def unoise_skews(alpha=2.0, max_total=None, max_diffs=None):
+    """UNOISE's skew limits as the table itsx_denoise_table takes: max_skew[d - 1] = 2.0 ** -(alpha * d + 1) for d = 1, 2, ...  The
+    table stops at the smaller of max_diffs (default 31) and the last d with max_skew * max_total >= 1 (max_total: the largest feature
+    total; None: no such stop): no later d can accept anything, since every feature holds at least one read."""
+    alpha = float(alpha)
+    if not alpha > 0:
+        raise ValueError("unoise_skews: alpha must be above 0")
+    top = 31 if max_diffs is None else int(max_diffs)
+    if not 0 <= top <= 31:
+        raise ValueError("unoise_skews: max_diffs is 0 .. 31")
+    out = []
+    for d in range(1, top + 1):
+        v = 2.0 ** -(alpha * d + 1)
+        if v <= 0.0 or (max_total is not None and not v * float(max_total) >= 1.0):
+            break
+        out.append(v)
+    return np.asarray(out, np.float64)
+
+
 class Engine:
     def __init__(self, device=None):
         self.L = _lib.lib()
@@ -895,6 +938,43 @@ class Engine:
         buf = C.create_string_buffer(int(t.seq_off[-1]) + 1)
         self._chk(self.L.itsx_trimmed_table_seqs(self.h, buf, None))
         t.bases = buf.raw[:int(t.seq_off[-1])]
+        return t
+
+    # ---- the feature table denoised into ZOTUs (the UNOISE rule)
+    def denoise_table(self, alpha=2.0, minsize=8, max_diffs=None, max_skew=None):
+        """The table of the last trimmed_table denoised (itsx_denoise_table): a DenoisedTable.  Features in table order; centroid t
+        takes feature q iff 1 <= d <= D (Levenshtein, symbols compared literally) and a_q <= max_skew[d - 1] * a_t; q joins the taker
+        with the smallest d, then the smallest t; an untaken q with a_q >= minsize is the next ZOTU, any other is unassigned and its
+        reads are dropped.  max_skew: unoise_skews(alpha, largest total, max_diffs) unless given (non-increasing values inside (0, 1),
+        at most 31).  The project's own statement of the rule: parity with usearch / vsearch is not pinned; no chimera step; one GPU,
+        whole-file read sets."""
+        nf = C.c_int64(0)
+        self._chk(self.L.itsx_trimmed_table_size(self.h, C.byref(nf), None, None))      # (the context's own F sizes the arrays below)
+        F = int(nf.value)
+        totals = np.zeros(max(F, 1), np.int32)
+        self._chk(self.L.itsx_trimmed_table_get(self.h, None, totals.ctypes.data if F else None, None, None, None, None))
+        if max_skew is None:
+            max_skew = unoise_skews(alpha, int(totals[0]) if F else 0, max_diffs)
+        skew = np.ascontiguousarray(max_skew, np.float64)
+        buf = skew if skew.size else np.zeros(1, np.float64)
+        nz, ne, nd, npairs, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_float(0)
+        self._chk(self.L.itsx_denoise_table(self.h, buf.ctypes.data, int(skew.size), int(minsize), C.byref(nz), C.byref(ne), C.byref(nd),
+                                            C.byref(npairs), C.byref(ms)))
+        Z, E = int(nz.value), int(ne.value)
+        t = DenoisedTable()
+        t.n_samples = int(self.L.itsx_num_samples(self.h))
+        t.n_dropped_reads, t.n_pairs, t.ms_kernels, t.max_skew = int(nd.value), int(npairs.value), float(ms.value), skew
+        t.zotu_feature, t.totals = np.zeros(Z, np.int32), np.zeros(Z, np.int32)
+        t.row_off = np.zeros(Z + 1, np.int64)
+        t.entry_sample, t.entry_count = np.zeros(E, np.int32), np.zeros(E, np.int32)
+        t.zotu_of_feature, t.dist_of_feature = np.zeros(F, np.int32), np.zeros(F, np.int32)
+        pad = lambda x: x.ctypes.data if x.size else None
+        self._chk(self.L.itsx_denoise_table_get(self.h, pad(t.zotu_feature), pad(t.totals), t.row_off.ctypes.data, pad(t.entry_sample),
+                                                pad(t.entry_count)))
+        self._chk(self.L.itsx_denoise_table_features(self.h, pad(t.zotu_of_feature), pad(t.dist_of_feature)))
+        nl, sk, sl, co = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.itsx_denoise_table_info(self.h, C.byref(nl), C.byref(sk), C.byref(sl), C.byref(co)))
+        t.n_levels, t.n_skipped_skew, t.n_skipped_length, t.n_columns = int(nl.value), int(sk.value), int(sl.value), int(co.value)
         return t
 
     # ---- f1 for a batch of paired samples: trimmed R1 / R2 FASTQ from the pair records the context keeps

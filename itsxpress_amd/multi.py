@@ -1073,6 +1073,10 @@ class MultiEngine(ShardedOps):
         raise EngineError(-5, "the feature table of the trimmed regions (trimmed_table) does not shard over GPUs: run it with ITSXPRESS_GPUS=1 "
                               "(DESIGN.md section 8)")
 
+    def denoise_table(self, alpha=2.0, minsize=8, max_diffs=None, max_skew=None):
+        raise EngineError(-5, "denoising the feature table (denoise_table) does not shard over GPUs: run it with ITSXPRESS_GPUS=1 "
+                              "(DESIGN.md section 8)")
+
     def _merge(self, r1, r2, out, maxdiffs, maxee, allow_stagger):
         for p in (r1, r2):
             if not os.path.exists(p):

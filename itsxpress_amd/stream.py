@@ -1065,5 +1065,9 @@ class StreamEngine(ShardedOps):
         raise EngineError(-5, "the feature table of the trimmed regions (trimmed_table) counts a whole-file read set and is not streamed: "
                               "run it without ITSXPRESS_STREAM (DESIGN.md section 8)")
 
+    def denoise_table(self, alpha=2.0, minsize=8, max_diffs=None, max_skew=None):
+        raise EngineError(-5, "denoising the feature table (denoise_table) needs the table of a whole-file read set and is not streamed: "
+                              "run it without ITSXPRESS_STREAM (DESIGN.md section 8)")
+
     def merge_pairs_files(self, r1, r2, out, maxdiffs=40, maxee=2.0, allow_stagger=False):
         return self._plain().merge_pairs_files(r1, r2, out, maxdiffs=maxdiffs, maxee=maxee, allow_stagger=allow_stagger)
